@@ -792,7 +792,15 @@ def main():
                          "that rounds 3-5 ran (no rev_cites / rev_affiliated_with, 35.8 M edges) for round-to-round comparison")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline pass computed in its LAST timed step as DIR/<name>.npy "
+                         "(rank 0): a fixed sample of the output logits, the per-hop sizes and a fixed sample of the node list "
+                         "of every call group of that step (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload == "mag":
+        ap.error("--dump-outputs is implemented for the SAGE workloads (products, papers100m, rmat26), not for mag")
     relaunch_if_needed(args)
     if args.workload == "mag":
         import bench_mag
@@ -965,8 +973,9 @@ def main():
     host_prof = {"sample_enqueue": 0.0, "forward_enqueue": 0.0, "wait_for_walk": 0.0, "groups": 0}
     last_per_rank = []
 
-    def run_groups(pipe, first, last, timers=None, sizes=None, mode="split"):
-        """software pipeline: walk(g+1) is enqueued before forward(g) waits for the sizes of g"""
+    def run_groups(pipe, first, last, timers=None, sizes=None, mode="split", capture=None):
+        """software pipeline: walk(g+1) is enqueued before forward(g) waits for the sizes of g.  capture(k, res, h, sz) is
+        called for the k-th call group of the last step (g >= last - gps), right behind that group's forward on its stream"""
         pipe.mode = mode
         pending = pipe.sample(batches[first % distinct], first)
         for g in range(first, last):
@@ -974,7 +983,9 @@ def main():
             nxt = pipe.sample(batches[(g + 1) % distinct], g + 1) if g + 1 < last else None
             t1 = time.perf_counter()
             w0 = pipe.host_wait_s
-            _, sz = pipe.forward(*pending, timers=timers, mode=mode)
+            h, sz = pipe.forward(*pending, timers=timers, mode=mode)
+            if capture is not None and g >= last - gps:
+                capture(g - (last - gps), pending[0], h, sz)
             host_prof["sample_enqueue"] += t1 - t0
             host_prof["forward_enqueue"] += time.perf_counter() - t1 - (pipe.host_wait_s - w0)
             host_prof["wait_for_walk"] += pipe.host_wait_s - w0
@@ -985,13 +996,13 @@ def main():
                 pipe.prefetch(nxt)
             pending = nxt
 
-    def measure(pipe, mode):
+    def measure(pipe, mode, capture=None):
         if fwd_masked is not None:
             with torch.cuda.stream(fwd_masked):
-                return measure_(pipe, mode)
-        return measure_(pipe, mode)
+                return measure_(pipe, mode, capture)
+        return measure_(pipe, mode, capture)
 
-    def measure_(pipe, mode):
+    def measure_(pipe, mode, capture=None):
         """warm-up steps, then EXACTLY args.steps steps between barriers; (max seconds over ranks, total edges)"""
         run_groups(pipe, 0, warm_groups, mode=mode)
         barrier()
@@ -999,7 +1010,7 @@ def main():
         szs = []
         for k in host_prof:
             host_prof[k] = 0
-        run_groups(pipe, warm_groups, total_groups, sizes=szs, mode=mode)
+        run_groups(pipe, warm_groups, total_groups, sizes=szs, mode=mode, capture=capture)
         barrier()
         secs = time.perf_counter() - t_start
         if args.host_profile and rank == 0:
@@ -1062,7 +1073,11 @@ def main():
         # kernel; --layer-kernel split keeps the aggregation kernel + library GEMM pair for every layer
         fusable = nn_mod.sage_layer_fused_preferred(pipe.dims[0], pipe.dims[1])
         head_mode = "fused" if (args.layer_kernel != "split" and fusable) else "split"
-        dt, edges_total = measure(pipe, head_mode)
+        dumped = {} if (args.dump_outputs and rank == 0) else None
+        if dumped is not None:
+            rows_d, pos_d = dump_positions(G * BATCH, CLASSES, gps, device)
+        dt, edges_total = measure(pipe, head_mode, capture=None if dumped is None else (
+            lambda k, res, h, sz: dumped.__setitem__(k, capture_outputs(res, h, sz, L, rows_d, pos_d))))
         per_rank = list(last_per_rank)
         # variants on the same groups: the other layer kernel, and the feature fetch folded into layer 1
         variants = {}
@@ -1121,7 +1136,7 @@ def main():
         split_ms = probe_stages(pipe, "split", 10)[0] if head_mode != "split" else stage_ms
         results[placement] = dict(dt=dt, edges=edges_total, variants=variants, stage_ms=stage_ms, psizes=psizes,
                                   split_ms=split_ms, head_mode=head_mode, stage_n=stage_n, pipe=pipe, feat=feat,
-                                  per_rank=per_rank, lazy_pass=lazy_pass)
+                                  per_rank=per_rank, lazy_pass=lazy_pass, dumped=dumped)
 
     def emit_line():
         """Rank 0 prints the ONE JSON line from whatever placements were measured; the headline is the first of HEAD_PREF
@@ -1439,11 +1454,48 @@ def main():
             placement_errors.setdefault(placement, "another rank could not build / verify / measure this placement")
             results.pop(placement, None)
     ok = emit_line()
+    if ok and args.dump_outputs and rank == 0:
+        head = next(p_ for p_ in HEAD_PREF if p_ in results)
+        dump_outputs(args.dump_outputs, results[head]["dumped"], gps)
     if dist.is_initialized():
         dist.barrier()
         dist.destroy_process_group()
     if not ok:
         sys.exit(1)
+
+
+DUMP_ROWS = 8192         # logit rows kept per call group (a fixed sample of the G x BATCH seed rows)
+DUMP_IDS = 4096          # node-list entries kept per call group
+DUMP_BYTES = 48 << 20    # bound on the logit sample of one step (the whole dump stays under 64 MB)
+
+
+def dump_positions(n_rows, n_cls, gps, device):
+    """The fixed sample positions of --dump-outputs: seed rows of the logits (seeded permutation, sorted; at most DUMP_ROWS per
+    call group and DUMP_BYTES per step) and DUMP_IDS evenly spaced fractions of the node list (scaled by its length later)."""
+    keep = max(1, min(n_rows, DUMP_ROWS, DUMP_BYTES // (gps * n_cls * 4)))
+    rows = torch.randperm(n_rows, generator=torch.Generator().manual_seed(0))[:keep].sort().values.to(device)
+    return rows, torch.arange(DUMP_IDS, dtype=torch.int64, device=device)
+
+
+def capture_outputs(res, h, sz, L, rows, pos):
+    """What one call group hands its caller, sampled on the device right behind the forward (the output buffers are reused by
+    the next group): the logit rows `rows`, the per-hop [edges, unique nodes] sizes and the entries of the last hop's node list
+    n_id at `pos` x len(n_id) / DUMP_IDS.  Same inputs, same positions, run after run."""
+    u_last = int(sz[2 * (L - 1) + 1])
+    return {"logits": h.index_select(0, rows), "logit_rows": rows,
+            "n_id": res.unique[L - 1].index_select(0, pos * u_last // DUMP_IDS) if u_last > 0 else torch.zeros_like(pos),
+            "sizes": torch.tensor(sz, dtype=torch.int64).view(L, 2)}
+
+
+def dump_outputs(out_dir, dumped, gps):
+    """DIR/<name>.npy, one leading axis over the call groups of the last timed step: logits [gps, rows, classes] float32,
+    logit_rows [gps, rows] (which seed rows those are), n_id [gps, DUMP_IDS] and sizes [gps, hops, 2] as float64 (exact)."""
+    torch.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    groups = [dumped[k] for k in range(gps)]
+    for name in ("logits", "logit_rows", "n_id", "sizes"):
+        a = np.stack([grp[name].cpu().numpy() for grp in groups])
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float32 if name == "logits" else np.float64))
 
 
 def feature_fetch_path(feat):

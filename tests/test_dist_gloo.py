@@ -34,6 +34,23 @@ class OracleLocalOps:
         oracle.scatter(OracleLocalOps._np(inp, table), idx.numpy(), OracleLocalOps._np(table, inp))
 
 
+def _start_without_gpu(procs):
+    """Start the workers with no GPU visible: they run the host logic over the oracle's row kernels exactly as on a machine
+    without one (a store's tensors go to the GPU where there is one, and the oracle's row kernels read host memory)."""
+    hidden = ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES")
+    saved = {k: os.environ.get(k) for k in hidden}
+    os.environ.update({k: "-1" for k in hidden})
+    try:
+        for p in procs:
+            p.start()
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -114,8 +131,7 @@ def test_partitioned_feature_store_world2(oracle_mod, offsets):
     q = ctx.Queue()
     port = _free_port()
     procs = [ctx.Process(target=_worker, args=(r, 2, port, offsets, q)) for r in range(2)]
-    for p in procs:
-        p.start()
+    _start_without_gpu(procs)
     results = [q.get(timeout=180) for _ in procs]
     for p in procs:
         p.join(timeout=60)
@@ -189,8 +205,7 @@ def test_pyg_stores_world2(oracle_mod):
     q = ctx.Queue()
     port = _free_port()
     procs = [ctx.Process(target=_store_worker, args=(r, 2, port, q)) for r in range(2)]
-    for p in procs:
-        p.start()
+    _start_without_gpu(procs)
     results = [q.get(timeout=180) for _ in procs]
     for p in procs:
         p.join(timeout=60)
@@ -318,8 +333,7 @@ def test_dist_tensor_embedding_matrix_world2(oracle_mod, tmp_path):
     q = ctx.Queue()
     port = _free_port()
     procs = [ctx.Process(target=_dist_tensor_worker, args=(r, 2, port, q, str(tmp_path))) for r in range(2)]
-    for p in procs:
-        p.start()
+    _start_without_gpu(procs)
     results = [q.get(timeout=240) for _ in procs]
     for p in procs:
         p.join(timeout=60)

@@ -61,30 +61,47 @@ def test_two_ranks_on_one_gpu_control_flow(hiplib):
     assert "rccl_ranks" in two      # None here: the gloo rehearsal has no RCCL communicator
 
 
-@pytest.mark.parametrize("dedup", ["0", "1"])
-def test_eight_ranks_control_flow_at_reduced_size(hiplib, dedup):
-    """The line the driver's N = 8 run will produce, rehearsed with eight processes on ONE GPU (gloo; RCCL refuses several ranks
-    per device, and eight processes time-slice the chip, so speeds mean nothing here): every rank joins the pre-flight and both
-    placements, the whole-job value is the sum over eight seed shards, and the partitioned fetch is exercised with the
-    de-duplicated exchange forced on and off (WGAMD_GATHER_DEDUP).  World sizes 2-8 of the C-level exchange itself — both
-    memory types, split communicators, empty partitions — run as threads over the RCCL stand-in in
-    tests/test_gpu_comm_multirank.py."""
-    d = _run(8, ["--dist-backend", "gloo", "--share-gpu"], env={"WGAMD_GATHER_DEDUP": dedup}, shape=("120000", "1500000", "4"))
-    assert d["n_gpus"] == 8 and d["scaling"] == "weak" and d["cpu_baseline"] is None
+def _check_many_ranks(d, n):
+    assert d["n_gpus"] == n and d["scaling"] == "weak" and d["cpu_baseline"] is None
     assert d["headline_placement"] == "partitioned" and set(d["placements"]) == {"replicated", "partitioned"}
-    assert "dp8" in d["config"]["parallelism"] and "all-to-all" in d["config"]["parallelism"]
+    assert "dp%d" % n in d["config"]["parallelism"] and "all-to-all" in d["config"]["parallelism"]
     assert d["selftest"]["partitioned"]["bit_exact"] is True and d["selftest"]["partitioned"]["dedup_bit_exact"] is True
-    assert d["selftest"]["partitioned"]["rows"] == 65537 * 8 + 3
+    assert d["selftest"]["partitioned"]["rows"] == 65537 * n + 3
     for name in ("replicated", "partitioned"):
         pr = d["placements"][name]["per_rank_value"]
-        assert len(pr) == 8 and all(v > 0 for v in pr)
+        assert len(pr) == n and all(v > 0 for v in pr)
         # the whole-job value = all ranks' edges over the SLOWEST rank's time: never above the sum of the per-rank rates (how far
-        # below says nothing here: eight processes time-slice one GPU and finish at very different times)
+        # below says nothing here: the ranks time-slice one GPU and finish at very different times)
         assert 0 < d["placements"][name]["value"] <= sum(pr) * 1.001
     part = d["placements"]["partitioned"]
     assert part["requested_rows_per_call_group"] > 0 and part["wire_rows_per_call_group"] <= part["requested_rows_per_call_group"]
-    assert part["all_to_all_bytes_per_gpu"] > 0 and d["xgmi_peak_GBps"] == 7 * 153.0
+    assert part["all_to_all_bytes_per_gpu"] > 0 and d["xgmi_peak_GBps"] == (n - 1) * 153.0
     assert d["call_group"] == 4 and d["batches_per_step"] == 8 and d["timed_call_groups"] == 6
+
+
+@pytest.mark.parametrize("dedup", ["0", "1"])
+def test_eight_ranks_control_flow_at_reduced_size(hiplib, dedup):
+    """The line the driver's N = 8 run will produce, rehearsed at reduced size (gloo; speeds mean nothing here): every rank
+    joins the pre-flight and both placements, the whole-job value is the sum over eight seed shards, and the partitioned
+    fetch is exercised with the de-duplicated exchange forced on and off (WGAMD_GATHER_DEDUP).  One rank per GPU: eight
+    processes on one shared GPU are more than it may have open at once, so this needs eight GPUs; the same control flow at
+    four ranks on one GPU is test_four_ranks_control_flow_at_reduced_size.  World sizes 2-8 of the C-level exchange itself
+    — both memory types, split communicators, empty partitions — run as threads over the RCCL stand-in in
+    tests/test_gpu_comm_multirank.py."""
+    import torch
+    found = torch.cuda.device_count()
+    if found < 8:
+        pytest.skip("needs 8 GPUs (one rank per GPU), found %d" % found)
+    d = _run(8, ["--dist-backend", "gloo"], env={"WGAMD_GATHER_DEDUP": dedup}, shape=("120000", "1500000", "4"))
+    _check_many_ranks(d, 8)
+
+
+@pytest.mark.parametrize("dedup", ["0", "1"])
+def test_four_ranks_control_flow_at_reduced_size(hiplib, dedup):
+    """test_eight_ranks_control_flow_at_reduced_size's rehearsal with four processes on ONE GPU (gloo; RCCL refuses several
+    ranks per device).  Four ranks plus the test process stay within the six processes that may have one shared GPU open at once."""
+    d = _run(4, ["--dist-backend", "gloo", "--share-gpu"], env={"WGAMD_GATHER_DEDUP": dedup}, shape=("120000", "1500000", "4"))
+    _check_many_ranks(d, 4)
 
 
 def test_partitioned_feature_store_two_ranks(hiplib):

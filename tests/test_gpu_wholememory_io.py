@@ -22,11 +22,19 @@ def comm():
     c.destroy()
 
 
-def _valid(dim, stride, offset, rr=0):
-    if stride < offset + dim:
-        pytest.skip("embedding_stride, embedding_dim and storage_offset configuration not valid")
-    if rr != 0 and offset != 0:
-        pytest.skip("round_robin_size != 0 with a storage offset is not valid")
+def _fits(dim, stride, offset):
+    """Does a view of `dim` columns at column `offset` fit inside a row of `stride` elements?  The reference test skips the
+    configurations where it does not; here they check that the file I/O refuses such a layout (before touching any memory).
+    (The reference test also skips round-robin loads into a view with a column offset; this loader places the payload at
+    the view's column offset for either sharding, so those configurations run the full load check.)"""
+    return stride >= offset + dim
+
+
+def _refused(call):
+    import wholegraph_amd as wg
+    with pytest.raises(wg.WholeMemoryError) as e:
+        call()
+    assert "INVALID_INPUT" in str(e.value)
 
 
 @pytest.mark.parametrize("file_part_count", [3, 5])
@@ -38,7 +46,6 @@ def _valid(dim, stride, offset, rr=0):
 def test_wholememory_load(comm, tmp_path, file_part_count, embedding_entry_count, embedding_dim, embedding_stride,
                           storage_offset, round_robin_size):
     import wholegraph_amd as wg
-    _valid(embedding_dim, embedding_stride, storage_offset, round_robin_size)
     random.seed(file_part_count * 1000 + embedding_dim)
     n = embedding_entry_count
     base = torch.randint(-1000000000, 1000000000, (n, embedding_dim), dtype=torch.int)
@@ -51,6 +58,13 @@ def test_wholememory_load(comm, tmp_path, file_part_count, embedding_entry_count
     extra = n   # one rank: the round-robin padding of the reference (test_wholememory_io.py:57-70) is empty
     root = wg.create_wholememory_tensor(comm, "distributed", "cuda", [extra, embedding_dim + storage_offset], torch.int32,
                                         [embedding_stride, 1])
+    if not _fits(embedding_dim, embedding_stride, storage_offset):
+        # the rows overlap: neither the root nor the view is ever read or written, the load must refuse the layout
+        view = root.get_sub_tensor([-1, storage_offset], [-1, -1])
+        _refused(lambda: view.from_filelist(files, round_robin_size))
+        view.destroy()
+        wg.destroy_wholememory_tensor(root)
+        return
     root.get_local_tensor()[0].fill_(-7)
     view = root.get_sub_tensor([-1, storage_offset], [-1, -1])
     assert view.shape == (extra, embedding_dim)
@@ -73,14 +87,20 @@ def test_wholememory_load(comm, tmp_path, file_part_count, embedding_entry_count
 @pytest.mark.parametrize("storage_offset", [0, 3])
 def test_wholememory_store(comm, tmp_path, embedding_entry_count, embedding_dim, embedding_stride, storage_offset):
     import wholegraph_amd as wg
-    _valid(embedding_dim, embedding_stride, storage_offset)
     n = embedding_entry_count
     base = torch.randint(-1000000000, 1000000000, (n, embedding_dim), dtype=torch.int)
     root = wg.create_wholememory_tensor(comm, "distributed", "cuda", [n, embedding_dim + storage_offset], torch.int32,
                                         [embedding_stride, 1])
     view = root.get_sub_tensor([-1, storage_offset], [-1, -1])
-    view.get_local_tensor()[0].copy_(base.cuda())
     name = str(tmp_path / "pytest_store_temp_file")
+    if not _fits(embedding_dim, embedding_stride, storage_offset):
+        # the rows overlap: the table is never read or written, the store must refuse the layout and write no file
+        _refused(lambda: view.local_to_file(name))
+        assert not os.path.exists(name)
+        view.destroy()
+        wg.destroy_wholememory_tensor(root)
+        return
+    view.get_local_tensor()[0].copy_(base.cuda())
     view.local_to_file(name)
     assert os.path.getsize(name) == n * embedding_dim * 4
     assert np.array_equal(np.fromfile(name, dtype=np.int32).reshape(n, embedding_dim), base.numpy())

@@ -21,7 +21,7 @@ def test_graph_store_csr_reverses_direction_and_keeps_edge_ids():
     assert gs._vertex_offsets == {"person": 0}
     attrs = gs.get_all_edge_attrs()
     assert len(attrs) == 1 and attrs[0].edge_type == ("person", "knows", "person") and tuple(attrs[0].size) == (6, 6)
-    assert torch.equal(gs.get_edge_index(("person", "knows", "person"), "coo"), ei)
+    assert torch.equal(gs.get_edge_index(("person", "knows", "person"), "coo").cpu(), ei)   # (on the GPU where there is one)
     ptr, minor = gs.get_edge_index(("person", "knows", "person"), "csr")
     assert ptr.tolist() == [0, 0, 0, 0, 2, 3, 4] and minor.tolist() == [0, 2, 1, 2]
 
@@ -114,8 +114,8 @@ def test_hetero_type_local_csrs():
     assert w.col.tolist() == [0, 1, 2, 3, 3, 0] and w.edge_id.tolist() == [0, 1, 2, 3, 4, 5]
     c = hg[("paper", "cites", "paper")]
     for v in range(6):      # row v = in-neighbours of paper v, edge ids point into the ORIGINAL arrays
-        ids = c.edge_id[c.row_ptr[v]:c.row_ptr[v + 1]]
-        assert (dst[ids] == v).all() and torch.equal(src[ids], c.col[c.row_ptr[v]:c.row_ptr[v + 1]])
+        ids = c.edge_id[c.row_ptr[v]:c.row_ptr[v + 1]].cpu()   # (the store's tensors live on the GPU where there is one)
+        assert (dst[ids] == v).all() and torch.equal(src[ids], c.col[c.row_ptr[v]:c.row_ptr[v + 1]].cpu())
 
 
 def test_hop_seed_derivation_is_stable():
