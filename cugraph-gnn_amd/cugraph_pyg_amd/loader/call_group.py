@@ -15,6 +15,7 @@ mini-batches, ``batch_ptr`` says which rows belong to which mini-batch, and ``la
 ``nn.SAGEConv`` reads through directly, so the gathered ``[N, F]`` copy — the largest tensor of a mini-batch — never exists;
 any other use gathers it once.
 """
+import weakref
 from typing import List, Optional
 
 import torch
@@ -172,8 +173,25 @@ class CallGroup:
             hops.append(HopGraph(res.offsets[k][:n_f + 1], col[:n_e], self_rows))
         lg = LayerGraph(hops)
         lg._keep = (seg_tab, seg_base)
+        me = weakref.ref(self)        # (the graph is cached on the group: no reference cycle back to it)
+        lg.degree_source = lambda: me()._degree_source(layer)
         self._layers[layer] = lg
         return lg
+
+    def _degree_source(self, layer: int):
+        """``LayerGraph.degree_source`` of layer ``layer`` (GCNConv's degrees, from the UNTRIMMED mini-batch graphs): every
+        vertex is a destination of exactly one hop — the one whose frontier it is in — with its whole sampled row; a vertex
+        found by the last hop has in-degree 0.  Layer 0's input rows are node-list rows, each destination's ``self_rows``
+        entry; layer j > 0 reads the output rows of layer j - 1, which are that layer's hops' destination rows back to back."""
+        if layer == 0:
+            lg = self.layer_graph(0)
+            return lg.hops, [-1] * len(lg.hops), self.num_nodes
+        prev = self.layer_graph(layer - 1)
+        base, at = [], 0
+        for h in prev.hops:
+            base.append(at)
+            at += h.n_rows
+        return prev.hops, base, at
 
     def _coo(self):
         """All sampled edges, hop-major, as rows of ``n_id``: (source row, destination row, CSR slot)."""

@@ -277,6 +277,21 @@ SYMBOLS = {
                                                c_void_p, c_void_p]),
     "wgamd_softmax_xent_backward_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, c_int64, c_void_p]),
+    # GCN layer (wg_gcn.hip)
+    "wgamd_gcn_layer_supported": (c_int, [c_int, c_int]),
+    "wgamd_gcn_layer_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64,
+                                    c_void_p]),
+    "wgamd_gcn_layer_f32_train": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_void_p, c_int,
+                                          c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "wgamd_gcn_aggregate_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_float, c_int, c_void_p, c_int64, c_void_p]),
+    "wgamd_gcn_degrees_f32": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p),
+                                      POINTER(c_int64), POINTER(c_int64), c_float, c_int, c_void_p, c_int64, c_void_p]),
+    "wgamd_gcn_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "wgamd_gcn_wgrad_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p,
+                                    c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "wgamd_bias_act_rows_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "wgamd_gat_transform_heads_supported": (c_int, [c_int, c_int, c_int]),
     "wgamd_gat_transform_weight_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -1031,6 +1031,10 @@ class LayerGraph:
 
     def __init__(self, hops):
         self.hops = list(hops)
+        # GCNConv's degrees of the layer's INPUT rows: a callable -> (hops, out_base, n_in), the hops whose destination rows are
+        # those input rows (out_base[h] = input row of hop h's row 0, or -1: row i is input row self_rows[i]); set by the
+        # loader (CallGroup.layer_graph), None for a user-built graph
+        self.degree_source = None
 
     @property
     def n_rows(self):
@@ -1370,6 +1374,381 @@ class GATConv(torch.nn.Module):
         if self.bias is not None:
             out = out + self.bias
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# GCN (torch_geometric.nn.GCNConv; the model of the reference's cugraph-pyg example gcn_dist_mnmg.py) — csrc/wg_gcn.hip
+# ---------------------------------------------------------------------------------------------------------------------
+GCN_ADD_SELF_LOOPS, GCN_RELU, GCN_MAX_HOPS = 1, 2, 8     # WGAMD_GCN_* (include/wgamd_ext.h)
+
+
+def gcn_layer_supported(F_: int, N: int) -> bool:
+    """Shapes of the one-kernel GCN layer (``wgamd_gcn_layer_f32``): F % 4 == 0, F <= 256, N <= 256."""
+    return bool(L.lib().wgamd_gcn_layer_supported(int(F_), int(N)))
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def gcn_degrees(hops, out_base, n_out: int, fill: float = 1.0, add_self_loops: bool = True, edge_weights=None, device=None):
+    """``dinv`` float32 [n_out] = deg^-1/2 of gcn_norm for the rows the hops' destinations are (``wgamd_gcn_degrees_f32``, one
+    launch): row i of hop h is entry ``out_base[h] + i``, or ``self_rows[i]`` when ``out_base[h] < 0``.  Entries no hop reaches
+    have in-degree 0: their degree is the added loop alone (``fill``), or 0 without self loops (factor 0)."""
+    import ctypes
+    hops = list(hops)
+    if len(hops) > GCN_MAX_HOPS:
+        raise ValueError("gcn_degrees: at most %d hops" % GCN_MAX_HOPS)
+    device = device if device is not None else hops[0].row_ptr.device
+    default = 1.0 / math.sqrt(fill) if add_self_loops and fill > 0 else 0.0
+    dinv = torch.full((int(n_out),), default, dtype=torch.float32, device=device)
+    if not hops:
+        return dinv
+    for h in hops:
+        _check_csr(h.row_ptr, h.col)
+        assert h.self_rows.dtype == torch.int64 and h.self_rows.is_contiguous()
+    n = len(hops)
+    P, I = ctypes.c_void_p * n, ctypes.c_int64 * n
+    ew = None
+    if edge_weights is not None:
+        for w in edge_weights:
+            assert w is None or (w.dtype == torch.float32 and w.is_contiguous())
+        ew = P(*[_ptr(w) for w in edge_weights])
+    L.check(L.lib().wgamd_gcn_degrees_f32(
+        n, P(*[h.row_ptr.data_ptr() for h in hops]), P(*[h.col.data_ptr() for h in hops]), P(*[h.self_rows.data_ptr() for h in hops]),
+        ew, I(*[h.n_rows for h in hops]), I(*[int(b) for b in out_base]), float(fill), int(bool(add_self_loops)), dinv.data_ptr(),
+        int(n_out), get_stream()), "wgamd_gcn_degrees_f32")
+    return dinv
+
+
+def _gcn_args(x, src_ids):
+    ids_ptr, ids_dt = None, 0
+    if src_ids is not None:
+        assert src_ids.is_contiguous()
+        ids_ptr, ids_dt = src_ids.data_ptr(), _ids_code(x, src_ids)
+    return ids_ptr, ids_dt
+
+
+def gcn_layer_forward(row_ptr, col, x, self_rows, weight, bias=None, dinv_src=None, dinv_dst=None, fill=1.0, add_self_loops=False,
+                      relu=False, src_ids=None, edge_weight=None, out=None, agg_out=None):
+    """A whole GCN layer over one hop in ONE kernel: ``act(agg @ weight^T + bias)`` with the normalised aggregate ``agg`` of
+    ``wgamd_gcn_layer_f32`` (include/wgamd_ext.h); ``weight`` is [N, F] (``torch.nn.Linear`` layout).  ``agg_out`` ([n_rows, F]):
+    the launch also keeps the aggregate (``_train``)."""
+    _check_csr(row_ptr, col)
+    n_rows, F_, N = row_ptr.shape[0] - 1, x.shape[1], weight.shape[0]
+    assert x.dtype == torch.float32 and x.stride(1) == 1 and weight.dtype == torch.float32 and weight.stride(1) == 1
+    assert weight.shape[1] == F_ and self_rows.dtype == torch.int64 and self_rows.is_contiguous()
+    if out is None:
+        out = torch.empty((n_rows, N), dtype=torch.float32, device=row_ptr.device)
+    assert out.shape == (n_rows, N) and out.stride(1) == 1
+    ids_ptr, ids_dt = _gcn_args(x, src_ids)
+    flags = (GCN_ADD_SELF_LOOPS if add_self_loops else 0) | (GCN_RELU if relu else 0)
+    common = (row_ptr.data_ptr(), col.data_ptr(), n_rows, x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt, self_rows.data_ptr(),
+              _ptr(edge_weight), _ptr(dinv_src), _ptr(dinv_dst), float(fill), weight.data_ptr(), weight.stride(0), N, _ptr(bias),
+              flags, out.data_ptr(), out.stride(0))
+    if agg_out is not None:
+        assert agg_out.shape == (n_rows, F_) and agg_out.stride(1) == 1
+        L.check(L.lib().wgamd_gcn_layer_f32_train(*common, agg_out.data_ptr(), agg_out.stride(0), get_stream()),
+                "wgamd_gcn_layer_f32_train")
+    else:
+        L.check(L.lib().wgamd_gcn_layer_f32(*common, get_stream()), "wgamd_gcn_layer_f32")
+    return out
+
+
+def gcn_aggregate(row_ptr, col, x, self_rows, dinv_src=None, dinv_dst=None, fill=1.0, add_self_loops=False, src_ids=None,
+                  edge_weight=None, out=None):
+    """The normalised aggregate of the GCN layer alone, any F (``wgamd_gcn_aggregate_f32``): what shapes outside the layer
+    kernel's domain multiply with a library GEMM."""
+    _check_csr(row_ptr, col)
+    n_rows, F_ = row_ptr.shape[0] - 1, x.shape[1]
+    assert x.dtype == torch.float32 and x.stride(1) == 1 and self_rows.dtype == torch.int64 and self_rows.is_contiguous()
+    if out is None:
+        out = torch.empty((n_rows, F_), dtype=torch.float32, device=row_ptr.device)
+    ids_ptr, ids_dt = _gcn_args(x, src_ids)
+    L.check(L.lib().wgamd_gcn_aggregate_f32(
+        row_ptr.data_ptr(), col.data_ptr(), n_rows, x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt, self_rows.data_ptr(),
+        _ptr(edge_weight), _ptr(dinv_src), _ptr(dinv_dst), float(fill), GCN_ADD_SELF_LOOPS if add_self_loops else 0,
+        out.data_ptr(), out.stride(0), get_stream()), "wgamd_gcn_aggregate_f32")
+    return out
+
+
+def gcn_wgrad(agg, grad_out, grad_w, grad_bias=None, act_out=None, accumulate=False):
+    """``grad_w (+)= dZ^T agg``, ``grad_bias (+)= colsum(dZ)``, ``dZ = grad_out * (act_out > 0)`` (``wgamd_gcn_wgrad_f32``:
+    deterministic split-K)."""
+    n, F_ = agg.shape
+    N = grad_out.shape[1]
+    assert agg.stride(1) == 1 and grad_out.stride(1) == 1 and grad_w.shape == (N, F_) and grad_w.is_contiguous()
+    assert act_out is None or (act_out.shape == grad_out.shape and act_out.stride(1) == 1)
+    need = L.lib().wgamd_gcn_wgrad_workspace_bytes(int(n), F_, N)
+    ws = torch.empty(max(int(need), 4), dtype=torch.uint8, device=agg.device)
+    L.check(L.lib().wgamd_gcn_wgrad_f32(agg.data_ptr(), agg.stride(0), n, F_, grad_out.data_ptr(), grad_out.stride(0), _ptr(act_out),
+                                        0 if act_out is None else act_out.stride(0), N, grad_w.data_ptr(), _ptr(grad_bias),
+                                        int(bool(accumulate)), ws.data_ptr(), ws.numel(), get_stream()), "wgamd_gcn_wgrad_f32")
+
+
+def _gcn_transposed(hop: HopGraph, n_src: int, edge_weight):
+    """``(row_ptr_t, col_t, self_t, edge_weight_t)`` of a hop seen from its input rows: the source-major CSR (hop order inside a
+    source row: deterministic sums), ``self_t[j]`` = the destination row that is input row j itself, -1 where there is none,
+    and the edge weights in source-major order."""
+    if edge_weight is None:
+        row_ptr_t, col_t, _ = hop.transposed(n_src, need_self=False)
+        w_t = None
+    else:
+        row_ptr_t, perm, _, col_t = _csr_transpose(hop.row_ptr, hop.col, n_src, want_perm=True, want_col_t=True)
+        w_t = edge_weight[perm.long()].contiguous()
+    key = (n_src, hop.self_rows.data_ptr())
+    st = getattr(hop, "_gcn_self_t", None)
+    if st is None or st[0] != key:
+        self_t = torch.full((n_src,), -1, dtype=torch.int64, device=hop.row_ptr.device)
+        self_t[hop.self_rows] = torch.arange(hop.n_rows, dtype=torch.int64, device=hop.row_ptr.device)
+        st = hop._gcn_self_t = (key, self_t)
+    return row_ptr_t, col_t, st[1], w_t
+
+
+def _gcn_input_grad(hop, g, n_src, dinv_in, conv, edge_weight, weight=None):
+    """``A_hat^T g`` over one hop (rows = the layer's input rows), times ``weight`` ([F, Nq], the layer's W^T zero-padded to
+    Nq rows) when given: the GCN kernel run over the hop's transpose — destination rows become the summed rows, so the
+    per-row factor and the per-edge factor swap places (``dinv_dst`` = the input rows', ``dinv_src`` = the destinations')."""
+    row_ptr_t, col_t, self_t, w_t = _gcn_transposed(hop, n_src, edge_weight)
+    d_out = dinv_in[hop.self_rows] if dinv_in is not None else None
+    loops = conv.normalize and conv.add_self_loops
+    if weight is None:
+        return gcn_aggregate(row_ptr_t, col_t, g, self_t, dinv_src=d_out, dinv_dst=dinv_in, fill=conv._fill, add_self_loops=loops,
+                             edge_weight=w_t)
+    return gcn_layer_forward(row_ptr_t, col_t, g, self_t, weight, dinv_src=d_out, dinv_dst=dinv_in, fill=conv._fill,
+                             add_self_loops=loops, edge_weight=w_t)
+
+
+def _gcn_launch_args(conv, dinv_in):
+    return dict(dinv_src=dinv_in, fill=conv._fill, add_self_loops=conv.normalize and conv.add_self_loops)
+
+
+class _GcnLayer(torch.autograd.Function):
+    """The one-kernel GCN layer over a ``LayerGraph`` (one ``wgamd_gcn_layer_f32`` launch per hop; under autograd the
+    ``_train`` form keeps the aggregate).  Backward: ``wgamd_gcn_wgrad_f32`` per hop (dW, db) and, when the input rows need a
+    gradient, the same layer kernel over every hop's transpose with ``W^T`` as the weight (dX = A_hat^T dZ W)."""
+
+    @staticmethod
+    def forward(ctx, src, weight, bias, conv, graph, dinv_in, ids, relu, edge_weights, n_src):
+        N, F_ = weight.shape
+        keep = any(ctx.needs_input_grad[:3])
+        if keep and ctx.needs_input_grad[0] and ids is not None:
+            raise NotImplementedError("gradient w.r.t. a feature table read through ids (LazyRows): trainable node "
+                                      "embeddings go through wholegraph_amd.embedding")
+        out = torch.empty((graph.n_rows, N), dtype=torch.float32, device=weight.device)
+        aggs, at = [], 0
+        w = weight.detach()
+        b = bias.detach() if bias is not None else None
+        for k, h in enumerate(graph.hops):
+            n = h.n_rows
+            agg = torch.empty((n, F_), dtype=torch.float32, device=weight.device) if keep and ctx.needs_input_grad[1] and n > 0 else None
+            if n > 0:
+                gcn_layer_forward(h.row_ptr, h.col, src, h.self_rows, w, b, relu=relu, src_ids=ids,
+                                  edge_weight=None if edge_weights is None else edge_weights[k], out=out[at:at + n], agg_out=agg,
+                                  **_gcn_launch_args(conv, dinv_in))
+            aggs.append(agg)
+            at += n
+        if keep:
+            ctx.save_for_backward(weight, out)
+            ctx.conv, ctx.graph, ctx.dinv_in, ctx.relu, ctx.edge_weights, ctx.n_src, ctx.aggs = \
+                conv, graph, dinv_in, relu, edge_weights, n_src, aggs
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.aggs is None:
+            raise RuntimeError("wholegraph_amd.nn.GCNConv: backward through this layer a second time — its kept aggregates were "
+                               "released by the first backward pass (retain_graph=True is not supported by the one-kernel layer)")
+        weight, out = ctx.saved_tensors
+        N, F_ = weight.shape
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        g = g.contiguous().float()
+        act = out if ctx.relu else None
+        if ctx.relu and need_x:
+            g, act = torch.ops.aten.threshold_backward(g, out, 0), None      # dZ once, read by both gradients
+        gw = torch.empty_like(weight, memory_format=torch.contiguous_format) if need_w else None
+        gb = torch.empty(N, dtype=torch.float32, device=g.device) if need_b else None
+        gx = None
+        if need_x:
+            Nq = (N + 3) // 4 * 4
+            w_bwd = torch.zeros((F_, Nq), dtype=torch.float32, device=g.device)
+            w_bwd[:, :N] = weight.detach().t()
+            if Nq != N:
+                gq = torch.zeros((g.shape[0], Nq), dtype=torch.float32, device=g.device)
+                gq[:, :N] = g
+            else:
+                gq = g
+        at, first = 0, True
+        for k, (h, agg) in enumerate(zip(ctx.graph.hops, ctx.aggs)):
+            n = h.n_rows
+            if n > 0:
+                if need_w:
+                    gcn_wgrad(agg, g[at:at + n], gw, gb, None if act is None else act[at:at + n], accumulate=not first)
+                elif need_b:
+                    gz = g[at:at + n] if act is None else g[at:at + n] * (act[at:at + n] > 0)
+                    gb = gz.sum(0) if first else gb.add_(gz.sum(0))
+                first = False
+                if need_x:
+                    gh = _gcn_input_grad(h, gq[at:at + n], ctx.n_src, ctx.dinv_in, ctx.conv,
+                                         None if ctx.edge_weights is None else ctx.edge_weights[k], weight=w_bwd)
+                    gx = gh if gx is None else gx.add_(gh)
+            at += n
+        if first:
+            if gw is not None:
+                gw.zero_()
+            if gb is not None:
+                gb.zero_()
+        if need_x and gx is None:
+            gx = torch.zeros((ctx.n_src, F_), dtype=torch.float32, device=g.device)
+        ctx.aggs = None
+        return gx, gw, gb, None, None, None, None, None, None, None
+
+
+class _GcnAggregate(torch.autograd.Function):
+    """The normalised aggregate over every hop of a ``LayerGraph`` (``wgamd_gcn_aggregate_f32``), rows back to back; backward =
+    the same kernel over the hops' transposes.  The route of shapes the one-kernel layer does not take."""
+
+    @staticmethod
+    def forward(ctx, x, conv, graph, dinv_in, edge_weights):
+        aggs = []
+        for k, h in enumerate(graph.hops):
+            if h.n_rows > 0:
+                aggs.append(gcn_aggregate(h.row_ptr, h.col, x, h.self_rows,
+                                          edge_weight=None if edge_weights is None else edge_weights[k],
+                                          **_gcn_launch_args(conv, dinv_in)))
+        ctx.conv, ctx.graph, ctx.dinv_in, ctx.edge_weights, ctx.n_src = conv, graph, dinv_in, edge_weights, x.shape[0]
+        if not aggs:
+            return torch.zeros((0, x.shape[1]), dtype=torch.float32, device=x.device)
+        return aggs[0] if len(aggs) == 1 else torch.cat(aggs)
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        gx, at = None, 0
+        for k, h in enumerate(ctx.graph.hops):
+            n = h.n_rows
+            if n > 0:
+                gh = _gcn_input_grad(h, g[at:at + n], ctx.n_src, ctx.dinv_in, ctx.conv,
+                                     None if ctx.edge_weights is None else ctx.edge_weights[k])
+                gx = gh if gx is None else gx.add_(gh)
+            at += n
+        if gx is None:
+            gx = torch.zeros((ctx.n_src, g.shape[1]), dtype=torch.float32, device=g.device)
+        return gx, None, None, None, None
+
+
+def _coo_to_csr_weighted(edge_index, edge_weight, n_dst):
+    """COO ``edge_index`` + per-edge weights -> destination-major CSR with the weights in CSR order (stable: edge order kept
+    inside a destination)."""
+    src, dst = edge_index[0], edge_index[1]
+    order = torch.sort(dst, stable=True).indices
+    col = src[order].to(torch.int32).contiguous()
+    w = edge_weight[order].to(torch.float32).contiguous()
+    row_ptr = torch.zeros(n_dst + 1, dtype=torch.int32, device=dst.device)
+    row_ptr[1:] = torch.cumsum(torch.bincount(dst, minlength=n_dst), 0)
+    return row_ptr, col, w
+
+
+class GCNConv(torch.nn.Module):
+    """PyG ``GCNConv`` (``flow="source_to_target"``, sum aggregation): ``x' = D^-1/2 (A + L) D^-1/2 (x W^T) + b`` with the
+    self loops of ``add_remaining_self_loops`` (a node with a loop edge keeps that loop's weight; ``fill`` = 2 when
+    ``improved``, else 1).  Parameters as PyG names them (``lin.weight`` glorot, ``bias`` zeros), so a PyG ``state_dict`` loads.
+
+    ``forward(x, graph, act=None, edge_weight=None)``: ``graph`` = a COO ``edge_index`` (the ``for batch in loader`` loop of
+    gcn_dist_mnmg.py; output rows = x's rows), a ``[csr_row_ptr, csr_col_ind]`` pair (destinations = the first rows of x), or a
+    call group's ``LayerGraph`` with ``x`` a tensor or ``LazyRows`` (degrees from the untrimmed mini-batch graph, which the
+    loader attaches).  The layer — feature fetch, normalised aggregation, ``x W^T``, bias, optional ``act="relu"`` — is ONE
+    kernel per hop (``wgamd_gcn_layer_f32``) for F % 4 == 0, F <= 256, N <= 256; other shapes run the normalised-aggregate
+    kernel and a library GEMM."""
+
+    def __init__(self, in_channels: int, out_channels: int, improved: bool = False, cached: bool = False,
+                 add_self_loops: bool = True, normalize: bool = True, bias: bool = True):
+        super().__init__()
+        if cached:
+            raise ValueError("GCNConv(cached=True): the graph of a mini-batch changes on every call; nothing can be cached")
+        self.in_channels, self.out_channels = in_channels, out_channels
+        self.improved, self.cached, self.add_self_loops, self.normalize = improved, cached, add_self_loops, normalize
+        self.lin = torch.nn.Linear(in_channels, out_channels, bias=False)
+        self.bias = torch.nn.Parameter(torch.empty(out_channels)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        torch.nn.init.xavier_uniform_(self.lin.weight)     # glorot, as PyG's Linear(weight_initializer="glorot")
+        if self.bias is not None:
+            torch.nn.init.zeros_(self.bias)
+
+    @property
+    def _fill(self) -> float:
+        return 2.0 if self.improved else 1.0
+
+    def _dinv(self, lg: LayerGraph, device):
+        """dinv of the layer's input rows (None without normalisation), computed once per layer graph and configuration."""
+        if not self.normalize:
+            return None
+        key = (self._fill, bool(self.add_self_loops))
+        cache = getattr(lg, "_gcn_dinv", None)
+        if cache is None:
+            cache = lg._gcn_dinv = {}
+        if key not in cache:
+            if lg.degree_source is None:
+                raise ValueError("GCNConv over a LayerGraph needs the degrees of its input rows in the untrimmed mini-batch "
+                                 "graph: use CallGroup.layer_graph(j) (it attaches them), or set LayerGraph.degree_source")
+            hops, base, n_in = lg.degree_source()
+            cache[key] = gcn_degrees(hops, base, n_in, self._fill, self.add_self_loops,
+                                     edge_weights=getattr(lg, "_gcn_edge_weights", None), device=device)
+        return cache[key]
+
+    def _forward_layer(self, x, lg: LayerGraph, act=None, edge_weights=None):
+        assert act in (None, "relu"), "act: None or 'relu'"
+        relu = act == "relu"
+        lazy = isinstance(x, LazyRows)
+        src = x.table if lazy else x
+        n_src = len(x) if lazy else x.shape[0]
+        F_, N = self.in_channels, self.out_channels
+        if x.shape[1] != F_:
+            raise ValueError("GCNConv: x has %d features, the layer takes %d" % (x.shape[1], F_))
+        dinv = self._dinv(lg, src.device)
+        if (gcn_layer_supported(F_, N) and src.dtype == torch.float32 and src.is_cuda and src.stride(1) == 1
+                and src.stride(0) % 4 == 0 and src.data_ptr() % 16 == 0):
+            return _GcnLayer.apply(src, self.lin.weight, self.bias, self, lg, dinv, x.ids if lazy else None, relu, edge_weights,
+                                   n_src)
+        xd = x.materialize() if lazy else x
+        agg = _GcnAggregate.apply(xd.contiguous().float(), self, lg, dinv, edge_weights)
+        out = torch.nn.functional.linear(agg, self.lin.weight, self.bias)
+        return torch.relu(out) if relu else out
+
+    def forward(self, x, graph, act=None, edge_weight=None):
+        if _capturing():
+            # (the degrees and transposes a layer graph keeps are cached in Python against the graph object: a replay would
+            #  keep using those of the capture)
+            raise RuntimeError("wholegraph_amd.nn.GCNConv is not supported under HIP-graph capture (loader.PerBatchStep): its "
+                               "per-graph degree caches are not capture-safe; SAGEConv layers are")
+        if edge_weight is not None and torch.is_grad_enabled() and edge_weight.requires_grad:
+            raise NotImplementedError("GCNConv: no gradient w.r.t. edge_weight")
+        if isinstance(graph, LayerGraph):
+            if edge_weight is not None:
+                raise ValueError("GCNConv: edge_weight is not taken with a call group's LayerGraph (its edges are unweighted)")
+            return self._forward_layer(x, graph, act)
+        if isinstance(x, LazyRows):
+            x = x.materialize()
+        n_src = x.shape[0]
+        if isinstance(graph, (tuple, list)):
+            row_ptr, col = graph[0], graph[1]          # [csr_row_ptr, csr_col_ind]: destinations = the first rows of x
+            _check_csr(row_ptr, col)
+            w = None
+            if edge_weight is not None:
+                w = edge_weight.to(torch.float32).contiguous()
+        elif edge_weight is not None:
+            row_ptr, col, w = _coo_to_csr_weighted(graph, edge_weight, n_src)
+        else:
+            row_ptr, col = _to_csr(graph, n_src)
+            w = None
+        n_dst = row_ptr.shape[0] - 1
+        hop = HopGraph(row_ptr, col, _arange(n_dst, x.device))
+        lg = LayerGraph([hop])
+        lg.degree_source = lambda: ([hop], [0], n_src)
+        lg._gcn_edge_weights = None if w is None else [w]
+        return self._forward_layer(x, lg, act, None if w is None else [w])
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -730,6 +730,58 @@ wholememory_error_code_t wgamd_softmax_xent_backward_f32(const float* logits, in
                                                          const void* state, const float* grad_loss, float* grad_logits, int64_t ldg,
                                                          void* stream);
 
+/* ---- GCN layer (csrc/wg_gcn.hip): torch_geometric.nn.GCNConv over a sampled hop ---------------------------------------------
+ * The model of the reference's headline cugraph-pyg example (python/cugraph-pyg/cugraph_pyg/examples/gcn_dist_mnmg.py):
+ *   agg[i]  = s_i ( sum_{e = (j -> i), not a loop} w_e d_j X[j]  +  [loops] loopw_i d_self X[self_rows[i]] )
+ *   out[i]  = act(agg[i] @ W^T + b)
+ * "a loop" = col[e] == self_rows[i] while WGAMD_GCN_ADD_SELF_LOOPS is set (add_remaining_self_loops: the loop edge is not
+ * summed, it gives the added loop its weight — the last one of the row; loopw_i = fill when the row has none);
+ * w_e = edge_weight[e] (nullable = 1); d_j = dinv_src[j] (nullable = 1); s_i = dinv_dst[i], or dinv_src[self_rows[i]] when
+ * dinv_dst is null (1 when both are); d_self = dinv_src[self_rows[i]].  self_rows[i] < 0: row i has no self term (a
+ * transposed hop's source-only rows).  X[r] = x[src_ids ? src_ids[r] : r] (INT, INT64 or WGAMD_IDS_BYTE_OFFSETS).  W is
+ * [N, ldw] row-major (the layout of torch.nn.Linear.weight).  Sums run in CSR order: run-to-run deterministic.
+ * Layer kernel: wgamd_gcn_layer_supported(F, N) (F % 4 == 0, F <= 256, N <= 256), x / w rows 16-B aligned; the product runs
+ * on the exact fp32 matrix pipe (v_mfma_f32_16x16x4_f32).  _train also writes agg [n_rows, F] (ld_agg, 16-B aligned rows;
+ * same bits as the operand of the product) for the weight gradient.  wgamd_gcn_aggregate_f32: agg alone, any F. */
+#define WGAMD_GCN_ADD_SELF_LOOPS 1
+#define WGAMD_GCN_RELU 2
+#define WGAMD_GCN_MAX_HOPS 8
+int wgamd_gcn_layer_supported(int F, int N);
+wholememory_error_code_t wgamd_gcn_layer_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx, int F,
+                                             const void* src_ids, wholememory_dtype_t src_ids_dtype, const int64_t* self_rows,
+                                             const float* edge_weight, const float* dinv_src, const float* dinv_dst, float fill,
+                                             const float* w, int64_t ldw, int N, const float* bias, int flags, float* out,
+                                             int64_t ldo, void* stream);
+wholememory_error_code_t wgamd_gcn_layer_f32_train(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx,
+                                                   int F, const void* src_ids, wholememory_dtype_t src_ids_dtype,
+                                                   const int64_t* self_rows, const float* edge_weight, const float* dinv_src,
+                                                   const float* dinv_dst, float fill, const float* w, int64_t ldw, int N,
+                                                   const float* bias, int flags, float* out, int64_t ldo, float* agg_out,
+                                                   int64_t ld_agg, void* stream);
+wholememory_error_code_t wgamd_gcn_aggregate_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx,
+                                                 int F, const void* src_ids, wholememory_dtype_t src_ids_dtype,
+                                                 const int64_t* self_rows, const float* edge_weight, const float* dinv_src,
+                                                 const float* dinv_dst, float fill, int flags, float* out, int64_t ldo,
+                                                 void* stream);
+/* dinv = deg^-1/2 (0 where deg == 0) of the destination rows of up to WGAMD_GCN_MAX_HOPS hops in ONE launch: deg_i = the
+ * weights of row i's edges (loop edges excluded and loopw_i added when add_self_loops, as above).  Row i of hop h goes to
+ * dinv[out_base[h] + i], or to dinv[self_rows[h][i]] when out_base[h] < 0; indices outside [0, n_out) are skipped, entries
+ * no row reaches are left as they are.  The arrays of pointers / counts are host arrays of n_hops entries (edge_weight:
+ * nullable, or an array of nullable pointers). */
+wholememory_error_code_t wgamd_gcn_degrees_f32(int n_hops, const int* const* row_ptr, const int* const* col,
+                                               const int64_t* const* self_rows, const float* const* edge_weight,
+                                               const int64_t* n_rows, const int64_t* out_base, float fill, int add_self_loops,
+                                               float* dinv, int64_t n_out, void* stream);
+/* Weight gradient of the GCN layer over one hop: dZ = grad_out masked by act_out > 0 (act_out nullable = no activation),
+ *   grad_w[n, f] (+)= sum_i dZ[i, n] agg[i, f]        grad_bias[n] (+)= sum_i dZ[i, n]        (grad_bias nullable)
+ * F, N <= 256.  Split-K over row ranges on fp32 MFMA; partial sums (workspace: wgamd_gcn_wgrad_workspace_bytes bytes) added
+ * in workgroup order — no atomics, the same bits from run to run. */
+size_t wgamd_gcn_wgrad_workspace_bytes(int64_t n_rows, int F, int N);
+wholememory_error_code_t wgamd_gcn_wgrad_f32(const float* agg, int64_t ld_agg, int64_t n_rows, int F, const float* grad_out,
+                                             int64_t ldg, const float* act_out, int64_t ld_act, int N, float* grad_w,
+                                             float* grad_bias, int accumulate, void* workspace, size_t workspace_bytes,
+                                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
