@@ -173,6 +173,7 @@ class CallGroup:
             hops.append(HopGraph(res.offsets[k][:n_f + 1], col[:n_e], self_rows))
         lg = LayerGraph(hops)
         lg._keep = (seg_tab, seg_base)
+        lg.num_group_edges = self.num_edges       # (a per-edge attribute of the group covers every hop; this layer reads a prefix)
         me = weakref.ref(self)        # (the graph is cached on the group: no reference cycle back to it)
         lg.degree_source = lambda: me()._degree_source(layer)
         self._layers[layer] = lg
@@ -221,6 +222,25 @@ class CallGroup:
     @property
     def e_id(self) -> torch.Tensor:
         return self._coo()[1]
+
+    def edge_attr(self, name: str, group_name=None) -> torch.Tensor:
+        """A stored edge attribute for every sampled edge, hop-major — ``feature_store[group, name, None][e_id]`` — gathered
+        through the hops' CSR slots (``edge_gid`` -> ``graph.edge_id`` -> attribute) without building ``edge_index``.  Hop k's
+        edges are in the order of its ``layer_graph`` hop (CSR slot order), so the result is what ``RGCNConv`` takes as
+        ``edge_type`` for every layer."""
+        self._wait()
+        if group_name is None:
+            names = sorted({a.group_name for a in self._fs.get_all_tensor_attrs()
+                            if a.attr_name == name and isinstance(a.group_name, tuple)}, key=str)
+            if len(names) != 1:
+                raise KeyError(f"edge attribute {name!r}: found in groups {names}")
+            group_name = names[0]
+        t = self._fs[group_name, name, None]
+        res = self._res
+        g = torch.cat([res.edge_gid[k][:self._n_edges[k]] for k in range(self.hops)])
+        if self._graph.edge_id is not None:
+            g = self._graph.edge_id[g]
+        return t[g]
 
     @property
     def num_sampled_edges(self) -> List[int]:

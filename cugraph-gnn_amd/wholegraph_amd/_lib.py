@@ -292,6 +292,15 @@ SYMBOLS = {
     "wgamd_gcn_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "wgamd_gcn_wgrad_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p,
                                     c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    # RGCN layer (wg_rgcn.hip)
+    "wgamd_rgcn_layer_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "wgamd_rgcn_edge_coef": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "wgamd_rgcn_layer_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64,
+                                     c_void_p]),
+    "wgamd_rgcn_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "wgamd_rgcn_wgrad_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                     c_int, c_void_p, c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "wgamd_bias_act_rows_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "wgamd_gat_transform_heads_supported": (c_int, [c_int, c_int, c_int]),
     "wgamd_gat_transform_weight_bytes": (c_size_t, [c_int, c_int, c_int]),

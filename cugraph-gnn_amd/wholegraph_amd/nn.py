@@ -1752,6 +1752,407 @@ class GCNConv(torch.nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# RGCN (torch_geometric.nn.RGCNConv / FastRGCNConv; the model of the reference's cugraph-pyg example
+# rgcn_link_class_mnmg.py) — csrc/wg_rgcn.hip
+# ---------------------------------------------------------------------------------------------------------------------
+_RGCN_PAIRS_PER_ITEM_MIN, _RGCN_MAX_ITEMS = 256, 1024
+
+
+def rgcn_layer_supported(F_: int, N: int, B: int, has_root: bool = True) -> bool:
+    """Shapes of the one-kernel RGCN layer (``wgamd_rgcn_layer_f32``): F % 4 == 0, N <= 256, (B + root) F <= 1024."""
+    return bool(L.lib().wgamd_rgcn_layer_supported(int(F_), int(N), int(B), int(bool(has_root))))
+
+
+def _nonempty(t, dtype):
+    """``t``, or a one-element buffer when ``t`` is empty (the kernels take no null pointer for a hop's edge arrays)."""
+    return t if t.numel() > 0 else torch.zeros(1, dtype=dtype, device=t.device)
+
+
+_RGCN_LONG_ROW = 4096      # rows longer than this count relations by a sort (the ballot count is quadratic in the degree)
+
+
+def _rgcn_check_types(edge_type, R: int, n_edges: int, device):
+    """Refuse relation ids of the wrong type, device, count or range (ValueError) — the range once per tensor version: the
+    kernels never read ids from another device nor index with one outside [0, R), and this is where the caller learns of it."""
+    if not torch.is_tensor(edge_type) or edge_type.dtype not in (torch.int32, torch.int64) or edge_type.dim() != 1:
+        raise ValueError("RGCNConv: edge_type must be a 1-D int32 or int64 tensor")
+    if edge_type.device != torch.device(device):
+        raise ValueError("RGCNConv: edge_type is on %s, the graph on %s" % (edge_type.device, torch.device(device)))
+    if edge_type.shape[0] != n_edges:
+        raise ValueError("RGCNConv: edge_type has %d entries for %d edges" % (edge_type.shape[0], n_edges))
+    key = (edge_type.data_ptr(), edge_type._version, edge_type.shape[0], int(R))
+    if getattr(edge_type, "_wgamd_rgcn_checked", None) == key:
+        return
+    if edge_type.numel() > 0 and bool(((edge_type < 0) | (edge_type >= R)).any()):
+        raise ValueError("RGCNConv: a relation id lies outside [0, %d)" % R)
+    edge_type._wgamd_rgcn_checked = key
+
+
+def rgcn_edge_coef(row_ptr, edge_type, R: int, mean: bool = True, long_rows: bool = False):
+    """Per-edge ``(rel int32, coef float32)`` of one hop (``wgamd_rgcn_edge_coef``, one launch): ``coef[e]`` = 1 / the number of
+    edges of e's destination row with e's relation (``mean``), else 1.  ``edge_type`` (int32 / int64, ids in [0, R), on the
+    graph's device) is in CSR order.  ``long_rows``: the hop has rows of more than ``_RGCN_LONG_ROW`` edges (a COO or CSR
+    graph over a whole power-law graph): the counts come from one sort of (row, relation) keys instead."""
+    assert row_ptr.dtype == torch.int32 and row_ptr.is_cuda and row_ptr.is_contiguous()
+    assert edge_type.device == row_ptr.device, "edge_type must be on the graph's device"
+    E, dev = edge_type.shape[0], row_ptr.device
+    et = edge_type.contiguous()
+    if long_rows and E > 0:
+        rel = et.to(torch.int32)
+        if not mean:
+            return rel, torch.ones(E, dtype=torch.float32, device=dev)
+        n = row_ptr.shape[0] - 1
+        row = torch.repeat_interleave(torch.arange(n, device=dev), (row_ptr[1:] - row_ptr[:-1]).long(), output_size=E)
+        _, inv, cnt = torch.unique(row * R + et.long(), return_inverse=True, return_counts=True)
+        return rel, 1.0 / cnt.to(torch.float32)[inv]
+    rel = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
+    coef = torch.empty(max(E, 1), dtype=torch.float32, device=dev)
+    if E > 0:
+        L.check(L.lib().wgamd_rgcn_edge_coef(row_ptr.data_ptr(), row_ptr.shape[0] - 1, et.data_ptr(), torch_dtype_to_wm(et.dtype),
+                                             int(R), int(bool(mean)), rel.data_ptr(), coef.data_ptr(), get_stream()),
+                "wgamd_rgcn_edge_coef")
+    return rel[:E], coef[:E]
+
+
+def rgcn_layer_forward(row_ptr, col, x, self_rows, rel, coef, wt, comp, B: int, has_root: bool, bias=None, relu=False, src_ids=None,
+                       out=None):
+    """A whole RGCN layer over one hop in ONE kernel (``wgamd_rgcn_layer_f32``, include/wgamd_ext.h): ``wt`` is the stacked weight
+    transposed, [N, (B + root) F] (``_rgcn_stacked``); ``comp`` [R, B], or None for the identity (B = R)."""
+    _check_csr(row_ptr, col)
+    n_rows, F_, N = row_ptr.shape[0] - 1, x.shape[1], wt.shape[0]
+    assert x.dtype == torch.float32 and x.stride(1) == 1 and wt.dtype == torch.float32 and wt.stride(1) == 1
+    assert self_rows is None or (self_rows.dtype == torch.int64 and self_rows.is_contiguous())
+    assert rel.dtype == torch.int32 and coef.dtype == torch.float32 and rel.shape[0] == col.shape[0] == coef.shape[0]
+    if out is None:
+        out = torch.empty((n_rows, N), dtype=torch.float32, device=row_ptr.device)
+    assert out.shape == (n_rows, N) and out.stride(1) == 1
+    ids_ptr, ids_dt = _gcn_args(x, src_ids)
+    L.check(L.lib().wgamd_rgcn_layer_f32(
+        row_ptr.data_ptr(), _nonempty(col, torch.int32).data_ptr(), n_rows, x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt,
+        _ptr(self_rows), _nonempty(rel, torch.int32).data_ptr(), _nonempty(coef, torch.float32).data_ptr(), _ptr(comp), int(B),
+        int(bool(has_root)), wt.data_ptr(), wt.stride(0), N, _ptr(bias), int(bool(relu)), out.data_ptr(), out.stride(0),
+        get_stream()), "wgamd_rgcn_layer_f32")
+    return out
+
+
+def rgcn_wgrad(x, pair_src, pair_dst, pair_coef, seg, n_seg: int, grad, src_ids=None):
+    """``M[s] = sum_{pairs p of segment s} pair_coef[p] X[pair_src[p]]^T grad[pair_dst[p]]`` -> float32 [n_seg, F, N]
+    (``wgamd_rgcn_wgrad_f32``): one stable sort of the pairs by segment, work items of at most S pairs of one segment, partial
+    sums added in item order — the same bits from run to run."""
+    F_, N, P, dev = x.shape[1], grad.shape[1], pair_src.shape[0], grad.device
+    assert grad.dtype == torch.float32 and grad.stride(1) == 1 and x.stride(1) == 1
+    M = torch.empty((n_seg, F_, N), dtype=torch.float32, device=dev)
+    order = torch.sort(seg, stable=True).indices
+    ps, pd, pc = pair_src[order].contiguous(), pair_dst[order].contiguous(), pair_coef[order].contiguous()
+    S = max(_RGCN_PAIRS_PER_ITEM_MIN, (-(-P // _RGCN_MAX_ITEMS) + 3) // 4 * 4)
+    cnt = torch.bincount(seg, minlength=n_seg)
+    seg_ptr = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
+    item_start = torch.zeros(n_seg + 1, dtype=torch.int64, device=dev)
+    seg_ptr[1:] = torch.cumsum(cnt, 0)
+    item_start[1:] = torch.cumsum((cnt + S - 1) // S, 0)
+    max_items = -(-P // S) + n_seg if P > 0 else 0
+    ws = torch.empty(max(int(L.lib().wgamd_rgcn_wgrad_workspace_bytes(max_items, F_, N)), 4), dtype=torch.uint8, device=dev)
+    ids_ptr, ids_dt = _gcn_args(x, src_ids)
+    L.check(L.lib().wgamd_rgcn_wgrad_f32(
+        x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt, _nonempty(ps, torch.int64).data_ptr(), _nonempty(pd, torch.int64).data_ptr(),
+        _nonempty(pc, torch.float32).data_ptr(), grad.data_ptr(), grad.stride(0), N, item_start.data_ptr(), seg_ptr.data_ptr(),
+        n_seg, S, max_items, M.data_ptr(), ws.data_ptr(), ws.numel(), get_stream()), "wgamd_rgcn_wgrad_f32")
+    return M
+
+
+def _rgcn_stacked(weight, root, Nq=None):
+    """The kernel's transposed stacked weight.  Forward (``Nq`` None): [N, (B + root) F] with column b F + f = basis_b[f, :].
+    Input gradient: [F, (B + root) Nq] with column b Nq + n = basis_b[:, n] (the rows of basis_b^T), N zero-padded to Nq."""
+    w = weight.detach()
+    B, F_, N = w.shape
+    r = None if root is None else root.detach()
+    if Nq is None:
+        parts = [w.reshape(B * F_, N)] + ([] if r is None else [r])
+        return torch.cat(parts).t().contiguous()
+    if Nq != N:
+        w = torch.nn.functional.pad(w, (0, Nq - N))
+        r = None if r is None else torch.nn.functional.pad(r, (0, Nq - N))
+    parts = [w.permute(1, 0, 2).reshape(F_, B * Nq)] + ([] if r is None else [r])
+    return torch.cat(parts, 1).contiguous()
+
+
+def _rgcn_transposed(hop: HopGraph, n_src: int, rel, coef):
+    """``(row_ptr_t, col_t, self_t, rel_t, coef_t)`` of a hop seen from its input rows: the source-major CSR (hop order inside a
+    source row: deterministic sums), ``self_t[j]`` = the destination row that is input row j itself (-1: none), and the edge
+    arrays permuted alike."""
+    dev = hop.row_ptr.device
+    if hop.col.shape[0] > 0:
+        row_ptr_t, perm, _, col_t = _csr_transpose(hop.row_ptr, hop.col, n_src, want_perm=True, want_col_t=True)
+        p = perm.long()
+        rel_t, coef_t = rel[p].contiguous(), coef[p].contiguous()
+    else:
+        row_ptr_t, col_t, rel_t, coef_t = torch.zeros(n_src + 1, dtype=torch.int32, device=dev), hop.col, rel, coef
+    self_t = torch.full((n_src,), -1, dtype=torch.int64, device=dev)
+    self_t[hop.self_rows] = torch.arange(hop.n_rows, dtype=torch.int64, device=dev)
+    return row_ptr_t, col_t, self_t, rel_t, coef_t
+
+
+class _RgcnLayer(torch.autograd.Function):
+    """The one-kernel RGCN layer over a ``LayerGraph`` (one ``wgamd_rgcn_layer_f32`` launch per hop); nothing is kept but the
+    per-edge coefficients and the output.  Backward: ``wgamd_rgcn_wgrad_f32`` once over every hop's (source, destination)
+    pairs segmented by relation, the root's self pairs as segment R (dW = M[:R], or dbasis = comp^T M[:R] and dcomp = M[:R]
+    basis^T; droot = M[R]) and, when the input rows need a gradient, the layer kernel over every hop's transpose with
+    [basis_b^T; root^T] as the weight."""
+
+    @staticmethod
+    def forward(ctx, src, weight, comp, root, bias, conv, graph, coefs, ids, relu, n_src):
+        B, F_, N = weight.shape
+        out = torch.empty((graph.n_rows, N), dtype=torch.float32, device=weight.device)
+        wt = _rgcn_stacked(weight, root)
+        c = None if comp is None else comp.detach().contiguous()
+        b = None if bias is None else bias.detach()
+        at = 0
+        for h, (rel, coef) in zip(graph.hops, coefs):
+            n = h.n_rows
+            if n > 0:
+                rgcn_layer_forward(h.row_ptr, h.col, src, h.self_rows, rel, coef, wt, c, B, root is not None, b, relu=relu, src_ids=ids,
+                                   out=out[at:at + n])
+            at += n
+        if any(ctx.needs_input_grad[:5]):
+            ctx.save_for_backward(weight, comp, root, out)
+            ctx.src, ctx.ids, ctx.graph, ctx.coefs, ctx.relu, ctx.n_src, ctx.R = src, ids, graph, coefs, relu, n_src, conv.num_relations
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        weight, comp, root, out = ctx.saved_tensors
+        B, F_, N = weight.shape
+        R, dev = ctx.R, g.device
+        need_x, need_w, need_c, need_r, need_b = ctx.needs_input_grad[:5]
+        gz = g.contiguous().float()
+        if ctx.relu:
+            gz = torch.ops.aten.threshold_backward(gz, out, 0)
+        gx = gw = gc = gr = gb = None
+        if need_w or need_c or need_r:
+            ps, pd, pc, sg, at = [], [], [], [], 0
+            for h, (rel, coef) in zip(ctx.graph.hops, ctx.coefs):
+                n, E = h.n_rows, h.col.shape[0]
+                rows = torch.arange(at, at + n, dtype=torch.int64, device=dev)
+                ps.append(h.col.long())
+                pd.append(torch.repeat_interleave(rows, (h.row_ptr[1:] - h.row_ptr[:-1]).long(), output_size=E))
+                pc.append(coef)
+                sg.append(rel.long())
+                if root is not None:
+                    ps.append(h.self_rows)
+                    pd.append(rows)
+                    pc.append(torch.ones(n, dtype=torch.float32, device=dev))
+                    sg.append(torch.full((n,), R, dtype=torch.int64, device=dev))
+                at += n
+            M = rgcn_wgrad(ctx.src, torch.cat(ps), torch.cat(pd), torch.cat(pc), torch.cat(sg), R + (root is not None), gz,
+                           src_ids=ctx.ids)
+            if comp is None:
+                gw = M[:R] if need_w else None
+            else:
+                Mr = M[:R].reshape(R, F_ * N)
+                gw = (comp.detach().t() @ Mr).view(B, F_, N) if need_w else None
+                gc = Mr @ weight.detach().reshape(B, F_ * N).t() if need_c else None
+            gr = M[R] if need_r else None
+        if need_b:
+            gb = gz.sum(0)
+        if need_x:
+            Nq = (N + 3) // 4 * 4
+            w_bwd = _rgcn_stacked(weight, root, Nq)
+            gq = gz if Nq == N else torch.nn.functional.pad(gz, (0, Nq - N))
+            c = None if comp is None else comp.detach().contiguous()
+            at = 0
+            for h, (rel, coef) in zip(ctx.graph.hops, ctx.coefs):
+                n = h.n_rows
+                if n > 0:
+                    row_ptr_t, col_t, self_t, rel_t, coef_t = _rgcn_transposed(h, ctx.n_src, rel, coef)
+                    gh = rgcn_layer_forward(row_ptr_t, col_t, gq[at:at + n], self_t, rel_t, coef_t, w_bwd, c, B, root is not None)
+                    gx = gh if gx is None else gx.add_(gh)
+                at += n
+            if gx is None:
+                gx = torch.zeros((ctx.n_src, F_), dtype=torch.float32, device=dev)
+        ctx.src = ctx.coefs = None
+        return gx, gw, gc, gr, gb, None, None, None, None, None, None
+
+
+def _rgcn_library_ops(conv, x, lg: LayerGraph, coefs, relu: bool):
+    """The layer composed of library ops under autograd, from the same per-edge coefficients: the route of shapes outside the
+    one-kernel layer's domain (correctness, not speed).  Per hop: the per-relation sums H [n, R, F] (or per-basis, [n, B, F],
+    when there are fewer bases than relations), then one GEMM against the stacked weight."""
+    R, F_, N = conv.num_relations, conv.in_channels, conv.out_channels
+    by_basis = conv.comp is not None and conv.num_bases < R
+    if by_basis:
+        Wk, K = conv.weight, conv.num_bases
+    else:
+        Wk, K = conv._relation_weights(), R
+    outs = []
+    for h, (rel, coef) in zip(lg.hops, coefs):
+        n, E = h.n_rows, h.col.shape[0]
+        dst = torch.repeat_interleave(torch.arange(n, device=x.device), (h.row_ptr[1:] - h.row_ptr[:-1]).long(), output_size=E)
+        xs = x[h.col.long()]
+        if by_basis:
+            w_e = coef.unsqueeze(1) * conv.comp[rel.long()]                   # [E, B]
+            H = x.new_zeros((n, K, F_)).index_add(0, dst, w_e.unsqueeze(2) * xs.unsqueeze(1))
+        else:
+            H = x.new_zeros((n * K, F_)).index_add(0, dst * K + rel.long(), coef.unsqueeze(1) * xs)
+        o = H.reshape(n, K * F_) @ Wk.reshape(K * F_, N)
+        if conv.root is not None:
+            o = o + x[h.self_rows] @ conv.root
+        outs.append(o)
+    out = torch.cat(outs) if outs else x.new_zeros((0, N))
+    if conv.bias is not None:
+        out = out + conv.bias
+    return torch.relu(out) if relu else out
+
+
+class RGCNConv(torch.nn.Module):
+    """PyG ``RGCNConv`` (``FastRGCNConv`` is the same class): ``x'_i = sum_r agg_{j in N_r(i)} x_j W_r + x_i root + bias``, with
+    ``agg`` the per-relation mean (``aggr="mean"``) or sum (``"add"`` / ``"sum"``) and, with ``num_bases``, ``W_r = sum_b
+    comp[r, b] weight[b]``.  Parameters as PyG names them (``weight`` [B or R, in, out], ``comp`` [R, B], ``root`` [in, out],
+    ``bias``; glorot, bias zeros), so a PyG ``state_dict`` loads.
+
+    ``forward(x, graph, edge_type, act=None)``: ``graph`` = a COO ``edge_index`` with ``edge_type`` [E] (the ``for batch in
+    loader`` loop of rgcn_link_class_mnmg.py with ``rel[batch.e_id]``; output rows = x's rows), a ``[csr_row_ptr, csr_col_ind]``
+    pair with ``edge_type`` in CSR order (destinations = the first rows of x), or a call group's ``LayerGraph`` with ``x`` a
+    tensor or ``LazyRows`` and ``edge_type`` hop-major in ``CallGroup.e_id`` order (``CallGroup.edge_attr``; every layer takes
+    the same tensor and reads the prefix of its hops).  The layer — feature fetch, per-relation mean, the product with the
+    stacked weight, bias, optional ``act="relu"`` — is ONE kernel per hop (``wgamd_rgcn_layer_f32``) for F % 4 == 0, N <= 256,
+    (B + root) F <= 1024 (B = R without bases), and the input gradient is the same kernel over the hop's transpose.  When x
+    needs a gradient the transposed shape (F' = N rounded up to 4, N' = F) must fit as well; if either does not, the WHOLE
+    layer, forward included, runs library ops over the same per-edge coefficients (correct, not fast, not bitwise
+    reproducible).  ``edge_type`` must be on the graph's device; ids outside [0, R) or a wrong count raise ValueError."""
+
+    def __init__(self, in_channels: int, out_channels: int, num_relations: int, num_bases: Optional[int] = None,
+                 num_blocks: Optional[int] = None, aggr: str = "mean", root_weight: bool = True, is_sorted: bool = False,
+                 bias: bool = True):
+        super().__init__()
+        if num_blocks is not None:
+            raise NotImplementedError("RGCNConv: num_blocks (block-diagonal decomposition) is not supported")
+        if aggr not in ("mean", "add", "sum"):
+            raise ValueError("RGCNConv: aggr must be 'mean', 'add' or 'sum' (got %r)" % (aggr,))
+        if num_relations < 1 or (num_bases is not None and num_bases < 1):
+            raise ValueError("RGCNConv: num_relations and num_bases must be positive")
+        self.in_channels, self.out_channels, self.num_relations = in_channels, out_channels, num_relations
+        self.num_bases, self.num_blocks, self.aggr, self.is_sorted = num_bases, num_blocks, aggr, is_sorted
+        if num_bases is not None:
+            self.weight = torch.nn.Parameter(torch.empty(num_bases, in_channels, out_channels))
+            self.comp = torch.nn.Parameter(torch.empty(num_relations, num_bases))
+        else:
+            self.weight = torch.nn.Parameter(torch.empty(num_relations, in_channels, out_channels))
+            self.register_parameter("comp", None)
+        if root_weight:
+            self.root = torch.nn.Parameter(torch.empty(in_channels, out_channels))
+        else:
+            self.register_parameter("root", None)
+        if bias:
+            self.bias = torch.nn.Parameter(torch.empty(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for p in (self.weight, self.comp, self.root):     # PyG's glorot: U(-a, a), a = sqrt(6 / (size(-2) + size(-1)))
+            if p is not None:
+                a = math.sqrt(6.0 / (p.size(-2) + p.size(-1)))
+                torch.nn.init.uniform_(p, -a, a)
+        if self.bias is not None:
+            torch.nn.init.zeros_(self.bias)
+
+    @property
+    def _b_eff(self) -> int:
+        return self.num_bases if self.num_bases is not None else self.num_relations
+
+    def _relation_weights(self):
+        """W_r [R, in, out] (autograd through comp and weight)."""
+        if self.comp is None:
+            return self.weight
+        return (self.comp @ self.weight.reshape(self.num_bases, -1)).view(self.num_relations, self.in_channels, self.out_channels)
+
+    def _coefs(self, lg: LayerGraph, edge_type):
+        """Per hop ``(rel, coef)`` from the hop-major ``edge_type``: hop k reads the slice after the edges of hops < k."""
+        mean = self.aggr == "mean"
+        key = (edge_type._version, self.num_relations, mean)
+        cache = getattr(lg, "_rgcn_coefs", None)
+        if cache is not None and cache[0] is edge_type and cache[1] == key:     # (the tensor itself: a new one at a reused
+            return cache[2]                                                     #  address is not the old one)
+        coefs, at = [], 0
+        for h in lg.hops:
+            E = h.col.shape[0]
+            coefs.append(rgcn_edge_coef(h.row_ptr, edge_type[at:at + E], self.num_relations, mean,
+                                        long_rows=getattr(h, "_rgcn_long_rows", False)))
+            at += E
+        lg._rgcn_coefs = (edge_type, key, coefs)
+        return coefs
+
+    def _forward_layer(self, x, lg: LayerGraph, edge_type, act=None):
+        assert act in (None, "relu"), "act: None or 'relu'"
+        relu = act == "relu"
+        lazy = isinstance(x, LazyRows)
+        src = x.table if lazy else x
+        n_src = len(x) if lazy else x.shape[0]
+        F_, N = self.in_channels, self.out_channels
+        if x.shape[1] != F_:
+            raise ValueError("RGCNConv: x has %d features, the layer takes %d" % (x.shape[1], F_))
+        n_edges = sum(int(h.col.shape[0]) for h in lg.hops)
+        # a call group's layer graph: edge_type covers the whole group (every layer reads the prefix of its hops); any other
+        # layer graph: exactly its hops' edges
+        total = getattr(lg, "num_group_edges", None)
+        _rgcn_check_types(edge_type, self.num_relations, total if total is not None else n_edges,
+                          lg.hops[0].row_ptr.device if lg.hops else src.device)
+        grad_on = torch.is_grad_enabled()
+        if lazy and grad_on and getattr(src, "requires_grad", False):
+            raise NotImplementedError("gradient w.r.t. a feature table read through ids (LazyRows): trainable node "
+                                      "embeddings go through wholegraph_amd.embedding, or pass x = emb[n_id]")
+        coefs = self._coefs(lg, edge_type)
+        has_root, B = self.root is not None, self._b_eff
+        need_x = grad_on and not lazy and x.requires_grad
+        Nq = (N + 3) // 4 * 4
+        if (rgcn_layer_supported(F_, N, B, has_root) and (not need_x or rgcn_layer_supported(Nq, F_, B, has_root))
+                and src.dtype == torch.float32 and src.is_cuda and src.stride(1) == 1 and src.stride(0) % 4 == 0
+                and src.data_ptr() % 16 == 0):
+            return _RgcnLayer.apply(src, self.weight, self.comp, self.root, self.bias, self, lg, coefs, x.ids if lazy else None,
+                                    relu, n_src)
+        xd = x.materialize() if lazy else x
+        return _rgcn_library_ops(self, xd.float(), lg, coefs, relu)
+
+    def forward(self, x, graph, edge_type, act=None):
+        if _capturing():
+            # (the per-edge coefficients and transposes of a layer graph are cached in Python against the graph object: a
+            #  replay would keep using those of the capture)
+            raise RuntimeError("wholegraph_amd.nn.RGCNConv is not supported under HIP-graph capture (loader.PerBatchStep): its "
+                               "per-graph caches are not capture-safe; SAGEConv layers are")
+        if x is None or (torch.is_tensor(x) and not x.is_floating_point()):
+            raise ValueError("RGCNConv: featureless input (x = None or node indices) is not supported; pass node features")
+        if isinstance(graph, HeteroLayerGraph):
+            raise NotImplementedError("RGCNConv over a heterogeneous call group's layer graph is not supported")
+        if isinstance(graph, LayerGraph):
+            return self._forward_layer(x, graph, edge_type, act)
+        if isinstance(x, LazyRows):
+            x = x.materialize()
+        n_src = x.shape[0]
+        if isinstance(graph, (tuple, list)):
+            row_ptr, col = graph[0], graph[1]          # [csr_row_ptr, csr_col_ind]: destinations = the first rows of x
+            _check_csr(row_ptr, col)
+            _rgcn_check_types(edge_type, self.num_relations, col.shape[0], row_ptr.device)
+            et = edge_type
+        else:
+            _rgcn_check_types(edge_type, self.num_relations, graph.shape[1], graph.device)
+            src_ids, dst = graph[0], graph[1]
+            order = torch.sort(dst, stable=True).indices  # destination-major, edge order kept inside a destination
+            col = src_ids[order].to(torch.int32).contiguous()
+            et = edge_type[order].contiguous()
+            et._wgamd_rgcn_checked = (et.data_ptr(), et._version, et.shape[0], int(self.num_relations))
+            row_ptr = torch.zeros(n_src + 1, dtype=torch.int32, device=dst.device)
+            row_ptr[1:] = torch.cumsum(torch.bincount(dst, minlength=n_src), 0)
+        n_dst = row_ptr.shape[0] - 1
+        hop = HopGraph(row_ptr, col, _arange(n_dst, x.device))
+        if n_dst > 0:                                  # (these paths may synchronise: the range check above does)
+            hop._rgcn_long_rows = int((row_ptr[1:] - row_ptr[:-1]).max()) > _RGCN_LONG_ROW
+        return self._forward_layer(x, LayerGraph([hop]), et, act)
+
+
+FastRGCNConv = RGCNConv
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # heterogeneous layers over a call group (BASELINE configs[4]: ogbn-mag-like 2-hop walk + HeteroConv{GATConv})
 # ---------------------------------------------------------------------------------------------------------------------
 _stage_hook = None

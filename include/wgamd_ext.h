@@ -782,6 +782,39 @@ wholememory_error_code_t wgamd_gcn_wgrad_f32(const float* agg, int64_t ld_agg, i
                                              float* grad_bias, int accumulate, void* workspace, size_t workspace_bytes,
                                              void* stream);
 
+/* ---- RGCN layer (csrc/wg_rgcn.hip): torch_geometric.nn.RGCNConv / FastRGCNConv over a sampled hop -----------------------------
+ * The model of the reference's cugraph-pyg example rgcn_link_class_mnmg.py:
+ *   C_b[i]  = sum_{e = (j -> i)} coef[e] comp[rel[e], b] X[j]      (b < B; comp null = the identity, B = R)
+ *   out[i]  = act( sum_b C_b[i] @ basis_b  +  [has_root] X[self_rows[i]] @ root  +  bias )
+ * X[r] = x[src_ids ? src_ids[r] : r] (INT, INT64 or WGAMD_IDS_BYTE_OFFSETS); self_rows[i] < 0: no root term (a transposed hop's
+ * source-only rows).  The weight goes in transposed and stacked: wt [N, ldw] with wt[n, b F + f] = basis_b[f, n] and
+ * wt[n, B F + f] = root[f, n].  Sums run in CSR order: run-to-run deterministic.  Domain: wgamd_rgcn_layer_supported
+ * (F % 4 == 0, N <= 256, K = (B + has_root) F <= 1024: one float4 of the C row per thread, a 16 x K fp32 tile in LDS);
+ * x / wt rows 16-B aligned.  The product runs on the exact fp32 matrix pipe (v_mfma_f32_16x16x4_f32).
+ * wgamd_rgcn_edge_coef: per edge of a hop, rel[e] = edge_type[e] and coef[e] = 1 / (edges of row i with that relation) when
+ * mean, else 1; an id outside [0, R) gets rel 0 and coef 0 (callers refuse such ids; the kernels never index with them). */
+int wgamd_rgcn_layer_supported(int F, int N, int B, int has_root);
+wholememory_error_code_t wgamd_rgcn_edge_coef(const int* row_ptr, int64_t n_rows, const void* edge_type,
+                                              wholememory_dtype_t edge_type_dtype, int R, int mean, int* rel, float* coef,
+                                              void* stream);
+wholememory_error_code_t wgamd_rgcn_layer_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx, int F,
+                                              const void* src_ids, wholememory_dtype_t src_ids_dtype, const int64_t* self_rows,
+                                              const int* rel, const float* coef, const float* comp, int B, int has_root,
+                                              const float* wt, int64_t ldw, int N, const float* bias, int relu, float* out,
+                                              int64_t ldo, void* stream);
+/* Relation-segmented weight gradient: M[s] (n_seg x [F, N], row-major) = sum over pairs p of segment s of
+ *   pair_coef[p] X[pair_src[p]]^T grad[pair_dst[p]]
+ * with the pairs sorted by segment (seg_ptr [n_seg + 1]: pair range of each segment) and cut into work items of at most
+ * pairs_per_item pairs of one segment (item_start [n_seg + 1]: first item of each segment, on the device; max_items >= the
+ * total, the launch's grid).  Item partials (workspace: wgamd_rgcn_wgrad_workspace_bytes) are added in item order — no
+ * atomics, the same bits from run to run.  N <= 256, pairs_per_item % 4 == 0. */
+size_t wgamd_rgcn_wgrad_workspace_bytes(int64_t max_items, int F, int N);
+wholememory_error_code_t wgamd_rgcn_wgrad_f32(const float* x, int64_t ldx, int F, const void* src_ids,
+                                              wholememory_dtype_t src_ids_dtype, const int64_t* pair_src, const int64_t* pair_dst,
+                                              const float* pair_coef, const float* grad, int64_t ldg, int N,
+                                              const int64_t* item_start, const int64_t* seg_ptr, int n_seg, int64_t pairs_per_item,
+                                              int64_t max_items, float* M, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
