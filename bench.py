@@ -18,8 +18,11 @@ collective-free replicated table are measured in the same run and reported under
 pre-flight (`selftest`) sends a known-answer table through the same exchange on every rank and compares bit for bit.
 
 Contract: python bench.py --gpus N --steps K --warmup W   (N>1: launched by torch.distributed.run)
-Prints ONE JSON line on rank 0 with `roofline` (dominant HIP kernel, measured live with HIP
-events on the launch stream) and `cpu_baseline` (the C oracle, OpenMP over host cores, bounded sample).
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline needs: set up, warm up, time the K steps,
+write --dump-outputs, print.  `--full` adds everything else the benchmark measures or checks: the other code paths timed as
+`variants` (and the drop-in loader API), the per-stage HIP-event pass behind `stage_ms_per_call_group` and `roofline` (dominant
+HIP kernel, measured live with HIP events on the launch stream), `cpu_baseline` (the C oracle, OpenMP over host cores, bounded
+sample) and, at N > 1, the other feature placements next to the headline's and the known-answer pre-flight.
 Synthetic data: RMAT (a=.57,b=.19,c=.19) symmetrised + dedup, V=2,449,029, ~123.7 M directed
 edges; features U(-1,1) fp32 [V,100]; random-init weights.
 """
@@ -49,6 +52,8 @@ WORKLOADS = {"products": (V_PRODUCTS, E_UNDIRECTED, 100, 47, [25, 10]),
              "rmat26": (1 << 26, 1 << 29, 256, 64, [15, 10, 5])}
 HIDDEN = 256
 SPMM1, SPMM2 = "spmm1(mean)+self", "spmm2(mean)+self"   # stage labels (layer-1 F = feature dim, layer-j F = HIDDEN)
+FETCH_DISTINCT = ("distinct rows of the call group gathered ONCE (list de-duplicated on the walk stream: "
+                  "wgamd_unique_bounded_live), layer 1 reads them through the inverse index")
 
 
 def spmm_label(j):
@@ -762,8 +767,8 @@ def main():
                          "peer-mapped partitions only (HIP IPC, loads over xGMI in one kernel; single node); auto = both "
                          "(headline: all-to-all)")
     ap.add_argument("--selftest", action="store_true",
-                    help="run the known-answer pre-flight of the feature exchange even on a single-rank communicator (it always "
-                         "runs for partitioned placements at N > 1)")
+                    help="run the known-answer pre-flight of the feature exchange in a plain run, or on a single-rank "
+                         "communicator (with --full it always runs for partitioned placements at N > 1)")
     ap.add_argument("--host-profile", action="store_true",
                     help="print (stderr) where the HOST spends a call group: enqueueing the walk, enqueueing the forward, blocked")
     ap.add_argument("--force-partitioned", action="store_true",
@@ -781,7 +786,11 @@ def main():
     ap.add_argument("--dist-backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for the "
                                                             "one-GPU rehearsal of the N>1 control flow in the tests)")
     ap.add_argument("--share-gpu", action="store_true", help="test aid: every rank uses cuda:0")
-    ap.add_argument("--no-variants", action="store_true", help="skip the extra timed passes of the other code paths")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the other code paths (variants), the per-stage pass and roofline, the CPU "
+                         "baseline and, at N > 1, the other feature placements and the pre-flight (a plain run times the "
+                         "headline alone)")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip the extra timed passes of the other code paths")
     ap.add_argument("--fetch", choices=["distinct", "rows"], default="distinct",
                     help="feature fetch of the headline: 'distinct' (default) gathers every distinct row of a call group once and "
                          "lets layer 1 read through the inverse index; 'rows' gathers x = feat[n_id] row for row (rounds 1-5)")
@@ -790,7 +799,7 @@ def main():
     ap.add_argument("--mag-rels", choices=["all", "r5"], default="all",
                     help="--workload mag: all 8 directed edge types (4 + reverses, ~42 M edges: BASELINE configs[4]) or the six "
                          "that rounds 3-5 ran (no rev_cites / rev_affiliated_with, 35.8 M edges) for round-to-round comparison")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=15.0)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the headline pass computed in its LAST timed step as DIR/<name>.npy "
@@ -801,6 +810,9 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.workload == "mag":
         ap.error("--dump-outputs is implemented for the SAGE workloads (products, papers100m, rmat26), not for mag")
+    if not args.full:
+        # a plain run: the headline alone (no other code paths, no CPU baseline; the rest is gated on args.full below)
+        args.no_variants = args.no_cpu_baseline = True
     relaunch_if_needed(args)
     if args.workload == "mag":
         import bench_mag
@@ -859,6 +871,8 @@ def main():
             placements = part
         else:
             placements = ["replicated"] + part
+    if not args.full:
+        placements = [next(p_ for p_ in HEAD_PREF if p_ in placements)]     # the headline's placement alone
     wm_comm = None
 
     def library_comm():
@@ -1129,11 +1143,13 @@ def main():
                 variants.update(loader_api_variants(row_ptr, col, feat.local_tensor, pipe.convs, order, min(groups, 24), G))
             except Exception as exc:   # a variant must never cost the headline line
                 variants["loader_api"] = {"value": None, "error": repr(exc)[:300]}
-        stage_n = max(10, min(groups, 20))
-        stage_ms, psizes = probe_stages(pipe, head_mode, stage_n)
-        # the BASELINE metric also names the stand-alone SAGEConv SpMM: time it (aggregate kernel + GEMM) when the
-        # headline path runs the layer as one kernel
-        split_ms = probe_stages(pipe, "split", 10)[0] if head_mode != "split" else stage_ms
+        stage_n, stage_ms, psizes, split_ms = 0, None, None, None
+        if args.full:
+            stage_n = max(10, min(groups, 20))
+            stage_ms, psizes = probe_stages(pipe, head_mode, stage_n)
+            # the BASELINE metric also names the stand-alone SAGEConv SpMM: time it (aggregate kernel + GEMM) when the
+            # headline path runs the layer as one kernel
+            split_ms = probe_stages(pipe, "split", 10)[0] if head_mode != "split" else stage_ms
         results[placement] = dict(dt=dt, edges=edges_total, variants=variants, stage_ms=stage_ms, psizes=psizes,
                                   split_ms=split_ms, head_mode=head_mode, stage_n=stage_n, pipe=pipe, feat=feat,
                                   per_rank=per_rank, lazy_pass=lazy_pass, dumped=dumped)
@@ -1152,114 +1168,9 @@ def main():
         head = results[head_name]
         pipe, feat = head["pipe"], head["feat"]
         partitioned = head_name != "replicated"
-        dt, edges_total, variants, stage_ms, psizes, split_ms, head_mode, stage_n = (
-            head[k] for k in ("dt", "edges", "variants", "stage_ms", "psizes", "split_ms", "head_mode", "stage_n"))
-        fused = variants.get("fused_fetch") or variants.get("split_fetch")
-        hop_e = [sum(s[2 * k] for s in psizes) / stage_n for k in range(L)]       # edges per call group, seed hop first
-        hop_u = [sum(s[2 * k + 1] for s in psizes) / stage_n for k in range(L)]   # unique nodes after each hop
-        n_src = hop_u[L - 1]
+        dt, edges_total, head_mode = head["dt"], head["edges"], head["head_mode"]
 
         if rank == 0:
-            # algorithmic bytes per launch; b = id bytes, fp32 features
-            F = FEAT_DIM
-            idb = 4 if id_dtype == torch.int32 else 8
-            n_fetch = (sum(pipe.distinct_rows) / len(pipe.distinct_rows)) if (pipe.dedup and pipe.distinct_rows) else n_src
-            kernels = {"gather": ("row_copy_kernel", n_fetch * ((8 if pipe.dedup else idb) + 2 * 4 * F))}
-            layer1_ids = "int" if pipe.dedup else None    # layer 1 reads the gathered rows through the int32 inverse index
-            spmm_root = {}
-            for j in range(L):
-                k = L - 1 - j
-                fj = pipe.dims[j]
-                n_dst = hop_u[k - 1] if k >= 1 else G * BATCH
-                # STRICT SURVEY §8(d): E(4F+4) + N_dst(4F+8).  The kernel also copies the root row next to the aggregate
-                # (one more row read and written per destination): that term is reported under its own key, never in spmm_GBps
-                kernels[spmm_label(j)] = ("spmm_csr_kernel", hop_e[k] * (4 * fj + 4) + n_dst * (4 * fj + 8))
-                spmm_root[spmm_label(j)] = n_dst * (8 * fj + 8)
-            for j in range(L):   # one-kernel layers: same reads minus the [agg|x_self] round trip, plus the output write
-                k = L - 1 - j
-                fj, nj = pipe.dims[j], pipe.dims[j + 1]
-                n_dst = hop_u[k - 1] if k >= 1 else G * BATCH
-                # (the layer runs at its output width padded to 64 / 128 / 256: 47 classes -> 64 columns)
-                kname = "sage_layer_mfma_kernel" if (nn_mod.sage_layer_fused_precision() == "bf16x3" and nn_mod.L.lib(
-                ).wgamd_sage_layer_bf16x3_supported(fj, nn_mod._padded_width(nj))) else "sage_layer_fused_kernel"
-                kernels["sage_layer%d(fused)" % (j + 1)] = (kname, hop_e[k] * (4 * fj + 4) + n_dst * (4 * fj + 16) + n_dst * 4 * nj)
-            std_shape = G == std_call_group and args.nodes == wv and args.edges == we   # the shape the committed profiles are of
-
-            def roof_entry(st):
-                """The roofline of one stage's kernel: algorithmic bytes over the live HIP-event time (`frac`), over the committed
-                rocprofv3 average (`frac_profiled`), the committed PMC traffic, and for a one-kernel layer its matrix side."""
-                ach = kernels[st][1] / (stage_ms[st] * 1e-3) / 1e9
-                r = {"bound": "hbm", "kernel": kernels[st][0], "stage": st, "achieved": round(ach, 1),
-                     "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBPS, 4),
-                     "traffic": None, "algorithmic_bytes_per_launch": int(kernels[st][1]),
-                     "avg_launch_ms": round(stage_ms[st], 5),
-                     "timing": "HIP events around the launch on the launch stream, one launch per call group of "
-                               f"{G} mini-batches, averaged over {stage_n} call groups"}
-                pref = layer1_ids if st == "sage_layer1(fused)" else ("long" if (st == "gather" and pipe.dedup) else None)
-                if st.startswith("sage_layer") and st != "sage_layer1(fused)":
-                    # a hidden layer reads its input directly (ids type void); rows wider than 128 floats take 64-lane groups
-                    pref = "void,64" if pipe.dims[int(st[len("sage_layer")]) - 1] > 128 else "void"
-                if std_shape:
-                    prof = load_profiled_avg(r["kernel"], args.workload, prefer=pref)
-                    if prof:    # the same algorithmic bytes over the committed profile's average launch duration
-                        r["frac_profiled"] = round(kernels[st][1] / (prof["avg_ns"] * 1e-9) / 1e9 / HBM_PEAK_GBPS, 4)
-                        r["profiled_avg_launch_ms"] = round(prof["avg_ns"] * 1e-6, 5)
-                        r["profiled_source"] = "%s (%d launches, min %.1f us)" % (prof["source"], prof["calls"], prof["min_ns"] * 1e-3)
-                    hit = load_pmc(r["kernel"], workload=args.workload, prefer=pref)
-                    if hit:
-                        r["traffic"] = hit["bytes"]
-                        r["traffic_over_algorithmic"] = round(hit["bytes"] / kernels[st][1], 3)
-                        r["traffic_source"] = hit["source"] + " kernel " + hit["kernel"]
-                if st.startswith("sage_layer"):
-                    # one-kernel layer: HBM-side and MFMA-side work of the same launch
-                    jj = int(st[len("sage_layer")]) - 1
-                    kk = L - 1 - jj
-                    n_dst_ = hop_u[kk - 1] if kk >= 1 else G * BATCH
-                    flops = 2.0 * n_dst_ * 2 * pipe.dims[jj] * pipe.dims[jj + 1]
-                    r["hbm_frac"] = r["frac"]
-                    if r["kernel"] != "sage_layer_mfma_kernel":
-                        tfs = flops / (stage_ms[st] * 1e-3) / 1e12
-                        r["mfma_TFps"], r["mfma_frac"] = round(tfs, 1), round(tfs / MFMA_F32_PEAK_TFPS, 4)
-                        r["mfma_dtype"] = "f32 (v_mfma_f32_16x16x4_f32)"
-                        if r["mfma_frac"] > r["frac"]:
-                            r.update(bound="mfma", achieved=round(tfs, 1), peak=MFMA_F32_PEAK_TFPS, unit="TFLOP/s", frac=r["mfma_frac"])
-                    else:
-                        # 3-way bf16 split of both operands, 6 bf16 MFMA products per fp32 product (fp32 accumulate): the matrix
-                        # work is 6 x flops on the bf16 pipe (2.5 PFLOP/s dense) -> far from binding, the launch is HBM-bound
-                        tfs = 6.0 * flops / (stage_ms[st] * 1e-3) / 1e12
-                        r["mfma_TFps"], r["mfma_frac"] = round(tfs, 1), round(tfs / MFMA_BF16_PEAK_TFPS, 4)
-                        r["mfma_dtype"] = "bf16x3 split (6 v_mfma_f32_32x32x16_bf16 per fp32 product, fp32 accumulate)"
-                return r
-
-            # dominant kernel = the longest stage; the runner-up rides along under `also` (the feature gather and the
-            # one-kernel layer 1 are within a per cent of each other on the products workload: which one leads depends on the box)
-            ranked = sorted((k for k in kernels if k in stage_ms), key=lambda k: -stage_ms[k])
-            dom = ranked[0] if ranked else None
-            roofline = roof_entry(dom) if dom is not None else None
-            if roofline is not None and len(ranked) > 1:
-                roofline["also"] = roof_entry(ranked[1])
-            spmm_gbps = spmm_root_gbps = spmm_pmc = None
-            if SPMM1 in split_ms:
-                spmm_gbps = kernels[SPMM1][1] / (split_ms[SPMM1] * 1e-3) / 1e9
-                spmm_root_gbps = (kernels[SPMM1][1] + spmm_root[SPMM1]) / (split_ms[SPMM1] * 1e-3) / 1e9
-                hit = load_pmc("spmm_csr_kernel", workload=args.workload) if std_shape else None
-                if hit:     # real HBM utilisation of the launch: (2 x FETCH_SIZE + WRITE_SIZE) / time / 8 TB/s
-                    spmm_pmc = {"hbm_util": round(hit["bytes"] / (split_ms[SPMM1] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                                "traffic_bytes_per_launch": hit["bytes"], "source": hit["source"] + " kernel " + hit["kernel"]}
-            cpu = None
-            if not args.no_cpu_baseline and world == 1:   # the CPU baseline is timed at N=1 only (rank 0 owns the host cores)
-                nb = min(2048, order.numel() // BATCH)   # time-bounded inside cpu_baseline (--cpu-budget seconds)
-                cb = order[: nb * BATCH].view(nb, BATCH).to(id_dtype).cpu().numpy()  # same seed stream, one mini-batch at a time
-                if V * FEAT_DIM * 4 > (8 << 30):
-                    # papers100M-scale table: a lazily-zeroed host array of the same shape (only the gathered
-                    # rows' pages are ever touched; values do not matter for the timing)
-                    feat_h = np.zeros((V, FEAT_DIM), dtype=np.float32)
-                elif partitioned:
-                    feat_h = np.random.default_rng(0).random((V, FEAT_DIM), dtype=np.float32) * 2 - 1
-                else:
-                    feat_h = feat.local_tensor.cpu().numpy()
-                weights = [(c.lin_l.weight.cpu(), c.lin_l.bias.cpu(), c.lin_r.weight.cpu()) for c in pipe.convs]
-                cpu = cpu_baseline(row_ptr.cpu().numpy(), col.cpu().numpy(), feat_h, cb, weights, args.cpu_budget)
             wl_name = "RMAT-26" if args.workload == "rmat26" else "ogbn-" + args.workload
             prec = nn_mod.sage_layer_fused_precision() if hasattr(nn_mod, "sage_layer_fused_precision") else "f32"
             out = {
@@ -1291,30 +1202,11 @@ def main():
                 "timed_region_ms": round(dt * 1e3, 2),
                 "timed_call_groups": groups,
                 "ms_per_batch": dt / (groups * G) * 1e3,
-                "edges_per_batch": dict([("hop%d" % (k + 1), hop_e[k] / G) for k in range(L)] + [("unique_nodes", n_src / G)]),
-                "stage_ms_per_call_group": {k: round(v, 5) for k, v in stage_ms.items()},
-                "split_stage_ms_per_call_group": None if split_ms is stage_ms else {k: round(v, 5) for k, v in split_ms.items()},
-                "spmm_GBps": None if spmm_gbps is None else round(spmm_gbps, 1),
-                "spmm_frac_of_hbm_peak": None if spmm_gbps is None else round(spmm_gbps / HBM_PEAK_GBPS, 4),
-                "spmm_accounting": "SURVEY.md §8(d) strict: E(4F+4) + N_dst(4F+8) bytes / HIP-event time of the layer-1 "
-                                   "aggregation launch (effective bandwidth: part of x is served by L2/MALL)",
-                "spmm_with_root_copy_GBps": None if spmm_root_gbps is None else round(spmm_root_gbps, 1),
-                "spmm_hbm_util_pmc": spmm_pmc,
                 "layer_kernel": head_mode,
-                "feature_fetch": ("distinct rows of the call group gathered ONCE (list de-duplicated on the walk stream: "
-                                  "wgamd_unique_bounded_live), layer 1 reads them through the inverse index; %d listed rows -> %d "
-                                  "gathered per call group" % (int(n_src), int(n_fetch))) if pipe.dedup else
-                                 "x = feat[n_id] row for row",
-                # the same pipeline with EVERY listed row gathered (what the reference's loader fetches per mini-batch; the headline of
-                # rounds 1-5), measured in this run — next to `value` at the top level so that neither figure is read without the other
-                "value_row_for_row_fetch": (variants.get("materialised_full") or {}).get("value") if pipe.dedup else None,
-                "fused_fetch_variant": fused,
-                "variants": variants,
-                "roofline": roofline,
-                "cpu_baseline": cpu,
+                "feature_fetch": FETCH_DISTINCT if pipe.dedup else "x = feat[n_id] row for row",
             }
-            if cpu is not None:
-                out["gpu_over_cpu"] = round(out["value"] / cpu["value"], 2)
+            if args.full:
+                out.update(full_fields(head, partitioned))
             if placement_errors:
                 out["placement_errors"] = placement_errors
             if world > 1 or partitioned:
@@ -1329,7 +1221,8 @@ def main():
                            "per_rank_value": [round(e_ / t_, 1) for t_, e_ in pr["per_rank"]]}
                     if pr.get("lazy_pass"):
                         rep["fetch_in_layer"] = pr["lazy_pass"]
-                    if name != "replicated":
+                    if name != "replicated" and pr["psizes"] is not None:     # (the per-stage pass: --full)
+                        F = FEAT_DIM
                         p_src = sum(s_[2 * L - 1] for s_ in pr["psizes"]) / pr["stage_n"]
                         # the partitioned fetch sends every DISTINCT row of the call group once (the list is de-duplicated
                         # behind the walk; layer 1 reads the fetched rows through the inverse index); ids travel as int64
@@ -1350,7 +1243,7 @@ def main():
                 out["placements"] = {name: report(name) for name in HEAD_PREF if name in results}
                 out["per_rank_value"] = out["placements"][head_name]["per_rank_value"]
                 out["xgmi_peak_GBps"] = link_peak
-                if partitioned:
+                if partitioned and args.full:
                     out["all_to_all_bytes_per_gpu"] = out["placements"][head_name]["all_to_all_bytes_per_gpu"]
                     out["xgmi_frac"] = out["placements"][head_name]["xgmi_frac"]
                 st = selftests.get(head_name) or {}
@@ -1363,6 +1256,140 @@ def main():
             ctypes.CDLL(None).fflush(None)
             print(json.dumps(out), flush=True)
         return True
+
+    def full_fields(head, partitioned):
+        """What --full adds to rank 0's line: the per-stage pass's times and hop sizes, the roofline of the dominant
+        kernel, the variants and the CPU baseline."""
+        pipe, feat = head["pipe"], head["feat"]
+        variants, stage_ms, psizes, split_ms, head_mode, stage_n = (
+            head[k] for k in ("variants", "stage_ms", "psizes", "split_ms", "head_mode", "stage_n"))
+        fused = variants.get("fused_fetch") or variants.get("split_fetch")
+        hop_e = [sum(s[2 * k] for s in psizes) / stage_n for k in range(L)]       # edges per call group, seed hop first
+        hop_u = [sum(s[2 * k + 1] for s in psizes) / stage_n for k in range(L)]   # unique nodes after each hop
+        n_src = hop_u[L - 1]
+        # algorithmic bytes per launch (SURVEY.md §8(d)); b = id bytes, fp32 features
+        F = FEAT_DIM
+        idb = 4 if id_dtype == torch.int32 else 8
+        n_fetch = (sum(pipe.distinct_rows) / len(pipe.distinct_rows)) if (pipe.dedup and pipe.distinct_rows) else n_src
+        kernels = {"gather": ("row_copy_kernel", n_fetch * ((8 if pipe.dedup else idb) + 2 * 4 * F))}
+        layer1_ids = "int" if pipe.dedup else None    # layer 1 reads the gathered rows through the int32 inverse index
+        spmm_root = {}
+        for j in range(L):
+            k = L - 1 - j
+            fj = pipe.dims[j]
+            n_dst = hop_u[k - 1] if k >= 1 else G * BATCH
+            # STRICT SURVEY §8(d): E(4F+4) + N_dst(4F+8).  The kernel also copies the root row next to the aggregate
+            # (one more row read and written per destination): that term is reported under its own key, never in spmm_GBps
+            kernels[spmm_label(j)] = ("spmm_csr_kernel", hop_e[k] * (4 * fj + 4) + n_dst * (4 * fj + 8))
+            spmm_root[spmm_label(j)] = n_dst * (8 * fj + 8)
+        for j in range(L):   # one-kernel layers: same reads minus the [agg|x_self] round trip, plus the output write
+            k = L - 1 - j
+            fj, nj = pipe.dims[j], pipe.dims[j + 1]
+            n_dst = hop_u[k - 1] if k >= 1 else G * BATCH
+            # (the layer runs at its output width padded to 64 / 128 / 256: 47 classes -> 64 columns)
+            kname = "sage_layer_mfma_kernel" if (nn_mod.sage_layer_fused_precision() == "bf16x3" and nn_mod.L.lib(
+            ).wgamd_sage_layer_bf16x3_supported(fj, nn_mod._padded_width(nj))) else "sage_layer_fused_kernel"
+            kernels["sage_layer%d(fused)" % (j + 1)] = (kname, hop_e[k] * (4 * fj + 4) + n_dst * (4 * fj + 16) + n_dst * 4 * nj)
+        std_shape = G == std_call_group and args.nodes == wv and args.edges == we   # the shape the committed profiles are of
+
+        def roof_entry(st):
+            """The roofline of one stage's kernel: algorithmic bytes over the live HIP-event time (`frac`), over the committed
+            rocprofv3 average (`frac_profiled`), the committed PMC traffic, and for a one-kernel layer its matrix side."""
+            ach = kernels[st][1] / (stage_ms[st] * 1e-3) / 1e9
+            r = {"bound": "hbm", "kernel": kernels[st][0], "stage": st, "achieved": round(ach, 1),
+                 "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBPS, 4),
+                 "traffic": None, "algorithmic_bytes_per_launch": int(kernels[st][1]),
+                 "avg_launch_ms": round(stage_ms[st], 5),
+                 "timing": "HIP events around the launch on the launch stream, one launch per call group of "
+                           f"{G} mini-batches, averaged over {stage_n} call groups"}
+            pref = layer1_ids if st == "sage_layer1(fused)" else ("long" if (st == "gather" and pipe.dedup) else None)
+            if st.startswith("sage_layer") and st != "sage_layer1(fused)":
+                # a hidden layer reads its input directly (ids type void); rows wider than 128 floats take 64-lane groups
+                pref = "void,64" if pipe.dims[int(st[len("sage_layer")]) - 1] > 128 else "void"
+            if std_shape:
+                prof = load_profiled_avg(r["kernel"], args.workload, prefer=pref)
+                if prof:    # the same algorithmic bytes over the committed profile's average launch duration
+                    r["frac_profiled"] = round(kernels[st][1] / (prof["avg_ns"] * 1e-9) / 1e9 / HBM_PEAK_GBPS, 4)
+                    r["profiled_avg_launch_ms"] = round(prof["avg_ns"] * 1e-6, 5)
+                    r["profiled_source"] = "%s (%d launches, min %.1f us)" % (prof["source"], prof["calls"], prof["min_ns"] * 1e-3)
+                hit = load_pmc(r["kernel"], workload=args.workload, prefer=pref)
+                if hit:
+                    r["traffic"] = hit["bytes"]
+                    r["traffic_over_algorithmic"] = round(hit["bytes"] / kernels[st][1], 3)
+                    r["traffic_source"] = hit["source"] + " kernel " + hit["kernel"]
+            if st.startswith("sage_layer"):
+                # one-kernel layer: HBM-side and MFMA-side work of the same launch
+                jj = int(st[len("sage_layer")]) - 1
+                kk = L - 1 - jj
+                n_dst_ = hop_u[kk - 1] if kk >= 1 else G * BATCH
+                flops = 2.0 * n_dst_ * 2 * pipe.dims[jj] * pipe.dims[jj + 1]
+                r["hbm_frac"] = r["frac"]
+                if r["kernel"] != "sage_layer_mfma_kernel":
+                    tfs = flops / (stage_ms[st] * 1e-3) / 1e12
+                    r["mfma_TFps"], r["mfma_frac"] = round(tfs, 1), round(tfs / MFMA_F32_PEAK_TFPS, 4)
+                    r["mfma_dtype"] = "f32 (v_mfma_f32_16x16x4_f32)"
+                    if r["mfma_frac"] > r["frac"]:
+                        r.update(bound="mfma", achieved=round(tfs, 1), peak=MFMA_F32_PEAK_TFPS, unit="TFLOP/s", frac=r["mfma_frac"])
+                else:
+                    # 3-way bf16 split of both operands, 6 bf16 MFMA products per fp32 product (fp32 accumulate): the matrix
+                    # work is 6 x flops on the bf16 pipe (2.5 PFLOP/s dense) -> far from binding, the launch is HBM-bound
+                    tfs = 6.0 * flops / (stage_ms[st] * 1e-3) / 1e12
+                    r["mfma_TFps"], r["mfma_frac"] = round(tfs, 1), round(tfs / MFMA_BF16_PEAK_TFPS, 4)
+                    r["mfma_dtype"] = "bf16x3 split (6 v_mfma_f32_32x32x16_bf16 per fp32 product, fp32 accumulate)"
+            return r
+
+        # dominant kernel = the longest stage; the runner-up rides along under `also` (the feature gather and the
+        # one-kernel layer 1 are within a per cent of each other on the products workload: which one leads depends on the box)
+        ranked = sorted((k for k in kernels if k in stage_ms), key=lambda k: -stage_ms[k])
+        dom = ranked[0] if ranked else None
+        roofline = roof_entry(dom) if dom is not None else None
+        if roofline is not None and len(ranked) > 1:
+            roofline["also"] = roof_entry(ranked[1])
+        spmm_gbps = spmm_root_gbps = spmm_pmc = None
+        if SPMM1 in split_ms:
+            spmm_gbps = kernels[SPMM1][1] / (split_ms[SPMM1] * 1e-3) / 1e9
+            spmm_root_gbps = (kernels[SPMM1][1] + spmm_root[SPMM1]) / (split_ms[SPMM1] * 1e-3) / 1e9
+            hit = load_pmc("spmm_csr_kernel", workload=args.workload) if std_shape else None
+            if hit:     # real HBM utilisation of the launch: (2 x FETCH_SIZE + WRITE_SIZE) / time / 8 TB/s
+                spmm_pmc = {"hbm_util": round(hit["bytes"] / (split_ms[SPMM1] * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                            "traffic_bytes_per_launch": hit["bytes"], "source": hit["source"] + " kernel " + hit["kernel"]}
+        cpu = None
+        if not args.no_cpu_baseline and world == 1:   # the CPU baseline is timed at N=1 only (rank 0 owns the host cores)
+            nb = min(2048, order.numel() // BATCH)   # time-bounded inside cpu_baseline (--cpu-budget seconds)
+            cb = order[: nb * BATCH].view(nb, BATCH).to(id_dtype).cpu().numpy()  # same seed stream, one mini-batch at a time
+            if V * FEAT_DIM * 4 > (8 << 30):
+                # papers100M-scale table: a lazily-zeroed host array of the same shape (only the gathered
+                # rows' pages are ever touched; values do not matter for the timing)
+                feat_h = np.zeros((V, FEAT_DIM), dtype=np.float32)
+            elif partitioned:
+                feat_h = np.random.default_rng(0).random((V, FEAT_DIM), dtype=np.float32) * 2 - 1
+            else:
+                feat_h = feat.local_tensor.cpu().numpy()
+            weights = [(c.lin_l.weight.cpu(), c.lin_l.bias.cpu(), c.lin_r.weight.cpu()) for c in pipe.convs]
+            cpu = cpu_baseline(row_ptr.cpu().numpy(), col.cpu().numpy(), feat_h, cb, weights, args.cpu_budget)
+        out = {
+            "edges_per_batch": dict([("hop%d" % (k + 1), hop_e[k] / G) for k in range(L)] + [("unique_nodes", n_src / G)]),
+            "stage_ms_per_call_group": {k: round(v, 5) for k, v in stage_ms.items()},
+            "split_stage_ms_per_call_group": None if split_ms is stage_ms else {k: round(v, 5) for k, v in split_ms.items()},
+            "spmm_GBps": None if spmm_gbps is None else round(spmm_gbps, 1),
+            "spmm_frac_of_hbm_peak": None if spmm_gbps is None else round(spmm_gbps / HBM_PEAK_GBPS, 4),
+            "spmm_accounting": "SURVEY.md §8(d) strict: E(4F+4) + N_dst(4F+8) bytes / HIP-event time of the layer-1 "
+                               "aggregation launch (effective bandwidth: part of x is served by L2/MALL)",
+            "spmm_with_root_copy_GBps": None if spmm_root_gbps is None else round(spmm_root_gbps, 1),
+            "spmm_hbm_util_pmc": spmm_pmc,
+            "feature_fetch": (FETCH_DISTINCT + "; %d listed rows -> %d gathered per call group" % (int(n_src), int(n_fetch)))
+                             if pipe.dedup else "x = feat[n_id] row for row",
+            # the same pipeline with EVERY listed row gathered (what the reference's loader fetches per mini-batch; the headline of
+            # rounds 1-5), measured in this run — next to `value` at the top level so that neither figure is read without the other
+            "value_row_for_row_fetch": (variants.get("materialised_full") or {}).get("value") if pipe.dedup else None,
+            "fused_fetch_variant": fused,
+            "variants": variants,
+            "roofline": roofline,
+            "cpu_baseline": cpu,
+        }
+        if cpu is not None:
+            out["gpu_over_cpu"] = round(head["edges"] / head["dt"] / cpu["value"], 2)
+        return out
 
     def arm_watchdog(seconds, what):
         """A placement with collectives in it runs under a watchdog: if it has not finished in time (a rank threw inside a
@@ -1407,7 +1434,7 @@ def main():
         hooks = placement != placements[0]       # test hooks act on the first placement after the first
         feat, ok = None, 1
         try:
-            if placement != "replicated" and (world > 1 or args.selftest):
+            if placement != "replicated" and ((world > 1 and args.full) or args.selftest):
                 selftests[placement] = selftest(placement)
             feat = make_table(placement)
         except Exception as e:       # noqa: BLE001

@@ -42,3 +42,20 @@ def test_dump_outputs_of_the_last_step_are_reproducible(hiplib, tmp_path):
     # a different number of steps ends on different call groups (the walk's seeds follow the group index)
     _, c = _bench(tmp_path / "c", 4)
     assert not np.array_equal(a["n_id"], c["n_id"])
+
+
+def test_plain_run_prints_the_headline_alone(hiplib):
+    """Without --full the run times the headline and nothing else: the line carries the headline's fields, none of what the
+    variants, the per-stage pass or the CPU baseline would add."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--nodes", "200000", "--edges", "3000000", "--call-group", "16", "--groups-per-step", "2"]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "sampled-edges/s" and d["higher_is_better"] is True
+    assert d["steps"] == 2 and d["timed_call_groups"] == 4 and "ids" in d["dtype"] and "workload" in d["config"]
+    for key in ("variants", "roofline", "cpu_baseline", "stage_ms_per_call_group", "edges_per_batch", "placements", "selftest"):
+        assert key not in d, key

@@ -23,7 +23,7 @@ def _free_port():
 def _run(nproc, extra, env=None, shape=("200000", "3000000", "16")):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={nproc}", "--master-addr", "127.0.0.1",
            "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "3", "--warmup", "1",
-           "--nodes", shape[0], "--edges", shape[1], "--call-group", shape[2], "--groups-per-step", "2", "--no-variants"] + extra
+           "--nodes", shape[0], "--edges", shape[1], "--call-group", shape[2], "--groups-per-step", "2", "--full", "--no-variants"] + extra
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, **(env or {})))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]
@@ -126,7 +126,7 @@ def test_rank_dying_in_the_extra_placement_does_not_cost_the_headline(hiplib):
     the others and rank 0 answers with the headline line it already has (the launcher itself then reports the failed worker)."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--nodes", "200000", "--edges", "3000000", "--call-group", "16", "--groups-per-step", "2", "--no-variants", "--dist-backend", "gloo",
+           "--nodes", "200000", "--edges", "3000000", "--call-group", "16", "--groups-per-step", "2", "--full", "--no-variants", "--dist-backend", "gloo",
            "--share-gpu"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, WGAMD_BENCH_TEST_DIE="1"))
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]

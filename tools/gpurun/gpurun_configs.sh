@@ -6,7 +6,7 @@ set -x
 R=$GRAFT_REPO_ROOT; TAG=${1:-r04}; OUT=$R/gpurun_out/configs_$TAG; mkdir -p $OUT; cd /tmp && export TMPDIR=/tmp
 HOT="row_copy|spmm_csr|sage_layer_fused|sage_layer_mfma|sample_uniform|renumber_lds|bucket_sort|renumber_emit|gat_aggregate_heads|gat_layer_fused|gat_transform|gather_terms|gat_csr"
 for W in ${WORKLOADS:-papers100m rmat26 mag}; do
-  EXTRA="--no-variants"; [ $W = mag ] && EXTRA=""
+  EXTRA="--full --no-variants"; [ $W = mag ] && EXTRA="--full"
   rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pc_$W -o $W -- python $R/bench.py --workload $W --steps 3 --warmup 1 --no-cpu-baseline $EXTRA > $OUT/prof_$W.log 2>&1
   cp /tmp/pc_$W/${W}_kernel_stats.csv $OUT/
   for C in FETCH_SIZE WRITE_SIZE; do
@@ -21,7 +21,7 @@ cd $R
 for W in ${WORKLOADS:-papers100m rmat26 mag}; do
   case $W in papers100m) ST="--steps 10 --warmup 3";; *) ST="--steps 6 --warmup 2";; esac
   N=$W; [ $W = mag ] && N=mag_hetero
-  python bench.py --workload $W $ST --cpu-budget 10 > $OUT/$W.log 2> $OUT/$W.err
+  python bench.py --workload $W $ST --full --cpu-budget 10 > $OUT/$W.log 2> $OUT/$W.err
   grep '^{"metric' $OUT/$W.log | tail -1 > $OUT/bench_${N}_n1.json
 done
 ls -la $OUT; tail -c 400 $OUT/*.err; head -c 600 $OUT/bench_*_n1.json
