@@ -1,0 +1,525 @@
+// Graph transformer layer (torch_geometric.nn.TransformerConv, flow source_to_target) over a sampled hop, aggregate-first:
+//     s_ijh   = u_ih . X[j] + w_ih . a_ij                      (u = W_k^T q / sqrt(C), w = W_e^T q / sqrt(C): per destination)
+//     alpha   = softmax_j(s_ijh)                               (per destination row and head)
+//     A_i     = [ agg_i0 | ... | agg_i(H-1) | XD[self_rows[i]] ],  agg_ih = sum_j alpha_ijh [X[j] | a_ij | 1 | 0 pad]
+//     out_i   = act( A_i @ Wstack + bias )
+// The query-key product q_i . k_j is linear in X[j], so the logits need only the per-destination vectors u, w (one library GEMM
+// over the destination rows); lin_key's bias is constant over a row and cancels.  Each head block of A is W4 = ceil4(F + D + 1)
+// wide (the tail is zero) so every block starts 16-B aligned.  The model of the reference's cugraph-pyg example mag_lp_mnmg.py.
+//
+// Pieces:
+//   * tconv_layer_kernel — the whole layer, one launch per hop: 16-row tiles, 256 threads.  Phase 1: one wave per destination
+//     row, lane = one float4 of the source row (F <= 256) and, for lane <= D, one column of [a_ij | 1].  The row's edges go by
+//     in groups of 4 (4 neighbour rows in flight); each group's H logits are wave sums (xor butterflies: every lane ends with
+//     the same bits) and an online softmax (running max and sum, accumulators rescaled once per group) keeps any degree exact.
+//     The finished row goes to the LDS tile (and, when training, to A in global memory: the weight gradient reads it, and the
+//     backward's row sums sum_j alpha dalpha are dA_ih . A_ih — cheaper to keep than to rebuild).  The logits are written to
+//     alpha [E, H] as they are made and turned into alpha by a second pass over the row once its max and sum are known.
+//     Phase 2: the [16 x K] tile times Wstack (passed transposed, [N, K]) on the exact fp32 matrix pipe
+//     (v_mfma_f32_16x16x4_f32) as in wg_rgcn.hip, bias and ReLU fused.
+//   * tconv_bwd_dst_kernel — destination-major: per edge and head dalpha = dA_ih . [X[j] | a_ij | 1] and
+//     ds = alpha (dalpha - dA_ih . A_ih); du_ih = sum ds X[j], dw_ih = sum ds a_ij, ds written [E, H].  One wave per row.
+//   * tconv_bwd_src_kernel — source-major over the hop's transpose (HopGraph.transposed with the edge permutation):
+//     dX[j] = sum_e sum_h (alpha dA_ih[:F] + ds u_ih) plus the skip block of dA where input row j is a destination itself.
+//     One wave per input row.
+// No atomics anywhere: every sum runs in CSR (or transposed-CSR) order, the same bits from run to run.
+#include "wg_common.hpp"
+#include "wgamd_ext.h"
+
+namespace wgamd {
+namespace {
+
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+constexpr int kTileRows = 16;
+constexpr int kThreads  = 256;
+constexpr int kMaxK     = 1024;
+constexpr int kMaxF     = 256;     // one float4 of a source row per lane
+constexpr int kMaxD     = 32;      // [a | 1 | pad] within one wave's lanes
+constexpr int kMaxH     = 8;
+
+template <int KIND>
+__device__ __forceinline__ const float* x_row(const float* x, int64_t ldx, const void* ids, int64_t r)
+{
+  if constexpr (KIND == 0) return x + r * ldx;
+  else if constexpr (KIND == 1) return x + (int64_t) static_cast<const int32_t*>(ids)[r] * ldx;
+  else if constexpr (KIND == 2) return x + static_cast<const int64_t*>(ids)[r] * ldx;
+  else return reinterpret_cast<const float*>(reinterpret_cast<const char*>(x) + static_cast<const int64_t*>(ids)[r]);
+}
+
+// sum over the wave; xor butterflies give every lane the same bits (each step adds the same two values, commuted)
+__device__ __forceinline__ float wave_sum(float v)
+{
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
+
+struct tconv_args {
+  const int* row_ptr;
+  const int* col;
+  int64_t n_rows;
+  const float* x;             // source rows X[r] = x[src_ids ? src_ids[r] : r]
+  int64_t ldx;
+  int F;
+  const void* src_ids;
+  const float* xd;            // destination rows XD[self_rows[i]]; read through src_ids when xd_ids
+  int64_t ldxd;
+  int Fd;                     // 0: no skip block
+  const int64_t* self_rows;
+  int xd_ids;
+  const float* ea;            // [E, D] in CSR order (D = 0: none)
+  int D;
+  const float* u;             // [n_rows, ldu]: u[i, h F + f]
+  int64_t ldu;
+  const float* w;             // [n_rows, ldwv]: w[i, h D + d]
+  int64_t ldwv;
+  int H;
+  const float* wt;            // [N, ldwt] = Wstack^T
+  int64_t ldwt;
+  int N;
+  const float* bias;
+  int relu;
+  float* out;
+  int64_t ldo;
+  float* alpha;               // [E, H] or null
+  float* a_save;              // [n_rows, K] or null
+  int W4, K, K16, SD;
+};
+
+template <int KIND, int HM>
+__global__ void __launch_bounds__(kThreads) tconv_layer_kernel(tconv_args a)
+{
+  extern __shared__ __attribute__((aligned(16))) float tile[];
+  __shared__ int rp[kTileRows + 1];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t row0 = (int64_t)blockIdx.x * kTileRows;
+  const int rows_here = (int)std::min<int64_t>(kTileRows, a.n_rows - row0);
+  if (tid <= kTileRows) rp[tid] = a.row_ptr[row0 + std::min(tid, rows_here)];
+  const int pad4 = (a.K16 - a.K) / 4;             // the tile's k padding [K, K16) is zero
+  for (int p = tid; p < kTileRows * pad4; p += kThreads)
+    reinterpret_cast<f32x4*>(tile + (p / pad4) * a.SD + a.K)[p % pad4] = f32x4{0.f, 0.f, 0.f, 0.f};
+  __syncthreads();
+
+  // ---- phase 1: one wave per destination row ----
+  const int F4 = a.F / 4, H = a.H, D = a.D;
+  const bool fx = lane < F4;
+  const int ext_w = a.W4 - a.F;                   // [a | 1 | pad] columns of a head block
+  for (int lr = wave; lr < kTileRows; lr += 4) {
+    float* trow = tile + lr * a.SD;
+    if (lr >= rows_here) {
+      for (int q = lane; q < a.K / 4; q += 64) reinterpret_cast<f32x4*>(trow)[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+      continue;
+    }
+    const int64_t i = row0 + lr;
+    const int s = rp[lr], t = rp[lr + 1];
+    f32x4 uh[HM], acc[HM];
+    float wh[HM], ext[HM], m[HM], l[HM];
+#pragma unroll
+    for (int h = 0; h < HM; ++h) {
+      uh[h] = acc[h] = f32x4{0.f, 0.f, 0.f, 0.f};
+      wh[h] = ext[h] = l[h] = 0.f;
+      m[h] = -INFINITY;
+      if (h < H) {
+        if (fx) uh[h] = reinterpret_cast<const f32x4*>(a.u + i * a.ldu + (int64_t)h * a.F)[lane];
+        if (lane < D) wh[h] = a.w[i * a.ldwv + h * D + lane];
+      }
+    }
+    for (int e0 = s; e0 < t; e0 += 4) {
+      f32x4 xv[4];
+      float av[4];
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const int e = e0 + v;
+        xv[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+        av[v] = 0.f;
+        if (e < t) {
+          const int j = a.col[e];
+          if (fx) xv[v] = reinterpret_cast<const f32x4*>(x_row<KIND>(a.x, a.ldx, a.src_ids, j))[lane];
+          av[v] = lane < D ? a.ea[(int64_t)e * D + lane] : (lane == D ? 1.f : 0.f);
+        }
+      }
+#pragma unroll
+      for (int h = 0; h < HM; ++h) {
+        if (h >= H) break;
+        float sc[4];
+        float mx = m[h];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          sc[v] = wave_sum(dot4(uh[h], xv[v]) + (lane < D ? wh[h] * av[v] : 0.f));
+          if (e0 + v < t) mx = fmaxf(mx, sc[v]);
+        }
+        const float r = expf(m[h] - mx);          // (m = -inf before the first group: r = 0)
+        acc[h] *= r;
+        ext[h] *= r;
+        l[h] *= r;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          if (e0 + v < t) {
+            const float p = expf(sc[v] - mx);
+            acc[h] += p * xv[v];
+            ext[h] += p * av[v];
+            l[h] += p;
+            if (a.alpha && lane == v) a.alpha[(int64_t)(e0 + v) * H + h] = sc[v];   // the logit; alpha after the row
+          }
+        }
+        m[h] = mx;
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < HM; ++h) {
+      if (h >= H) break;
+      const float inv = l[h] > 0.f ? 1.f / l[h] : 0.f;
+      if (fx) reinterpret_cast<f32x4*>(trow + h * a.W4)[lane] = acc[h] * inv;
+      if (lane < ext_w) trow[h * a.W4 + a.F + lane] = ext[h] * inv;
+      l[h] = inv;
+    }
+    if (a.Fd > 0 && lane < a.Fd / 4) {
+      const int64_t self = a.self_rows[i];
+      const float* xr = a.xd_ids ? x_row<KIND>(a.xd, a.ldxd, a.src_ids, self) : a.xd + self * a.ldxd;
+      reinterpret_cast<f32x4*>(trow + H * a.W4)[lane] = reinterpret_cast<const f32x4*>(xr)[lane];
+    }
+    if (a.alpha) {
+      __threadfence_block();                      // the logits this wave wrote, read back by other lanes
+      for (int e = s + lane; e < t; e += 64)
+#pragma unroll
+        for (int h = 0; h < HM; ++h) {
+          if (h >= H) break;
+          float* p = a.alpha + (int64_t)e * H + h;
+          *p = expf(*p - m[h]) * l[h];
+        }
+    }
+  }
+  __syncthreads();
+  if (a.a_save) {                                 // A for the backward: rows_here x K, row-major
+    const int K4 = a.K / 4;
+    for (int p = tid; p < rows_here * K4; p += kThreads)
+      reinterpret_cast<f32x4*>(a.a_save + (row0 + p / K4) * a.K)[p % K4] = reinterpret_cast<const f32x4*>(tile + (p / K4) * a.SD)[p % K4];
+  }
+
+  // ---- phase 2: [16 x K16] tile @ wt^T on v_mfma_f32_16x16x4_f32; wave w owns the 16-column tiles w, w + 4, ... ----
+  const int n_ct = (a.N + 15) / 16;
+  if (wave >= n_ct) return;
+  const int mm = lane & 15, g = lane >> 4;
+  f32x4 cacc[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) cacc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int kb = 0; kb < a.K16; kb += 16) {
+    const int k = kb + 4 * g;
+    const f32x4 av = *reinterpret_cast<const f32x4*>(tile + mm * a.SD + k);
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+      const int ct = wave + 4 * qq;
+      if (ct < n_ct) {
+        const int n = ct * 16 + mm;
+        f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+        if (n < a.N && k < a.K) bv = *reinterpret_cast<const f32x4*>(a.wt + (int64_t)n * a.ldwt + k);
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) cacc[qq] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], bv[kk], cacc[qq], 0, 0, 0);
+      }
+    }
+  }
+  // C/D map of the 16x16 MFMA: col = lane & 15, row = 4 (lane >> 4) + reg
+#pragma unroll
+  for (int qq = 0; qq < 4; ++qq) {
+    const int n = (wave + 4 * qq) * 16 + mm;
+    if (wave + 4 * qq >= n_ct || n >= a.N) continue;
+    const float bb = a.bias ? a.bias[n] : 0.f;
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int64_t i = row0 + 4 * g + reg;
+      if (i < a.n_rows) {
+        float y = cacc[qq][reg] + bb;
+        if (a.relu) y = fmaxf(y, 0.f);
+        a.out[i * a.ldo + n] = y;
+      }
+    }
+  }
+}
+
+// ---- destination-major backward ---------------------------------------------------------------------------------------------
+struct tconv_bwd_args {
+  const int* row_ptr;
+  const int* col;
+  int64_t n_rows;
+  const float* x;
+  int64_t ldx;
+  int F;
+  const void* src_ids;
+  const float* ea;
+  int D;
+  int H, W4;
+  const float* alpha;         // [E, H]
+  const float* dA;            // [n_rows, ldda]
+  int64_t ldda;
+  const float* A;             // [n_rows, lda]: the forward's saved rows
+  int64_t lda;
+  float* du;                  // [n_rows, H F]
+  float* dw;                  // [n_rows, H D] (D > 0)
+  float* ds;                  // [E, H]
+};
+
+template <int KIND, int HM>
+__global__ void __launch_bounds__(256) tconv_bwd_dst_kernel(tconv_bwd_args a)
+{
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= a.n_rows) return;                      // (wave-uniform)
+  const int F4 = a.F / 4, H = a.H, D = a.D;
+  const bool fx = lane < F4;
+  const int s = a.row_ptr[i], t = a.row_ptr[i + 1];
+  f32x4 dah[HM], gu[HM];
+  float dae[HM], gw[HM], rdot[HM];
+#pragma unroll
+  for (int h = 0; h < HM; ++h) {
+    dah[h] = gu[h] = f32x4{0.f, 0.f, 0.f, 0.f};
+    dae[h] = gw[h] = rdot[h] = 0.f;
+    if (h < H) {
+      const float* dr = a.dA + i * a.ldda + (int64_t)h * a.W4;
+      const float* ar = a.A + i * a.lda + (int64_t)h * a.W4;
+      float p = 0.f;
+      if (fx) {
+        dah[h] = reinterpret_cast<const f32x4*>(dr)[lane];
+        p = dot4(dah[h], reinterpret_cast<const f32x4*>(ar)[lane]);
+      }
+      if (lane <= D) {
+        dae[h] = dr[a.F + lane];
+        p += dae[h] * ar[a.F + lane];
+      }
+      rdot[h] = wave_sum(p);                      // sum_j alpha dalpha = dA_ih . agg_ih
+    }
+  }
+  for (int e0 = s; e0 < t; e0 += 4) {
+    f32x4 xv[4];
+    float av[4];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      const int e = e0 + v;
+      xv[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+      av[v] = 0.f;
+      if (e < t) {
+        const int j = a.col[e];
+        if (fx) xv[v] = reinterpret_cast<const f32x4*>(x_row<KIND>(a.x, a.ldx, a.src_ids, j))[lane];
+        av[v] = lane < D ? a.ea[(int64_t)e * D + lane] : (lane == D ? 1.f : 0.f);
+      }
+    }
+#pragma unroll
+    for (int h = 0; h < HM; ++h) {
+      if (h >= H) break;
+#pragma unroll
+      for (int v = 0; v < 4; ++v) {
+        const float dal = wave_sum(dot4(dah[h], xv[v]) + dae[h] * av[v]);
+        if (e0 + v < t) {
+          const int64_t eh = (int64_t)(e0 + v) * H + h;
+          const float dsv = a.alpha[eh] * (dal - rdot[h]);
+          gu[h] += dsv * xv[v];
+          gw[h] += dsv * av[v];
+          if (lane == v) a.ds[eh] = dsv;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < HM; ++h) {
+    if (h >= H) break;
+    if (fx) reinterpret_cast<f32x4*>(a.du + i * ((int64_t)H * a.F) + (int64_t)h * a.F)[lane] = gu[h];
+    if (lane < D) a.dw[i * ((int64_t)H * D) + h * D + lane] = gw[h];
+  }
+}
+
+// ---- source-major backward: the input rows' gradient -----------------------------------------------------------------------
+__global__ void __launch_bounds__(256) tconv_bwd_src_kernel(const int* __restrict__ row_ptr_t, const int* __restrict__ col_t,
+                                                            const int* __restrict__ perm, const int64_t* __restrict__ self_t,
+                                                            int64_t n_rows, int64_t n_src, int F, int H, int W4, int skip_at,
+                                                            const float* __restrict__ alpha, const float* __restrict__ ds,
+                                                            const float* __restrict__ dA, int64_t ldda, const float* __restrict__ u,
+                                                            int64_t ldu, float* __restrict__ gx, int64_t ldgx, int accumulate)
+{
+  const int lane = threadIdx.x & 63;
+  const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= n_src || lane >= F / 4) return;
+  const int s = row_ptr_t[j], t = row_ptr_t[j + 1];
+  f32x4 g = {0.f, 0.f, 0.f, 0.f};
+  for (int p = s; p < t; ++p) {
+    const int64_t i = col_t[p], e = perm[p];
+    for (int h = 0; h < H; ++h) {
+      const float al = alpha[e * H + h], dv = ds[e * H + h];
+      const f32x4 d  = reinterpret_cast<const f32x4*>(dA + i * ldda + (int64_t)h * W4)[lane];
+      const f32x4 uu = reinterpret_cast<const f32x4*>(u + i * ldu + (int64_t)h * F)[lane];
+      g += al * d + dv * uu;
+    }
+  }
+  if (self_t && skip_at >= 0) {                   // self_t[j] = n_rows + i (input row j is destination i), else 2 n_rows
+    const int64_t i = self_t[j] - n_rows;
+    if (i >= 0 && i < n_rows) g += reinterpret_cast<const f32x4*>(dA + i * ldda + skip_at)[lane];
+  }
+  f32x4* o = reinterpret_cast<f32x4*>(gx + j * ldgx) + lane;
+  *o = accumulate ? *o + g : g;
+}
+
+int ids_kind(const void* src_ids, wholememory_dtype_t dt)
+{
+  if (src_ids == nullptr) return 0;
+  if (dt == WHOLEMEMORY_DT_INT) return 1;
+  if (dt == WHOLEMEMORY_DT_INT64) return 2;
+  if (dt == WGAMD_IDS_BYTE_OFFSETS) return 3;
+  throw invalid_input("src_ids must be INT, INT64 or WGAMD_IDS_BYTE_OFFSETS");
+}
+
+int heads_bucket(int H) { return H <= 1 ? 1 : H <= 2 ? 2 : H <= 4 ? 4 : 8; }
+
+template <int KIND, int HM>
+void launch_layer(const tconv_args& a, hipStream_t st)
+{
+  const dim3 grid((unsigned)((a.n_rows + kTileRows - 1) / kTileRows));
+  const size_t lds = (size_t)kTileRows * a.SD * 4;
+  auto kern        = tconv_layer_kernel<KIND, HM>;
+  WG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  kern<<<grid, kThreads, lds, st>>>(a);
+}
+
+template <int KIND>
+void launch_layer_h(const tconv_args& a, hipStream_t st)
+{
+  switch (heads_bucket(a.H)) {
+    case 1: launch_layer<KIND, 1>(a, st); break;
+    case 2: launch_layer<KIND, 2>(a, st); break;
+    case 4: launch_layer<KIND, 4>(a, st); break;
+    default: launch_layer<KIND, 8>(a, st); break;
+  }
+}
+
+template <int KIND>
+void launch_bwd_h(const tconv_bwd_args& a, hipStream_t st)
+{
+  const dim3 grid((unsigned)((a.n_rows + 3) / 4));
+  switch (heads_bucket(a.H)) {
+    case 1: tconv_bwd_dst_kernel<KIND, 1><<<grid, 256, 0, st>>>(a); break;
+    case 2: tconv_bwd_dst_kernel<KIND, 2><<<grid, 256, 0, st>>>(a); break;
+    case 4: tconv_bwd_dst_kernel<KIND, 4><<<grid, 256, 0, st>>>(a); break;
+    default: tconv_bwd_dst_kernel<KIND, 8><<<grid, 256, 0, st>>>(a); break;
+  }
+}
+
+int block_width(int F, int D) { return (F + D + 1 + 3) / 4 * 4; }
+
+}  // namespace
+}  // namespace wgamd
+
+extern "C" int wgamd_transformer_layer_supported(int F_src, int F_dst, int D, int H, int N)
+{
+  using namespace wgamd;
+  if (F_src <= 0 || F_src % 4 != 0 || F_src > kMaxF || F_dst < 0 || F_dst % 4 != 0 || F_dst > kMaxF) return 0;
+  if (D < 0 || D > kMaxD || H < 1 || H > kMaxH || N < 1 || N > 256) return 0;
+  const int64_t K = (int64_t)H * block_width(F_src, D) + F_dst;
+  return K <= kMaxK;
+}
+
+extern "C" int wgamd_transformer_block_width(int F_src, int D) { return wgamd::block_width(F_src, D); }
+
+extern "C" wholememory_error_code_t wgamd_transformer_layer_f32(
+    const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx, int F_src, const void* src_ids,
+    wholememory_dtype_t src_ids_dtype, const float* x_dst, int64_t ldx_dst, int F_dst, const int64_t* self_rows, int x_dst_ids,
+    const float* edge_attr, int D, const float* u, int64_t ldu, const float* w, int64_t ldw, int H, const float* wt, int64_t ldwt,
+    int N, const float* bias, int relu, float* out, int64_t ldo, float* alpha, float* a_save, void* stream)
+{
+  using namespace wgamd;
+  return guarded("wgamd_transformer_layer_f32", [&] {
+    WG_REQUIRE_INPUT(n_rows >= 0, "bad sizes");
+    if (!wgamd_transformer_layer_supported(F_src, F_dst, D, H, N))
+      throw logic_error(fmt("unsupported shape: F_src=%d, F_dst=%d (multiples of 4, <= %d), D=%d (<= %d), H=%d (<= %d), N=%d "
+                            "(<= 256), K <= %d", F_src, F_dst, kMaxF, D, kMaxD, H, kMaxH, N, kMaxK));
+    if (n_rows == 0) return;
+    WG_REQUIRE_INPUT(row_ptr && col && x && u && wt && out && (D == 0 || (edge_attr && w)) && (F_dst == 0 || (x_dst && self_rows)),
+                     "null pointer");
+    WG_REQUIRE_INPUT(ldo >= N && ldu >= (int64_t)H * F_src && (D == 0 || ldw >= (int64_t)H * D), "leading dimension too small");
+    const int kind = ids_kind(src_ids, src_ids_dtype);
+    WG_REQUIRE_INPUT(!x_dst_ids || kind != 0, "x_dst_ids needs src_ids");
+    tconv_args a{};
+    a.row_ptr = row_ptr, a.col = col, a.n_rows = n_rows, a.x = x, a.ldx = ldx, a.F = F_src, a.src_ids = src_ids;
+    a.xd = x_dst, a.ldxd = ldx_dst, a.Fd = F_dst, a.self_rows = self_rows, a.xd_ids = x_dst_ids ? 1 : 0;
+    a.ea = edge_attr, a.D = D, a.u = u, a.ldu = ldu, a.w = w, a.ldwv = ldw, a.H = H;
+    a.wt = wt, a.ldwt = ldwt, a.N = N, a.bias = bias, a.relu = relu ? 1 : 0, a.out = out, a.ldo = ldo;
+    a.alpha = alpha, a.a_save = a_save;
+    a.W4  = block_width(F_src, D);
+    a.K   = H * a.W4 + F_dst;
+    a.K16 = (a.K + 15) / 16 * 16;
+    a.SD  = a.K16 + 4;      // rows 4 banks apart: the 16 rows of a fragment read spread over the 64 banks
+    WG_REQUIRE_INPUT(kind == 3 || ldx >= F_src, "leading dimension too small");
+    WG_REQUIRE_INPUT(F_dst == 0 || (x_dst_ids && kind == 3) || ldx_dst >= F_dst, "leading dimension too small");
+    WG_REQUIRE_INPUT(ldwt >= a.K, "leading dimension too small");
+    const auto mis = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+    if ((kind != 3 && ldx % 4 != 0) || mis(x) || (F_dst > 0 && (mis(x_dst) || ldx_dst % 4 != 0)) || ldwt % 4 != 0 || mis(wt) ||
+        mis(u) || ldu % 4 != 0 || (a_save && mis(a_save)))
+      throw logic_error("x / x_dst / u / wt / a_save rows must be 16-B aligned");
+    auto st = static_cast<hipStream_t>(stream);
+    switch (kind) {
+      case 0: launch_layer_h<0>(a, st); break;
+      case 1: launch_layer_h<1>(a, st); break;
+      case 2: launch_layer_h<2>(a, st); break;
+      default: launch_layer_h<3>(a, st); break;
+    }
+    WG_HIP_CHECK(hipGetLastError());
+  });
+}
+
+extern "C" wholememory_error_code_t wgamd_transformer_bwd_dst_f32(
+    const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx, int F_src, const void* src_ids,
+    wholememory_dtype_t src_ids_dtype, const float* edge_attr, int D, int H, const float* alpha, const float* dA, int64_t ldda,
+    const float* A, int64_t lda, float* du, float* dw, float* ds, void* stream)
+{
+  using namespace wgamd;
+  return guarded("wgamd_transformer_bwd_dst_f32", [&] {
+    WG_REQUIRE_INPUT(n_rows >= 0, "bad sizes");
+    if (!wgamd_transformer_layer_supported(F_src, 0, D, H, 1))
+      throw logic_error(fmt("unsupported shape: F_src=%d, D=%d, H=%d", F_src, D, H));
+    if (n_rows == 0) return;
+    WG_REQUIRE_INPUT(row_ptr && col && x && alpha && dA && A && du && ds && (D == 0 || (edge_attr && dw)), "null pointer");
+    const int kind = ids_kind(src_ids, src_ids_dtype);
+    tconv_bwd_args a{};
+    a.row_ptr = row_ptr, a.col = col, a.n_rows = n_rows, a.x = x, a.ldx = ldx, a.F = F_src, a.src_ids = src_ids;
+    a.ea = edge_attr, a.D = D, a.H = H, a.W4 = block_width(F_src, D), a.alpha = alpha, a.dA = dA, a.ldda = ldda, a.A = A, a.lda = lda;
+    a.du = du, a.dw = dw, a.ds = ds;
+    WG_REQUIRE_INPUT(ldda >= (int64_t)H * a.W4 && lda >= (int64_t)H * a.W4, "leading dimension too small");
+    WG_REQUIRE_INPUT(kind == 3 || ldx >= F_src, "leading dimension too small");
+    const auto mis = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+    if ((kind != 3 && ldx % 4 != 0) || mis(x) || mis(dA) || ldda % 4 != 0 || mis(A) || lda % 4 != 0 || mis(du))
+      throw logic_error("x / dA / A / du rows must be 16-B aligned");
+    auto st = static_cast<hipStream_t>(stream);
+    switch (kind) {
+      case 0: launch_bwd_h<0>(a, st); break;
+      case 1: launch_bwd_h<1>(a, st); break;
+      case 2: launch_bwd_h<2>(a, st); break;
+      default: launch_bwd_h<3>(a, st); break;
+    }
+    WG_HIP_CHECK(hipGetLastError());
+  });
+}
+
+extern "C" wholememory_error_code_t wgamd_transformer_bwd_src_f32(
+    const int* row_ptr_t, const int* col_t, const int* perm, const int64_t* self_t, int64_t n_rows, int64_t n_src, int F_src, int D,
+    int H, int skip_at, const float* alpha, const float* ds, const float* dA, int64_t ldda, const float* u, int64_t ldu, float* gx,
+    int64_t ldgx, int accumulate, void* stream)
+{
+  using namespace wgamd;
+  return guarded("wgamd_transformer_bwd_src_f32", [&] {
+    WG_REQUIRE_INPUT(n_src >= 0 && n_rows >= 0, "bad sizes");
+    if (!wgamd_transformer_layer_supported(F_src, 0, D, H, 1))
+      throw logic_error(fmt("unsupported shape: F_src=%d, D=%d, H=%d", F_src, D, H));
+    if (n_src == 0) return;
+    WG_REQUIRE_INPUT(row_ptr_t && col_t && perm && alpha && ds && dA && u && gx, "null pointer");
+    const int W4 = wgamd::block_width(F_src, D);
+    WG_REQUIRE_INPUT(ldda >= (int64_t)H * W4 && ldu >= (int64_t)H * F_src && ldgx >= F_src, "leading dimension too small");
+    WG_REQUIRE_INPUT(skip_at < 0 || (skip_at % 4 == 0 && ldda >= (int64_t)skip_at + F_src), "bad skip offset");
+    const auto mis = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
+    if (mis(dA) || ldda % 4 != 0 || mis(u) || ldu % 4 != 0 || mis(gx) || ldgx % 4 != 0)
+      throw logic_error("dA / u / gx rows must be 16-B aligned");
+    auto st = static_cast<hipStream_t>(stream);
+    wgamd::tconv_bwd_src_kernel<<<(unsigned)((n_src + 3) / 4), 256, 0, st>>>(row_ptr_t, col_t, perm, self_t, n_rows, n_src, F_src, H,
+                                                                              W4, skip_at, alpha, ds, dA, ldda, u, ldu, gx, ldgx,
+                                                                              accumulate ? 1 : 0);
+    WG_HIP_CHECK(hipGetLastError());
+  });
+}

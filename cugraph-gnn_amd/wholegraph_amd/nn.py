@@ -1000,29 +1000,34 @@ class HopGraph:
             self._loops = (rp, col)
         return self._loops
 
-    def transposed(self, n_src: int, need_self: bool = True):
+    def transposed(self, n_src: int, need_self: bool = True, need_perm: bool = False):
         """The hop seen from its ``n_src`` input rows, for the backward pass — computed once per hop and kept, whichever layers
         and however many backward calls use it: ``(row_ptr_t, col_t, self_t)`` with the source-major CSR of
         ``wgamd_csr_transpose_i32`` (entries = destination rows, hop order inside a source: deterministic sums) and
         ``self_t[j]`` = ``n_rows + i`` where input row j is destination i itself (``self_rows`` is injective: every
         destination is a different vertex of its mini-batch), ``2 n_rows`` otherwise — the row indices ``_sage_dx`` reads its
-        stacked gradient through."""
+        stacked gradient through; ``self_t`` is None without ``need_self``.  With ``need_perm`` a fourth entry, ``perm`` int32:
+        the hop's CSR edge of every transposed entry (how per-edge arrays are read source-major; one element when the hop
+        has no edges)."""
         # (under HIP-graph capture the hop's arrays are fixed buffers REFILLED before every replay: the transpose must be part
         #  of the graph, once per capture)
         key = (n_src, _capture_epoch if _capturing() else 0)
-        if self._t is None or self._t[0] != key:
+        stale = self._t is None or self._t[0] != key
+        if stale or (need_perm and self._t[4] is None):
             n, dev = self.n_rows, self.row_ptr.device
             if self.col.shape[0] > 0:
-                row_ptr_t, _, _, col_t = _csr_transpose(self.row_ptr, self.col, n_src, want_col_t=True)
+                row_ptr_t, perm, _, col_t = _csr_transpose(self.row_ptr, self.col, n_src, want_perm=need_perm, want_col_t=True)
             else:
                 row_ptr_t, col_t = torch.zeros(n_src + 1, dtype=torch.int32, device=dev), self.col
-            self._t = [key, row_ptr_t, col_t, None]
+                perm = torch.zeros(1, dtype=torch.int32, device=dev) if need_perm else None
+            self._t = [key, row_ptr_t, col_t, None if stale else self._t[3], perm]
         if need_self and self._t[3] is None:     # (only the layer kernel over the transposed hop reads it: three launches)
             n, dev = self.n_rows, self.row_ptr.device
             self_t = torch.full((n_src,), 2 * n, dtype=torch.int64, device=dev)
             self_t[self.self_rows] = torch.arange(n, 2 * n, dtype=torch.int64, device=dev)
             self._t[3] = self_t
-        return tuple(self._t[1:])
+        res = tuple(self._t[1:4])
+        return res + (self._t[4],) if need_perm else res
 
 
 class LayerGraph:
@@ -2150,6 +2155,471 @@ class RGCNConv(torch.nn.Module):
 
 
 FastRGCNConv = RGCNConv
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Graph transformer (torch_geometric.nn.TransformerConv; the layer of the reference's cugraph-pyg example mag_lp_mnmg.py)
+# — csrc/wg_transformer.hip
+# ---------------------------------------------------------------------------------------------------------------------
+def transformer_layer_supported(F_src: int, F_dst: int, D: int, H: int, N: int) -> bool:
+    """Shapes of the one-kernel transformer layer (``wgamd_transformer_layer_f32``): F_src and F_dst (0: no skip) multiples of 4
+    and <= 256, edge_dim D <= 32, heads H <= 8, output width N <= 256, K = H ceil4(F_src + D + 1) + F_dst <= 1024."""
+    return bool(L.lib().wgamd_transformer_layer_supported(int(F_src), int(F_dst), int(D), int(H), int(N)))
+
+
+def transformer_block_width(F_src: int, D: int) -> int:
+    """Width of one head's block of the layer's rows A: ``[x_j | a_ij | 1]`` padded to a multiple of 4."""
+    return (F_src + D + 1 + 3) // 4 * 4
+
+
+def transformer_folds(conv):
+    """The parameters of ``conv`` (a ``TransformerConv``) in the aggregate-first form, built with torch ops (under autograd when
+    it is on), in the parameters' dtype and device:
+      ``(Fu [F_dst, H F_src], bu [H F_src], Fw [F_dst, H D] | None, bw [H D] | None, wt [N, K], bias [N] | None)``
+    with ``u = x_dst @ Fu + bu`` (u_ih = W_k,h^T q_ih / sqrt(C)), ``w = x_dst @ Fw + bw`` (W_e,h^T q_ih / sqrt(C)) and
+    ``wt = Wstack^T``: the columns of head h's block are ``[W_v,h | W_e,h | b_v,h | 0]`` (scaled by 1 / H and summed over the
+    heads when ``concat=False``), then ``lin_skip.weight`` (root_weight).  lin_key's bias cancels in the softmax; it enters u
+    as an exact 0 so that it still receives a (zero) gradient."""
+    H, C = conv.heads, conv.out_channels
+    Fs, Fd, D = conv.in_src, conv.in_dst, conv.edge_dim or 0
+    sc = 1.0 / math.sqrt(C)
+    Wq, bq = conv.lin_query.weight.view(H, C, Fd), conv.lin_query.bias.view(H, C)
+    Wk = conv.lin_key.weight.view(H, C, Fs)
+    Fu = torch.einsum("hcd,hcf->dhf", Wq, Wk).reshape(Fd, H * Fs) * sc
+    bu = torch.einsum("hc,hcf->hf", bq, Wk).reshape(H * Fs) * sc + 0.0 * conv.lin_key.bias.sum()
+    Fw = bw = None
+    parts = [conv.lin_value.weight.view(H, C, Fs)]
+    if D:
+        We = conv.lin_edge.weight.view(H, C, D)
+        Fw = torch.einsum("hcd,hce->dhe", Wq, We).reshape(Fd, H * D) * sc
+        bw = torch.einsum("hc,hce->he", bq, We).reshape(H * D) * sc
+        parts.append(We)
+    parts.append(conv.lin_value.bias.view(H, C, 1))
+    W4 = transformer_block_width(Fs, D)
+    if W4 > Fs + D + 1:
+        parts.append(Fu.new_zeros((H, C, W4 - Fs - D - 1)))
+    blk = torch.cat(parts, 2)                                        # [H, C, W4]
+    if conv.concat:
+        wt = torch.block_diag(*blk.unbind(0))                        # [H C, H W4]
+    else:
+        wt = blk.permute(1, 0, 2).reshape(C, H * W4) / H             # [C, H W4]
+    bias = None
+    if conv.root_weight:
+        wt = torch.cat([wt, conv.lin_skip.weight], 1)
+        bias = conv.lin_skip.bias
+    return Fu, bu, Fw, bw, wt, bias
+
+
+def transformer_layer_forward(row_ptr, col, x, u, wt, H: int, self_rows=None, x_dst=None, x_dst_ids=False, edge_attr=None, w=None,
+                              bias=None, relu=False, src_ids=None, out=None, alpha=None, a_save=None):
+    """A whole transformer layer over one hop in ONE kernel (``wgamd_transformer_layer_f32``, include/wgamd_ext.h).  ``u``
+    [n, H F_src] and ``w`` [n, H D] are the per-destination vectors (``transformer_folds``), ``wt`` = Wstack^T [N, K];
+    ``x_dst`` (None: no skip block) is read at ``self_rows`` (through ``src_ids`` when ``x_dst_ids``)."""
+    _check_csr(row_ptr, col)
+    n_rows, F_, N = row_ptr.shape[0] - 1, x.shape[1], wt.shape[0]
+    D = 0 if edge_attr is None else edge_attr.shape[1]
+    Fd = 0 if x_dst is None else x_dst.shape[1]
+    assert x.dtype == torch.float32 and x.stride(1) == 1 and wt.dtype == torch.float32 and wt.stride(1) == 1
+    assert u.dtype == torch.float32 and u.stride(1) == 1 and u.shape == (n_rows, H * F_)
+    assert edge_attr is None or (edge_attr.dtype == torch.float32 and edge_attr.is_contiguous() and edge_attr.shape[0] == col.shape[0])
+    assert w is None or (w.dtype == torch.float32 and w.stride(1) == 1 and w.shape == (n_rows, H * D))
+    assert x_dst is None or (self_rows is not None and self_rows.dtype == torch.int64 and self_rows.is_contiguous())
+    if out is None:
+        out = torch.empty((n_rows, N), dtype=torch.float32, device=row_ptr.device)
+    assert out.shape == (n_rows, N) and out.stride(1) == 1
+    assert alpha is None or (alpha.shape == (col.shape[0], H) and alpha.is_contiguous())
+    assert a_save is None or a_save.is_contiguous()
+    ids_ptr, ids_dt = _gcn_args(x, src_ids)
+    L.check(L.lib().wgamd_transformer_layer_f32(
+        row_ptr.data_ptr(), _nonempty(col, torch.int32).data_ptr(), n_rows, x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt,
+        _ptr(x_dst), 0 if x_dst is None else x_dst.stride(0), Fd, _ptr(self_rows), int(bool(x_dst_ids)),
+        None if D == 0 else _nonempty(edge_attr, torch.float32).data_ptr(), D, u.data_ptr(), u.stride(0), _ptr(w),
+        0 if w is None else w.stride(0), int(H), wt.data_ptr(), wt.stride(0), N, _ptr(bias), int(bool(relu)), out.data_ptr(),
+        out.stride(0), None if alpha is None or alpha.numel() == 0 else alpha.data_ptr(), _ptr(a_save), get_stream()),
+        "wgamd_transformer_layer_f32")
+    return out
+
+
+def _tconv_rows_ok(t) -> bool:
+    """``t`` [rows, F] is what the transformer kernels read in place: float32 on the device, unit column stride, 16-B aligned
+    rows."""
+    return (t.dtype == torch.float32 and t.is_cuda and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0)
+
+
+def _tconv_rows(t):
+    """``t`` as the kernels read it: float32, and a contiguous copy when its rows are strided or not 16-B aligned (a fresh
+    allocation is; F is a multiple of 4 in the kernel's domain).  Under autograd: the gradient reaches ``t``."""
+    t = t.float()
+    if not _tconv_rows_ok(t):
+        t = t.contiguous() if not t.is_contiguous() else t.clone()
+    return t
+
+
+class _TconvLayer(torch.autograd.Function):
+    """The one-kernel transformer layer over a ``LayerGraph`` (one ``wgamd_transformer_layer_f32`` launch per hop), from the
+    aggregate-first folds ``u``, ``w`` and ``wt`` (built from the parameters under autograd by the caller: their gradients
+    reach the parameters through autograd over small tensors).  When training the forward keeps alpha [E, H] and the rows A
+    [n, K] — A is both the weight gradient's operand (dWstack = A^T dZ, a library GEMM) and what gives the softmax backward its
+    row sums (dA_ih . A_ih), so keeping it costs one [n, K] write and saves rebuilding it.  Backward: dA = dZ Wstack^T (library
+    GEMM), then ``wgamd_transformer_bwd_dst_f32`` per hop (du, dw, ds) and, for x, ``wgamd_transformer_bwd_src_f32`` over each
+    hop's transpose (no atomics).  The edge-attribute gradient, when asked for, is library ops."""
+
+    @staticmethod
+    def forward(ctx, x, x_dst, u, w, edge_attr, wt, bias, graph, ids, relu, H, skip, n_src, want_alpha):
+        lg, dev = graph, wt.device
+        n, N, F_ = lg.n_rows, wt.shape[0], x.shape[1]
+        D = 0 if edge_attr is None else edge_attr.shape[1]
+        train = any(ctx.needs_input_grad[:7])
+        E = sum(int(h.col.shape[0]) for h in lg.hops)
+        out = torch.empty((n, N), dtype=torch.float32, device=dev)
+        alpha = torch.empty((E, H), dtype=torch.float32, device=dev) if (train or want_alpha) else None
+        A = torch.empty((n, wt.shape[1]), dtype=torch.float32, device=dev) if train else None
+        wt_d, b_d = wt.detach().contiguous(), None if bias is None else bias.detach()
+        u_d, w_d = u.detach().contiguous(), None if w is None else w.detach().contiguous()
+        xd = x_dst if x_dst is not None else x
+        at = eat = 0
+        for h in lg.hops:
+            nh, Eh = h.n_rows, int(h.col.shape[0])
+            if nh > 0:
+                transformer_layer_forward(
+                    h.row_ptr, h.col, x, u_d[at:at + nh], wt_d, H, self_rows=h.self_rows, x_dst=xd if skip else None,
+                    x_dst_ids=ids is not None and x_dst is None, edge_attr=None if D == 0 else edge_attr[eat:eat + Eh],
+                    w=None if w_d is None else w_d[at:at + nh], bias=b_d, relu=relu, src_ids=ids, out=out[at:at + nh],
+                    alpha=None if alpha is None else alpha[eat:eat + Eh], a_save=None if A is None else A[at:at + nh])
+            at += nh
+            eat += Eh
+        ctx.set_materialize_grads(False)
+        if train:
+            ctx.save_for_backward(u_d, w_d, wt_d, out, alpha, A)
+            ctx.x, ctx.edge_attr, ctx.graph, ctx.ids, ctx.relu, ctx.H, ctx.skip, ctx.n_src = x, edge_attr, lg, ids, relu, H, skip, n_src
+            ctx.bipartite = x_dst is not None
+        if want_alpha:
+            ctx.mark_non_differentiable(alpha)
+            return out, alpha
+        return out
+
+    @staticmethod
+    def backward(ctx, g, *unused):
+        u, w, wt, out, alpha, A = ctx.saved_tensors
+        need_x, need_xd, need_u, need_w, need_ea, need_wt, need_b = ctx.needs_input_grad[:7]
+        x, ea, lg, H = ctx.x, ctx.edge_attr, ctx.graph, ctx.H
+        dev, F_ = wt.device, x.shape[1]
+        D = 0 if ea is None else ea.shape[1]
+        W4 = transformer_block_width(F_, D)
+        n = lg.n_rows
+        gx = gxd = gu = gw = gea = gwt = gb = None
+        if g is None:
+            g = torch.zeros_like(out)
+        gz = g.contiguous().float()
+        if ctx.relu:
+            gz = torch.ops.aten.threshold_backward(gz, out, 0)
+        if need_wt:
+            gwt = gz.t() @ A
+        if need_b:
+            gb = gz.sum(0)
+        if need_x or need_xd or need_u or need_w or need_ea:
+            dA = (gz @ wt).contiguous()                                          # [n, K]
+            E = alpha.shape[0]
+            du = torch.empty((n, H * F_), dtype=torch.float32, device=dev)
+            dw = torch.empty((n, H * D), dtype=torch.float32, device=dev) if D else None
+            ds = torch.empty((E, H), dtype=torch.float32, device=dev)
+            ids_ptr, ids_dt = _gcn_args(x, ctx.ids)
+            at = eat = 0
+            for h in lg.hops:
+                nh, Eh = h.n_rows, int(h.col.shape[0])
+                if nh > 0:
+                    L.check(L.lib().wgamd_transformer_bwd_dst_f32(
+                        h.row_ptr.data_ptr(), _nonempty(h.col, torch.int32).data_ptr(), nh, x.data_ptr(), x.stride(0), F_, ids_ptr,
+                        ids_dt, None if D == 0 else _nonempty(ea[eat:eat + Eh], torch.float32).data_ptr(), D, H,
+                        _nonempty(alpha[eat:eat + Eh], torch.float32).data_ptr(), dA[at:at + nh].data_ptr(), dA.stride(0),
+                        A[at:at + nh].data_ptr(), A.stride(0), du[at:at + nh].data_ptr(), None if dw is None else dw[at:at + nh].data_ptr(),
+                        _nonempty(ds[eat:eat + Eh], torch.float32).data_ptr(), get_stream()), "wgamd_transformer_bwd_dst_f32")
+                at += nh
+                eat += Eh
+            gu, gw = du, dw
+            if need_x:
+                gx = torch.zeros((ctx.n_src, F_), dtype=torch.float32, device=dev)
+                # the skip block reaches x only when the destinations are rows of x itself (not an (x_src, x_dst) pair,
+                # whose self_rows index x_dst)
+                own_skip = ctx.skip and not ctx.bipartite
+                skip_at = H * W4 if own_skip else -1
+                at = eat = 0
+                for h in lg.hops:
+                    nh, Eh = h.n_rows, int(h.col.shape[0])
+                    if nh > 0:
+                        row_ptr_t, col_t, self_t, perm = h.transposed(ctx.n_src, need_self=own_skip, need_perm=True)
+                        L.check(L.lib().wgamd_transformer_bwd_src_f32(
+                            row_ptr_t.data_ptr(), _nonempty(col_t, torch.int32).data_ptr(), perm.data_ptr(), _ptr(self_t), nh,
+                            ctx.n_src, F_, D, H, skip_at,
+                            _nonempty(alpha[eat:eat + Eh], torch.float32).data_ptr(), _nonempty(ds[eat:eat + Eh], torch.float32).data_ptr(),
+                            dA[at:at + nh].data_ptr(), dA.stride(0), u[at:at + nh].data_ptr(), u.stride(0), gx.data_ptr(), gx.stride(0), 1,
+                            get_stream()), "wgamd_transformer_bwd_src_f32")
+                    at += nh
+                    eat += Eh
+            if need_xd and ctx.skip:
+                gxd = dA[:, H * W4:].contiguous()
+            if need_ea and D:
+                gea = torch.zeros_like(ea)
+                dA3 = dA[:, :H * W4].view(n, H, W4)
+                w3 = w.view(n, H, D)
+                at = eat = 0
+                for h in lg.hops:
+                    nh, Eh = h.n_rows, int(h.col.shape[0])
+                    if Eh > 0:
+                        dst = at + torch.repeat_interleave(torch.arange(nh, device=dev), (h.row_ptr[1:] - h.row_ptr[:-1]).long(),
+                                                           output_size=Eh)
+                        a_e, s_e = alpha[eat:eat + Eh].unsqueeze(2), ds[eat:eat + Eh].unsqueeze(2)
+                        gea[eat:eat + Eh] = (a_e * dA3[dst, :, F_:F_ + D] + s_e * w3[dst]).sum(1)
+                    at += nh
+                    eat += Eh
+        ctx.x = ctx.edge_attr = None
+        return gx, gxd, gu, gw, gea, gwt, gb, None, None, None, None, None, None, None
+
+
+def _tconv_library_ops(conv, x_src, x_dst_rows, lg: LayerGraph, edge_attr, relu: bool):
+    """The layer in PyG's own formulation, composed of library ops under autograd: the route of shapes outside the one-kernel
+    layer's domain (correctness, not speed).  Returns ``(out, alpha)`` with alpha [E, H] hop-major in CSR order."""
+    H, C = conv.heads, conv.out_channels
+    outs, alphas, at, eat = [], [], 0, 0
+    for h in lg.hops:
+        nh, Eh = h.n_rows, int(h.col.shape[0])
+        xd = x_dst_rows[at:at + nh]
+        dst = torch.repeat_interleave(torch.arange(nh, device=xd.device), (h.row_ptr[1:] - h.row_ptr[:-1]).long(), output_size=Eh)
+        xs = x_src[h.col.long()]
+        q = conv.lin_query(xd).view(nh, H, C)
+        k = conv.lin_key(xs).view(Eh, H, C)
+        v = conv.lin_value(xs).view(Eh, H, C)
+        if conv.lin_edge is not None:
+            e = conv.lin_edge(edge_attr[eat:eat + Eh]).view(Eh, H, C)
+            k, v = k + e, v + e
+        s = (q[dst] * k).sum(-1) / math.sqrt(C)                                   # [E, H]
+        smax = s.new_full((nh, H), -math.inf).scatter_reduce(0, dst.unsqueeze(1).expand(Eh, H), s, "amax", include_self=True)
+        ex = (s - smax[dst]).exp()
+        den = s.new_zeros((nh, H)).index_add(0, dst, ex) + 1e-16
+        alpha = ex / den[dst]
+        o = s.new_zeros((nh, H, C)).index_add(0, dst, alpha.unsqueeze(2) * v)
+        o = o.reshape(nh, H * C) if conv.concat else o.mean(1)
+        if conv.root_weight:
+            o = o + conv.lin_skip(xd)
+        outs.append(o)
+        alphas.append(alpha)
+        at += nh
+        eat += Eh
+    out = torch.cat(outs) if outs else x_src.new_zeros((0, H * C if conv.concat else C))
+    alpha = torch.cat(alphas) if alphas else x_src.new_zeros((0, H))
+    return (torch.relu(out) if relu else out), alpha
+
+
+class TransformerConv(torch.nn.Module):
+    """PyG ``TransformerConv`` (flow source_to_target):
+        alpha_ij = softmax_j( q_i . (k_j + e_ij) / sqrt(C) ),   out_i = sum_j alpha_ij (v_j + e_ij)  [+ lin_skip(x_i)]
+    with ``q = lin_query(x_dst)``, ``k = lin_key(x_src)``, ``v = lin_value(x_src)``, ``e = lin_edge(edge_attr)`` (``edge_dim``),
+    per head; ``concat=True`` concatenates the heads ([N, H C]), ``concat=False`` averages them ([N, C]).  A destination with no
+    edges gets no message (no value bias), only the skip term.  Parameters as PyG names them (``lin_key``, ``lin_query``,
+    ``lin_value``, ``lin_skip``: ``weight`` [out, in] and ``bias``; ``lin_edge.weight``), initialised as ``torch.nn.Linear``
+    does, so a PyG ``state_dict`` loads.  ``lin_skip`` exists whatever ``root_weight`` says (as in PyG); ``bias`` is its bias.
+
+    ``forward(x, graph, edge_attr=None, act=None, return_attention_weights=False)``: ``graph`` = a COO ``edge_index`` (the ``for
+    batch in loader`` loop of mag_lp_mnmg.py with ``attr[batch.e_id]``; x a tensor or an ``(x_src, x_dst)`` pair, output rows
+    = the destination rows), a ``[csr_row_ptr, csr_col_ind]`` pair with ``edge_attr`` in CSR order (destinations = the first
+    rows of x, or x_dst), or a call group's ``LayerGraph`` with x a tensor or ``LazyRows`` and ``edge_attr`` hop-major in
+    ``CallGroup.e_id`` order (``CallGroup.edge_attr``; every layer takes the same tensor and reads the prefix of its hops).
+    ``edge_attr`` is [E, edge_dim] (or [E] when edge_dim is 1), floating, on the graph's device; a wrong length, width, dtype or
+    device, or none when ``edge_dim`` is set, raises ValueError (without ``edge_dim`` it is ignored, as in PyG).
+
+    The layer is computed aggregate-first: the logit is linear in x_j, so each destination keeps ``u = W_k^T q / sqrt(C)`` and
+    ``w = W_e^T q / sqrt(C)`` (one library GEMM over the destination rows) and ONE kernel per hop (``wgamd_transformer_layer_f32``)
+    walks the edges with an online softmax, builds ``[sum alpha [x_j | a_ij | 1] per head | x_dst]`` and multiplies it by the
+    stacked value / edge / skip weight on the fp32 matrix pipe, bias and ``act="relu"`` fused.  The backward is two more kernels
+    and library GEMMs, without atomics (the same bits from run to run).  Inputs of another floating dtype, or with strided or
+    misaligned rows, are first copied to float32 rows (a lazy table of that kind is gathered).  Shapes outside the kernel's
+    domain (``transformer_layer_supported``: in_channels multiples of 4 and <= 256, edge_dim <= 32, heads <= 8, output width
+    <= 256, K <= 1024), and inputs on the CPU, run the WHOLE layer as library ops in PyG's formulation — correct, not fast.
+    Other keyword arguments of PyG's are refused (TypeError) except its defaults ``aggr="add"`` and ``node_dim=0``.
+    ``return_attention_weights=True`` also returns alpha [E, H] (not differentiable): ``(out, (edge_index, alpha))`` in the
+    edge_index's order for a COO graph, ``(out, alpha)`` in CSR / hop-major order otherwise.
+
+    Not supported: ``beta=True`` (NotImplementedError at construction) and attention dropout (``dropout > 0`` raises
+    NotImplementedError in training mode; in eval mode dropout is the identity, as in PyG)."""
+
+    def __init__(self, in_channels: Union[int, Tuple[int, int]], out_channels: int, heads: int = 1, concat: bool = True,
+                 beta: bool = False, dropout: float = 0.0, edge_dim: Optional[int] = None, bias: bool = True,
+                 root_weight: bool = True, **kwargs):
+        super().__init__()
+        for k, v in kwargs.items():
+            if not ((k == "aggr" and v == "add") or (k == "node_dim" and v == 0)):
+                raise TypeError("TransformerConv: unsupported argument %s=%r (of PyG's MessagePassing arguments only the defaults "
+                                "aggr='add' and node_dim=0 are accepted)" % (k, v))
+        if beta:
+            raise NotImplementedError("TransformerConv: beta=True (the gated skip connection) is not supported")
+        if heads < 1 or out_channels < 1:
+            raise ValueError("TransformerConv: heads and out_channels must be positive")
+        if isinstance(in_channels, int):
+            in_channels = (in_channels, in_channels)
+        self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, concat
+        self.in_src, self.in_dst = int(in_channels[0]), int(in_channels[1])
+        self.beta, self.dropout, self.edge_dim, self.root_weight = beta, float(dropout), edge_dim, root_weight
+        HC = heads * out_channels
+        self.lin_key = torch.nn.Linear(self.in_src, HC)
+        self.lin_query = torch.nn.Linear(self.in_dst, HC)
+        self.lin_value = torch.nn.Linear(self.in_src, HC)
+        self.lin_edge = torch.nn.Linear(edge_dim, HC, bias=False) if edge_dim is not None else None
+        self.lin_skip = torch.nn.Linear(self.in_dst, HC if concat else out_channels, bias=bias)
+        self._folded = None
+
+    def reset_parameters(self):
+        for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_edge, self.lin_skip):
+            if lin is not None:
+                lin.reset_parameters()
+
+    @property
+    def _out_width(self) -> int:
+        return self.heads * self.out_channels if self.concat else self.out_channels
+
+    def _folds(self):
+        """``transformer_folds`` in float32: under autograd when a parameter needs a gradient, else cached against the
+        parameters' versions (as ``HeteroConv._rel``)."""
+        params = [p for p in self.parameters()]
+        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            return [None if t is None else t.float() for t in transformer_folds(self)]
+        key = tuple((p._version, p.data_ptr(), p.device) for p in params) + (_weights_gen,)
+        if self._folded is None or self._folded[0] != key:
+            with torch.no_grad():
+                f = [None if t is None else t.float().contiguous() for t in transformer_folds(self)]
+            self._folded = (key, f)
+        return self._folded[1]
+
+    def _check_edge_attr(self, edge_attr, n_edges: int, device):
+        """The edge attribute as the kernels read it (float32 [E, D] contiguous), or None without edge_dim; ValueError on a
+        missing one or a wrong length, width, dtype or device — before any launch."""
+        if self.edge_dim is None:
+            return None
+        D = self.edge_dim
+        if edge_attr is None:
+            raise ValueError("TransformerConv: edge_dim=%d needs edge_attr" % D)
+        if not torch.is_tensor(edge_attr) or not edge_attr.is_floating_point():
+            raise ValueError("TransformerConv: edge_attr must be a floating-point tensor")
+        if edge_attr.dim() == 1 and D == 1:
+            edge_attr = edge_attr.unsqueeze(1)
+        if edge_attr.dim() != 2 or edge_attr.shape[1] != D:
+            raise ValueError("TransformerConv: edge_attr has shape %s, the layer takes [E, %d]" % (tuple(edge_attr.shape), D))
+        if edge_attr.device != torch.device(device):
+            raise ValueError("TransformerConv: edge_attr is on %s, the graph on %s" % (edge_attr.device, torch.device(device)))
+        if edge_attr.shape[0] != n_edges:
+            raise ValueError("TransformerConv: edge_attr has %d rows for %d edges" % (edge_attr.shape[0], n_edges))
+        return edge_attr
+
+    def _forward_layer(self, x, lg: LayerGraph, edge_attr, act, x_dst=None, want_alpha=False):
+        """``x`` (tensor or LazyRows) over a layer graph; ``x_dst`` (bipartite, one hop with self_rows = arange): the destination
+        rows.  Returns ``(out, alpha or None)`` with alpha hop-major in CSR order."""
+        assert act in (None, "relu"), "act: None or 'relu'"
+        relu = act == "relu"
+        lazy = isinstance(x, LazyRows)
+        src = x.table if lazy else x
+        n_src = len(x) if lazy else x.shape[0]
+        H, N, D = self.heads, self._out_width, self.edge_dim or 0
+        if x.shape[1] != self.in_src:
+            raise ValueError("TransformerConv: x has %d features, the layer takes %d" % (x.shape[1], self.in_src))
+        if x_dst is not None and x_dst.shape[1] != self.in_dst:
+            raise ValueError("TransformerConv: x_dst has %d features, the layer takes %d" % (x_dst.shape[1], self.in_dst))
+        if x_dst is None and self.in_src != self.in_dst:
+            raise ValueError("TransformerConv: in_channels = %s needs an (x_src, x_dst) pair" % (self.in_channels,))
+        n_edges = sum(int(h.col.shape[0]) for h in lg.hops)
+        total = getattr(lg, "num_group_edges", None)
+        dev = lg.hops[0].row_ptr.device if lg.hops else src.device
+        ea = self._check_edge_attr(edge_attr, total if total is not None else n_edges, dev)
+        grad_on = torch.is_grad_enabled()
+        if lazy and grad_on and getattr(src, "requires_grad", False):
+            raise NotImplementedError("gradient w.r.t. a feature table read through ids (LazyRows): trainable node "
+                                      "embeddings go through wholegraph_amd.embedding, or pass x = emb[n_id]")
+        skip = self.root_weight
+        kernel = transformer_layer_supported(self.in_src, self.in_dst if skip else 0, D, H, N) and src.is_cuda and (
+            x_dst is None or x_dst.is_cuda)
+        if kernel:
+            # rows as the kernel reads them (float32, unit column stride, 16-B aligned rows): copied (under autograd) when they
+            # are not; a lazy table that is not is gathered
+            if lazy and not _tconv_rows_ok(src):
+                x, lazy = x.materialize(), False
+            if not lazy:
+                x = src = _tconv_rows(x)
+            if x_dst is not None:
+                x_dst = _tconv_rows(x_dst)
+        self_all = torch.cat([h.self_rows for h in lg.hops]) if lg.hops else torch.zeros(0, dtype=torch.int64, device=dev)
+        # the destination rows as a tensor: the query's input (and the skip's, on the library route)
+        if x_dst is not None:
+            xd_rows = x_dst
+        elif lazy:
+            xd_rows = src[x.ids[self_all].long()] if not getattr(src, "byte_offset_ids", False) else x.materialize()[self_all]
+        else:
+            xd_rows = x[self_all]
+        if kernel:
+            Fu, bu, Fw, bw, wt, bias = self._folds()
+            xq = xd_rows.float()
+            u = torch.addmm(bu, xq, Fu)
+            w = torch.addmm(bw, xq, Fw) if D else None
+            eak = None if ea is None else ea.float().contiguous()
+            res = _TconvLayer.apply(src, x_dst, u, w, eak, wt, bias, lg, x.ids if lazy else None, relu, H, skip, n_src,
+                                    want_alpha)
+            return res if want_alpha else (res, None)
+        xs = x.materialize() if lazy else x
+        out, alpha = _tconv_library_ops(self, xs.float(), xd_rows.float(), lg, None if ea is None else ea.float(), relu)
+        return out, (alpha.detach() if want_alpha else None)
+
+    def forward(self, x, graph, edge_attr=None, act=None, return_attention_weights=False):
+        if self.dropout > 0 and self.training:
+            raise NotImplementedError("TransformerConv: attention dropout (dropout > 0 in training mode) is not supported")
+        if _capturing():
+            raise RuntimeError("wholegraph_amd.nn.TransformerConv is not supported under HIP-graph capture (loader.PerBatchStep): "
+                               "its per-graph caches are not capture-safe; SAGEConv layers are")
+        if isinstance(graph, HeteroLayerGraph):
+            raise NotImplementedError("TransformerConv over a heterogeneous call group's layer graph is not supported")
+        x_dst = None
+        if isinstance(x, (tuple, list)):
+            x, x_dst = x
+        for t in (x, x_dst):
+            if t is not None and not isinstance(t, LazyRows) and (not torch.is_tensor(t) or not t.is_floating_point()):
+                raise ValueError("TransformerConv: featureless input (x = None or node indices) is not supported; pass node features")
+        if x is None:
+            raise ValueError("TransformerConv: featureless input (x = None or node indices) is not supported; pass node features")
+        if isinstance(graph, LayerGraph):
+            if x_dst is not None:
+                raise NotImplementedError("TransformerConv: an (x_src, x_dst) pair over a LayerGraph is not supported")
+            out, alpha = self._forward_layer(x, graph, edge_attr, act, want_alpha=return_attention_weights)
+            return (out, alpha) if return_attention_weights else out
+        if isinstance(x, LazyRows):
+            x = x.materialize()
+        if isinstance(x_dst, LazyRows):
+            x_dst = x_dst.materialize()
+        n_dst = x.shape[0] if x_dst is None else x_dst.shape[0]
+        order = None
+        if isinstance(graph, (tuple, list)):
+            row_ptr, col = graph[0], graph[1]          # [csr_row_ptr, csr_col_ind]: destinations = the first rows of x (or x_dst)
+            _check_csr(row_ptr, col)
+            n_dst = row_ptr.shape[0] - 1
+            ea = self._check_edge_attr(edge_attr, col.shape[0], row_ptr.device)
+        else:
+            ea = self._check_edge_attr(edge_attr, graph.shape[1], graph.device)
+            src_ids, dst = graph[0], graph[1]
+            order = torch.sort(dst, stable=True).indices  # destination-major, edge order kept inside a destination
+            col = src_ids[order].to(torch.int32).contiguous()
+            ea = None if ea is None else ea[order]
+            row_ptr = torch.zeros(n_dst + 1, dtype=torch.int32, device=dst.device)
+            row_ptr[1:] = torch.cumsum(torch.bincount(dst, minlength=n_dst), 0)
+        if x_dst is not None and x_dst.shape[0] < n_dst:
+            raise ValueError("TransformerConv: x_dst has %d rows for %d destinations" % (x_dst.shape[0], n_dst))
+        if x_dst is None and x.shape[0] < n_dst:
+            raise ValueError("TransformerConv: x has %d rows for %d destinations" % (x.shape[0], n_dst))
+        hop = HopGraph(row_ptr, col, _arange(n_dst, x.device))
+        if x_dst is not None:
+            x_dst = x_dst[:n_dst]
+        out, alpha = self._forward_layer(x, LayerGraph([hop]), ea, act, x_dst=x_dst, want_alpha=return_attention_weights)
+        if not return_attention_weights:
+            return out
+        if order is None:
+            return out, alpha
+        a = torch.empty_like(alpha)
+        a[order] = alpha
+        return out, (graph, a)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -815,6 +815,47 @@ wholememory_error_code_t wgamd_rgcn_wgrad_f32(const float* x, int64_t ldx, int F
                                               const int64_t* item_start, const int64_t* seg_ptr, int n_seg, int64_t pairs_per_item,
                                               int64_t max_items, float* M, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- Graph transformer layer (csrc/wg_transformer.hip): torch_geometric.nn.TransformerConv over a sampled hop ---------------------
+ * The model of the reference's cugraph-pyg example mag_lp_mnmg.py, aggregate-first:
+ *   s[e, h]  = u[i, h F + :] . X[j]  +  w[i, h D + :] . edge_attr[e]          (e = (j -> i); u, w already scaled by 1 / sqrt(C))
+ *   alpha    = softmax over the edges of row i of s[:, h]
+ *   A[i]     = [ blk_0 | ... | blk_(H-1) | XD[self_rows[i]] ],  blk_h = sum_e alpha[e, h] [X[j] | edge_attr[e] | 1 | 0 ...]
+ *   out[i]   = act( A[i] @ Wstack + bias )
+ * X[r] = x[src_ids ? src_ids[r] : r] (INT, INT64 or WGAMD_IDS_BYTE_OFFSETS); XD[r] = x_dst[r], or x_dst[src_ids[r]] with
+ * x_dst_ids.  Each head block is W4 = wgamd_transformer_block_width(F_src, D) = ceil4(F_src + D + 1) wide; K = H W4 + F_dst
+ * (F_dst = 0: no skip block).  The weight goes in transposed: wt [N, ldwt] = Wstack^T.  edge_attr [E, D] row-major in CSR
+ * order.  A row without edges has a zero aggregate.  alpha (optional, [E, H]) receives the attention weights, a_save (optional,
+ * [n_rows, K] row-major, 16-B aligned) the rows A — what the backward reads.  Sums run in CSR order: run-to-run deterministic.
+ * Domain: wgamd_transformer_layer_supported (F_src, F_dst multiples of 4 and <= 256, D <= 32, H <= 8, N <= 256, K <= 1024);
+ * x / x_dst / u / wt rows 16-B aligned.  The product runs on the exact fp32 matrix pipe (v_mfma_f32_16x16x4_f32).
+ * wgamd_transformer_bwd_dst_f32 (destination-major, given dA = dZ Wstack^T [n_rows, ldda] and the saved A): per edge and head
+ * dalpha = dA[i, blk_h] . [X[j] | edge_attr[e] | 1] and ds = alpha (dalpha - dA[i, blk_h] . A[i, blk_h]); du [n_rows, H F_src]
+ * = sum_e ds X[j], dw [n_rows, H D] = sum_e ds edge_attr[e], ds [E, H].
+ * wgamd_transformer_bwd_src_f32 (source-major over the hop's transpose: row_ptr_t / col_t = destination rows / perm = CSR edge
+ * of every transposed entry, over n_src input rows and the hop's n_rows destinations):
+ *   gx[j] (+)= sum_e sum_h (alpha dA[i, h W4 + :F] + ds u[i, h F + :])  +  dA[self_t[j] - n_rows, skip_at + :]
+ * where self_t[j] = n_rows + i when input row j is destination i (the skip term; any other value, a null self_t or
+ * skip_at < 0: none) — HopGraph.transposed's self_t.  No atomics: the same bits from run to run. */
+int wgamd_transformer_layer_supported(int F_src, int F_dst, int D, int H, int N);
+int wgamd_transformer_block_width(int F_src, int D);
+wholememory_error_code_t wgamd_transformer_layer_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx,
+                                                     int F_src, const void* src_ids, wholememory_dtype_t src_ids_dtype,
+                                                     const float* x_dst, int64_t ldx_dst, int F_dst, const int64_t* self_rows,
+                                                     int x_dst_ids, const float* edge_attr, int D, const float* u, int64_t ldu,
+                                                     const float* w, int64_t ldw, int H, const float* wt, int64_t ldwt, int N,
+                                                     const float* bias, int relu, float* out, int64_t ldo, float* alpha, float* a_save,
+                                                     void* stream);
+wholememory_error_code_t wgamd_transformer_bwd_dst_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx,
+                                                       int F_src, const void* src_ids, wholememory_dtype_t src_ids_dtype,
+                                                       const float* edge_attr, int D, int H, const float* alpha, const float* dA,
+                                                       int64_t ldda, const float* A, int64_t lda, float* du, float* dw, float* ds,
+                                                       void* stream);
+wholememory_error_code_t wgamd_transformer_bwd_src_f32(const int* row_ptr_t, const int* col_t, const int* perm, const int64_t* self_t,
+                                                       int64_t n_rows, int64_t n_src, int F_src, int D, int H, int skip_at,
+                                                       const float* alpha, const float* ds, const float* dA, int64_t ldda,
+                                                       const float* u, int64_t ldu, float* gx, int64_t ldgx, int accumulate,
+                                                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
