@@ -7,46 +7,25 @@
 // Pieces:
 //   * gcn_degrees_kernel — dinv of a layer's input rows from the hops that have those rows as destinations: one launch for
 //     all hops of a layer graph (the degree of a vertex is the one of its row in the hop whose frontier it is in).
-//   * gcn_layer_kernel — the whole layer, one launch per hop: 16-row tiles (WG_GCN_TILE_ROWS), 4 waves.  Phase 1: lane groups of LG lanes
+//   * gcn_layer_kernel — the whole layer, one launch per hop: 16-row tiles, 4 waves.  Phase 1: lane groups of LG lanes
 //     (LG >= F / 4; one float4 of a row per lane) walk a destination row's edges 8 at a time (ids, dinv and rows of 8 edges
 //     in flight per lane group), sum in CSR order and store the normalised aggregate row to the LDS tile (and to agg_out for
-//     the weight gradient).  Phase 2: the [64 x F] tile times W^T on the exact fp32 matrix pipe (v_mfma_f32_16x16x4_f32):
-//     wave w owns the 16-column tiles w, w + 4, w + 8, w + 12 and every 16-row tile; a lane reads one float4 of the tile
-//     (ds_read_b128) and one float4 of a weight row per 16 k — the four k of a float4 are four MFMA k-steps — so W is read
-//     in its torch.nn.Linear layout [N, F], no transposed copy.  Occupancy (several tiles per CU) overlaps the two phases;
-//     the layer is bound by the latency of phase 1's dependent loads (row bounds -> column ids -> node ids / dinv -> rows),
-//     so small tiles (more of them resident per CU, fewer accumulators) beat large ones: 16 rows 4.14 ms, 32 rows 4.38,
-//     64 rows 5.03 at the products layer-1 shape (tools/bench_gcn.py).
+//     the weight gradient).  Phase 2: the [16 x F] tile times W^T (tile_times_wt, wg_layer_parts.hpp); W is read in its
+//     torch.nn.Linear layout [N, F], no transposed copy.  Occupancy (several tiles per CU) overlaps the two phases; the layer
+//     is bound by the latency of phase 1's dependent loads (row bounds -> column ids -> node ids / dinv -> rows), so small
+//     tiles (more of them resident per CU, fewer accumulators) beat large ones: 16 rows 4.14 ms, 32 rows 4.38, 64 rows 5.03
+//     at the products layer-1 shape (tools/bench_gcn.py).
 //     The same kernel runs the input gradient over the hop's transpose (dinv_src / dinv_dst swapped, W^T as the weight).
 //   * gcn_aggregate_kernel — the normalised aggregate alone for any F (shapes outside the layer kernel's domain: the
 //     caller multiplies with a library GEMM).
 //   * gcn_wgrad_kernel + gcn_wgrad_reduce_kernel — dW = dZ^T agg, db = colsum(dZ) (ReLU mask folded into dZ): split-K over
 //     row ranges on fp32 MFMA, partial sums added in workgroup order (no atomics: the same bits from run to run).
-#include "wg_common.hpp"
-#include "wgamd_ext.h"
+#include "wg_layer_parts.hpp"
 
 namespace wgamd {
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-#ifndef WG_GCN_TILE_ROWS
-#define WG_GCN_TILE_ROWS 16
-#endif
-constexpr int kTileRows = WG_GCN_TILE_ROWS;
-constexpr int kRT       = kTileRows / 16;   // 16-row MFMA tiles per tile
-constexpr int kThreads  = 256;
-constexpr int kUnroll   = 8;
-
-// id kinds: 0 = x is indexed by the row itself, 1 = int32 node list, 2 = int64 node list, 3 = int64 BYTE offsets from x
-template <int KIND>
-__device__ __forceinline__ const float* x_row(const float* x, int64_t ldx, const void* ids, int64_t r)
-{
-  if constexpr (KIND == 0) return x + r * ldx;
-  else if constexpr (KIND == 1) return x + (int64_t) static_cast<const int32_t*>(ids)[r] * ldx;
-  else if constexpr (KIND == 2) return x + static_cast<const int64_t*>(ids)[r] * ldx;
-  else return reinterpret_cast<const float*>(reinterpret_cast<const char*>(x) + static_cast<const int64_t*>(ids)[r]);
-}
+constexpr int kUnroll = 8;
 
 struct gcn_args {
   const int* row_ptr;
@@ -124,7 +103,7 @@ template <int KIND, int LG>
 __global__ void __launch_bounds__(kThreads) gcn_layer_kernel(gcn_args a)
 {
   extern __shared__ __attribute__((aligned(16))) float tile[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.x * kTileRows;
 
   // ---- phase 1: the normalised aggregate rows of the tile -> LDS (and agg_out) ----
@@ -143,53 +122,8 @@ __global__ void __launch_bounds__(kThreads) gcn_layer_kernel(gcn_args a)
   }
   __syncthreads();
 
-  // ---- phase 2: [64 x F16] tile @ W^T on v_mfma_f32_16x16x4_f32 ----
-  const int n_ct = (a.N + 15) / 16;
-  if (wave >= n_ct) return;
-  const int m = lane & 15, g = lane >> 4;
-  f32x4 acc[kRT][4];
-#pragma unroll
-  for (int rt = 0; rt < kRT; ++rt)
-#pragma unroll
-    for (int k = 0; k < 4; ++k) acc[rt][k] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int kb = 0; kb < a.F16; kb += 16) {
-    const int k = kb + 4 * g;
-    f32x4 av[kRT];
-#pragma unroll
-    for (int rt = 0; rt < kRT; ++rt) av[rt] = *reinterpret_cast<const f32x4*>(tile + (rt * 16 + m) * a.SD + k);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int ct = wave + 4 * q;
-      if (ct < n_ct) {
-        const int n = ct * 16 + m;
-        f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-        if (n < a.N && k < a.F) bv = *reinterpret_cast<const f32x4*>(a.w + (int64_t)n * a.ldw + k);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk)
-#pragma unroll
-          for (int rt = 0; rt < kRT; ++rt)
-            acc[rt][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[rt][kk], bv[kk], acc[rt][q], 0, 0, 0);
-      }
-    }
-  }
-  // C/D map of the 16x16 MFMA: col = lane & 15, row = 4 (lane >> 4) + reg
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int n = (wave + 4 * q) * 16 + m;
-    if (wave + 4 * q >= n_ct || n >= a.N) continue;
-    const float b = a.bias ? a.bias[n] : 0.f;
-#pragma unroll
-    for (int rt = 0; rt < kRT; ++rt)
-#pragma unroll
-      for (int reg = 0; reg < 4; ++reg) {
-        const int64_t i = row0 + rt * 16 + 4 * g + reg;
-        if (i < a.n_rows) {
-          float y = acc[rt][q][reg] + b;
-          if (a.relu) y = fmaxf(y, 0.f);
-          a.out[i * a.ldo + n] = y;
-        }
-      }
-  }
+  // ---- phase 2: [16 x F16] tile @ W^T ----
+  tile_times_wt(tile, a.SD, a.F, a.F16, a.w, a.ldw, a.N, a.bias, a.relu, a.out, a.ldo, row0, a.n_rows);
 }
 
 // normalised aggregate only, any F: one wave per row, one feature per lane and 64-feature block
@@ -333,34 +267,15 @@ int wgrad_grid_x(int64_t n_rows)
   return (int)std::max<int64_t>(1, std::min<int64_t>(kWgradMaxGridX, (n_rows + 511) / 512));
 }
 
-int ids_kind(const void* src_ids, wholememory_dtype_t dt)
-{
-  if (src_ids == nullptr) return 0;
-  if (dt == WHOLEMEMORY_DT_INT) return 1;
-  if (dt == WHOLEMEMORY_DT_INT64) return 2;
-  if (dt == WGAMD_IDS_BYTE_OFFSETS) return 3;
-  throw invalid_input("src_ids must be INT, INT64 or WGAMD_IDS_BYTE_OFFSETS");
-}
-
-template <int KIND, int LG>
-void launch_layer_lg(const gcn_args& a, hipStream_t st)
-{
-  const dim3 grid((unsigned)((a.n_rows + kTileRows - 1) / kTileRows));
-  const size_t lds = (size_t)kTileRows * a.SD * 4;     // (66.5 KB at 64 rows and F = 256: above the 64 KB default)
-  auto kern        = gcn_layer_kernel<KIND, LG>;
-  WG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  kern<<<grid, kThreads, lds, st>>>(a);
-}
-
 template <int KIND>
 void launch_layer(const gcn_args& a, hipStream_t st)
 {
   const int c4 = a.F / 4;
-  if (c4 <= 4) launch_layer_lg<KIND, 4>(a, st);
-  else if (c4 <= 8) launch_layer_lg<KIND, 8>(a, st);
-  else if (c4 <= 16) launch_layer_lg<KIND, 16>(a, st);
-  else if (c4 <= 32) launch_layer_lg<KIND, 32>(a, st);
-  else launch_layer_lg<KIND, 64>(a, st);
+  if (c4 <= 4) launch_tiles(gcn_layer_kernel<KIND, 4>, a, st);
+  else if (c4 <= 8) launch_tiles(gcn_layer_kernel<KIND, 8>, a, st);
+  else if (c4 <= 16) launch_tiles(gcn_layer_kernel<KIND, 16>, a, st);
+  else if (c4 <= 32) launch_tiles(gcn_layer_kernel<KIND, 32>, a, st);
+  else launch_tiles(gcn_layer_kernel<KIND, 64>, a, st);
 }
 
 gcn_args make_args(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx, int F, const void* src_ids,
@@ -424,21 +339,13 @@ extern "C" wholememory_error_code_t wgamd_gcn_layer_f32_train(const int* row_ptr
     WG_REQUIRE_INPUT(ldw >= F && ldo >= N && (agg_out == nullptr || ld_agg >= F), "leading dimension too small");
     const int kind = ids_kind(src_ids, src_ids_dtype);
     WG_REQUIRE_INPUT(kind == 3 || ldx >= F, "leading dimension too small");
-    if ((kind != 3 && ldx % 4 != 0) || (reinterpret_cast<uintptr_t>(x) & 15) != 0 || ldw % 4 != 0 ||
-        (reinterpret_cast<uintptr_t>(w) & 15) != 0 ||
-        (agg_out && (ld_agg % 4 != 0 || (reinterpret_cast<uintptr_t>(agg_out) & 15) != 0)))
+    if (!aligned_rows(x, kind == 3 ? 0 : ldx) || !aligned_rows(w, ldw) || (agg_out && !aligned_rows(agg_out, ld_agg)))
       throw logic_error("x / w / agg_out rows must be 16-B aligned");
     gcn_args a = make_args(row_ptr, col, n_rows, x, ldx, F, src_ids, self_rows, edge_weight, dinv_src, dinv_dst, fill, flags);
     a.w = w, a.ldw = ldw, a.N = N, a.bias = bias, a.out = out, a.ldo = ldo, a.agg_out = agg_out, a.ld_agg = ld_agg;
     a.F16 = (F + 15) / 16 * 16;
     a.SD  = a.F16 + 4;      // rows 4 banks apart: the 16 rows of a fragment read spread over the 64 banks
-    auto st = static_cast<hipStream_t>(stream);
-    switch (kind) {
-      case 0: launch_layer<0>(a, st); break;
-      case 1: launch_layer<1>(a, st); break;
-      case 2: launch_layer<2>(a, st); break;
-      default: launch_layer<3>(a, st); break;
-    }
+    with_kind(kind, [&](auto k) { launch_layer<decltype(k)::value>(a, static_cast<hipStream_t>(stream)); });
     WG_HIP_CHECK(hipGetLastError());
   });
 }
@@ -471,12 +378,7 @@ extern "C" wholememory_error_code_t wgamd_gcn_aggregate_f32(const int* row_ptr, 
     a.out = out, a.ldo = ldo;
     auto st = static_cast<hipStream_t>(stream);
     const unsigned blocks = (unsigned)((n_rows + 3) / 4);
-    switch (kind) {
-      case 0: gcn_aggregate_kernel<0><<<blocks, 256, 0, st>>>(a); break;
-      case 1: gcn_aggregate_kernel<1><<<blocks, 256, 0, st>>>(a); break;
-      case 2: gcn_aggregate_kernel<2><<<blocks, 256, 0, st>>>(a); break;
-      default: gcn_aggregate_kernel<3><<<blocks, 256, 0, st>>>(a); break;
-    }
+    with_kind(kind, [&](auto k) { gcn_aggregate_kernel<decltype(k)::value><<<blocks, 256, 0, st>>>(a); });
     WG_HIP_CHECK(hipGetLastError());
   });
 }

@@ -13,33 +13,19 @@
 //     is K = (B + root) F floats, K / 4 <= 256 float4 chunks, one chunk per thread held in a register while the thread walks
 //     the edges of its rows (edge metadata of 16 edges in flight, then their row chunks), flushed to the LDS tile at each row
 //     boundary.  When K / 4 <= 128 several rows are built at once (P = 2, 4, ... slots of K / 4 threads).  Phase 2: the
-//     [16 x K] tile times the stacked weight [basis_0; ...; basis_{B-1}; root] on the exact fp32 matrix pipe
-//     (v_mfma_f32_16x16x4_f32) as in wg_gcn.hip; the weight is passed transposed ([N, K]) so a lane reads one float4 along k.
+//     [16 x K] tile times the stacked weight [basis_0; ...; basis_{B-1}; root] (tile_times_wt, wg_layer_parts.hpp); the
+//     weight is passed transposed ([N, K]) so a lane reads one float4 along k.
 //     The same kernel runs the input gradient over the hop's transpose (dZ as x, basis_b^T / root^T as the weight).
 //   * rgcn_wgrad_kernel + rgcn_wgrad_reduce_kernel — M[s] = sum_{p in segment s} c_p X[src_p]^T G[dst_p] over (source row,
 //     gradient row, coefficient) pairs sorted by segment (relation, or R for the root's self pairs): work items of at most S
 //     pairs of one segment on fp32 MFMA, the item partials added in item order — no atomics, the same bits from run to run.
-#include "wg_common.hpp"
-#include "wgamd_ext.h"
+#include "wg_layer_parts.hpp"
 
 namespace wgamd {
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-constexpr int kTileRows = 16;
-constexpr int kThreads  = 256;
-constexpr int kUnroll   = 16;
-constexpr int kMaxK     = 1024;
-
-template <int KIND>
-__device__ __forceinline__ const float* x_row(const float* x, int64_t ldx, const void* ids, int64_t r)
-{
-  if constexpr (KIND == 0) return x + r * ldx;
-  else if constexpr (KIND == 1) return x + (int64_t) static_cast<const int32_t*>(ids)[r] * ldx;
-  else if constexpr (KIND == 2) return x + static_cast<const int64_t*>(ids)[r] * ldx;
-  else return reinterpret_cast<const float*>(reinterpret_cast<const char*>(x) + static_cast<const int64_t*>(ids)[r]);
-}
+constexpr int kUnroll = 16;
+constexpr int kMaxK   = 1024;
 
 // ---- per-edge coefficients ----------------------------------------------------------------------------------------------------
 template <typename T>
@@ -111,7 +97,7 @@ __global__ void __launch_bounds__(kThreads) rgcn_layer_kernel(rgcn_args a)
 {
   extern __shared__ __attribute__((aligned(16))) float tile[];
   __shared__ int rp[kTileRows + 1];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.x * kTileRows;
   const int rows_here = (int)std::min<int64_t>(kTileRows, a.n_rows - row0);
   if (tid <= kTileRows) rp[tid] = a.row_ptr[row0 + std::min(tid, rows_here)];
@@ -180,44 +166,8 @@ __global__ void __launch_bounds__(kThreads) rgcn_layer_kernel(rgcn_args a)
   }
   __syncthreads();
 
-  // ---- phase 2: [16 x K16] tile @ wt^T on v_mfma_f32_16x16x4_f32; wave w owns the 16-column tiles w, w + 4, ... ----
-  const int n_ct = (a.N + 15) / 16;
-  if (wave >= n_ct) return;
-  const int m = lane & 15, g = lane >> 4;
-  f32x4 acc[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) acc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int kb = 0; kb < a.K16; kb += 16) {
-    const int k = kb + 4 * g;
-    const f32x4 av = *reinterpret_cast<const f32x4*>(tile + m * a.SD + k);
-#pragma unroll
-    for (int qq = 0; qq < 4; ++qq) {
-      const int ct = wave + 4 * qq;
-      if (ct < n_ct) {
-        const int n = ct * 16 + m;
-        f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-        if (n < a.N && k < a.K) bv = *reinterpret_cast<const f32x4*>(a.wt + (int64_t)n * a.ldw + k);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) acc[qq] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], bv[kk], acc[qq], 0, 0, 0);
-      }
-    }
-  }
-  // C/D map of the 16x16 MFMA: col = lane & 15, row = 4 (lane >> 4) + reg
-#pragma unroll
-  for (int qq = 0; qq < 4; ++qq) {
-    const int n = (wave + 4 * qq) * 16 + m;
-    if (wave + 4 * qq >= n_ct || n >= a.N) continue;
-    const float bb = a.bias ? a.bias[n] : 0.f;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int64_t i = row0 + 4 * g + reg;
-      if (i < a.n_rows) {
-        float y = acc[qq][reg] + bb;
-        if (a.relu) y = fmaxf(y, 0.f);
-        a.out[i * a.ldo + n] = y;
-      }
-    }
-  }
+  // ---- phase 2: [16 x K16] tile @ wt^T ----
+  tile_times_wt(tile, a.SD, a.K, a.K16, a.wt, a.ldw, a.N, a.bias, a.relu, a.out, a.ldo, row0, a.n_rows);
 }
 
 // ---- weight gradient --------------------------------------------------------------------------------------------------------
@@ -292,25 +242,6 @@ __global__ void rgcn_wgrad_reduce_kernel(const float* __restrict__ part, const i
   }
 }
 
-int ids_kind(const void* src_ids, wholememory_dtype_t dt)
-{
-  if (src_ids == nullptr) return 0;
-  if (dt == WHOLEMEMORY_DT_INT) return 1;
-  if (dt == WHOLEMEMORY_DT_INT64) return 2;
-  if (dt == WGAMD_IDS_BYTE_OFFSETS) return 3;
-  throw invalid_input("src_ids must be INT, INT64 or WGAMD_IDS_BYTE_OFFSETS");
-}
-
-template <int KIND>
-void launch_layer(const rgcn_args& a, hipStream_t st)
-{
-  const dim3 grid((unsigned)((a.n_rows + kTileRows - 1) / kTileRows));
-  const size_t lds = (size_t)kTileRows * a.SD * 4;     // 16 x (1024 + 4) floats = 65.8 KB at the largest K: above the 64 KB default
-  auto kern        = rgcn_layer_kernel<KIND>;
-  WG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  kern<<<grid, kThreads, lds, st>>>(a);
-}
-
 }  // namespace
 }  // namespace wgamd
 
@@ -370,16 +301,8 @@ extern "C" wholememory_error_code_t wgamd_rgcn_layer_f32(const int* row_ptr, con
     while (a.P < kTileRows && 2 * a.P * a.Q <= kThreads) a.P *= 2;
     WG_REQUIRE_INPUT(kind == 3 || ldx >= F, "leading dimension too small");
     WG_REQUIRE_INPUT(ldw >= a.K, "leading dimension too small");
-    if ((kind != 3 && ldx % 4 != 0) || (reinterpret_cast<uintptr_t>(x) & 15) != 0 || ldw % 4 != 0 ||
-        (reinterpret_cast<uintptr_t>(wt) & 15) != 0)
-      throw logic_error("x / wt rows must be 16-B aligned");
-    auto st = static_cast<hipStream_t>(stream);
-    switch (kind) {
-      case 0: launch_layer<0>(a, st); break;
-      case 1: launch_layer<1>(a, st); break;
-      case 2: launch_layer<2>(a, st); break;
-      default: launch_layer<3>(a, st); break;
-    }
+    if (!aligned_rows(x, kind == 3 ? 0 : ldx) || !aligned_rows(wt, ldw)) throw logic_error("x / wt rows must be 16-B aligned");
+    with_kind(kind, [&](auto k) { launch_tiles(rgcn_layer_kernel<decltype(k)::value>, a, static_cast<hipStream_t>(stream)); });
     WG_HIP_CHECK(hipGetLastError());
   });
 }
@@ -412,12 +335,10 @@ extern "C" wholememory_error_code_t wgamd_rgcn_wgrad_f32(const float* x, int64_t
       WG_REQUIRE_INPUT(ldg >= N, "leading dimension too small");
       float* part = static_cast<float*>(workspace);
       const dim3 grid((unsigned)max_items, (F + 63) / 64);
-      switch (kind) {
-        case 0: rgcn_wgrad_kernel<0><<<grid, 256, 0, st>>>(x, ldx, F, src_ids, pair_src, pair_dst, pair_coef, grad, ldg, N, item_start, seg_ptr, n_seg, pairs_per_item, part); break;
-        case 1: rgcn_wgrad_kernel<1><<<grid, 256, 0, st>>>(x, ldx, F, src_ids, pair_src, pair_dst, pair_coef, grad, ldg, N, item_start, seg_ptr, n_seg, pairs_per_item, part); break;
-        case 2: rgcn_wgrad_kernel<2><<<grid, 256, 0, st>>>(x, ldx, F, src_ids, pair_src, pair_dst, pair_coef, grad, ldg, N, item_start, seg_ptr, n_seg, pairs_per_item, part); break;
-        default: rgcn_wgrad_kernel<3><<<grid, 256, 0, st>>>(x, ldx, F, src_ids, pair_src, pair_dst, pair_coef, grad, ldg, N, item_start, seg_ptr, n_seg, pairs_per_item, part); break;
-      }
+      with_kind(kind, [&](auto k) {
+        rgcn_wgrad_kernel<decltype(k)::value><<<grid, 256, 0, st>>>(x, ldx, F, src_ids, pair_src, pair_dst, pair_coef, grad, ldg, N,
+                                                                      item_start, seg_ptr, n_seg, pairs_per_item, part);
+      });
       WG_HIP_CHECK(hipGetLastError());
     }
     const int64_t total = (int64_t)n_seg * FN;

@@ -15,37 +15,23 @@
 //     The finished row goes to the LDS tile (and, when training, to A in global memory: the weight gradient reads it, and the
 //     backward's row sums sum_j alpha dalpha are dA_ih . A_ih — cheaper to keep than to rebuild).  The logits are written to
 //     alpha [E, H] as they are made and turned into alpha by a second pass over the row once its max and sum are known.
-//     Phase 2: the [16 x K] tile times Wstack (passed transposed, [N, K]) on the exact fp32 matrix pipe
-//     (v_mfma_f32_16x16x4_f32) as in wg_rgcn.hip, bias and ReLU fused.
+//     Phase 2: the [16 x K] tile times Wstack (passed transposed, [N, K]; tile_times_wt, wg_layer_parts.hpp), bias and
+//     ReLU fused.
 //   * tconv_bwd_dst_kernel — destination-major: per edge and head dalpha = dA_ih . [X[j] | a_ij | 1] and
 //     ds = alpha (dalpha - dA_ih . A_ih); du_ih = sum ds X[j], dw_ih = sum ds a_ij, ds written [E, H].  One wave per row.
 //   * tconv_bwd_src_kernel — source-major over the hop's transpose (HopGraph.transposed with the edge permutation):
 //     dX[j] = sum_e sum_h (alpha dA_ih[:F] + ds u_ih) plus the skip block of dA where input row j is a destination itself.
 //     One wave per input row.
 // No atomics anywhere: every sum runs in CSR (or transposed-CSR) order, the same bits from run to run.
-#include "wg_common.hpp"
-#include "wgamd_ext.h"
+#include "wg_layer_parts.hpp"
 
 namespace wgamd {
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-constexpr int kTileRows = 16;
-constexpr int kThreads  = 256;
-constexpr int kMaxK     = 1024;
-constexpr int kMaxF     = 256;     // one float4 of a source row per lane
-constexpr int kMaxD     = 32;      // [a | 1 | pad] within one wave's lanes
-constexpr int kMaxH     = 8;
-
-template <int KIND>
-__device__ __forceinline__ const float* x_row(const float* x, int64_t ldx, const void* ids, int64_t r)
-{
-  if constexpr (KIND == 0) return x + r * ldx;
-  else if constexpr (KIND == 1) return x + (int64_t) static_cast<const int32_t*>(ids)[r] * ldx;
-  else if constexpr (KIND == 2) return x + static_cast<const int64_t*>(ids)[r] * ldx;
-  else return reinterpret_cast<const float*>(reinterpret_cast<const char*>(x) + static_cast<const int64_t*>(ids)[r]);
-}
+constexpr int kMaxK = 1024;
+constexpr int kMaxF = 256;     // one float4 of a source row per lane
+constexpr int kMaxD = 32;      // [a | 1 | pad] within one wave's lanes
+constexpr int kMaxH = 8;
 
 // sum over the wave; xor butterflies give every lane the same bits (each step adds the same two values, commuted)
 __device__ __forceinline__ float wave_sum(float v)
@@ -199,44 +185,8 @@ __global__ void __launch_bounds__(kThreads) tconv_layer_kernel(tconv_args a)
       reinterpret_cast<f32x4*>(a.a_save + (row0 + p / K4) * a.K)[p % K4] = reinterpret_cast<const f32x4*>(tile + (p / K4) * a.SD)[p % K4];
   }
 
-  // ---- phase 2: [16 x K16] tile @ wt^T on v_mfma_f32_16x16x4_f32; wave w owns the 16-column tiles w, w + 4, ... ----
-  const int n_ct = (a.N + 15) / 16;
-  if (wave >= n_ct) return;
-  const int mm = lane & 15, g = lane >> 4;
-  f32x4 cacc[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) cacc[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int kb = 0; kb < a.K16; kb += 16) {
-    const int k = kb + 4 * g;
-    const f32x4 av = *reinterpret_cast<const f32x4*>(tile + mm * a.SD + k);
-#pragma unroll
-    for (int qq = 0; qq < 4; ++qq) {
-      const int ct = wave + 4 * qq;
-      if (ct < n_ct) {
-        const int n = ct * 16 + mm;
-        f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-        if (n < a.N && k < a.K) bv = *reinterpret_cast<const f32x4*>(a.wt + (int64_t)n * a.ldwt + k);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) cacc[qq] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], bv[kk], cacc[qq], 0, 0, 0);
-      }
-    }
-  }
-  // C/D map of the 16x16 MFMA: col = lane & 15, row = 4 (lane >> 4) + reg
-#pragma unroll
-  for (int qq = 0; qq < 4; ++qq) {
-    const int n = (wave + 4 * qq) * 16 + mm;
-    if (wave + 4 * qq >= n_ct || n >= a.N) continue;
-    const float bb = a.bias ? a.bias[n] : 0.f;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int64_t i = row0 + 4 * g + reg;
-      if (i < a.n_rows) {
-        float y = cacc[qq][reg] + bb;
-        if (a.relu) y = fmaxf(y, 0.f);
-        a.out[i * a.ldo + n] = y;
-      }
-    }
-  }
+  // ---- phase 2: [16 x K16] tile @ wt^T ----
+  tile_times_wt(tile, a.SD, a.K, a.K16, a.wt, a.ldwt, a.N, a.bias, a.relu, a.out, a.ldo, row0, a.n_rows);
 }
 
 // ---- destination-major backward ---------------------------------------------------------------------------------------------
@@ -359,35 +309,16 @@ __global__ void __launch_bounds__(256) tconv_bwd_src_kernel(const int* __restric
   *o = accumulate ? *o + g : g;
 }
 
-int ids_kind(const void* src_ids, wholememory_dtype_t dt)
-{
-  if (src_ids == nullptr) return 0;
-  if (dt == WHOLEMEMORY_DT_INT) return 1;
-  if (dt == WHOLEMEMORY_DT_INT64) return 2;
-  if (dt == WGAMD_IDS_BYTE_OFFSETS) return 3;
-  throw invalid_input("src_ids must be INT, INT64 or WGAMD_IDS_BYTE_OFFSETS");
-}
-
 int heads_bucket(int H) { return H <= 1 ? 1 : H <= 2 ? 2 : H <= 4 ? 4 : 8; }
-
-template <int KIND, int HM>
-void launch_layer(const tconv_args& a, hipStream_t st)
-{
-  const dim3 grid((unsigned)((a.n_rows + kTileRows - 1) / kTileRows));
-  const size_t lds = (size_t)kTileRows * a.SD * 4;
-  auto kern        = tconv_layer_kernel<KIND, HM>;
-  WG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  kern<<<grid, kThreads, lds, st>>>(a);
-}
 
 template <int KIND>
 void launch_layer_h(const tconv_args& a, hipStream_t st)
 {
   switch (heads_bucket(a.H)) {
-    case 1: launch_layer<KIND, 1>(a, st); break;
-    case 2: launch_layer<KIND, 2>(a, st); break;
-    case 4: launch_layer<KIND, 4>(a, st); break;
-    default: launch_layer<KIND, 8>(a, st); break;
+    case 1: launch_tiles(tconv_layer_kernel<KIND, 1>, a, st); break;
+    case 2: launch_tiles(tconv_layer_kernel<KIND, 2>, a, st); break;
+    case 4: launch_tiles(tconv_layer_kernel<KIND, 4>, a, st); break;
+    default: launch_tiles(tconv_layer_kernel<KIND, 8>, a, st); break;
   }
 }
 
@@ -450,17 +381,10 @@ extern "C" wholememory_error_code_t wgamd_transformer_layer_f32(
     WG_REQUIRE_INPUT(kind == 3 || ldx >= F_src, "leading dimension too small");
     WG_REQUIRE_INPUT(F_dst == 0 || (x_dst_ids && kind == 3) || ldx_dst >= F_dst, "leading dimension too small");
     WG_REQUIRE_INPUT(ldwt >= a.K, "leading dimension too small");
-    const auto mis = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
-    if ((kind != 3 && ldx % 4 != 0) || mis(x) || (F_dst > 0 && (mis(x_dst) || ldx_dst % 4 != 0)) || ldwt % 4 != 0 || mis(wt) ||
-        mis(u) || ldu % 4 != 0 || (a_save && mis(a_save)))
+    if (!aligned_rows(x, kind == 3 ? 0 : ldx) || (F_dst > 0 && !aligned_rows(x_dst, ldx_dst)) || !aligned_rows(wt, ldwt) ||
+        !aligned_rows(u, ldu) || (a_save && !aligned_rows(a_save, 0)))
       throw logic_error("x / x_dst / u / wt / a_save rows must be 16-B aligned");
-    auto st = static_cast<hipStream_t>(stream);
-    switch (kind) {
-      case 0: launch_layer_h<0>(a, st); break;
-      case 1: launch_layer_h<1>(a, st); break;
-      case 2: launch_layer_h<2>(a, st); break;
-      default: launch_layer_h<3>(a, st); break;
-    }
+    with_kind(kind, [&](auto k) { launch_layer_h<decltype(k)::value>(a, static_cast<hipStream_t>(stream)); });
     WG_HIP_CHECK(hipGetLastError());
   });
 }
@@ -484,16 +408,9 @@ extern "C" wholememory_error_code_t wgamd_transformer_bwd_dst_f32(
     a.du = du, a.dw = dw, a.ds = ds;
     WG_REQUIRE_INPUT(ldda >= (int64_t)H * a.W4 && lda >= (int64_t)H * a.W4, "leading dimension too small");
     WG_REQUIRE_INPUT(kind == 3 || ldx >= F_src, "leading dimension too small");
-    const auto mis = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
-    if ((kind != 3 && ldx % 4 != 0) || mis(x) || mis(dA) || ldda % 4 != 0 || mis(A) || lda % 4 != 0 || mis(du))
+    if (!aligned_rows(x, kind == 3 ? 0 : ldx) || !aligned_rows(dA, ldda) || !aligned_rows(A, lda) || !aligned_rows(du, 0))
       throw logic_error("x / dA / A / du rows must be 16-B aligned");
-    auto st = static_cast<hipStream_t>(stream);
-    switch (kind) {
-      case 0: launch_bwd_h<0>(a, st); break;
-      case 1: launch_bwd_h<1>(a, st); break;
-      case 2: launch_bwd_h<2>(a, st); break;
-      default: launch_bwd_h<3>(a, st); break;
-    }
+    with_kind(kind, [&](auto k) { launch_bwd_h<decltype(k)::value>(a, static_cast<hipStream_t>(stream)); });
     WG_HIP_CHECK(hipGetLastError());
   });
 }
@@ -513,8 +430,7 @@ extern "C" wholememory_error_code_t wgamd_transformer_bwd_src_f32(
     const int W4 = wgamd::block_width(F_src, D);
     WG_REQUIRE_INPUT(ldda >= (int64_t)H * W4 && ldu >= (int64_t)H * F_src && ldgx >= F_src, "leading dimension too small");
     WG_REQUIRE_INPUT(skip_at < 0 || (skip_at % 4 == 0 && ldda >= (int64_t)skip_at + F_src), "bad skip offset");
-    const auto mis = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; };
-    if (mis(dA) || ldda % 4 != 0 || mis(u) || ldu % 4 != 0 || mis(gx) || ldgx % 4 != 0)
+    if (!aligned_rows(dA, ldda) || !aligned_rows(u, ldu) || !aligned_rows(gx, ldgx))
       throw logic_error("dA / u / gx rows must be 16-B aligned");
     auto st = static_cast<hipStream_t>(stream);
     wgamd::tconv_bwd_src_kernel<<<(unsigned)((n_src + 3) / 4), 256, 0, st>>>(row_ptr_t, col_t, perm, self_t, n_rows, n_src, F_src, H,

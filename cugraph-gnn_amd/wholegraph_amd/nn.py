@@ -25,6 +25,24 @@ def _ids_code(x, src_ids) -> int:
     return L.IDS_BYTE_OFFSETS if getattr(x, "byte_offset_ids", False) else torch_dtype_to_wm(src_ids.dtype)
 
 
+def _ids_args(x, src_ids):
+    """``(src_ids, src_ids_dtype)`` arguments of the layer kernels: null when ``x`` is read by row."""
+    ids_ptr, ids_dt = None, 0
+    if src_ids is not None:
+        assert src_ids.is_contiguous()
+        ids_ptr, ids_dt = src_ids.data_ptr(), _ids_code(x, src_ids)
+    return ids_ptr, ids_dt
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _nonempty(t, dtype):
+    """``t``, or a one-element buffer when ``t`` is empty (the kernels take no null pointer for a hop's edge arrays)."""
+    return t if t.numel() > 0 else torch.zeros(1, dtype=dtype, device=t.device)
+
+
 def _check_csr(row_ptr, col):
     assert row_ptr.dtype == torch.int32 and col.dtype == torch.int32, "per-hop CSR is int32 (sampler output)"
     assert row_ptr.is_cuda and col.is_cuda and row_ptr.is_contiguous() and col.is_contiguous()
@@ -146,6 +164,14 @@ def bump_weight_generation():
 
 def _capturing() -> bool:
     return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+def _refuse_capture(layer, caches: str):
+    """RuntimeError under HIP-graph capture for a layer that keeps ``caches`` in Python (derived weights against the parameters'
+    versions, or per-graph forms against the graph object): a replayed graph would keep using the ones of the capture."""
+    if _capturing():
+        raise RuntimeError("wholegraph_amd.nn.%s is not supported under HIP-graph capture (loader.PerBatchStep): its %s are not "
+                           "capture-safe; SAGEConv layers are" % (type(layer).__name__, caches))
 
 
 def _padded_head(w_t: torch.Tensor, bias, Np: int):
@@ -755,38 +781,56 @@ class _GatCsr(torch.autograd.Function):
         return gx.reshape(x.shape), ga_src, ga_dst, None, None, None, None
 
 
-def _to_csr(edge_index, n_dst):
-    """edge_index [2,E] (row 0 = source j, row 1 = destination i; PyG) -> destination-major CSR (edge order kept inside a
-    destination).  int64 ids on the device go through ``wgamd_coo_to_csr_i64`` (one radix sort over the bits a destination
-    id needs); anything else through the torch formulation of the same."""
-    ready = getattr(edge_index, "_wgamd_csr", None)      # (version, n_dst, row_ptr, col): made by the loader for its call group
-    if ready is not None and ready[0] == edge_index._version and ready[1] == n_dst:
-        return ready[2], ready[3]
-    src, dst = edge_index[0], edge_index[1]
+def _single_hop(graph, n_dst, *edge_arrays):
+    """A layer's ``graph`` argument as a one-hop ``LayerGraph`` whose destinations are the first rows of the layer's input:
+    ``(lg, order, *edge_arrays)`` with every per-edge array (None passes through) in the hop's CSR order.
+
+    ``graph`` is a ``[csr_row_ptr, csr_col_ind]`` pair (``n_dst`` is then its row count) or a COO ``edge_index`` [2, E] (row 0 =
+    source j, row 1 = destination i; PyG) over ``n_dst`` destinations.  ``order`` (CSR edge k is COO edge ``order[k]``) is None
+    when the edges are destination-major already: a CSR pair, or a loader's edge list; otherwise it is the order of a stable sort
+    on the destination, so the CSR is the same on every route (edge order kept inside a destination).  int64 ids on the device
+    go through ``wgamd_coo_to_csr_i64`` (one radix sort over the bits a destination id needs), anything else through the torch
+    formulation of the same."""
+    order = None
+    ready = getattr(graph, "_wgamd_csr", None)      # (version, n_dst, row_ptr, col): made by the loader for its call group
+    if isinstance(graph, (tuple, list)):
+        row_ptr, col = graph[0], graph[1]
+        _check_csr(row_ptr, col)
+    elif ready is not None and ready[0] == graph._version and ready[1] == n_dst:
+        row_ptr, col = ready[2], ready[3]
     # (the flag is the tensor's version counter at the time the loader vouched for the order: an in-place edit of the
     #  edge list afterwards — a permutation, self loops written into the same storage — bumps the counter and the sort runs)
-    if getattr(edge_index, "_wgamd_dst_sorted", None) == edge_index._version and edge_index.is_cuda:
+    elif getattr(graph, "_wgamd_dst_sorted", None) == graph._version and graph.is_cuda:
         # the loaders' own edge lists are destination-major already (hop after hop, a hop's edges in the CSR order of its
         # frontier, every hop's destinations after the previous hop's): the CSR is a search for the run boundaries and a cast
         # — no sort (0.77 ms per 88 k-edge mini-batch through the radix sort below, most of it launch latency)
-        row_ptr = torch.searchsorted(dst.contiguous(), torch.arange(n_dst + 1, device=dst.device, dtype=dst.dtype)).to(torch.int32)
-        return row_ptr, src.to(torch.int32).contiguous()
-    if edge_index.dtype == torch.int64 and edge_index.is_cuda:
-        src, dst = src.contiguous(), dst.contiguous()
+        dst = graph[1].contiguous()
+        row_ptr = torch.searchsorted(dst, torch.arange(n_dst + 1, device=dst.device, dtype=dst.dtype)).to(torch.int32)
+        col = graph[0].to(torch.int32).contiguous()
+    elif graph.dtype == torch.int64 and graph.is_cuda:
+        src, dst = graph[0].contiguous(), graph[1].contiguous()
         E, dev = dst.shape[0], dst.device
         row_ptr = torch.empty(n_dst + 1, dtype=torch.int32, device=dev)
         col = torch.empty(E, dtype=torch.int32, device=dev)
+        order = torch.empty(E, dtype=torch.int32, device=dev)
         need = L.lib().wgamd_coo_to_csr_workspace_bytes(E, n_dst)
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        L.check(L.lib().wgamd_coo_to_csr_i64(src.data_ptr(), dst.data_ptr(), E, n_dst, row_ptr.data_ptr(), col.data_ptr(), None,
-                                             ws.data_ptr(), need, get_stream()), "wgamd_coo_to_csr_i64")
-        return row_ptr, col
-    order = torch.sort(dst, stable=True).indices
-    col = src[order].to(torch.int32).contiguous()
-    counts = torch.bincount(dst, minlength=n_dst)
-    row_ptr = torch.zeros(n_dst + 1, dtype=torch.int32, device=dst.device)
-    row_ptr[1:] = torch.cumsum(counts, 0)
-    return row_ptr, col
+        L.check(L.lib().wgamd_coo_to_csr_i64(src.data_ptr(), dst.data_ptr(), E, n_dst, row_ptr.data_ptr(), col.data_ptr(),
+                                             order.data_ptr(), ws.data_ptr(), need, get_stream()), "wgamd_coo_to_csr_i64")
+    else:
+        src, dst = graph[0], graph[1]
+        order = torch.sort(dst, stable=True).indices
+        col = src[order].to(torch.int32).contiguous()
+        row_ptr = torch.zeros(n_dst + 1, dtype=torch.int32, device=dst.device)
+        row_ptr[1:] = torch.cumsum(torch.bincount(dst, minlength=n_dst), 0)
+    lg = LayerGraph([HopGraph(row_ptr, col, _arange(row_ptr.shape[0] - 1, row_ptr.device))])
+    return (lg, order) + tuple(t if t is None or order is None else t[order] for t in edge_arrays)
+
+
+def _to_csr(edge_index, n_dst):
+    """The destination-major CSR ``(row_ptr, col)`` of a COO ``edge_index`` (``_single_hop``)."""
+    hop = _single_hop(edge_index, n_dst)[0].hops[0]
+    return hop.row_ptr, hop.col
 
 
 _ARANGE = {}
@@ -1020,7 +1064,7 @@ class HopGraph:
             else:
                 row_ptr_t, col_t = torch.zeros(n_src + 1, dtype=torch.int32, device=dev), self.col
                 perm = torch.zeros(1, dtype=torch.int32, device=dev) if need_perm else None
-            self._t = [key, row_ptr_t, col_t, None if stale else self._t[3], perm]
+            self._t = [key, row_ptr_t, col_t] + ([None, perm, None] if stale else [self._t[3], perm, self._t[5]])
         if need_self and self._t[3] is None:     # (only the layer kernel over the transposed hop reads it: three launches)
             n, dev = self.n_rows, self.row_ptr.device
             self_t = torch.full((n_src,), 2 * n, dtype=torch.int64, device=dev)
@@ -1028,6 +1072,17 @@ class HopGraph:
             self._t[3] = self_t
         res = tuple(self._t[1:4])
         return res + (self._t[4],) if need_perm else res
+
+    def input_dst(self, n_src: int):
+        """int64 [n_src]: the destination row that input row j is itself, -1 where there is none — the ``self_rows`` of a
+        GCN / RGCN layer kernel run over the transposed hop; kept with ``transposed``."""
+        self.transposed(n_src, need_self=False)
+        if self._t[5] is None:
+            dev = self.row_ptr.device
+            dst = torch.full((n_src,), -1, dtype=torch.int64, device=dev)
+            dst[self.self_rows] = torch.arange(self.n_rows, dtype=torch.int64, device=dev)
+            self._t[5] = dst
+        return self._t[5]
 
 
 class LayerGraph:
@@ -1044,6 +1099,54 @@ class LayerGraph:
     @property
     def n_rows(self):
         return sum(h.n_rows for h in self.hops)
+
+
+def _hops(lg: LayerGraph):
+    """``(hop, rows, edges)`` for every hop of ``lg``: the hop with the slices of the layer's output rows and of its hop-major
+    per-edge arrays that are the hop's."""
+    at = eat = 0
+    for h in lg.hops:
+        n, E = h.n_rows, int(h.col.shape[0])
+        yield h, slice(at, at + n), slice(eat, eat + E)
+        at += n
+        eat += E
+
+
+def _edge_dst(row_ptr, n_edges: int, first: int = 0):
+    """int64 [n_edges]: the destination row of every CSR edge, rows numbered from ``first``."""
+    n = row_ptr.shape[0] - 1
+    return torch.repeat_interleave(torch.arange(first, first + n, device=row_ptr.device), (row_ptr[1:] - row_ptr[:-1]).long(),
+                                   output_size=int(n_edges))
+
+
+def _kernel_rows_ok(t) -> bool:
+    """``t`` [rows, F] is what the layer kernels read in place: float32 on the device, unit column stride, 16-B aligned rows."""
+    return (t.dtype == torch.float32 and t.is_cuda and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0)
+
+
+def _layer_input(layer, x, lg: LayerGraph, F_: int):
+    """The input of a layer over ``lg`` as the one-kernel layers take it: ``(src, ids, n_src, n_edges)`` — the rows the kernel
+    reads (a ``LazyRows`` input: its table), the node list it reads them through (None: by row), the input's row count, and the
+    edge count the layer's per-edge arrays cover (a call group's layer graph: the whole group's, every layer reads the prefix
+    of its hops; any other: its hops').  ValueError when x is not ``F_`` wide; NotImplementedError for a gradient through a
+    lazy table."""
+    lazy = isinstance(x, LazyRows)
+    if x.shape[1] != F_:
+        raise ValueError("%s: x has %d features, the layer takes %d" % (type(layer).__name__, x.shape[1], F_))
+    src = x.table if lazy else x
+    if lazy and torch.is_grad_enabled() and getattr(src, "requires_grad", False):
+        raise NotImplementedError("gradient w.r.t. a feature table read through ids (LazyRows): trainable node "
+                                  "embeddings go through wholegraph_amd.embedding, or pass x = emb[n_id]")
+    total = getattr(lg, "num_group_edges", None)
+    n_edges = total if total is not None else sum(int(h.col.shape[0]) for h in lg.hops)
+    return src, (x.ids if lazy else None), (len(x) if lazy else x.shape[0]), n_edges
+
+
+def _refuse_featureless(layer, x):
+    """ValueError unless ``x`` holds node features (a floating tensor or ``LazyRows``)."""
+    if not isinstance(x, LazyRows) and not (torch.is_tensor(x) and x.is_floating_point()):
+        raise ValueError("%s: featureless input (x = None or node indices) is not supported; pass node features"
+                         % type(layer).__name__)
 
 
 _SAGE_DX_SMALL_ROWS = int(os.environ.get("WGAMD_SAGE_DX_SMALL_ROWS", 16384))
@@ -1351,11 +1454,8 @@ class GATConv(torch.nn.Module):
         return torch.relu(out) if act == "relu" else out
 
     def forward(self, x, graph, act=None):
-        if _capturing():
-            # (the derived forms of this layer's parameters — folded attention vectors, weight tiles, pooled buffers — are cached
-            #  in Python against the parameters' versions: a replayed graph would keep using the ones of the capture)
-            raise RuntimeError("wholegraph_amd.nn.%s is not supported under HIP-graph capture (loader.PerBatchStep): its "
-                               "derived-weight caches are not capture-safe; SAGEConv layers are" % type(self).__name__)
+        # (folded attention vectors, weight tiles, pooled buffers: cached against the parameters' versions)
+        _refuse_capture(self, "derived-weight caches")
         from . import graph_ops
         if isinstance(graph, LayerGraph):
             if self.in_channels % 4 == 0 and self.in_channels <= 256 and self.heads in (1, 2, 4, 8):
@@ -1392,10 +1492,6 @@ def gcn_layer_supported(F_: int, N: int) -> bool:
     return bool(L.lib().wgamd_gcn_layer_supported(int(F_), int(N)))
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def gcn_degrees(hops, out_base, n_out: int, fill: float = 1.0, add_self_loops: bool = True, edge_weights=None, device=None):
     """``dinv`` float32 [n_out] = deg^-1/2 of gcn_norm for the rows the hops' destinations are (``wgamd_gcn_degrees_f32``, one
     launch): row i of hop h is entry ``out_base[h] + i``, or ``self_rows[i]`` when ``out_base[h] < 0``.  Entries no hop reaches
@@ -1414,24 +1510,17 @@ def gcn_degrees(hops, out_base, n_out: int, fill: float = 1.0, add_self_loops: b
         assert h.self_rows.dtype == torch.int64 and h.self_rows.is_contiguous()
     n = len(hops)
     P, I = ctypes.c_void_p * n, ctypes.c_int64 * n
+    cols = [_nonempty(h.col, torch.int32) for h in hops]
     ew = None
     if edge_weights is not None:
         for w in edge_weights:
             assert w is None or (w.dtype == torch.float32 and w.is_contiguous())
         ew = P(*[_ptr(w) for w in edge_weights])
     L.check(L.lib().wgamd_gcn_degrees_f32(
-        n, P(*[h.row_ptr.data_ptr() for h in hops]), P(*[h.col.data_ptr() for h in hops]), P(*[h.self_rows.data_ptr() for h in hops]),
+        n, P(*[h.row_ptr.data_ptr() for h in hops]), P(*[c.data_ptr() for c in cols]), P(*[h.self_rows.data_ptr() for h in hops]),
         ew, I(*[h.n_rows for h in hops]), I(*[int(b) for b in out_base]), float(fill), int(bool(add_self_loops)), dinv.data_ptr(),
         int(n_out), get_stream()), "wgamd_gcn_degrees_f32")
     return dinv
-
-
-def _gcn_args(x, src_ids):
-    ids_ptr, ids_dt = None, 0
-    if src_ids is not None:
-        assert src_ids.is_contiguous()
-        ids_ptr, ids_dt = src_ids.data_ptr(), _ids_code(x, src_ids)
-    return ids_ptr, ids_dt
 
 
 def gcn_layer_forward(row_ptr, col, x, self_rows, weight, bias=None, dinv_src=None, dinv_dst=None, fill=1.0, add_self_loops=False,
@@ -1446,9 +1535,10 @@ def gcn_layer_forward(row_ptr, col, x, self_rows, weight, bias=None, dinv_src=No
     if out is None:
         out = torch.empty((n_rows, N), dtype=torch.float32, device=row_ptr.device)
     assert out.shape == (n_rows, N) and out.stride(1) == 1
-    ids_ptr, ids_dt = _gcn_args(x, src_ids)
+    ids_ptr, ids_dt = _ids_args(x, src_ids)
     flags = (GCN_ADD_SELF_LOOPS if add_self_loops else 0) | (GCN_RELU if relu else 0)
-    common = (row_ptr.data_ptr(), col.data_ptr(), n_rows, x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt, self_rows.data_ptr(),
+    common = (row_ptr.data_ptr(), _nonempty(col, torch.int32).data_ptr(), n_rows, x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt,
+              self_rows.data_ptr(),
               _ptr(edge_weight), _ptr(dinv_src), _ptr(dinv_dst), float(fill), weight.data_ptr(), weight.stride(0), N, _ptr(bias),
               flags, out.data_ptr(), out.stride(0))
     if agg_out is not None:
@@ -1469,9 +1559,9 @@ def gcn_aggregate(row_ptr, col, x, self_rows, dinv_src=None, dinv_dst=None, fill
     assert x.dtype == torch.float32 and x.stride(1) == 1 and self_rows.dtype == torch.int64 and self_rows.is_contiguous()
     if out is None:
         out = torch.empty((n_rows, F_), dtype=torch.float32, device=row_ptr.device)
-    ids_ptr, ids_dt = _gcn_args(x, src_ids)
+    ids_ptr, ids_dt = _ids_args(x, src_ids)
     L.check(L.lib().wgamd_gcn_aggregate_f32(
-        row_ptr.data_ptr(), col.data_ptr(), n_rows, x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt, self_rows.data_ptr(),
+        row_ptr.data_ptr(), _nonempty(col, torch.int32).data_ptr(), n_rows, x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt, self_rows.data_ptr(),
         _ptr(edge_weight), _ptr(dinv_src), _ptr(dinv_dst), float(fill), GCN_ADD_SELF_LOOPS if add_self_loops else 0,
         out.data_ptr(), out.stride(0), get_stream()), "wgamd_gcn_aggregate_f32")
     return out
@@ -1491,30 +1581,17 @@ def gcn_wgrad(agg, grad_out, grad_w, grad_bias=None, act_out=None, accumulate=Fa
                                         int(bool(accumulate)), ws.data_ptr(), ws.numel(), get_stream()), "wgamd_gcn_wgrad_f32")
 
 
-def _gcn_transposed(hop: HopGraph, n_src: int, edge_weight):
-    """``(row_ptr_t, col_t, self_t, edge_weight_t)`` of a hop seen from its input rows: the source-major CSR (hop order inside a
-    source row: deterministic sums), ``self_t[j]`` = the destination row that is input row j itself, -1 where there is none,
-    and the edge weights in source-major order."""
-    if edge_weight is None:
-        row_ptr_t, col_t, _ = hop.transposed(n_src, need_self=False)
-        w_t = None
-    else:
-        row_ptr_t, perm, _, col_t = _csr_transpose(hop.row_ptr, hop.col, n_src, want_perm=True, want_col_t=True)
-        w_t = edge_weight[perm.long()].contiguous()
-    key = (n_src, hop.self_rows.data_ptr())
-    st = getattr(hop, "_gcn_self_t", None)
-    if st is None or st[0] != key:
-        self_t = torch.full((n_src,), -1, dtype=torch.int64, device=hop.row_ptr.device)
-        self_t[hop.self_rows] = torch.arange(hop.n_rows, dtype=torch.int64, device=hop.row_ptr.device)
-        st = hop._gcn_self_t = (key, self_t)
-    return row_ptr_t, col_t, st[1], w_t
-
-
 def _gcn_input_grad(hop, g, n_src, dinv_in, conv, edge_weight, weight=None):
     """``A_hat^T g`` over one hop (rows = the layer's input rows), times ``weight`` ([F, Nq], the layer's W^T zero-padded to
     Nq rows) when given: the GCN kernel run over the hop's transpose — destination rows become the summed rows, so the
     per-row factor and the per-edge factor swap places (``dinv_dst`` = the input rows', ``dinv_src`` = the destinations')."""
-    row_ptr_t, col_t, self_t, w_t = _gcn_transposed(hop, n_src, edge_weight)
+    if edge_weight is None:
+        row_ptr_t, col_t, _ = hop.transposed(n_src, need_self=False)
+        w_t = None
+    else:
+        row_ptr_t, col_t, _, perm = hop.transposed(n_src, need_self=False, need_perm=True)
+        w_t = edge_weight[perm[:hop.col.shape[0]]]
+    self_t = hop.input_dst(n_src)
     d_out = dinv_in[hop.self_rows] if dinv_in is not None else None
     loops = conv.normalize and conv.add_self_loops
     if weight is None:
@@ -1537,22 +1614,18 @@ class _GcnLayer(torch.autograd.Function):
     def forward(ctx, src, weight, bias, conv, graph, dinv_in, ids, relu, edge_weights, n_src):
         N, F_ = weight.shape
         keep = any(ctx.needs_input_grad[:3])
-        if keep and ctx.needs_input_grad[0] and ids is not None:
-            raise NotImplementedError("gradient w.r.t. a feature table read through ids (LazyRows): trainable node "
-                                      "embeddings go through wholegraph_amd.embedding")
         out = torch.empty((graph.n_rows, N), dtype=torch.float32, device=weight.device)
-        aggs, at = [], 0
+        aggs = []
         w = weight.detach()
         b = bias.detach() if bias is not None else None
-        for k, h in enumerate(graph.hops):
+        for k, (h, rows, _) in enumerate(_hops(graph)):
             n = h.n_rows
             agg = torch.empty((n, F_), dtype=torch.float32, device=weight.device) if keep and ctx.needs_input_grad[1] and n > 0 else None
             if n > 0:
                 gcn_layer_forward(h.row_ptr, h.col, src, h.self_rows, w, b, relu=relu, src_ids=ids,
-                                  edge_weight=None if edge_weights is None else edge_weights[k], out=out[at:at + n], agg_out=agg,
+                                  edge_weight=None if edge_weights is None else edge_weights[k], out=out[rows], agg_out=agg,
                                   **_gcn_launch_args(conv, dinv_in))
             aggs.append(agg)
-            at += n
         if keep:
             ctx.save_for_backward(weight, out)
             ctx.conv, ctx.graph, ctx.dinv_in, ctx.relu, ctx.edge_weights, ctx.n_src, ctx.aggs = \
@@ -1583,21 +1656,19 @@ class _GcnLayer(torch.autograd.Function):
                 gq[:, :N] = g
             else:
                 gq = g
-        at, first = 0, True
-        for k, (h, agg) in enumerate(zip(ctx.graph.hops, ctx.aggs)):
-            n = h.n_rows
-            if n > 0:
+        first = True
+        for k, ((h, rows, _), agg) in enumerate(zip(_hops(ctx.graph), ctx.aggs)):
+            if h.n_rows > 0:
                 if need_w:
-                    gcn_wgrad(agg, g[at:at + n], gw, gb, None if act is None else act[at:at + n], accumulate=not first)
+                    gcn_wgrad(agg, g[rows], gw, gb, None if act is None else act[rows], accumulate=not first)
                 elif need_b:
-                    gz = g[at:at + n] if act is None else g[at:at + n] * (act[at:at + n] > 0)
+                    gz = g[rows] if act is None else g[rows] * (act[rows] > 0)
                     gb = gz.sum(0) if first else gb.add_(gz.sum(0))
                 first = False
                 if need_x:
-                    gh = _gcn_input_grad(h, gq[at:at + n], ctx.n_src, ctx.dinv_in, ctx.conv,
+                    gh = _gcn_input_grad(h, gq[rows], ctx.n_src, ctx.dinv_in, ctx.conv,
                                          None if ctx.edge_weights is None else ctx.edge_weights[k], weight=w_bwd)
                     gx = gh if gx is None else gx.add_(gh)
-            at += n
         if first:
             if gw is not None:
                 gw.zero_()
@@ -1629,29 +1700,15 @@ class _GcnAggregate(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         g = g.contiguous()
-        gx, at = None, 0
-        for k, h in enumerate(ctx.graph.hops):
-            n = h.n_rows
-            if n > 0:
-                gh = _gcn_input_grad(h, g[at:at + n], ctx.n_src, ctx.dinv_in, ctx.conv,
+        gx = None
+        for k, (h, rows, _) in enumerate(_hops(ctx.graph)):
+            if h.n_rows > 0:
+                gh = _gcn_input_grad(h, g[rows], ctx.n_src, ctx.dinv_in, ctx.conv,
                                      None if ctx.edge_weights is None else ctx.edge_weights[k])
                 gx = gh if gx is None else gx.add_(gh)
-            at += n
         if gx is None:
             gx = torch.zeros((ctx.n_src, g.shape[1]), dtype=torch.float32, device=g.device)
         return gx, None, None, None, None
-
-
-def _coo_to_csr_weighted(edge_index, edge_weight, n_dst):
-    """COO ``edge_index`` + per-edge weights -> destination-major CSR with the weights in CSR order (stable: edge order kept
-    inside a destination)."""
-    src, dst = edge_index[0], edge_index[1]
-    order = torch.sort(dst, stable=True).indices
-    col = src[order].to(torch.int32).contiguous()
-    w = edge_weight[order].to(torch.float32).contiguous()
-    row_ptr = torch.zeros(n_dst + 1, dtype=torch.int32, device=dst.device)
-    row_ptr[1:] = torch.cumsum(torch.bincount(dst, minlength=n_dst), 0)
-    return row_ptr, col, w
 
 
 class GCNConv(torch.nn.Module):
@@ -1706,28 +1763,18 @@ class GCNConv(torch.nn.Module):
     def _forward_layer(self, x, lg: LayerGraph, act=None, edge_weights=None):
         assert act in (None, "relu"), "act: None or 'relu'"
         relu = act == "relu"
-        lazy = isinstance(x, LazyRows)
-        src = x.table if lazy else x
-        n_src = len(x) if lazy else x.shape[0]
         F_, N = self.in_channels, self.out_channels
-        if x.shape[1] != F_:
-            raise ValueError("GCNConv: x has %d features, the layer takes %d" % (x.shape[1], F_))
+        src, ids, n_src, _ = _layer_input(self, x, lg, F_)
         dinv = self._dinv(lg, src.device)
-        if (gcn_layer_supported(F_, N) and src.dtype == torch.float32 and src.is_cuda and src.stride(1) == 1
-                and src.stride(0) % 4 == 0 and src.data_ptr() % 16 == 0):
-            return _GcnLayer.apply(src, self.lin.weight, self.bias, self, lg, dinv, x.ids if lazy else None, relu, edge_weights,
-                                   n_src)
-        xd = x.materialize() if lazy else x
+        if gcn_layer_supported(F_, N) and _kernel_rows_ok(src):
+            return _GcnLayer.apply(src, self.lin.weight, self.bias, self, lg, dinv, ids, relu, edge_weights, n_src)
+        xd = x.materialize() if isinstance(x, LazyRows) else x
         agg = _GcnAggregate.apply(xd.contiguous().float(), self, lg, dinv, edge_weights)
         out = torch.nn.functional.linear(agg, self.lin.weight, self.bias)
         return torch.relu(out) if relu else out
 
     def forward(self, x, graph, act=None, edge_weight=None):
-        if _capturing():
-            # (the degrees and transposes a layer graph keeps are cached in Python against the graph object: a replay would
-            #  keep using those of the capture)
-            raise RuntimeError("wholegraph_amd.nn.GCNConv is not supported under HIP-graph capture (loader.PerBatchStep): its "
-                               "per-graph degree caches are not capture-safe; SAGEConv layers are")
+        _refuse_capture(self, "per-graph degree caches")      # (degrees and transposes, cached against the graph object)
         if edge_weight is not None and torch.is_grad_enabled() and edge_weight.requires_grad:
             raise NotImplementedError("GCNConv: no gradient w.r.t. edge_weight")
         if isinstance(graph, LayerGraph):
@@ -1737,23 +1784,11 @@ class GCNConv(torch.nn.Module):
         if isinstance(x, LazyRows):
             x = x.materialize()
         n_src = x.shape[0]
-        if isinstance(graph, (tuple, list)):
-            row_ptr, col = graph[0], graph[1]          # [csr_row_ptr, csr_col_ind]: destinations = the first rows of x
-            _check_csr(row_ptr, col)
-            w = None
-            if edge_weight is not None:
-                w = edge_weight.to(torch.float32).contiguous()
-        elif edge_weight is not None:
-            row_ptr, col, w = _coo_to_csr_weighted(graph, edge_weight, n_src)
-        else:
-            row_ptr, col = _to_csr(graph, n_src)
-            w = None
-        n_dst = row_ptr.shape[0] - 1
-        hop = HopGraph(row_ptr, col, _arange(n_dst, x.device))
-        lg = LayerGraph([hop])
+        lg, _, w = _single_hop(graph, n_src, edge_weight)
+        hop = lg.hops[0]
         lg.degree_source = lambda: ([hop], [0], n_src)
-        lg._gcn_edge_weights = None if w is None else [w]
-        return self._forward_layer(x, lg, act, None if w is None else [w])
+        lg._gcn_edge_weights = None if w is None else [w.to(torch.float32).contiguous()]
+        return self._forward_layer(x, lg, act, lg._gcn_edge_weights)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -1766,11 +1801,6 @@ _RGCN_PAIRS_PER_ITEM_MIN, _RGCN_MAX_ITEMS = 256, 1024
 def rgcn_layer_supported(F_: int, N: int, B: int, has_root: bool = True) -> bool:
     """Shapes of the one-kernel RGCN layer (``wgamd_rgcn_layer_f32``): F % 4 == 0, N <= 256, (B + root) F <= 1024."""
     return bool(L.lib().wgamd_rgcn_layer_supported(int(F_), int(N), int(B), int(bool(has_root))))
-
-
-def _nonempty(t, dtype):
-    """``t``, or a one-element buffer when ``t`` is empty (the kernels take no null pointer for a hop's edge arrays)."""
-    return t if t.numel() > 0 else torch.zeros(1, dtype=dtype, device=t.device)
 
 
 _RGCN_LONG_ROW = 4096      # rows longer than this count relations by a sort (the ballot count is quadratic in the degree)
@@ -1806,9 +1836,7 @@ def rgcn_edge_coef(row_ptr, edge_type, R: int, mean: bool = True, long_rows: boo
         rel = et.to(torch.int32)
         if not mean:
             return rel, torch.ones(E, dtype=torch.float32, device=dev)
-        n = row_ptr.shape[0] - 1
-        row = torch.repeat_interleave(torch.arange(n, device=dev), (row_ptr[1:] - row_ptr[:-1]).long(), output_size=E)
-        _, inv, cnt = torch.unique(row * R + et.long(), return_inverse=True, return_counts=True)
+        _, inv, cnt = torch.unique(_edge_dst(row_ptr, E) * R + et.long(), return_inverse=True, return_counts=True)
         return rel, 1.0 / cnt.to(torch.float32)[inv]
     rel = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
     coef = torch.empty(max(E, 1), dtype=torch.float32, device=dev)
@@ -1831,7 +1859,7 @@ def rgcn_layer_forward(row_ptr, col, x, self_rows, rel, coef, wt, comp, B: int, 
     if out is None:
         out = torch.empty((n_rows, N), dtype=torch.float32, device=row_ptr.device)
     assert out.shape == (n_rows, N) and out.stride(1) == 1
-    ids_ptr, ids_dt = _gcn_args(x, src_ids)
+    ids_ptr, ids_dt = _ids_args(x, src_ids)
     L.check(L.lib().wgamd_rgcn_layer_f32(
         row_ptr.data_ptr(), _nonempty(col, torch.int32).data_ptr(), n_rows, x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt,
         _ptr(self_rows), _nonempty(rel, torch.int32).data_ptr(), _nonempty(coef, torch.float32).data_ptr(), _ptr(comp), int(B),
@@ -1857,7 +1885,7 @@ def rgcn_wgrad(x, pair_src, pair_dst, pair_coef, seg, n_seg: int, grad, src_ids=
     item_start[1:] = torch.cumsum((cnt + S - 1) // S, 0)
     max_items = -(-P // S) + n_seg if P > 0 else 0
     ws = torch.empty(max(int(L.lib().wgamd_rgcn_wgrad_workspace_bytes(max_items, F_, N)), 4), dtype=torch.uint8, device=dev)
-    ids_ptr, ids_dt = _gcn_args(x, src_ids)
+    ids_ptr, ids_dt = _ids_args(x, src_ids)
     L.check(L.lib().wgamd_rgcn_wgrad_f32(
         x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt, _nonempty(ps, torch.int64).data_ptr(), _nonempty(pd, torch.int64).data_ptr(),
         _nonempty(pc, torch.float32).data_ptr(), grad.data_ptr(), grad.stride(0), N, item_start.data_ptr(), seg_ptr.data_ptr(),
@@ -1881,22 +1909,6 @@ def _rgcn_stacked(weight, root, Nq=None):
     return torch.cat(parts, 1).contiguous()
 
 
-def _rgcn_transposed(hop: HopGraph, n_src: int, rel, coef):
-    """``(row_ptr_t, col_t, self_t, rel_t, coef_t)`` of a hop seen from its input rows: the source-major CSR (hop order inside a
-    source row: deterministic sums), ``self_t[j]`` = the destination row that is input row j itself (-1: none), and the edge
-    arrays permuted alike."""
-    dev = hop.row_ptr.device
-    if hop.col.shape[0] > 0:
-        row_ptr_t, perm, _, col_t = _csr_transpose(hop.row_ptr, hop.col, n_src, want_perm=True, want_col_t=True)
-        p = perm.long()
-        rel_t, coef_t = rel[p].contiguous(), coef[p].contiguous()
-    else:
-        row_ptr_t, col_t, rel_t, coef_t = torch.zeros(n_src + 1, dtype=torch.int32, device=dev), hop.col, rel, coef
-    self_t = torch.full((n_src,), -1, dtype=torch.int64, device=dev)
-    self_t[hop.self_rows] = torch.arange(hop.n_rows, dtype=torch.int64, device=dev)
-    return row_ptr_t, col_t, self_t, rel_t, coef_t
-
-
 class _RgcnLayer(torch.autograd.Function):
     """The one-kernel RGCN layer over a ``LayerGraph`` (one ``wgamd_rgcn_layer_f32`` launch per hop); nothing is kept but the
     per-edge coefficients and the output.  Backward: ``wgamd_rgcn_wgrad_f32`` once over every hop's (source, destination)
@@ -1911,13 +1923,10 @@ class _RgcnLayer(torch.autograd.Function):
         wt = _rgcn_stacked(weight, root)
         c = None if comp is None else comp.detach().contiguous()
         b = None if bias is None else bias.detach()
-        at = 0
-        for h, (rel, coef) in zip(graph.hops, coefs):
-            n = h.n_rows
-            if n > 0:
+        for (h, rows, _), (rel, coef) in zip(_hops(graph), coefs):
+            if h.n_rows > 0:
                 rgcn_layer_forward(h.row_ptr, h.col, src, h.self_rows, rel, coef, wt, c, B, root is not None, b, relu=relu, src_ids=ids,
-                                   out=out[at:at + n])
-            at += n
+                                   out=out[rows])
         if any(ctx.needs_input_grad[:5]):
             ctx.save_for_backward(weight, comp, root, out)
             ctx.src, ctx.ids, ctx.graph, ctx.coefs, ctx.relu, ctx.n_src, ctx.R = src, ids, graph, coefs, relu, n_src, conv.num_relations
@@ -1934,20 +1943,18 @@ class _RgcnLayer(torch.autograd.Function):
             gz = torch.ops.aten.threshold_backward(gz, out, 0)
         gx = gw = gc = gr = gb = None
         if need_w or need_c or need_r:
-            ps, pd, pc, sg, at = [], [], [], [], 0
-            for h, (rel, coef) in zip(ctx.graph.hops, ctx.coefs):
-                n, E = h.n_rows, h.col.shape[0]
-                rows = torch.arange(at, at + n, dtype=torch.int64, device=dev)
+            ps, pd, pc, sg = [], [], [], []
+            for (h, rows, _), (rel, coef) in zip(_hops(ctx.graph), ctx.coefs):
+                n = h.n_rows
                 ps.append(h.col.long())
-                pd.append(torch.repeat_interleave(rows, (h.row_ptr[1:] - h.row_ptr[:-1]).long(), output_size=E))
+                pd.append(_edge_dst(h.row_ptr, h.col.shape[0], rows.start))
                 pc.append(coef)
                 sg.append(rel.long())
                 if root is not None:
                     ps.append(h.self_rows)
-                    pd.append(rows)
+                    pd.append(torch.arange(rows.start, rows.stop, dtype=torch.int64, device=dev))
                     pc.append(torch.ones(n, dtype=torch.float32, device=dev))
                     sg.append(torch.full((n,), R, dtype=torch.int64, device=dev))
-                at += n
             M = rgcn_wgrad(ctx.src, torch.cat(ps), torch.cat(pd), torch.cat(pc), torch.cat(sg), R + (root is not None), gz,
                            src_ids=ctx.ids)
             if comp is None:
@@ -1964,14 +1971,13 @@ class _RgcnLayer(torch.autograd.Function):
             w_bwd = _rgcn_stacked(weight, root, Nq)
             gq = gz if Nq == N else torch.nn.functional.pad(gz, (0, Nq - N))
             c = None if comp is None else comp.detach().contiguous()
-            at = 0
-            for h, (rel, coef) in zip(ctx.graph.hops, ctx.coefs):
-                n = h.n_rows
-                if n > 0:
-                    row_ptr_t, col_t, self_t, rel_t, coef_t = _rgcn_transposed(h, ctx.n_src, rel, coef)
-                    gh = rgcn_layer_forward(row_ptr_t, col_t, gq[at:at + n], self_t, rel_t, coef_t, w_bwd, c, B, root is not None)
+            for (h, rows, _), (rel, coef) in zip(_hops(ctx.graph), ctx.coefs):
+                if h.n_rows > 0:
+                    row_ptr_t, col_t, _, perm = h.transposed(ctx.n_src, need_self=False, need_perm=True)
+                    p = perm[:h.col.shape[0]]
+                    gh = rgcn_layer_forward(row_ptr_t, col_t, gq[rows], h.input_dst(ctx.n_src), rel[p], coef[p], w_bwd, c, B,
+                                            root is not None)
                     gx = gh if gx is None else gx.add_(gh)
-                at += n
             if gx is None:
                 gx = torch.zeros((ctx.n_src, F_), dtype=torch.float32, device=dev)
         ctx.src = ctx.coefs = None
@@ -1990,8 +1996,8 @@ def _rgcn_library_ops(conv, x, lg: LayerGraph, coefs, relu: bool):
         Wk, K = conv._relation_weights(), R
     outs = []
     for h, (rel, coef) in zip(lg.hops, coefs):
-        n, E = h.n_rows, h.col.shape[0]
-        dst = torch.repeat_interleave(torch.arange(n, device=x.device), (h.row_ptr[1:] - h.row_ptr[:-1]).long(), output_size=E)
+        n = h.n_rows
+        dst = _edge_dst(h.row_ptr, h.col.shape[0])
         xs = x[h.col.long()]
         if by_basis:
             w_e = coef.unsqueeze(1) * conv.comp[rel.long()]                   # [E, B]
@@ -2078,80 +2084,44 @@ class RGCNConv(torch.nn.Module):
         cache = getattr(lg, "_rgcn_coefs", None)
         if cache is not None and cache[0] is edge_type and cache[1] == key:     # (the tensor itself: a new one at a reused
             return cache[2]                                                     #  address is not the old one)
-        coefs, at = [], 0
-        for h in lg.hops:
-            E = h.col.shape[0]
-            coefs.append(rgcn_edge_coef(h.row_ptr, edge_type[at:at + E], self.num_relations, mean,
-                                        long_rows=getattr(h, "_rgcn_long_rows", False)))
-            at += E
+        coefs = [rgcn_edge_coef(h.row_ptr, edge_type[edges], self.num_relations, mean, long_rows=getattr(h, "_rgcn_long_rows", False))
+                 for h, _, edges in _hops(lg)]
         lg._rgcn_coefs = (edge_type, key, coefs)
         return coefs
 
     def _forward_layer(self, x, lg: LayerGraph, edge_type, act=None):
         assert act in (None, "relu"), "act: None or 'relu'"
         relu = act == "relu"
-        lazy = isinstance(x, LazyRows)
-        src = x.table if lazy else x
-        n_src = len(x) if lazy else x.shape[0]
         F_, N = self.in_channels, self.out_channels
-        if x.shape[1] != F_:
-            raise ValueError("RGCNConv: x has %d features, the layer takes %d" % (x.shape[1], F_))
-        n_edges = sum(int(h.col.shape[0]) for h in lg.hops)
-        # a call group's layer graph: edge_type covers the whole group (every layer reads the prefix of its hops); any other
-        # layer graph: exactly its hops' edges
-        total = getattr(lg, "num_group_edges", None)
-        _rgcn_check_types(edge_type, self.num_relations, total if total is not None else n_edges,
-                          lg.hops[0].row_ptr.device if lg.hops else src.device)
-        grad_on = torch.is_grad_enabled()
-        if lazy and grad_on and getattr(src, "requires_grad", False):
-            raise NotImplementedError("gradient w.r.t. a feature table read through ids (LazyRows): trainable node "
-                                      "embeddings go through wholegraph_amd.embedding, or pass x = emb[n_id]")
+        src, ids, n_src, n_edges = _layer_input(self, x, lg, F_)
+        _rgcn_check_types(edge_type, self.num_relations, n_edges, lg.hops[0].row_ptr.device if lg.hops else src.device)
         coefs = self._coefs(lg, edge_type)
         has_root, B = self.root is not None, self._b_eff
-        need_x = grad_on and not lazy and x.requires_grad
+        need_x = torch.is_grad_enabled() and ids is None and x.requires_grad
         Nq = (N + 3) // 4 * 4
         if (rgcn_layer_supported(F_, N, B, has_root) and (not need_x or rgcn_layer_supported(Nq, F_, B, has_root))
-                and src.dtype == torch.float32 and src.is_cuda and src.stride(1) == 1 and src.stride(0) % 4 == 0
-                and src.data_ptr() % 16 == 0):
-            return _RgcnLayer.apply(src, self.weight, self.comp, self.root, self.bias, self, lg, coefs, x.ids if lazy else None,
-                                    relu, n_src)
-        xd = x.materialize() if lazy else x
+                and _kernel_rows_ok(src)):
+            return _RgcnLayer.apply(src, self.weight, self.comp, self.root, self.bias, self, lg, coefs, ids, relu, n_src)
+        xd = x.materialize() if isinstance(x, LazyRows) else x
         return _rgcn_library_ops(self, xd.float(), lg, coefs, relu)
 
     def forward(self, x, graph, edge_type, act=None):
-        if _capturing():
-            # (the per-edge coefficients and transposes of a layer graph are cached in Python against the graph object: a
-            #  replay would keep using those of the capture)
-            raise RuntimeError("wholegraph_amd.nn.RGCNConv is not supported under HIP-graph capture (loader.PerBatchStep): its "
-                               "per-graph caches are not capture-safe; SAGEConv layers are")
-        if x is None or (torch.is_tensor(x) and not x.is_floating_point()):
-            raise ValueError("RGCNConv: featureless input (x = None or node indices) is not supported; pass node features")
+        _refuse_capture(self, "per-graph caches")             # (per-edge coefficients and transposes)
+        _refuse_featureless(self, x)
         if isinstance(graph, HeteroLayerGraph):
             raise NotImplementedError("RGCNConv over a heterogeneous call group's layer graph is not supported")
         if isinstance(graph, LayerGraph):
             return self._forward_layer(x, graph, edge_type, act)
         if isinstance(x, LazyRows):
             x = x.materialize()
-        n_src = x.shape[0]
-        if isinstance(graph, (tuple, list)):
-            row_ptr, col = graph[0], graph[1]          # [csr_row_ptr, csr_col_ind]: destinations = the first rows of x
-            _check_csr(row_ptr, col)
-            _rgcn_check_types(edge_type, self.num_relations, col.shape[0], row_ptr.device)
-            et = edge_type
-        else:
-            _rgcn_check_types(edge_type, self.num_relations, graph.shape[1], graph.device)
-            src_ids, dst = graph[0], graph[1]
-            order = torch.sort(dst, stable=True).indices  # destination-major, edge order kept inside a destination
-            col = src_ids[order].to(torch.int32).contiguous()
-            et = edge_type[order].contiguous()
-            et._wgamd_rgcn_checked = (et.data_ptr(), et._version, et.shape[0], int(self.num_relations))
-            row_ptr = torch.zeros(n_src + 1, dtype=torch.int32, device=dst.device)
-            row_ptr[1:] = torch.cumsum(torch.bincount(dst, minlength=n_src), 0)
-        n_dst = row_ptr.shape[0] - 1
-        hop = HopGraph(row_ptr, col, _arange(n_dst, x.device))
-        if n_dst > 0:                                  # (these paths may synchronise: the range check above does)
-            hop._rgcn_long_rows = int((row_ptr[1:] - row_ptr[:-1]).max()) > _RGCN_LONG_ROW
-        return self._forward_layer(x, LayerGraph([hop]), et, act)
+        # (graph[1]: the CSR pair's col, or the COO list's destinations — one entry per edge either way)
+        _rgcn_check_types(edge_type, self.num_relations, graph[1].shape[0], graph[0].device)
+        lg, _, et = _single_hop(graph, x.shape[0], edge_type)
+        et._wgamd_rgcn_checked = (et.data_ptr(), et._version, et.shape[0], int(self.num_relations))
+        hop = lg.hops[0]
+        if hop.n_rows > 0:                             # (these paths may synchronise: the range check above does)
+            hop._rgcn_long_rows = int((hop.row_ptr[1:] - hop.row_ptr[:-1]).max()) > _RGCN_LONG_ROW
+        return self._forward_layer(x, lg, et, act)
 
 
 FastRGCNConv = RGCNConv
@@ -2229,7 +2199,7 @@ def transformer_layer_forward(row_ptr, col, x, u, wt, H: int, self_rows=None, x_
     assert out.shape == (n_rows, N) and out.stride(1) == 1
     assert alpha is None or (alpha.shape == (col.shape[0], H) and alpha.is_contiguous())
     assert a_save is None or a_save.is_contiguous()
-    ids_ptr, ids_dt = _gcn_args(x, src_ids)
+    ids_ptr, ids_dt = _ids_args(x, src_ids)
     L.check(L.lib().wgamd_transformer_layer_f32(
         row_ptr.data_ptr(), _nonempty(col, torch.int32).data_ptr(), n_rows, x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt,
         _ptr(x_dst), 0 if x_dst is None else x_dst.stride(0), Fd, _ptr(self_rows), int(bool(x_dst_ids)),
@@ -2240,17 +2210,11 @@ def transformer_layer_forward(row_ptr, col, x, u, wt, H: int, self_rows=None, x_
     return out
 
 
-def _tconv_rows_ok(t) -> bool:
-    """``t`` [rows, F] is what the transformer kernels read in place: float32 on the device, unit column stride, 16-B aligned
-    rows."""
-    return (t.dtype == torch.float32 and t.is_cuda and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0)
-
-
 def _tconv_rows(t):
     """``t`` as the kernels read it: float32, and a contiguous copy when its rows are strided or not 16-B aligned (a fresh
     allocation is; F is a multiple of 4 in the kernel's domain).  Under autograd: the gradient reaches ``t``."""
     t = t.float()
-    if not _tconv_rows_ok(t):
+    if not _kernel_rows_ok(t):
         t = t.contiguous() if not t.is_contiguous() else t.clone()
     return t
 
@@ -2277,17 +2241,13 @@ class _TconvLayer(torch.autograd.Function):
         wt_d, b_d = wt.detach().contiguous(), None if bias is None else bias.detach()
         u_d, w_d = u.detach().contiguous(), None if w is None else w.detach().contiguous()
         xd = x_dst if x_dst is not None else x
-        at = eat = 0
-        for h in lg.hops:
-            nh, Eh = h.n_rows, int(h.col.shape[0])
-            if nh > 0:
+        for h, rows, edges in _hops(lg):
+            if h.n_rows > 0:
                 transformer_layer_forward(
-                    h.row_ptr, h.col, x, u_d[at:at + nh], wt_d, H, self_rows=h.self_rows, x_dst=xd if skip else None,
-                    x_dst_ids=ids is not None and x_dst is None, edge_attr=None if D == 0 else edge_attr[eat:eat + Eh],
-                    w=None if w_d is None else w_d[at:at + nh], bias=b_d, relu=relu, src_ids=ids, out=out[at:at + nh],
-                    alpha=None if alpha is None else alpha[eat:eat + Eh], a_save=None if A is None else A[at:at + nh])
-            at += nh
-            eat += Eh
+                    h.row_ptr, h.col, x, u_d[rows], wt_d, H, self_rows=h.self_rows, x_dst=xd if skip else None,
+                    x_dst_ids=ids is not None and x_dst is None, edge_attr=None if D == 0 else edge_attr[edges],
+                    w=None if w_d is None else w_d[rows], bias=b_d, relu=relu, src_ids=ids, out=out[rows],
+                    alpha=None if alpha is None else alpha[edges], a_save=None if A is None else A[rows])
         ctx.set_materialize_grads(False)
         if train:
             ctx.save_for_backward(u_d, w_d, wt_d, out, alpha, A)
@@ -2323,19 +2283,15 @@ class _TconvLayer(torch.autograd.Function):
             du = torch.empty((n, H * F_), dtype=torch.float32, device=dev)
             dw = torch.empty((n, H * D), dtype=torch.float32, device=dev) if D else None
             ds = torch.empty((E, H), dtype=torch.float32, device=dev)
-            ids_ptr, ids_dt = _gcn_args(x, ctx.ids)
-            at = eat = 0
-            for h in lg.hops:
-                nh, Eh = h.n_rows, int(h.col.shape[0])
-                if nh > 0:
+            ids_ptr, ids_dt = _ids_args(x, ctx.ids)
+            for h, rows, edges in _hops(lg):
+                if h.n_rows > 0:
                     L.check(L.lib().wgamd_transformer_bwd_dst_f32(
-                        h.row_ptr.data_ptr(), _nonempty(h.col, torch.int32).data_ptr(), nh, x.data_ptr(), x.stride(0), F_, ids_ptr,
-                        ids_dt, None if D == 0 else _nonempty(ea[eat:eat + Eh], torch.float32).data_ptr(), D, H,
-                        _nonempty(alpha[eat:eat + Eh], torch.float32).data_ptr(), dA[at:at + nh].data_ptr(), dA.stride(0),
-                        A[at:at + nh].data_ptr(), A.stride(0), du[at:at + nh].data_ptr(), None if dw is None else dw[at:at + nh].data_ptr(),
-                        _nonempty(ds[eat:eat + Eh], torch.float32).data_ptr(), get_stream()), "wgamd_transformer_bwd_dst_f32")
-                at += nh
-                eat += Eh
+                        h.row_ptr.data_ptr(), _nonempty(h.col, torch.int32).data_ptr(), h.n_rows, x.data_ptr(), x.stride(0), F_,
+                        ids_ptr, ids_dt, None if D == 0 else _nonempty(ea[edges], torch.float32).data_ptr(), D, H,
+                        _nonempty(alpha[edges], torch.float32).data_ptr(), dA[rows].data_ptr(), dA.stride(0), A[rows].data_ptr(),
+                        A.stride(0), du[rows].data_ptr(), None if dw is None else dw[rows].data_ptr(),
+                        _nonempty(ds[edges], torch.float32).data_ptr(), get_stream()), "wgamd_transformer_bwd_dst_f32")
             gu, gw = du, dw
             if need_x:
                 gx = torch.zeros((ctx.n_src, F_), dtype=torch.float32, device=dev)
@@ -2343,35 +2299,26 @@ class _TconvLayer(torch.autograd.Function):
                 # whose self_rows index x_dst)
                 own_skip = ctx.skip and not ctx.bipartite
                 skip_at = H * W4 if own_skip else -1
-                at = eat = 0
-                for h in lg.hops:
-                    nh, Eh = h.n_rows, int(h.col.shape[0])
-                    if nh > 0:
+                for h, rows, edges in _hops(lg):
+                    if h.n_rows > 0:
                         row_ptr_t, col_t, self_t, perm = h.transposed(ctx.n_src, need_self=own_skip, need_perm=True)
                         L.check(L.lib().wgamd_transformer_bwd_src_f32(
-                            row_ptr_t.data_ptr(), _nonempty(col_t, torch.int32).data_ptr(), perm.data_ptr(), _ptr(self_t), nh,
+                            row_ptr_t.data_ptr(), _nonempty(col_t, torch.int32).data_ptr(), perm.data_ptr(), _ptr(self_t), h.n_rows,
                             ctx.n_src, F_, D, H, skip_at,
-                            _nonempty(alpha[eat:eat + Eh], torch.float32).data_ptr(), _nonempty(ds[eat:eat + Eh], torch.float32).data_ptr(),
-                            dA[at:at + nh].data_ptr(), dA.stride(0), u[at:at + nh].data_ptr(), u.stride(0), gx.data_ptr(), gx.stride(0), 1,
+                            _nonempty(alpha[edges], torch.float32).data_ptr(), _nonempty(ds[edges], torch.float32).data_ptr(),
+                            dA[rows].data_ptr(), dA.stride(0), u[rows].data_ptr(), u.stride(0), gx.data_ptr(), gx.stride(0), 1,
                             get_stream()), "wgamd_transformer_bwd_src_f32")
-                    at += nh
-                    eat += Eh
             if need_xd and ctx.skip:
                 gxd = dA[:, H * W4:].contiguous()
             if need_ea and D:
                 gea = torch.zeros_like(ea)
                 dA3 = dA[:, :H * W4].view(n, H, W4)
                 w3 = w.view(n, H, D)
-                at = eat = 0
-                for h in lg.hops:
-                    nh, Eh = h.n_rows, int(h.col.shape[0])
-                    if Eh > 0:
-                        dst = at + torch.repeat_interleave(torch.arange(nh, device=dev), (h.row_ptr[1:] - h.row_ptr[:-1]).long(),
-                                                           output_size=Eh)
-                        a_e, s_e = alpha[eat:eat + Eh].unsqueeze(2), ds[eat:eat + Eh].unsqueeze(2)
-                        gea[eat:eat + Eh] = (a_e * dA3[dst, :, F_:F_ + D] + s_e * w3[dst]).sum(1)
-                    at += nh
-                    eat += Eh
+                for h, rows, edges in _hops(lg):
+                    if edges.stop > edges.start:
+                        dst = _edge_dst(h.row_ptr, edges.stop - edges.start, rows.start)
+                        a_e, s_e = alpha[edges].unsqueeze(2), ds[edges].unsqueeze(2)
+                        gea[edges] = (a_e * dA3[dst, :, F_:F_ + D] + s_e * w3[dst]).sum(1)
         ctx.x = ctx.edge_attr = None
         return gx, gxd, gu, gw, gea, gwt, gb, None, None, None, None, None, None, None
 
@@ -2380,17 +2327,17 @@ def _tconv_library_ops(conv, x_src, x_dst_rows, lg: LayerGraph, edge_attr, relu:
     """The layer in PyG's own formulation, composed of library ops under autograd: the route of shapes outside the one-kernel
     layer's domain (correctness, not speed).  Returns ``(out, alpha)`` with alpha [E, H] hop-major in CSR order."""
     H, C = conv.heads, conv.out_channels
-    outs, alphas, at, eat = [], [], 0, 0
-    for h in lg.hops:
+    outs, alphas = [], []
+    for h, rows, edges in _hops(lg):
         nh, Eh = h.n_rows, int(h.col.shape[0])
-        xd = x_dst_rows[at:at + nh]
-        dst = torch.repeat_interleave(torch.arange(nh, device=xd.device), (h.row_ptr[1:] - h.row_ptr[:-1]).long(), output_size=Eh)
+        xd = x_dst_rows[rows]
+        dst = _edge_dst(h.row_ptr, Eh)
         xs = x_src[h.col.long()]
         q = conv.lin_query(xd).view(nh, H, C)
         k = conv.lin_key(xs).view(Eh, H, C)
         v = conv.lin_value(xs).view(Eh, H, C)
         if conv.lin_edge is not None:
-            e = conv.lin_edge(edge_attr[eat:eat + Eh]).view(Eh, H, C)
+            e = conv.lin_edge(edge_attr[edges]).view(Eh, H, C)
             k, v = k + e, v + e
         s = (q[dst] * k).sum(-1) / math.sqrt(C)                                   # [E, H]
         smax = s.new_full((nh, H), -math.inf).scatter_reduce(0, dst.unsqueeze(1).expand(Eh, H), s, "amax", include_self=True)
@@ -2403,8 +2350,6 @@ def _tconv_library_ops(conv, x_src, x_dst_rows, lg: LayerGraph, edge_attr, relu:
             o = o + conv.lin_skip(xd)
         outs.append(o)
         alphas.append(alpha)
-        at += nh
-        eat += Eh
     out = torch.cat(outs) if outs else x_src.new_zeros((0, H * C if conv.concat else C))
     alpha = torch.cat(alphas) if alphas else x_src.new_zeros((0, H))
     return (torch.relu(out) if relu else out), alpha
@@ -2514,31 +2459,22 @@ class TransformerConv(torch.nn.Module):
         rows.  Returns ``(out, alpha or None)`` with alpha hop-major in CSR order."""
         assert act in (None, "relu"), "act: None or 'relu'"
         relu = act == "relu"
-        lazy = isinstance(x, LazyRows)
-        src = x.table if lazy else x
-        n_src = len(x) if lazy else x.shape[0]
         H, N, D = self.heads, self._out_width, self.edge_dim or 0
-        if x.shape[1] != self.in_src:
-            raise ValueError("TransformerConv: x has %d features, the layer takes %d" % (x.shape[1], self.in_src))
+        src, ids, n_src, n_edges = _layer_input(self, x, lg, self.in_src)
+        lazy = ids is not None
         if x_dst is not None and x_dst.shape[1] != self.in_dst:
             raise ValueError("TransformerConv: x_dst has %d features, the layer takes %d" % (x_dst.shape[1], self.in_dst))
         if x_dst is None and self.in_src != self.in_dst:
             raise ValueError("TransformerConv: in_channels = %s needs an (x_src, x_dst) pair" % (self.in_channels,))
-        n_edges = sum(int(h.col.shape[0]) for h in lg.hops)
-        total = getattr(lg, "num_group_edges", None)
         dev = lg.hops[0].row_ptr.device if lg.hops else src.device
-        ea = self._check_edge_attr(edge_attr, total if total is not None else n_edges, dev)
-        grad_on = torch.is_grad_enabled()
-        if lazy and grad_on and getattr(src, "requires_grad", False):
-            raise NotImplementedError("gradient w.r.t. a feature table read through ids (LazyRows): trainable node "
-                                      "embeddings go through wholegraph_amd.embedding, or pass x = emb[n_id]")
+        ea = self._check_edge_attr(edge_attr, n_edges, dev)
         skip = self.root_weight
         kernel = transformer_layer_supported(self.in_src, self.in_dst if skip else 0, D, H, N) and src.is_cuda and (
             x_dst is None or x_dst.is_cuda)
         if kernel:
             # rows as the kernel reads them (float32, unit column stride, 16-B aligned rows): copied (under autograd) when they
             # are not; a lazy table that is not is gathered
-            if lazy and not _tconv_rows_ok(src):
+            if lazy and not _kernel_rows_ok(src):
                 x, lazy = x.materialize(), False
             if not lazy:
                 x = src = _tconv_rows(x)
@@ -2568,19 +2504,15 @@ class TransformerConv(torch.nn.Module):
     def forward(self, x, graph, edge_attr=None, act=None, return_attention_weights=False):
         if self.dropout > 0 and self.training:
             raise NotImplementedError("TransformerConv: attention dropout (dropout > 0 in training mode) is not supported")
-        if _capturing():
-            raise RuntimeError("wholegraph_amd.nn.TransformerConv is not supported under HIP-graph capture (loader.PerBatchStep): "
-                               "its per-graph caches are not capture-safe; SAGEConv layers are")
+        _refuse_capture(self, "per-graph caches")
         if isinstance(graph, HeteroLayerGraph):
             raise NotImplementedError("TransformerConv over a heterogeneous call group's layer graph is not supported")
         x_dst = None
         if isinstance(x, (tuple, list)):
             x, x_dst = x
-        for t in (x, x_dst):
-            if t is not None and not isinstance(t, LazyRows) and (not torch.is_tensor(t) or not t.is_floating_point()):
-                raise ValueError("TransformerConv: featureless input (x = None or node indices) is not supported; pass node features")
-        if x is None:
-            raise ValueError("TransformerConv: featureless input (x = None or node indices) is not supported; pass node features")
+        _refuse_featureless(self, x)
+        if x_dst is not None:
+            _refuse_featureless(self, x_dst)
         if isinstance(graph, LayerGraph):
             if x_dst is not None:
                 raise NotImplementedError("TransformerConv: an (x_src, x_dst) pair over a LayerGraph is not supported")
@@ -2590,36 +2522,26 @@ class TransformerConv(torch.nn.Module):
             x = x.materialize()
         if isinstance(x_dst, LazyRows):
             x_dst = x_dst.materialize()
-        n_dst = x.shape[0] if x_dst is None else x_dst.shape[0]
-        order = None
-        if isinstance(graph, (tuple, list)):
-            row_ptr, col = graph[0], graph[1]          # [csr_row_ptr, csr_col_ind]: destinations = the first rows of x (or x_dst)
-            _check_csr(row_ptr, col)
-            n_dst = row_ptr.shape[0] - 1
-            ea = self._check_edge_attr(edge_attr, col.shape[0], row_ptr.device)
-        else:
-            ea = self._check_edge_attr(edge_attr, graph.shape[1], graph.device)
-            src_ids, dst = graph[0], graph[1]
-            order = torch.sort(dst, stable=True).indices  # destination-major, edge order kept inside a destination
-            col = src_ids[order].to(torch.int32).contiguous()
-            ea = None if ea is None else ea[order]
-            row_ptr = torch.zeros(n_dst + 1, dtype=torch.int32, device=dst.device)
-            row_ptr[1:] = torch.cumsum(torch.bincount(dst, minlength=n_dst), 0)
+        # (graph[1]: the CSR pair's col, or the COO list's destinations — one entry per edge either way)
+        ea = self._check_edge_attr(edge_attr, graph[1].shape[0], graph[0].device)
+        lg, order, ea = _single_hop(graph, x.shape[0] if x_dst is None else x_dst.shape[0], ea)
+        n_dst = lg.n_rows
         if x_dst is not None and x_dst.shape[0] < n_dst:
             raise ValueError("TransformerConv: x_dst has %d rows for %d destinations" % (x_dst.shape[0], n_dst))
         if x_dst is None and x.shape[0] < n_dst:
             raise ValueError("TransformerConv: x has %d rows for %d destinations" % (x.shape[0], n_dst))
-        hop = HopGraph(row_ptr, col, _arange(n_dst, x.device))
         if x_dst is not None:
             x_dst = x_dst[:n_dst]
-        out, alpha = self._forward_layer(x, LayerGraph([hop]), ea, act, x_dst=x_dst, want_alpha=return_attention_weights)
+        out, alpha = self._forward_layer(x, lg, ea, act, x_dst=x_dst, want_alpha=return_attention_weights)
         if not return_attention_weights:
             return out
-        if order is None:
+        if isinstance(graph, (tuple, list)):
             return out, alpha
-        a = torch.empty_like(alpha)
-        a[order] = alpha
-        return out, (graph, a)
+        if order is not None:                          # alpha back in edge_index order
+            a = torch.empty_like(alpha)
+            a[order] = alpha
+            alpha = a
+        return out, (graph, alpha)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -2970,11 +2892,8 @@ class HeteroConv(torch.nn.Module):
         return c.heads * c.out_channels if c.concat else c.out_channels
 
     def forward(self, x_dict, graph, act=None):
-        if _capturing():
-            # (the derived forms of this layer's parameters — folded attention vectors, weight tiles, pooled buffers — are cached
-            #  in Python against the parameters' versions: a replayed graph would keep using the ones of the capture)
-            raise RuntimeError("wholegraph_amd.nn.%s is not supported under HIP-graph capture (loader.PerBatchStep): its "
-                               "derived-weight caches are not capture-safe; SAGEConv layers are" % type(self).__name__)
+        # (folded attention vectors, weight tiles, pooled buffers: cached against the parameters' versions)
+        _refuse_capture(self, "derived-weight caches")
         if isinstance(graph, HeteroLayerGraph):
             needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
             plain = all(self.conv(et).concat and not self.conv(et).add_self_loops for et in self.edge_types)

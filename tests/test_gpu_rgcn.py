@@ -193,6 +193,12 @@ def test_edge_index_and_csr_pair_paths(hiplib, F, N, R, bases):
     with torch.no_grad():
         got2 = conv(x, [rp, ei[0][order].to(torch.int32).contiguous()], et[order].to(torch.int32))
     _close(got2, ref, scale, "csr pair")
+    # a destination-sorted edge_index with the loader's marker: taken in its own order, the same rows as the unsorted list
+    ei_s = ei[:, order].contiguous()
+    ei_s._wgamd_dst_sorted = ei_s._version
+    with torch.no_grad():
+        got3 = conv(x, ei_s, et[order])
+    assert torch.equal(got3, got)
     xg = x.clone().requires_grad_(True)
     conv(xg, ei, et).sum().backward()
     xr = x.double().requires_grad_(True)

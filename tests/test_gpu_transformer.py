@@ -249,6 +249,12 @@ def test_edge_index_and_csr_pair_paths(hiplib, H, concat, D):
     with torch.no_grad():
         got2 = conv(x, [rp, ei[0][order].to(torch.int32).contiguous()], ea[order])
     _close(got2, ref, scale, "csr pair")
+    # a destination-sorted edge_index with the loader's marker: taken in its own order, the same rows and alpha as the unsorted list
+    ei_s = ei[:, order].contiguous()
+    ei_s._wgamd_dst_sorted = ei_s._version
+    with torch.no_grad():
+        got3, (_, alpha3) = conv(x, ei_s, ea[order], return_attention_weights=True)
+    assert torch.equal(got3, got) and torch.equal(alpha3, alpha[order])
 
 
 def test_bad_edge_attr_and_fallback(hiplib, monkeypatch):
