@@ -1,4 +1,4 @@
-// Shared pieces of the one-kernel layers over a sampled hop (wg_gcn.hip, wg_rgcn.hip, wg_transformer.hip): an input row read
+// Shared pieces of the one-kernel layers over a sampled hop (wg_gcn.hip, wg_rgcn.hip, wg_transformer.hip, wg_sage_hetero.hip): an input row read
 // through the layer's node list, the kind of that list, the launch for the kind found at run time, the 16-B row test, the
 // dynamic-LDS launch of a layer kernel, and phase 2 of every layer kernel — the [16 x K16] LDS tile times wt^T on the exact
 // fp32 matrix pipe (v_mfma_f32_16x16x4_f32), bias and ReLU fused.
@@ -65,9 +65,11 @@ void launch_tiles(void (*kern)(Args), const Args& a, hipStream_t st)
 // Phase 2: out[row0 + r, n] = act(sum_k tile[r, k] wt[n, k] + bias[n]) for r < 16 (rows below n_rows), n < N, k < K16.  The
 // tile's columns [K, K16) are zero and wt is read for k < K only.  Wave w owns the 16-column tiles w, w + 4, w + 8, w + 12; a
 // lane reads one float4 of the tile (ds_read_b128) and one float4 of a wt row per 16 k — the four k of a float4 are four MFMA
-// k-steps.  Rows SD floats apart in the tile.
+// k-steps.  Rows SD floats apart in the tile.  acc_in (nullable, rows ld_acc apart): a running sum added before the activation;
+// out_rows (nullable): row i is written to out[out_rows[i]].
 __device__ __forceinline__ void tile_times_wt(const float* tile, int SD, int K, int K16, const float* wt, int64_t ldw, int N,
-                                              const float* bias, int relu, float* out, int64_t ldo, int64_t row0, int64_t n_rows)
+                                              const float* bias, int relu, float* out, int64_t ldo, int64_t row0, int64_t n_rows,
+                                              const float* acc_in = nullptr, int64_t ld_acc = 0, const int64_t* out_rows = nullptr)
 {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n_ct = (N + 15) / 16;
@@ -102,8 +104,9 @@ __device__ __forceinline__ void tile_times_wt(const float* tile, int SD, int K, 
       const int64_t i = row0 + 4 * g + reg;
       if (i < n_rows) {
         float y = acc[q][reg] + b;
+        if (acc_in) y += acc_in[i * ld_acc + n];
         if (relu) y = fmaxf(y, 0.f);
-        out[i * ldo + n] = y;
+        out[(out_rows ? out_rows[i] : i) * ldo + n] = y;
       }
     }
   }

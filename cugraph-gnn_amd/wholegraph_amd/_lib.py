@@ -31,9 +31,16 @@ _ERROR_NAMES = ["SUCCESS", "UNKNOW_ERROR", "NOT_IMPLEMENTED", "LOGIC_ERROR", "CU
  DT_COUNT) = range(10)
 
 IDS_BYTE_OFFSETS = 64   # WGAMD_IDS_BYTE_OFFSETS (include/wgamd_ext.h): src_ids = int64 byte offsets from x
+HETERO_SAGE_MAX_RELATIONS, HETERO_SAGE_RELU = 8, 1   # WGAMD_HETERO_SAGE_* (include/wgamd_ext.h)
 
 # wholememory_memory_allocation_type_t
 MA_NONE, MA_DEVICE, MA_HOST, MA_PINNED = range(4)
+
+
+class HeteroSageRelation(Structure):
+    """wgamd_hetero_sage_relation_t (include/wgamd_ext.h)."""
+    _fields_ = [("row_ptr", c_void_p), ("col", c_void_p), ("x", c_void_p), ("ldx", c_int64), ("src_ids", c_void_p),
+                ("src_scale", c_void_p), ("F", c_int), ("ids_kind", c_int), ("mean", c_int), ("col0", c_int)]
 
 
 class WholeGraphLibraryError(RuntimeError):
@@ -312,6 +319,14 @@ SYMBOLS = {
                                               c_void_p]),
     "wgamd_transformer_bwd_src_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_int, c_void_p,
                                               c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),
+    # heterogeneous SAGE layer (wg_sage_hetero.hip)
+    "wgamd_hetero_sage_layer_supported": (c_int, [POINTER(c_int), c_int, c_int, c_int]),
+    "wgamd_hetero_sage_layer_f32": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                            c_int64, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                            c_void_p]),
+    "wgamd_hetero_sage_layer_f32_train": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int,
+                                                  c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                                  c_int64, c_void_p, c_int64, c_void_p]),
     "wgamd_bias_act_rows_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "wgamd_gat_transform_heads_supported": (c_int, [c_int, c_int, c_int]),
     "wgamd_gat_transform_weight_bytes": (c_size_t, [c_int, c_int, c_int]),

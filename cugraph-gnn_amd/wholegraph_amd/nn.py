@@ -2684,10 +2684,206 @@ class _GatAggregateHeads(torch.autograd.Function):
         return gx, ga_src, ga_dst, None, None, None, None, None, None, None, None, None
 
 
+# ---- heterogeneous SAGE layer: one launch per (hop, destination type) ---------------------------------------------------------
+HETERO_SAGE_MAX_K = 1024          # floats of one launch's C row (the 16 x (K + 4) fp32 LDS tile of wg_sage_hetero.hip)
+hetero_sage_launches = 0          # wgamd_hetero_sage_layer_f32(_train) launches so far (tests: the kernel route ran)
+
+
+def hetero_sage_plan(widths, F_dst: int = 0, max_k: int = HETERO_SAGE_MAX_K, max_rel: int = L.HETERO_SAGE_MAX_RELATIONS):
+    """The launches of one (hop, destination type) group whose relation blocks are ``widths`` floats wide (in order) and whose
+    root block is ``F_dst`` wide (0: none): ``[(lo, hi, root), ...]`` — launch k reduces relations ``[lo, hi)``; whole
+    relations, in order, at most ``max_rel`` of them and ``K <= max_k`` floats per launch (greedy: a launch takes relations
+    while they fit).  Only the LAST launch has ``root`` — with it go the bias, the activation and the row placement; every
+    launch but the first adds the running sum of the ones before it.  A root block that does not fit next to the last
+    relations gets a launch of its own.  ValueError when a single block is wider than ``max_k``."""
+    widths = [int(w) for w in widths]
+    if any(w <= 0 or w > max_k for w in widths) or not 0 <= F_dst <= max_k:
+        raise ValueError("hetero_sage_plan: a block of %s + [%d] floats does not fit a launch (K <= %d)" % (widths, F_dst, max_k))
+    plan, lo, k = [], 0, 0
+    for i, w in enumerate(widths):
+        if k + w > max_k or i - lo == max_rel:
+            plan.append((lo, i, False))
+            lo, k = i, 0
+        k += w
+    if k + F_dst > max_k:
+        plan.append((lo, len(widths), False))
+        lo, k = len(widths), 0
+    if lo < len(widths) or F_dst > 0 or not plan:
+        plan.append((lo, len(widths), F_dst > 0))
+    return plan
+
+
+def _sage_ids_kind(ids) -> int:
+    return 0 if ids is None else (1 if ids.dtype == torch.int32 else 2)
+
+
+def hetero_sage_launch(rels, n_rows: int, wt, N: int, root=None, bias=None, relu=False, acc_in=None, out_rows=None, out=None,
+                       c_out=None):
+    """One ``wgamd_hetero_sage_layer_f32`` launch (include/wgamd_ext.h).  ``rels``: ``[(row_ptr, col, x, ids, scale, mean), ...]``
+    (x [*, F] float32 rows, ``ids`` the node list x is read through or None, ``scale`` a per-source-row factor or None);
+    ``root``: ``(x_dst, dst_rows, dst_ids)`` or None; ``wt`` [N, >= K] (a column slice of the stacked weight); ``c_out``
+    [n_rows, >= K]: the launch also keeps its C rows (``_train``)."""
+    global hetero_sage_launches
+    arr = (L.HeteroSageRelation * max(len(rels), 1))()
+    keep, at = [], 0
+    for k, (row_ptr, col, x, ids, scale, mean) in enumerate(rels):
+        _check_csr(row_ptr, col)
+        assert row_ptr.shape[0] == n_rows + 1 and x.dtype == torch.float32 and x.stride(1) == 1
+        assert ids is None or ids.is_contiguous()
+        col = _nonempty(col, torch.int32)
+        keep.append(col)
+        d = arr[k]
+        d.row_ptr, d.col, d.x, d.ldx = row_ptr.data_ptr(), col.data_ptr(), x.data_ptr(), x.stride(0)
+        d.src_ids, d.src_scale = _ptr(ids), _ptr(scale)
+        d.F, d.ids_kind, d.mean, d.col0 = int(x.shape[1]), _sage_ids_kind(ids), int(bool(mean)), at
+        at += int(x.shape[1])
+    x_dst, dst_rows, dst_ids = root if root is not None else (None, None, None)
+    if x_dst is not None:
+        assert x_dst.dtype == torch.float32 and x_dst.stride(1) == 1 and (dst_rows is None or dst_rows.dtype == torch.int64)
+        at += int(x_dst.shape[1])
+    assert wt.dtype == torch.float32 and wt.stride(1) == 1 and wt.shape[0] == N and wt.shape[1] >= at
+    if out is None:
+        out = torch.empty((n_rows, N), dtype=torch.float32, device=wt.device)
+    assert out.stride(1) == 1 and out.shape[1] == N and (acc_in is None or (acc_in.stride(1) == 1 and acc_in.shape == (n_rows, N)))
+    assert out_rows is None or (out_rows.dtype == torch.int64 and out_rows.is_contiguous())
+    common = (arr, len(rels), n_rows, _ptr(x_dst), 0 if x_dst is None else x_dst.stride(0), 0 if x_dst is None else int(x_dst.shape[1]),
+              _ptr(dst_rows), _ptr(dst_ids), _sage_ids_kind(dst_ids), wt.data_ptr(), wt.stride(0), N, _ptr(bias),
+              L.HETERO_SAGE_RELU if relu else 0, _ptr(acc_in), 0 if acc_in is None else acc_in.stride(0), _ptr(out_rows),
+              out.data_ptr(), out.stride(0))
+    if c_out is not None:
+        assert c_out.stride(1) == 1 and c_out.shape[0] == n_rows and c_out.shape[1] >= at
+        L.check(L.lib().wgamd_hetero_sage_layer_f32_train(*common, c_out.data_ptr(), c_out.stride(0), get_stream()),
+                "wgamd_hetero_sage_layer_f32_train")
+    else:
+        L.check(L.lib().wgamd_hetero_sage_layer_f32(*common, get_stream()), "wgamd_hetero_sage_layer_f32")
+    hetero_sage_launches += 1
+    return out
+
+
+class _SageGroup:
+    """What one (hop, destination type) group of the hetero SAGE layer launches over: per relation block ``(row_ptr, col, x, ids,
+    mean, src)`` (``src``: index of x among the group's differentiable source tensors, None for a table read through a node
+    list), the root ``(x_dst, dst_rows, dst_ids)`` or None, the plan, and the ``RelationHop`` of every block (None: the hop
+    lists no such relation) for the transposes of the backward pass."""
+
+    def __init__(self, blocks, hops, root, plan, n_rows, N, relu, tag):
+        self.blocks, self.hops, self.root, self.plan = blocks, hops, root, plan
+        self.n_rows, self.N, self.relu, self.tag = n_rows, N, relu, tag
+        self.col0 = [0]
+        for b in blocks:
+            self.col0.append(self.col0[-1] + int(b[2].shape[1]))
+        self.K = self.col0[-1] + (int(root[0].shape[1]) if root is not None else 0)
+
+    def run(self, wstack, bias, out=None, out_rows=None, c_out=None):
+        """The group's launches -> act(C @ wstack^T + bias), placed through ``out_rows`` into ``out`` when given."""
+        acc = None
+        for k, (lo, hi, with_root) in enumerate(self.plan):
+            last = k == len(self.plan) - 1
+            rels = [(b[0], b[1], b[2], b[3], None, b[4]) for b in self.blocks[lo:hi]]
+            at = self.col0[lo]
+            names = ",".join(str(h.edge_type[1]) for h in self.hops[lo:hi] if h is not None)
+            name = "sage%s:%s (%d rows, launch %d/%d)" % (self.tag, names, self.n_rows, k + 1, len(self.plan))
+            res = _stage(name, lambda: hetero_sage_launch(
+                rels, self.n_rows, wstack[:, at:], self.N, root=self.root if with_root else None, bias=bias if last else None,
+                relu=self.relu and last, acc_in=acc, out_rows=out_rows if last else None, out=out if last else None,
+                c_out=None if c_out is None else c_out[:, at:]))
+            acc = res
+        return acc
+
+
+def _relation_transpose(r: RelationHop, n_src: int, mean: bool):
+    """``(row_ptr_t, col_t, scale)`` of a relation hop seen from its ``n_src`` input rows (entries = the hop's frontier entries,
+    hop order inside a source row: deterministic sums; ``scale`` = 1 / degree of every frontier entry for a mean relation) —
+    computed once and kept on the ``RelationHop``."""
+    hit = getattr(r, "_sage_t", None)
+    if hit is None or hit[0] != n_src:
+        if r.n_edges > 0:
+            row_ptr_t, _, _, col_t = _csr_transpose(r.row_ptr, r.col, n_src, want_col_t=True)
+        else:
+            row_ptr_t, col_t = torch.zeros(n_src + 1, dtype=torch.int32, device=r.row_ptr.device), r.col
+        deg = (r.row_ptr[1:] - r.row_ptr[:-1]).clamp(min=1)
+        hit = (n_src, row_ptr_t, col_t, (1.0 / deg.float()).contiguous())
+        r._sage_t = hit
+    return hit[1], hit[2], (hit[3] if mean else None)
+
+
+class _HeteroSageGroup(torch.autograd.Function):
+    """One (hop, destination type) group of the hetero SAGE layer under autograd.  Differentiable inputs: the stacked weight,
+    the bias sum, the resident destination rows and the resident source tensors.  Forward: the group's launches in their
+    ``_train`` form (C kept).  Backward: ``wgamd_gcn_wgrad_f32`` over column blocks of C (dW, db: deterministic split-K);
+    the root's ``dX_dst[dst_rows] = dZ W_root`` (a library GEMM, rows distinct); per resident source type the layer kernel
+    itself over the relations' transposes with dZ as the input rows and the relations' ``W_l`` transposed as the weight — no
+    atomics anywhere: the same bits from run to run."""
+
+    @staticmethod
+    def forward(ctx, grp, wstack, bias, x_dst, *srcs):
+        w, b = wstack.detach(), None if bias is None else bias.detach()
+        c = _agg_pool.take((grp.n_rows, grp.K), torch.float32, w.device)
+        z = grp.run(w, b, c_out=c)
+        ctx.grp, ctx.c, ctx.n_srcs = grp, c, len(srcs)
+        ctx.src_shapes = [tuple(t.shape) for t in srcs]
+        ctx.dst_shape = None if x_dst is None else tuple(x_dst.shape)
+        ctx.save_for_backward(w, z)
+        return z
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.c is None:
+            raise RuntimeError("wholegraph_amd.nn.HeteroConv: backward through this SAGE layer a second time — its kept rows were "
+                               "released by the first backward pass (retain_graph=True is not supported by the one-kernel layer)")
+        grp, c = ctx.grp, ctx.c
+        w, z = ctx.saved_tensors
+        N, K = grp.N, grp.K
+        g = g.contiguous().float()
+        if grp.relu:
+            g = torch.ops.aten.threshold_backward(g, z, 0)          # dZ once, read by every gradient
+        need_w, need_b, need_dst = ctx.needs_input_grad[1:4]
+        gw = gb = gdst = None
+        if need_w or need_b:
+            gw = torch.empty((N, K), dtype=torch.float32, device=g.device)
+            gb = torch.empty(N, dtype=torch.float32, device=g.device) if need_b else None
+            for at in range(0, K, 256):
+                blk = torch.empty((N, min(256, K - at)), dtype=torch.float32, device=g.device)
+                gcn_wgrad(c[:, at:at + blk.shape[1]], g, blk, gb if at == 0 else None)
+                gw[:, at:at + blk.shape[1]] = blk
+            if not need_w:
+                gw = None
+        if need_dst and grp.root is not None:
+            rows = grp.root[1]
+            gdst = torch.zeros(ctx.dst_shape, dtype=torch.float32, device=g.device)
+            gdst.index_copy_(0, rows, g @ w[:, grp.col0[-1]:])      # (rows of one group are distinct vertices)
+        gsrcs = [None] * ctx.n_srcs
+        for si in range(ctx.n_srcs):
+            if not ctx.needs_input_grad[4 + si]:
+                continue
+            mine = [k for k, blk in enumerate(grp.blocks) if blk[5] == si and grp.hops[k] is not None and grp.hops[k].n_edges > 0]
+            n_src, F_ = ctx.src_shapes[si]
+            gx = None
+            fits = N % 4 == 0 and F_ <= 256 and g.data_ptr() % 16 == 0
+            per = max(1, min(L.HETERO_SAGE_MAX_RELATIONS, HETERO_SAGE_MAX_K // N))      # relations per launch: K = per N <= 1024
+            while mine:
+                now, mine = mine[:per], mine[per:]
+                if fits:
+                    rels = []
+                    for k in now:
+                        row_ptr_t, col_t, scale = _relation_transpose(grp.hops[k], n_src, grp.blocks[k][4])
+                        rels.append((row_ptr_t, col_t, g, None, scale, False))
+                    wt = torch.cat([w[:, grp.col0[k]:grp.col0[k + 1]].t() for k in now], 1).contiguous()
+                    gx = _stage("sage%s dX" % grp.tag, lambda: hetero_sage_launch(rels, n_src, wt, F_, acc_in=gx))
+                else:
+                    for k in now:
+                        part = spmm_csr_backward(grp.blocks[k][0], grp.blocks[k][1], g @ w[:, grp.col0[k]:grp.col0[k + 1]], n_src,
+                                                 mean=grp.blocks[k][4])
+                        gx = part if gx is None else gx.add_(part)
+            gsrcs[si] = gx if gx is not None else torch.zeros((n_src, F_), dtype=torch.float32, device=g.device)
+        ctx.c = None
+        return (None, gw, gb, gdst) + tuple(gsrcs)
+
+
 class HeteroConv(torch.nn.Module):
-    """``torch_geometric.nn.HeteroConv({edge_type: conv}, aggr="sum")`` for ``GATConv`` relations: the output of a node type
-    is the sum over the relations ending in it (examples/mag_lp_mnmg.py:141 builds this stack; GATConv as
-    pylibwholegraph/torch/gnn_model.py:45-59).
+    """``torch_geometric.nn.HeteroConv({edge_type: conv}, aggr="sum")`` for ``GATConv`` relations, or for ``SAGEConv``
+    relations: the output of a node type is the sum over the relations ending in it (examples/mag_lp_mnmg.py:141 builds this
+    stack; GATConv as pylibwholegraph/torch/gnn_model.py:45-59; bipartite SAGEConv per direction as movielens_mnmg.py).
 
     ``forward(x_dict, graph, act=None)``
       * ``graph`` a ``HeteroLayerGraph`` of a loader call group (no autograd): every (hop, edge type) is ONE launch —
@@ -2695,7 +2891,8 @@ class HeteroConv(torch.nn.Module):
         weights are applied to the few destination rows afterwards: the ``lin`` GEMM over every source row, 10-20x more rows,
         never runs), attention logits ``x @ fold(W, att)`` made by the feature gather itself when ``x_dict[t]`` is a
         ``LazyRows`` (``wgamd_gather_terms_f32``), HeteroConv's running sum, bias, ReLU and the row placement folded into the
-        last relation's launch (``wgamd_gat_layer_fused_bf16x3`` / ``wgamd_gat_transform_heads_bf16x3``).
+        last relation's launch (``wgamd_gat_layer_fused_bf16x3`` / ``wgamd_gat_transform_heads_bf16x3``).  With ``SAGEConv``
+        relations (autograd too) every (hop, destination type) is ONE launch: ``_forward_layer_sage``.
       * ``graph`` a dict ``{edge_type: edge_index | [csr_row_ptr, csr_col_ind]}`` (a mini-batch ``HeteroData``; autograd):
         ``convs[edge_type]((x_src, x_dst), graph[edge_type])`` summed per destination type — PyG's own formulation."""
 
@@ -2760,6 +2957,8 @@ class HeteroConv(torch.nn.Module):
     def _bias(self, dt):
         """Sum of the biases of the relations ending in ``dt`` (HeteroConv adds the relations' outputs, bias included)."""
         rels = [et for et in self.edge_types if et[2] == dt]
+        if rels and all(isinstance(self.conv(et), SAGEConv) for et in rels):
+            return self._sage_weights(dt)[1]
         for et in rels:
             self._rel(et)
         hit = self._folded.get(("bias", dt))
@@ -2889,12 +3088,18 @@ class HeteroConv(torch.nn.Module):
 
     def _width(self, dt):
         c = next(self.conv(et) for et in self.edge_types if et[2] == dt)
-        return c.heads * c.out_channels if c.concat else c.out_channels
+        return c.heads * c.out_channels if getattr(c, "concat", False) else c.out_channels
 
     def forward(self, x_dict, graph, act=None):
         # (folded attention vectors, weight tiles, pooled buffers: cached against the parameters' versions)
         _refuse_capture(self, "derived-weight caches")
         if isinstance(graph, HeteroLayerGraph):
+            sage = [isinstance(self.conv(et), SAGEConv) for et in self.edge_types]
+            if all(sage):
+                return self._forward_layer_sage(x_dict, graph, act)
+            if any(sage) or not all(isinstance(self.conv(et), GATConv) for et in self.edge_types):
+                raise NotImplementedError("HeteroConv over a HeteroLayerGraph: every relation a GATConv, or every relation a "
+                                          "SAGEConv (mixed layer classes run over a dict of edge_index only)")
             needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
             plain = all(self.conv(et).concat and not self.conv(et).add_self_loops for et in self.edge_types)
             if not needs_grad and plain:
@@ -2911,6 +3116,170 @@ class HeteroConv(torch.nn.Module):
             y = self.conv(et)((x_dict[et[0]], x_dict[et[2]]), graph[et])
             out[et[2]] = y if et[2] not in out else out[et[2]] + y
         return {t: torch.relu(v) for t, v in out.items()} if act == "relu" else out
+
+    # ---- SAGEConv relations: one launch per (hop, destination type) -----------------------------------------------------
+    def _sage_weights(self, dt, grad: bool = False):
+        """``(Wstack [N, K], bias sum [N] | None)`` of destination type ``dt``: ``[W_l^r1 | W_l^r2 | ... | sum_r W_r^r]`` over the
+        relations ending in it (sorted edge types; the root block is absent when no relation has a root weight).  ``grad``:
+        built by torch ops on the parameters (autograd hands each relation its slice and every ``lin_r`` the shared root
+        gradient); otherwise detached and cached against the parameters' versions."""
+        convs = [self.conv(et) for et in self.edge_types if et[2] == dt]
+        ps = [p for c in convs for p in c.parameters()]
+        key = tuple((p._version, p.data_ptr()) for p in ps) + (_weights_gen,)
+        hit = self._folded.get(("sage", dt))
+        if not grad and hit is not None and hit[0] == key:
+            return hit[1:]
+        with torch.set_grad_enabled(grad):
+            roots = [c.lin_r.weight for c in convs if c.lin_r is not None]
+            parts = [c.lin_l.weight for c in convs]
+            if roots:
+                parts.append(roots[0] if len(roots) == 1 else torch.stack(roots).sum(0))
+            wstack = torch.cat(parts, 1)
+            bs = [c.lin_l.bias for c in convs if c.lin_l.bias is not None]
+            bias = None if not bs else (bs[0] if len(bs) == 1 else torch.stack(bs).sum(0))
+        if not grad:
+            wstack, bias = wstack.detach(), None if bias is None else bias.detach()
+            self._folded[("sage", dt)] = (key, wstack, bias)
+        return wstack, bias
+
+    def _forward_layer_sage(self, xs, graph: HeteroLayerGraph, act=None):
+        """``HeteroConv({edge_type: SAGEConv})`` over a call group's layer graph: per (hop, destination type) the sum over the
+        relations ending in the type is ONE product ``[mean_r1 | mean_r2 | ... | x_dst] @ [W_l^r1 | W_l^r2 | ... | sum W_r]^T``
+        — one ``wgamd_hetero_sage_layer_f32`` launch (a group wider than 1024 floats: consecutive launches of whole relations,
+        ``hetero_sage_plan``), bias, ReLU and row placement folded in.  A ``LazyRows`` input (int64 ids, fp32 table, 16-B rows)
+        is read through its node list, per node type.  Under autograd one ``_HeteroSageGroup`` per group.  Shapes outside the
+        kernel's domain: ``_forward_sage_library``."""
+        if act not in (None, "relu"):
+            raise ValueError("HeteroConv: act is None or 'relu', not %r" % (act,))
+        relu = act == "relu"
+        X, ids = {}, {}
+        for t, v in xs.items():
+            if v is None:
+                continue
+            if isinstance(v, LazyRows):
+                if torch.is_grad_enabled() and getattr(v.table, "requires_grad", False):
+                    raise NotImplementedError("gradient w.r.t. a feature table read through ids (LazyRows): trainable node "
+                                              "embeddings go through wholegraph_amd.embedding, or pass x = emb[n_id]")
+                if isinstance(v.table, torch.Tensor) and v.ids.dtype == torch.int64 and _kernel_rows_ok(v.table) and v._rows is None:
+                    X[t], ids[t] = v.table, v.ids
+                    continue
+                v = v.materialize()
+            X[t], ids[t] = v, None
+        convs = [self.conv(et) for et in self.edge_types]
+        in_domain = all(c.aggr in ("mean", "sum", "add") and c.out_channels <= 256 for c in convs) and all(
+            _kernel_rows_ok(v) and v.shape[1] % 4 == 0 and v.shape[1] <= HETERO_SAGE_MAX_K for v in X.values())
+        if not in_domain:
+            return self._forward_sage_library({t: (v.materialize() if isinstance(v, LazyRows) else v) for t, v in xs.items()
+                                               if v is not None}, graph, relu)
+        needs_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
+                                                  or any(ids[t] is None and v.requires_grad for t, v in X.items()))
+        dev = next(iter(X.values())).device
+        groups = {}
+        for r in graph.relations:
+            groups.setdefault((r.hop, r.edge_type[2]), []).append(r)
+        make = torch.zeros if needs_grad else torch.empty
+        out = {t: make((n, self._width(t)), dtype=torch.float32, device=dev) for t, n in graph.n_out.items()
+               if n > 0 and any(dt == t for _, dt in groups)}
+        weights = {}
+        for (hop, dt), mine in sorted(groups.items(), key=lambda kv: (kv[0][0], kv[0][1])):
+            n_f = mine[0].n_rows
+            if n_f == 0:
+                continue
+            listed = {r.edge_type: r for r in mine}
+            blocks, hops, srcs = [], [], []
+            for et in self.edge_types:
+                if et[2] != dt:
+                    continue
+                c, x, r = self.conv(et), X[et[0]], listed.get(et)
+                if x.shape[1] != c.lin_l.weight.shape[1]:
+                    raise ValueError("HeteroConv: x_dict[%r] has %d features, SAGEConv of %r takes %d"
+                                     % (et[0], x.shape[1], et, c.lin_l.weight.shape[1]))
+                si = None
+                if ids[et[0]] is None:
+                    si = next((k for k, t in enumerate(srcs) if t is x), None)
+                    if si is None:
+                        srcs.append(x)
+                        si = len(srcs) - 1
+                if r is None:       # the hop lists no such relation: its root term and bias still count
+                    row_ptr, col = torch.zeros(n_f + 1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+                else:
+                    row_ptr, col = r.row_ptr, r.col
+                blocks.append((row_ptr, col, x, ids[et[0]], c.aggr == "mean", si))
+                hops.append(r)
+            root = root_src = None
+            roots = [self.conv(et).lin_r for et in self.edge_types if et[2] == dt and self.conv(et).lin_r is not None]
+            if roots:
+                F_dst = roots[0].weight.shape[1]
+                if X[dt].shape[1] != F_dst:
+                    raise ValueError("HeteroConv: x_dict[%r] has %d features, the root weights take %d" % (dt, X[dt].shape[1], F_dst))
+                root = (X[dt], mine[0].dst_rows, ids[dt])
+                root_src = X[dt] if ids[dt] is None else None
+            plan = hetero_sage_plan([b[2].shape[1] for b in blocks], 0 if root is None else root[0].shape[1])
+            grp = _SageGroup(blocks, hops, root, plan, n_f, self._width(dt), relu, self.stage_tag + " hop %d %s" % (hop + 1, dt))
+            place = mine[0].out_rows
+            if dt not in weights:
+                weights[dt] = self._sage_weights(dt, grad=needs_grad)
+            wstack, bias = weights[dt]
+            if needs_grad:
+                z = _HeteroSageGroup.apply(grp, wstack, bias, root_src, *srcs)
+                if place is None:
+                    out[dt] = z
+                else:
+                    out[dt].index_copy_(0, place, z)      # (in place: the hops of a type write disjoint rows of one buffer)
+            elif place is None:
+                out[dt] = grp.run(wstack, bias)
+            else:
+                grp.run(wstack, bias, out=out[dt], out_rows=place)
+        return out
+
+    def _forward_sage_library(self, x, graph: HeteroLayerGraph, relu: bool):
+        """The same layer out of library ops in PyG's formulation, relation by relation, with ordinary autograd — what shapes
+        outside the kernel's domain (F % 4 != 0, N > 256, other dtypes, CPU tensors, other aggregators) take; correctness only."""
+        dev = next(iter(x.values())).device
+        groups = {}
+        for r in graph.relations:
+            groups.setdefault((r.hop, r.edge_type[2]), []).append(r)
+        out = {}
+        for (hop, dt), mine in sorted(groups.items(), key=lambda kv: (kv[0][0], kv[0][1])):
+            n_f = mine[0].n_rows
+            if n_f == 0:
+                continue
+            listed = {r.edge_type: r for r in mine}
+            y = None
+            for et in self.edge_types:
+                if et[2] != dt:
+                    continue
+                c, r, xs = self.conv(et), listed.get(et), x[et[0]]
+                agg = torch.zeros((n_f, xs.shape[1]), dtype=xs.dtype, device=dev)
+                if r is not None and r.n_edges > 0:
+                    if xs.is_cuda and xs.dtype == torch.float32 and c.aggr in ("mean", "sum", "add"):
+                        agg = spmm_csr(xs, r.row_ptr, r.col, "mean" if c.aggr == "mean" else "sum")
+                    else:
+                        deg = (r.row_ptr[1:] - r.row_ptr[:-1]).long()
+                        row = torch.repeat_interleave(torch.arange(n_f, device=dev), deg)
+                        rows = xs[r.col.long()[:r.n_edges]]
+                        if c.aggr in ("mean", "sum", "add"):
+                            agg = agg.index_add(0, row, rows)
+                            if c.aggr == "mean":
+                                agg = agg / deg.clamp(min=1).unsqueeze(1).to(agg.dtype)
+                        elif c.aggr in ("max", "min"):
+                            agg = agg.scatter_reduce(0, row.unsqueeze(1).expand_as(rows), rows, "a" + c.aggr, include_self=False)
+                        else:
+                            raise NotImplementedError("HeteroConv: SAGEConv aggr %r (mean, sum, max, min)" % (c.aggr,))
+                o = c.lin_l(agg)
+                if c.lin_r is not None:
+                    o = o + c.lin_r(x[dt][mine[0].dst_rows])
+                y = o if y is None else y + o
+            if relu:
+                y = torch.relu(y)
+            place = mine[0].out_rows
+            if place is None:
+                out[dt] = y
+            else:
+                if dt not in out:
+                    out[dt] = torch.zeros((graph.n_out[dt], y.shape[1]), dtype=y.dtype, device=dev)
+                out[dt] = out[dt].index_copy(0, place, y)
+        return out
 
     def _forward_layer_train(self, xs, graph: HeteroLayerGraph, act=None):
         """The call-group layer under autograd, AGGREGATE-FIRST like the inference route: per relation the attention-weighted

@@ -856,6 +856,48 @@ wholememory_error_code_t wgamd_transformer_bwd_src_f32(const int* row_ptr_t, con
                                                        const float* u, int64_t ldu, float* gx, int64_t ldgx, int accumulate,
                                                        void* stream);
 
+/* ---- Heterogeneous SAGE layer (csrc/wg_sage_hetero.hip): HeteroConv({edge type: SAGEConv}, aggr = "sum") over one (hop,
+ * destination type) of a call group — the sum over the relations ending in the type as ONE product:
+ *   C[i]   = [ REDUCE_0(i) | ... | REDUCE_(n_rel-1)(i) | XD[dst_rows[i]] ]                  K = sum_r F_r + F_dst floats
+ *   REDUCE_r(i) = (mean_r ? 1 / deg_r(i) : 1) sum_{e in row i of r} src_scale_r[col_r[e]] X_r[col_r[e]]    (src_scale nullable = 1)
+ *   out[out_rows ? out_rows[i] : i] = act( C[i] @ wt^T + bias + acc_in[i] )
+ * Every relation has its own CSR over the same n_rows rows, its own input X_r[j] = x[ids_kind ? src_ids[j] : j] (ids_kind 0: by
+ * row, 1: int32 node list, 2: int64 node list) and its own width F; col0 is the column of its block in C (blocks back to back
+ * from 0, in array order; the root block follows them).  Root block: XD[r] = x_dst[dst_ids_kind ? dst_ids[r] : r], dst_rows
+ * nullable = row i itself, x_dst nullable = no root block.  wt [N, ldw] row-major = [ W_l^0 | ... | sum_r W_r^r ]; bias, acc_in
+ * ([n_rows, ld_acc]: the running sum of an earlier launch of the same rows) and out_rows nullable.  An empty row reduces to 0.
+ * Sums run in CSR order: run-to-run deterministic.  _train also writes C ([n_rows, ldc], 16-B aligned rows; same bits as the
+ * operand of the product) for the weight gradient (wgamd_gcn_wgrad_f32 over column blocks of it).
+ * Domain: wgamd_hetero_sage_layer_supported (at most WGAMD_HETERO_SAGE_MAX_RELATIONS relations, every F and F_dst a multiple
+ * of 4, N <= 256, 0 < K <= 1024; F_dst = 0: no root block); x / x_dst / wt rows 16-B aligned.  The product runs on the exact fp32
+ * matrix pipe (v_mfma_f32_16x16x4_f32). */
+#define WGAMD_HETERO_SAGE_MAX_RELATIONS 8
+#define WGAMD_HETERO_SAGE_RELU 1
+typedef struct {
+  const int* row_ptr;
+  const int* col;
+  const float* x;
+  int64_t ldx;
+  const void* src_ids;
+  const float* src_scale;
+  int F;
+  int ids_kind;
+  int mean;
+  int col0;
+} wgamd_hetero_sage_relation_t;
+int wgamd_hetero_sage_layer_supported(const int* F, int n_rel, int F_dst, int N);
+wholememory_error_code_t wgamd_hetero_sage_layer_f32(const wgamd_hetero_sage_relation_t* rels, int n_rel, int64_t n_rows,
+                                                     const float* x_dst, int64_t ldx_dst, int F_dst, const int64_t* dst_rows,
+                                                     const void* dst_ids, int dst_ids_kind, const float* wt, int64_t ldw, int N,
+                                                     const float* bias, int flags, const float* acc_in, int64_t ld_acc,
+                                                     const int64_t* out_rows, float* out, int64_t ldo, void* stream);
+wholememory_error_code_t wgamd_hetero_sage_layer_f32_train(const wgamd_hetero_sage_relation_t* rels, int n_rel, int64_t n_rows,
+                                                           const float* x_dst, int64_t ldx_dst, int F_dst, const int64_t* dst_rows,
+                                                           const void* dst_ids, int dst_ids_kind, const float* wt, int64_t ldw,
+                                                           int N, const float* bias, int flags, const float* acc_in,
+                                                           int64_t ld_acc, const int64_t* out_rows, float* out, int64_t ldo,
+                                                           float* c_out, int64_t ldc, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
