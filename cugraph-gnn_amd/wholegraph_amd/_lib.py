@@ -327,6 +327,17 @@ SYMBOLS = {
     "wgamd_hetero_sage_layer_f32_train": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int,
                                                   c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p,
                                                   c_int64, c_void_p, c_int64, c_void_p]),
+    # GIN layer and add pooling (wg_gin.hip)
+    "wgamd_gin_layer_supported": (c_int, [c_int, c_int, c_int]),
+    "wgamd_gin_layer_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int,
+                                    c_void_p, c_int64, c_void_p]),
+    "wgamd_gin_layer_f32_train": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                          c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                                          c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "wgamd_gin_aggregate_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                        c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "wgamd_segment_sum_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "wgamd_bias_act_rows_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "wgamd_gat_transform_heads_supported": (c_int, [c_int, c_int, c_int]),
     "wgamd_gat_transform_weight_bytes": (c_size_t, [c_int, c_int, c_int]),

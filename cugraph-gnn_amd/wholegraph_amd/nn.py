@@ -2545,6 +2545,439 @@ class TransformerConv(torch.nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# GIN (torch_geometric.nn.GINConv with the GIN paper's MLP, and global_add_pool; the model of the reference's cugraph-pyg
+# example dist_gin_sg.py) — csrc/wg_gin.hip
+# ---------------------------------------------------------------------------------------------------------------------
+GIN_RELU_HIDDEN, GIN_RELU_OUT = 1, 2     # WGAMD_GIN_* (include/wgamd_ext.h)
+
+
+def gin_layer_supported(F_: int, H: int, N: int = 0) -> bool:
+    """Shapes of the one-kernel GIN layer (``wgamd_gin_layer_f32``): F % 4 == 0; F, H, N <= 256; H % 4 == 0 with a second
+    product (N > 0; N = 0: the layer ends after the first product)."""
+    return bool(L.lib().wgamd_gin_layer_supported(int(F_), int(H), int(N)))
+
+
+def _gin_hop_args(row_ptr, col, x, self_rows, x_dst, eps, src_ids):
+    _check_csr(row_ptr, col)
+    F_ = x.shape[1]
+    assert x.dtype == torch.float32 and x.stride(1) == 1
+    assert self_rows is None or (self_rows.dtype == torch.int64 and self_rows.is_contiguous())
+    assert x_dst is None or (x_dst.dtype == torch.float32 and x_dst.stride(1) == 1 and x_dst.shape[1] == F_
+                             and x_dst.shape[0] >= row_ptr.shape[0] - 1)
+    assert eps is None or (eps.dtype == torch.float32 and eps.is_cuda and eps.numel() == 1)
+    ids_ptr, ids_dt = _ids_args(x, src_ids)
+    return (row_ptr.data_ptr(), _nonempty(col, torch.int32).data_ptr(), row_ptr.shape[0] - 1, x.data_ptr(), x.stride(0), F_, ids_ptr,
+            ids_dt, None if x_dst is not None else _ptr(self_rows), _ptr(x_dst), 0 if x_dst is None else x_dst.stride(0), _ptr(eps))
+
+
+def gin_layer_forward(row_ptr, col, x, self_rows, w1, b1=None, w2=None, b2=None, eps=None, relu_hidden=True, relu_out=False,
+                      src_ids=None, x_dst=None, out=None, keep=False, agg_out=None, hidden_out=None):
+    """A whole GIN layer over one hop in ONE kernel (``wgamd_gin_layer_f32``, include/wgamd_ext.h):
+    ``act2(act1(agg @ w1^T + b1) @ w2^T + b2)`` with ``agg = sum of the neighbour rows + (1 + eps) self row``; ``w1`` [H, F] and
+    ``w2`` [N, H] in ``torch.nn.Linear`` layout, ``eps`` a one-element float32 device tensor (None: 0).  ``w2 = None``: the layer
+    ends after the first product (output [n_rows, H]).  The self row of destination i is ``x_dst[i]`` when ``x_dst`` is given,
+    else row ``self_rows[i]`` of x; neither: no self term.  ``keep`` (or ``agg_out`` / ``hidden_out`` buffers): the launch also
+    stores the aggregate and, with a second product, the hidden activation (``_train``), and ``(out, agg, hidden)`` is returned."""
+    hop = _gin_hop_args(row_ptr, col, x, self_rows, x_dst, eps, src_ids)
+    n_rows, F_, H = row_ptr.shape[0] - 1, x.shape[1], w1.shape[0]
+    N = 0 if w2 is None else w2.shape[0]
+    for w, k in ((w1, F_), (w2, H)):
+        assert w is None or (w.dtype == torch.float32 and w.stride(1) == 1 and w.shape[1] == k)
+    dev = row_ptr.device
+    if out is None:
+        out = torch.empty((n_rows, N or H), dtype=torch.float32, device=dev)
+    assert out.shape == (n_rows, N or H) and out.stride(1) == 1
+    flags = (GIN_RELU_HIDDEN if relu_hidden else 0) | (GIN_RELU_OUT if relu_out else 0)
+    common = hop + (w1.data_ptr(), w1.stride(0), H, _ptr(b1), _ptr(w2), 0 if w2 is None else w2.stride(0), N, _ptr(b2), flags,
+                    out.data_ptr(), out.stride(0))
+    if not (keep or agg_out is not None or hidden_out is not None):
+        L.check(L.lib().wgamd_gin_layer_f32(*common, get_stream()), "wgamd_gin_layer_f32")
+        return out
+    if keep and agg_out is None:
+        agg_out = torch.empty((n_rows, F_), dtype=torch.float32, device=dev)
+    if keep and hidden_out is None and w2 is not None:
+        hidden_out = torch.empty((n_rows, H), dtype=torch.float32, device=dev)
+    assert agg_out is None or (agg_out.shape == (n_rows, F_) and agg_out.stride(1) == 1)
+    assert hidden_out is None or (w2 is not None and hidden_out.shape == (n_rows, H) and hidden_out.stride(1) == 1)
+    L.check(L.lib().wgamd_gin_layer_f32_train(*common, _ptr(agg_out), 0 if agg_out is None else agg_out.stride(0), _ptr(hidden_out),
+                                              0 if hidden_out is None else hidden_out.stride(0), get_stream()),
+            "wgamd_gin_layer_f32_train")
+    return out, agg_out, hidden_out
+
+
+def gin_aggregate(row_ptr, col, x, self_rows, eps=None, src_ids=None, x_dst=None, out=None):
+    """The GIN aggregate alone, any F (``wgamd_gin_aggregate_f32``): the sum of the neighbour rows plus ``(1 + eps)`` times the
+    self row (``gin_layer_forward``'s)."""
+    hop = _gin_hop_args(row_ptr, col, x, self_rows, x_dst, eps, src_ids)
+    n_rows, F_ = row_ptr.shape[0] - 1, x.shape[1]
+    if out is None:
+        out = torch.empty((n_rows, F_), dtype=torch.float32, device=row_ptr.device)
+    assert out.shape == (n_rows, F_) and out.stride(1) == 1
+    L.check(L.lib().wgamd_gin_aggregate_f32(*hop, out.data_ptr(), out.stride(0), get_stream()), "wgamd_gin_aggregate_f32")
+    return out
+
+
+def _gin_self_rows(src, ids, x_dst, graph: LayerGraph):
+    """The self rows of a GIN layer's destinations as a tensor [n_rows, F] (the operand of d eps)."""
+    if x_dst is not None:
+        return x_dst[:graph.n_rows]
+    self_all = torch.cat([h.self_rows for h in graph.hops])
+    if ids is None:
+        return src[self_all]
+    if getattr(src, "byte_offset_ids", False):
+        raise NotImplementedError("GINConv(train_eps=True) over a peer-mapped feature table: pass the gathered rows")
+    return src[ids[self_all].long()]
+
+
+def _gin_hop_self(h: HopGraph, rows, x_dst, no_root: bool):
+    """``(self_rows, x_dst rows)`` of one hop as the kernels take them."""
+    if no_root:
+        return None, None
+    return (None, x_dst[rows]) if x_dst is not None else (h.self_rows, None)
+
+
+def _gin_input_grad(graph: LayerGraph, g, n_src: int, eps, has_self: bool, weight=None):
+    """``A^T g + (1 + eps) S^T g`` over every hop of ``graph`` (rows = the layer's input rows; the second term only where an
+    input row is a destination itself, and only with ``has_self``), times ``weight`` ([F, Hq]) when given: the GIN kernels run
+    over the hops' transposes."""
+    gx = None
+    for h, rows, _ in _hops(graph):
+        if h.n_rows == 0:
+            continue
+        row_ptr_t, col_t, _ = h.transposed(n_src, need_self=False)
+        self_t = h.input_dst(n_src) if has_self else None
+        if weight is None:
+            gh = gin_aggregate(row_ptr_t, col_t, g[rows], self_t, eps=eps)
+        else:
+            gh = gin_layer_forward(row_ptr_t, col_t, g[rows], self_t, weight, eps=eps, relu_hidden=False)
+        gx = gh if gx is None else gx.add_(gh)
+    if gx is None:
+        gx = torch.zeros((n_src, g.shape[1] if weight is None else weight.shape[0]), dtype=torch.float32, device=g.device)
+    return gx
+
+
+class _GinLayer(torch.autograd.Function):
+    """The one-kernel GIN layer over a ``LayerGraph`` (one ``wgamd_gin_layer_f32`` launch per hop; under autograd the ``_train``
+    form keeps the aggregate and the hidden activation).  Backward, no atomics: ``wgamd_gcn_wgrad_f32`` per hop and product
+    (dW2, db2 from the hidden activation; dW1, db1 from the aggregate), one library GEMM between them (dHidden = dOut W2), and
+    for the input rows the GIN kernel over every hop's transpose with ``W1^T`` as its only weight."""
+
+    @staticmethod
+    def forward(ctx, src, x_dst, eps, w1, b1, w2, b2, graph, ids, relu_hidden, relu_out, n_src, no_root):
+        H, F_ = w1.shape
+        two = w2 is not None
+        keep = any(ctx.needs_input_grad[:7])
+        dev = w1.device
+        n = graph.n_rows
+        out = torch.empty((n, w2.shape[0] if two else H), dtype=torch.float32, device=dev)
+        agg = torch.empty((n, F_), dtype=torch.float32, device=dev) if keep else None
+        hidden = torch.empty((n, H), dtype=torch.float32, device=dev) if keep and two else None
+        det = lambda t: None if t is None else t.detach()      # noqa: E731
+        for h, rows, _ in _hops(graph):
+            if h.n_rows > 0:
+                self_rows, xd = _gin_hop_self(h, rows, det(x_dst), no_root)
+                gin_layer_forward(h.row_ptr, h.col, src, self_rows, det(w1), det(b1), det(w2), det(b2), eps=det(eps),
+                                  relu_hidden=relu_hidden, relu_out=relu_out, src_ids=ids, x_dst=xd, out=out[rows],
+                                  agg_out=None if agg is None else agg[rows], hidden_out=None if hidden is None else hidden[rows])
+        if keep:
+            ctx.save_for_backward(w1, w2, eps, out, x_dst)
+            ctx.kept = (agg, hidden)
+            ctx.src = src if ctx.needs_input_grad[2] else None      # (d eps reads the self rows; a mapped table is no tensor)
+            ctx.graph, ctx.ids, ctx.flags, ctx.n_src, ctx.no_root = graph, ids, (relu_hidden, relu_out), n_src, no_root
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if ctx.kept is None:
+            raise RuntimeError("wholegraph_amd.nn.GINConv: backward through this layer a second time — its kept activations were "
+                               "released by the first backward pass (retain_graph=True is not supported by the one-kernel layer)")
+        w1, w2, eps, out, x_dst = ctx.saved_tensors
+        agg, hidden = ctx.kept
+        src = ctx.src
+        relu_hidden, relu_out = ctx.flags
+        need_x, need_xd, need_eps, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:7]
+        H, F_ = w1.shape
+        dev = g.device
+        graph = ctx.graph
+        g = g.contiguous().float()
+        gw1 = gb1 = gw2 = gb2 = None
+        some = any(h.n_rows > 0 for h in graph.hops)
+
+        def wgrad(a, gz, w, want_w, want_b, act):
+            """(dW, db) of one product over every hop: gz^T a and colsum(gz), gz masked by ``act > 0`` when given."""
+            if not (want_w or want_b):
+                return None, None
+            gw = torch.empty_like(w, memory_format=torch.contiguous_format)
+            gb = torch.empty(w.shape[0], dtype=torch.float32, device=dev) if want_b else None
+            first = True
+            for h, rows, _ in _hops(graph):
+                if h.n_rows > 0:
+                    gcn_wgrad(a[rows], gz[rows], gw, gb, None if act is None else act[rows], accumulate=not first)
+                    first = False
+            if first:
+                gw.zero_()
+                if gb is not None:
+                    gb.zero_()
+            return (gw if want_w else None), gb
+
+        if w2 is not None:
+            if relu_out:
+                g = torch.ops.aten.threshold_backward(g, out, 0)
+            gw2, gb2 = wgrad(hidden, g, w2, need_w2, need_b2, None)
+            g1, act1 = g @ w2.detach(), hidden if relu_hidden else None          # dHidden: one library GEMM
+        else:
+            g1, act1 = g, out if relu_hidden else None
+        lower = need_x or need_xd or need_eps
+        if act1 is not None and lower:
+            g1, act1 = torch.ops.aten.threshold_backward(g1, act1, 0), None      # dZ1 once, read by every gradient below
+        gw1, gb1 = wgrad(agg, g1, w1, need_w1, need_b1, act1)
+        gx = gxd = geps = None
+        has_self = not ctx.no_root and x_dst is None
+        if need_x:
+            Hq = (H + 3) // 4 * 4
+            w_bwd = torch.zeros((F_, Hq), dtype=torch.float32, device=dev)
+            w_bwd[:, :H] = w1.detach().t()
+            if Hq != H:
+                gq = torch.zeros((g1.shape[0], Hq), dtype=torch.float32, device=dev)
+                gq[:, :H] = g1
+            else:
+                gq = g1
+            gx = _gin_input_grad(graph, gq, ctx.n_src, eps.detach(), has_self, weight=w_bwd)
+        if (need_xd or need_eps) and not ctx.no_root:
+            d_agg = g1 @ w1.detach() if some else torch.zeros((0, F_), dtype=torch.float32, device=dev)
+            if need_xd:
+                gxd = torch.zeros_like(x_dst, dtype=torch.float32)
+                gxd[:d_agg.shape[0]] = (1.0 + eps.detach()) * d_agg
+            if need_eps:
+                geps = (d_agg * _gin_self_rows(src, ctx.ids, x_dst, graph)).sum().reshape(eps.shape)
+        elif need_eps:
+            geps = torch.zeros_like(eps)
+        ctx.kept = None
+        return gx, gxd, geps, gw1, gb1, gw2, gb2, None, None, None, None, None, None
+
+
+class _GinAggregate(torch.autograd.Function):
+    """The GIN aggregate over every hop of a ``LayerGraph`` (``wgamd_gin_aggregate_f32``), rows back to back; backward = the same
+    kernel over the hops' transposes.  The route of shapes and ``nn`` modules the one-kernel layer does not take."""
+
+    @staticmethod
+    def forward(ctx, x, x_dst, eps, graph, no_root):
+        out = torch.empty((graph.n_rows, x.shape[1]), dtype=torch.float32, device=x.device)
+        for h, rows, _ in _hops(graph):
+            if h.n_rows > 0:
+                self_rows, xd = _gin_hop_self(h, rows, x_dst, no_root)
+                gin_aggregate(h.row_ptr, h.col, x, self_rows, eps=eps, x_dst=xd, out=out[rows])
+        ctx.save_for_backward(x, x_dst, eps)
+        ctx.graph, ctx.no_root = graph, no_root
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, x_dst, eps = ctx.saved_tensors
+        need_x, need_xd, need_eps = ctx.needs_input_grad[:3]
+        g = g.contiguous()
+        gx = gxd = geps = None
+        if need_x:
+            gx = _gin_input_grad(ctx.graph, g, x.shape[0], eps, not ctx.no_root and x_dst is None)
+        if need_xd:
+            gxd = torch.zeros_like(x_dst)
+            gxd[:g.shape[0]] = (1.0 + eps) * g
+        if need_eps:
+            geps = torch.zeros_like(eps) if ctx.no_root else (g * _gin_self_rows(x, None, x_dst, ctx.graph)).sum().reshape(eps.shape)
+        return gx, gxd, geps, None, None
+
+
+def _gin_aggregate_torch(x, x_dst, eps, lg: LayerGraph, no_root: bool):
+    """PyG's formulation of the GIN aggregate in torch ops (CPU tensors)."""
+    aggs = []
+    for h, rows, _ in _hops(lg):
+        n, E = h.n_rows, int(h.col.shape[0])
+        agg = torch.zeros((n, x.shape[1]), dtype=x.dtype, device=x.device)
+        if E > 0:
+            agg = agg.index_add_(0, _edge_dst(h.row_ptr, E), x[h.col.long()])
+        if not no_root:
+            agg = agg + (1.0 + eps.to(x.dtype)) * (x_dst[rows] if x_dst is not None else x[h.self_rows])
+        aggs.append(agg)
+    if not aggs:
+        return torch.zeros((0, x.shape[1]), dtype=x.dtype, device=x.device)
+    return aggs[0] if len(aggs) == 1 else torch.cat(aggs)
+
+
+class GINConv(torch.nn.Module):
+    """PyG ``GINConv`` (``flow="source_to_target"``): ``x'_i = nn((1 + eps) x_i + sum_{j -> i} x_j)`` — every edge is summed,
+    loop edges and duplicates too.  ``eps`` is a Parameter with ``train_eps`` and a buffer otherwise, ``nn`` any module
+    (``nn.*`` in the state dict), so a PyG ``state_dict`` loads.
+
+    ``forward(x, graph, act=None)``: ``graph`` = a COO ``edge_index`` (output rows = x's rows; ``x`` may be a pair
+    ``(x_src, x_dst)``, ``x_dst = None`` = no root term), a ``[csr_row_ptr, csr_col_ind]`` pair (destinations = the first rows of
+    x), or a call group's ``LayerGraph`` with ``x`` a tensor or ``LazyRows``.  ``act="relu"`` is the ``.relu()`` that follows the
+    layer in the reference's model.  What runs depends on ``nn`` (``route``):
+
+    * ``"mlp"`` — ``Sequential(Linear(F, H), ReLU(), Linear(H, N))``, the GIN paper's MLP: the whole layer is ONE kernel per hop
+      (``wgamd_gin_layer_f32``: aggregate, both products, biases, ReLUs; the hidden activation never leaves LDS);
+    * ``"linear"`` — a ``Linear``, or a ``Sequential`` that starts with one (a ``ReLU`` right behind it included): one kernel for
+      the aggregate and that product, the remaining modules run as they are (a BatchNorm between the Linears lands here);
+    * ``"aggregate"`` — anything else, and shapes outside the kernel's domain (F % 4 == 0; F, H, N <= 256; H % 4 == 0 for
+      ``"mlp"``): the aggregate kernel, then ``nn``.  CPU tensors run PyG's formulation in torch ops."""
+
+    def __init__(self, nn: torch.nn.Module, eps: float = 0.0, train_eps: bool = False, **kwargs):
+        super().__init__()
+        if kwargs:
+            raise TypeError("GINConv: unsupported keyword argument(s) %s (sum aggregation, flow source_to_target)"
+                            % sorted(kwargs))
+        if not isinstance(nn, torch.nn.Module):
+            raise TypeError("GINConv: nn must be a torch.nn.Module")
+        self.nn, self.initial_eps, self.train_eps = nn, float(eps), bool(train_eps)
+        if train_eps:
+            self.eps = torch.nn.Parameter(torch.empty(1))
+        else:
+            self.register_buffer("eps", torch.empty(1))
+        self.eps.data.fill_(self.initial_eps)
+
+    def reset_parameters(self):
+        for m in self.nn.modules():
+            if hasattr(m, "reset_parameters"):
+                m.reset_parameters()
+        self.eps.data.fill_(self.initial_eps)
+
+    def _plan(self):
+        """``(route, lin1, relu1, lin2, rest)``: the leading modules the kernel runs and the ones that follow it."""
+        mods = list(self.nn) if isinstance(self.nn, torch.nn.Sequential) else [self.nn]
+        if not mods or type(mods[0]) is not torch.nn.Linear:
+            return "aggregate", None, False, None, [self.nn]
+        lin1 = mods[0]
+        relu1 = len(mods) > 1 and type(mods[1]) is torch.nn.ReLU
+        rest = mods[2:] if relu1 else mods[1:]
+        F_, H = lin1.in_features, lin1.out_features
+        if relu1 and len(rest) == 1 and type(rest[0]) is torch.nn.Linear and gin_layer_supported(F_, H, rest[0].out_features):
+            return "mlp", lin1, True, rest[0], []
+        if gin_layer_supported(F_, H, 0):
+            return "linear", lin1, relu1, None, rest
+        return "aggregate", None, False, None, [self.nn]
+
+    @property
+    def route(self) -> str:
+        """``"mlp"``, ``"linear"`` or ``"aggregate"``: what ``nn``'s form and shapes select on the device."""
+        return self._plan()[0]
+
+    def _forward_layer(self, x, lg: LayerGraph, act=None, x_dst=None, no_root=False):
+        assert act in (None, "relu"), "act: None or 'relu'"
+        relu = act == "relu"
+        lazy = isinstance(x, LazyRows)
+        F_ = x.shape[1]
+        if x_dst is not None and x_dst.shape[1] != F_:
+            raise ValueError("GINConv: x_dst has %d features, x_src %d" % (x_dst.shape[1], F_))
+        src, ids, n_src, _ = _layer_input(self, x, lg, F_)
+        if not src.is_cuda:                                     # CPU tensors: PyG's formulation
+            out = self.nn(_gin_aggregate_torch(x.materialize() if lazy else x, x_dst, self.eps, lg, no_root))
+            return torch.relu(out) if relu else out
+        eps = self.eps if self.eps.dtype == torch.float32 else self.eps.float()
+        route, lin1, relu1, lin2, rest = self._plan()
+        if route != "aggregate":
+            ws = [t for t in (lin1.weight, lin1.bias, lin2 and lin2.weight, lin2 and lin2.bias) if t is not None]
+            ok = all(t.dtype == torch.float32 and t.is_cuda for t in ws) and _kernel_rows_ok(lin1.weight) and (
+                lin2 is None or _kernel_rows_ok(lin2.weight)) and all(t.is_contiguous() for t in ws if t.dim() == 1)
+            if ok and lazy and not _kernel_rows_ok(src):
+                x, lazy = x.materialize(), False
+                src, ids = x, None
+            if ok and not lazy and not _kernel_rows_ok(src):
+                src = x = x.float().contiguous()
+            if ok and x_dst is not None and not _kernel_rows_ok(x_dst):
+                x_dst = x_dst.float().contiguous()
+            if not ok or lin1.in_features != F_:
+                route = "aggregate"
+                rest = [self.nn]
+        if route == "aggregate":
+            xd = (x.materialize() if lazy else x).float().contiguous()
+            out = _GinAggregate.apply(xd, None if x_dst is None else x_dst.float().contiguous(), eps, lg, no_root)
+            out = self.nn(out)
+            return torch.relu(out) if relu else out
+        fuse_act = relu and not rest                            # the layer's ReLU rides in the kernel when nothing follows it
+        if lin2 is None:
+            out = _GinLayer.apply(src, x_dst, eps, lin1.weight, lin1.bias, None, None, lg, ids, relu1 or fuse_act, False, n_src,
+                                  no_root)
+        else:
+            out = _GinLayer.apply(src, x_dst, eps, lin1.weight, lin1.bias, lin2.weight, lin2.bias, lg, ids, True, fuse_act, n_src,
+                                  no_root)
+        for m in rest:
+            out = m(out)
+        return torch.relu(out) if relu and not fuse_act else out
+
+    def forward(self, x, graph, act=None):
+        _refuse_capture(self, "per-graph caches")              # (the hops' transposes, cached against the graph object)
+        x_dst, pair = None, False
+        if isinstance(x, (tuple, list)):
+            (x, x_dst), pair = x, True
+        _refuse_featureless(self, x)
+        if x_dst is not None:
+            _refuse_featureless(self, x_dst)
+        if isinstance(graph, HeteroLayerGraph):
+            raise NotImplementedError("GINConv over a heterogeneous call group's layer graph is not supported")
+        if isinstance(graph, LayerGraph):
+            if pair:
+                raise NotImplementedError("GINConv: an (x_src, x_dst) pair over a LayerGraph is not supported")
+            return self._forward_layer(x, graph, act)
+        if isinstance(x, LazyRows):
+            x = x.materialize()
+        if isinstance(x_dst, LazyRows):
+            x_dst = x_dst.materialize()
+        if isinstance(graph, (tuple, list)):
+            n_dst = int(graph[0].shape[0]) - 1
+        elif not pair:
+            n_dst = x.shape[0]
+        elif x_dst is not None:
+            n_dst = x_dst.shape[0]
+        else:                                                   # (x_src, None): as many rows as the edges reach (one read-back)
+            n_dst = int(graph[1].max()) + 1 if graph.shape[1] > 0 else 0
+        have = x.shape[0] if not pair else (x_dst.shape[0] if x_dst is not None else n_dst)
+        if have < n_dst:
+            raise ValueError("GINConv: %d destination rows for %d destinations" % (have, n_dst))
+        lg = _single_hop(graph, n_dst)[0]
+        return self._forward_layer(x, lg, act, x_dst=None if x_dst is None else x_dst[:n_dst], no_root=pair and x_dst is None)
+
+
+class _SegmentSum(torch.autograd.Function):
+    """``out[g] = sum of rows [offsets[g], offsets[g + 1])`` of x (``wgamd_segment_sum_f32``: rows added in order, no atomics)."""
+
+    @staticmethod
+    def forward(ctx, x, offsets, batch):
+        n_seg, F_ = offsets.shape[0] - 1, x.shape[1]
+        out = torch.empty((n_seg, F_), dtype=torch.float32, device=x.device)
+        if F_ > 0:
+            L.check(L.lib().wgamd_segment_sum_f32(x.data_ptr(), x.stride(0), F_, offsets.data_ptr(), n_seg, out.data_ptr(),
+                                                  out.stride(0), get_stream()), "wgamd_segment_sum_f32")
+        ctx.save_for_backward(batch)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (batch,) = ctx.saved_tensors
+        return g[batch], None, None
+
+
+def global_add_pool(x: torch.Tensor, batch: Optional[torch.Tensor], size: Optional[int] = None, ptr: Optional[torch.Tensor] = None):
+    """PyG ``global_add_pool``: ``out[g] = sum of the rows of x with batch == g``, [size, F] (``size`` None: ``batch.max() + 1``,
+    one read-back; ``batch`` None: one graph).  A sorted ``batch`` on the device runs ``wgamd_segment_sum_f32`` over its segment
+    offsets — rows added in order, the same bits from run to run, empty graphs give zero rows.  ``ptr`` (PyG's ``Batch.ptr``)
+    vouches that ``batch`` is sorted and gives ``size``; without it one ``(batch[1:] >= batch[:-1]).all()`` check is made.  An
+    unsorted or CPU ``batch`` goes through ``index_add_``.  Gradient: ``grad[batch]``."""
+    if batch is None:
+        return x.sum(0, keepdim=True)
+    assert x.dim() == 2 and batch.dim() == 1 and batch.shape[0] == x.shape[0]
+    if size is None:
+        size = int(ptr.shape[0]) - 1 if ptr is not None else (int(batch.max()) + 1 if batch.numel() > 0 else 0)
+    size = int(size)
+    batch = batch.long()
+    on_device = x.is_cuda and batch.is_cuda and x.dtype == torch.float32
+    if on_device and (ptr is not None or batch.numel() < 2 or bool((batch[1:] >= batch[:-1]).all())):
+        if x.stride(1) != 1:
+            x = x.contiguous()
+        offsets = torch.searchsorted(batch.contiguous(), torch.arange(size + 1, device=batch.device))
+        return _SegmentSum.apply(x, offsets.contiguous(), batch)
+    return torch.zeros((size, x.shape[1]), dtype=x.dtype, device=x.device).index_add_(0, batch, x)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # heterogeneous layers over a call group (BASELINE configs[4]: ogbn-mag-like 2-hop walk + HeteroConv{GATConv})
 # ---------------------------------------------------------------------------------------------------------------------
 _stage_hook = None

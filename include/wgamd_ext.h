@@ -898,6 +898,43 @@ wholememory_error_code_t wgamd_hetero_sage_layer_f32_train(const wgamd_hetero_sa
                                                            int64_t ld_acc, const int64_t* out_rows, float* out, int64_t ldo,
                                                            float* c_out, int64_t ldc, void* stream);
 
+/* ---- GIN layer (csrc/wg_gin.hip): torch_geometric.nn.GINConv with the GIN paper's MLP over a sampled hop ----------------------
+ * The model of the reference's cugraph-pyg example dist_gin_sg.py (GINConv(MLP([in, hidden, hidden])), then global_add_pool):
+ *   agg[i]    = sum_{e = (j -> i)} X[j]  +  (1 + eps) XS[i]          (every edge is summed: loop edges and duplicates too)
+ *   hidden[i] = act1(agg[i] @ W1^T + b1)                              act1 = ReLU with WGAMD_GIN_RELU_HIDDEN
+ *   out[i]    = act2(hidden[i] @ W2^T + b2)                           act2 = ReLU with WGAMD_GIN_RELU_OUT
+ * X[r] = x[src_ids ? src_ids[r] : r] (INT, INT64 or WGAMD_IDS_BYTE_OFFSETS).  XS[i] = x_dst[i] when x_dst is given (the
+ * bipartite form), else X[self_rows[i]]; self_rows[i] < 0, or both arrays null: row i has no self term.  eps: ONE float on the
+ * device, nullable = 0.  W1 [H, ldw1] and W2 [N, ldw2] are row-major (torch.nn.Linear.weight); b1, b2 nullable.  With w2 null
+ * and N = 0 the layer ends after the first product: out = hidden [n_rows, H].  Sums run in CSR order: run-to-run deterministic.
+ * Layer kernel: wgamd_gin_layer_supported(F, H, N) (F % 4 == 0; F, H, N <= 256; H % 4 == 0 unless N == 0), x / x_dst / w1 / w2
+ * rows 16-B aligned; both products run on the exact fp32 matrix pipe (v_mfma_f32_16x16x4_f32), the hidden activation stays in
+ * LDS.  _train also writes agg [n_rows, F] and, with a second product, hidden [n_rows, H] (16-B aligned rows; the same bits as
+ * the operands of the products) for the weight gradients (wgamd_gcn_wgrad_f32).  wgamd_gin_aggregate_f32: agg alone, any F.
+ * wgamd_segment_sum_f32 (global_add_pool over a sorted batch vector): out[g] = sum of rows [offsets[g], offsets[g + 1]) of x,
+ * offsets int64 [n_segments + 1] non-decreasing; rows are added in order, no atomics; an empty segment gives a zero row. */
+#define WGAMD_GIN_RELU_HIDDEN 1
+#define WGAMD_GIN_RELU_OUT 2
+int wgamd_gin_layer_supported(int F, int H, int N);
+wholememory_error_code_t wgamd_gin_layer_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx, int F,
+                                             const void* src_ids, wholememory_dtype_t src_ids_dtype, const int64_t* self_rows,
+                                             const float* x_dst, int64_t ldx_dst, const float* eps, const float* w1, int64_t ldw1,
+                                             int H, const float* b1, const float* w2, int64_t ldw2, int N, const float* b2,
+                                             int flags, float* out, int64_t ldo, void* stream);
+wholememory_error_code_t wgamd_gin_layer_f32_train(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx,
+                                                   int F, const void* src_ids, wholememory_dtype_t src_ids_dtype,
+                                                   const int64_t* self_rows, const float* x_dst, int64_t ldx_dst, const float* eps,
+                                                   const float* w1, int64_t ldw1, int H, const float* b1, const float* w2,
+                                                   int64_t ldw2, int N, const float* b2, int flags, float* out, int64_t ldo,
+                                                   float* agg_out, int64_t ld_agg, float* hidden_out, int64_t ld_hidden,
+                                                   void* stream);
+wholememory_error_code_t wgamd_gin_aggregate_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx,
+                                                 int F, const void* src_ids, wholememory_dtype_t src_ids_dtype,
+                                                 const int64_t* self_rows, const float* x_dst, int64_t ldx_dst, const float* eps,
+                                                 float* out, int64_t ldo, void* stream);
+wholememory_error_code_t wgamd_segment_sum_f32(const float* x, int64_t ldx, int F, const int64_t* offsets, int64_t n_segments,
+                                               float* out, int64_t ldo, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
