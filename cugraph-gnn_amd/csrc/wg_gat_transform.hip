@@ -226,8 +226,7 @@ void launch_gt(const gt_args& a, hipStream_t st)
 {
   const int cus         = stream_cu_count(st);
   const int64_t n_tiles = (a.n_rows + 31) / 32;
-  static const bool no_stat = [] { const char* e = getenv("WGAMD_GT_STAT"); return e && e[0] == '0'; }();   // (tuning)
-  const bool stat       = !no_stat && KS <= 8 && (a.H == 1 || a.H == 2 || a.H == 4);
+  const bool stat       = KS <= 8 && (a.H == 1 || a.H == 2 || a.H == 4);
   const int64_t blocks  = stat ? (n_tiles + (4 / a.H) - 1) / (4 / a.H) : (n_tiles * a.H + 3) / 4;
   const int grid        = (int)std::max<int64_t>(1, std::min<int64_t>(blocks, 2 * (int64_t)cus));
   if constexpr (KS <= 8) {

@@ -18,8 +18,6 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 
-#include <cstdlib>
-
 #include "wg_common.hpp"
 
 namespace wgamd {
@@ -239,7 +237,7 @@ inline int grid_for(int64_t n_rows, int log2_lanes, int rows_per_group)
   // workgroups) on purpose: with 8 — a fully persistent grid — the kernel itself runs just as fast, but its workgroups hold
   // every wave slot until the launch ends and a kernel of another stream (the sampling walk of the next call group) cannot
   // get a foot in; with short-lived workgroups the two interleave: +3 % end to end (3.40 -> 3.52 G edges/s, A/B x 3)
-  static const int per_cu = getenv("WGAMD_GATHER_WG_PER_CU") ? atoi(getenv("WGAMD_GATHER_WG_PER_CU")) : 128;
+  constexpr int per_cu = 128;
   if (blocks > 256 * per_cu) blocks = 256 * per_cu;
   if (blocks < 1) blocks = 1;
   return (int)blocks;

@@ -15,8 +15,6 @@
 // with col = the row r and the k-order of step (m, i) chosen as k = 16 m + 4 q + i, that is exactly float i of the lane's
 // chunk m — no shuffle, no LDS.  The A operand (V^T in the same k-order) sits in registers for the whole launch.  The
 // accumulator tile D[t = 4 (lane / 16) + v][r = lane % 16] leaves as one 16-byte store per lane: out_terms[r, 4 q' .. 4 q' + 3].
-#include <cstdlib>
-
 #include "wg_common.hpp"
 #include "wgamd_ext.h"
 
@@ -25,87 +23,13 @@ namespace {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-// KM = F / 16 chunks per lane, TT = 16-term tiles (T <= 16 TT)
-template <typename IdT, int KM, int TT>
-__global__ void __launch_bounds__(256)
-gather_terms_kernel(const float* __restrict__ table, int64_t ldt, const IdT* __restrict__ ids, int64_t n, const float* __restrict__ v,
-                    int T, float* __restrict__ out_x, int64_t ldx, float* __restrict__ out_terms, int64_t ldo, int group)
-{
-  const int lane = threadIdx.x & 63;
-  const int r = lane & 15, q = lane >> 4;
-  // A operand: a[tt][m][i] = V[16 m + 4 q + i][16 tt + r]  (zero past T)
-  float a[TT][KM][4];
-#pragma unroll
-  for (int tt = 0; tt < TT; tt++) {
-    const int t = tt * 16 + r;
-#pragma unroll
-    for (int m = 0; m < KM; m++)
-#pragma unroll
-      for (int i = 0; i < 4; i++) a[tt][m][i] = t < T ? v[(int64_t)(16 * m + 4 * q + i) * T + t] : 0.f;
-  }
-  const int64_t n_tiles  = (n + 15) / 16;
-  const int64_t wave     = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  const int64_t n_waves  = (int64_t)gridDim.x * (blockDim.x >> 6);
-  // the id of the NEXT tile's row is requested before this tile's rows are waited for: one dependent round trip per tile, not two
-  int64_t id_next = (wave < n_tiles && wave * 16 + r < n) ? (int64_t)ids[wave * 16 + r] : -1;
-  for (int64_t tile = wave; tile < n_tiles; tile += n_waves) {
-    const int64_t row  = tile * 16 + r;
-    const bool in      = row < n;
-    const int64_t id   = id_next;
-    {
-      const int64_t nrow = (tile + n_waves) * 16 + r;
-      id_next            = (tile + n_waves < n_tiles && nrow < n) ? (int64_t)ids[nrow] : -1;
-    }
-    const bool live    = id >= 0;                         // a negative id: the row is skipped, its terms are zero
-    const float* src   = table + (live ? id : 0) * ldt + 4 * q;
-    f32x4 x[KM];
-#pragma unroll
-    for (int m = 0; m < KM; m++) x[m] = *reinterpret_cast<const f32x4*>(src + 16 * m);
-    if (live) {
-      float* dst = out_x + row * ldx + 4 * q;
-#pragma unroll
-      for (int m = 0; m < KM; m++) *reinterpret_cast<f32x4*>(dst + 16 * m) = x[m];
-    }
-    f32x4 acc[TT];
-#pragma unroll
-    for (int tt = 0; tt < TT; tt++) acc[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int m = 0; m < KM; m++)
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const float b = live ? x[m][i] : 0.f;
-#pragma unroll
-        for (int tt = 0; tt < TT; tt++) acc[tt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[tt][m][i], b, acc[tt], 0, 0, 0);
-      }
-    // D[t = 16 tt + 4 q + v][row r]: four consecutive terms of one row per lane
-    if (in) {
-#pragma unroll
-      for (int tt = 0; tt < TT; tt++) {
-        const int t0 = tt * 16 + 4 * q;
-        if (group == 4) {   // slabs [T / 4][n][4]: the four terms of one (row, relation end) are one 16-byte store
-          if (t0 < T) *reinterpret_cast<f32x4*>(out_terms + ((int64_t)(t0 >> 2) * n + row) * 4) = acc[tt];
-          continue;
-        }
-        float* o = out_terms + row * ldo + t0;
-        if (t0 + 4 <= T && (ldo & 3) == 0) {
-          *reinterpret_cast<f32x4*>(o) = acc[tt];
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; i++)
-            if (t0 + i < T) o[i] = acc[tt][i];
-        }
-      }
-    }
-  }
-}
-
-// The same tile step, software-pipelined: the A operand (V^T) lives in LDS (one ds_read_b128 per (term tile, chunk) — 64
-// registers back for F = 128, T > 16), which pays for a SECOND set of row registers: the loads of tile t + 1 are in flight
-// while tile t is stored and multiplied (112-115 registers, four waves per SIMD with two tiles each).  Same MFMA order,
-// bit-identical results; the default (WGAMD_GATHER_TERMS_PIPELINED=0 selects the kernel above).  Same box, ogbn-mag call
-// group (tools/bench_gather_terms.py): paper rows (10.0 M, T = 24) 2.35 -> 2.12 ms, author (3.85 M, T = 12) 0.85 -> 0.79,
-// field_of_study (2.25 M, T = 8) 0.46 -> 0.43.  Measured without effect on top: non-temporal stores of the rows, 4 / 6 / 16
-// workgroups per CU instead of 8.
+// KM = F / 16 chunks per lane, TT = 16-term tiles (T <= 16 TT).  The tile step is software-pipelined: the A operand (V^T)
+// lives in LDS (one ds_read_b128 per (term tile, chunk) — 64 registers back for F = 128, T > 16), which pays for a SECOND set
+// of row registers: the loads of tile t + 1 are in flight while tile t is stored and multiplied (112-115 registers, four
+// waves per SIMD with two tiles each).  Against a kernel without the pipeline (A operand in registers, one tile in flight;
+// same MFMA order, bit-identical, removed), ogbn-mag call group (tools/bench_gather_terms.py): paper rows (10.0 M, T = 24)
+// 2.35 -> 2.12 ms, author (3.85 M, T = 12) 0.85 -> 0.79, field_of_study (2.25 M, T = 8) 0.46 -> 0.43.  Measured without
+// effect on top: non-temporal stores of the rows, 4 / 6 / 16 workgroups per CU instead of 8.
 template <typename IdT, int KM, int TT>
 __global__ void __launch_bounds__(256)
 gather_terms_pipelined_kernel(const float* __restrict__ table, int64_t ldt, const IdT* __restrict__ ids, int64_t n,
@@ -210,17 +134,8 @@ template <typename IdT, int KM>
 void launch_tt(int TT, int grid, hipStream_t st, const float* table, int64_t ldt, const IdT* ids, int64_t n, const float* v, int T,
                float* out_x, int64_t ldx, float* out_terms, int64_t ldo, int group)
 {
-  static const bool pipelined = [] {
-    const char* e = getenv("WGAMD_GATHER_TERMS_PIPELINED");
-    return e == nullptr || e[0] != '0';
-  }();
-  if (pipelined || ids == nullptr || out_x == nullptr) {
-    if (TT == 1) gather_terms_pipelined_kernel<IdT, KM, 1><<<grid, 256, 0, st>>>(table, ldt, ids, n, v, T, out_x, ldx, out_terms, ldo, group);
-    else gather_terms_pipelined_kernel<IdT, KM, 2><<<grid, 256, 0, st>>>(table, ldt, ids, n, v, T, out_x, ldx, out_terms, ldo, group);
-    return;
-  }
-  if (TT == 1) gather_terms_kernel<IdT, KM, 1><<<grid, 256, 0, st>>>(table, ldt, ids, n, v, T, out_x, ldx, out_terms, ldo, group);
-  else gather_terms_kernel<IdT, KM, 2><<<grid, 256, 0, st>>>(table, ldt, ids, n, v, T, out_x, ldx, out_terms, ldo, group);
+  if (TT == 1) gather_terms_pipelined_kernel<IdT, KM, 1><<<grid, 256, 0, st>>>(table, ldt, ids, n, v, T, out_x, ldx, out_terms, ldo, group);
+  else gather_terms_pipelined_kernel<IdT, KM, 2><<<grid, 256, 0, st>>>(table, ldt, ids, n, v, T, out_x, ldx, out_terms, ldo, group);
 }
 
 template <typename IdT>

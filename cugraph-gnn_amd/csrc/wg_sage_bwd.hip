@@ -367,8 +367,7 @@ __host__ inline wgrad_plan plan_for(int F, int N)
   while (WN > 2 && (mtiles + (8 / WN) - 1) / (8 / WN) > 8) WN /= 2;   // at most 8 accumulator tiles per wave
   // (rows per tile: the LDS holds two tiles of three bf16 planes of 2F x (TR + 8); narrow shapes — the dense tails of the GAT layers,
   //  F = 64 — take 64-row tiles: a tile is so few MFMAs that the per-tile staging and barriers were the launch's time, 1.5 TB/s)
-  static const bool wide_tiles = [] { const char* e = getenv("WGAMD_WGRAD_TR64"); return !(e && e[0] == '0'); }();
-  const int WM = 8 / WN, mt = (mtiles + WM - 1) / WM, TR = (F <= 64 && wide_tiles) ? 64 : (F <= 128 ? 32 : 16);
+  const int WM = 8 / WN, mt = (mtiles + WM - 1) / WM, TR = F <= 64 ? 64 : (F <= 128 ? 32 : 16);
   // (accumulator tiles per wave are a template parameter: 4, 8, and 7 for the products layer-1 shape, whose 16 registers
   //  fewer keep that instance clear of spills)
   const int MT = mt <= 4 ? 4 : (mt == 7 && TR == 32 && WN == 8 ? 7 : 8);

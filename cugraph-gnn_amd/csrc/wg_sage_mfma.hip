@@ -569,11 +569,10 @@ constexpr size_t kLdsBudget = 160 * 1024;
 __host__ inline size_t lds_bytes(int F, int TR) { return (size_t)(2 * TR * row_stride_dw(F) + 16 + 4 * kScratchDw + 16) * 4; }
 __host__ inline size_t lds_bytes_half(int F) { return (size_t)(2 * 64 * row_stride_half_dw(F) + 16 + 4 * kScratchDw + 16) * 4; }
 // 64-row tiles in two halves: when two whole 64-row tiles do not fit but the halves of one do, and the halves are whole
-// k-steps (WGAMD_SAGE_HALF_TILES=0 keeps the 32-row tiles)
+// k-steps
 __host__ inline bool use_half_tiles(int F)
 {
-  static const bool off = [] { const char* e = getenv("WGAMD_SAGE_HALF_TILES"); return e && e[0] == '0'; }();
-  return !off && F % 16 == 0 && lds_bytes(F, 64) > kLdsBudget && lds_bytes_half(F) <= kLdsBudget;
+  return F % 16 == 0 && lds_bytes(F, 64) > kLdsBudget && lds_bytes_half(F) <= kLdsBudget;
 }
 
 template <typename IdT, int LG, int CW>
@@ -748,15 +747,7 @@ extern "C" wholememory_error_code_t wgamd_sage_layer_fused_bf16x3_train(const in
       a.row_scale = 1;
       a.x_bytes   = 0;
     }
-    // WGAMD_SAGE_DEBUG=<bits> (tuning only; results are WRONG with 4 / 8): the ablation switches of mfma_args::debug
-    static const int dbg = [] { const char* e = getenv("WGAMD_SAGE_DEBUG"); return e ? atoi(e) : 0; }();
-    a.debug = dbg;
     auto st = static_cast<hipStream_t>(stream);
-    if (agg_out == nullptr && !byte_offsets && !a.full_tiles && sage_ws_supported(F, N)) {
-      if (src_ids != nullptr && src_ids_dtype != WHOLEMEMORY_DT_INT && src_ids_dtype != WHOLEMEMORY_DT_INT64)
-        throw invalid_input("src_ids must be INT or INT64");
-      return sage_ws_launch(a, src_ids == nullptr ? 0 : (src_ids_dtype == WHOLEMEMORY_DT_INT ? 1 : 2), st);
-    }
     if (src_ids == nullptr) launch_groups<void>(a, st);
     else if (src_ids_dtype == WHOLEMEMORY_DT_INT) launch_groups<int32_t>(a, st);
     else if (src_ids_dtype == WHOLEMEMORY_DT_INT64 || byte_offsets) launch_groups<int64_t>(a, st);

@@ -1,5 +1,4 @@
-// Shared device pieces of the one-kernel SAGE layer (wg_sage_mfma.hip: producer / consumer waves; wg_sage_ws.hip: the
-// weight-stationary variant): argument block, the exact 3-way bf16 split, the fetching side (`producer`), fragment loads,
+// Shared device pieces of the one-kernel SAGE layer (wg_sage_mfma.hip: producer / consumer waves): argument block, the exact 3-way bf16 split, the fetching side (`producer`), fragment loads,
 // the six-product MFMA step and the LDS-transposed epilogue.  See wg_sage_mfma.hip for the design notes.
 #pragma once
 #include <algorithm>
@@ -381,8 +380,7 @@ struct producer {
   {
     long_rows_from<kNb + kW2, kLongUnroll>(tile, m, tile_lds);
   }
-  // (kStart = kNb without second_window(): every row past the first window, kUnroll row loads in flight — the
-  //  weight-stationary kernel has no registers for sixteen)
+  // (kStart = kNb without second_window(): every row past the first window, kUnroll row loads in flight)
   template <int kStart, int kUnroll>
   __device__ __forceinline__ void long_rows_from(int64_t tile, const meta_t<IT, off_t>& m, float* tile_lds) const
   {
@@ -610,47 +608,6 @@ __device__ __forceinline__ void store_agg(const mfma_args& a, const float* tile_
         *reinterpret_cast<const f32x4*>(tile_lds + (cw * kRows + r) * a.SD + q * 4);
   }
 }
-
-// The same epilogue in eight pieces — piece (rt, g) = the 8 rows 32 rt + 8 g .. + 7 — for a caller that spreads the stores
-// between other work (wg_sage_ws.hip)
-struct epilogue_lane_t {
-  float bj[2];
-  float* obase;
-  int64_t row0;
-  bool full;
-};
-template <int RT>
-__device__ __forceinline__ void epilogue_begin(const mfma_args& a, epilogue_lane_t& e, int64_t row0, int cw, int lane)
-{
-#pragma unroll
-  for (int ct = 0; ct < 2; ct++) e.bj[ct] = a.bias ? a.bias[cw * 64 + ct * 32 + (lane & 31)] : 0.f;
-  e.row0  = row0;
-  e.full  = row0 + RT * 32 <= a.n_rows;
-  e.obase = a.out + (row0 + (lane >> 4)) * a.ldo + cw * 64 + (lane & 15) * 4;
-}
-template <int RT, int rt, int g>
-__device__ __forceinline__ void epilogue_piece(const mfma_args& a, const epilogue_lane_t& e, f32x16 (&c)[RT][2], int lane,
-                                               float* scratch)
-{
-  const int lm = lane & 31, lh = lane >> 5, rl = lane >> 4, cl = (lane & 15) * 4;
-#pragma unroll
-  for (int ct = 0; ct < 2; ct++)
-#pragma unroll
-    for (int jj = 0; jj < 4; jj++) {
-      const float v = c[rt][ct][4 * g + jj] + e.bj[ct];
-      scratch[(jj + 4 * lh) * 64 + ct * 32 + lm] = a.relu ? fmaxf(v, 0.f) : v;
-    }
-#pragma unroll
-  for (int pass = 0; pass < 2; pass++) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(scratch + (rl + 4 * pass) * 64 + cl);
-    const int r   = rt * 32 + 8 * g + 4 * pass;   // + rl
-    if (e.full || e.row0 + r + rl < a.n_rows) *reinterpret_cast<f32x4*>(e.obase + (int64_t)r * a.ldo) = v;
-  }
-}
-
-// weight-stationary variant (wg_sage_ws.hip); id_kind: 0 = no indirection, 1 = int32 src_ids, 2 = int64 src_ids
-bool sage_ws_supported(int F, int N);
-void sage_ws_launch(const mfma_args& a, int id_kind, hipStream_t st);
 
 }  // namespace sage_mfma
 }  // namespace wgamd

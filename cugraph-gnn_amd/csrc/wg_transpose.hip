@@ -269,15 +269,6 @@ __global__ void __launch_bounds__(kSmallThreads) csr_transpose_small_kernel(cons
   }
 }
 
-bool small_transpose_enabled()
-{
-  static const bool on = [] {
-    const char* v = getenv("WGAMD_TRANSPOSE_SMALL");
-    return !(v && v[0] == '0');
-  }();
-  return on;
-}
-
 unsigned key_bits(int64_t n_src)
 {
   unsigned bits = 1;
@@ -323,7 +314,7 @@ extern "C" wholememory_error_code_t wgamd_csr_transpose_i32(const int* row_ptr, 
       WG_HIP_CHECK(hipMemsetAsync(row_ptr_t, 0, sizeof(int) * (size_t)(n_src + 1), st));
       return;
     }
-    if (n_src >= 1 && n_src + 1 + n_edges + (n_edges + 1) / 2 <= kSmallLdsInts && n_rows < 32768 && small_transpose_enabled()) {
+    if (n_src >= 1 && n_src + 1 + n_edges + (n_edges + 1) / 2 <= kSmallLdsInts && n_rows < 32768) {
       const size_t lds = sizeof(int) * (size_t)(n_src + 1 + n_edges + (n_edges + 1) / 2);
       WG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(csr_transpose_small_kernel),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(int) * kSmallLdsInts)));

@@ -10,7 +10,6 @@ segmented reduce / edge softmax run in hand-written gfx950 kernels, the dense ``
 plain ``torch.nn.functional.linear`` (hipBLASLt, MFMA).
 """
 import math
-import os
 from typing import Optional, Tuple, Union
 
 import torch
@@ -214,7 +213,7 @@ def sage_weight_planes(w_t: torch.Tensor) -> torch.Tensor:
 
 
 SAGE_FULL_TILES = 2          # WGAMD_SAGE_FULL_TILES (include/wgamd_ext.h): or-ed into the relu argument of a small launch
-_SAGE_SMALL_ROWS = int(os.environ.get("WGAMD_SAGE_SMALL_ROWS", 8192))
+_SAGE_SMALL_ROWS = 8192
 
 
 def sage_layer_small_launch(F_: int, n_rows: int) -> bool:
@@ -405,8 +404,6 @@ def spmm_csr_backward(row_ptr, col, grad_out, n_src, mean=True, atomic=False):
         deg = (row_ptr[1:] - row_ptr[:-1]).clamp_(min=1)
         g = g / deg.unsqueeze(1)
     row_ptr_t, col_t = csr_transpose(row_ptr, col, n_src)
-    if not _BWD_SEGMENTS:
-        return spmm_csr_forward(row_ptr_t, col_t, g, mean=False)
     # The transposed hop is power-law (a hub is a neighbour of thousands of sampled rows) while the gather kernel walks a
     # row with one lane group: the launch would last as long as its longest row.  wgamd_spmm_csr_segmented_f32 sums rows
     # in pieces of 64 entries and adds the pieces of a row up in order (deterministic, nothing read back).
@@ -418,10 +415,6 @@ def spmm_csr_backward(row_ptr, col, grad_out, n_src, mean=True, atomic=False):
                                                  out.data_ptr(), out.stride(0), ws.data_ptr(), need, get_stream()),
             "wgamd_spmm_csr_segmented_f32")
     return out
-
-
-_BWD_SEGMENTS = os.environ.get("WGAMD_SPMM_BWD_SEGMENTS", "1") != "0"
-
 
 
 class _SpmmCsr(torch.autograd.Function):
@@ -550,7 +543,7 @@ def gat_aggregate_heads(row_ptr, col, x, a_src, a_dst, heads, dst_rows=None, neg
     return out
 
 
-def gat_transform_heads(agg, w, heads, out=None, overwrite=False, fused=None):
+def gat_transform_heads(agg, w, heads, out=None, overwrite=False, fused=True):
     """``out[i, h*C:(h+1)*C] (+)= agg[i, h, :] @ w[:, h*C:(h+1)*C]`` — the H small GEMMs after ``gat_aggregate_heads``.
     ``out`` given: accumulated into (HeteroConv's sum), or written (``overwrite``).  Shapes
     ``wgamd_gat_transform_heads_bf16x3`` is built for (C = 64, F in {64, 128, 256}) run on it (``gat_transform_heads_fused``:
@@ -558,8 +551,6 @@ def gat_transform_heads(agg, w, heads, out=None, overwrite=False, fused=None):
     (fp32 MFMA through hipBLASLt)."""
     n, F_ = agg.shape[0], agg.shape[1] // heads
     C = w.shape[1] // heads
-    if fused is None:
-        fused = _GAT_TRANSFORM_FUSED
     if fused and n > 0 and agg.is_cuda and agg.stride(1) == 1 and w.stride(1) == 1 and gat_transform_supported(F_, heads, C) \
             and (out is None or out.stride(1) == 1):
         return gat_transform_heads_fused(agg, w, heads, acc_in=None if (out is None or overwrite) else out, out=out)
@@ -572,10 +563,6 @@ def gat_transform_heads(agg, w, heads, out=None, overwrite=False, fused=None):
     acc = out.view(n, heads, C).permute(1, 0, 2)
     torch.baddbmm(acc, a, b, beta=0 if overwrite else 1, out=acc)
     return out
-
-
-_GAT_TRANSFORM_FUSED = os.environ.get("WGAMD_GAT_TRANSFORM", "bf16x3") != "library"
-_GAT_LAYER_FUSED = os.environ.get("WGAMD_GAT_LAYER", "fused") != "split"      # one-kernel relation for hops of fan-out <= 10
 
 
 def gat_transform_supported(F_: int, heads: int, C: int) -> bool:
@@ -836,7 +823,7 @@ def _to_csr(edge_index, n_dst):
 _ARANGE = {}
 
 
-_HEADS_WGRAD_MIN_ROWS = int(os.environ.get("WGAMD_HEADS_WGRAD_MIN_ROWS", 16384))
+_HEADS_WGRAD_MIN_ROWS = 16384
 
 
 class _HeadsTransform(torch.autograd.Function):
@@ -858,7 +845,7 @@ class _HeadsTransform(torch.autograd.Function):
         C = w3.shape[2]
         if acc3 is not None:
             ctx.mark_dirty(acc3)
-        if _GAT_TRANSFORM_FUSED and gat_transform_supported(F_, H, C) and agg3.is_contiguous() and (acc3 is None or acc3.is_contiguous()):
+        if gat_transform_supported(F_, H, C) and agg3.is_contiguous() and (acc3 is None or acc3.is_contiguous()):
             # the inference route's kernel: all heads in ONE pass on the bf16 matrix pipe at fp32 accuracy, the running sum read and
             # written in place (the library's four [n, 128] x [128, 64] products run at 0.9 TB/s: 1.45 ms per mag relation)
             y = acc3 if acc3 is not None else torch.empty((n, H, C), dtype=torch.float32, device=agg3.device)
@@ -1149,7 +1136,7 @@ def _refuse_featureless(layer, x):
                          % type(layer).__name__)
 
 
-_SAGE_DX_SMALL_ROWS = int(os.environ.get("WGAMD_SAGE_DX_SMALL_ROWS", 16384))
+_SAGE_DX_SMALL_ROWS = 16384
 
 
 def _sage_dx(hop: HopGraph, gz: torch.Tensor, w_l: torch.Tensor, w_r: torch.Tensor, w_bwd, mean: bool, n_src: int):
@@ -1176,7 +1163,7 @@ def _sage_dx(hop: HopGraph, gz: torch.Tensor, w_l: torch.Tensor, w_r: torch.Tens
             xs[:n, :N] = gz
         xs[n:2 * n, :N] = gz
         return sage_layer_fused_forward(row_ptr_t, col_t, xs, self_t, w_bwd, None, relu=False, mean=False)
-    if n <= _SAGE_DX_SMALL_ROWS and n > 0 and hop.col.shape[0] > 0 and _BWD_SEGMENTS:
+    if n <= _SAGE_DX_SMALL_ROWS and n > 0 and hop.col.shape[0] > 0:
         # the hop's own (kept) transpose + the segmented SpMM; self_rows is injective, so the W_r term is a plain indexed add
         row_ptr_t, col_t, _ = hop.transposed(n_src, need_self=False)
         g = gz
@@ -3339,13 +3326,13 @@ class HeteroConv(torch.nn.Module):
         # the one-kernel relation keeps 10 neighbours of a row in registers and continues longer rows one neighbour at a time:
         # hops with a larger fan-out take the two-kernel path (the fan-out-25 hop of the mag workload through the one-kernel
         # relation: 0.77 ms instead of 0.39 + 0.16 per call group)
-        self.fused_max_fanout = int(os.environ.get("WGAMD_GAT_FUSED_MAX_FANOUT", "10"))
+        self.fused_max_fanout = 10
         # a LazyRows input (table + node list) stays lazy: its attention terms come from one read-only pass over the listed rows
         # and every relation kernel reads the table through the list — the [n, F] copy of the rows is never written
-        self.fetch_in_layer = os.environ.get("WGAMD_GAT_FETCH_IN_LAYER", "1") != "0"
-        # under autograd a call-group layer is aggregate-first too (``_forward_layer_train``); 0: PyG's own relation-by-relation,
+        self.fetch_in_layer = True
+        # under autograd a call-group layer is aggregate-first too (``_forward_layer_train``); False: PyG's own relation-by-relation,
         # transform-first formulation on ``GATConv`` (``_forward_relations``: the lin GEMM over every source row)
-        self.train_aggregate_first = os.environ.get("WGAMD_GAT_TRAIN_AGGREGATE_FIRST", "1") != "0"
+        self.train_aggregate_first = True
 
     def conv(self, edge_type):
         return self.convs["__".join(edge_type)]
@@ -3475,7 +3462,7 @@ class HeteroConv(torch.nn.Module):
             acc = torch.empty((n_f, HC), dtype=torch.float32, device=dev)
             c0 = self.conv(mine[0].edge_type)
             H, C = c0.heads, c0.out_channels
-            one_pass = bool(live) and _GAT_TRANSFORM_FUSED and all(
+            one_pass = bool(live) and all(
                 gat_transform_supported(x[r.edge_type[0]].shape[1], H, C) for r in live)
             target = out[dt] if place is not None else None
             if one_pass and place is None:
@@ -3498,7 +3485,7 @@ class HeteroConv(torch.nn.Module):
                 tail = dict(acc_in=acc if j > 0 else None, bias=bias if (last and one_pass) else None, relu=last and one_pass and relu,
                             out_rows=place if (last and one_pass) else None, out=target if (last and one_pass) else acc)
                 name = "%s hop %d (%d rows, %d edges)" % (et[1], hop + 1, n_f, r.n_edges)
-                if one_pass and _GAT_LAYER_FUSED and r.fanout <= self.fused_max_fanout and gat_layer_fused_supported(xsrc.shape[1], H, C):
+                if one_pass and r.fanout <= self.fused_max_fanout and gat_layer_fused_supported(xsrc.shape[1], H, C):
                     # deep hop (fan-out <= 10): aggregation + dense tail as ONE kernel, the aggregate stays in LDS
                     _stage("gat%s+transform:" % self.stage_tag + name, lambda: gat_layer_fused(r.row_ptr, r.col, xsrc, a_src[et], a_dst[et], w, H,
                                                                             dst_rows=r.dst_rows, **through, **tail))

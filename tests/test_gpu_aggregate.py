@@ -446,6 +446,54 @@ def test_sage_layer_fused_long_rows(hiplib, F, N, mean):
     assert torch.all((got.double() - ref).abs() <= 1e-5 * scale + 1e-6)
 
 
+def test_sage_layer_fused_products_layer1_shape(hiplib):
+    """F = 100, N = 256 over 40,007 rows (a ragged last tile, many workgroups), degree-37 rows past the register window and
+    empty rows, on the default bf16x3 kernel: mean + bias + ReLU over resident rows, a bare sum, and the feature fetch folded
+    in through int64 and int32 node lists — each against the float64 formula, 1e-5 x scale."""
+    import torch
+    from wholegraph_amd import nn
+    dev = "cuda"
+    g = torch.Generator(device=dev).manual_seed(11)
+    F, N, n_dst, n_src, V = 100, 256, 40_007, 90_000, 150_000
+    deg = torch.randint(0, 11, (n_dst,), generator=g, device=dev)
+    deg[::97] = 37
+    deg[3::101] = 0
+    rp = torch.zeros(n_dst + 1, dtype=torch.int32, device=dev)
+    rp[1:] = torch.cumsum(deg, 0)
+    col = torch.randint(0, n_src, (int(rp[-1]),), generator=g, device=dev, dtype=torch.int32)
+    x = torch.rand((n_src, F), generator=g, device=dev) - 0.5
+    table = torch.rand((V, F), generator=g, device=dev) - 0.5
+    n_id = torch.randint(0, V, (n_src,), generator=g, device=dev)
+    rows = torch.randint(0, n_src, (n_dst,), generator=g, device=dev)
+    w_t = torch.rand((2 * F, N), generator=g, device=dev) - 0.5
+    bias = torch.rand(N, generator=g, device=dev)
+    edge_dst = torch.repeat_interleave(torch.arange(n_dst, device=dev), deg)
+    inv_deg = 1.0 / deg.clamp(min=1).double().unsqueeze(1)
+
+    def cat64(rows_x, mean):      # float64 [aggregate | self rows] of the layer's input rows
+        x64 = rows_x.double()
+        agg = torch.zeros((n_dst, F), dtype=torch.float64, device=dev).index_add_(0, edge_dst, x64[col.long()])
+        return torch.cat([agg * inv_deg if mean else agg, x64[rows]], 1)
+
+    cat_x, cat_sum, cat_table = cat64(x, True), cat64(x, False), cat64(table[n_id], True)
+    cases = {
+        "plain": (nn.sage_layer_fused_forward(rp, col, x, rows, w_t, bias, relu=True), cat_x, True),
+        "sum": (nn.sage_layer_fused_forward(rp, col, x, rows, w_t, None, relu=False, mean=False), cat_sum, False),
+        "fetch64": (nn.sage_layer_fused_forward(rp, col, table, rows, w_t, bias, relu=True, src_ids=n_id), cat_table, True),
+        "fetch32": (nn.sage_layer_fused_forward(rp, col, table, rows, w_t, bias, relu=True, src_ids=n_id.to(torch.int32)), cat_table, True),
+    }
+    for form, (got, cat, bias_relu) in cases.items():
+        ref = cat @ w_t.double()
+        scale = cat.abs() @ w_t.double().abs()
+        if bias_relu:
+            ref = torch.relu(ref + bias.double())
+            scale = scale + bias.double().abs()
+        assert got.shape == ref.shape and bool(torch.isfinite(got).all()), form
+        err = (got.double() - ref).abs()
+        print(form, "max err %.3e, max err / bound %.3f" % (float(err.max()), float((err / (1e-5 * scale + 1e-6)).max())))
+        assert torch.all(err <= 1e-5 * scale + 1e-6), (form, float(err.max()))
+
+
 def test_bf16x3_split_is_exact_and_product_is_fp32_class(hiplib):
     """The weight planes of wgamd_sage_split_weight_bf16x3 sum back to the fp32 weight EXACTLY (hi + mid + lo == w, each
     piece a bf16), zero rows pad K to the 16-wide k-step; and the layer on adversarial magnitudes (1e-30 .. 1e30 mixed

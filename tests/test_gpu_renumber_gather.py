@@ -138,20 +138,6 @@ def test_multilayer_walk_sync_and_nosync(oracle_mod, hiplib, col_dtype, fanouts)
         assert rp[i].shape[0] == tg[i + 1].shape[0] + 1 and int(ci[i].max()) < tg[i].shape[0]
 
 
-def test_walk_is_identical_with_the_single_launch_scan(hiplib):
-    """WGAMD_SCAN_CHAINED=1 swaps every multi-tile exclusive scan for the single-pass (decoupled look-back) kernel of
-    wg_scan_chain.hpp — slower on gfx950 (wg_scan.hip header) and therefore off by default, but it must stay correct: the
-    walk / call-group / sampling parity tests pass under it unchanged."""
-    import os
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "tests/test_gpu_callgroup.py",
-                        "tests/test_gpu_renumber_gather.py", "-k", "not single_launch_scan"],
-                       cwd=root, env=dict(os.environ, WGAMD_SCAN_CHAINED="1"), capture_output=True, text=True, timeout=900)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-2000:]
-
-
 @pytest.mark.parametrize("n,bound,dtype", [(0, 10, np.int64), (1, 1, np.int64), (5000, 300, np.int32), (300, 5000, np.int64),
                                            (200000, 70001, np.int64), (4097, 4096, np.int32)])
 def test_unique_bounded_matches_numpy(oracle_mod, hiplib, n, bound, dtype):

@@ -1,7 +1,6 @@
-"""A/B of the two gather+terms kernels (csrc/wg_gather_terms.hip) at the ogbn-mag call-group shapes:
-   WGAMD_GATHER_TERMS_PIPELINED=0|1 python tools/bench_gather_terms.py
-Prints ms per launch, the plain row gather of the same rows next to it, and a checksum of the outputs (the two kernels issue
-the same MFMAs in the same order: the checksums must be equal)."""
+"""Times the gather+terms kernel (csrc/wg_gather_terms.hip) at the ogbn-mag call-group shapes:
+   python tools/bench_gather_terms.py
+Prints ms per launch, the plain row gather of the same rows next to it, and a checksum of the terms (equal from run to run)."""
 import hashlib
 import os
 import sys
@@ -28,7 +27,6 @@ def timed(fn, iters=20):
     return s.elapsed_time(e) / iters
 
 
-print("pipelined =", os.environ.get("WGAMD_GATHER_TERMS_PIPELINED", "1 (default)"))
 for name, rows, n, T in (("paper", 736_389, 10_040_933, 24), ("author", 1_134_649, 3_854_993, 12),
                          ("field_of_study", 59_965, 2_254_250, 8)):
     table = torch.randn((rows, 128), generator=g, device=dev)
