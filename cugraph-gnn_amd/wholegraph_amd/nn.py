@@ -1,13 +1,22 @@
-"""GraphSAGE / GAT mini-batch aggregation on the sampler's per-hop CSR (HIP kernels of
-``include/wgamd_ext.h``), packaged as the conv layers the reference's models instantiate.
+"""The conv layers of a mini-batch GNN on the sampler's per-hop CSR (HIP kernels of ``include/wgamd_ext.h``), with PyG's class
+names, parameter names and maths, so they drop into the reference's models (pylibwholegraph/torch/gnn_model.py:25-59,119-125,
+178-199 builds ``SAGEConv`` / ``GATConv`` and feeds them ``(x, x_target)`` plus the hop's ``[csr_row_ptr, csr_col_ind]`` or COO)
+and into its cugraph-pyg examples.  Six layers run ONE kernel per hop of a call group's ``LayerGraph``, forward and backward
+(each an autograd Function over the hops): ``SAGEConv``, ``GCNConv``, ``RGCNConv``, ``TransformerConv``, ``GINConv``, and
+``HeteroConv`` over SAGEConv relations (one kernel per hop and destination type).  ``GATConv`` and ``HeteroConv`` over GATConv
+relations are aggregate kernels with a dense tail.
 
-The reference has no aggregation kernel: ``HomoGNNModel`` builds ``torch_geometric.nn.SAGEConv`` /
-``GATConv`` and feeds them ``(x, x_target)`` plus the hop's ``[csr_row_ptr, csr_col_ind]`` or COO
-(/root/reference/python/pylibwholegraph/pylibwholegraph/torch/gnn_model.py:25-59,119-125,178-199).
-``SAGEConv`` / ``GATConv`` below keep PyG's parameter names (``lin_l``, ``lin_r``, ``lin``,
-``att_src``, ``att_dst``, ``bias``) and maths so they are a drop-in for that call shape; the
-segmented reduce / edge softmax run in hand-written gfx950 kernels, the dense ``lin_*`` tail is a
-plain ``torch.nn.functional.linear`` (hipBLASLt, MFMA).
+Order of the file: ctypes helpers and the plumbing the one-kernel layers share; the SAGE-era kernel wrappers, derived-weight
+caches and GAT kernel wrappers; graph forms (``_single_hop``, ``LazyRows``, ``HopGraph``, ``LayerGraph``) and the helpers that
+walk a layer graph; then a section per layer — SAGE and GAT, GCN, RGCN, transformer, GIN, heterogeneous — each with its kernel
+wrappers, its autograd Function(s) and its module.
+
+Shared by the one-kernel layers, so that they cannot drift apart: ``_hop_args`` (the eight leading arguments of a launch over a
+hop, with their checks), ``_out_rows`` (a launch's output: the caller's or a fresh one), ``_hops`` / ``_sum_over_hops`` (a layer
+graph's hops with their row and edge slices; the sum of the hops' input gradients), ``_layer_input`` / ``_kernel_rows_ok`` (a
+tensor or ``LazyRows`` input as the kernels read it), ``_padded_wt`` / ``_pad_cols`` (the operands of an input gradient run as
+the layer kernel over ``HopGraph.transposed``), ``_dense_wgrad`` (``gcn_wgrad`` per hop: dW, db of a dense product), and
+``_released`` (the RuntimeError of a second backward through a layer whose kept tensors the first one released).
 """
 import math
 from typing import Optional, Tuple, Union
@@ -45,6 +54,49 @@ def _nonempty(t, dtype):
 def _check_csr(row_ptr, col):
     assert row_ptr.dtype == torch.int32 and col.dtype == torch.int32, "per-hop CSR is int32 (sampler output)"
     assert row_ptr.is_cuda and col.is_cuda and row_ptr.is_contiguous() and col.is_contiguous()
+
+
+def _hop_args(row_ptr, col, x, src_ids):
+    """The eight leading arguments of a layer kernel over one hop: ``row_ptr, col, n_rows, x, ldx, F, src_ids, src_ids_dtype``
+    (``x`` float32 rows with unit column stride, read by row or through ``src_ids``; an empty ``col`` goes in as one element)."""
+    _check_csr(row_ptr, col)
+    assert x.dtype == torch.float32 and x.stride(1) == 1
+    return (row_ptr.data_ptr(), _nonempty(col, torch.int32).data_ptr(), row_ptr.shape[0] - 1, x.data_ptr(), x.stride(0),
+            x.shape[1]) + _ids_args(x, src_ids)
+
+
+def _out_rows(out, n_rows: int, width: int, device):
+    """A launch's float32 ``[n_rows, width]`` output: the caller's ``out`` (checked), or a fresh buffer."""
+    if out is None:
+        out = torch.empty((n_rows, width), dtype=torch.float32, device=device)
+    assert out.shape == (n_rows, width) and out.stride(1) == 1
+    return out
+
+
+def _padded_wt(weight, Nq: int):
+    """``weight^T`` ([N, F] -> [F, Nq]), zero columns from N up: the weight of a layer kernel run over the transposed hop."""
+    N, F_ = weight.shape
+    wt = torch.zeros((F_, Nq), dtype=torch.float32, device=weight.device)
+    wt[:, :N] = weight.detach().t()
+    return wt
+
+
+def _pad_cols(g, Nq: int):
+    """``g`` [n, N] with zero columns up to ``Nq`` (``g`` itself when it is that wide already)."""
+    N = g.shape[1]
+    if Nq == N:
+        return g
+    gq = torch.zeros((g.shape[0], Nq), dtype=torch.float32, device=g.device)
+    gq[:, :N] = g
+    return gq
+
+
+def _released(kept, layer_name: str, what: str, advice: str = ""):
+    """RuntimeError on a second backward through a one-kernel layer: what its forward kept (``kept``: None once it is gone) is
+    released by the first backward pass whatever retain_graph says, and autograd's own message covers saved tensors only."""
+    if kept is None:
+        raise RuntimeError("wholegraph_amd.nn.%s: backward through this layer a second time — its kept %s were released by the first "
+                           "backward pass (retain_graph=True is not supported by the one-kernel layer%s)" % (layer_name, what, advice))
 
 
 def spmm_csr_forward(row_ptr, col, x, mean=True, src_ids=None, out=None):
@@ -281,10 +333,9 @@ def sage_layer_fused_forward(row_ptr, col, x, self_rows, w_t, bias=None, relu=Fa
         user_out.copy_(res)
         return user_out
     N = Np
-    ids_ptr, ids_dt = None, 0
-    if src_ids is not None:
-        assert src_ids.is_contiguous()
-        ids_ptr, ids_dt = src_ids.data_ptr(), _ids_code(x, src_ids)
+    ids_ptr, ids_dt = _ids_args(x, src_ids)
+    # (an edge-less hop: an empty tensor's null pointer is refused by the entry points; every row is empty, so the stand-in is not read)
+    col_ptr = _nonempty(col, torch.int32).data_ptr()
     assert ids_dt != L.IDS_BYTE_OFFSETS or (sage_layer_fused_supported(F_, N) and _pick_precision(F_, N, precision) == "bf16x3"), \
         "a peer-mapped table is read by the bf16x3 layer kernel only"
     if (sage_layer_fused_supported(F_, N) and _pick_precision(F_, N, precision) == "bf16x3"
@@ -294,19 +345,19 @@ def sage_layer_fused_forward(row_ptr, col, x, self_rows, w_t, bias=None, relu=Fa
         if agg_out is not None:
             assert agg_out.shape == (n_rows, F_) and agg_out.dtype == torch.float32 and agg_out.stride(1) == 1
             L.check(L.lib().wgamd_sage_layer_fused_bf16x3_train(
-                row_ptr.data_ptr(), col.data_ptr(), n_rows, x.data_ptr(), x.stride(0), x.shape[0], F_, ids_ptr, ids_dt,
+                row_ptr.data_ptr(), col_ptr, n_rows, x.data_ptr(), x.stride(0), x.shape[0], F_, ids_ptr, ids_dt,
                 self_rows.data_ptr(), int(bool(mean)), planes.data_ptr(), N, None if bias is None else bias.data_ptr(),
                 flags, out.data_ptr(), out.stride(0), agg_out.data_ptr(), agg_out.stride(0), get_stream()),
                 "wgamd_sage_layer_fused_bf16x3_train")
             return done(out)
         L.check(L.lib().wgamd_sage_layer_fused_bf16x3(
-            row_ptr.data_ptr(), col.data_ptr(), n_rows, x.data_ptr(), x.stride(0), x.shape[0], F_, ids_ptr, ids_dt,
+            row_ptr.data_ptr(), col_ptr, n_rows, x.data_ptr(), x.stride(0), x.shape[0], F_, ids_ptr, ids_dt,
             self_rows.data_ptr(), int(bool(mean)), planes.data_ptr(), N, None if bias is None else bias.data_ptr(),
             flags, out.data_ptr(), out.stride(0), get_stream()), "wgamd_sage_layer_fused_bf16x3")
         return done(out)
     assert agg_out is None, "agg_out: only the bf16x3 layer kernel keeps the aggregate (sage_layer_train_supported)"
     L.check(L.lib().wgamd_sage_layer_fused_f32(
-        row_ptr.data_ptr(), col.data_ptr(), n_rows, x.data_ptr(), x.stride(0), x.shape[0], F_, ids_ptr, ids_dt,
+        row_ptr.data_ptr(), col_ptr, n_rows, x.data_ptr(), x.stride(0), x.shape[0], F_, ids_ptr, ids_dt,
         self_rows.data_ptr(),
         int(bool(mean)), w_t.data_ptr(), w_t.stride(0), N, None if bias is None else bias.data_ptr(), int(bool(relu)),
         out.data_ptr(), out.stride(0), get_stream()), "wgamd_sage_layer_fused_f32")
@@ -350,10 +401,7 @@ def sage_wgrad(agg, x, self_rows, grad_out, grad_w_l, grad_w_r, grad_bias=None, 
     assert grad_w_l.shape == (N, F_) and grad_w_l.is_contiguous() and grad_w_r.shape == (N, F_) and grad_w_r.is_contiguous()
     assert act_out is None or (act_out.shape == grad_out.shape and act_out.stride(1) == 1)
     assert grad_bias is None or (grad_bias.shape == (N,) and grad_bias.is_contiguous())
-    ids_ptr, ids_dt = None, 0
-    if src_ids is not None:
-        assert src_ids.is_contiguous()
-        ids_ptr, ids_dt = src_ids.data_ptr(), _ids_code(x, src_ids)
+    ids_ptr, ids_dt = _ids_args(x, src_ids)
     ws = _wgrad_workspace(n, F_, N, agg.device)
     L.check(L.lib().wgamd_sage_wgrad_bf16x3(
         agg.data_ptr(), agg.stride(0), x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt, self_rows.data_ptr(), n,
@@ -374,9 +422,8 @@ def _csr_transpose(row_ptr, col, n_src, want_perm=False, want_dst=False, want_co
     col_t = torch.empty(E, **i32) if want_col_t else None
     need = L.lib().wgamd_csr_transpose_workspace_bytes(E, n_src)
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
     L.check(L.lib().wgamd_csr_transpose_i32(row_ptr.data_ptr(), col.data_ptr(), n_dst, E, n_src, row_ptr_t.data_ptr(),
-                                            ptr(perm), ptr(dst), ptr(col_t), ws.data_ptr(), need, get_stream()),
+                                            _ptr(perm), _ptr(dst), _ptr(col_t), ws.data_ptr(), need, get_stream()),
             "wgamd_csr_transpose_i32")
     return row_ptr_t, perm, dst, col_t
 
@@ -403,10 +450,14 @@ def spmm_csr_backward(row_ptr, col, grad_out, n_src, mean=True, atomic=False):
     if mean:
         deg = (row_ptr[1:] - row_ptr[:-1]).clamp_(min=1)
         g = g / deg.unsqueeze(1)
-    row_ptr_t, col_t = csr_transpose(row_ptr, col, n_src)
-    # The transposed hop is power-law (a hub is a neighbour of thousands of sampled rows) while the gather kernel walks a
-    # row with one lane group: the launch would last as long as its longest row.  wgamd_spmm_csr_segmented_f32 sums rows
-    # in pieces of 64 entries and adds the pieces of a row up in order (deterministic, nothing read back).
+    return _spmm_csr_segmented(*csr_transpose(row_ptr, col, n_src), n_src, g)
+
+
+def _spmm_csr_segmented(row_ptr_t, col_t, n_src: int, g):
+    """``out[j] = sum_{e in row j} g[col_t[e]]`` over a transposed hop.  The transposed hop is power-law (a hub is a neighbour of
+    thousands of sampled rows) while the gather kernel walks a row with one lane group: the launch would last as long as its
+    longest row.  wgamd_spmm_csr_segmented_f32 sums rows in pieces of 64 entries and adds the pieces of a row up in order
+    (deterministic, nothing read back)."""
     E, F_ = col_t.shape[0], g.shape[1]
     out = torch.empty((n_src, F_), dtype=torch.float32, device=g.device)
     need = L.lib().wgamd_spmm_csr_segmented_workspace_bytes(E, F_)
@@ -1006,6 +1057,15 @@ def mapped_lazy_rows(wm_tensor, ids: torch.Tensor) -> LazyRows:
     return lazy
 
 
+class _Transposed:
+    """What ``HopGraph.transposed`` / ``input_dst`` keep of a hop seen from its input rows, under ``key`` = (n_src, capture epoch)."""
+    __slots__ = ("key", "row_ptr_t", "col_t", "self_t", "perm", "input_dst")
+
+    def __init__(self, key):
+        self.key = key
+        self.row_ptr_t = self.col_t = self.self_t = self.perm = self.input_dst = None
+
+
 class HopGraph:
     """One sampled hop as a layer consumes it: CSR over the hop's destination rows (``row_ptr`` int32 [n + 1]), ``col`` int32
     = row of every edge's source IN THE LAYER'S INPUT, ``self_rows`` int64 [n] = input row of every destination itself."""
@@ -1043,33 +1103,33 @@ class HopGraph:
         # (under HIP-graph capture the hop's arrays are fixed buffers REFILLED before every replay: the transpose must be part
         #  of the graph, once per capture)
         key = (n_src, _capture_epoch if _capturing() else 0)
-        stale = self._t is None or self._t[0] != key
-        if stale or (need_perm and self._t[4] is None):
-            n, dev = self.n_rows, self.row_ptr.device
+        t = self._t
+        if t is None or t.key != key:
+            t = self._t = _Transposed(key)
+        if t.row_ptr_t is None or (need_perm and t.perm is None):      # (a perm asked for later: the transpose runs again)
+            dev = self.row_ptr.device
             if self.col.shape[0] > 0:
-                row_ptr_t, perm, _, col_t = _csr_transpose(self.row_ptr, self.col, n_src, want_perm=need_perm, want_col_t=True)
+                t.row_ptr_t, t.perm, _, t.col_t = _csr_transpose(self.row_ptr, self.col, n_src, want_perm=need_perm, want_col_t=True)
             else:
-                row_ptr_t, col_t = torch.zeros(n_src + 1, dtype=torch.int32, device=dev), self.col
-                perm = torch.zeros(1, dtype=torch.int32, device=dev) if need_perm else None
-            self._t = [key, row_ptr_t, col_t] + ([None, perm, None] if stale else [self._t[3], perm, self._t[5]])
-        if need_self and self._t[3] is None:     # (only the layer kernel over the transposed hop reads it: three launches)
+                t.row_ptr_t, t.col_t = torch.zeros(n_src + 1, dtype=torch.int32, device=dev), self.col
+                t.perm = torch.zeros(1, dtype=torch.int32, device=dev) if need_perm else None
+        if need_self and t.self_t is None:     # (only the layer kernel over the transposed hop reads it: three launches)
             n, dev = self.n_rows, self.row_ptr.device
-            self_t = torch.full((n_src,), 2 * n, dtype=torch.int64, device=dev)
-            self_t[self.self_rows] = torch.arange(n, 2 * n, dtype=torch.int64, device=dev)
-            self._t[3] = self_t
-        res = tuple(self._t[1:4])
-        return res + (self._t[4],) if need_perm else res
+            t.self_t = torch.full((n_src,), 2 * n, dtype=torch.int64, device=dev)
+            t.self_t[self.self_rows] = torch.arange(n, 2 * n, dtype=torch.int64, device=dev)
+        res = (t.row_ptr_t, t.col_t, t.self_t)
+        return res + (t.perm,) if need_perm else res
 
     def input_dst(self, n_src: int):
         """int64 [n_src]: the destination row that input row j is itself, -1 where there is none — the ``self_rows`` of a
         GCN / RGCN layer kernel run over the transposed hop; kept with ``transposed``."""
         self.transposed(n_src, need_self=False)
-        if self._t[5] is None:
+        t = self._t
+        if t.input_dst is None:
             dev = self.row_ptr.device
-            dst = torch.full((n_src,), -1, dtype=torch.int64, device=dev)
-            dst[self.self_rows] = torch.arange(self.n_rows, dtype=torch.int64, device=dev)
-            self._t[5] = dst
-        return self._t[5]
+            t.input_dst = torch.full((n_src,), -1, dtype=torch.int64, device=dev)
+            t.input_dst[self.self_rows] = torch.arange(self.n_rows, dtype=torch.int64, device=dev)
+        return t.input_dst
 
 
 class LayerGraph:
@@ -1097,6 +1157,17 @@ def _hops(lg: LayerGraph):
         yield h, slice(at, at + n), slice(eat, eat + E)
         at += n
         eat += E
+
+
+def _sum_over_hops(lg: LayerGraph, zeros_shape, device, per_hop):
+    """The sum, in hop order, of the tensors ``per_hop(hop, rows, edges, k)`` returns for the hops of ``lg`` that have rows (hop k
+    with its ``_hops`` slices; the first tensor is added to in place).  Every hop empty: float32 zeros of ``zeros_shape``."""
+    total = None
+    for k, (h, rows, edges) in enumerate(_hops(lg)):
+        if h.n_rows > 0:
+            part = per_hop(h, rows, edges, k)
+            total = part if total is None else total.add_(part)
+    return torch.zeros(zeros_shape, dtype=torch.float32, device=device) if total is None else total
 
 
 def _edge_dst(row_ptr, n_edges: int, first: int = 0):
@@ -1170,15 +1241,7 @@ def _sage_dx(hop: HopGraph, gz: torch.Tensor, w_l: torch.Tensor, w_r: torch.Tens
         if mean:
             g = gz * hop.inv_deg.unsqueeze(1) if hop.inv_deg is not None \
                 else gz / (hop.row_ptr[1:] - hop.row_ptr[:-1]).clamp_(min=1).unsqueeze(1)
-        gl = g @ w_l
-        E = col_t.shape[0]
-        gx = torch.empty((n_src, F_), dtype=torch.float32, device=gz.device)
-        need = L.lib().wgamd_spmm_csr_segmented_workspace_bytes(E, F_)
-        ws = torch.empty(need, dtype=torch.uint8, device=gz.device)
-        L.check(L.lib().wgamd_spmm_csr_segmented_f32(row_ptr_t.data_ptr(), col_t.data_ptr(), n_src, E, gl.data_ptr(), gl.stride(0), F_,
-                                                     gx.data_ptr(), gx.stride(0), ws.data_ptr(), need, get_stream()),
-                "wgamd_spmm_csr_segmented_f32")
-        return gx.index_add_(0, hop.self_rows, gz @ w_r)
+        return _spmm_csr_segmented(row_ptr_t, col_t, n_src, g @ w_l).index_add_(0, hop.self_rows, gz @ w_r)
     gx = spmm_csr_backward(hop.row_ptr, hop.col, gz @ w_l, n_src, mean)
     return gx.index_add_(0, hop.self_rows, gz @ w_r)
 
@@ -1197,15 +1260,14 @@ def _sage_layer_launch(ctx, src, w_l, w_r, bias, conv, graph, ids, relu, mean):
             and w_l.stride(1) == 1 and w_r.stride(1) == 1:
         # (a mini-batch's few thousand rows at a width of half tiles: whole 32-row tiles — sage_layer_small_launch)
         prepared = sage_layer_planes(w_l, w_r, bias, Np, full_tiles=all(sage_layer_small_launch(F_, h.n_rows) for h in graph.hops))
-    w_t, aggs, at = (None if prepared is not None else conv._weight_t()), [], 0
-    for h in graph.hops:
+    w_t, aggs = (None if prepared is not None else conv._weight_t()), []
+    for h, rows, _ in _hops(graph):
         n = h.n_rows
         agg = torch.empty((n, F_), dtype=torch.float32, device=src.device) if keep and n > 0 else None
         if n > 0:
             sage_layer_fused_forward(h.row_ptr, h.col, src, h.self_rows, w_t, bias, relu=relu, mean=mean, src_ids=ids,
-                                     out=buf[at:at + n, :N], agg_out=agg, prepared=prepared)
+                                     out=buf[rows, :N], agg_out=agg, prepared=prepared)
         aggs.append(agg)
-        at += n
     out = buf[:, :N]
     if keep:
         if ctx.needs_input_grad[0] and ids is not None:
@@ -1233,12 +1295,7 @@ class _SageLayer(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.aggs is None:
-            # the kept aggregates (the largest tensors of the layer) are released by the first backward pass whatever
-            # retain_graph says — they are not autograd-saved tensors, so autograd's own message would not appear
-            raise RuntimeError("wholegraph_amd.nn.SAGEConv: backward through this layer a second time — its kept aggregates were "
-                               "released by the first backward pass (retain_graph=True is not supported by the one-kernel "
-                               "layer; run the forward again, or sum the losses before calling backward)")
+        _released(ctx.aggs, "SAGEConv", "aggregates", "; run the forward again, or sum the losses before calling backward")
         src, w_l, w_r, out = ctx.saved_tensors if len(ctx.saved_tensors) == 4 else (ctx.src_obj,) + tuple(ctx.saved_tensors)
         graph, ids, relu, mean = ctx.graph, ctx.ids, ctx.relu, ctx.mean
         N, F_ = w_l.shape
@@ -1251,17 +1308,16 @@ class _SageLayer(torch.autograd.Function):
         gwl, gwr = torch.empty_like(w_l, memory_format=torch.contiguous_format), torch.empty_like(w_r, memory_format=torch.contiguous_format)
         gb = torch.empty(N, dtype=torch.float32, device=g.device) if ctx.has_bias else None
         w_bwd = ctx.conv._weight_bwd() if need_x and any(h.n_rows > _SAGE_DX_SMALL_ROWS for h in graph.hops) else None
-        gx, at, first = None, 0, True
-        for h, agg in zip(graph.hops, ctx.aggs):
-            n = h.n_rows
-            if n > 0:
-                sage_wgrad(agg, src, h.self_rows, g[at:at + n], gwl, gwr, gb, None if act is None else act[at:at + n],
-                           src_ids=ids, accumulate=not first)
+        # (not _sum_over_hops: a hop's weight gradient launch goes right before its input gradient, and x may need none)
+        gx, first = None, True
+        for (h, rows, _), agg in zip(_hops(graph), ctx.aggs):
+            if h.n_rows > 0:
+                sage_wgrad(agg, src, h.self_rows, g[rows], gwl, gwr, gb, None if act is None else act[rows], src_ids=ids,
+                           accumulate=not first)
                 first = False
                 if need_x:
-                    gh = _sage_dx(h, g[at:at + n], w_l, w_r, w_bwd, mean, src.shape[0])
+                    gh = _sage_dx(h, g[rows], w_l, w_r, w_bwd, mean, src.shape[0])
                     gx = gh if gx is None else gx.add_(gh)
-            at += n
         if first:
             gwl.zero_(), gwr.zero_()
             if gb is not None:
@@ -1515,19 +1571,14 @@ def gcn_layer_forward(row_ptr, col, x, self_rows, weight, bias=None, dinv_src=No
     """A whole GCN layer over one hop in ONE kernel: ``act(agg @ weight^T + bias)`` with the normalised aggregate ``agg`` of
     ``wgamd_gcn_layer_f32`` (include/wgamd_ext.h); ``weight`` is [N, F] (``torch.nn.Linear`` layout).  ``agg_out`` ([n_rows, F]):
     the launch also keeps the aggregate (``_train``)."""
-    _check_csr(row_ptr, col)
+    hop = _hop_args(row_ptr, col, x, src_ids)
     n_rows, F_, N = row_ptr.shape[0] - 1, x.shape[1], weight.shape[0]
-    assert x.dtype == torch.float32 and x.stride(1) == 1 and weight.dtype == torch.float32 and weight.stride(1) == 1
+    assert weight.dtype == torch.float32 and weight.stride(1) == 1
     assert weight.shape[1] == F_ and self_rows.dtype == torch.int64 and self_rows.is_contiguous()
-    if out is None:
-        out = torch.empty((n_rows, N), dtype=torch.float32, device=row_ptr.device)
-    assert out.shape == (n_rows, N) and out.stride(1) == 1
-    ids_ptr, ids_dt = _ids_args(x, src_ids)
+    out = _out_rows(out, n_rows, N, row_ptr.device)
     flags = (GCN_ADD_SELF_LOOPS if add_self_loops else 0) | (GCN_RELU if relu else 0)
-    common = (row_ptr.data_ptr(), _nonempty(col, torch.int32).data_ptr(), n_rows, x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt,
-              self_rows.data_ptr(),
-              _ptr(edge_weight), _ptr(dinv_src), _ptr(dinv_dst), float(fill), weight.data_ptr(), weight.stride(0), N, _ptr(bias),
-              flags, out.data_ptr(), out.stride(0))
+    common = hop + (self_rows.data_ptr(), _ptr(edge_weight), _ptr(dinv_src), _ptr(dinv_dst), float(fill), weight.data_ptr(),
+                    weight.stride(0), N, _ptr(bias), flags, out.data_ptr(), out.stride(0))
     if agg_out is not None:
         assert agg_out.shape == (n_rows, F_) and agg_out.stride(1) == 1
         L.check(L.lib().wgamd_gcn_layer_f32_train(*common, agg_out.data_ptr(), agg_out.stride(0), get_stream()),
@@ -1541,16 +1592,12 @@ def gcn_aggregate(row_ptr, col, x, self_rows, dinv_src=None, dinv_dst=None, fill
                   edge_weight=None, out=None):
     """The normalised aggregate of the GCN layer alone, any F (``wgamd_gcn_aggregate_f32``): what shapes outside the layer
     kernel's domain multiply with a library GEMM."""
-    _check_csr(row_ptr, col)
-    n_rows, F_ = row_ptr.shape[0] - 1, x.shape[1]
-    assert x.dtype == torch.float32 and x.stride(1) == 1 and self_rows.dtype == torch.int64 and self_rows.is_contiguous()
-    if out is None:
-        out = torch.empty((n_rows, F_), dtype=torch.float32, device=row_ptr.device)
-    ids_ptr, ids_dt = _ids_args(x, src_ids)
+    hop = _hop_args(row_ptr, col, x, src_ids)
+    assert self_rows.dtype == torch.int64 and self_rows.is_contiguous()
+    out = _out_rows(out, row_ptr.shape[0] - 1, x.shape[1], row_ptr.device)
     L.check(L.lib().wgamd_gcn_aggregate_f32(
-        row_ptr.data_ptr(), _nonempty(col, torch.int32).data_ptr(), n_rows, x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt, self_rows.data_ptr(),
-        _ptr(edge_weight), _ptr(dinv_src), _ptr(dinv_dst), float(fill), GCN_ADD_SELF_LOOPS if add_self_loops else 0,
-        out.data_ptr(), out.stride(0), get_stream()), "wgamd_gcn_aggregate_f32")
+        *hop, self_rows.data_ptr(), _ptr(edge_weight), _ptr(dinv_src), _ptr(dinv_dst), float(fill),
+        GCN_ADD_SELF_LOOPS if add_self_loops else 0, out.data_ptr(), out.stride(0), get_stream()), "wgamd_gcn_aggregate_f32")
     return out
 
 
@@ -1566,6 +1613,24 @@ def gcn_wgrad(agg, grad_out, grad_w, grad_bias=None, act_out=None, accumulate=Fa
     L.check(L.lib().wgamd_gcn_wgrad_f32(agg.data_ptr(), agg.stride(0), n, F_, grad_out.data_ptr(), grad_out.stride(0), _ptr(act_out),
                                         0 if act_out is None else act_out.stride(0), N, grad_w.data_ptr(), _ptr(grad_bias),
                                         int(bool(accumulate)), ws.data_ptr(), ws.numel(), get_stream()), "wgamd_gcn_wgrad_f32")
+
+
+def _dense_wgrad(lg: LayerGraph, a, gz, w, want_b: bool, act):
+    """``(dW, db)`` of a dense product ``z = a @ w^T + b`` whose rows are the hops of ``lg`` back to back: ``gz^T a`` and (with
+    ``want_b``, else None) ``colsum(gz)``, ``gz`` masked by ``act > 0`` when ``act`` is given — one ``gcn_wgrad`` per hop with rows,
+    accumulated in hop order; zeros when no hop has rows."""
+    gw = torch.empty_like(w, memory_format=torch.contiguous_format)
+    gb = torch.empty(w.shape[0], dtype=torch.float32, device=gz.device) if want_b else None
+    first = True
+    for h, rows, _ in _hops(lg):
+        if h.n_rows > 0:
+            gcn_wgrad(a[rows], gz[rows], gw, gb, None if act is None else act[rows], accumulate=not first)
+            first = False
+    if first:
+        gw.zero_()
+        if gb is not None:
+            gb.zero_()
+    return gw, gb
 
 
 def _gcn_input_grad(hop, g, n_src, dinv_in, conv, edge_weight, weight=None):
@@ -1602,68 +1667,44 @@ class _GcnLayer(torch.autograd.Function):
         N, F_ = weight.shape
         keep = any(ctx.needs_input_grad[:3])
         out = torch.empty((graph.n_rows, N), dtype=torch.float32, device=weight.device)
-        aggs = []
         w = weight.detach()
         b = bias.detach() if bias is not None else None
+        agg = torch.empty((graph.n_rows, F_), dtype=torch.float32, device=weight.device) if ctx.needs_input_grad[1] else None
         for k, (h, rows, _) in enumerate(_hops(graph)):
-            n = h.n_rows
-            agg = torch.empty((n, F_), dtype=torch.float32, device=weight.device) if keep and ctx.needs_input_grad[1] and n > 0 else None
-            if n > 0:
+            if h.n_rows > 0:
                 gcn_layer_forward(h.row_ptr, h.col, src, h.self_rows, w, b, relu=relu, src_ids=ids,
-                                  edge_weight=None if edge_weights is None else edge_weights[k], out=out[rows], agg_out=agg,
-                                  **_gcn_launch_args(conv, dinv_in))
-            aggs.append(agg)
+                                  edge_weight=None if edge_weights is None else edge_weights[k], out=out[rows],
+                                  agg_out=None if agg is None else agg[rows], **_gcn_launch_args(conv, dinv_in))
         if keep:
             ctx.save_for_backward(weight, out)
-            ctx.conv, ctx.graph, ctx.dinv_in, ctx.relu, ctx.edge_weights, ctx.n_src, ctx.aggs = \
-                conv, graph, dinv_in, relu, edge_weights, n_src, aggs
+            # (kept is a 1-tuple: agg is None when the weight needs no gradient, and None itself is what _released reads as released)
+            ctx.conv, ctx.graph, ctx.dinv_in, ctx.relu, ctx.edge_weights, ctx.n_src, ctx.kept = \
+                conv, graph, dinv_in, relu, edge_weights, n_src, (agg,)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.aggs is None:
-            raise RuntimeError("wholegraph_amd.nn.GCNConv: backward through this layer a second time — its kept aggregates were "
-                               "released by the first backward pass (retain_graph=True is not supported by the one-kernel layer)")
+        _released(ctx.kept, "GCNConv", "aggregates")
         weight, out = ctx.saved_tensors
+        (agg,) = ctx.kept
         N, F_ = weight.shape
+        graph, n_src, dev = ctx.graph, ctx.n_src, g.device
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
         g = g.contiguous().float()
         act = out if ctx.relu else None
         if ctx.relu and need_x:
             g, act = torch.ops.aten.threshold_backward(g, out, 0), None      # dZ once, read by both gradients
-        gw = torch.empty_like(weight, memory_format=torch.contiguous_format) if need_w else None
-        gb = torch.empty(N, dtype=torch.float32, device=g.device) if need_b else None
-        gx = None
+        gx = gw = gb = None
+        if need_w:
+            gw, gb = _dense_wgrad(graph, agg, g, weight, need_b, act)
+        elif need_b:      # (no aggregate was kept: the hops' column sums in torch)
+            gb = _sum_over_hops(graph, (N,), dev, lambda h, rows, _, k: (g[rows] if act is None else g[rows] * (act[rows] > 0)).sum(0))
         if need_x:
             Nq = (N + 3) // 4 * 4
-            w_bwd = torch.zeros((F_, Nq), dtype=torch.float32, device=g.device)
-            w_bwd[:, :N] = weight.detach().t()
-            if Nq != N:
-                gq = torch.zeros((g.shape[0], Nq), dtype=torch.float32, device=g.device)
-                gq[:, :N] = g
-            else:
-                gq = g
-        first = True
-        for k, ((h, rows, _), agg) in enumerate(zip(_hops(ctx.graph), ctx.aggs)):
-            if h.n_rows > 0:
-                if need_w:
-                    gcn_wgrad(agg, g[rows], gw, gb, None if act is None else act[rows], accumulate=not first)
-                elif need_b:
-                    gz = g[rows] if act is None else g[rows] * (act[rows] > 0)
-                    gb = gz.sum(0) if first else gb.add_(gz.sum(0))
-                first = False
-                if need_x:
-                    gh = _gcn_input_grad(h, gq[rows], ctx.n_src, ctx.dinv_in, ctx.conv,
-                                         None if ctx.edge_weights is None else ctx.edge_weights[k], weight=w_bwd)
-                    gx = gh if gx is None else gx.add_(gh)
-        if first:
-            if gw is not None:
-                gw.zero_()
-            if gb is not None:
-                gb.zero_()
-        if need_x and gx is None:
-            gx = torch.zeros((ctx.n_src, F_), dtype=torch.float32, device=g.device)
-        ctx.aggs = None
+            w_bwd, gq, ew = _padded_wt(weight, Nq), _pad_cols(g, Nq), ctx.edge_weights
+            gx = _sum_over_hops(graph, (n_src, F_), dev, lambda h, rows, _, k: _gcn_input_grad(
+                h, gq[rows], n_src, ctx.dinv_in, ctx.conv, None if ew is None else ew[k], weight=w_bwd))
+        ctx.kept = None
         return gx, gw, gb, None, None, None, None, None, None, None
 
 
@@ -1686,15 +1727,9 @@ class _GcnAggregate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        g = g.contiguous()
-        gx = None
-        for k, (h, rows, _) in enumerate(_hops(ctx.graph)):
-            if h.n_rows > 0:
-                gh = _gcn_input_grad(h, g[rows], ctx.n_src, ctx.dinv_in, ctx.conv,
-                                     None if ctx.edge_weights is None else ctx.edge_weights[k])
-                gx = gh if gx is None else gx.add_(gh)
-        if gx is None:
-            gx = torch.zeros((ctx.n_src, g.shape[1]), dtype=torch.float32, device=g.device)
+        g, ew = g.contiguous(), ctx.edge_weights
+        gx = _sum_over_hops(ctx.graph, (ctx.n_src, g.shape[1]), g.device, lambda h, rows, _, k: _gcn_input_grad(
+            h, g[rows], ctx.n_src, ctx.dinv_in, ctx.conv, None if ew is None else ew[k]))
         return gx, None, None, None, None
 
 
@@ -1838,18 +1873,14 @@ def rgcn_layer_forward(row_ptr, col, x, self_rows, rel, coef, wt, comp, B: int, 
                        out=None):
     """A whole RGCN layer over one hop in ONE kernel (``wgamd_rgcn_layer_f32``, include/wgamd_ext.h): ``wt`` is the stacked weight
     transposed, [N, (B + root) F] (``_rgcn_stacked``); ``comp`` [R, B], or None for the identity (B = R)."""
-    _check_csr(row_ptr, col)
-    n_rows, F_, N = row_ptr.shape[0] - 1, x.shape[1], wt.shape[0]
-    assert x.dtype == torch.float32 and x.stride(1) == 1 and wt.dtype == torch.float32 and wt.stride(1) == 1
+    hop = _hop_args(row_ptr, col, x, src_ids)
+    N = wt.shape[0]
+    assert wt.dtype == torch.float32 and wt.stride(1) == 1
     assert self_rows is None or (self_rows.dtype == torch.int64 and self_rows.is_contiguous())
     assert rel.dtype == torch.int32 and coef.dtype == torch.float32 and rel.shape[0] == col.shape[0] == coef.shape[0]
-    if out is None:
-        out = torch.empty((n_rows, N), dtype=torch.float32, device=row_ptr.device)
-    assert out.shape == (n_rows, N) and out.stride(1) == 1
-    ids_ptr, ids_dt = _ids_args(x, src_ids)
+    out = _out_rows(out, row_ptr.shape[0] - 1, N, row_ptr.device)
     L.check(L.lib().wgamd_rgcn_layer_f32(
-        row_ptr.data_ptr(), _nonempty(col, torch.int32).data_ptr(), n_rows, x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt,
-        _ptr(self_rows), _nonempty(rel, torch.int32).data_ptr(), _nonempty(coef, torch.float32).data_ptr(), _ptr(comp), int(B),
+        *hop, _ptr(self_rows), _nonempty(rel, torch.int32).data_ptr(), _nonempty(coef, torch.float32).data_ptr(), _ptr(comp), int(B),
         int(bool(has_root)), wt.data_ptr(), wt.stride(0), N, _ptr(bias), int(bool(relu)), out.data_ptr(), out.stride(0),
         get_stream()), "wgamd_rgcn_layer_f32")
     return out
@@ -1921,6 +1952,7 @@ class _RgcnLayer(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        _released(ctx.coefs, "RGCNConv", "per-edge coefficients")
         weight, comp, root, out = ctx.saved_tensors
         B, F_, N = weight.shape
         R, dev = ctx.R, g.device
@@ -1955,18 +1987,14 @@ class _RgcnLayer(torch.autograd.Function):
             gb = gz.sum(0)
         if need_x:
             Nq = (N + 3) // 4 * 4
-            w_bwd = _rgcn_stacked(weight, root, Nq)
-            gq = gz if Nq == N else torch.nn.functional.pad(gz, (0, Nq - N))
+            w_bwd, gq, coefs, n_src = _rgcn_stacked(weight, root, Nq), _pad_cols(gz, Nq), ctx.coefs, ctx.n_src
             c = None if comp is None else comp.detach().contiguous()
-            for (h, rows, _), (rel, coef) in zip(_hops(ctx.graph), ctx.coefs):
-                if h.n_rows > 0:
-                    row_ptr_t, col_t, _, perm = h.transposed(ctx.n_src, need_self=False, need_perm=True)
-                    p = perm[:h.col.shape[0]]
-                    gh = rgcn_layer_forward(row_ptr_t, col_t, gq[rows], h.input_dst(ctx.n_src), rel[p], coef[p], w_bwd, c, B,
-                                            root is not None)
-                    gx = gh if gx is None else gx.add_(gh)
-            if gx is None:
-                gx = torch.zeros((ctx.n_src, F_), dtype=torch.float32, device=dev)
+
+            def input_grad(h, rows, _, k):      # the layer kernel over hop k's transpose, per-edge arrays in the transposed order
+                row_ptr_t, col_t, _, perm = h.transposed(n_src, need_self=False, need_perm=True)
+                p, (rel, coef) = perm[:h.col.shape[0]], coefs[k]
+                return rgcn_layer_forward(row_ptr_t, col_t, gq[rows], h.input_dst(n_src), rel[p], coef[p], w_bwd, c, B, root is not None)
+            gx = _sum_over_hops(ctx.graph, (n_src, F_), dev, input_grad)
         ctx.src = ctx.coefs = None
         return gx, gw, gc, gr, gb, None, None, None, None, None, None
 
@@ -2172,29 +2200,48 @@ def transformer_layer_forward(row_ptr, col, x, u, wt, H: int, self_rows=None, x_
     """A whole transformer layer over one hop in ONE kernel (``wgamd_transformer_layer_f32``, include/wgamd_ext.h).  ``u``
     [n, H F_src] and ``w`` [n, H D] are the per-destination vectors (``transformer_folds``), ``wt`` = Wstack^T [N, K];
     ``x_dst`` (None: no skip block) is read at ``self_rows`` (through ``src_ids`` when ``x_dst_ids``)."""
-    _check_csr(row_ptr, col)
+    hop = _hop_args(row_ptr, col, x, src_ids)
     n_rows, F_, N = row_ptr.shape[0] - 1, x.shape[1], wt.shape[0]
     D = 0 if edge_attr is None else edge_attr.shape[1]
     Fd = 0 if x_dst is None else x_dst.shape[1]
-    assert x.dtype == torch.float32 and x.stride(1) == 1 and wt.dtype == torch.float32 and wt.stride(1) == 1
+    assert wt.dtype == torch.float32 and wt.stride(1) == 1
     assert u.dtype == torch.float32 and u.stride(1) == 1 and u.shape == (n_rows, H * F_)
     assert edge_attr is None or (edge_attr.dtype == torch.float32 and edge_attr.is_contiguous() and edge_attr.shape[0] == col.shape[0])
     assert w is None or (w.dtype == torch.float32 and w.stride(1) == 1 and w.shape == (n_rows, H * D))
     assert x_dst is None or (self_rows is not None and self_rows.dtype == torch.int64 and self_rows.is_contiguous())
-    if out is None:
-        out = torch.empty((n_rows, N), dtype=torch.float32, device=row_ptr.device)
-    assert out.shape == (n_rows, N) and out.stride(1) == 1
+    out = _out_rows(out, n_rows, N, row_ptr.device)
     assert alpha is None or (alpha.shape == (col.shape[0], H) and alpha.is_contiguous())
     assert a_save is None or a_save.is_contiguous()
-    ids_ptr, ids_dt = _ids_args(x, src_ids)
     L.check(L.lib().wgamd_transformer_layer_f32(
-        row_ptr.data_ptr(), _nonempty(col, torch.int32).data_ptr(), n_rows, x.data_ptr(), x.stride(0), F_, ids_ptr, ids_dt,
-        _ptr(x_dst), 0 if x_dst is None else x_dst.stride(0), Fd, _ptr(self_rows), int(bool(x_dst_ids)),
+        *hop, _ptr(x_dst), 0 if x_dst is None else x_dst.stride(0), Fd, _ptr(self_rows), int(bool(x_dst_ids)),
         None if D == 0 else _nonempty(edge_attr, torch.float32).data_ptr(), D, u.data_ptr(), u.stride(0), _ptr(w),
         0 if w is None else w.stride(0), int(H), wt.data_ptr(), wt.stride(0), N, _ptr(bias), int(bool(relu)), out.data_ptr(),
         out.stride(0), None if alpha is None or alpha.numel() == 0 else alpha.data_ptr(), _ptr(a_save), get_stream()),
         "wgamd_transformer_layer_f32")
     return out
+
+
+def transformer_bwd_dst(row_ptr, col, x, H: int, alpha, dA, A, du, ds, edge_attr=None, dw=None, src_ids=None):
+    """The destination-major backward launch of one hop (``wgamd_transformer_bwd_dst_f32``, include/wgamd_ext.h): from ``dA`` = dZ
+    Wstack^T and the kept rows ``A`` (both [n_rows, K]) and ``alpha`` [E, H], writes ``du`` [n_rows, H F_src], ``dw`` [n_rows,
+    H D] (with ``edge_attr`` [E, D]) and ``ds`` [E, H]."""
+    D = 0 if edge_attr is None else edge_attr.shape[1]
+    assert dA.stride(1) == 1 and A.stride(1) == 1 and du.is_contiguous() and (dw is None or dw.is_contiguous())
+    L.check(L.lib().wgamd_transformer_bwd_dst_f32(
+        *_hop_args(row_ptr, col, x, src_ids), None if D == 0 else _nonempty(edge_attr, torch.float32).data_ptr(), D, int(H),
+        _nonempty(alpha, torch.float32).data_ptr(), dA.data_ptr(), dA.stride(0), A.data_ptr(), A.stride(0), du.data_ptr(),
+        _ptr(dw), _nonempty(ds, torch.float32).data_ptr(), get_stream()), "wgamd_transformer_bwd_dst_f32")
+
+
+def transformer_bwd_src(row_ptr_t, col_t, perm, self_t, D: int, H: int, skip_at: int, alpha, ds, dA, u, gx):
+    """The source-major backward launch of one hop over its transpose (``wgamd_transformer_bwd_src_f32``, include/wgamd_ext.h):
+    ``gx`` [n_src, F_src] += the hop's part of the input gradient, from the hop's rows of ``dA`` and ``u``; ``row_ptr_t, col_t,
+    self_t, perm`` as ``HopGraph.transposed`` gives them (``self_t`` None or ``skip_at`` < 0: no skip term)."""
+    assert dA.stride(1) == 1 and u.stride(1) == 1 and gx.stride(1) == 1 and u.shape[0] == dA.shape[0]
+    L.check(L.lib().wgamd_transformer_bwd_src_f32(
+        row_ptr_t.data_ptr(), _nonempty(col_t, torch.int32).data_ptr(), perm.data_ptr(), _ptr(self_t), dA.shape[0], gx.shape[0],
+        gx.shape[1], D, H, skip_at, _nonempty(alpha, torch.float32).data_ptr(), _nonempty(ds, torch.float32).data_ptr(), dA.data_ptr(),
+        dA.stride(0), u.data_ptr(), u.stride(0), gx.data_ptr(), gx.stride(0), 1, get_stream()), "wgamd_transformer_bwd_src_f32")
 
 
 def _tconv_rows(t):
@@ -2247,6 +2294,7 @@ class _TconvLayer(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, *unused):
+        _released(ctx.x, "TransformerConv", "input rows")
         u, w, wt, out, alpha, A = ctx.saved_tensors
         need_x, need_xd, need_u, need_w, need_ea, need_wt, need_b = ctx.needs_input_grad[:7]
         x, ea, lg, H = ctx.x, ctx.edge_attr, ctx.graph, ctx.H
@@ -2270,15 +2318,10 @@ class _TconvLayer(torch.autograd.Function):
             du = torch.empty((n, H * F_), dtype=torch.float32, device=dev)
             dw = torch.empty((n, H * D), dtype=torch.float32, device=dev) if D else None
             ds = torch.empty((E, H), dtype=torch.float32, device=dev)
-            ids_ptr, ids_dt = _ids_args(x, ctx.ids)
             for h, rows, edges in _hops(lg):
                 if h.n_rows > 0:
-                    L.check(L.lib().wgamd_transformer_bwd_dst_f32(
-                        h.row_ptr.data_ptr(), _nonempty(h.col, torch.int32).data_ptr(), h.n_rows, x.data_ptr(), x.stride(0), F_,
-                        ids_ptr, ids_dt, None if D == 0 else _nonempty(ea[edges], torch.float32).data_ptr(), D, H,
-                        _nonempty(alpha[edges], torch.float32).data_ptr(), dA[rows].data_ptr(), dA.stride(0), A[rows].data_ptr(),
-                        A.stride(0), du[rows].data_ptr(), None if dw is None else dw[rows].data_ptr(),
-                        _nonempty(ds[edges], torch.float32).data_ptr(), get_stream()), "wgamd_transformer_bwd_dst_f32")
+                    transformer_bwd_dst(h.row_ptr, h.col, x, H, alpha[edges], dA[rows], A[rows], du[rows], ds[edges],
+                                        edge_attr=None if D == 0 else ea[edges], dw=None if dw is None else dw[rows], src_ids=ctx.ids)
             gu, gw = du, dw
             if need_x:
                 gx = torch.zeros((ctx.n_src, F_), dtype=torch.float32, device=dev)
@@ -2289,12 +2332,7 @@ class _TconvLayer(torch.autograd.Function):
                 for h, rows, edges in _hops(lg):
                     if h.n_rows > 0:
                         row_ptr_t, col_t, self_t, perm = h.transposed(ctx.n_src, need_self=own_skip, need_perm=True)
-                        L.check(L.lib().wgamd_transformer_bwd_src_f32(
-                            row_ptr_t.data_ptr(), _nonempty(col_t, torch.int32).data_ptr(), perm.data_ptr(), _ptr(self_t), h.n_rows,
-                            ctx.n_src, F_, D, H, skip_at,
-                            _nonempty(alpha[edges], torch.float32).data_ptr(), _nonempty(ds[edges], torch.float32).data_ptr(),
-                            dA[rows].data_ptr(), dA.stride(0), u[rows].data_ptr(), u.stride(0), gx.data_ptr(), gx.stride(0), 1,
-                            get_stream()), "wgamd_transformer_bwd_src_f32")
+                        transformer_bwd_src(row_ptr_t, col_t, perm, self_t, D, H, skip_at, alpha[edges], ds[edges], dA[rows], u[rows], gx)
             if need_xd and ctx.skip:
                 gxd = dA[:, H * W4:].contiguous()
             if need_ea and D:
@@ -2544,17 +2582,15 @@ def gin_layer_supported(F_: int, H: int, N: int = 0) -> bool:
     return bool(L.lib().wgamd_gin_layer_supported(int(F_), int(H), int(N)))
 
 
-def _gin_hop_args(row_ptr, col, x, self_rows, x_dst, eps, src_ids):
-    _check_csr(row_ptr, col)
+def _gin_hop_args(row_ptr, x, self_rows, x_dst, eps):
+    """GIN's four arguments behind ``_hop_args``: ``self_rows, x_dst, ldx_dst, eps`` (the self row of destination i is ``x_dst[i]``
+    when ``x_dst`` is given, else row ``self_rows[i]`` of x)."""
     F_ = x.shape[1]
-    assert x.dtype == torch.float32 and x.stride(1) == 1
     assert self_rows is None or (self_rows.dtype == torch.int64 and self_rows.is_contiguous())
     assert x_dst is None or (x_dst.dtype == torch.float32 and x_dst.stride(1) == 1 and x_dst.shape[1] == F_
                              and x_dst.shape[0] >= row_ptr.shape[0] - 1)
     assert eps is None or (eps.dtype == torch.float32 and eps.is_cuda and eps.numel() == 1)
-    ids_ptr, ids_dt = _ids_args(x, src_ids)
-    return (row_ptr.data_ptr(), _nonempty(col, torch.int32).data_ptr(), row_ptr.shape[0] - 1, x.data_ptr(), x.stride(0), F_, ids_ptr,
-            ids_dt, None if x_dst is not None else _ptr(self_rows), _ptr(x_dst), 0 if x_dst is None else x_dst.stride(0), _ptr(eps))
+    return (None if x_dst is not None else _ptr(self_rows), _ptr(x_dst), 0 if x_dst is None else x_dst.stride(0), _ptr(eps))
 
 
 def gin_layer_forward(row_ptr, col, x, self_rows, w1, b1=None, w2=None, b2=None, eps=None, relu_hidden=True, relu_out=False,
@@ -2565,15 +2601,13 @@ def gin_layer_forward(row_ptr, col, x, self_rows, w1, b1=None, w2=None, b2=None,
     ends after the first product (output [n_rows, H]).  The self row of destination i is ``x_dst[i]`` when ``x_dst`` is given,
     else row ``self_rows[i]`` of x; neither: no self term.  ``keep`` (or ``agg_out`` / ``hidden_out`` buffers): the launch also
     stores the aggregate and, with a second product, the hidden activation (``_train``), and ``(out, agg, hidden)`` is returned."""
-    hop = _gin_hop_args(row_ptr, col, x, self_rows, x_dst, eps, src_ids)
+    hop = _hop_args(row_ptr, col, x, src_ids) + _gin_hop_args(row_ptr, x, self_rows, x_dst, eps)
     n_rows, F_, H = row_ptr.shape[0] - 1, x.shape[1], w1.shape[0]
     N = 0 if w2 is None else w2.shape[0]
     for w, k in ((w1, F_), (w2, H)):
         assert w is None or (w.dtype == torch.float32 and w.stride(1) == 1 and w.shape[1] == k)
     dev = row_ptr.device
-    if out is None:
-        out = torch.empty((n_rows, N or H), dtype=torch.float32, device=dev)
-    assert out.shape == (n_rows, N or H) and out.stride(1) == 1
+    out = _out_rows(out, n_rows, N or H, dev)
     flags = (GIN_RELU_HIDDEN if relu_hidden else 0) | (GIN_RELU_OUT if relu_out else 0)
     common = hop + (w1.data_ptr(), w1.stride(0), H, _ptr(b1), _ptr(w2), 0 if w2 is None else w2.stride(0), N, _ptr(b2), flags,
                     out.data_ptr(), out.stride(0))
@@ -2595,11 +2629,8 @@ def gin_layer_forward(row_ptr, col, x, self_rows, w1, b1=None, w2=None, b2=None,
 def gin_aggregate(row_ptr, col, x, self_rows, eps=None, src_ids=None, x_dst=None, out=None):
     """The GIN aggregate alone, any F (``wgamd_gin_aggregate_f32``): the sum of the neighbour rows plus ``(1 + eps)`` times the
     self row (``gin_layer_forward``'s)."""
-    hop = _gin_hop_args(row_ptr, col, x, self_rows, x_dst, eps, src_ids)
-    n_rows, F_ = row_ptr.shape[0] - 1, x.shape[1]
-    if out is None:
-        out = torch.empty((n_rows, F_), dtype=torch.float32, device=row_ptr.device)
-    assert out.shape == (n_rows, F_) and out.stride(1) == 1
+    hop = _hop_args(row_ptr, col, x, src_ids) + _gin_hop_args(row_ptr, x, self_rows, x_dst, eps)
+    out = _out_rows(out, row_ptr.shape[0] - 1, x.shape[1], row_ptr.device)
     L.check(L.lib().wgamd_gin_aggregate_f32(*hop, out.data_ptr(), out.stride(0), get_stream()), "wgamd_gin_aggregate_f32")
     return out
 
@@ -2627,20 +2658,13 @@ def _gin_input_grad(graph: LayerGraph, g, n_src: int, eps, has_self: bool, weigh
     """``A^T g + (1 + eps) S^T g`` over every hop of ``graph`` (rows = the layer's input rows; the second term only where an
     input row is a destination itself, and only with ``has_self``), times ``weight`` ([F, Hq]) when given: the GIN kernels run
     over the hops' transposes."""
-    gx = None
-    for h, rows, _ in _hops(graph):
-        if h.n_rows == 0:
-            continue
+    def per_hop(h, rows, _, k):
         row_ptr_t, col_t, _ = h.transposed(n_src, need_self=False)
         self_t = h.input_dst(n_src) if has_self else None
         if weight is None:
-            gh = gin_aggregate(row_ptr_t, col_t, g[rows], self_t, eps=eps)
-        else:
-            gh = gin_layer_forward(row_ptr_t, col_t, g[rows], self_t, weight, eps=eps, relu_hidden=False)
-        gx = gh if gx is None else gx.add_(gh)
-    if gx is None:
-        gx = torch.zeros((n_src, g.shape[1] if weight is None else weight.shape[0]), dtype=torch.float32, device=g.device)
-    return gx
+            return gin_aggregate(row_ptr_t, col_t, g[rows], self_t, eps=eps)
+        return gin_layer_forward(row_ptr_t, col_t, g[rows], self_t, weight, eps=eps, relu_hidden=False)
+    return _sum_over_hops(graph, (n_src, g.shape[1] if weight is None else weight.shape[0]), g.device, per_hop)
 
 
 class _GinLayer(torch.autograd.Function):
@@ -2675,9 +2699,7 @@ class _GinLayer(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.kept is None:
-            raise RuntimeError("wholegraph_amd.nn.GINConv: backward through this layer a second time — its kept activations were "
-                               "released by the first backward pass (retain_graph=True is not supported by the one-kernel layer)")
+        _released(ctx.kept, "GINConv", "activations")
         w1, w2, eps, out, x_dst = ctx.saved_tensors
         agg, hidden = ctx.kept
         src = ctx.src
@@ -2689,47 +2711,26 @@ class _GinLayer(torch.autograd.Function):
         g = g.contiguous().float()
         gw1 = gb1 = gw2 = gb2 = None
         some = any(h.n_rows > 0 for h in graph.hops)
-
-        def wgrad(a, gz, w, want_w, want_b, act):
-            """(dW, db) of one product over every hop: gz^T a and colsum(gz), gz masked by ``act > 0`` when given."""
-            if not (want_w or want_b):
-                return None, None
-            gw = torch.empty_like(w, memory_format=torch.contiguous_format)
-            gb = torch.empty(w.shape[0], dtype=torch.float32, device=dev) if want_b else None
-            first = True
-            for h, rows, _ in _hops(graph):
-                if h.n_rows > 0:
-                    gcn_wgrad(a[rows], gz[rows], gw, gb, None if act is None else act[rows], accumulate=not first)
-                    first = False
-            if first:
-                gw.zero_()
-                if gb is not None:
-                    gb.zero_()
-            return (gw if want_w else None), gb
-
         if w2 is not None:
             if relu_out:
                 g = torch.ops.aten.threshold_backward(g, out, 0)
-            gw2, gb2 = wgrad(hidden, g, w2, need_w2, need_b2, None)
+            if need_w2 or need_b2:      # (a bias gradient alone: the product's launches all the same, dW dropped)
+                gw2, gb2 = _dense_wgrad(graph, hidden, g, w2, need_b2, None)
+                gw2 = gw2 if need_w2 else None
             g1, act1 = g @ w2.detach(), hidden if relu_hidden else None          # dHidden: one library GEMM
         else:
             g1, act1 = g, out if relu_hidden else None
         lower = need_x or need_xd or need_eps
         if act1 is not None and lower:
             g1, act1 = torch.ops.aten.threshold_backward(g1, act1, 0), None      # dZ1 once, read by every gradient below
-        gw1, gb1 = wgrad(agg, g1, w1, need_w1, need_b1, act1)
+        if need_w1 or need_b1:
+            gw1, gb1 = _dense_wgrad(graph, agg, g1, w1, need_b1, act1)
+            gw1 = gw1 if need_w1 else None
         gx = gxd = geps = None
         has_self = not ctx.no_root and x_dst is None
         if need_x:
             Hq = (H + 3) // 4 * 4
-            w_bwd = torch.zeros((F_, Hq), dtype=torch.float32, device=dev)
-            w_bwd[:, :H] = w1.detach().t()
-            if Hq != H:
-                gq = torch.zeros((g1.shape[0], Hq), dtype=torch.float32, device=dev)
-                gq[:, :H] = g1
-            else:
-                gq = g1
-            gx = _gin_input_grad(graph, gq, ctx.n_src, eps.detach(), has_self, weight=w_bwd)
+            gx = _gin_input_grad(graph, _pad_cols(g1, Hq), ctx.n_src, eps.detach(), has_self, weight=_padded_wt(w1, Hq))
         if (need_xd or need_eps) and not ctx.no_root:
             d_agg = g1 @ w1.detach() if some else torch.zeros((0, F_), dtype=torch.float32, device=dev)
             if need_xd:
@@ -3248,9 +3249,7 @@ class _HeteroSageGroup(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        if ctx.c is None:
-            raise RuntimeError("wholegraph_amd.nn.HeteroConv: backward through this SAGE layer a second time — its kept rows were "
-                               "released by the first backward pass (retain_graph=True is not supported by the one-kernel layer)")
+        _released(ctx.c, "HeteroConv (SAGEConv relations)", "rows")
         grp, c = ctx.grp, ctx.c
         w, z = ctx.saved_tensors
         N, K = grp.N, grp.K

@@ -155,6 +155,38 @@ def test_gradients_match_float64_and_repeat_bit_for_bit(hiplib):
     assert err <= 1e-4 * scale
 
 
+def test_second_backward_raises_and_a_fresh_pass_repeats_the_gradients(hiplib):
+    """The kept C rows of a group are released by the first backward pass whatever retain_graph says: a second backward raises
+    a RuntimeError that says so, and a fresh forward and backward gives the first pass's gradients bit for bit."""
+    import torch
+    from wholegraph_amd import nn
+    grp, etypes, dev, g = mag_group(64)
+    (layer,) = sage_model(etypes, [(64, 64)], dev)
+    params = list(layer.parameters())
+    xp = grp.x_dict["paper"].materialize().clone().requires_grad_(True)
+    xs = {t: (xp if t == "paper" else v) for t, v in grp.x_dict.items()}
+    graph = grp.layer_graph(0)
+
+    def loss():
+        before = nn.hetero_sage_launches
+        out = layer(xs, graph, act="relu")
+        assert nn.hetero_sage_launches - before == expected_launches(layer, graph), "the kernel route did not run"
+        return sum(v.sum() for v in out.values())
+    total = loss()
+    total.backward(retain_graph=True)
+    reached = {r.edge_type[2] for r in graph.relations if r.n_rows > 0}      # (a type no hop ends in launches nothing)
+    assert xp.grad is not None and "paper" in reached
+    assert all(p.grad is not None for et in layer.edge_types if et[2] in reached for p in layer.conv(et).parameters())
+    first = [None if t.grad is None else t.grad.clone() for t in [xp] + params]
+    with pytest.raises(RuntimeError, match="a second time"):
+        total.backward()
+    for t in [xp] + params:
+        t.grad = None
+    loss().backward()
+    for t, want in zip([xp] + params, first):
+        assert (t.grad is None and want is None) or torch.equal(t.grad, want)
+
+
 def random_csr(n_rows, n_src, max_deg, g, dev):
     import torch
     deg = torch.randint(0, max_deg + 1, (n_rows,), generator=g, device=dev) if max_deg > 0 else torch.zeros(n_rows, dtype=torch.int64, device=dev)
