@@ -43,6 +43,17 @@
 //     256 -> 256 layer 1.69 -> 1.51 ms (no weight loads at all: 1.34; the multiplying waves alone: 0.90, of which 0.43 is
 //     the matrix pipe; the fetching waves alone: 0.73 = the HBM floor of the shape).
 //   * one s_barrier per step behind an LDS-only wait (s_waitcnt lgkmcnt(0)): neither side's global loads are drained.
+//   * TILES ARE HANDED OUT BY TICKET, not by a fixed stride.  A workgroup's first tile is its block index; every later one is
+//     gridDim.x + atomicAdd(ticket, 1) on the launch's slot in device memory (`mfma_args::tickets`, `ticket_slot` below), so a
+//     workgroup that starts late or runs on a slowly fed CU takes fewer tiles instead of holding the launch open with its
+//     fixed share of them.  Lane 0 of the first fetching wave draws the tile of step n + 2 at the start of step n — the
+//     metadata pipeline reads the bounds of tile n + 1 at the start of step n, so a tile number is needed two steps before it
+//     is multiplied — and publishes it in a 3-entry LDS ring before the step's barrier; every wave reads entry n + 1 behind
+//     the barrier of step n - 1.  No barrier, fence or wait was added: the ticket comes back under the step's row fetches.  A
+//     ticket >= the tile count means "none left".  The slot rewinds itself: a second word counts the workgroups that have
+//     left, and the last one zeroes both, so the next launch on the stream — or the next replay of a captured graph, which
+//     has the slot's address baked in — starts from zero without a memset.  Which workgroup runs a tile changes no bit of
+//     its rows (tests/test_gpu_sage_dynamic_tiles.py).  Measured spread of the workgroups' end times: profiles/r07/README.md.
 #include "wg_sage_mfma_parts.hpp"
 
 namespace wgamd {
@@ -280,7 +291,12 @@ sage_layer_mfma_kernel(mfma_args a)
   const int tile_dw = TR * a.SD;
   // every word the MFMA can touch must be finite: pad columns, the rows of a tile that is still being written for the
   // first time, and the few floats the last k-step reads past a row (times the zero rows of the weight)
+  // ring of the tile numbers of steps n, n + 1, n + 2 (the unused second half of the role keys' 16 words)
+  uint32_t* ring = reinterpret_cast<uint32_t*>(lds + 2 * tile_dw + 16 + CW * kScratchDw) + 8;
+  uint32_t first_ticket = kNoTile;
+  if (threadIdx.x == 0 && (int64_t)blockIdx.x < (a.n_rows + TR - 1) / TR) first_ticket = (uint32_t)gridDim.x + atomicAdd(a.tickets, 1u);
   for (int i = threadIdx.x; i < 2 * tile_dw + 16; i += blockDim.x) lds[i] = 0.f;   // (scratch and role keys need no init)
+  if (threadIdx.x == 0) ring[0] = blockIdx.x, ring[1] = first_ticket;
   __syncthreads();
   const int lane = threadIdx.x & 63;
   // Optional ROLES BY SIMD (see the header; off): every wave reads its SIMD id (HW_REG_HW_ID bits 5:4), the workgroup ranks
@@ -299,9 +315,23 @@ sage_layer_mfma_kernel(mfma_args a)
     wave = __builtin_amdgcn_readfirstlane(rank);
     __syncthreads();
   }
-  const int64_t n_tiles = (a.n_rows + TR - 1) / TR;
-  const int64_t mine    = blockIdx.x < n_tiles ? (n_tiles - blockIdx.x + gridDim.x - 1) / gridDim.x : 0;
-  auto tile_of          = [&](int64_t n) { return (int64_t)blockIdx.x + n * gridDim.x; };
+  // TILE HAND-OUT (see the header): t_cur is the tile of this step — the fetching waves fill it, the multiplying waves run
+  // t_prev — and t_next the tile after it, which the fetching waves' metadata pipeline already reads.  A tile number
+  // >= n_tiles means "none left"; the counter only grows, so every later one says the same.
+  // (tile numbers are 32-bit: the launch helpers refuse a tile count that does not leave room for the tickets past it)
+  const uint32_t n_tiles = (uint32_t)((a.n_rows + TR - 1) / TR);
+  const bool drawer      = wave == CW && lane == 0;
+  auto draw              = [&](uint32_t known) {   // the tile after `known` (one lane)
+    return known < n_tiles ? (uint32_t)gridDim.x + atomicAdd(a.tickets, 1u) : kNoTile;
+  };
+  auto ring_at = [&](int r) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)ring[r]); };   // wave-uniform
+  uint32_t t_prev = kNoTile, t_cur = ring_at(0);
+  int r_next = 1;                                      // ring entry of step n + 1
+  auto advance = [&](uint32_t t_next) {                // behind the step's barrier
+    t_prev = t_cur, t_cur = t_next;
+    r_next = r_next == 2 ? 0 : r_next + 1;
+  };
+  auto r_draw = [&] { return r_next == 2 ? 0 : r_next + 1; };   // ring entry of step n + 2
   auto stamp            = [&](int64_t n, int which) {
     if (a.stamps && blockIdx.x == 0 && lane == 0 && n < 64) a.stamps[(n * 8 + wave) * 2 + which] = __builtin_readcyclecounter();
   };
@@ -328,37 +358,43 @@ sage_layer_mfma_kernel(mfma_args a)
       ids_t<IT> i_next;
       meta_t<IT, off_t> cur;
       f32x4 buf[kDepth][kNb + 1];
-      auto sub_of = [&](int64_t j) { return 2 * tile_of(j >> 1) + (j & 1); };
-      p.load_bounds(sub_of(0), b_next);
-      p.load_ids(sub_of(0), b_next, i_next);
+      p.load_bounds(2 * (int64_t)t_cur, b_next);
+      p.load_ids(2 * (int64_t)t_cur, b_next, i_next);
       p.finish(i_next, cur);
 #pragma unroll
       for (int it = 0; it < kDepth - 1; it++) p.issue(cur, it, buf[it]);
       constexpr int kHalf = IT / 2;
-      for (int64_t n = 0; n <= mine; n++) {
-        if (n < mine && !(a.debug & 2)) {
+      for (int n = 0;; n++) {
+        const uint32_t t_next = ring_at(r_next);
+        uint32_t drawn       = kNoTile;
+        if (drawer && t_cur < n_tiles) drawn = draw(t_next);   // the tile of step n + 2, published below
+        if (t_cur < n_tiles && !(a.debug & 2)) {
           float* tile_lds = lds + (n & 1) * tile_dw;
 #pragma unroll
           for (int sub = 0; sub < 2; sub++) {
-            const int64_t j = 2 * n + sub;
+            const int64_t s_cur = 2 * (int64_t)t_cur + sub, s_next = sub == 0 ? s_cur + 1 : 2 * (int64_t)t_next;
             float* rows_lds = tile_lds + sub * 32 * a.SD;
-            p.load_bounds(sub_of(j + 1), b_next);
+            p.load_bounds(s_next, b_next);
 #pragma unroll
             for (int it = 0; it < IT; it++) {
-              if (it == kHalf) p.load_ids(sub_of(j + 1), b_next, i_next);
+              if (it == kHalf) p.load_ids(s_next, b_next, i_next);
               if (it + kDepth - 1 < IT) p.issue(cur, it + kDepth - 1, buf[(it + kDepth - 1) % kDepth]);
               p.reduce_store(cur, it, buf[it % kDepth], rows_lds);
             }
             p.second_window(cur, rows_lds);
-            p.long_rows(sub_of(j), cur, rows_lds);
+            p.long_rows(s_cur, cur, rows_lds);
+            // (the ticket came back long ago: publishing it here, before the next rows are requested, waits for nothing)
+            if (sub == 1 && drawer) ring[r_draw()] = drawn;
             p.finish(i_next, cur);
-            if (j + 1 < 2 * mine) {
+            if (sub == 0 || t_next < n_tiles) {
 #pragma unroll
               for (int it = 0; it < kDepth - 1; it++) p.issue(cur, it, buf[it]);
             }
           }
-        }
+        } else if (drawer) ring[r_draw()] = drawn;
         lds_barrier();
+        if (t_cur >= n_tiles) break;
+        advance(t_next);
       }
     } else {
       constexpr int RT = TR / 32;
@@ -372,9 +408,10 @@ sage_layer_mfma_kernel(mfma_args a)
         load_b_planes(b[1], b_lane, (int64_t)a.KS * a.N * 8, a.N, 1);
       }
       const IdT* src_ids = static_cast<const IdT*>(a.src_ids);
-      for (int64_t n = 0; n <= mine; n++) {
+      for (int n = 0;; n++) {
+        const uint32_t t_next = ring_at(r_next);
         if (n >= 1 && !(a.debug & 1)) {
-          const int64_t row0 = tile_of(n - 1) * TR;
+          const int64_t row0 = (int64_t)t_prev * TR;
           // this lane's self row of every row tile (rows past the end: any row, never stored); the two dependent loads
           // are requested here and waited for after the mean half
           const float* self_ptr[RT];
@@ -405,6 +442,8 @@ sage_layer_mfma_kernel(mfma_args a)
           epilogue<RT>(a, c, row0, wave, lane, scratch);
         }
         lds_barrier();
+        if (t_cur >= n_tiles) break;
+        advance(t_next);
       }
     }
   } else if (wave >= CW) {
@@ -421,35 +460,42 @@ sage_layer_mfma_kernel(mfma_args a)
     meta_t<IT, off_t> cur;
     f32x4 buf[kDepth][kNb + 1];
     {
-      p.load_bounds(tile_of(0), b_next);
-      p.load_ids(tile_of(0), b_next, i_next);
+      p.load_bounds(t_cur, b_next);
+      p.load_ids(t_cur, b_next, i_next);
       p.finish(i_next, cur);
     }
 #pragma unroll
     for (int it = 0; it < kDepth - 1; it++) p.issue(cur, it, buf[it]);
     constexpr int kHalf = IT / 2;
-    for (int64_t n = 0; n <= mine; n++) {
+    for (int n = 0;; n++) {
       stamp(n, 0);
-      if (n < mine && !(a.debug & 2)) {
+      const uint32_t t_next = ring_at(r_next);
+      uint32_t drawn       = kNoTile;
+      if (drawer && t_cur < n_tiles) drawn = draw(t_next);   // the tile of step n + 2, published below
+      if (t_cur < n_tiles && !(a.debug & 2)) {
         float* tile_lds = lds + (n & 1) * tile_dw;
-        p.load_bounds(tile_of(n + 1), b_next);
+        p.load_bounds(t_next, b_next);
 #pragma unroll
         for (int it = 0; it < IT; it++) {
-          if (it == kHalf) p.load_ids(tile_of(n + 1), b_next, i_next);
+          if (it == kHalf) p.load_ids(t_next, b_next, i_next);
           if (it + kDepth - 1 < IT) p.issue(cur, it + kDepth - 1, buf[(it + kDepth - 1) % kDepth]);
           p.reduce_store(cur, it, buf[it % kDepth], tile_lds);
         }
         p.second_window(cur, tile_lds);
-        p.long_rows(tile_of(n), cur, tile_lds);
-        // offsets of tile n+1, and its first rows in flight BEFORE the barrier
+        p.long_rows(t_cur, cur, tile_lds);
+        // (the ticket came back long ago: publishing it here, before the next rows are requested, waits for nothing)
+        if (drawer) ring[r_draw()] = drawn;
+        // offsets of the next tile, and its first rows in flight BEFORE the barrier
         p.finish(i_next, cur);
-        if (n + 1 < mine) {
+        if (t_next < n_tiles) {
 #pragma unroll
           for (int it = 0; it < kDepth - 1; it++) p.issue(cur, it, buf[it]);
         }
-      }
+      } else if (drawer) ring[r_draw()] = drawn;
       stamp(n, 1);
       lds_barrier();
+      if (t_cur >= n_tiles) break;
+      advance(t_next);
     }
   } else {
     if (a.debug & 32) __builtin_amdgcn_s_setprio(3);
@@ -463,33 +509,45 @@ sage_layer_mfma_kernel(mfma_args a)
       // under the other wave's MFMAs instead of both idling the pipe together.
       const bool late = (wave & 1) && !(a.debug & 128);
       int64_t pending = -1;
-      for (int64_t n = 0; n <= mine; n++) {
+      for (int n = 0;; n++) {
         stamp(n, 0);
+        const uint32_t t_next = ring_at(r_next);
         if (n >= 1 && !(a.debug & 1)) {
           const float* tile_lds = lds + ((n - 1) & 1) * tile_dw;
-          store_agg<TR, CW>(a, tile_lds, tile_of(n - 1) * TR, wave, lane);
+          store_agg<TR, CW>(a, tile_lds, (int64_t)t_prev * TR, wave, lane);
           if (late) {
             if (pending >= 0) cons.store(a, pending, wave, lane, scratch);
             cons.multiply(a, tile_lds, lane);
-            pending = tile_of(n - 1);
+            pending = t_prev;
           } else {
             cons.multiply(a, tile_lds, lane);
-            cons.store(a, tile_of(n - 1), wave, lane, scratch);
+            cons.store(a, t_prev, wave, lane, scratch);
           }
         }
         stamp(n, 1);
         lds_barrier();
+        if (t_cur >= n_tiles) break;
+        advance(t_next);
       }
       if (late && pending >= 0) cons.store(a, pending, wave, lane, scratch);
     } else {
-      for (int64_t n = 0; n <= mine; n++) {
+      for (int n = 0;; n++) {
+        const uint32_t t_next = ring_at(r_next);
         if (n >= 1 && !(a.debug & 1)) {
-          store_agg<TR, CW>(a, lds + ((n - 1) & 1) * tile_dw, tile_of(n - 1) * TR, wave, lane);
-          consume_tile<TR>(a, tile_of(n - 1), lds + ((n - 1) & 1) * tile_dw, wave, lane, scratch);
+          store_agg<TR, CW>(a, lds + ((n - 1) & 1) * tile_dw, (int64_t)t_prev * TR, wave, lane);
+          consume_tile<TR>(a, t_prev, lds + ((n - 1) & 1) * tile_dw, wave, lane, scratch);
         }
         lds_barrier();
+        if (t_cur >= n_tiles) break;
+        advance(t_next);
       }
     }
+  }
+  // Every ticket this workgroup drew came back before one of the barriers above.  The last workgroup to leave therefore
+  // leaves after every draw of the launch, and rewinds the slot for the next launch (or graph replay) that uses it.
+  if (threadIdx.x == 0 && atomicAdd(a.tickets + 1, 1u) == gridDim.x - 1) {
+    atomicExch(a.tickets, 0u);
+    atomicExch(a.tickets + 1, 0u);
   }
 }
 
@@ -565,6 +623,57 @@ __global__ void layer_weight_kernel(const float* __restrict__ w_l, int64_t ldl, 
   }
 }
 
+// ---- ticket slots ------------------------------------------------------------------------------------------------------
+// A launch hands out its tiles through a slot of two words in device memory: {tickets drawn, workgroups gone}.  Both are zero
+// between launches — the pool is zeroed when it is allocated and the last workgroup of a launch rewinds its slot — so no
+// launch needs a memset in front of it and a captured launch replays from zero with the slot's address baked into the graph.
+// Two launches may use one slot only if the first has ended when the second starts.  A slot therefore belongs to ONE
+// (device, stream) — a stream runs its kernels one after the other — and, under stream capture, to one (capture, stream):
+// the nodes a capture records from one stream form a chain, parallel branches come from different streams, and a graph may
+// be replayed on any stream next to eager launches or other graphs, so it never shares with them.  Slots are never handed
+// back: 8 bytes per stream ever used and per stream of every capture, carved from 4 KiB blocks.
+constexpr int kSlotsPerBlock = 512;
+__host__ inline uint32_t* ticket_slot(hipStream_t st)
+{
+  struct key_t {
+    int dev;
+    hipStream_t st;
+    unsigned long long capture;
+    bool operator<(const key_t& o) const { return std::tie(dev, st, capture) < std::tie(o.dev, o.st, o.capture); }
+  };
+  struct block_t {
+    uint32_t* base;
+    int used;
+  };
+  static std::mutex m;
+  static std::map<key_t, uint32_t*> slot_of;
+  static std::map<int, block_t> block_of;   // the block being carved, per device
+  key_t key{0, st, 0};
+  WG_HIP_CHECK(hipGetDevice(&key.dev));
+  hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+  if (st != nullptr) WG_HIP_CHECK(hipStreamGetCaptureInfo(st, &status, &key.capture));
+  if (status != hipStreamCaptureStatusActive) key.capture = 0;
+  std::lock_guard<std::mutex> g(m);
+  auto it = slot_of.find(key);
+  if (it != slot_of.end()) return it->second;
+  block_t& b = block_of[key.dev];
+  if (b.base == nullptr || b.used == kSlotsPerBlock) {
+    // (a capture in progress on this thread must not see the allocation: relaxed mode for its duration, as allocators do)
+    hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+    WG_HIP_CHECK(hipThreadExchangeStreamCaptureMode(&mode));
+    void* p             = nullptr;
+    const hipError_t e1 = hipMalloc(&p, kSlotsPerBlock * 2 * sizeof(uint32_t));
+    const hipError_t e2 = e1 == hipSuccess ? hipMemset(p, 0, kSlotsPerBlock * 2 * sizeof(uint32_t)) : e1;
+    WG_HIP_CHECK(hipThreadExchangeStreamCaptureMode(&mode));
+    WG_HIP_CHECK(e1);
+    WG_HIP_CHECK(e2);
+    b = block_t{static_cast<uint32_t*>(p), 0};
+  }
+  uint32_t* slot = b.base + 2 * b.used++;
+  slot_of.emplace(key, slot);
+  return slot;
+}
+
 constexpr size_t kLdsBudget = 160 * 1024;
 __host__ inline size_t lds_bytes(int F, int TR) { return (size_t)(2 * TR * row_stride_dw(F) + 16 + 4 * kScratchDw + 16) * 4; }
 __host__ inline size_t lds_bytes_half(int F) { return (size_t)(2 * 64 * row_stride_half_dw(F) + 16 + 4 * kScratchDw + 16) * 4; }
@@ -579,6 +688,7 @@ template <typename IdT, int LG, int CW>
 void launch_half(mfma_args a, hipStream_t st)
 {
   const int cus         = stream_cu_count(st);
+  a.tickets             = ticket_slot(st);
   a.SD                  = row_stride_half_dw(a.F);
   const int64_t n_tiles = (a.n_rows + 63) / 64;
   const size_t lds      = lds_bytes_half(a.F);
@@ -593,9 +703,10 @@ void launch_half(mfma_args a, hipStream_t st)
 }
 
 template <typename IdT, int LG, int TR, int CW, int FC = 0>
-void launch(const mfma_args& a, hipStream_t st)
+void launch(mfma_args a, hipStream_t st)
 {
   const int cus         = stream_cu_count(st);
+  a.tickets             = ticket_slot(st);
   const int64_t n_tiles = (a.n_rows + TR - 1) / TR;
   const size_t lds      = lds_bytes(a.F, TR) + (FC > 0 && TR == 64 ? (size_t)w_lds_ksteps(FC) * CW * 64 * 64 : 0);
   // ONE workgroup per CU: the SIMD role split needs the CU to itself (two waves per SIMD)
@@ -734,6 +845,7 @@ extern "C" wholememory_error_code_t wgamd_sage_layer_fused_bf16x3_train(const in
     if (!wgamd_sage_layer_bf16x3_supported(F, N) || ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(x) & 15) != 0)
       throw logic_error(fmt("unsupported shape: F=%d (multiple of 4, <= 256), N=%d (64, 128 or 256), 16-B aligned rows", F, N));
     WG_REQUIRE_INPUT(ldo >= N, "leading dimension smaller than N");
+    WG_REQUIRE_INPUT(n_rows < ((int64_t)1 << 36), "too many rows for 32-bit tile numbers");
     if (ldo % 4 != 0 || (reinterpret_cast<uintptr_t>(out) & 15) != 0) throw logic_error("output rows must be 16-B aligned");
     if (agg_out != nullptr && (ld_agg < F || ld_agg % 4 != 0 || (reinterpret_cast<uintptr_t>(agg_out) & 15) != 0))
       throw logic_error("agg_out rows must hold F floats and be 16-B aligned");

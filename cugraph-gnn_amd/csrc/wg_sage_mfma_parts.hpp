@@ -3,6 +3,9 @@
 #pragma once
 #include <algorithm>
 #include <cstdlib>
+#include <map>
+#include <mutex>
+#include <tuple>
 #include <type_traits>
 
 #include "wg_common.hpp"
@@ -23,6 +26,7 @@ using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 #define WG_MFMA_DEPTH 2   // destination rows in flight per producer lane group
 #endif
 constexpr int kProducerWaves = 4;
+constexpr uint32_t kNoTile   = 0xffffffffu;   // tile hand-out: "no tile left" (any number >= the tile count says the same)
 constexpr int kRingDepth     = WG_MFMA_DEPTH;
 
 template <typename IdT>
@@ -61,6 +65,8 @@ struct mfma_args {
   int64_t ld_agg;            // kernel (wg_sage_bwd.hip) reads them back instead of fetching every neighbour row a second time
   int full_tiles;            // host side only: w_tiles holds fp32 tiles and the launch takes whole 32-row tiles even where F
                              // would take 64-row half tiles (relu flag WGAMD_SAGE_FULL_TILES: a small launch, see wgamd_ext.h)
+  uint32_t* tickets;         // {tickets drawn, workgroups gone} of this launch, both zero when it starts (filled in by the launch
+                             // helpers: ticket_slot in wg_sage_mfma.hip)
 };
 
 // a == hi + mid + lo exactly; every piece has <= 8 significant bits, i.e. is a bf16 (the top half of the fp32 word)
