@@ -696,11 +696,13 @@ wholememory_error_code_t wgamd_rows_terms_bwd_f32(const float* x, int64_t ldx, i
  *                                   range-partitioned table); capacity min(n, id_bound) entries
  *   inverse[i]                      position of ids[i] in `distinct`; -1 for a negative id (a row to skip) and for an id
  *                                   >= id_bound (then *out_of_bound_dev = 1, nullable)
- * Mark -> scan over the bound -> compact -> look up: no sort, no hash table, no host synchronisation.
+ * Mark -> scan over the bound -> compact -> look up: no sort, no hash table, no host synchronisation (csrc/wg_unique.hip).
  * Used by the partitioned FeatureStore to send each distinct row of a call group over xGMI ONCE
  * (wholegraph_amd/tensor.py, DistributedWholeMemoryTensor.gather(dedup=...)): the reference's
  * wholememory_gather_nccl exchanges every requested id (/root/reference/cpp/src/wholememory_ops/gather_op_impl_nccl.cu:23-171).
- * Workspace: wgamd_unique_bounded_workspace_bytes(id_bound) (0 = bound not supported: must be in (0, 2^31 - 4096)), 256-byte aligned. */
+ * Workspace: wgamd_unique_bounded_workspace_bytes(id_bound) (0 = bound not supported: must be in (0, 2^31 - 4096)), 256-byte aligned:
+ * about 1.4 bytes per possible id, plus — for bounds up to 2^23, whose marks are kept as bits in LDS — the workgroups' bit slabs,
+ * up to 256 x 128 KB = 32 MB.  Always ask; the size depends on the bound only, never on n. */
 size_t wgamd_unique_bounded_workspace_bytes(int64_t id_bound);
 wholememory_error_code_t wgamd_unique_bounded(const void* ids, wholememory_dtype_t id_dtype, int64_t n, int64_t id_bound,
                                               int64_t* distinct, int* inverse, int* n_distinct_dev, int* out_of_bound_dev,
