@@ -453,6 +453,9 @@ extern "C" wholememory_error_code_t wgamd_sage_wgrad_bf16x3(const float* agg, in
     if (src_ids != nullptr && src_ids_dtype != WHOLEMEMORY_DT_INT && src_ids_dtype != WHOLEMEMORY_DT_INT64 && !byte_offsets)
       throw invalid_input("src_ids must be INT, INT64 or WGAMD_IDS_BYTE_OFFSETS");
     const wgrad_plan p = plan_for(F, N);
+    // agg, grad_out and act_out are read per tile of up to 64 rows through a buffer resource, 32-bit byte offsets from its first row
+    WG_REQUIRE_INPUT(std::max({ld_agg, ldg, act_out ? ld_act : (int64_t)0}) < ((int64_t)1 << 24),
+                     "row stride too large: 64 rows of agg / grad_out / act_out must span less than 4 GiB");
     const int cus      = stream_cu_count(st);
     const int64_t tiles = (n_rows + p.TR - 1) / p.TR;
     // every workgroup leaves a [2F + 1, N] partial sum that wgrad_reduce_kernel adds up: with few row tiles (one mini-batch:

@@ -623,7 +623,9 @@ wholememory_error_code_t wgamd_sage_layer_fused_bf16x3_train(const int* row_ptr,
  * workgroup owns a contiguous range of rows, keeps its [2F, N] partial sum in registers and writes it once; the partial sums
  * are added in workgroup order by a second launch — no atomics, the same bits from run to run.
  * Shapes: F % 4 == 0, F <= 256, N <= 256; x / agg rows 16-B aligned.  workspace: wgamd_sage_wgrad_workspace_bytes(n_rows, F, N)
- * bytes of device scratch (0 = shape not supported). */
+ * bytes of device scratch (0 = shape not supported).  Extents: x of any size (64-bit row offsets, every id kind); agg, grad_out
+ * and act_out anywhere, any n_rows, but a tile of rows is read with 32-bit offsets from its first row: a row stride (ld_agg, ldg,
+ * ld_act) of 2^24 floats or more (64 rows spanning 4 GiB) is WHOLEMEMORY_INVALID_INPUT. */
 size_t wgamd_sage_wgrad_workspace_bytes(int64_t n_rows, int F, int N);
 wholememory_error_code_t wgamd_sage_wgrad_bf16x3(const float* agg, int64_t ld_agg, const float* x, int64_t ldx, int F,
                                                  const void* src_ids, wholememory_dtype_t src_ids_dtype,

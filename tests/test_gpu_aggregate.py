@@ -237,7 +237,9 @@ def test_sage_layer_fused_rejects_unsupported_shapes(hiplib):
 
 
 def test_sage_layer_fused_64bit_offset_path_and_tiny_inputs(hiplib):
-    """x_rows = 0 (unknown extent) selects the 64-bit row-offset code path; it must agree bit-for-bit with the 32-bit one.
+    """x_rows = 0 (unknown extent) selects the 64-bit row-offset code path on a 3000-row table: the same bits as the 32-bit
+    path, but every offset's high word is zero here — offsets past 2^31 and 2^32 bytes, where the high word counts, are checked
+    in tests/test_gpu_far_offsets.py (test_sage_layer_band_rows_at_three_extents).
     Also: fewer rows than one 64-row tile, a single row, int32 id indirection."""
     import torch
     from wholegraph_amd import _lib as L
