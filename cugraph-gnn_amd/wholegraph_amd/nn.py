@@ -17,6 +17,12 @@ graph's hops with their row and edge slices; the sum of the hops' input gradient
 tensor or ``LazyRows`` input as the kernels read it), ``_padded_wt`` / ``_pad_cols`` (the operands of an input gradient run as
 the layer kernel over ``HopGraph.transposed``), ``_dense_wgrad`` (``gcn_wgrad`` per hop: dW, db of a dense product), and
 ``_released`` (the RuntimeError of a second backward through a layer whose kept tensors the first one released).
+
+Shared by ``GATConv`` and the routes of ``HeteroConv`` over a call group: ``_table_through_ids`` (a ``LazyRows`` input the kernels
+may read in place through its node list) with ``_terms_by_id`` (whose attention terms are then the table's rows') and
+``_refuse_lazy_table_grad``; ``_sum_of`` (the relations' biases or root weights added up); ``_relation_groups`` /
+``_group_outputs`` / ``_place_rows`` (a heterogeneous layer graph's relations per (hop, destination type), the per-type float32
+outputs and a group's rows placed in them); ``HeteroConv._cached`` (every derived parameter keyed on the parameters it is built from).
 """
 import math
 from typing import Optional, Tuple, Union
@@ -275,7 +281,7 @@ def sage_layer_small_launch(F_: int, n_rows: int) -> bool:
 
 
 def sage_layer_planes(w_l: torch.Tensor, w_r: torch.Tensor, bias, Np: int, full_tiles: bool = False):
-    """``(planes, padded bias, N)`` of a layer straight from its ``torch.nn.Linear`` parameters in ONE launch
+    """``(planes, padded bias, N, full_tiles)`` of a layer straight from its ``torch.nn.Linear`` parameters in ONE launch
     (``wgamd_sage_layer_weight_planes``) — what ``sage_layer_fused_forward(prepared=...)`` takes instead of deriving the
     transposed / padded / split forms with half a dozen framework launches.  Not cached: made for captured training steps,
     whose weights change on every replay."""
@@ -1182,6 +1188,42 @@ def _kernel_rows_ok(t) -> bool:
     return (t.dtype == torch.float32 and t.is_cuda and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0)
 
 
+def _table_through_ids(x):
+    """``(table, ids)`` when the kernels may read the ``LazyRows`` input ``x`` in place through its node list — a tensor table
+    that is ``_kernel_rows_ok``, int64 ids, rows not gathered yet —, None otherwise (the caller works on ``materialize()``)."""
+    if isinstance(x, LazyRows) and isinstance(x.table, torch.Tensor) and x.ids.dtype == torch.int64 and _kernel_rows_ok(x.table) \
+            and x._rows is None:
+        return x.table, x.ids
+    return None
+
+
+def _terms_by_id(rows_of_table: int, listed_rows: int) -> bool:
+    """The attention terms of a table read through a node list are those of the TABLE's rows, which the relation kernels read
+    through the list, when the table is at most half as long as the list: a call group lists a table row once per mini-batch
+    that sampled it, so a short table's terms cost fewer rows than the list's (made in every call, nothing kept between calls)."""
+    return 2 * rows_of_table <= listed_rows
+
+
+def _lazy_table_grad_error():
+    """What a gradient into a feature table read through ids is refused with."""
+    return NotImplementedError("gradient w.r.t. a feature table read through ids (LazyRows): trainable node "
+                               "embeddings go through wholegraph_amd.embedding, or pass x = emb[n_id]")
+
+
+def _refuse_lazy_table_grad(table):
+    """NotImplementedError when autograd is on and ``table``, the table of a ``LazyRows`` input, requires a gradient."""
+    if torch.is_grad_enabled() and getattr(table, "requires_grad", False):
+        raise _lazy_table_grad_error()
+
+
+def _sum_of(tensors):
+    """The sum of same-shaped tensors (the biases or root weights of the relations ending in a node type): None for none, the
+    tensor itself for one, ``torch.stack(..).sum(0)`` otherwise — one reduction, not chained adds: the bits depend on it."""
+    if len(tensors) < 2:
+        return tensors[0] if tensors else None
+    return torch.stack(tensors).sum(0)
+
+
 def _layer_input(layer, x, lg: LayerGraph, F_: int):
     """The input of a layer over ``lg`` as the one-kernel layers take it: ``(src, ids, n_src, n_edges)`` — the rows the kernel
     reads (a ``LazyRows`` input: its table), the node list it reads them through (None: by row), the input's row count, and the
@@ -1192,9 +1234,8 @@ def _layer_input(layer, x, lg: LayerGraph, F_: int):
     if x.shape[1] != F_:
         raise ValueError("%s: x has %d features, the layer takes %d" % (type(layer).__name__, x.shape[1], F_))
     src = x.table if lazy else x
-    if lazy and torch.is_grad_enabled() and getattr(src, "requires_grad", False):
-        raise NotImplementedError("gradient w.r.t. a feature table read through ids (LazyRows): trainable node "
-                                  "embeddings go through wholegraph_amd.embedding, or pass x = emb[n_id]")
+    if lazy:
+        _refuse_lazy_table_grad(src)
     total = getattr(lg, "num_group_edges", None)
     n_edges = total if total is not None else sum(int(h.col.shape[0]) for h in lg.hops)
     return src, (x.ids if lazy else None), (len(x) if lazy else x.shape[0]), n_edges
@@ -1271,8 +1312,7 @@ def _sage_layer_launch(ctx, src, w_l, w_r, bias, conv, graph, ids, relu, mean):
     out = buf[:, :N]
     if keep:
         if ctx.needs_input_grad[0] and ids is not None:
-            raise NotImplementedError("gradient w.r.t. a feature table read through ids (LazyRows): trainable node "
-                                      "embeddings go through wholegraph_amd.embedding")
+            raise _lazy_table_grad_error()
         if isinstance(src, torch.Tensor):
             ctx.save_for_backward(src, w_l, w_r, out)
         else:                                     # (a MappedTable: an address space, not a tensor)
@@ -1464,12 +1504,10 @@ class GATConv(torch.nn.Module):
         code trains (``wgamd_gat_aggregate_heads_bwd_f32``)."""
         assert act in (None, "relu")
         H, C, F_ = self.heads, self.out_channels, self.in_channels
-        lazy = isinstance(x, LazyRows) and isinstance(x.table, torch.Tensor) and x.ids.dtype == torch.int64 \
-            and x.table.dtype == torch.float32 and x.table.stride(1) == 1 and x.table.stride(0) % 4 == 0 \
-            and x.table.data_ptr() % 16 == 0 and x._rows is None
-        if lazy:
-            X, ids = x.table, x.ids
-            by_id = 2 * X.shape[0] <= len(x)
+        lazy = _table_through_ids(x)
+        if lazy is not None:
+            X, ids = lazy
+            by_id = _terms_by_id(X.shape[0], len(x))
             rows = X if by_id else x.materialize()
         else:
             X = x.materialize() if isinstance(x, LazyRows) else x
@@ -3010,6 +3048,30 @@ class HeteroLayerGraph:
         return sum(r.n_edges for r in self.relations)
 
 
+def _relation_groups(graph: HeteroLayerGraph):
+    """``[((hop, dst_type), [RelationHop, ...]), ...]`` sorted by hop, then type: the relation hops of a layer graph that add up
+    to the same output rows (in the graph's order; they share ``n_rows``, ``dst_rows`` and ``out_rows``)."""
+    groups = {}
+    for r in graph.relations:
+        groups.setdefault((r.hop, r.edge_type[2]), []).append(r)
+    return sorted(groups.items(), key=lambda kv: kv[0])
+
+
+def _group_outputs(graph: HeteroLayerGraph, groups, width, device, make=torch.empty):
+    """``{type: make([n_out, width(type)])}`` float32 for the node types some group of ``groups`` ends in."""
+    ends = {dt for (_, dt), _ in groups}
+    return {t: make((n, width(t)), dtype=torch.float32, device=device) for t, n in graph.n_out.items() if n > 0 and t in ends}
+
+
+def _place_rows(out, dt, y, out_rows):
+    """The rows ``y`` of one group in the output of type ``dt``: the output itself (``out_rows`` None: row j is output row j), or
+    copied to ``out_rows`` in place — the hops of a type write disjoint rows of one buffer."""
+    if out_rows is None:
+        out[dt] = y
+    else:
+        out[dt].index_copy_(0, out_rows, y)
+
+
 from .pool import GrowOnlyPool  # noqa: E402
 
 _agg_pool = GrowOnlyPool()
@@ -3025,8 +3087,7 @@ class _NarrowTerms(torch.autograd.Function):
     def forward(ctx, x, v):
         v = v.contiguous()
         F_, T = int(v.shape[0]), int(v.shape[1])
-        fast = x.dtype == torch.float32 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 \
-            and gather_terms_supported(F_, T)
+        fast = _kernel_rows_ok(x) and gather_terms_supported(F_, T)
         terms = rows_terms(x, v) if fast and x.shape[0] > 0 else x @ v
         ctx.save_for_backward(x, v)
         return terms
@@ -3337,23 +3398,28 @@ class HeteroConv(torch.nn.Module):
         return self.convs["__".join(edge_type)]
 
     # ---- parameters in the form the kernels read -----------------------------------------------------------------------
+    def _cached(self, name, params, build):
+        """``build()`` (run without autograd), kept under ``name`` for as long as ``params`` — every parameter it is built from —
+        are what they were: same storage, same version, and no ``bump_weight_generation`` since."""
+        key = tuple((p._version, p.data_ptr()) for p in params) + (_weights_gen,)
+        hit = self._folded.get(name)
+        if hit is None or hit[0] != key:
+            with torch.no_grad():
+                hit = (key, build())
+            self._folded[name] = hit
+        return hit[1]
+
     def _rel(self, et):
         """(w [in, H C] contiguous, fold(w, att_src) [in, H], fold(w, att_dst) [in, H]) of a relation, rebuilt when a parameter
         changed: ``alpha_src = ((x W).view(H, C) * att).sum(-1) = x (W . att)``."""
         c = self.conv(et)
-        key = tuple((p._version, p.data_ptr()) for p in (c.lin.weight, c.att_src, c.att_dst) + ((c.bias,) if c.bias is not None else ())) \
-            + (_weights_gen,)
-        hit = self._folded.get(et)
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                w = c.lin.weight.t().contiguous()
-                w3 = w.view(w.shape[0], c.heads, c.out_channels)
-                hit = (key, w, (w3 * c.att_src.view(1, c.heads, c.out_channels)).sum(-1).contiguous(),
-                       (w3 * c.att_dst.view(1, c.heads, c.out_channels)).sum(-1).contiguous())
-            self._folded[et] = hit
-            self._folded.pop(("terms", et[0]), None), self._folded.pop(("terms", et[2]), None)
-            self._folded.pop(("bias", et[2]), None)
-        return hit[1:]
+
+        def build():
+            w = c.lin.weight.t().contiguous()
+            w3 = w.view(w.shape[0], c.heads, c.out_channels)
+            return (w, (w3 * c.att_src.view(1, c.heads, c.out_channels)).sum(-1).contiguous(),
+                    (w3 * c.att_dst.view(1, c.heads, c.out_channels)).sum(-1).contiguous())
+        return self._cached(et, (c.lin.weight, c.att_src, c.att_dst), build)
 
     def _term_keys(self, t):
         keys = []
@@ -3366,34 +3432,29 @@ class HeteroConv(torch.nn.Module):
 
     def _terms_matrix(self, t):
         """[in, H x relation ends of node type t]: the folded attention vectors of every relation end reading type t."""
-        mats = [self._rel(et)[1 if end == "src" else 2] for end, et in self._term_keys(t)]      # (refreshes stale folds first)
-        hit = self._folded.get(("terms", t))
-        if hit is None:
-            hit = torch.cat(mats, 1).contiguous() if mats else None
-            self._folded[("terms", t)] = hit
-        return hit
+        ends = self._term_keys(t)
+        convs = [self.conv(et) for et in self.edge_types if t in (et[0], et[2])]
+
+        def build():
+            mats = [self._rel(et)[1 if end == "src" else 2] for end, et in ends]
+            return torch.cat(mats, 1).contiguous() if mats else None
+        return self._cached(("terms", t), [p for c in convs for p in (c.lin.weight, c.att_src, c.att_dst)], build)
 
     def _bias(self, dt):
         """Sum of the biases of the relations ending in ``dt`` (HeteroConv adds the relations' outputs, bias included)."""
         rels = [et for et in self.edge_types if et[2] == dt]
         if rels and all(isinstance(self.conv(et), SAGEConv) for et in rels):
             return self._sage_weights(dt)[1]
-        for et in rels:
-            self._rel(et)
-        hit = self._folded.get(("bias", dt))
-        if hit is None:
-            bs = [self.conv(et).bias.detach() for et in rels if self.conv(et).bias is not None]
-            hit = (torch.stack(bs).sum(0).contiguous() if bs else None,)
-            self._folded[("bias", dt)] = hit
-        return hit[0]
+        bs = [self.conv(et).bias for et in rels if self.conv(et).bias is not None]
+        return self._cached(("bias", dt), bs, lambda: _sum_of([b.detach() for b in bs]))
 
     # ---- call-group layer ----------------------------------------------------------------------------------------------
     def _attention_terms(self, xs, graph):
-        """-> (x tensors, a_src{et}, a_dst{et}): ``x_t @ [fold(W_r, att_src) | fold(W_r, att_dst) ...]`` in ONE pass over the
-        rows of every node type — inside the row gather for a ``LazyRows`` input, a streaming pass over a resident one."""
+        """-> (x tensors, a_src{et}, a_dst{et}, by_id): ``x_t @ [fold(W_r, att_src) | fold(W_r, att_dst) ...]`` in ONE pass over
+        the rows of every node type — inside the row gather for a ``LazyRows`` input, a streaming pass over a resident one.
+        ``by_id``: the node types whose terms are those of the TABLE's rows (``_terms_by_id``)."""
         from .tensor import local_gather
-        x, a_src, a_dst = {}, {}, {}
-        self._by_id = set()          # node types whose terms are those of the TABLE's rows (read through the node list)
+        x, a_src, a_dst, by_id = {}, {}, {}, set()
         for t in graph.node_types:
             v = xs.get(t)
             if v is None:
@@ -3405,14 +3466,11 @@ class HeteroConv(torch.nn.Module):
             if isinstance(v, LazyRows):
                 n, F_ = len(v), v.table.shape[1]
                 terms_ok = vt is not None and n > 0 and H == 4 and v.table.dtype == torch.float32 and gather_terms_supported(F_, vt.shape[1])
-                if self.fetch_in_layer and terms_ok and v.ids.dtype == torch.int64 and isinstance(v.table, torch.Tensor) \
-                        and v._rows is None and v.table.stride(1) == 1 and v.table.stride(0) % 4 == 0 and v.table.data_ptr() % 16 == 0:
+                if self.fetch_in_layer and terms_ok and _table_through_ids(v) is not None:
                     x[t] = v
-                    if 2 * v.table.shape[0] <= n:
-                        # the group lists a table row once per mini-batch that sampled it: terms of the TABLE's rows (made in
-                        # every call: nothing is kept between calls), which the relation kernels read through the node lists
+                    if _terms_by_id(v.table.shape[0], n):
                         slabs = _stage("attn_terms(table)" + self.stage_tag, lambda: rows_terms(v.table, vt, heads=4))
-                        self._by_id.add(t)
+                        by_id.add(t)
                     else:
                         slabs = _stage("attn_terms(lazy)" + self.stage_tag, lambda: lazy_rows_terms(v.table, v.ids, vt, heads=4))
                     for k, (dst, et) in enumerate(keys):
@@ -3429,30 +3487,23 @@ class HeteroConv(torch.nn.Module):
                 continue
             if slabs is None:
                 xt = x[t]
-                if H == 4 and xt.stride(1) == 1 and xt.stride(0) % 4 == 0 and xt.data_ptr() % 16 == 0 \
-                        and gather_terms_supported(int(xt.shape[1]), int(vt.shape[1])):
+                if H == 4 and _kernel_rows_ok(xt) and gather_terms_supported(int(xt.shape[1]), int(vt.shape[1])):
                     slabs = _stage("attn_terms" + self.stage_tag, lambda: rows_terms(xt, vt, heads=4))
                 else:
                     both = _stage("attn_terms" + self.stage_tag, lambda: xt @ vt)
                     slabs = both.view(both.shape[0], len(keys), H).permute(1, 0, 2).contiguous()
             for k, (dst, et) in enumerate(keys):
                 dst[et] = slabs[k]
-        return x, a_src, a_dst
+        return x, a_src, a_dst, by_id
 
     def _forward_layer(self, xs, graph: HeteroLayerGraph, act=None):
         assert act in (None, "relu")
         relu = act == "relu"
-        x, a_src, a_dst = self._attention_terms(xs, graph)
+        x, a_src, a_dst, by_id = self._attention_terms(xs, graph)
         dev = next(iter(x.values())).device
-        out = {}
-        groups = {}
-        listed = set()
-        for r in graph.relations:
-            groups.setdefault((r.hop, r.edge_type[2]), []).append(r)
-        for t, n in graph.n_out.items():
-            if n > 0 and any(dt == t for _, dt in groups):
-                out[t] = torch.empty((n, self._width(t)), dtype=torch.float32, device=dev)
-        for (hop, dt), mine in sorted(groups.items(), key=lambda kv: (kv[0][0], kv[0][1])):
+        groups, listed = _relation_groups(graph), set()
+        out = _group_outputs(graph, groups, self._width, dev)
+        for (hop, dt), mine in groups:
             n_f, HC = mine[0].n_rows, self._width(dt)
             if n_f == 0:
                 continue
@@ -3473,10 +3524,10 @@ class HeteroConv(torch.nn.Module):
                 ids, through = None, {}
                 if isinstance(xsrc, LazyRows):      # fetch in the layer: the kernels read the table through the node list
                     xsrc, ids = xsrc.table, xsrc.ids
-                    through = dict(src_ids=ids, src_terms_by_id=et[0] in self._by_id)
-                    if et[2] in self._by_id:
+                    through = dict(src_ids=ids, src_terms_by_id=et[0] in by_id)
+                    if et[2] in by_id:
                         through.update(dst_ids=x[et[2]].ids, dst_terms_by_id=True)
-                elif et[2] in self._by_id and et not in listed:
+                elif et[2] in by_id and et not in listed:
                     # (terms of the destination TABLE's rows next to a resident source: per-list terms, made once per edge type —
                     #  the relation runs in several hops)
                     a_dst[et] = gather_term_slabs(a_dst[et].unsqueeze(0), x[et[2]].ids)[0]
@@ -3543,23 +3594,16 @@ class HeteroConv(torch.nn.Module):
         built by torch ops on the parameters (autograd hands each relation its slice and every ``lin_r`` the shared root
         gradient); otherwise detached and cached against the parameters' versions."""
         convs = [self.conv(et) for et in self.edge_types if et[2] == dt]
-        ps = [p for c in convs for p in c.parameters()]
-        key = tuple((p._version, p.data_ptr()) for p in ps) + (_weights_gen,)
-        hit = self._folded.get(("sage", dt))
-        if not grad and hit is not None and hit[0] == key:
-            return hit[1:]
-        with torch.set_grad_enabled(grad):
-            roots = [c.lin_r.weight for c in convs if c.lin_r is not None]
-            parts = [c.lin_l.weight for c in convs]
-            if roots:
-                parts.append(roots[0] if len(roots) == 1 else torch.stack(roots).sum(0))
-            wstack = torch.cat(parts, 1)
-            bs = [c.lin_l.bias for c in convs if c.lin_l.bias is not None]
-            bias = None if not bs else (bs[0] if len(bs) == 1 else torch.stack(bs).sum(0))
-        if not grad:
-            wstack, bias = wstack.detach(), None if bias is None else bias.detach()
-            self._folded[("sage", dt)] = (key, wstack, bias)
-        return wstack, bias
+
+        def build():
+            root = _sum_of([c.lin_r.weight for c in convs if c.lin_r is not None])
+            wstack = torch.cat([c.lin_l.weight for c in convs] + ([] if root is None else [root]), 1)
+            return wstack, _sum_of([c.lin_l.bias for c in convs if c.lin_l.bias is not None])
+        if grad:
+            with torch.enable_grad():
+                return build()
+        return self._cached(("sage", dt), [p for c in convs for p in c.parameters()],
+                            lambda: tuple(None if t is None else t.detach() for t in build()))
 
     def _forward_layer_sage(self, xs, graph: HeteroLayerGraph, act=None):
         """``HeteroConv({edge_type: SAGEConv})`` over a call group's layer graph: per (hop, destination type) the sum over the
@@ -3575,15 +3619,13 @@ class HeteroConv(torch.nn.Module):
         for t, v in xs.items():
             if v is None:
                 continue
+            lazy = _table_through_ids(v)
             if isinstance(v, LazyRows):
-                if torch.is_grad_enabled() and getattr(v.table, "requires_grad", False):
-                    raise NotImplementedError("gradient w.r.t. a feature table read through ids (LazyRows): trainable node "
-                                              "embeddings go through wholegraph_amd.embedding, or pass x = emb[n_id]")
-                if isinstance(v.table, torch.Tensor) and v.ids.dtype == torch.int64 and _kernel_rows_ok(v.table) and v._rows is None:
-                    X[t], ids[t] = v.table, v.ids
-                    continue
-                v = v.materialize()
-            X[t], ids[t] = v, None
+                _refuse_lazy_table_grad(v.table)
+            if lazy is not None:
+                X[t], ids[t] = lazy
+            else:
+                X[t], ids[t] = (v.materialize() if isinstance(v, LazyRows) else v), None
         convs = [self.conv(et) for et in self.edge_types]
         in_domain = all(c.aggr in ("mean", "sum", "add") and c.out_channels <= 256 for c in convs) and all(
             _kernel_rows_ok(v) and v.shape[1] % 4 == 0 and v.shape[1] <= HETERO_SAGE_MAX_K for v in X.values())
@@ -3593,14 +3635,10 @@ class HeteroConv(torch.nn.Module):
         needs_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
                                                   or any(ids[t] is None and v.requires_grad for t, v in X.items()))
         dev = next(iter(X.values())).device
-        groups = {}
-        for r in graph.relations:
-            groups.setdefault((r.hop, r.edge_type[2]), []).append(r)
-        make = torch.zeros if needs_grad else torch.empty
-        out = {t: make((n, self._width(t)), dtype=torch.float32, device=dev) for t, n in graph.n_out.items()
-               if n > 0 and any(dt == t for _, dt in groups)}
+        groups = _relation_groups(graph)
+        out = _group_outputs(graph, groups, self._width, dev, make=torch.zeros if needs_grad else torch.empty)
         weights = {}
-        for (hop, dt), mine in sorted(groups.items(), key=lambda kv: (kv[0][0], kv[0][1])):
+        for (hop, dt), mine in groups:
             n_f = mine[0].n_rows
             if n_f == 0:
                 continue
@@ -3640,11 +3678,7 @@ class HeteroConv(torch.nn.Module):
                 weights[dt] = self._sage_weights(dt, grad=needs_grad)
             wstack, bias = weights[dt]
             if needs_grad:
-                z = _HeteroSageGroup.apply(grp, wstack, bias, root_src, *srcs)
-                if place is None:
-                    out[dt] = z
-                else:
-                    out[dt].index_copy_(0, place, z)      # (in place: the hops of a type write disjoint rows of one buffer)
+                _place_rows(out, dt, _HeteroSageGroup.apply(grp, wstack, bias, root_src, *srcs), place)
             elif place is None:
                 out[dt] = grp.run(wstack, bias)
             else:
@@ -3655,11 +3689,8 @@ class HeteroConv(torch.nn.Module):
         """The same layer out of library ops in PyG's formulation, relation by relation, with ordinary autograd — what shapes
         outside the kernel's domain (F % 4 != 0, N > 256, other dtypes, CPU tensors, other aggregators) take; correctness only."""
         dev = next(iter(x.values())).device
-        groups = {}
-        for r in graph.relations:
-            groups.setdefault((r.hop, r.edge_type[2]), []).append(r)
         out = {}
-        for (hop, dt), mine in sorted(groups.items(), key=lambda kv: (kv[0][0], kv[0][1])):
+        for (hop, dt), mine in _relation_groups(graph):
             n_f = mine[0].n_rows
             if n_f == 0:
                 continue
@@ -3691,13 +3722,9 @@ class HeteroConv(torch.nn.Module):
                 y = o if y is None else y + o
             if relu:
                 y = torch.relu(y)
-            place = mine[0].out_rows
-            if place is None:
-                out[dt] = y
-            else:
-                if dt not in out:
-                    out[dt] = torch.zeros((graph.n_out[dt], y.shape[1]), dtype=y.dtype, device=dev)
-                out[dt] = out[dt].index_copy(0, place, y)
+            if mine[0].out_rows is not None and dt not in out:      # (whatever dtype the rows have: not ``_group_outputs``)
+                out[dt] = torch.zeros((graph.n_out[dt], y.shape[1]), dtype=y.dtype, device=dev)
+            _place_rows(out, dt, y, mine[0].out_rows)
         return out
 
     def _forward_layer_train(self, xs, graph: HeteroLayerGraph, act=None):
@@ -3713,12 +3740,11 @@ class HeteroConv(torch.nn.Module):
             if v is None:
                 continue
             ends = self._term_keys(t)
-            if isinstance(v, LazyRows) and isinstance(v.table, torch.Tensor) and v.ids.dtype == torch.int64 \
-                    and v.table.dtype == torch.float32 and v.table.stride(1) == 1 and v.table.stride(0) % 4 == 0 \
-                    and v.table.data_ptr() % 16 == 0 and v._rows is None:
-                X[t], ids[t] = v.table, v.ids
-                by_id[t] = 2 * v.table.shape[0] <= len(v)
-                rows = v.table if by_id[t] else None
+            lazy = _table_through_ids(v)
+            if lazy is not None:
+                X[t], ids[t] = lazy
+                by_id[t] = _terms_by_id(X[t].shape[0], len(v))
+                rows = X[t] if by_id[t] else None
             else:
                 X[t] = v.materialize() if isinstance(v, LazyRows) else v
                 ids[t], by_id[t], rows = None, False, X[t]
@@ -3736,12 +3762,9 @@ class HeteroConv(torch.nn.Module):
             for k, (end, et) in enumerate(ends):
                 terms[(end, et)] = both[:, k * H:(k + 1) * H]
         dev = next(iter(X.values())).device
-        groups = {}
-        for r in graph.relations:
-            groups.setdefault((r.hop, r.edge_type[2]), []).append(r)
-        out = {t: torch.zeros((n, self._width(t)), dtype=torch.float32, device=dev) for t, n in graph.n_out.items()
-               if n > 0 and any(dt == t for _, dt in groups)}
-        for (hop, dt), mine in sorted(groups.items(), key=lambda kv: (kv[0][0], kv[0][1])):
+        groups = _relation_groups(graph)
+        out = _group_outputs(graph, groups, self._width, dev, make=torch.zeros)
+        for (hop, dt), mine in groups:
             n_f = mine[0].n_rows
             if n_f == 0:
                 continue
@@ -3772,16 +3795,13 @@ class HeteroConv(torch.nn.Module):
                 acc = acc.reshape(n_f, -1)
             if acc is None:
                 acc = torch.zeros((n_f, self._width(dt)), dtype=torch.float32, device=dev)
-            bs = [self.conv(r.edge_type).bias for r in mine if self.conv(r.edge_type).bias is not None]
-            if bs:            # the relations' biases summed first: ONE pass over the rows (HeteroConv adds outputs, bias included)
-                acc = acc + (bs[0] if len(bs) == 1 else torch.stack(bs).sum(0))
+            # the relations' biases summed first: ONE pass over the rows (HeteroConv adds outputs, bias included)
+            bias = _sum_of([self.conv(r.edge_type).bias for r in mine if self.conv(r.edge_type).bias is not None])
+            if bias is not None:
+                acc = acc + bias
             if act == "relu":
                 acc = torch.relu(acc)
-            place = mine[0].out_rows
-            if place is None:
-                out[dt] = acc
-            else:
-                out[dt].index_copy_(0, place, acc)      # (in place: the hops of a type write disjoint rows of one buffer)
+            _place_rows(out, dt, acc, mine[0].out_rows)
         return out
 
     def _forward_relations(self, xs, graph: HeteroLayerGraph, act=None):

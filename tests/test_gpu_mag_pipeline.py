@@ -360,6 +360,68 @@ def test_hetero_conv_trains_aggregate_first_like_relation_by_relation(hiplib, ta
         assert float((a - b).abs().max()) <= 2e-3 * scale + 1e-7, (float((a - b).abs().max()), scale, tuple(a.shape))
 
 
+def test_hetero_conv_inference_keeps_no_call_state_on_the_module(hiplib):
+    """nn.HeteroConv's inference route over the small mag-like group of the training test above (the 200-row institution table
+    is listed far more than 400 times: its attention terms are the TABLE's rows', read through the node list).  Lazy inputs,
+    then the same modules on gathered rows, then the lazy inputs again: the third output has the bits of the first, and no
+    forward leaves anything on the module — which node types went by id is a value of the call, not an attribute."""
+    import torch
+    import bench_mag as bm
+    from wholegraph_amd import nn as wnn
+    dev = torch.device("cuda", 0)
+    nodes = {"paper": 3000, "author": 4000, "institution": 200, "field_of_study": 500}
+    rels = {k: max(v // 400, 1500) for k, v in bm.MAG_RELS.items()}
+    graphs, num_nodes = bm.build_mag_like(dev, nodes, rels, seed=9)
+    etypes, ntypes = sorted(graphs), sorted(num_nodes)
+    g = torch.Generator(device=dev).manual_seed(2)
+    tables = {t: torch.rand((num_nodes[t], bm.F_IN), generator=g, device=dev) * 2 - 1 for t in ntypes}
+    model = bm.build_model(bm.make_params(etypes, ntypes, dev), etypes, ntypes, dev)
+    B, G = 128, 4
+    seeds = torch.randperm(num_nodes["paper"], generator=g, device=dev)[:B * G]
+    grp = next(iter(bm.make_loader(bm.build_mag_like.graph_store, tables, seeds, B, G).call_groups()))
+    lazy = grp.x_dict
+    assert all(isinstance(v, wnn.LazyRows) and v._rows is None for v in lazy.values())
+    assert len(lazy["institution"]) > 2 * nodes["institution"]
+    gathered = {t: v.table[v.ids] for t, v in lazy.items()}          # (not materialize(): the lazy inputs stay lazy)
+    attrs = [set(vars(layer)) for layer in model]
+    stages = []
+    wnn.set_stage_hook(lambda name, fn: (stages[-1].append(name), fn())[1])
+    try:
+        outs = []
+        with torch.no_grad():
+            for xs in (lazy, gathered, lazy):
+                stages.append([])
+                h = xs
+                for j, layer in enumerate(model):
+                    h = layer(h, grp.layer_graph(j), act="relu" if j == 0 else None)
+                outs.append(h["paper"].clone())
+    finally:
+        wnn.set_stage_hook(None)
+    assert "attn_terms(table)" in stages[0] and "attn_terms(table)" not in stages[1] and stages[2] == stages[0]
+    assert outs[0].shape == (B * G, bm.HC) and bool(torch.isfinite(outs[0]).all())
+    assert torch.equal(outs[2], outs[0])
+    assert [set(vars(layer)) for layer in model] == attrs
+
+
+def test_lazy_input_helper_on_device_tables():
+    """nn._table_through_ids on what only a device shows: an aligned fp32 table with int64 ids is read in place; a view whose
+    rows start 4 bytes off, or whose row stride is no multiple of 4 floats, is not."""
+    import torch
+    from wholegraph_amd import nn
+    table = torch.randn((64, 16), device="cuda")
+    ids = torch.randint(0, 64, (300,), device="cuda")
+    got = nn._table_through_ids(nn.LazyRows(table, ids))
+    assert got is not None and got[0] is table and got[1].data_ptr() == ids.data_ptr()
+    assert nn._table_through_ids(nn.LazyRows(table, ids.int())) is None          # the table qualifies: the ids alone do not
+    gathered = nn.LazyRows(table, ids)
+    gathered.materialize()
+    assert gathered._rows is not None and nn._table_through_ids(gathered) is None
+    assert nn._table_through_ids(nn.LazyRows(table.double(), ids)) is None
+    assert nn._table_through_ids(nn.LazyRows(table[:, 1:], ids)) is None
+    odd = torch.randn((64, 18), device="cuda")[:, :16]
+    assert odd.data_ptr() % 16 == 0 and odd.stride(0) % 4 != 0 and nn._table_through_ids(nn.LazyRows(odd, ids)) is None
+
+
 def test_mag_pipeline_matches_cpu_port(oracle_mod, hiplib):
     """The config-5 path through the PACKAGE — GraphStore + FeatureStore -> NeighborLoader.call_groups() (HeteroCallGroup) ->
     2 x nn.HeteroConv{GATConv(., 64, heads=4)} — against the float64 composition on the C oracle, mini-batch by mini-batch."""

@@ -290,6 +290,68 @@ def test_hetero_conv_folds_attention_vectors_and_sums_relation_biases():
     assert torch.allclose(hc._bias("author"), hc.conv(ets[2]).bias)
 
 
+def test_hetero_conv_derived_parameters_follow_the_parameters_they_are_built_from():
+    """Every derived parameter of ``nn.HeteroConv`` is cached against the parameters it is built from, and only those: after an
+    in-place change of ONE relation's ``lin.weight`` everything equals what a fresh module over the same parameters derives,
+    while the entries built from other relations' parameters are still the very tensors of before; ``bump_weight_generation``
+    rebuilds all of them (host logic, no kernel)."""
+    import copy
+    from wholegraph_amd import nn
+    torch.manual_seed(5)
+    ets = [("author", "writes", "paper"), ("paper", "cites", "paper"), ("paper", "rev_writes", "author"),
+           ("institution", "funds", "institution")]
+    types = ["author", "paper", "institution"]
+    hc = nn.HeteroConv({et: nn.GATConv(12, 5, heads=4, add_self_loops=False) for et in ets})
+    with torch.no_grad():
+        for et in ets:
+            hc.conv(et).bias.uniform_(-1, 1)
+
+    def derived(m):
+        d = {("rel", et, k): v for et in ets for k, v in enumerate(m._rel(et))}
+        d.update({("terms", t): m._terms_matrix(t) for t in types})
+        d.update({("bias", t): m._bias(t) for t in types})
+        return d
+
+    def fresh():
+        return derived(nn.HeteroConv({et: copy.deepcopy(hc.conv(et)) for et in ets}))
+
+    first = derived(hc)
+    again = derived(hc)
+    assert all(again[k] is first[k] for k in first)                 # nothing changed: nothing is rebuilt
+    with torch.no_grad():
+        hc.conv(ets[0]).lin.weight.mul_(1.5)
+    got, want = derived(hc), fresh()
+    assert set(got) == set(want) and all(torch.equal(got[k], want[k]) for k in want)
+    touched = {("rel", ets[0], k) for k in range(3)} | {("terms", "author"), ("terms", "paper")}
+    for k in first:
+        if k in touched:
+            assert not torch.equal(got[k], first[k]), k
+        else:                                                       # other relations' folds, every bias sum, the far type's terms
+            assert got[k] is first[k], k
+    assert torch.equal(hc._bias("paper"), torch.stack([hc.conv(ets[0]).bias, hc.conv(ets[1]).bias]).sum(0))
+    nn.bump_weight_generation()
+    bumped, want = derived(hc), fresh()
+    assert all(torch.equal(bumped[k], want[k]) for k in want)
+    assert all(bumped[k] is not got[k] for k in got)                # every entry was rebuilt
+
+
+def test_lazy_input_helper_truth_table_on_cpu_tensors():
+    """``nn._table_through_ids``: no kernel reads a CPU table, int32 ids or rows that were gathered already — None for each, and
+    for a plain tensor; ``nn._terms_by_id``: the table's rows carry the attention terms from a list twice as long as the table."""
+    from wholegraph_amd import nn
+    table = torch.randn(40, 8)
+    ids = torch.randint(0, 40, (100,))
+    assert nn._table_through_ids(nn.LazyRows(table, ids)) is None
+    assert nn._table_through_ids(nn.LazyRows(table, ids.int())) is None
+    lazy = nn.LazyRows(table, ids)
+    lazy._rows = table[ids]                                         # (what materialize() leaves behind)
+    assert nn._table_through_ids(lazy) is None
+    assert nn._table_through_ids(table) is None
+    assert nn._table_through_ids(nn.LazyRows(nn.MappedTable(4096, 8, "cpu"), ids)) is None      # (an address space, not a tensor)
+    rows = 40
+    assert not nn._terms_by_id(rows, 2 * rows - 1) and nn._terms_by_id(rows, 2 * rows) and nn._terms_by_id(rows, 2 * rows + 1)
+
+
 def test_hetero_default_call_group_is_sized_from_the_walks_capacities():
     """HeteroNeighborSampler.seeds_per_call without local_seeds_per_call: a seed costs what the heterogeneous walk allocates for
     it (frontier capacities grow per node type, an edge type's call holds frontier x fan-out slots), not the reference's
