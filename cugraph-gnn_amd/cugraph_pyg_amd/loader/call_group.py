@@ -413,6 +413,29 @@ class HeteroCallGroup:
             got[level_b] = (dst_b, col_b[:n_e] if want_col_b else None)
         return got
 
+    def edge_attr(self, name: str):
+        """{edge type: a stored edge attribute for every sampled edge of the type} for the edge types that store ``name`` —
+        ``feature_store[et, name, None][graphs[et].edge_id[CSR slot]]``, the hops in call order (the order ``layer_graph`` lists
+        the relation hops in; hop k's edges in CSR slot order, from row ``RelationHop.edge_base``), so every layer of a
+        ``HeteroConv`` of ``TransformerConv``s takes the same dict as ``edge_attr_dict`` and reads the prefix of its hops."""
+        self._wait()
+        have = {a.group_name for a in self._fs.get_all_tensor_attrs() if a.attr_name == name and isinstance(a.group_name, tuple)}
+        main = torch.cuda.current_stream() if self._walk_stream is not None else None
+        out = {}
+        for et in self.edge_types:
+            if et not in have:
+                continue
+            slots = []
+            for c, lv in zip(self._rec["calls"], self._live):
+                if c is not None and c["et"] == et and lv[1] > 0:
+                    if main is not None:
+                        c["gid"].record_stream(main)
+                    slots.append(c["gid"][:lv[1]])
+            g = torch.cat(slots) if slots else torch.zeros(0, dtype=torch.int64, device=self._rec["calls_seed_seg"].device)
+            edge_id = self._walk.graphs[et].edge_id
+            out[et] = self._fs[et, name, None][edge_id[g] if edge_id is not None else g]
+        return out
+
     def layer_graph(self, layer: int) -> HeteroLayerGraph:
         """The relation hops layer ``layer`` (0 = the one that reads ``x_dict``) of an H-layer model runs over, trimmed
         (``torch_geometric.utils.trim_to_layer`` per node / edge type): it computes rows for the vertices discovered by the
@@ -425,16 +448,22 @@ class HeteroCallGroup:
         if layer in self._layers:
             return self._layers[layer]
         lvl_in, lvl_out = H - layer, H - 1 - layer
-        rels = []
+        rels, edge_base = [], {}
         for ci, (c, lv) in enumerate(zip(self._rec["calls"], self._live)):
-            if c is None or lv[0] == 0 or c["hop"] > lvl_out:
+            if c is None:
+                continue
+            base = edge_base.get(c["et"], 0)      # edges of the same edge type in the earlier hops (``edge_attr``'s order)
+            edge_base[c["et"]] = base + lv[1]
+            if lv[0] == 0 or c["hop"] > lvl_out:
                 continue            # (a hop with frontier entries but no sampled edge stays: its rows still get act(bias))
             n_f, n_e = lv
             got = self._numbered(ci, lvl_in, lvl_out, want_col_b=c["hop"] < lvl_out)
             dst_in, col_in = got[lvl_in]
             rels.append(RelationHop(c["et"], c["hop"], c["offsets"][:n_f + 1], col_in, dst_in,
-                                    None if lvl_out == 0 else got[lvl_out][0], n_e, self._walk.fanout[c["et"]][c["hop"]]))
-        lg = HeteroLayerGraph(rels, {t: self._n_level[lvl_out][t] for t in self.node_types}, self.node_types)
+                                    None if lvl_out == 0 else got[lvl_out][0], n_e, self._walk.fanout[c["et"]][c["hop"]],
+                                    edge_base=base))
+        lg = HeteroLayerGraph(rels, {t: self._n_level[lvl_out][t] for t in self.node_types}, self.node_types,
+                              num_group_edges={et: edge_base.get(et, 0) for et in self.edge_types})
         self._layers[layer] = lg
         return lg
 

@@ -32,6 +32,7 @@ _ERROR_NAMES = ["SUCCESS", "UNKNOW_ERROR", "NOT_IMPLEMENTED", "LOGIC_ERROR", "CU
 
 IDS_BYTE_OFFSETS = 64   # WGAMD_IDS_BYTE_OFFSETS (include/wgamd_ext.h): src_ids = int64 byte offsets from x
 HETERO_SAGE_MAX_RELATIONS, HETERO_SAGE_RELU = 8, 1   # WGAMD_HETERO_SAGE_* (include/wgamd_ext.h)
+HETERO_TRANSFORMER_MAX_RELATIONS, HETERO_TRANSFORMER_RELU = 8, 1   # WGAMD_HETERO_TRANSFORMER_* (include/wgamd_ext.h)
 
 # wholememory_memory_allocation_type_t
 MA_NONE, MA_DEVICE, MA_HOST, MA_PINNED = range(4)
@@ -41,6 +42,13 @@ class HeteroSageRelation(Structure):
     """wgamd_hetero_sage_relation_t (include/wgamd_ext.h)."""
     _fields_ = [("row_ptr", c_void_p), ("col", c_void_p), ("x", c_void_p), ("ldx", c_int64), ("src_ids", c_void_p),
                 ("src_scale", c_void_p), ("F", c_int), ("ids_kind", c_int), ("mean", c_int), ("col0", c_int)]
+
+
+class HeteroTransformerRelation(Structure):
+    """wgamd_hetero_transformer_relation_t (include/wgamd_ext.h)."""
+    _fields_ = [("row_ptr", c_void_p), ("col", c_void_p), ("x", c_void_p), ("ldx", c_int64), ("src_ids", c_void_p),
+                ("edge_attr", c_void_p), ("u", c_void_p), ("ldu", c_int64), ("w", c_void_p), ("ldw", c_int64), ("alpha", c_void_p),
+                ("F", c_int), ("ids_kind", c_int), ("D", c_int), ("H", c_int), ("col0", c_int)]
 
 
 class WholeGraphLibraryError(RuntimeError):
@@ -327,6 +335,14 @@ SYMBOLS = {
     "wgamd_hetero_sage_layer_f32_train": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int,
                                                   c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p,
                                                   c_int64, c_void_p, c_int64, c_void_p]),
+    # heterogeneous graph transformer layer (wg_transformer_hetero.hip)
+    "wgamd_hetero_transformer_layer_supported": (c_int, [POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, c_int, c_int]),
+    "wgamd_hetero_transformer_layer_f32": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int,
+                                                   c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                                   c_int64, c_void_p]),
+    "wgamd_hetero_transformer_layer_f32_train": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                                         c_int, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64,
+                                                         c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     # GIN layer and add pooling (wg_gin.hip)
     "wgamd_gin_layer_supported": (c_int, [c_int, c_int, c_int]),
     "wgamd_gin_layer_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,

@@ -24,6 +24,7 @@ may read in place through its node list) with ``_terms_by_id`` (whose attention 
 ``_group_outputs`` / ``_place_rows`` (a heterogeneous layer graph's relations per (hop, destination type), the per-type float32
 outputs and a group's rows placed in them); ``HeteroConv._cached`` (every derived parameter keyed on the parameters it is built from).
 """
+import ctypes
 import math
 from typing import Optional, Tuple, Union
 
@@ -2569,7 +2570,8 @@ class TransformerConv(torch.nn.Module):
             raise NotImplementedError("TransformerConv: attention dropout (dropout > 0 in training mode) is not supported")
         _refuse_capture(self, "per-graph caches")
         if isinstance(graph, HeteroLayerGraph):
-            raise NotImplementedError("TransformerConv over a heterogeneous call group's layer graph is not supported")
+            raise NotImplementedError("TransformerConv over a heterogeneous call group's layer graph is not supported "
+                                      "(wrap the relations in HeteroConv({edge_type: TransformerConv}))")
         x_dst = None
         if isinstance(x, (tuple, list)):
             x, x_dst = x
@@ -3024,11 +3026,14 @@ class RelationHop:
     """One (hop, edge type) of a heterogeneous call group as a layer consumes it: CSR over the hop's frontier entries of the
     destination type (``row_ptr`` int32 [n + 1]); ``col`` int32 = row of every edge's source in the layer's INPUT of the source
     type; ``dst_rows`` int64 [n] = row of every frontier entry in the layer's input of the destination type (its attention
-    term); ``out_rows`` int64 [n] = its row in the layer's OUTPUT of the destination type (None: entry j is output row j)."""
+    term); ``out_rows`` int64 [n] = its row in the layer's OUTPUT of the destination type (None: entry j is output row j);
+    ``edge_base`` = row of the hop's first edge in the edge type's hop-major per-edge tensors (``edge_attr_dict[edge_type]``:
+    the number of edges of the same edge type in the earlier hops)."""
 
-    def __init__(self, edge_type, hop, row_ptr, col, dst_rows, out_rows, n_edges, fanout):
+    def __init__(self, edge_type, hop, row_ptr, col, dst_rows, out_rows, n_edges, fanout, edge_base=0):
         self.edge_type, self.hop, self.row_ptr, self.col = edge_type, hop, row_ptr, col
         self.dst_rows, self.out_rows, self.n_edges, self.fanout = dst_rows, out_rows, int(n_edges), int(fanout)
+        self.edge_base = int(edge_base)
 
     @property
     def n_rows(self):
@@ -3038,10 +3043,12 @@ class RelationHop:
 class HeteroLayerGraph:
     """What ONE layer of a trimmed heterogeneous GNN runs over (``cugraph_pyg_amd.loader.HeteroCallGroup.layer_graph``): the
     relation hops, and per node type the number of output rows (every output row of a type is a frontier entry of exactly one
-    hop of that type)."""
+    hop of that type).  ``num_group_edges`` ({edge type: edges of the whole call group}, None for a user-built graph): the
+    length of the edge type's hop-major per-edge tensors, of which every layer reads the prefix of its hops."""
 
-    def __init__(self, relations, n_out, node_types):
+    def __init__(self, relations, n_out, node_types, num_group_edges=None):
         self.relations, self.n_out, self.node_types = list(relations), dict(n_out), list(node_types)
+        self.num_group_edges = None if num_group_edges is None else dict(num_group_edges)
 
     @property
     def num_edges(self):
@@ -3360,21 +3367,244 @@ class _HeteroSageGroup(torch.autograd.Function):
         return (None, gw, gb, gdst) + tuple(gsrcs)
 
 
+# ---- heterogeneous transformer layer: one launch per (hop, destination type) — csrc/wg_transformer_hetero.hip ------------------
+HETERO_TRANSFORMER_MAX_K = 1024   # floats of one launch's A row (the 16 x (K + 4) fp32 LDS tile of wg_transformer_hetero.hip)
+hetero_transformer_launches = 0   # wgamd_hetero_transformer_layer_f32(_train) launches so far (tests: the kernel route ran)
+
+
+def hetero_transformer_stack(convs):
+    """The parameters of the ``TransformerConv`` relations ``convs`` ending in ONE node type, stacked the way
+    ``wgamd_hetero_transformer_layer_f32`` reads them (torch ops in the parameters' dtype, under autograd when it is on):
+      ``(wt [N, K], bias [N] | None, fold [F_dst, T], fold_bias [T], layout)``
+    ``wt = [wt_r1[:, :H W4] | wt_r2[:, :H W4] | ... | sum_r lin_skip_r.weight]`` (``transformer_folds`` per relation; the skip
+    block and ``bias`` = the sum of the skip biases cover the relations with ``root_weight``, and are absent when none has
+    it), ``fold = [Fu_r1 | Fu_r2 | ... | Fw_r1 | ... | 0 pad]`` so that ``x_dst @ fold + fold_bias`` holds every relation's
+    ``u`` and ``w`` as column slices (T a multiple of 4: rows stay 16-B aligned), and ``layout[r] = dict(col0, width, W4, u0,
+    w0, H, F, D)``: the relation's columns of ``wt`` and of the fold product (``w0`` None without ``edge_dim``)."""
+    N = {c._out_width for c in convs}
+    Fd = {c.in_dst for c in convs}
+    if len(N) != 1 or len(Fd) != 1:
+        raise ValueError("HeteroConv: the TransformerConv relations ending in one node type must agree on the output width "
+                         "(heads x out_channels, or out_channels with concat=False) and on in_channels[1]; got widths %s, "
+                         "destination widths %s" % (sorted(N), sorted(Fd)))
+    folds = [transformer_folds(c) for c in convs]
+    layout, wts, at, ut = [], [], 0, 0
+    for c, (Fu, bu, Fw, bw, wt, _) in zip(convs, folds):
+        D = c.edge_dim or 0
+        W4 = transformer_block_width(c.in_src, D)
+        layout.append(dict(col0=at, width=c.heads * W4, W4=W4, u0=ut, w0=None, H=c.heads, F=c.in_src, D=D))
+        wts.append(wt[:, :c.heads * W4])
+        at += c.heads * W4
+        ut += c.heads * c.in_src
+    us, ub = [f[0] for f in folds], [f[1] for f in folds]
+    for c, lay, f in zip(convs, layout, folds):
+        if lay["D"]:
+            lay["w0"] = ut
+            us.append(f[2])
+            ub.append(f[3])
+            ut += c.heads * lay["D"]
+    if ut % 4:
+        us.append(us[0].new_zeros((us[0].shape[0], 4 - ut % 4)))
+        ub.append(ub[0].new_zeros(4 - ut % 4))
+    skips = [c.lin_skip for c in convs if c.root_weight]
+    bias = None
+    if skips:
+        wts.append(_sum_of([l.weight for l in skips]))
+        bias = _sum_of([l.bias for l in skips if l.bias is not None])
+    return torch.cat(wts, 1), bias, torch.cat(us, 1), torch.cat(ub), layout
+
+
+def hetero_transformer_launch(rels, n_rows: int, wt, N: int, root=None, bias=None, relu=False, acc_in=None, out_rows=None,
+                              out=None, a_save=None):
+    """One ``wgamd_hetero_transformer_layer_f32`` launch (include/wgamd_ext.h).  ``rels``: ``[(row_ptr, col, x, ids, edge_attr,
+    u, w, H, alpha), ...]`` (x [*, F] float32 rows, ``ids`` the node list x is read through or None, ``edge_attr`` [E, D] in
+    CSR order or None, ``u`` [n_rows, H F] / ``w`` [n_rows, H D] column slices of the fold product, ``alpha`` [E, H] or None);
+    ``root``: ``(x_dst, dst_rows, dst_ids)`` or None; ``wt`` [N, >= K] (a column slice of the stacked weight); ``a_save``
+    [n_rows, >= K]: the launch also keeps its A rows, and every relation its alpha (``_train``)."""
+    global hetero_transformer_launches
+    arr = (L.HeteroTransformerRelation * max(len(rels), 1))()
+    keep, at = [], 0
+    for k, (row_ptr, col, x, ids, ea, u, w, H, alpha) in enumerate(rels):
+        _check_csr(row_ptr, col)
+        F_, D = int(x.shape[1]), 0 if ea is None else int(ea.shape[1])
+        assert row_ptr.shape[0] == n_rows + 1 and x.dtype == torch.float32 and x.stride(1) == 1
+        assert ids is None or ids.is_contiguous()
+        assert u.dtype == torch.float32 and u.stride(1) == 1 and u.shape == (n_rows, H * F_)
+        assert ea is None or (ea.dtype == torch.float32 and ea.is_contiguous() and ea.shape[0] == col.shape[0])
+        assert (w is None) == (ea is None) and (w is None or (w.dtype == torch.float32 and w.stride(1) == 1 and w.shape == (n_rows, H * D)))
+        assert alpha is None or (alpha.dtype == torch.float32 and alpha.is_contiguous() and alpha.shape == (col.shape[0], H))
+        assert a_save is None or alpha is not None
+        col = _nonempty(col, torch.int32)
+        bufs = [col] + [None if t is None else _nonempty(t, torch.float32) for t in (ea, alpha)]
+        keep.append(bufs)
+        d = arr[k]
+        d.row_ptr, d.col, d.x, d.ldx, d.src_ids = row_ptr.data_ptr(), col.data_ptr(), x.data_ptr(), x.stride(0), _ptr(ids)
+        d.edge_attr, d.u, d.ldu, d.w, d.ldw = _ptr(bufs[1]), u.data_ptr(), u.stride(0), _ptr(w), 0 if w is None else w.stride(0)
+        d.alpha, d.F, d.ids_kind, d.D, d.H, d.col0 = _ptr(bufs[2]), F_, _sage_ids_kind(ids), D, int(H), at
+        at += int(H) * transformer_block_width(F_, D)
+    x_dst, dst_rows, dst_ids = root if root is not None else (None, None, None)
+    if x_dst is not None:
+        assert x_dst.dtype == torch.float32 and x_dst.stride(1) == 1 and (dst_rows is None or dst_rows.dtype == torch.int64)
+        at += int(x_dst.shape[1])
+    assert wt.dtype == torch.float32 and wt.stride(1) == 1 and wt.shape[0] == N and wt.shape[1] >= at
+    if out is None:
+        out = torch.empty((n_rows, N), dtype=torch.float32, device=wt.device)
+    assert out.stride(1) == 1 and out.shape[1] == N and (acc_in is None or (acc_in.stride(1) == 1 and acc_in.shape == (n_rows, N)))
+    assert out_rows is None or (out_rows.dtype == torch.int64 and out_rows.is_contiguous())
+    common = (arr, len(rels), n_rows, _ptr(x_dst), 0 if x_dst is None else x_dst.stride(0), 0 if x_dst is None else int(x_dst.shape[1]),
+              _ptr(dst_rows), _ptr(dst_ids), _sage_ids_kind(dst_ids), wt.data_ptr(), wt.stride(0), N, _ptr(bias),
+              L.HETERO_TRANSFORMER_RELU if relu else 0, _ptr(acc_in), 0 if acc_in is None else acc_in.stride(0), _ptr(out_rows),
+              out.data_ptr(), out.stride(0))
+    if a_save is not None:
+        assert a_save.dtype == torch.float32 and a_save.stride(1) == 1 and a_save.shape[0] == n_rows and a_save.shape[1] >= at
+        L.check(L.lib().wgamd_hetero_transformer_layer_f32_train(*common, a_save.data_ptr(), a_save.stride(0), get_stream()),
+                "wgamd_hetero_transformer_layer_f32_train")
+    else:
+        L.check(L.lib().wgamd_hetero_transformer_layer_f32(*common, get_stream()), "wgamd_hetero_transformer_layer_f32")
+    hetero_transformer_launches += 1
+    return out
+
+
+class _TconvGroup:
+    """What one (hop, destination type) group of the hetero transformer layer launches over: per relation block a dict
+    ``(row_ptr, col, x, ids, ea, src, n_edges)`` (``ea``: the hop's rows of the relation's edge attributes or None; ``src``:
+    index of x among the group's differentiable source tensors, None for a table read through a node list) next to the
+    relation's ``layout`` entry of ``hetero_transformer_stack``, the root ``(x_dst, dst_rows, dst_ids)`` or None, the plan, and
+    the ``RelationHop`` of every block (None: the hop lists no such relation) for the transposes of the backward pass."""
+
+    def __init__(self, blocks, layout, hops, root, plan, n_rows, N, relu, tag):
+        self.blocks, self.layout, self.hops, self.root, self.plan = blocks, layout, hops, root, plan
+        self.n_rows, self.N, self.relu, self.tag = n_rows, N, relu, tag
+        self.K_rel = layout[-1]["col0"] + layout[-1]["width"] if layout else 0
+        self.K = self.K_rel + (int(root[0].shape[1]) if root is not None else 0)
+
+    def u_w(self, uw, k):
+        lay = self.layout[k]
+        u = uw[:, lay["u0"]:lay["u0"] + lay["H"] * lay["F"]]
+        return u, (uw[:, lay["w0"]:lay["w0"] + lay["H"] * lay["D"]] if lay["D"] else None)
+
+    def run(self, wt, bias, uw, out=None, out_rows=None, a_save=None, alphas=None):
+        """The group's launches -> act(A @ wt^T + bias), placed through ``out_rows`` into ``out`` when given."""
+        acc = None
+        for k, (lo, hi, with_root) in enumerate(self.plan):
+            last = k == len(self.plan) - 1
+            rels = []
+            for b in range(lo, hi):
+                blk, (u, w) = self.blocks[b], self.u_w(uw, b)
+                rels.append((blk["row_ptr"], blk["col"], blk["x"], blk["ids"], blk["ea"], u, w, self.layout[b]["H"],
+                             None if alphas is None else alphas[b]))
+            at = self.layout[lo]["col0"] if lo < len(self.layout) else self.K_rel
+            names = ",".join(str(h.edge_type[1]) for h in self.hops[lo:hi] if h is not None)
+            name = "tconv%s:%s (%d rows, launch %d/%d)" % (self.tag, names, self.n_rows, k + 1, len(self.plan))
+            res = _stage(name, lambda: hetero_transformer_launch(
+                rels, self.n_rows, wt[:, at:], self.N, root=self.root if with_root else None, bias=bias if last else None,
+                relu=self.relu and last, acc_in=acc, out_rows=out_rows if last else None, out=out if last else None,
+                a_save=None if a_save is None else a_save[:, at:]))
+            acc = res
+        return acc
+
+
+def _relation_transpose_perm(r: RelationHop, n_src: int):
+    """``(row_ptr_t, col_t, perm)`` of a relation hop seen from its ``n_src`` input rows (entries = the hop's frontier entries,
+    hop order inside a source row: deterministic sums; ``perm`` = the hop's CSR edge of every transposed entry) — computed once
+    and kept on the ``RelationHop``, like ``_relation_transpose``."""
+    hit = getattr(r, "_tconv_t", None)
+    if hit is None or hit[0] != n_src:
+        row_ptr_t, perm, _, col_t = _csr_transpose(r.row_ptr, r.col, n_src, want_perm=True, want_col_t=True)
+        hit = (n_src, row_ptr_t, col_t, perm)
+        r._tconv_t = hit
+    return hit[1], hit[2], hit[3]
+
+
+class _HeteroTconvGroup(torch.autograd.Function):
+    """One (hop, destination type) group of the hetero transformer layer under autograd.  Differentiable inputs: the stacked
+    weight, the bias sum, the fold product ``uw`` (every relation's u and w: their gradients reach the query folds and the
+    destination rows through autograd over the GEMM that made it), the resident destination rows (the skip block) and the
+    resident source tensors.  Forward: the group's launches in their ``_train`` form (A [n, K] and every relation's alpha
+    kept).  Backward: ``gwt = gz^T A`` and ``dA = gz wt`` (library GEMMs); per relation ``wgamd_transformer_bwd_dst_f32`` on
+    the column slices of dA and A at the relation's col0 (du, dw, ds) and, per resident source tensor,
+    ``wgamd_transformer_bwd_src_f32`` over the relation hop's transpose; the skip block's ``dA[:, K_rel:]`` goes to the
+    destination rows through ``dst_rows`` (rows of one group are distinct vertices) — no atomics: the same bits every run."""
+
+    @staticmethod
+    def forward(ctx, grp, wt, bias, uw, x_dst, *srcs):
+        w, b, uw_d = wt.detach().contiguous(), None if bias is None else bias.detach(), uw.detach()
+        dev = w.device
+        A = torch.empty((grp.n_rows, grp.K), dtype=torch.float32, device=dev)
+        alphas = [torch.empty((blk["n_edges"], lay["H"]), dtype=torch.float32, device=dev) for blk, lay in zip(grp.blocks, grp.layout)]
+        z = grp.run(w, b, uw_d, a_save=A, alphas=alphas)
+        ctx.grp, ctx.A, ctx.alphas, ctx.n_srcs = grp, A, alphas, len(srcs)
+        ctx.src_shapes = [tuple(t.shape) for t in srcs]
+        ctx.dst_shape = None if x_dst is None else tuple(x_dst.shape)
+        ctx.save_for_backward(w, uw_d, z)
+        return z
+
+    @staticmethod
+    def backward(ctx, g):
+        _released(ctx.A, "HeteroConv (TransformerConv relations)", "rows")
+        grp, A, alphas = ctx.grp, ctx.A, ctx.alphas
+        w, uw, z = ctx.saved_tensors
+        n, dev = grp.n_rows, w.device
+        g = g.contiguous().float()
+        if grp.relu:
+            g = torch.ops.aten.threshold_backward(g, z, 0)          # dZ once, read by every gradient
+        need_w, need_b, need_uw, need_dst = ctx.needs_input_grad[1:5]
+        need_src = [ctx.needs_input_grad[5 + si] for si in range(ctx.n_srcs)]
+        gw = g.t() @ A if need_w else None
+        gb = g.sum(0) if need_b else None
+        guw = gdst = None
+        gsrcs = [None] * ctx.n_srcs
+        if need_uw or need_dst or any(need_src):
+            dA = (g @ w).contiguous()                                # [n, K]
+            guw = torch.zeros_like(uw)
+            for si in range(ctx.n_srcs):
+                if need_src[si]:
+                    gsrcs[si] = torch.zeros(ctx.src_shapes[si], dtype=torch.float32, device=dev)
+            for k, (blk, lay) in enumerate(zip(grp.blocks, grp.layout)):
+                if blk["n_edges"] == 0:
+                    continue
+                H, F_, D, c0 = lay["H"], lay["F"], lay["D"], lay["col0"]
+                du = torch.empty((n, H * F_), dtype=torch.float32, device=dev)
+                dw = torch.empty((n, H * D), dtype=torch.float32, device=dev) if D else None
+                ds = torch.empty((blk["n_edges"], H), dtype=torch.float32, device=dev)
+                transformer_bwd_dst(blk["row_ptr"], blk["col"], blk["x"], H, alphas[k], dA[:, c0:], A[:, c0:], du, ds,
+                                    edge_attr=blk["ea"], dw=dw, src_ids=blk["ids"])
+                guw[:, lay["u0"]:lay["u0"] + H * F_] = du
+                if D:
+                    guw[:, lay["w0"]:lay["w0"] + H * D] = dw
+                si = blk["src"]
+                if si is not None and need_src[si]:
+                    row_ptr_t, col_t, perm = _relation_transpose_perm(grp.hops[k], ctx.src_shapes[si][0])
+                    transformer_bwd_src(row_ptr_t, col_t, perm, None, D, H, -1, alphas[k], ds, dA[:, c0:], grp.u_w(uw, k)[0], gsrcs[si])
+            if need_dst and grp.root is not None:
+                gdst = torch.zeros(ctx.dst_shape, dtype=torch.float32, device=dev)
+                gdst.index_copy_(0, grp.root[1], dA[:, grp.K_rel:])  # (rows of one group are distinct vertices)
+            if not need_uw:
+                guw = None
+        ctx.A = ctx.alphas = None
+        return (None, gw, gb, guw, gdst) + tuple(gsrcs)
+
+
 class HeteroConv(torch.nn.Module):
     """``torch_geometric.nn.HeteroConv({edge_type: conv}, aggr="sum")`` for ``GATConv`` relations, or for ``SAGEConv``
     relations: the output of a node type is the sum over the relations ending in it (examples/mag_lp_mnmg.py:141 builds this
     stack; GATConv as pylibwholegraph/torch/gnn_model.py:45-59; bipartite SAGEConv per direction as movielens_mnmg.py).
 
-    ``forward(x_dict, graph, act=None)``
+    ``forward(x_dict, graph, act=None, edge_attr_dict=None)``
       * ``graph`` a ``HeteroLayerGraph`` of a loader call group (no autograd): every (hop, edge type) is ONE launch —
         AGGREGATE-FIRST (the attention-weighted sum is linear, so it runs over the UNTRANSFORMED source rows and the per-head
         weights are applied to the few destination rows afterwards: the ``lin`` GEMM over every source row, 10-20x more rows,
         never runs), attention logits ``x @ fold(W, att)`` made by the feature gather itself when ``x_dict[t]`` is a
         ``LazyRows`` (``wgamd_gather_terms_f32``), HeteroConv's running sum, bias, ReLU and the row placement folded into the
         last relation's launch (``wgamd_gat_layer_fused_bf16x3`` / ``wgamd_gat_transform_heads_bf16x3``).  With ``SAGEConv``
-        relations (autograd too) every (hop, destination type) is ONE launch: ``_forward_layer_sage``.
+        relations (autograd too) every (hop, destination type) is ONE launch: ``_forward_layer_sage``; with ``TransformerConv``
+        relations likewise (``_forward_layer_tconv``, the to_hetero'd encoder of mag_lp_mnmg.py:53-66), ``edge_attr_dict[et]``
+        = the edge type's attributes [edges of et in the call group, edge_dim], hop-major (``HeteroCallGroup.edge_attr``):
+        every layer takes the same dict and reads the prefix of the hops it runs (``RelationHop.edge_base``).
       * ``graph`` a dict ``{edge_type: edge_index | [csr_row_ptr, csr_col_ind]}`` (a mini-batch ``HeteroData``; autograd):
-        ``convs[edge_type]((x_src, x_dst), graph[edge_type])`` summed per destination type — PyG's own formulation."""
+        ``convs[edge_type]((x_src, x_dst), graph[edge_type])`` summed per destination type — PyG's own formulation; a
+        ``TransformerConv`` relation with ``edge_dim`` takes ``edge_attr_dict[edge_type]`` as its ``edge_attr``.
+    A relation with ``edge_dim`` and no entry in ``edge_attr_dict`` raises ValueError before any launch."""
 
     def __init__(self, convs, aggr: str = "sum"):
         super().__init__()
@@ -3393,6 +3623,9 @@ class HeteroConv(torch.nn.Module):
         # under autograd a call-group layer is aggregate-first too (``_forward_layer_train``); False: PyG's own relation-by-relation,
         # transform-first formulation on ``GATConv`` (``_forward_relations``: the lin GEMM over every source row)
         self.train_aggregate_first = True
+        # TransformerConv relations over a call group: True runs the library-ops route (``_forward_tconv_library``) whatever the
+        # shapes — the comparison route of examples/hetero_transformer_call_groups.py --torch-ops
+        self.transformer_library_ops = False
 
     def conv(self, edge_type):
         return self.convs["__".join(edge_type)]
@@ -3560,16 +3793,20 @@ class HeteroConv(torch.nn.Module):
         c = next(self.conv(et) for et in self.edge_types if et[2] == dt)
         return c.heads * c.out_channels if getattr(c, "concat", False) else c.out_channels
 
-    def forward(self, x_dict, graph, act=None):
+    def forward(self, x_dict, graph, act=None, edge_attr_dict=None):
         # (folded attention vectors, weight tiles, pooled buffers: cached against the parameters' versions)
         _refuse_capture(self, "derived-weight caches")
         if isinstance(graph, HeteroLayerGraph):
             sage = [isinstance(self.conv(et), SAGEConv) for et in self.edge_types]
             if all(sage):
                 return self._forward_layer_sage(x_dict, graph, act)
-            if any(sage) or not all(isinstance(self.conv(et), GATConv) for et in self.edge_types):
-                raise NotImplementedError("HeteroConv over a HeteroLayerGraph: every relation a GATConv, or every relation a "
-                                          "SAGEConv (mixed layer classes run over a dict of edge_index only)")
+            tconv = [isinstance(self.conv(et), TransformerConv) for et in self.edge_types]
+            if all(tconv):
+                return self._forward_layer_tconv(x_dict, graph, act, edge_attr_dict)
+            if any(sage) or any(tconv) or not all(isinstance(self.conv(et), GATConv) for et in self.edge_types):
+                raise NotImplementedError("HeteroConv over a HeteroLayerGraph: every relation a GATConv, every relation a "
+                                          "SAGEConv, or every relation a TransformerConv (mixed layer classes run over a dict "
+                                          "of edge_index only)")
             needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
             plain = all(self.conv(et).concat and not self.conv(et).add_self_loops for et in self.edge_types)
             if not needs_grad and plain:
@@ -3580,10 +3817,17 @@ class HeteroConv(torch.nn.Module):
                 return self._forward_layer_train(x_dict, graph, act)
             return self._forward_relations(x_dict, graph, act)
         out = {}
-        for et in self.edge_types:
-            if et not in graph or x_dict.get(et[0]) is None or x_dict.get(et[2]) is None:
-                continue
-            y = self.conv(et)((x_dict[et[0]], x_dict[et[2]]), graph[et])
+        live = [et for et in self.edge_types if et in graph and x_dict.get(et[0]) is not None and x_dict.get(et[2]) is not None]
+        attrs = {}
+        for et in live:       # (a TransformerConv relation takes its edge attributes: checked before any launch)
+            c = self.conv(et)
+            if isinstance(c, TransformerConv) and c.edge_dim is not None:
+                if edge_attr_dict is None or edge_attr_dict.get(et) is None:
+                    raise ValueError("HeteroConv: TransformerConv of %r has edge_dim=%d and edge_attr_dict has no entry for it"
+                                     % (et, c.edge_dim))
+                attrs[et] = dict(edge_attr=c._check_edge_attr(edge_attr_dict[et], graph[et][1].shape[0], graph[et][0].device))
+        for et in live:
+            y = self.conv(et)((x_dict[et[0]], x_dict[et[2]]), graph[et], **attrs.get(et, {}))
             out[et[2]] = y if et[2] not in out else out[et[2]] + y
         return {t: torch.relu(v) for t, v in out.items()} if act == "relu" else out
 
@@ -3683,6 +3927,199 @@ class HeteroConv(torch.nn.Module):
                 out[dt] = grp.run(wstack, bias)
             else:
                 grp.run(wstack, bias, out=out[dt], out_rows=place)
+        return out
+
+    # ---- TransformerConv relations: one launch per (hop, destination type) ----------------------------------------------
+    def _tconv_weights(self, ets, grad: bool = False):
+        """``hetero_transformer_stack`` of the relations ``ets`` (those ending in one node type whose source type has input
+        rows) in float32.  ``grad``: built by torch ops on the parameters (autograd hands each relation its slice and every
+        ``lin_skip`` the shared skip gradient); otherwise detached and cached against the parameters' versions."""
+        convs = [self.conv(et) for et in ets]
+
+        def build():
+            wt, bias, fold, fold_b, layout = hetero_transformer_stack(convs)
+            return (wt.float().contiguous(), None if bias is None else bias.float(), fold.float().contiguous(), fold_b.float(), layout)
+        if grad:
+            with torch.enable_grad():
+                return build()
+        return self._cached(("tconv", tuple(ets)), [p for c in convs for p in c.parameters()],
+                            lambda: tuple(t.detach() if torch.is_tensor(t) else t for t in build()))
+
+    def _tconv_edge_attrs(self, ets, graph: HeteroLayerGraph, edge_attr_dict, device):
+        """{edge type: the edge type's hop-major edge attributes as the kernels read them (float32 [E, D] contiguous)} for the
+        relations of ``ets`` with ``edge_dim``; ValueError on a missing entry, a wrong width, dtype, device or length (the
+        call group's edge count of the type, ``graph.num_group_edges``; for a user-built graph the rows its hops cover) — before
+        any launch.  NotImplementedError for an attribute that requires a gradient: edge attributes are data here."""
+        out = {}
+        for et in ets:
+            c = self.conv(et)
+            if c.edge_dim is None:
+                continue
+            if edge_attr_dict is None or edge_attr_dict.get(et) is None:
+                raise ValueError("HeteroConv: TransformerConv of %r has edge_dim=%d and edge_attr_dict has no entry for it"
+                                 % (et, c.edge_dim))
+            total = None if graph.num_group_edges is None else graph.num_group_edges.get(et)
+            if total is None:
+                total = max([r.edge_base + r.n_edges for r in graph.relations if r.edge_type == et] + [0])
+            ea = c._check_edge_attr(edge_attr_dict[et], int(total), device)
+            if torch.is_grad_enabled() and ea.requires_grad:
+                raise NotImplementedError("HeteroConv over a HeteroLayerGraph: a gradient w.r.t. edge_attr_dict[%r] is not "
+                                          "supported (edge attributes are data here)" % (et,))
+            out[et] = ea.detach().float().contiguous()
+        return out
+
+    def _forward_layer_tconv(self, xs, graph: HeteroLayerGraph, act=None, edge_attr_dict=None):
+        """``HeteroConv({edge_type: TransformerConv})`` over a call group's layer graph: the softmax is per relation and the sum
+        over the relations ending in a type is linear, so per (hop, destination type) the relations' rows ``[sum alpha [x_j |
+        a_ij | 1] per head]`` sit side by side, followed by ``x_dst``, and meet ONE stacked weight ``[Wstack_r1 | Wstack_r2 |
+        ... | sum_r lin_skip_r]`` — one ``wgamd_hetero_transformer_layer_f32`` launch (a group wider than 1024 floats:
+        consecutive launches of whole relations, ``hetero_sage_plan``), bias, ReLU and row placement folded in; every
+        relation's ``u`` and ``w`` are column slices of ONE library GEMM over the destination rows.  Every relation ending in
+        the type whose source type has input rows adds its skip term to every row, whether or not the hop sampled an edge of
+        it.  A ``LazyRows`` input (int64 or int32 ids, fp32 table, 16-B rows) is read through its node list, per node type.
+        Under autograd one ``_HeteroTconvGroup`` per group.  Shapes outside the kernel's domain, and CPU tensors:
+        ``_forward_tconv_library``."""
+        if act not in (None, "relu"):
+            raise ValueError("HeteroConv: act is None or 'relu', not %r" % (act,))
+        relu = act == "relu"
+        for et in self.edge_types:
+            c = self.conv(et)
+            if c.dropout > 0 and c.training:
+                raise NotImplementedError("TransformerConv: attention dropout (dropout > 0 in training mode) is not supported")
+        X, ids = {}, {}
+        for t, v in xs.items():
+            if v is None:
+                continue
+            _refuse_featureless(self, v)
+            if isinstance(v, LazyRows):
+                _refuse_lazy_table_grad(v.table)
+                if isinstance(v.table, torch.Tensor) and _kernel_rows_ok(v.table) and v._rows is None:
+                    X[t], ids[t] = v.table, v.ids
+                    continue
+                v = v.materialize()
+            X[t], ids[t] = v, None
+        groups = _relation_groups(graph)
+        ends = {}
+        for (_, dt), mine in groups:
+            if dt in ends:
+                continue
+            for r in mine:      # (a source type without input rows has no edges: its relation adds nothing)
+                if (r.edge_type[0] not in X and r.n_edges > 0) or (dt not in X and r.n_rows > 0):
+                    raise ValueError("HeteroConv: x_dict has no rows for %r, which relation %r needs" % (
+                        dt if dt not in X else r.edge_type[0], r.edge_type))
+            ends[dt] = [et for et in self.edge_types if et[2] == dt and et[0] in X]
+            if not ends[dt]:
+                raise ValueError("HeteroConv: x_dict has rows for no source type of the relations ending in %r" % (dt,))
+            for et in ends[dt]:
+                c = self.conv(et)
+                if X[et[0]].shape[1] != c.in_src or X[dt].shape[1] != c.in_dst:
+                    raise ValueError("HeteroConv: x_dict[%r] / x_dict[%r] have %d / %d features, TransformerConv of %r takes %s"
+                                     % (et[0], dt, X[et[0]].shape[1], X[dt].shape[1], et, (c.in_src, c.in_dst)))
+            if len({self.conv(et)._out_width for et in ends[dt]}) > 1:
+                raise ValueError("HeteroConv: the TransformerConv relations ending in %r have output widths %s; they are summed, so "
+                                 "they must agree" % (dt, sorted({self.conv(et)._out_width for et in ends[dt]})))
+        dev = next(iter(X.values())).device
+        used = [et for dt in ends for et in ends[dt]]
+        eas = self._tconv_edge_attrs(used, graph, edge_attr_dict, graph.relations[0].row_ptr.device if graph.relations else dev)
+
+        def fits(et):
+            c = self.conv(et)
+            one = (ctypes.c_int * 1)
+            return bool(L.lib().wgamd_hetero_transformer_layer_supported(one(c.in_src), one(c.edge_dim or 0), one(c.heads), 1,
+                                                                         c.in_dst if c.root_weight else 0, c._out_width))
+        in_domain = not self.transformer_library_ops and all(torch.is_tensor(v) and v.is_cuda for v in X.values()) and all(
+            fits(et) for et in used) and all(
+            self.conv(et).in_dst % 4 == 0 and self.conv(et).in_dst <= 256 for et in used)
+        if not in_domain:
+            return self._forward_tconv_library({t: (v.materialize() if isinstance(v, LazyRows) else v) for t, v in xs.items()
+                                                if v is not None}, graph, relu, eas)
+        for t in X:       # rows as the kernel reads them (float32, unit column stride, 16-B aligned rows): copied when they are not
+            if ids[t] is None:
+                X[t] = _tconv_rows(X[t])
+        needs_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
+                                                  or any(ids[t] is None and v.requires_grad for t, v in X.items()))
+        out = _group_outputs(graph, groups, self._width, dev, make=torch.zeros if needs_grad else torch.empty)
+        weights = {}
+        for (hop, dt), mine in groups:
+            n_f = mine[0].n_rows
+            if n_f == 0:
+                continue
+            listed = {r.edge_type: r for r in mine}
+            if dt not in weights:
+                weights[dt] = self._tconv_weights(ends[dt], grad=needs_grad)
+            wt, bias, fold, fold_b, layout = weights[dt]
+            dst_rows = mine[0].dst_rows
+            # the queries: x_dst[dst_rows] (through the node list for a lazy type) times every relation's folds at once
+            xq = X[dt][dst_rows] if ids[dt] is None else X[dt][ids[dt][dst_rows].long()]
+            uw = torch.addmm(fold_b, xq, fold)
+            blocks, hops, srcs = [], [], []
+            for et in ends[dt]:
+                x, r = X[et[0]], listed.get(et)
+                si = None
+                if ids[et[0]] is None:
+                    si = next((k for k, t in enumerate(srcs) if t is x), None)
+                    if si is None:
+                        srcs.append(x)
+                        si = len(srcs) - 1
+                D = self.conv(et).edge_dim or 0
+                if r is None or r.n_edges == 0:      # no edge of the relation in this hop: zero blocks, its skip term still counts
+                    row_ptr = torch.zeros(n_f + 1, dtype=torch.int32, device=dev)
+                    col, n_e = torch.zeros(0, dtype=torch.int32, device=dev), 0
+                    ea = torch.zeros((0, D), dtype=torch.float32, device=dev) if D else None
+                else:
+                    row_ptr, col, n_e = r.row_ptr, r.col[:r.n_edges], r.n_edges
+                    ea = eas[et][r.edge_base:r.edge_base + n_e] if D else None
+                blocks.append(dict(row_ptr=row_ptr, col=col, x=x, ids=ids[et[0]], ea=ea, src=si, n_edges=n_e))
+                hops.append(r)
+            root = root_src = None
+            if any(self.conv(et).root_weight for et in ends[dt]):
+                root = (X[dt], dst_rows, ids[dt])
+                root_src = X[dt] if ids[dt] is None else None
+            plan = hetero_sage_plan([lay["width"] for lay in layout], 0 if root is None else root[0].shape[1],
+                                    max_k=HETERO_TRANSFORMER_MAX_K, max_rel=L.HETERO_TRANSFORMER_MAX_RELATIONS)
+            grp = _TconvGroup(blocks, layout, hops, root, plan, n_f, self._width(dt), relu, self.stage_tag + " hop %d %s" % (hop + 1, dt))
+            place = mine[0].out_rows
+            if needs_grad:
+                _place_rows(out, dt, _HeteroTconvGroup.apply(grp, wt, bias, uw, root_src, *srcs), place)
+            elif place is None:
+                out[dt] = grp.run(wt, bias, uw)
+            else:
+                grp.run(wt, bias, uw, out=out[dt], out_rows=place)
+        return out
+
+    def _forward_tconv_library(self, x, graph: HeteroLayerGraph, relu: bool, eas):
+        """The same layer out of library ops in PyG's formulation (``_tconv_library_ops`` per relation hop, summed, activation
+        applied, placed through ``out_rows``), with ordinary autograd — what shapes outside the kernel's domain and CPU tensors
+        take; correctness only."""
+        dev = next(iter(x.values())).device
+        out = {}
+        for (hop, dt), mine in _relation_groups(graph):
+            n_f = mine[0].n_rows
+            if n_f == 0:
+                continue
+            listed = {r.edge_type: r for r in mine}
+            xd = x[dt][mine[0].dst_rows].float()
+            y = None
+            for et in self.edge_types:
+                if et[2] != dt or et[0] not in x:
+                    continue
+                c, r = self.conv(et), listed.get(et)
+                if r is not None and r.n_edges > 0:
+                    ea = eas[et][r.edge_base:r.edge_base + r.n_edges] if c.edge_dim is not None else None
+                    one = LayerGraph([HopGraph(r.row_ptr, r.col[:r.n_edges], None)])
+                    o, _ = _tconv_library_ops(c, x[et[0]].float(), xd, one, ea, False)
+                elif c.root_weight:
+                    o = c.lin_skip(xd)
+                else:
+                    continue
+                y = o if y is None else y + o
+            if y is None:
+                y = torch.zeros((n_f, self._width(dt)), dtype=torch.float32, device=dev)
+            if relu:
+                y = torch.relu(y)
+            if mine[0].out_rows is not None and dt not in out:
+                out[dt] = torch.zeros((graph.n_out[dt], y.shape[1]), dtype=y.dtype, device=dev)
+            _place_rows(out, dt, y, mine[0].out_rows)
         return out
 
     def _forward_sage_library(self, x, graph: HeteroLayerGraph, relu: bool):

@@ -902,6 +902,62 @@ wholememory_error_code_t wgamd_hetero_sage_layer_f32_train(const wgamd_hetero_sa
                                                            int64_t ld_acc, const int64_t* out_rows, float* out, int64_t ldo,
                                                            float* c_out, int64_t ldc, void* stream);
 
+/* ---- Heterogeneous graph transformer layer (csrc/wg_transformer_hetero.hip): HeteroConv({edge type: TransformerConv}, aggr =
+ * "sum") over one (hop, destination type) of a call group — what to_hetero makes of the encoder of the reference's cugraph-pyg
+ * example mag_lp_mnmg.py.  The softmax is per relation and the sum over relations is linear, so it is ONE product:
+ *   s_r[e, h] = u_r[i, h F_r + :] . X_r[j]  +  w_r[i, h D_r + :] . edge_attr_r[e]     (e = (j -> i) of relation r; u, w scaled)
+ *   alpha_r   = softmax over the edges of row i of relation r of s_r[:, h]
+ *   A[i]      = [ blk_r0,0 | ... | blk_r0,(H_0 - 1) | blk_r1,0 | ... | XD[dst_rows[i]] ]          K = sum_r H_r W4_r + F_dst floats
+ *   blk_r,h   = sum_e alpha_r[e, h] [X_r[j] | edge_attr_r[e] | 1 | 0 ...]            W4_r = wgamd_transformer_block_width(F_r, D_r)
+ *   out[out_rows ? out_rows[i] : i] = act( A[i] @ wt^T + bias + acc_in[i] )
+ * Every relation has its own CSR over the same n_rows rows, its own input X_r[j] = x[ids_kind ? src_ids[j] : j] (ids_kind 0: by
+ * row, 1: int32 node list, 2: int64 node list), its own edge_attr [E_r, D] in CSR order (D = 0: none), per-destination vectors
+ * u [n_rows, ldu] and w [n_rows, ldw] (wgamd_transformer_layer_f32's, per relation) and widths F, D, H; col0 is the column of
+ * its first block in A (blocks back to back from 0, in array order; the skip block follows them).  A row without edges in a
+ * relation leaves that relation's blocks exactly zero.  alpha (nullable; [E_r, H], required by _train) receives the relation's
+ * attention weights.  Skip block: XD[r] = x_dst[dst_ids_kind ? dst_ids[r] : r], dst_rows nullable = row i itself, x_dst nullable
+ * = no skip block.  wt [N, ldw] row-major = [ Wstack_r0^T | Wstack_r1^T | ... | sum_r lin_skip_r ]; bias, acc_in ([n_rows,
+ * ld_acc]: the running sum of an earlier launch of the same rows) and out_rows nullable.  _train also writes A ([n_rows, lda],
+ * 16-B aligned rows; the operand of the product): with alpha what wgamd_transformer_bwd_dst_f32 / _bwd_src_f32 read, per
+ * relation, through column slices at col0.  No atomics; sums run in CSR order: run-to-run deterministic.
+ * Domain: wgamd_hetero_transformer_layer_supported (at most WGAMD_HETERO_TRANSFORMER_MAX_RELATIONS relations, every F and F_dst
+ * a multiple of 4 and <= 256, D <= 32, H <= 8, N <= 256, 0 < K <= 1024; F_dst = 0: no skip block); x / x_dst / u / wt rows 16-B
+ * aligned.  The product runs on the exact fp32 matrix pipe (v_mfma_f32_16x16x4_f32). */
+#define WGAMD_HETERO_TRANSFORMER_MAX_RELATIONS 8
+#define WGAMD_HETERO_TRANSFORMER_RELU 1
+typedef struct {
+  const int* row_ptr;
+  const int* col;
+  const float* x;
+  int64_t ldx;
+  const void* src_ids;
+  const float* edge_attr;
+  const float* u;
+  int64_t ldu;
+  const float* w;
+  int64_t ldw;
+  float* alpha;
+  int F;
+  int ids_kind;
+  int D;
+  int H;
+  int col0;
+} wgamd_hetero_transformer_relation_t;
+int wgamd_hetero_transformer_layer_supported(const int* F, const int* D, const int* H, int n_rel, int F_dst, int N);
+wholememory_error_code_t wgamd_hetero_transformer_layer_f32(const wgamd_hetero_transformer_relation_t* rels, int n_rel,
+                                                            int64_t n_rows, const float* x_dst, int64_t ldx_dst, int F_dst,
+                                                            const int64_t* dst_rows, const void* dst_ids, int dst_ids_kind,
+                                                            const float* wt, int64_t ldw, int N, const float* bias, int flags,
+                                                            const float* acc_in, int64_t ld_acc, const int64_t* out_rows,
+                                                            float* out, int64_t ldo, void* stream);
+wholememory_error_code_t wgamd_hetero_transformer_layer_f32_train(const wgamd_hetero_transformer_relation_t* rels, int n_rel,
+                                                                  int64_t n_rows, const float* x_dst, int64_t ldx_dst, int F_dst,
+                                                                  const int64_t* dst_rows, const void* dst_ids, int dst_ids_kind,
+                                                                  const float* wt, int64_t ldw, int N, const float* bias,
+                                                                  int flags, const float* acc_in, int64_t ld_acc,
+                                                                  const int64_t* out_rows, float* out, int64_t ldo, float* a_save,
+                                                                  int64_t lda, void* stream);
+
 /* ---- GIN layer (csrc/wg_gin.hip): torch_geometric.nn.GINConv with the GIN paper's MLP over a sampled hop ----------------------
  * The model of the reference's cugraph-pyg example dist_gin_sg.py (GINConv(MLP([in, hidden, hidden])), then global_add_pool):
  *   agg[i]    = sum_{e = (j -> i)} X[j]  +  (1 + eps) XS[i]          (every edge is summed: loop edges and duplicates too)
