@@ -118,19 +118,21 @@ __device__ __forceinline__ void mfma_valu_interleave()
 // load_a(dst, ks) requests the fp32 A fragment of k-step ks (LDS: AD = 1 k-step ahead; global self rows: AD = 2).  The
 // weight stream is one sequence over the whole kernel — k-step (ks + 2) mod KS is requested in step ks — and the ring is
 // rotated back to position 0 when a range ends, so every range starts with b[0] = its first k-step, b[1] = its second.
-template <int RT, int AD, typename LoadA>
+// RawT: the A fragment as it travels — fp32 (`araw_t`), or the 16-bit self rows of a float16 / bfloat16 table (`araw16_t`),
+// which become fp32 where they are split, a k-step or two after their load was requested.
+template <int RT, int AD, typename RawT = araw_t<RT>, typename LoadA>
 __device__ __forceinline__ void consume_range(const mfma_args& a, f32x16 (&c)[RT][2], bfrag_t (&b)[3], int ks0, int ks1, int cw,
                                               int lane, LoadA load_a)
 {
   const int lm = lane & 31, lh = lane >> 5;
   const int64_t b_plane_dw = (int64_t)a.KS * a.N * 8;
   const uint32_t* b_lane   = reinterpret_cast<const uint32_t*>(a.w_tiles) + ((int64_t)(cw * 64 + lm)) * 8 + lh * 4;
-  araw_t<RT> raw[AD];
+  RawT raw[AD];
   afrag_t<RT> fa[2];
   const int kl = ks1 - 1;
   load_a(raw[0], ks0);
   if constexpr (AD == 2) load_a(raw[1], ks0 + 1 < kl ? ks0 + 1 : kl);
-  split_a<RT>(raw[0], fa[0]);
+  split_raw<RT>(raw[0], fa[0]);
   auto step = [&](auto I, int ks) {
     constexpr int i = decltype(I)::value;
     load_a(raw[i % AD], ks + AD < kl ? ks + AD : kl);
@@ -138,7 +140,7 @@ __device__ __forceinline__ void consume_range(const mfma_args& a, f32x16 (&c)[RT
     kb     = kb >= a.KS ? kb - a.KS : kb;
     load_b_planes(b[(i + 2) % 3], b_lane, b_plane_dw, a.N, kb);
     mma_frags<RT>(c, fa[i & 1], b[i % 3]);
-    split_a<RT>(raw[(i + 1) % AD], fa[(i + 1) & 1]);
+    split_raw<RT>(raw[(i + 1) % AD], fa[(i + 1) & 1]);
     mfma_valu_interleave<4, 6 * RT * 2 - 4, 5>();
     __builtin_amdgcn_sched_barrier(0);
   };
@@ -279,9 +281,13 @@ struct static_consumer {
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
-// CW = N / 64 consumer waves + 4 producer waves; TR = rows per tile; FC = compile-time feature width (0 = runtime a.F)
+// CW = N / 64 consumer waves + 4 producer waves; TR = rows per tile; FC = compile-time feature width (0 = runtime a.F);
+// XT = element type of x (float, _Float16, __bf16: a.x points at rows of it, a.ldx counts elements, a.row_scale bytes).  A 16-bit
+// table changes the ROW LOADS only — 8 B per lane instead of 16, converted to fp32 exactly where the value is summed or split
+// (wg_x16.hpp) — so the lane mapping, the LDS image, the sums' order and every bit of the result are those of the float32 table
+// holding the same values.
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename IdT, int LG, int TR, int CW, bool OFF32, int FC, bool HALF = false>
+template <typename IdT, int LG, int TR, int CW, bool OFF32, int FC, bool HALF = false, typename XT = float>
 __global__ void __launch_bounds__((CW + kProducerWaves) * 64)
 sage_layer_mfma_kernel(mfma_args a)
 {
@@ -349,7 +355,7 @@ sage_layer_mfma_kernel(mfma_args a)
     if (wave >= CW) {
       // the 64-row tile is produced as two 32-row SUB-TILES (sub-tile 2 t + h = rows 32 (2 t + h) ...): eight rows of
       // metadata per lane group in registers instead of sixteen; the metadata pipeline simply runs across the sub-tiles
-      using P     = producer<IdT, LG, 32, OFF32, true>;
+      using P     = producer<IdT, LG, 32, OFF32, true, XT>;
       using off_t = typename P::off_t;
       constexpr int IT = P::IT, kNb = P::kNb, kDepth = P::kDepth;
       static_assert(TR == 64, "two 32-row sub-tiles per tile");
@@ -357,7 +363,7 @@ sage_layer_mfma_kernel(mfma_args a)
       bounds_t<IT> b_next;
       ids_t<IT> i_next;
       meta_t<IT, off_t> cur;
-      f32x4 buf[kDepth][kNb + 1];
+      typename P::raw_t buf[kDepth][kNb + 1];
       p.load_bounds(2 * (int64_t)t_cur, b_next);
       p.load_ids(2 * (int64_t)t_cur, b_next, i_next);
       p.finish(i_next, cur);
@@ -414,12 +420,14 @@ sage_layer_mfma_kernel(mfma_args a)
           const int64_t row0 = (int64_t)t_prev * TR;
           // this lane's self row of every row tile (rows past the end: any row, never stored); the two dependent loads
           // are requested here and waited for after the mean half
-          const float* self_ptr[RT];
+          constexpr int kEB = x16::row_elems<XT>::kBytes;
+          using self_t      = typename std::conditional<kEB == 4, float, uint16_t>::type;   // (an element of x as stored)
+          const self_t* self_ptr[RT];
 #pragma unroll
           for (int rt = 0; rt < RT; rt++) {
             const int64_t row  = row0 + rt * 32 + (lane & 31);
             const int64_t srow = a.self_rows[row < a.n_rows ? row : a.n_rows - 1];
-            self_ptr[rt]       = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.x) + table_row<IdT>(src_ids, srow) * a.row_scale) +
+            self_ptr[rt]       = reinterpret_cast<const self_t*>(reinterpret_cast<const char*>(a.x) + table_row<IdT>(src_ids, srow) * a.row_scale) +
                            (lane >> 5) * 8;
           }
 #pragma unroll
@@ -431,14 +439,24 @@ sage_layer_mfma_kernel(mfma_args a)
           store_agg<TR, CW>(a, lds + ((n - 1) & 1) * tile_dw, row0, wave, lane);
           const float* a_lane = lds + ((n - 1) & 1) * tile_dw + (lane & 31) * a.SD + (lane >> 5) * 8;
           consume_range<RT, 1>(a, c, b, 0, KSh, wave, lane, [&](araw_t<RT>& f, int ks) { load_a_raw<RT>(f, a_lane, a.SD, ks); });
-          consume_range<RT, 2>(a, c, b, KSh, a.KS, wave, lane, [&](araw_t<RT>& f, int ks) {
+          if constexpr (kEB == 4) {
+            consume_range<RT, 2>(a, c, b, KSh, a.KS, wave, lane, [&](araw_t<RT>& f, int ks) {
 #pragma unroll
-            for (int rt = 0; rt < RT; rt++) {
-              const float* p = self_ptr[rt] + (ks - KSh) * 16;
-              f.v[rt][0]     = *reinterpret_cast<const f32x4*>(p);
-              f.v[rt][1]     = *reinterpret_cast<const f32x4*>(p + 4);
-            }
-          });
+              for (int rt = 0; rt < RT; rt++) {
+                const float* p = self_ptr[rt] + (ks - KSh) * 16;
+                f.v[rt][0]     = *reinterpret_cast<const f32x4*>(p);
+                f.v[rt][1]     = *reinterpret_cast<const f32x4*>(p + 4);
+              }
+            });
+          } else {
+            // a 16-bit table: the lane's half k-step is 16 contiguous bytes (8-B aligned: rows are), ONE load, kept as it
+            // came until the k-step is split
+            consume_range<RT, 2, araw16_t<XT, RT>>(a, c, b, KSh, a.KS, wave, lane, [&](araw16_t<XT, RT>& f, int ks) {
+#pragma unroll
+              for (int rt = 0; rt < RT; rt++)
+                f.v[rt] = *reinterpret_cast<const x16::u32x4_a8*>(self_ptr[rt] + (ks - KSh) * 16);
+            });
+          }
           epilogue<RT>(a, c, row0, wave, lane, scratch);
         }
         lds_barrier();
@@ -448,7 +466,7 @@ sage_layer_mfma_kernel(mfma_args a)
     }
   } else if (wave >= CW) {
     if (a.debug & 16) __builtin_amdgcn_s_setprio(3);
-    using P     = producer<IdT, LG, TR, OFF32>;
+    using P     = producer<IdT, LG, TR, OFF32, false, XT>;
     using off_t = typename P::off_t;
     constexpr int IT = P::IT, kNb = P::kNb, kDepth = P::kDepth;
     P p(a, wave - CW, lane);
@@ -458,7 +476,7 @@ sage_layer_mfma_kernel(mfma_args a)
     bounds_t<IT> b_next;
     ids_t<IT> i_next;
     meta_t<IT, off_t> cur;
-    f32x4 buf[kDepth][kNb + 1];
+    typename P::raw_t buf[kDepth][kNb + 1];
     {
       p.load_bounds(t_cur, b_next);
       p.load_ids(t_cur, b_next, i_next);
@@ -684,7 +702,7 @@ __host__ inline bool use_half_tiles(int F)
   return F % 16 == 0 && lds_bytes(F, 64) > kLdsBudget && lds_bytes_half(F) <= kLdsBudget;
 }
 
-template <typename IdT, int LG, int CW>
+template <typename IdT, int LG, int CW, typename XT = float>
 void launch_half(mfma_args a, hipStream_t st)
 {
   const int cus         = stream_cu_count(st);
@@ -698,11 +716,11 @@ void launch_half(mfma_args a, hipStream_t st)
     kern<<<grid, (CW + kProducerWaves) * 64, lds, st>>>(a);
     WG_HIP_CHECK(hipGetLastError());
   };
-  if (a.x_bytes != 0) go(sage_layer_mfma_kernel<IdT, LG, 64, CW, true, 0, true>);
-  else go(sage_layer_mfma_kernel<IdT, LG, 64, CW, false, 0, true>);
+  if (a.x_bytes != 0) go(sage_layer_mfma_kernel<IdT, LG, 64, CW, true, 0, true, XT>);
+  else go(sage_layer_mfma_kernel<IdT, LG, 64, CW, false, 0, true, XT>);
 }
 
-template <typename IdT, int LG, int TR, int CW, int FC = 0>
+template <typename IdT, int LG, int TR, int CW, int FC = 0, typename XT = float>
 void launch(mfma_args a, hipStream_t st)
 {
   const int cus         = stream_cu_count(st);
@@ -717,64 +735,80 @@ void launch(mfma_args a, hipStream_t st)
     kern<<<grid, (CW + kProducerWaves) * 64, lds, st>>>(a);
     WG_HIP_CHECK(hipGetLastError());
   };
-  if (a.x_bytes != 0) go(sage_layer_mfma_kernel<IdT, LG, TR, CW, true, FC>);
-  else go(sage_layer_mfma_kernel<IdT, LG, TR, CW, false, FC>);
+  if (a.x_bytes != 0) go(sage_layer_mfma_kernel<IdT, LG, TR, CW, true, FC, false, XT>);
+  else go(sage_layer_mfma_kernel<IdT, LG, TR, CW, false, FC, false, XT>);
 }
 
 // the feature width is a compile-time constant for the BASELINE layer shapes (F = 100: products, F = 128: papers100M / mag)
 // with N = 256; every other shape takes the runtime-shape consumer
-template <typename IdT, int LG, int TR>
+template <typename IdT, int LG, int TR, typename XT = float>
 void launch_cw(const mfma_args& a, hipStream_t st)
 {
   switch (a.N / 64) {
-    case 1: launch<IdT, LG, TR, 1>(a, st); break;
-    case 2: launch<IdT, LG, TR, 2>(a, st); break;
+    case 1: launch<IdT, LG, TR, 1, 0, XT>(a, st); break;
+    case 2: launch<IdT, LG, TR, 2, 0, XT>(a, st); break;
     default:
       if constexpr (LG == 32 && TR == 64) {
-        if (a.F == 100) return launch<IdT, LG, TR, 4, 100>(a, st);
-        if (a.F == 128) return launch<IdT, LG, TR, 4, 128>(a, st);
+        if (a.F == 100) return launch<IdT, LG, TR, 4, 100, XT>(a, st);
+        if (a.F == 128) return launch<IdT, LG, TR, 4, 128, XT>(a, st);
       }
       // (F = 256, RMAT-26's layers: a compile-time consumer was tried — 32 unrolled k-steps spill 63 VGPRs and lose 13 %;
       //  that shape is bound by its 6 x 2 N_dst 2F N bf16 flops on time-sliced SIMDs, not by the weight prefetch)
-      launch<IdT, LG, TR, 4>(a, st);
+      launch<IdT, LG, TR, 4, 0, XT>(a, st);
       break;
   }
 }
 
 // F <= 128: two whole 64-row tiles; wider rows: 64-row tiles in two halves when the halves are whole k-steps and fit, 32-row
 // tiles otherwise; only the (LG, TR) pairs that can occur are instantiated
-template <typename IdT, int LG>
+template <typename IdT, int LG, typename XT = float>
 void launch_tr(const mfma_args& a, hipStream_t st)
 {
   if constexpr (LG <= 32) {
-    launch_cw<IdT, LG, 64>(a, st);
+    launch_cw<IdT, LG, 64, XT>(a, st);
   } else {
     // (128 < F <= 148: two whole 64-row tiles would fit, but a 64-lane group then carries sixteen rows of metadata per tile
     //  and the kernel spills ~100 VGPRs; 32-row tiles do not)
     if (use_half_tiles(a.F) && !a.full_tiles) {
       switch (a.N / 64) {
-        case 1: launch_half<IdT, LG, 1>(a, st); break;
-        case 2: launch_half<IdT, LG, 2>(a, st); break;
-        default: launch_half<IdT, LG, 4>(a, st); break;
+        case 1: launch_half<IdT, LG, 1, XT>(a, st); break;
+        case 2: launch_half<IdT, LG, 2, XT>(a, st); break;
+        default: launch_half<IdT, LG, 4, XT>(a, st); break;
       }
-    } else launch_cw<IdT, LG, 32>(a, st);
+    } else launch_cw<IdT, LG, 32, XT>(a, st);
   }
 }
 
-template <typename IdT>
+template <typename IdT, typename XT = float>
 void launch_groups(const mfma_args& a, hipStream_t st)
 {
   const int units = a.F / 4;
-  if (units <= 8) launch_tr<IdT, 8>(a, st);
-  else if (units <= 16) launch_tr<IdT, 16>(a, st);
-  else if (units <= 32) launch_tr<IdT, 32>(a, st);
-  else launch_tr<IdT, 64>(a, st);
+  if (units <= 8) launch_tr<IdT, 8, XT>(a, st);
+  else if (units <= 16) launch_tr<IdT, 16, XT>(a, st);
+  else if (units <= 32) launch_tr<IdT, 32, XT>(a, st);
+  else launch_tr<IdT, 64, XT>(a, st);
 }
 
 }  // namespace
+
+// The kernels of a float16 / bfloat16 table are built in translation units of their own — wg_sage_mfma_f16.hip and
+// wg_sage_mfma_bf16.hip include this file with WG_SAGE_X16_TYPE set — which compile next to this one instead of behind it (this
+// file is the longest of the library's build).  `ids_bytes`: 0 = x read by row, 4 / 8 = through int32 / int64 row numbers.
+namespace sage_mfma {
+void launch_f16(const mfma_args& a, int ids_bytes, hipStream_t st);
+void launch_bf16(const mfma_args& a, int ids_bytes, hipStream_t st);
+#ifdef WG_SAGE_X16_TYPE
+void WG_SAGE_X16_LAUNCH(const mfma_args& a, int ids_bytes, hipStream_t st)
+{
+  if (ids_bytes == 0) launch_groups<void, WG_SAGE_X16_TYPE>(a, st);
+  else if (ids_bytes == 4) launch_groups<int32_t, WG_SAGE_X16_TYPE>(a, st);
+  else launch_groups<int64_t, WG_SAGE_X16_TYPE>(a, st);
+}
+#endif
+}  // namespace sage_mfma
 }  // namespace wgamd
 
-#ifndef WG_MFMA_TUNE_HARNESS
+#if !defined(WG_MFMA_TUNE_HARNESS) && !defined(WG_SAGE_X16_TYPE)
 // (sized for the larger of the two formats: bf16 planes are 96 B per (k-step, column), fp32 tiles 64 B)
 extern "C" size_t wgamd_sage_weight_planes_bytes(int K, int N) { return (size_t)3 * ((K + 15) / 16) * (size_t)N * 32; }
 
@@ -826,8 +860,8 @@ extern "C" wholememory_error_code_t wgamd_sage_layer_fused_bf16x3(const int* row
                                                                   int N, const float* bias, int relu, float* out, int64_t ldo,
                                                                   void* stream)
 {
-  return wgamd_sage_layer_fused_bf16x3_train(row_ptr, col, n_rows, x, ldx, x_rows, F, src_ids, src_ids_dtype, self_rows, mean,
-                                             w_planes, N, bias, relu, out, ldo, nullptr, 0, stream);
+  return wgamd_sage_layer_fused_bf16x3_x_train(row_ptr, col, n_rows, x, WHOLEMEMORY_DT_FLOAT, ldx, x_rows, F, src_ids, src_ids_dtype,
+                                               self_rows, mean, w_planes, N, bias, relu, out, ldo, nullptr, 0, stream);
 }
 
 extern "C" wholememory_error_code_t wgamd_sage_layer_fused_bf16x3_train(const int* row_ptr, const int* col, int64_t n_rows,
@@ -837,33 +871,78 @@ extern "C" wholememory_error_code_t wgamd_sage_layer_fused_bf16x3_train(const in
                                                                         int N, const float* bias, int relu, float* out,
                                                                         int64_t ldo, float* agg_out, int64_t ld_agg, void* stream)
 {
+  return wgamd_sage_layer_fused_bf16x3_x_train(row_ptr, col, n_rows, x, WHOLEMEMORY_DT_FLOAT, ldx, x_rows, F, src_ids, src_ids_dtype,
+                                               self_rows, mean, w_planes, N, bias, relu, out, ldo, agg_out, ld_agg, stream);
+}
+
+extern "C" int wgamd_sage_layer_x16_supported(int F, int N, wholememory_dtype_t x_dtype)
+{
+  return (x_dtype == WHOLEMEMORY_DT_FLOAT || x_dtype == WHOLEMEMORY_DT_HALF || x_dtype == WHOLEMEMORY_DT_BF16) &&
+         wgamd_sage_layer_bf16x3_supported(F, N);
+}
+
+extern "C" wholememory_error_code_t wgamd_sage_layer_fused_bf16x3_x(const int* row_ptr, const int* col, int64_t n_rows,
+                                                                    const void* x, wholememory_dtype_t x_dtype, int64_t ldx,
+                                                                    int64_t x_rows, int F, const void* src_ids,
+                                                                    wholememory_dtype_t src_ids_dtype, const int64_t* self_rows,
+                                                                    int mean, const void* w_planes, int N, const float* bias,
+                                                                    int relu, float* out, int64_t ldo, void* stream)
+{
+  return wgamd_sage_layer_fused_bf16x3_x_train(row_ptr, col, n_rows, x, x_dtype, ldx, x_rows, F, src_ids, src_ids_dtype, self_rows,
+                                               mean, w_planes, N, bias, relu, out, ldo, nullptr, 0, stream);
+}
+
+extern "C" wholememory_error_code_t wgamd_sage_layer_fused_bf16x3_x_train(const int* row_ptr, const int* col, int64_t n_rows,
+                                                                          const void* x, wholememory_dtype_t x_dtype, int64_t ldx,
+                                                                          int64_t x_rows, int F, const void* src_ids,
+                                                                          wholememory_dtype_t src_ids_dtype, const int64_t* self_rows,
+                                                                          int mean, const void* w_planes, int N, const float* bias,
+                                                                          int relu, float* out, int64_t ldo, float* agg_out,
+                                                                          int64_t ld_agg, void* stream)
+{
   using namespace wgamd;
   return guarded("wgamd_sage_layer_fused_bf16x3", [&] {
     WG_REQUIRE_INPUT(n_rows >= 0 && F > 0 && N > 0, "bad sizes");
+    const bool x32 = x_dtype == WHOLEMEMORY_DT_FLOAT;
+    if (!x32 && x_dtype != WHOLEMEMORY_DT_HALF && x_dtype != WHOLEMEMORY_DT_BF16) throw invalid_input("x must be FLOAT, HALF or BF16");
     if (n_rows == 0) return;
     WG_REQUIRE_INPUT(row_ptr && col && x && self_rows && w_planes && out, "null pointer");
-    if (!wgamd_sage_layer_bf16x3_supported(F, N) || ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(x) & 15) != 0)
-      throw logic_error(fmt("unsupported shape: F=%d (multiple of 4, <= 256), N=%d (64, 128 or 256), 16-B aligned rows", F, N));
+    // a lane loads its four features at once: 16 B of a float32 row, 8 B of a 16-bit one
+    const int64_t eb = x32 ? 4 : 2;
+    if (!wgamd_sage_layer_bf16x3_supported(F, N) || ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(x) & (uintptr_t)(4 * eb - 1)) != 0)
+      throw logic_error(fmt("unsupported shape: F=%d (multiple of 4, <= 256), N=%d (64, 128 or 256), %d-B aligned rows", F, N,
+                            (int)(4 * eb)));
     WG_REQUIRE_INPUT(ldo >= N, "leading dimension smaller than N");
     WG_REQUIRE_INPUT(n_rows < ((int64_t)1 << 36), "too many rows for 32-bit tile numbers");
     if (ldo % 4 != 0 || (reinterpret_cast<uintptr_t>(out) & 15) != 0) throw logic_error("output rows must be 16-B aligned");
     if (agg_out != nullptr && (ld_agg < F || ld_agg % 4 != 0 || (reinterpret_cast<uintptr_t>(agg_out) & 15) != 0))
       throw logic_error("agg_out rows must hold F floats and be 16-B aligned");
     // x below 2 GB (extent known): 32-bit row offsets and buffer loads whose out-of-range slots read as zero
-    const uint64_t xb = x_rows > 0 ? (uint64_t)x_rows * (uint64_t)ldx * 4u : 0;
-    mfma_args a{row_ptr, col, n_rows, x, ldx, (uint32_t)(xb > 0 && xb < (1ull << 31) ? xb : 0), F, src_ids, self_rows, mean,
-                static_cast<const float*>(w_planes), N, (2 * F + 15) / 16, bias, relu & 1, out, ldo, row_stride_dw(F), 0, nullptr,
-                ldx * 4, agg_out, ld_agg, (relu & WGAMD_SAGE_FULL_TILES) != 0};
+    const uint64_t xb = x_rows > 0 ? (uint64_t)x_rows * (uint64_t)ldx * (uint64_t)eb : 0;
+    mfma_args a{row_ptr, col, n_rows, static_cast<const float*>(x), ldx, (uint32_t)(xb > 0 && xb < (1ull << 31) ? xb : 0), F, src_ids,
+                self_rows, mean, static_cast<const float*>(w_planes), N, (2 * F + 15) / 16, bias, relu & 1, out, ldo, row_stride_dw(F), 0,
+                nullptr, ldx * eb, agg_out, ld_agg, (relu & WGAMD_SAGE_FULL_TILES) != 0};
     const bool byte_offsets = src_ids != nullptr && src_ids_dtype == WGAMD_IDS_BYTE_OFFSETS;
     if (byte_offsets) {      // rows addressed by byte offsets from x (a peer-mapped table): 64-bit addressing, no extent
+      if (!x32) throw logic_error("byte-offset ids (a peer-mapped table) are read as float32 rows only; a float16 / bfloat16 table is not");
       a.row_scale = 1;
       a.x_bytes   = 0;
     }
     auto st = static_cast<hipStream_t>(stream);
+    if (!x32) {
+      int ids_bytes = 0;
+      if (src_ids != nullptr) {
+        if (src_ids_dtype != WHOLEMEMORY_DT_INT && src_ids_dtype != WHOLEMEMORY_DT_INT64) throw invalid_input("src_ids of a 16-bit x must be INT or INT64");
+        ids_bytes = src_ids_dtype == WHOLEMEMORY_DT_INT ? 4 : 8;
+      }
+      if (x_dtype == WHOLEMEMORY_DT_HALF) sage_mfma::launch_f16(a, ids_bytes, st);
+      else sage_mfma::launch_bf16(a, ids_bytes, st);
+      return;
+    }
     if (src_ids == nullptr) launch_groups<void>(a, st);
     else if (src_ids_dtype == WHOLEMEMORY_DT_INT) launch_groups<int32_t>(a, st);
     else if (src_ids_dtype == WHOLEMEMORY_DT_INT64 || byte_offsets) launch_groups<int64_t>(a, st);
     else throw invalid_input("src_ids must be INT, INT64 or WGAMD_IDS_BYTE_OFFSETS");
   });
 }
-#endif  // WG_MFMA_TUNE_HARNESS
+#endif  // WG_MFMA_TUNE_HARNESS, WG_SAGE_X16_TYPE

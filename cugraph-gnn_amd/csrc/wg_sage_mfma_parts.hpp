@@ -10,6 +10,7 @@
 
 #include "wg_common.hpp"
 #include "wgamd_ext.h"
+#include "wg_x16.hpp"
 
 namespace wgamd {
 namespace sage_mfma {
@@ -119,8 +120,11 @@ struct meta_t {
   off_t self[IT];  // byte offset of the self row
 };
 
-template <typename IdT, int LG, int TR, bool OFF32, bool HALF = false>
+template <typename IdT, int LG, int TR, bool OFF32, bool HALF = false, typename XT = float>
 struct producer {
+  using E                             = x16::row_elems<XT>;   // float32 rows: 16 B per lane; float16 / bfloat16 rows: 8 B
+  using raw_t                         = typename E::raw_t;    // a lane's four features as they travel (converted where consumed)
+  static constexpr int kEB            = E::kBytes;
   using off_t                         = typename std::conditional<OFF32, uint32_t, int64_t>::type;
   static constexpr int kGroupsPerWave = 64 / LG;
   static constexpr int kGroups        = kGroupsPerWave * kProducerWaves;
@@ -147,6 +151,14 @@ struct producer {
   }
 
   __device__ __forceinline__ int64_t row_of(int64_t tile, int it) const { return tile * TR + group + it * kGroups; }
+
+  // this lane's four features of the row at byte offset `off` (+ its feature offset, added by the caller): ONE load either way
+  __device__ __forceinline__ raw_t bload(uint32_t off) const
+  {
+    if constexpr (kEB == 4) return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0));
+    else return __builtin_bit_cast(raw_t, __builtin_amdgcn_raw_buffer_load_b64(rsrc, off, 0, 0));
+  }
+  __device__ __forceinline__ raw_t gload(const char* p) const { return *reinterpret_cast<const raw_t*>(p); }
 
   // stage A: CSR bounds of the next tile (requested when a tile starts)
   __device__ __forceinline__ void load_bounds(int64_t tile, bounds_t<IT>& b) const
@@ -183,7 +195,7 @@ struct producer {
     }
   }
   // request the kNb neighbour rows + the self row of row `it`; every load is unconditional
-  __device__ __forceinline__ void issue(const meta_t<IT, off_t>& m, int it, f32x4* v) const
+  __device__ __forceinline__ void issue(const meta_t<IT, off_t>& m, int it, raw_t* v) const
   {
 #ifndef WG_ISSUE_READLANE64
 #define WG_ISSUE_READLANE64 1
@@ -208,11 +220,10 @@ struct producer {
 #pragma unroll
       for (int k = 0; k < kNb; k++) {
         const uint32_t off = (uint32_t)__shfl((int)m.src[it], gbase | (k & (LG - 1)), 64);
-        v[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, k < m.d[it] ? off + f0c * 4 : a.x_bytes, 0, 0));
+        v[k] = bload(k < m.d[it] ? off + f0c * kEB : a.x_bytes);
       }
       if constexpr (!HALF)
-        v[kNb] = __builtin_bit_cast(
-          f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, m.d[it] >= 0 ? (uint32_t)m.self[it] + f0c * 4 : a.x_bytes, 0, 0));
+        v[kNb] = bload(m.d[it] >= 0 ? (uint32_t)m.self[it] + f0c * kEB : a.x_bytes);
     } else {
       const char* xb = reinterpret_cast<const char*>(a.x);
 #pragma unroll
@@ -222,10 +233,10 @@ struct producer {
         const int hi       = __shfl((int)((int64_t)m.src[it] >> 32), src_lane, 64);
         int64_t off        = ((int64_t)hi << 32) | (uint32_t)lo;
         off                = k < m.d[it] ? off : (int64_t)0;   // slots past the degree read row 0 (L1-resident), masked below
-        v[k]               = *reinterpret_cast<const f32x4*>(xb + off + f0c * 4);
+        v[k]               = gload(xb + off + f0c * kEB);
       }
       if constexpr (!HALF)
-        v[kNb] = *reinterpret_cast<const f32x4*>(xb + (m.d[it] >= 0 ? (int64_t)m.self[it] : (int64_t)0) + f0c * 4);
+        v[kNb] = gload(xb + (m.d[it] >= 0 ? (int64_t)m.self[it] : (int64_t)0) + f0c * kEB);
     }
   }
   // 32-lane groups, the cheapest form: ONE v_permlane16_swap (gfx950) of the offset register with itself yields the register
@@ -237,22 +248,21 @@ struct producer {
   // (Also tried on top of it: dead slots pointing at a ZERO row so that the sum needs no per-slot select either — 40 fewer
   //  instructions per row and SLOWER, 1.57 -> 1.615 ms; not kept.)
   template <int k>
-  __device__ __forceinline__ void issue_dpp_one(const meta_t<IT, off_t>& m, int it, f32x4* v, int dlo, int dhi) const
+  __device__ __forceinline__ void issue_dpp_one(const meta_t<IT, off_t>& m, int it, raw_t* v, int dlo, int dhi) const
   {
     if constexpr (k < kNb) {
       const int lo = __builtin_amdgcn_update_dpp(0, dlo, 0x150 + k, 0xf, 0xf, false);
       if constexpr (OFF32) {
-        v[k] = __builtin_bit_cast(
-          f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, k < m.d[it] ? (uint32_t)lo + f0c * 4 : a.x_bytes, 0, 0));
+        v[k] = bload(k < m.d[it] ? (uint32_t)lo + f0c * kEB : a.x_bytes);
       } else {
         const int hi      = __builtin_amdgcn_update_dpp(0, dhi, 0x150 + k, 0xf, 0xf, false);
         const int64_t off = ((int64_t)hi << 32) | (uint32_t)lo;   // (lanes past the degree hold a valid row's offset: masked in reduce_store)
-        v[k]              = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(a.x) + off + f0c * 4);
+        v[k]              = gload(reinterpret_cast<const char*>(a.x) + off + f0c * kEB);
       }
       issue_dpp_one<k + 1>(m, it, v, dlo, dhi);
     }
   }
-  __device__ __forceinline__ void issue_dpp(const meta_t<IT, off_t>& m, int it, f32x4* v) const
+  __device__ __forceinline__ void issue_dpp(const meta_t<IT, off_t>& m, int it, raw_t* v) const
   {
     static_assert(kNb <= 16, "the first window sits in the even row of the group");
     const int slo = (int)((uint64_t)m.src[it] & 0xffffffffu);
@@ -280,7 +290,7 @@ struct producer {
     }
   }
   template <int k>
-  __device__ __forceinline__ void issue_all(const meta_t<IT, off_t>& m, int it, f32x4* v) const
+  __device__ __forceinline__ void issue_all(const meta_t<IT, off_t>& m, int it, raw_t* v) const
   {
     if constexpr (k < kNb + (HALF ? 0 : 1)) {
       issue_one<k>(m, it, v);
@@ -289,16 +299,15 @@ struct producer {
   }
   // ONE of the kNb + 1 loads of issue(): load k of row `it` (k == kNb: the self row)
   template <int k>
-  __device__ __forceinline__ void issue_one(const meta_t<IT, off_t>& m, int it, f32x4* v) const
+  __device__ __forceinline__ void issue_one(const meta_t<IT, off_t>& m, int it, raw_t* v) const
   {
     static_assert(!HALF || k < kNb, "no self slot in half-tile mode");
     if constexpr (OFF32) {
       if constexpr (k < kNb) {
         const uint32_t off = (uint32_t)group_lane<k>((int)m.src[it]);
-        v[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, k < m.d[it] ? off + f0c * 4 : a.x_bytes, 0, 0));
+        v[k] = bload(k < m.d[it] ? off + f0c * kEB : a.x_bytes);
       } else {
-        v[kNb] = __builtin_bit_cast(
-          f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, m.d[it] >= 0 ? (uint32_t)m.self[it] + f0c * 4 : a.x_bytes, 0, 0));
+        v[kNb] = bload(m.d[it] >= 0 ? (uint32_t)m.self[it] + f0c * kEB : a.x_bytes);
       }
     } else {
       const char* xb = reinterpret_cast<const char*>(a.x);
@@ -307,28 +316,28 @@ struct producer {
         const int hi = group_lane<k>((int)((int64_t)m.src[it] >> 32));
         int64_t off  = ((int64_t)hi << 32) | (uint32_t)lo;
         off          = k < m.d[it] ? off : (int64_t)0;
-        v[k]         = *reinterpret_cast<const f32x4*>(xb + off + f0c * 4);
+        v[k]         = gload(xb + off + f0c * kEB);
       } else {
-        v[kNb] = *reinterpret_cast<const f32x4*>(xb + (m.d[it] >= 0 ? (int64_t)m.self[it] : (int64_t)0) + f0c * 4);
+        v[kNb] = gload(xb + (m.d[it] >= 0 ? (int64_t)m.self[it] : (int64_t)0) + f0c * kEB);
       }
     }
   }
   // sum row `it` from its ring slot (CSR order) and store [mean | self] as fp32
-  __device__ __forceinline__ void reduce_store(const meta_t<IT, off_t>& m, int it, const f32x4* v, float* tile_lds) const
+  __device__ __forceinline__ void reduce_store(const meta_t<IT, off_t>& m, int it, const raw_t* v, float* tile_lds) const
   {
     const int deg = m.d[it];
     f32x4 acc     = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int k = 0; k < kNb; k++) {
-      if constexpr (OFF32) acc += v[k];                                   // the hardware already zeroed the dead slots
-      else acc += k < deg ? v[k] : f32x4{0.f, 0.f, 0.f, 0.f};             // select, never multiply by 0
+      if constexpr (OFF32) acc += E::f32(v[k]);                                   // the hardware already zeroed the dead slots
+      else acc += k < deg ? E::f32(v[k]) : f32x4{0.f, 0.f, 0.f, 0.f};             // select, never multiply by 0
     }
     if (a.mean && deg > 0 && deg <= kNb) acc *= __frcp_rn((float)deg);   // (longer rows: long_rows() continues this sum)
     if (live) {
       float* prow = tile_lds + (group + it * kGroups) * a.SD;
       *reinterpret_cast<f32x4*>(prow + f0) = acc;
       if constexpr (!HALF) {
-        f32x4 self = v[kNb];
+        f32x4 self = E::f32(v[kNb]);
         if constexpr (!OFF32) self = deg >= 0 ? self : f32x4{0.f, 0.f, 0.f, 0.f};
         *reinterpret_cast<f32x4*>(prow + a.F + f0) = self;
       }
@@ -347,19 +356,19 @@ struct producer {
         const int deg = m.d[it];
         if (__ballot(deg > kNb) == 0ull) continue;
         const bool mine = live && deg > kNb;
-        f32x4 v[kW2];
+        raw_t v[kW2];
 #pragma unroll
         for (int k = 0; k < kW2; k++) {
           const int kk = kNb + k;
           if constexpr (OFF32) {
             const uint32_t off = (uint32_t)__shfl((int)m.src[it], gbase | kk, 64);
-            v[k] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, kk < deg ? off + f0c * 4 : a.x_bytes, 0, 0));
+            v[k] = bload(kk < deg ? off + f0c * kEB : a.x_bytes);
           } else {
             const int lo = __shfl((int)(m.src[it] & 0xffffffff), gbase | kk, 64);
             const int hi = __shfl((int)((int64_t)m.src[it] >> 32), gbase | kk, 64);
             int64_t off  = ((int64_t)hi << 32) | (uint32_t)lo;
             off          = kk < deg ? off : (int64_t)0;
-            v[k]         = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(a.x) + off + f0c * 4);
+            v[k]         = gload(reinterpret_cast<const char*>(a.x) + off + f0c * kEB);
           }
         }
         float* prow = tile_lds + (group + it * kGroups) * a.SD + f0;
@@ -367,8 +376,8 @@ struct producer {
         if (mine) acc = *reinterpret_cast<const f32x4*>(prow);
 #pragma unroll
         for (int k = 0; k < kW2; k++) {
-          if constexpr (OFF32) acc += v[k];
-          else acc += kNb + k < deg ? v[k] : f32x4{0.f, 0.f, 0.f, 0.f};
+          if constexpr (OFF32) acc += E::f32(v[k]);
+          else acc += kNb + k < deg ? E::f32(v[k]) : f32x4{0.f, 0.f, 0.f, 0.f};
         }
         if (mine) {
           if (a.mean && deg <= kNb + kW2) acc *= __frcp_rn((float)deg);
@@ -409,7 +418,7 @@ struct producer {
         const int64_t my_src = (deg > kStart && c0 + sub < deg) ? table_row<IdT>(src_ids, (int64_t)a.col[s + c0 + sub]) : 0;
         const int chunk      = min(LG, maxdeg - c0);
         for (int j0 = 0; j0 < chunk; j0 += kUnroll) {
-          f32x4 v[kUnroll];
+          raw_t v[kUnroll];
 #pragma unroll
           for (int u = 0; u < kUnroll; u++) {
             const int j        = j0 + u;
@@ -418,12 +427,12 @@ struct producer {
             const int hi       = __shfl((int)(my_src >> 32), src_lane, 64);
             const int64_t rr   = (mine && j < chunk && c0 + j < deg) ? (((int64_t)hi << 32) | (uint32_t)lo) : (int64_t)0;
             // (dead slots read row 0, masked below)
-            v[u] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(a.x) + rr * a.row_scale + f0c * 4);
+            v[u] = gload(reinterpret_cast<const char*>(a.x) + rr * a.row_scale + f0c * kEB);
           }
 #pragma unroll
           for (int u = 0; u < kUnroll; u++) {
             const int j = j0 + u;
-            acc += (mine && j < chunk && c0 + j < deg) ? v[u] : f32x4{0.f, 0.f, 0.f, 0.f};
+            acc += (mine && j < chunk && c0 + j < deg) ? E::f32(v[u]) : f32x4{0.f, 0.f, 0.f, 0.f};
           }
         }
       }
@@ -441,6 +450,11 @@ struct producer {
 template <int RT>
 struct araw_t {
   f32x4 v[RT][2];  // [row tile][k 0-3 | k 4-7 of this lane's half k-step]
+};
+// a lane's half k-step of its self row as it travels from a float16 / bfloat16 table (HALF mode): 8 elements = ONE 16-B load
+template <typename XT, int RT>
+struct araw16_t {
+  x16::u32x4 v[RT];
 };
 template <int RT>
 struct afrag_t {
@@ -490,6 +504,23 @@ __device__ __forceinline__ void split_a(const araw_t<RT>& r, afrag_t<RT>& f)
       f.v[rt][2][j] = pack_hi16(l[2 * j], l[2 * j + 1]);
     }
   }
+}
+// the fragment as it travelled -> the three planes: fp32 as it is; 16-bit self rows become fp32 first (exact, wg_x16.hpp)
+template <int RT>
+__device__ __forceinline__ void split_raw(const araw_t<RT>& r, afrag_t<RT>& f)
+{
+  split_a<RT>(r, f);
+}
+template <int RT, typename XT>
+__device__ __forceinline__ void split_raw(const araw16_t<XT, RT>& r, afrag_t<RT>& f)
+{
+  araw_t<RT> w;
+#pragma unroll
+  for (int rt = 0; rt < RT; rt++) {
+    w.v[rt][0] = x16::to_f32x4<XT>(x16::u32x2{r.v[rt][0], r.v[rt][1]});
+    w.v[rt][1] = x16::to_f32x4<XT>(x16::u32x2{r.v[rt][2], r.v[rt][3]});
+  }
+  split_a<RT>(w, f);
 }
 // The weight travels as fp32 (4 B per element) and is split into its three bf16 planes by the multiplying wave, in the issue
 // slots under its own MFMAs — the pre-split planes of round 2 were 6 B per element, and the weight stream (once per 64-row

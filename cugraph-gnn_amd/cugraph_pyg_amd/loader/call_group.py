@@ -25,6 +25,11 @@ from wholegraph_amd.env import get_stream
 from wholegraph_amd.nn import HeteroLayerGraph, HopGraph, LayerGraph, LazyRows, RelationHop, mapped_lazy_rows
 
 
+# tables a call group hands out as ``LazyRows``: float32, and the 16-bit types the reference's users store features in
+# (nn.SAGEConv reads them in its layer kernel; every other layer gets float32 rows from one converting gather)
+_LAZY_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+
+
 def _peer_mapped_f32(wm) -> bool:
     """A handle-backed float32 [rows, F] table whose partitions are all addressable from this GPU (CHUNKED / CONTINUOUS over
     more than one rank of a node)."""
@@ -101,8 +106,14 @@ class CallGroup:
 
     def node_attr(self, name: str, group_name=None, lazy: bool = True):
         """A stored node attribute for all rows of the call group: ``LazyRows`` (table + ``n_id``, nothing gathered) when
-        the table is a float32 matrix held whole on this device and ``lazy``; the gathered rows otherwise (one fetch per
-        call group — a collective when the FeatureStore is partitioned)."""
+        the table is a float32, float16 or bfloat16 matrix held whole on this device and ``lazy``; the gathered rows
+        otherwise (one fetch per call group — a collective when the FeatureStore is partitioned).
+
+        A 16-bit table (features stored as the reference's examples store them) takes half the HBM.  ``nn.SAGEConv`` reads
+        its rows in the layer kernel and converts them to float32 exactly — the result is bit for bit that of the float32
+        table holding the same values; every other layer gets float32 rows from one converting gather
+        (``LazyRows.materialize()``).  Whether the layer-1 launch is also faster than
+        over a float32 table is not measured: the feature is there for the HBM it frees."""
         from ..sampler.sampler import _fetch_rows_agreed
         self._wait()
         if group_name is None:
@@ -115,7 +126,7 @@ class CallGroup:
         wm = getattr(t, "_tensor", None)
         table = getattr(wm, "local_tensor", None)
         if (lazy and table is not None and not getattr(wm, "is_distributed", True) and table.is_cuda and table.dim() == 2
-                and table.dtype == torch.float32 and table.stride(1) == 1):
+                and table.dtype in _LAZY_DTYPES and table.stride(1) == 1):
             return LazyRows(table, self.n_id)
         if lazy and _peer_mapped_f32(wm):
             return mapped_lazy_rows(wm, self.n_id)      # partitions on several GPUs, every one mapped here: read in the layer
@@ -333,7 +344,9 @@ class HeteroCallGroup:
 
     def node_attr(self, name: str, lazy: bool = True):
         """{node type: attribute rows of its vertices} — ``LazyRows`` (table + ids, nothing gathered: the first layer's
-        gather makes its attention logits in the same pass) where the table lives whole on this device, gathered otherwise."""
+        gather makes its attention logits in the same pass) where the table (float32, float16 or bfloat16) lives whole on this
+        device, gathered otherwise.  The layers of a heterogeneous model work on float32 rows: a 16-bit table is converted by
+        the one gather that ``LazyRows.materialize()`` is (the hetero SAGE kernel reads float32 tables only)."""
         from ..sampler.sampler import _fetch_rows_agreed
         self._wait()
         have = {a.group_name for a in self._fs.get_all_tensor_attrs() if a.attr_name == name and not isinstance(a.group_name, tuple)}
@@ -345,7 +358,7 @@ class HeteroCallGroup:
             wm = getattr(ten, "_tensor", None)
             table = getattr(wm, "local_tensor", None)
             if (lazy and table is not None and not getattr(wm, "is_distributed", True) and table.is_cuda and table.dim() == 2
-                    and table.dtype == torch.float32 and table.stride(1) == 1):
+                    and table.dtype in _LAZY_DTYPES and table.stride(1) == 1):
                 out[t] = LazyRows(table, ids[t])
             else:
                 out[t] = _fetch_rows_agreed(ten, ids[t])

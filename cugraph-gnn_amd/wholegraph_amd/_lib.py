@@ -264,6 +264,12 @@ SYMBOLS = {
     "wgamd_sage_layer_fused_bf16x3_train": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int,
                                                     c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64,
                                                     c_void_p, c_int64, c_void_p]),
+    "wgamd_sage_layer_x16_supported": (c_int, [c_int, c_int, c_int]),
+    "wgamd_sage_layer_fused_bf16x3_x": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p, c_int,
+                                                c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "wgamd_sage_layer_fused_bf16x3_x_train": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int64, c_int64, c_int, c_void_p,
+                                                      c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64,
+                                                      c_void_p, c_int64, c_void_p]),
     "wgamd_sage_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "wgamd_sage_wgrad_bf16x3": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p,
                                         c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,

@@ -34,6 +34,9 @@ from . import _lib as L
 from .env import get_stream, torch_dtype_to_wm
 
 
+_X16 = (torch.float16, torch.bfloat16)      # feature tables the bf16x3 SAGE layer kernel reads as they are (wgamd_sage_layer_fused_bf16x3_x)
+
+
 def _ids_code(x, src_ids) -> int:
     """``src_ids_dtype`` of the layer kernels: the ids' integer type, or WGAMD_IDS_BYTE_OFFSETS when ``x`` is the address space of
     a peer-mapped table (``MappedTable``) and ``src_ids`` holds byte offsets into it."""
@@ -303,9 +306,13 @@ def sage_layer_fused_forward(row_ptr, col, x, self_rows, w_t, bias=None, relu=Fa
     in too).  ``w_t`` = ``cat([W_l, W_r], 1).t()`` ([2F, N], contiguous).  The ``[n_rows, 2F]`` operand never leaves LDS.
     ``precision``: "bf16x3" (default where the shape allows) or "f32" — see ``_FUSED_PRECISION``.
     ``agg_out`` ([n_rows, F] fp32, training): the launch also keeps the aggregate half of its operand there
-    (``wgamd_sage_layer_fused_bf16x3_train``; same bits in ``out``) — needs ``sage_layer_train_supported``."""
+    (``wgamd_sage_layer_fused_bf16x3_train``; same bits in ``out``) — needs ``sage_layer_train_supported``.
+    ``x`` may be ``torch.float16`` / ``torch.bfloat16`` on the bf16x3 route (``wgamd_sage_layer_fused_bf16x3_x``: rows 8-B
+    aligned, read by row or through int32 / int64 ids): every stored value becomes fp32 exactly as it is read, ``out`` and
+    ``agg_out`` are float32 and bit for bit those of the same call on ``x.float()``.  The fp32-MFMA route refuses such an ``x``."""
     _check_csr(row_ptr, col)
-    assert x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1
+    x16 = x.dtype in _X16
+    assert (x.dtype == torch.float32 or x16) and x.dim() == 2 and x.stride(1) == 1
     assert self_rows.dtype == torch.int64 and self_rows.is_contiguous()
     if prepared is not None:      # (planes, padded bias, N) of sage_layer_planes: the bf16x3 kernel's operand, ready made
         n_rows, F_, N = row_ptr.shape[0] - 1, x.shape[1], prepared[2]
@@ -343,6 +350,22 @@ def sage_layer_fused_forward(row_ptr, col, x, self_rows, w_t, bias=None, relu=Fa
     ids_ptr, ids_dt = _ids_args(x, src_ids)
     # (an edge-less hop: an empty tensor's null pointer is refused by the entry points; every row is empty, so the stand-in is not read)
     col_ptr = _nonempty(col, torch.int32).data_ptr()
+    if x16:
+        if ids_dt == L.IDS_BYTE_OFFSETS:
+            raise ValueError("a peer-mapped table (byte-offset ids) is read as float32 rows only, not as %s" % x.dtype)
+        if not (sage_layer_fused_supported(F_, N) and _pick_precision(F_, N, precision) == "bf16x3"
+                and out.stride(0) % 4 == 0 and out.data_ptr() % 16 == 0):
+            raise ValueError("a %s x is read by the bf16x3 layer kernel only (precision=%r, F=%d, N=%d): pass x.float()"
+                             % (x.dtype, precision or _FUSED_PRECISION, F_, N))
+        planes = prepared[0] if prepared is not None else sage_weight_planes(w_t)
+        flags = int(bool(relu)) | (SAGE_FULL_TILES if prepared is not None and prepared[3] else 0)
+        assert agg_out is None or (agg_out.shape == (n_rows, F_) and agg_out.dtype == torch.float32 and agg_out.stride(1) == 1)
+        L.check(L.lib().wgamd_sage_layer_fused_bf16x3_x_train(
+            row_ptr.data_ptr(), col_ptr, n_rows, x.data_ptr(), torch_dtype_to_wm(x.dtype), x.stride(0), x.shape[0], F_, ids_ptr,
+            ids_dt, self_rows.data_ptr(), int(bool(mean)), planes.data_ptr(), N, None if bias is None else bias.data_ptr(),
+            flags, out.data_ptr(), out.stride(0), _ptr(agg_out), 0 if agg_out is None else agg_out.stride(0), get_stream()),
+            "wgamd_sage_layer_fused_bf16x3_x_train")
+        return done(out)
     assert ids_dt != L.IDS_BYTE_OFFSETS or (sage_layer_fused_supported(F_, N) and _pick_precision(F_, N, precision) == "bf16x3"), \
         "a peer-mapped table is read by the bf16x3 layer kernel only"
     if (sage_layer_fused_supported(F_, N) and _pick_precision(F_, N, precision) == "bf16x3"
@@ -980,7 +1003,14 @@ class LazyRows:
     whole on this device (single GPU, or replicated).  ``nn.SAGEConv`` consumes it as it is — its first-layer kernel reads
     the table through ``ids`` (``src_ids`` of ``wgamd_sage_layer_fused_*``), so the ``[n, F]`` copy of the rows, the
     largest tensor of a mini-batch, is never written to HBM nor read back.  Anything else calls ``materialize()`` (one
-    ``wholememory_gather``) or just uses it as a tensor: ``torch`` functions receive the gathered rows."""
+    ``wholememory_gather``) or just uses it as a tensor: ``torch`` functions receive the gathered rows.
+
+    A ``torch.float16`` / ``torch.bfloat16`` table (features stored in 16 bits, as the reference's examples store them): the
+    values are converted to float32 exactly on the way out, as the reference's WholeMemory gather does, and the model runs in
+    float32.  ``nn.SAGEConv`` reads the 16-bit rows in its layer kernel (half the bytes of the row fetch, bit for bit the result
+    over ``table.float()``); ``materialize()`` returns **float32** rows (one converting gather, kept), which is what every other
+    layer works on — it takes the route of a float32 tensor input holding ``table.float()[ids]``, so its result is that input's;
+    ``dtype`` keeps returning the TABLE's dtype — the dtype of what is stored, not of what a layer computes on."""
 
     def __init__(self, table: torch.Tensor, ids: torch.Tensor):
         assert table.dim() == 2 and ids.dim() == 1 and ids.dtype in (torch.int32, torch.int64)
@@ -1009,8 +1039,8 @@ class LazyRows:
             self._rows = self._gather()           # (a peer-mapped table: wholememory_gather over the mapping)
         if self._rows is None:
             from .tensor import local_gather
-            self._rows = local_gather(self.table, self.ids, torch.empty(tuple(self.shape), dtype=self.table.dtype,
-                                                                        device=self.table.device))
+            dtype = torch.float32 if self.table.dtype in _X16 else self.table.dtype      # (a 16-bit store: converted once, here)
+            self._rows = local_gather(self.table, self.ids, torch.empty(tuple(self.shape), dtype=dtype, device=self.table.device))
         return self._rows
 
     def __getitem__(self, index):
@@ -1242,6 +1272,15 @@ def _layer_input(layer, x, lg: LayerGraph, F_: int):
     return src, (x.ids if lazy else None), (len(x) if lazy else x.shape[0]), n_edges
 
 
+def _x16_as_rows(x):
+    """``x``, or — for a ``LazyRows`` over a float16 / bfloat16 table — its float32 rows (``materialize()``: one converting
+    gather, kept): the layers other than ``SAGEConv`` then take whatever route a float32 tensor input takes."""
+    if isinstance(x, LazyRows) and x.table.dtype in _X16:
+        _refuse_lazy_table_grad(x.table)
+        return x.materialize()
+    return x
+
+
 def _refuse_featureless(layer, x):
     """ValueError unless ``x`` holds node features (a floating tensor or ``LazyRows``)."""
     if not isinstance(x, LazyRows) and not (torch.is_tensor(x) and x.is_floating_point()):
@@ -1353,7 +1392,14 @@ class _SageLayer(torch.autograd.Function):
         gx, first = None, True
         for (h, rows, _), agg in zip(_hops(graph), ctx.aggs):
             if h.n_rows > 0:
-                sage_wgrad(agg, src, h.self_rows, g[rows], gwl, gwr, gb, None if act is None else act[rows], src_ids=ids,
+                xs, self_rows, xs_ids = src, h.self_rows, ids
+                if src.dtype in _X16:
+                    # a 16-bit table: the weight-gradient kernel reads float32 rows — the hop's self rows, one converting gather
+                    from .tensor import local_gather
+                    xs = local_gather(src, h.self_rows if ids is None else ids[h.self_rows],
+                                      torch.empty((h.n_rows, F_), dtype=torch.float32, device=g.device))
+                    self_rows, xs_ids = _arange(h.n_rows, g.device), None
+                sage_wgrad(agg, xs, self_rows, g[rows], gwl, gwr, gb, None if act is None else act[rows], src_ids=xs_ids,
                            accumulate=not first)
                 first = False
                 if need_x:
@@ -1375,7 +1421,14 @@ class SAGEConv(torch.nn.Module):
     ``forward(x, graph)``: ``graph`` = the hop's ``[csr_row_ptr, csr_col_ind]`` or a COO ``edge_index`` (the reference's call
     shapes, gnn_model.py:178-199), or a ``LayerGraph`` of a loader call group — then the whole layer (feature fetch when
     ``x`` is a ``LazyRows``, aggregation, both linear maps, bias and the optional ``act="relu"``) is ONE kernel per hop
-    (``wgamd_sage_layer_fused_*``) where the shape allows it, aggregation kernel + library GEMM otherwise."""
+    (``wgamd_sage_layer_fused_*``) where the shape allows it, aggregation kernel + library GEMM otherwise.
+
+    A ``LazyRows`` over a ``torch.float16`` / ``torch.bfloat16`` table takes the one-kernel route wherever a float32 table
+    would: the kernel loads the 16-bit rows (2 bytes per feature instead of 4 on the launch's largest stream) and converts them
+    to float32 exactly, so output, kept aggregate and gradients are those of the float32 layer over ``table.float()`` — the
+    forward bit for bit.  The weight gradient gets the hop's self rows as float32 from one converting gather.  Every other
+    route (an unsupported shape, ``root_weight=False``, aggregate + GEMM) receives float32 rows from one converting gather.  A
+    gradient into the table stays refused."""
 
     def __init__(self, in_channels: Union[int, Tuple[int, int]], out_channels: int, aggr: str = "mean",
                  root_weight: bool = True, bias: bool = True):
@@ -1420,7 +1473,17 @@ class SAGEConv(torch.nn.Module):
         F_, N = src.shape[1], self.out_channels
         relu = act == "relu"
         assert act in (None, "relu"), "act: None or 'relu'"
-        one_kernel = (self.lin_r is not None and self.aggr in ("mean", "sum") and src.dtype == torch.float32 and src.is_cuda
+        x16 = lazy and src.dtype in _X16
+        if x16 and not (self.lin_r is not None and self.aggr in ("mean", "sum") and isinstance(src, torch.Tensor) and src.is_cuda
+                        and src.stride(1) == 1 and src.stride(0) % 4 == 0 and src.data_ptr() % 8 == 0
+                        and sage_layer_fused_supported(F_, N) and _FUSED_PRECISION == "bf16x3"
+                        and L.lib().wgamd_sage_layer_x16_supported(F_, _padded_width(N), torch_dtype_to_wm(src.dtype))):
+            # a 16-bit table on a route that is not the bf16x3 layer kernel's: float32 rows from ONE converting gather, then
+            # whatever a float32 tensor input takes
+            _refuse_lazy_table_grad(src)
+            x = src = x.materialize()
+            lazy = x16 = False
+        one_kernel = (self.lin_r is not None and self.aggr in ("mean", "sum") and (src.dtype == torch.float32 or x16) and src.is_cuda
                       and src.stride(1) == 1 and sage_layer_fused_preferred(F_, N))
         if one_kernel and not sage_layer_train_supported(F_, N):
             # (a shape only the fp32-MFMA layer kernel takes has no backward kernels: under autograd it runs as aggregation
@@ -1825,6 +1888,7 @@ class GCNConv(torch.nn.Module):
         assert act in (None, "relu"), "act: None or 'relu'"
         relu = act == "relu"
         F_, N = self.in_channels, self.out_channels
+        x = _x16_as_rows(x)
         src, ids, n_src, _ = _layer_input(self, x, lg, F_)
         dinv = self._dinv(lg, src.device)
         if gcn_layer_supported(F_, N) and _kernel_rows_ok(src):
@@ -2147,6 +2211,7 @@ class RGCNConv(torch.nn.Module):
         assert act in (None, "relu"), "act: None or 'relu'"
         relu = act == "relu"
         F_, N = self.in_channels, self.out_channels
+        x = _x16_as_rows(x)
         src, ids, n_src, n_edges = _layer_input(self, x, lg, F_)
         _rgcn_check_types(edge_type, self.num_relations, n_edges, lg.hops[0].row_ptr.device if lg.hops else src.device)
         coefs = self._coefs(lg, edge_type)

@@ -11,7 +11,11 @@ On the products-like workload of bench.py this loop moves 2.3 G sampled edges/s 
 119-125) — while still sampling per call group: `cugraph_pyg_amd.loader.PerBatchStep` stages every mini-batch of a group into
 fixed-size buffers with one launch and replays the whole step (forward, loss, backward, Adam) as one HIP graph.
 
-    python examples/sage_call_group_training.py [--nodes 200000] [--epochs 3] [--per-batch]
+`--feat-dtype float16|bfloat16` stores the feature table in 16 bits, as the reference's examples do (`--fp16_embedding`,
+`--node_feat_format float16`, `--dtype bfloat16`): half the HBM for the table; the first layer's kernel reads the 16-bit rows and
+converts them to float32 exactly, the model runs in float32.  (Call groups only: `--per-batch` stages float32 rows.)
+
+    python examples/sage_call_group_training.py [--nodes 200000] [--epochs 3] [--per-batch] [--feat-dtype float16]
 """
 import argparse
 import os
@@ -41,7 +45,11 @@ def main():
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--per-batch", action="store_true", help="one optimizer step per mini-batch (the reference's semantics) through "
                                                              "loader.PerBatchStep instead of one per call group")
+    ap.add_argument("--feat-dtype", choices=["float32", "float16", "bfloat16"], default="float32",
+                    help="dtype the feature table is stored in (16-bit: read as it is by the first layer's kernel)")
     args = ap.parse_args()
+    if args.per_batch and args.feat_dtype != "float32":
+        ap.error("--per-batch takes a float32 feature table")
     assert torch.cuda.is_available(), "needs an MI355X (there is no CPU fallback)"
     dev = torch.device("cuda")
     g = torch.Generator(device=dev).manual_seed(0)
@@ -56,6 +64,7 @@ def main():
     x[torch.arange(V, device=dev), community % args.features] += 1.0
     graph_store, feature_store = GraphStore(), FeatureStore()
     graph_store[("node", "to", "node"), "coo", False, (V, V)] = torch.stack([src, dst])
+    x = x.to(getattr(torch, args.feat_dtype))
     feature_store["node", "x", None] = x
     train_ids = torch.randperm(V, generator=g, device=dev)[: V // 2]
     loader = NeighborLoader((feature_store, graph_store), num_neighbors=args.fanout, input_nodes=train_ids,

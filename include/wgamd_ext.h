@@ -613,6 +613,28 @@ wholememory_error_code_t wgamd_sage_layer_fused_bf16x3_train(const int* row_ptr,
                                                              float* out, int64_t ldo, float* agg_out, int64_t ld_agg,
                                                              void* stream);
 
+/* ---- the one-kernel layer over a float16 / bfloat16 feature table -------------------------------------------------------------
+ * wgamd_sage_layer_fused_bf16x3_x(_train): the two launches above with the element type of `x` as an argument — x_dtype =
+ * WHOLEMEMORY_DT_FLOAT, WHOLEMEMORY_DT_HALF or WHOLEMEMORY_DT_BF16; `ldx` counts ELEMENTS of that type (ldx % 4 == 0; x is 16-B
+ * aligned for FLOAT, 8-B aligned for the 16-bit types).  The stored value becomes fp32 exactly as it is read (as the reference's
+ * WholeMemory gather converts a 16-bit store on the way out), everything after that is the float32 layer: `out` and `agg_out` are
+ * bit for bit those of the FLOAT launch over the same values.  The row fetch, most of the launch's bytes, moves 2 bytes per
+ * feature instead of 4.  With FLOAT they ARE the entry points above (which call these).  A 16-bit x is read by row (src_ids NULL)
+ * or through INT / INT64 row numbers; WGAMD_IDS_BYTE_OFFSETS with a 16-bit x is WHOLEMEMORY_LOGIC_ERROR.
+ * wgamd_sage_layer_x16_supported(F, N, x_dtype): wgamd_sage_layer_bf16x3_supported for one of the three types, 0 for any other. */
+int wgamd_sage_layer_x16_supported(int F, int N, wholememory_dtype_t x_dtype);
+wholememory_error_code_t wgamd_sage_layer_fused_bf16x3_x(const int* row_ptr, const int* col, int64_t n_rows, const void* x,
+                                                         wholememory_dtype_t x_dtype, int64_t ldx, int64_t x_rows, int F,
+                                                         const void* src_ids, wholememory_dtype_t src_ids_dtype,
+                                                         const int64_t* self_rows, int mean, const void* w_planes, int N,
+                                                         const float* bias, int relu, float* out, int64_t ldo, void* stream);
+wholememory_error_code_t wgamd_sage_layer_fused_bf16x3_x_train(const int* row_ptr, const int* col, int64_t n_rows, const void* x,
+                                                               wholememory_dtype_t x_dtype, int64_t ldx, int64_t x_rows, int F,
+                                                               const void* src_ids, wholememory_dtype_t src_ids_dtype,
+                                                               const int64_t* self_rows, int mean, const void* w_planes, int N,
+                                                               const float* bias, int relu, float* out, int64_t ldo,
+                                                               float* agg_out, int64_t ld_agg, void* stream);
+
 /* Weight gradient of the layer  out = act([agg | X[self_rows]] @ [W_l | W_r]^T + b)  over one hop (csrc/wg_sage_bwd.hip):
  *   dZ[i, :]      = grad_out[i, :]  where  act_out == NULL or act_out[i, :] > 0,  else 0        (ReLU mask folded in)
  *   grad_w_l[n,f] (+)= sum_i dZ[i, n] agg[i, f]          grad_w_r[n,f] (+)= sum_i dZ[i, n] X[self_rows[i], f]
