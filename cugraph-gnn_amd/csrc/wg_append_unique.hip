@@ -405,6 +405,8 @@ constexpr int kLdsMaxRanges  = 2048;      // per batch; beyond, ranges simply st
 constexpr int kLdsStack      = 40;        // pending hash ranges of one workgroup (a split pushes two, pops one)
 constexpr int kLdsChunks     = 16;        // blocks per batch in the bucketing kernel = segments of a range
 constexpr int kBucketThreads = 256;
+constexpr int kNewStride     = 16;        // ints between two batches' new-vertex counters (per-batch ranks): one 64-byte line each,
+                                          // the table kernel's workgroups add to them with device-scope atomics
 constexpr int kBucketUnroll  = 4;         // ids in flight per thread of the bucketing kernel
 constexpr int kLdsUnroll     = WG_LDS_UNROLL;    // pairs per thread of the table kernel: 3,584 per trip (a range holds 3,000 on average)
 
@@ -466,12 +468,17 @@ struct sort_scratch {
 template <typename TgtT, typename NbrT>
 __global__ void __launch_bounds__(kBucketThreads)
 bucket_sort_kernel(const TgtT* __restrict__ targets, dev_count T_, const NbrT* __restrict__ neighbors, batch_view bv,
-                   packed_layout lay, sort_scratch sc)
+                   packed_layout lay, sort_scratch sc, int* __restrict__ batch_new)
 {
   constexpr bool ID32  = sizeof(NbrT) == 4;
   constexpr int kItems = kLdsMaxRanges / kBucketThreads;   // histogram entries a thread scans
   __shared__ int hist[kLdsMaxRanges];   // counts of the chunk per range, then the write cursors
   __shared__ int wave_tot[kBucketThreads / 64];
+  if (blockIdx.x == 0 && batch_new) {
+    // renumber_lds_kernel (the next launch) adds each batch's new vertices into these with atomics, and raises the flag
+    // behind them for a batch longer than the caller promised: cleared here, one launch earlier
+    for (int i = threadIdx.x; i <= bv.G * kNewStride; i += kBucketThreads) batch_new[i] = 0;
+  }
   int b, c;
   if (!batch_of_block(bv.G, kLdsChunks, b, c)) return;
   const batch_part bp(bv, b, sc.keys_target);
@@ -552,11 +559,11 @@ bucket_sort_kernel(const TgtT* __restrict__ targets, dev_count T_, const NbrT* _
 template <bool ID32>
 __global__ void __launch_bounds__(kLdsThreads)
 renumber_lds_kernel(dev_count T_, dev_count E_, batch_view bv, packed_layout lay, int wg_per_batch, sort_scratch sc,
-                    int* __restrict__ slot_of, int* __restrict__ tile_sums, int n_tile_sums)
+                    int* __restrict__ slot_of, int* __restrict__ tile_sums, int n_tile_sums, int* __restrict__ batch_new)
 {
   __shared__ unsigned long long tbl[kLdsSlots];
   __shared__ unsigned long long st_lo[kLdsStack], st_span[kLdsStack];
-  __shared__ int st_n, overfull;
+  __shared__ int st_n, overfull, new_cnt;
   __shared__ int seg_base[kLdsChunks], seg_pre[kLdsChunks + 1];
   const unsigned long long kEmpty = ~0ull;
   const int T = T_.get();
@@ -569,6 +576,13 @@ renumber_lds_kernel(dev_count T_, dev_count E_, batch_view bv, packed_layout lay
   if (!batch_of_block(bv.G, wg_per_batch, b, j)) return;
   const batch_part bp(bv, b, sc.keys_target);
   if (bp.nE <= 0) return;   // no neighbour needs a first position
+  // batch_new (per-batch ranks, see renumber_emit_ranked_kernel): [b] receives the batch's NEW vertices — a neighbour is the
+  // first occurrence of a new id exactly when the table's minimum for its id is its own position —, [G] is raised when the
+  // batch holds more edges than the emit kernel's LDS window was sized for.  Every neighbour is looked up exactly once (an
+  // overfull attempt is abandoned before its look-up pass; a split or multi-trip range filters by hash), and integer adds give
+  // the same sums under any schedule.
+  if (batch_new && j == 0 && tid == 0 && bp.nE > bv.batch_edge_cap) batch_new[bv.G * kNewStride] = 1;
+  int n_new = 0;
   const unsigned long long pos_mask = lay.pos_mask();
   const volatile int* overfull_now  = &overfull;
   static_assert(kLdsChunks == 16, "the segment search below is written for 16 segments");
@@ -687,7 +701,11 @@ renumber_lds_kernel(dev_count T_, dev_count E_, batch_view bv, packed_layout lay
 #pragma unroll
         for (int k = 0; k < kLdsUnroll; k++) {
           const int p = (int)(w[k] & pos_mask);
-          if (memo[k] >= 0 && p >= T) slot_of[p] = (int)(tbl[memo[k]] & pos_mask);
+          if (memo[k] >= 0 && p >= T) {
+            const int first = (int)(tbl[memo[k]] & pos_mask);
+            slot_of[p]      = first;
+            n_new += first == p;
+          }
         }
         __syncthreads();
         continue;
@@ -711,18 +729,31 @@ renumber_lds_kernel(dev_count T_, dev_count E_, batch_view bv, packed_layout lay
               s   = s + 1 == (uint32_t)kLdsSlots ? 0u : s + 1;
               cur = tbl[s];
             }
-            slot_of[p] = (int)(cur & pos_mask);
+            const int first = (int)(cur & pos_mask);
+            slot_of[p]      = first;
+            n_new += first == p;
           }
         }
       }
       __syncthreads();
     }
   }
+  if (batch_new) {
+    // per wave by ballot-free lane sums, per workgroup in LDS, then ONE global add for everything this workgroup finished
+    if (tid == 0) new_cnt = 0;
+    __syncthreads();
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) n_new += __shfl_down(n_new, d, 64);
+    if ((tid & 63) == 0 && n_new) atomicAdd(&new_cnt, n_new);
+    __syncthreads();
+    if (tid == 0 && new_cnt) atomicAdd(&batch_new[b * kNewStride], new_cnt);
+  }
 }
 
 // ---- first-appearance ranks --------------------------------------------------------------------------------------------
 // rank(q) = number of first occurrences among the neighbours before position q (q <= E).  Device-wide table paths keep it as
-// a plain int array (flags -> exclusive scan).  The LDS path keeps ONE BIT per neighbour and a running count per 64-bit word:
+// a plain int array (flags -> exclusive scan).  The LDS path of a call WITHOUT the uniform-batch promise (or whose per-batch window
+// does not fit LDS; with it: "per-batch ranks" below) keeps ONE BIT per neighbour and a running count per 64-bit word:
 // first_bits_kernel derives the bits from slot_of (neighbour e is a first occurrence iff slot_of[T + e] == T + e — the table
 // kernel no longer writes a flag array), the scan runs over E / 64 word counts instead of E flags, and the emit kernel's
 // random rank look-up lands in 12 bytes per 64 neighbours (2.4 MB for the 12.6 M neighbours of a products hop 2: it stays in
@@ -892,6 +923,201 @@ renumber_emit_batched_kernel(const TgtT* __restrict__ targets, const NbrT* __res
   }
 }
 
+// ---- per-batch ranks (call groups whose batches are promised uniform: bv.batch_edge_cap > 0) ------------------------------
+// A mini-batch is renumbered on its own, so the rows of its neighbours need two numbers only: how many new vertices the
+// EARLIER batches contributed (the shift) and the first-appearance rank INSIDE the batch.  The table kernel counts every
+// batch's new vertices while it looks the first positions up (batch_new, cleared by the bucketing kernel), so the shift is a
+// block reduction over at most G ints; the ranks inside the batch are resolved by the emit kernel itself, in LDS: a workgroup
+// (batch, part) reads the batch's slot_of stretch from the start of the batch to the end of its own part (a repeat's first
+// occurrence can lie anywhere earlier in the batch), forms the first-occurrence words by ballot and scans the per-word
+// counts; rank(q) is then an LDS read plus a popcount.  No bits, counts or prefix in global memory, no first_bits / scan
+// launches, and one global load per edge (slot_of) where the rank_bits form chased slot_of -> prefix[w] -> words[w].
+// All parts of a batch run on one XCD (batch_of_block): the repeated slot_of reads of the later parts are L2 hits.
+// The window (12 bytes per 64 edges of batch_edge_cap) is dynamic LDS; a hop whose window exceeds kRankWindowBytes keeps the
+// rank_bits path.  Parts x threads per batch: see the measured grid at kRankParts.
+// Measured grid (profiles/r09/README.md; products call group of 188, fan-out [25, 10], the walk alone, ms per group, two runs;
+// parent with first_bits + scan launches: 0.770 / 0.769):
+//   parts x threads   2 x 1024        4 x 1024        8 x 512         8 x 256
+//   walk              0.730 / 0.735   0.735 / 0.739   0.756 / 0.759   0.809 / 0.817
+// A part re-reads the batch's slot_of stretch below it, so fewer, larger workgroups win as long as G x parts covers the CUs
+// (188 x 2 = 376 workgroups of 16 waves on 256 CUs); 8 x 256 re-reads 4.5 x the stretch and loses to the parent.
+#ifndef WG_RANK_PARTS      // (tuning: -DWG_RANK_PARTS / WG_RANK_THREADS)
+#define WG_RANK_PARTS 2
+#define WG_RANK_THREADS 1024
+#endif
+constexpr int kRankParts       = WG_RANK_PARTS;
+constexpr int kRankThreads     = WG_RANK_THREADS;
+constexpr int kRankWaves       = kRankThreads / 64;
+constexpr int kRankUnroll      = 8;       // slot_of loads in flight per lane while the words are formed
+constexpr int kRankWindowBytes = 65536;   // dynamic LDS a workgroup may ask for without opting in to more
+__host__ __device__ inline int rank_window_words(int batch_edge_cap) { return batch_edge_cap / 64 + 1; }
+inline size_t rank_window_bytes(int batch_edge_cap) { return (size_t)rank_window_words(batch_edge_cap) * 12; }
+
+template <typename TgtT, typename NbrT>
+__global__ void __launch_bounds__(kRankThreads)
+renumber_emit_ranked_kernel(const TgtT* __restrict__ targets, const NbrT* __restrict__ neighbors,
+                            const int* __restrict__ slot_of, const int* __restrict__ batch_new, dev_count T_, dev_count E_,
+                            batch_view bv, TgtT* __restrict__ unique_out, int* __restrict__ map_out,
+                            int* __restrict__ counts_out)
+{
+  using KeyT = TgtT;
+  extern __shared__ unsigned long long rank_window[];   // [nw_cap] first-occurrence words, then [nw_cap] running counts
+  __shared__ int red_before[kRankWaves], red_all[kRankWaves], wave_tot[kRankWaves];
+  const int nw_cap          = rank_window_words(bv.batch_edge_cap);
+  unsigned long long* words = rank_window;
+  int* pre                  = reinterpret_cast<int*>(rank_window + nw_cap);
+  const int T = T_.get(), E = E_.get();
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int gtid = blockIdx.x * kRankThreads + tid, gsize = gridDim.x * kRankThreads;
+  int b, c;
+  const bool mine = batch_of_block(bv.G, kRankParts, b, c);   // (the padding blocks of the grid still help with the -1 fill)
+  // new vertices of the batches before mine (the shift of my rows) and of all batches (the size of `unique`)
+  int shift = 0, U = 0;
+  {
+    int before = 0, all = 0;
+    for (int g = tid; g < bv.G; g += kRankThreads) {
+      const int v = batch_new[g * kNewStride];
+      all += v;
+      before += g < b ? v : 0;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+      before += __shfl_down(before, d, 64);
+      all += __shfl_down(all, d, 64);
+    }
+    if (lane == 0) {
+      red_before[wave] = before;
+      red_all[wave]    = all;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < kRankWaves; w++) {
+      shift += red_before[w];
+      U += red_all[w];
+    }
+  }
+  if (batch_new[bv.G * kNewStride] != 0) {
+    // a batch holds more edges than the promised window: nothing is indexed past the LDS, the hop reports a negative size
+    if (gtid == 0 && counts_out) {
+      counts_out[0] = E;
+      counts_out[1] = -1;
+    }
+    return;
+  }
+  if (gtid == 0) {
+    if (counts_out) {
+      counts_out[0] = E;
+      counts_out[1] = T + U;
+    }
+    if (bv.unique_seg) {   // one past the last batch
+      bv.unique_seg[bv.G] = bv.target_seg[bv.G] + U;
+      if (bv.frontier_seg_out) bv.frontier_seg_out[bv.G] = U;
+    }
+  }
+  // the capacity slack of `unique` is padded with -1 unless the caller reads the sizes anyway (see renumber_emit_batched_kernel)
+  if (counts_out && !bv.no_pad)
+    for (int p = T + U + gtid; p < T_.host + E_.host; p += gsize) unique_out[p] = (KeyT)-1;
+  if (!mine) return;
+
+  const int t0 = bv.target_seg[b], nT = bv.target_seg[b + 1] - t0;
+  const int s0 = bv.sseg()[b];
+  const int e0 = bv.edge_offsets[s0], nE = bv.edge_offsets[bv.sseg()[b + 1]] - e0;
+  const int tail_row = t0 + nT + shift;   // row of the batch's first new vertex
+  const int local0   = bv.sample_local0 ? bv.sample_local0[b] : 0;
+  if (c == 0 && tid == 0 && bv.unique_seg) {
+    bv.unique_seg[b] = t0 + shift;
+    if (bv.frontier_seg_out) bv.frontier_seg_out[b] = shift;
+    if (bv.frontier_local0_out) bv.frontier_local0_out[b] = nT;
+  }
+  {
+    const int chunk = (nT + kRankParts - 1) / kRankParts;
+    const int end   = min(nT, (c + 1) * chunk);
+    for (int i = c * chunk + tid; i < end; i += kRankThreads) {
+      unique_out[t0 + i + shift] = targets[t0 + i];
+      if (bv.unique_batch) bv.unique_batch[t0 + i + shift] = b;
+    }
+  }
+  const int chunk = (nE + kRankParts - 1) / kRankParts;
+  const int begin = c * chunk, end = min(nE, begin + chunk);
+  if (begin >= end) return;   // (the same in every thread)
+  const int* first_of = slot_of + T + e0;   // first position of the id of the batch's edge i
+  const int p0        = T + e0;             // position of the batch's edge 0
+  // ---- first-occurrence words of the batch's edges [0, end), one wave per word, kRankUnroll words of a wave in flight -----
+  const int nw = (end + 63) >> 6;           // <= nw_cap: end <= nE <= batch_edge_cap (checked by the table kernel)
+  for (int w0 = wave; w0 < nw; w0 += kRankWaves * kRankUnroll) {
+    int first[kRankUnroll];
+#pragma unroll
+    for (int k = 0; k < kRankUnroll; k++) {
+      const int i = (w0 + k * kRankWaves) * 64 + lane;
+      first[k]    = i < nE ? first_of[i] : -1;
+    }
+#pragma unroll
+    for (int k = 0; k < kRankUnroll; k++) {
+      const int w = w0 + k * kRankWaves;
+      const unsigned long long word = __ballot(first[k] == p0 + w * 64 + lane);
+      if (lane == 0 && w < nw) {
+        words[w] = word;
+        pre[w]   = __popcll(word);
+      }
+    }
+  }
+  __syncthreads();
+  // ---- exclusive running counts (thread t owns the words [t * per, (t + 1) * per)) ------------------------------------
+  {
+    const int per = (nw + kRankThreads - 1) / kRankThreads;
+    const int lo = min(tid * per, nw), hi = min(lo + per, nw);
+    int sum = 0;
+    for (int w = lo; w < hi; w++) sum += pre[w];
+    int inc = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int up = __shfl_up(inc, d, 64);
+      if (lane >= d) inc += up;
+    }
+    if (lane == 63) wave_tot[wave] = inc;
+    __syncthreads();
+    int run = inc - sum;
+    for (int w = 0; w < wave; w++) run += wave_tot[w];
+    for (int w = lo; w < hi; w++) {
+      const int v = pre[w];
+      pre[w]      = run;
+      run += v;
+    }
+  }
+  __syncthreads();
+  // ---- emit my part: the first position (an L2 hit: read a moment ago), then its rank out of LDS ------------------------
+  for (int i0 = begin + tid; i0 < end; i0 += kRankThreads * kEmitUnroll) {
+    int first[kEmitUnroll], row[kEmitUnroll];
+#pragma unroll
+    for (int k = 0; k < kEmitUnroll; k++) first[k] = first_of[min(i0 + k * kRankThreads, end - 1)];
+#pragma unroll
+    for (int k = 0; k < kEmitUnroll; k++) {
+      const int q = max(first[k] - p0, 0);   // the batch's edge that saw the id first, q <= i (0: a target, not looked up)
+      row[k]      = first[k] < T ? first[k] + shift
+                                 : tail_row + pre[q >> 6] + __popcll(words[q >> 6] & ((1ull << (q & 63)) - 1ull));
+    }
+#pragma unroll
+    for (int k = 0; k < kEmitUnroll; k++) {
+      const int i = i0 + k * kRankThreads;
+      if (i >= end) break;
+      const int e = e0 + i;
+      if (first[k] == T + e) {
+        const KeyT id      = (KeyT)neighbors[e];
+        unique_out[row[k]] = id;
+        if (bv.unique_batch) bv.unique_batch[row[k]] = b;
+        if (bv.frontier_out) {  // next frontier, ordered by (batch, first appearance)
+          const int r = row[k] - (t0 + nT);
+          static_cast<KeyT*>(bv.frontier_out)[r] = id;
+          bv.frontier_batch_out[r]               = b;
+        }
+      }
+      if (map_out) map_out[e] = row[k];
+      if (bv.neighbor_local_out) bv.neighbor_local_out[e] = row[k] - (t0 + shift);
+      if (bv.center_local_out) bv.center_local_out[e] = bv.edge_row[e] - s0 + local0;
+    }
+  }
+}
+
 // boundary records the two kernels address: every batch starts at floor(positions before it / kLdsKeysTarget) + 2 b and
 // owns R + 1 rows of kLdsChunks ints
 inline int64_t lds_range_records(int64_t capacity_positions, int G) { return capacity_positions / kLdsKeysTarget + 3 * (int64_t)G + 2; }
@@ -924,6 +1150,13 @@ inline bool lds_path_taken(dev_count T, dev_count E, bool nbr64, const batch_vie
          packed_layout_for((int64_t)T.host + E.host, 1, bound, lay) && lds_scratch_fits((int64_t)T.host + E.host, bv.G, slots);
 }
 
+// does a call on the LDS path resolve its ranks per batch (renumber_emit_ranked_kernel)?  Shape alone: the caller's promise
+// and a window that fits; batch_new and its flag live in the hop's `rank` buffer (kNewStride G + 1 of its E.host + 1 ints)
+inline bool batch_ranks_taken(dev_count E, const batch_view& bv)
+{
+  return bv.batch_edge_cap > 0 && (int64_t)bv.G * kNewStride <= E.host && rank_window_bytes(bv.batch_edge_cap) <= (size_t)kRankWindowBytes;
+}
+
 template <typename TgtT, typename NbrT>
 void prepare_lds_t(const TgtT* targets, dev_count T, const NbrT* neighbors, dev_count E, batch_view bv, packed_layout lay,
                    void* keys, int* minpos, int* slot_of, int* rank, int* scan_tmp, hipStream_t stream)
@@ -934,13 +1167,20 @@ void prepare_lds_t(const TgtT* targets, dev_count T, const NbrT* neighbors, dev_
     sc.keys_target = lds_keys_target();
     sc.seg_off     = minpos;
     sc.words       = static_cast<unsigned long long*>(keys);
-    bucket_sort_kernel<TgtT, NbrT><<<batch_grid(bv.G, kLdsChunks), kBucketThreads, 0, stream>>>(targets, T, neighbors, bv, lay, sc);
+    const bool per_batch_ranks = batch_ranks_taken(E, bv);
+    int* batch_new             = per_batch_ranks ? rank : nullptr;
+    bucket_sort_kernel<TgtT, NbrT><<<batch_grid(bv.G, kLdsChunks), kBucketThreads, 0, stream>>>(targets, T, neighbors, bv, lay, sc,
+                                                                                                batch_new);
     const int64_t per_batch = (cap + bv.G - 1) / bv.G;
     const int wg_per_batch  = (int)std::max<int64_t>(1, std::min<int64_t>((per_batch + kLdsKeysTarget - 1) / kLdsKeysTarget, 32));
     const rank_bits_layout rl(E.host);
-    const int n_tiles = (int)((rl.nw + kScanTile - 1) / kScanTile);
+    const int n_tiles = per_batch_ranks ? 0 : (int)((rl.nw + kScanTile - 1) / kScanTile);
     renumber_lds_kernel<sizeof(NbrT) == 4><<<batch_grid(bv.G, wg_per_batch), kLdsThreads, 0, stream>>>(T, E, bv, lay, wg_per_batch, sc,
-                                                                                                     slot_of, scan_tmp, n_tiles);
+                                                                                                     slot_of, scan_tmp, n_tiles, batch_new);
+    if (per_batch_ranks) {   // the hop's renumbering is bucket_sort -> renumber_lds -> emit
+      WG_HIP_CHECK(hipGetLastError());
+      return;
+    }
     // first occurrences as bits + per-word counts (+ their per-tile sums), then the counts' running sums in place
     const int bits_grid = (int)std::min<int64_t>(((int64_t)rl.nw + kBitsWordsPerBlock - 1) / kBitsWordsPerBlock, 256 * 8);
     first_bits_kernel<<<bits_grid, 256, 0, stream>>>(slot_of, T, E, rank, scan_tmp);
@@ -1027,7 +1267,10 @@ void append_unique_emit_enqueue(const void* targets, dev_count T, bool tgt64, co
   with_id_types(tgt64, nbr64, targets, neighbors, [&](auto* t, auto* n) {
     using TgtT = std::remove_cv_t<std::remove_pointer_t<decltype(t)>>;
     using NbrT = std::remove_cv_t<std::remove_pointer_t<decltype(n)>>;
-    if (per_batch && bits) {
+    if (per_batch && bits && batch_ranks_taken(E, bv)) {
+      renumber_emit_ranked_kernel<TgtT, NbrT><<<batch_grid(bv.G, kRankParts), kRankThreads, rank_window_bytes(bv.batch_edge_cap), stream>>>(
+        t, n, slot_of, rank, T, E, bv, static_cast<TgtT*>(unique_out), map_out, counts_out);
+    } else if (per_batch && bits) {
       const rank_bits_layout rl(E.host);
       const rank_bits rb{rank, reinterpret_cast<const unsigned long long*>(rank + rl.words_at)};
       renumber_emit_batched_kernel<TgtT, NbrT, rank_bits><<<bgrid, 256, 0, stream>>>(t, n, slot_of, rb, T, E, bv,

@@ -356,6 +356,8 @@ struct batch_view {
   int* neighbor_local_out;  // out [E]   per-batch LOCAL id of every edge's neighbour
   int* center_local_out;    // out [E]   per-batch LOCAL id of every edge's expanded vertex
   int no_pad;               // 1: leave the capacity slack of the unique list unwritten (WGAMD_HOP_NO_UNIQUE_PAD)
+  int batch_edge_cap;       // > 0: the caller promises that no batch samples more edges than this in the hop
+                            // (WGAMD_HOP_UNIFORM_BATCHES: edge capacity / G); 0 = no promise
   __host__ __device__ const int* sbatch() const { return sample_batch ? sample_batch : target_batch; }
   __host__ __device__ const int* sseg() const { return sample_seg ? sample_seg : target_seg; }
 };

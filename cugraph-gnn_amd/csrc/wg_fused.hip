@@ -572,7 +572,7 @@ wholememory_error_code_t wgamd_sample_hop_batched_nosync_ex(
 {
   using namespace wgamd;
   return guarded("wgamd_sample_hop_batched_nosync", [&] {
-    WG_REQUIRE_INPUT((flags & ~(WGAMD_HOP_NO_UNIQUE_PAD | WGAMD_HOP_COL_INT32)) == 0, "unknown flag bits");
+    WG_REQUIRE_INPUT((flags & ~(WGAMD_HOP_NO_UNIQUE_PAD | WGAMD_HOP_COL_INT32 | WGAMD_HOP_UNIFORM_BATCHES)) == 0, "unknown flag bits");
     WG_REQUIRE_INPUT(!(flags & WGAMD_HOP_COL_INT32) || (id_dtype == WHOLEMEMORY_DT_INT64 && n_vertices > 0 &&
                                                         n_vertices < ((int64_t)1 << 31)),
                      "WGAMD_HOP_COL_INT32 needs INT64 ids and 0 < n_vertices < 2^31");
@@ -589,6 +589,7 @@ wholememory_error_code_t wgamd_sample_hop_batched_nosync_ex(
     a.bv.id_bound = n_vertices > 0 ? n_vertices : 0;
     a.bv.unique_batch = unique_batch; a.bv.unique_seg = unique_seg;
     a.bv.no_pad = (flags & WGAMD_HOP_NO_UNIQUE_PAD) ? 1 : 0;
+    a.bv.batch_edge_cap = (flags & WGAMD_HOP_UNIFORM_BATCHES) ? (int)ceil_div(edge_cap, (int64_t)n_batches) : 0;
     a.col32     = (flags & WGAMD_HOP_COL_INT32) != 0;
     a.offsets = offsets; a.neighbor_row = neighbor_row; a.center_row = center_row; a.edge_gid = edge_gid;
     a.edge_cap = edge_cap; a.unique = unique; a.counts_dev = counts_dev; a.workspace = workspace;
@@ -680,11 +681,12 @@ wholememory_error_code_t wgamd_sample_hop_pyg_nosync(const wgamd_pyg_hop_t* p, v
     a.bv.frontier_out = p->frontier_out; a.bv.frontier_batch_out = p->frontier_out_batch;
     a.bv.frontier_seg_out = p->frontier_out_seg; a.bv.frontier_local0_out = p->frontier_out_local0;
     a.bv.neighbor_local_out = p->neighbor_local; a.bv.center_local_out = p->center_local;
-    WG_REQUIRE_INPUT((p->flags & ~(WGAMD_HOP_NO_UNIQUE_PAD | WGAMD_HOP_COL_INT32)) == 0, "unknown flag bits");
+    WG_REQUIRE_INPUT((p->flags & ~(WGAMD_HOP_NO_UNIQUE_PAD | WGAMD_HOP_COL_INT32 | WGAMD_HOP_UNIFORM_BATCHES)) == 0, "unknown flag bits");
     WG_REQUIRE_INPUT(!(p->flags & WGAMD_HOP_COL_INT32) || (p->id_dtype == WHOLEMEMORY_DT_INT64 && p->n_vertices > 0 &&
                                                            p->n_vertices < ((int64_t)1 << 31)),
                      "WGAMD_HOP_COL_INT32 needs INT64 ids and 0 < n_vertices < 2^31");
     a.bv.no_pad = (p->flags & WGAMD_HOP_NO_UNIQUE_PAD) ? 1 : 0;
+    a.bv.batch_edge_cap = (p->flags & WGAMD_HOP_UNIFORM_BATCHES) ? (int)ceil_div(p->edge_cap, (int64_t)p->n_batches) : 0;
     a.col32     = (p->flags & WGAMD_HOP_COL_INT32) != 0;
     a.offsets = p->offsets; a.neighbor_row = p->neighbor_row_scratch; a.center_row = p->center_row_scratch;
     a.edge_gid = p->edge_gid; a.edge_cap = p->edge_cap; a.unique = p->nodes_out; a.counts_dev = p->counts_dev;

@@ -17,6 +17,7 @@ from .env import get_stream, torch_dtype_to_wm
 
 HOP_NO_UNIQUE_PAD = 1   # WGAMD_HOP_NO_UNIQUE_PAD (include/wgamd_ext.h)
 HOP_COL_INT32 = 2       # WGAMD_HOP_COL_INT32
+HOP_UNIFORM_BATCHES = 8  # WGAMD_HOP_UNIFORM_BATCHES: every batch of the call group starts from the same number of seeds
 
 _COL32 = {}             # (data_ptr, numel) -> (weakref to the int64 column tensor, its int32 copy)
 
@@ -184,7 +185,8 @@ class NoSyncWalk:
         with fewer than 2^31 vertices are read through their 32-bit twin (``compact_columns``); same results."""
         assert csr_row_ptr.is_cuda and csr_col_ind.is_cuda
         assert all(m > 0 for m in max_neighbors), "the no-sync walk needs positive fan-outs"
-        self.flags = 0 if pad_unique else HOP_NO_UNIQUE_PAD
+        # (every batch is B seeds: no batch can sample more than its share of a hop's edge capacity)
+        self.flags = (0 if pad_unique else HOP_NO_UNIQUE_PAD) | HOP_UNIFORM_BATCHES
         assert csr_col_ind.dtype == id_dtype, "no-sync walk: seeds and csr_col must share a dtype"
         self.row_ptr, self.col = csr_row_ptr, csr_col_ind
         self.n_vertices = int(csr_row_ptr.shape[0]) - 1     # every id is a row of the CSR
@@ -521,8 +523,10 @@ class PygNoSyncWalk:
         assert rs.shape == (hops, G)
         res = PygWalkResult(hops, G, self.B, counts=torch.empty((hops, 2), dtype=torch.int32, device=dev))
         res._keepalive = [rs]
+        flags = self.flags
         if seed_seg is None:
             seed_seg, seed_batch = self.seed_seg, self.seed_batch
+            flags |= HOP_UNIFORM_BATCHES     # B seeds per batch; a ragged list makes no such promise
         else:
             assert seed_seg.dtype == torch.int32 and seed_seg.shape[0] == G + 1 and seed_seg.is_contiguous()
             assert seed_batch.dtype == torch.int32 and seed_batch.shape[0] == G * self.B and seed_batch.is_contiguous()
@@ -548,7 +552,7 @@ class PygNoSyncWalk:
                         self.workspace.data_ptr() + self.ws_off, self.ws_bytes,
                         None if self.weight is None else self.weight.data_ptr(),
                         0 if self.weight is None else torch_dtype_to_wm(self.weight.dtype), self.max_row_len,
-                        int(self.row_ptr.shape[0]) - 1, self.flags)
+                        int(self.row_ptr.shape[0]) - 1, flags)
             L.check(lib.wgamd_sample_hop_pyg_nosync(_ct.byref(p), get_stream()), "wgamd_sample_hop_pyg_nosync")
             res.offsets.append(offsets)
             res.row_local.append(row_l)
@@ -669,6 +673,8 @@ class HeteroPygWalk:
                                 begin=self.zeros_g, gained_cap=int(ids.shape[0]))
         rec = dict(calls=[], sizes=[{t: (state[t]["seg"][1:] - state[t]["seg"][:-1]) for t in self.ntypes}])
         keep = [rs]
+        # B seeds per batch: a batch's share of every later frontier and edge capacity bounds what it can hold
+        flags = self.flags | (HOP_UNIFORM_BATCHES if seed_lists is None else 0)
         for h in range(self.hops):
             fronts = {t: (self._frontier(state[t], state[t]["gained_cap"]) if state[t]["gained_cap"] > 0 else None)
                       for t in self.ntypes}
@@ -712,7 +718,7 @@ class HeteroPygWalk:
                             g.weight.data_ptr() if self.biased else None,
                             torch_dtype_to_wm(g.weight.dtype) if self.biased else 0, mrl,
                             int(self.num_nodes.get(src_t, 0)),   # the renumbered ids are type-local ids of the SOURCE type
-                            self.flags | (0 if c32 is None else HOP_COL_INT32))
+                            flags | (0 if c32 is None else HOP_COL_INT32))
                 L.check(lib.wgamd_sample_hop_pyg_nosync(_ct.byref(p), get_stream()), "wgamd_sample_hop_pyg_nosync")
                 keep += [scratch_r, scratch_c, f_out, f_out_batch, f_out_seg, f_out_l0, counts, f_ids, f_batch, f_l0,
                          st["nodes"], st["batch"], st["seg"]]

@@ -261,6 +261,14 @@ wholememory_error_code_t wgamd_sample_hop_batched_nosync(const int64_t* csr_row_
  * sampler's random column picks, half the bytes of every renumber pass) and are widened where `unique` is written.  Same
  * results as the INT64 column array, bit for bit.  In the _ex entry point `unique_batch` may be NULL (not produced). */
 #define WGAMD_HOP_COL_INT32 2u
+/* WGAMD_HOP_UNIFORM_BATCHES: the caller promises that every mini-batch of the call group started from the same number of
+ * seeds, so that no batch samples more than ceil(edge_cap / n_batches) edges in this hop.  Where a batch's first-occurrence
+ * bits and their running counts for that many edges (12 bytes per 64) fit a workgroup's LDS, the renumbering resolves the
+ * first-appearance ranks per batch in LDS instead of over the whole edge array (three launches per hop instead of six).
+ * Same results, bit for bit; without the flag, or where the window does not fit, the hop runs as before.  A broken promise
+ * writes nothing out of bounds: the hop then publishes counts_dev = {n_edges, -1} and leaves its other outputs unwritten.
+ * (Bit value 4 is not assigned and is refused like any unknown bit.) */
+#define WGAMD_HOP_UNIFORM_BATCHES 8u
 
 wholememory_error_code_t wgamd_sample_hop_batched_nosync_ex(const int64_t* csr_row_ptr,
                                                          const void* csr_col,
