@@ -101,10 +101,7 @@ __global__ void __launch_bounds__(kThreads) rgcn_layer_kernel(rgcn_args a)
   const int64_t row0 = (int64_t)blockIdx.x * kTileRows;
   const int rows_here = (int)std::min<int64_t>(kTileRows, a.n_rows - row0);
   if (tid <= kTileRows) rp[tid] = a.row_ptr[row0 + std::min(tid, rows_here)];
-  // the tile's k padding [K, K16) is zero
-  const int pad4 = (a.K16 - a.K) / 4;
-  for (int p = tid; p < kTileRows * pad4; p += kThreads)
-    reinterpret_cast<f32x4*>(tile + (p / pad4) * a.SD + a.K)[p % pad4] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_tile_padding(tile, a.SD, a.K, a.K16);
   __syncthreads();
 
   // ---- phase 1: C rows -> LDS.  Thread = (slot, chunk q); chunk q is feature float4 c of block b ----

@@ -29,39 +29,10 @@ constexpr int kMaxK   = 1024;
 constexpr int kMaxRel = WGAMD_HETERO_SAGE_MAX_RELATIONS;
 constexpr int kStage  = 768;    // edges staged per piece, all relations together (9 KB next to the tile: 3 workgroups per CU at K = 640)
 
-struct hsage_args {
+struct hsage_args : hetero_frame {              // (kept = c_out: the C rows)
   wgamd_hetero_sage_relation_t rel[kMaxRel];
-  int n_rel;
-  int64_t n_rows;
-  const float* x_dst;         // the root block: null = none
-  int64_t ldx_dst;
-  int F_dst;
-  const int64_t* dst_rows;    // row of destination i in x_dst's numbering (null: i)
-  const void* dst_ids;
-  int dst_kind;
-  int root_col0;
-  const float* wt;
-  int64_t ldw;
-  int N;
-  const float* bias;
-  int relu;
-  const float* acc_in;
-  int64_t ld_acc;
-  const int64_t* out_rows;
-  float* out;
-  int64_t ldo;
-  float* c_out;               // _train: the C rows
-  int64_t ldc;
-  int K, K16, SD, Q, P;       // Q = K / 4 chunks; P row slots (power of 2, P Q <= 256)
+  int Q, P;                   // Q = K / 4 chunks; P row slots (power of 2, P Q <= 256)
 };
-
-// a row read through a node list whose kind is known at run time only (0 = by row, 1 = int32, 2 = int64)
-__device__ __forceinline__ const float* row_of(const float* x, int64_t ldx, const void* ids, int kind, int64_t r)
-{
-  if (kind == 1) r = static_cast<const int32_t*>(ids)[r];
-  else if (kind == 2) r = static_cast<const int64_t*>(ids)[r];
-  return x + r * ldx;
-}
 
 __global__ void __launch_bounds__(kThreads) hetero_sage_kernel(hsage_args a)
 {
@@ -72,14 +43,8 @@ __global__ void __launch_bounds__(kThreads) hetero_sage_kernel(hsage_args a)
   const int tid = threadIdx.x;
   const int64_t row0 = (int64_t)blockIdx.x * kTileRows;
   const int rows_here = (int)std::min<int64_t>(kTileRows, a.n_rows - row0);
-  if (tid < a.n_rel * (kTileRows + 1)) {
-    const int r = tid / (kTileRows + 1), t = tid % (kTileRows + 1);
-    rp[r][t] = a.rel[r].row_ptr[row0 + std::min(t, rows_here)];
-  }
-  // the tile's k padding [K, K16) is zero
-  const int pad4 = (a.K16 - a.K) / 4;
-  for (int p = tid; p < kTileRows * pad4; p += kThreads)
-    reinterpret_cast<f32x4*>(tile + (p / pad4) * a.SD + a.K)[p % pad4] = f32x4{0.f, 0.f, 0.f, 0.f};
+  load_row_windows(rp, a.rel, a.n_rel, row0, rows_here);
+  zero_tile_padding(tile, a.SD, a.K, a.K16);
   __syncthreads();
 
   // ---- phase 1: C rows -> LDS.  Thread = (slot, chunk q); chunk q is feature float4 c of relation block b (or of the root) ----
@@ -175,12 +140,7 @@ __global__ void __launch_bounds__(kThreads) hetero_sage_kernel(hsage_args a)
   }
   __syncthreads();
 
-  if (a.c_out != nullptr) {                           // the operand of the product, for the weight gradient
-    for (int p = tid; p < rows_here * a.Q; p += kThreads) {
-      const int lr = p / a.Q, qq = p % a.Q;
-      reinterpret_cast<f32x4*>(a.c_out + (row0 + lr) * a.ldc)[qq] = reinterpret_cast<const f32x4*>(tile + lr * a.SD)[qq];
-    }
-  }
+  if (a.kept) keep_tile_rows(tile, a.SD, a.K, rows_here, a.kept, a.ld_kept, row0);   // C, for the weight gradient
 
   // ---- phase 2: [16 x K16] tile @ wt^T ----
   tile_times_wt(tile, a.SD, a.K, a.K16, a.wt, a.ldw, a.N, a.bias, a.relu, a.out, a.ldo, row0, a.n_rows, a.acc_in, a.ld_acc,
@@ -222,26 +182,12 @@ wholememory_error_code_t launch(const char* what, const wgamd_hetero_sage_relati
       a.rel[r] = R;
       at += R.F;
     }
-    a.n_rel = n_rel, a.n_rows = n_rows;
-    if (x_dst) {
-      WG_REQUIRE_INPUT(F_dst > 0 && ldx_dst >= F_dst, "leading dimension too small");
-      WG_REQUIRE_INPUT(dst_ids_kind >= 0 && dst_ids_kind <= 2 && (dst_ids_kind == 0) == (dst_ids == nullptr), "bad node list kind");
-      if (!aligned_rows(x_dst, ldx_dst)) throw logic_error("x_dst rows must be 16-B aligned");
-      a.x_dst = x_dst, a.ldx_dst = ldx_dst, a.F_dst = F_dst, a.dst_rows = dst_rows, a.dst_ids = dst_ids, a.dst_kind = dst_ids_kind;
-      a.root_col0 = at;
-      at += F_dst;
-    }
-    a.wt = wt, a.ldw = ldw, a.N = N, a.bias = bias, a.relu = (flags & WGAMD_HETERO_SAGE_RELU) ? 1 : 0;
-    a.acc_in = acc_in, a.ld_acc = ld_acc, a.out_rows = out_rows, a.out = out, a.ldo = ldo, a.c_out = c_out, a.ldc = ldc;
-    a.K   = at;
-    a.K16 = (a.K + 15) / 16 * 16;
-    a.SD  = a.K16 + 4;      // rows 4 banks apart: the 16 rows of a fragment read spread over the 64 banks
+    fill_hetero_frame(a, n_rel, n_rows, at, x_dst, ldx_dst, F_dst, dst_rows, dst_ids, dst_ids_kind, wt, ldw, N, bias,
+                      flags & WGAMD_HETERO_SAGE_RELU, acc_in, ld_acc, out_rows, out, ldo, c_out, ldc,
+                      "c_out rows must be 16-B aligned, ldc >= K");
     a.Q   = a.K / 4;
     a.P   = 1;
     while (a.P < kTileRows && 2 * a.P * a.Q <= kThreads) a.P *= 2;
-    WG_REQUIRE_INPUT(ldw >= a.K && ldo >= N && (acc_in == nullptr || ld_acc >= N), "leading dimension too small");
-    if (!aligned_rows(wt, ldw)) throw logic_error("wt rows must be 16-B aligned");
-    if (c_out != nullptr && (ldc < a.K || !aligned_rows(c_out, ldc))) throw logic_error("c_out rows must be 16-B aligned, ldc >= K");
     launch_tiles(hetero_sage_kernel, a, static_cast<hipStream_t>(stream));
     WG_HIP_CHECK(hipGetLastError());
   });

@@ -23,25 +23,10 @@
 //     dX[j] = sum_e sum_h (alpha dA_ih[:F] + ds u_ih) plus the skip block of dA where input row j is a destination itself.
 //     One wave per input row.
 // No atomics anywhere: every sum runs in CSR (or transposed-CSR) order, the same bits from run to run.
-#include "wg_layer_parts.hpp"
+#include "wg_transformer_parts.hpp"
 
 namespace wgamd {
 namespace {
-
-constexpr int kMaxK = 1024;
-constexpr int kMaxF = 256;     // one float4 of a source row per lane
-constexpr int kMaxD = 32;      // [a | 1 | pad] within one wave's lanes
-constexpr int kMaxH = 8;
-
-// sum over the wave; xor butterflies give every lane the same bits (each step adds the same two values, commuted)
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ float dot4(f32x4 a, f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
 
 struct tconv_args {
   const int* row_ptr;
@@ -56,12 +41,12 @@ struct tconv_args {
   int Fd;                     // 0: no skip block
   const int64_t* self_rows;
   int xd_ids;
-  const float* ea;            // [E, D] in CSR order (D = 0: none)
+  const float* edge_attr;     // [E, D] in CSR order (D = 0: none)
   int D;
   const float* u;             // [n_rows, ldu]: u[i, h F + f]
   int64_t ldu;
-  const float* w;             // [n_rows, ldwv]: w[i, h D + d]
-  int64_t ldwv;
+  const float* w;             // [n_rows, ldw]: w[i, h D + d]
+  int64_t ldw;
   int H;
   const float* wt;            // [N, ldwt] = Wstack^T
   int64_t ldwt;
@@ -84,15 +69,10 @@ __global__ void __launch_bounds__(kThreads) tconv_layer_kernel(tconv_args a)
   const int64_t row0 = (int64_t)blockIdx.x * kTileRows;
   const int rows_here = (int)std::min<int64_t>(kTileRows, a.n_rows - row0);
   if (tid <= kTileRows) rp[tid] = a.row_ptr[row0 + std::min(tid, rows_here)];
-  const int pad4 = (a.K16 - a.K) / 4;             // the tile's k padding [K, K16) is zero
-  for (int p = tid; p < kTileRows * pad4; p += kThreads)
-    reinterpret_cast<f32x4*>(tile + (p / pad4) * a.SD + a.K)[p % pad4] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_tile_padding(tile, a.SD, a.K, a.K16);
   __syncthreads();
 
-  // ---- phase 1: one wave per destination row ----
-  const int F4 = a.F / 4, H = a.H, D = a.D;
-  const bool fx = lane < F4;
-  const int ext_w = a.W4 - a.F;                   // [a | 1 | pad] columns of a head block
+  // ---- phase 1: one wave per destination row (tconv_row_walk, wg_transformer_parts.hpp) ----
   for (int lr = wave; lr < kTileRows; lr += 4) {
     float* trow = tile + lr * a.SD;
     if (lr >= rows_here) {
@@ -100,90 +80,16 @@ __global__ void __launch_bounds__(kThreads) tconv_layer_kernel(tconv_args a)
       continue;
     }
     const int64_t i = row0 + lr;
-    const int s = rp[lr], t = rp[lr + 1];
-    f32x4 uh[HM], acc[HM];
-    float wh[HM], ext[HM], m[HM], l[HM];
-#pragma unroll
-    for (int h = 0; h < HM; ++h) {
-      uh[h] = acc[h] = f32x4{0.f, 0.f, 0.f, 0.f};
-      wh[h] = ext[h] = l[h] = 0.f;
-      m[h] = -INFINITY;
-      if (h < H) {
-        if (fx) uh[h] = reinterpret_cast<const f32x4*>(a.u + i * a.ldu + (int64_t)h * a.F)[lane];
-        if (lane < D) wh[h] = a.w[i * a.ldwv + h * D + lane];
-      }
-    }
-    for (int e0 = s; e0 < t; e0 += 4) {
-      f32x4 xv[4];
-      float av[4];
-#pragma unroll
-      for (int v = 0; v < 4; ++v) {
-        const int e = e0 + v;
-        xv[v] = f32x4{0.f, 0.f, 0.f, 0.f};
-        av[v] = 0.f;
-        if (e < t) {
-          const int j = a.col[e];
-          if (fx) xv[v] = reinterpret_cast<const f32x4*>(x_row<KIND>(a.x, a.ldx, a.src_ids, j))[lane];
-          av[v] = lane < D ? a.ea[(int64_t)e * D + lane] : (lane == D ? 1.f : 0.f);
-        }
-      }
-#pragma unroll
-      for (int h = 0; h < HM; ++h) {
-        if (h >= H) break;
-        float sc[4];
-        float mx = m[h];
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          sc[v] = wave_sum(dot4(uh[h], xv[v]) + (lane < D ? wh[h] * av[v] : 0.f));
-          if (e0 + v < t) mx = fmaxf(mx, sc[v]);
-        }
-        const float r = expf(m[h] - mx);          // (m = -inf before the first group: r = 0)
-        acc[h] *= r;
-        ext[h] *= r;
-        l[h] *= r;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          if (e0 + v < t) {
-            const float p = expf(sc[v] - mx);
-            acc[h] += p * xv[v];
-            ext[h] += p * av[v];
-            l[h] += p;
-            if (a.alpha && lane == v) a.alpha[(int64_t)(e0 + v) * H + h] = sc[v];   // the logit; alpha after the row
-          }
-        }
-        m[h] = mx;
-      }
-    }
-#pragma unroll
-    for (int h = 0; h < HM; ++h) {
-      if (h >= H) break;
-      const float inv = l[h] > 0.f ? 1.f / l[h] : 0.f;
-      if (fx) reinterpret_cast<f32x4*>(trow + h * a.W4)[lane] = acc[h] * inv;
-      if (lane < ext_w) trow[h * a.W4 + a.F + lane] = ext[h] * inv;
-      l[h] = inv;
-    }
+    const auto row_at = [x = a.x, ldx = a.ldx, ids = a.src_ids](int64_t j) { return x_row<KIND>(x, ldx, ids, j); };
+    tconv_row_walk<HM>(a, a.W4, row_at, trow, i, rp[lr], rp[lr + 1], lane);
     if (a.Fd > 0 && lane < a.Fd / 4) {
       const int64_t self = a.self_rows[i];
       const float* xr = a.xd_ids ? x_row<KIND>(a.xd, a.ldxd, a.src_ids, self) : a.xd + self * a.ldxd;
-      reinterpret_cast<f32x4*>(trow + H * a.W4)[lane] = reinterpret_cast<const f32x4*>(xr)[lane];
-    }
-    if (a.alpha) {
-      __threadfence_block();                      // the logits this wave wrote, read back by other lanes
-      for (int e = s + lane; e < t; e += 64)
-#pragma unroll
-        for (int h = 0; h < HM; ++h) {
-          if (h >= H) break;
-          float* p = a.alpha + (int64_t)e * H + h;
-          *p = expf(*p - m[h]) * l[h];
-        }
+      reinterpret_cast<f32x4*>(trow + a.H * a.W4)[lane] = reinterpret_cast<const f32x4*>(xr)[lane];
     }
   }
   __syncthreads();
-  if (a.a_save) {                                 // A for the backward: rows_here x K, row-major
-    const int K4 = a.K / 4;
-    for (int p = tid; p < rows_here * K4; p += kThreads)
-      reinterpret_cast<f32x4*>(a.a_save + (row0 + p / K4) * a.K)[p % K4] = reinterpret_cast<const f32x4*>(tile + (p / K4) * a.SD)[p % K4];
-  }
+  if (a.a_save) keep_tile_rows(tile, a.SD, a.K, rows_here, a.a_save, a.K, row0);   // A for the backward, row-major
 
   // ---- phase 2: [16 x K16] tile @ wt^T ----
   tile_times_wt(tile, a.SD, a.K, a.K16, a.wt, a.ldwt, a.N, a.bias, a.relu, a.out, a.ldo, row0, a.n_rows);
@@ -309,33 +215,6 @@ __global__ void __launch_bounds__(256) tconv_bwd_src_kernel(const int* __restric
   *o = accumulate ? *o + g : g;
 }
 
-int heads_bucket(int H) { return H <= 1 ? 1 : H <= 2 ? 2 : H <= 4 ? 4 : 8; }
-
-template <int KIND>
-void launch_layer_h(const tconv_args& a, hipStream_t st)
-{
-  switch (heads_bucket(a.H)) {
-    case 1: launch_tiles(tconv_layer_kernel<KIND, 1>, a, st); break;
-    case 2: launch_tiles(tconv_layer_kernel<KIND, 2>, a, st); break;
-    case 4: launch_tiles(tconv_layer_kernel<KIND, 4>, a, st); break;
-    default: launch_tiles(tconv_layer_kernel<KIND, 8>, a, st); break;
-  }
-}
-
-template <int KIND>
-void launch_bwd_h(const tconv_bwd_args& a, hipStream_t st)
-{
-  const dim3 grid((unsigned)((a.n_rows + 3) / 4));
-  switch (heads_bucket(a.H)) {
-    case 1: tconv_bwd_dst_kernel<KIND, 1><<<grid, 256, 0, st>>>(a); break;
-    case 2: tconv_bwd_dst_kernel<KIND, 2><<<grid, 256, 0, st>>>(a); break;
-    case 4: tconv_bwd_dst_kernel<KIND, 4><<<grid, 256, 0, st>>>(a); break;
-    default: tconv_bwd_dst_kernel<KIND, 8><<<grid, 256, 0, st>>>(a); break;
-  }
-}
-
-int block_width(int F, int D) { return (F + D + 1 + 3) / 4 * 4; }
-
 }  // namespace
 }  // namespace wgamd
 
@@ -371,7 +250,7 @@ extern "C" wholememory_error_code_t wgamd_transformer_layer_f32(
     tconv_args a{};
     a.row_ptr = row_ptr, a.col = col, a.n_rows = n_rows, a.x = x, a.ldx = ldx, a.F = F_src, a.src_ids = src_ids;
     a.xd = x_dst, a.ldxd = ldx_dst, a.Fd = F_dst, a.self_rows = self_rows, a.xd_ids = x_dst_ids ? 1 : 0;
-    a.ea = edge_attr, a.D = D, a.u = u, a.ldu = ldu, a.w = w, a.ldwv = ldw, a.H = H;
+    a.edge_attr = edge_attr, a.D = D, a.u = u, a.ldu = ldu, a.w = w, a.ldw = ldw, a.H = H;
     a.wt = wt, a.ldwt = ldwt, a.N = N, a.bias = bias, a.relu = relu ? 1 : 0, a.out = out, a.ldo = ldo;
     a.alpha = alpha, a.a_save = a_save;
     a.W4  = block_width(F_src, D);
@@ -384,7 +263,11 @@ extern "C" wholememory_error_code_t wgamd_transformer_layer_f32(
     if (!aligned_rows(x, kind == 3 ? 0 : ldx) || (F_dst > 0 && !aligned_rows(x_dst, ldx_dst)) || !aligned_rows(wt, ldwt) ||
         !aligned_rows(u, ldu) || (a_save && !aligned_rows(a_save, 0)))
       throw logic_error("x / x_dst / u / wt / a_save rows must be 16-B aligned");
-    with_kind(kind, [&](auto k) { launch_layer_h<decltype(k)::value>(a, static_cast<hipStream_t>(stream)); });
+    with_kind(kind, [&](auto k) {
+      with_heads(H, [&](auto hm) {
+        launch_tiles(tconv_layer_kernel<decltype(k)::value, decltype(hm)::value>, a, static_cast<hipStream_t>(stream));
+      });
+    });
     WG_HIP_CHECK(hipGetLastError());
   });
 }
@@ -410,7 +293,12 @@ extern "C" wholememory_error_code_t wgamd_transformer_bwd_dst_f32(
     WG_REQUIRE_INPUT(kind == 3 || ldx >= F_src, "leading dimension too small");
     if (!aligned_rows(x, kind == 3 ? 0 : ldx) || !aligned_rows(dA, ldda) || !aligned_rows(A, lda) || !aligned_rows(du, 0))
       throw logic_error("x / dA / A / du rows must be 16-B aligned");
-    with_kind(kind, [&](auto k) { launch_bwd_h<decltype(k)::value>(a, static_cast<hipStream_t>(stream)); });
+    const dim3 grid((unsigned)((n_rows + 3) / 4));
+    with_kind(kind, [&](auto k) {
+      with_heads(H, [&](auto hm) {
+        tconv_bwd_dst_kernel<decltype(k)::value, decltype(hm)::value><<<grid, 256, 0, static_cast<hipStream_t>(stream)>>>(a);
+      });
+    });
     WG_HIP_CHECK(hipGetLastError());
   });
 }

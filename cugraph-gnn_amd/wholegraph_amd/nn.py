@@ -3271,6 +3271,31 @@ def _sage_ids_kind(ids) -> int:
     return 0 if ids is None else (1 if ids.dtype == torch.int32 else 2)
 
 
+def _hetero_launch_tail(name: str, relu_flag: int, arr, n_rel: int, at: int, n_rows: int, wt, N: int, root, bias, relu, acc_in,
+                        out_rows, out, kept):
+    """The second half of ``hetero_sage_launch`` / ``hetero_transformer_launch``: the relation descriptors ``arr`` (``n_rel`` of
+    them, ``at`` floats wide together) are filled; unpacks the root, checks ``wt``, ``out``, ``acc_in``, ``out_rows`` and the
+    ``kept`` rows, and calls the library's ``name`` (``name + "_train"`` with ``kept``).  Returns ``out``."""
+    x_dst, dst_rows, dst_ids = root if root is not None else (None, None, None)
+    if x_dst is not None:
+        assert x_dst.dtype == torch.float32 and x_dst.stride(1) == 1 and (dst_rows is None or dst_rows.dtype == torch.int64)
+        at += int(x_dst.shape[1])
+    assert wt.dtype == torch.float32 and wt.stride(1) == 1 and wt.shape[0] == N and wt.shape[1] >= at
+    if out is None:
+        out = torch.empty((n_rows, N), dtype=torch.float32, device=wt.device)
+    assert out.stride(1) == 1 and out.shape[1] == N and (acc_in is None or (acc_in.stride(1) == 1 and acc_in.shape == (n_rows, N)))
+    assert out_rows is None or (out_rows.dtype == torch.int64 and out_rows.is_contiguous())
+    args = (arr, n_rel, n_rows, _ptr(x_dst), 0 if x_dst is None else x_dst.stride(0), 0 if x_dst is None else int(x_dst.shape[1]),
+            _ptr(dst_rows), _ptr(dst_ids), _sage_ids_kind(dst_ids), wt.data_ptr(), wt.stride(0), N, _ptr(bias),
+            relu_flag if relu else 0, _ptr(acc_in), 0 if acc_in is None else acc_in.stride(0), _ptr(out_rows),
+            out.data_ptr(), out.stride(0))
+    if kept is not None:
+        assert kept.stride(1) == 1 and kept.shape[0] == n_rows and kept.shape[1] >= at
+        name, args = name + "_train", args + (kept.data_ptr(), kept.stride(0))
+    L.check(getattr(L.lib(), name)(*args, get_stream()), name)
+    return out
+
+
 def hetero_sage_launch(rels, n_rows: int, wt, N: int, root=None, bias=None, relu=False, acc_in=None, out_rows=None, out=None,
                        c_out=None):
     """One ``wgamd_hetero_sage_layer_f32`` launch (include/wgamd_ext.h).  ``rels``: ``[(row_ptr, col, x, ids, scale, mean), ...]``
@@ -3291,74 +3316,75 @@ def hetero_sage_launch(rels, n_rows: int, wt, N: int, root=None, bias=None, relu
         d.src_ids, d.src_scale = _ptr(ids), _ptr(scale)
         d.F, d.ids_kind, d.mean, d.col0 = int(x.shape[1]), _sage_ids_kind(ids), int(bool(mean)), at
         at += int(x.shape[1])
-    x_dst, dst_rows, dst_ids = root if root is not None else (None, None, None)
-    if x_dst is not None:
-        assert x_dst.dtype == torch.float32 and x_dst.stride(1) == 1 and (dst_rows is None or dst_rows.dtype == torch.int64)
-        at += int(x_dst.shape[1])
-    assert wt.dtype == torch.float32 and wt.stride(1) == 1 and wt.shape[0] == N and wt.shape[1] >= at
-    if out is None:
-        out = torch.empty((n_rows, N), dtype=torch.float32, device=wt.device)
-    assert out.stride(1) == 1 and out.shape[1] == N and (acc_in is None or (acc_in.stride(1) == 1 and acc_in.shape == (n_rows, N)))
-    assert out_rows is None or (out_rows.dtype == torch.int64 and out_rows.is_contiguous())
-    common = (arr, len(rels), n_rows, _ptr(x_dst), 0 if x_dst is None else x_dst.stride(0), 0 if x_dst is None else int(x_dst.shape[1]),
-              _ptr(dst_rows), _ptr(dst_ids), _sage_ids_kind(dst_ids), wt.data_ptr(), wt.stride(0), N, _ptr(bias),
-              L.HETERO_SAGE_RELU if relu else 0, _ptr(acc_in), 0 if acc_in is None else acc_in.stride(0), _ptr(out_rows),
-              out.data_ptr(), out.stride(0))
-    if c_out is not None:
-        assert c_out.stride(1) == 1 and c_out.shape[0] == n_rows and c_out.shape[1] >= at
-        L.check(L.lib().wgamd_hetero_sage_layer_f32_train(*common, c_out.data_ptr(), c_out.stride(0), get_stream()),
-                "wgamd_hetero_sage_layer_f32_train")
-    else:
-        L.check(L.lib().wgamd_hetero_sage_layer_f32(*common, get_stream()), "wgamd_hetero_sage_layer_f32")
+    out = _hetero_launch_tail("wgamd_hetero_sage_layer_f32", L.HETERO_SAGE_RELU, arr, len(rels), at, n_rows, wt, N, root, bias, relu,
+                              acc_in, out_rows, out, c_out)
     hetero_sage_launches += 1
     return out
 
 
-class _SageGroup:
-    """What one (hop, destination type) group of the hetero SAGE layer launches over: per relation block ``(row_ptr, col, x, ids,
-    mean, src)`` (``src``: index of x among the group's differentiable source tensors, None for a table read through a node
-    list), the root ``(x_dst, dst_rows, dst_ids)`` or None, the plan, and the ``RelationHop`` of every block (None: the hop
-    lists no such relation) for the transposes of the backward pass."""
+class _HeteroGroup:
+    """What one (hop, destination type) group of a hetero layer launches over: the relation ``blocks``, the root ``(x_dst,
+    dst_rows, dst_ids)`` or None, the plan (``hetero_sage_plan``), and the ``RelationHop`` of every block (None: the hop lists
+    no such relation) for the transposes of the backward pass.  A subclass names its stages (``stage``) and supplies
+    ``launch`` (its ``hetero_*_launch``), ``rels(lo, hi, *operands)`` — the relation tuples of blocks ``[lo, hi)`` — and
+    ``first_col(lo)``, the first column of block ``lo`` in the stacked weight."""
 
     def __init__(self, blocks, hops, root, plan, n_rows, N, relu, tag):
         self.blocks, self.hops, self.root, self.plan = blocks, hops, root, plan
         self.n_rows, self.N, self.relu, self.tag = n_rows, N, relu, tag
+
+    def run(self, wt, bias, *operands, out=None, out_rows=None, kept=None):
+        """The group's launches -> act(tile @ wt^T + bias), placed through ``out_rows`` into ``out`` when given; bias, ReLU,
+        placement and root go with the last launch, every launch but the first adds the running sum of the ones before."""
+        acc = None
+        for k, (lo, hi, with_root) in enumerate(self.plan):
+            last = k == len(self.plan) - 1
+            rels, at = self.rels(lo, hi, *operands), self.first_col(lo)
+            names = ",".join(str(h.edge_type[1]) for h in self.hops[lo:hi] if h is not None)
+            name = "%s%s:%s (%d rows, launch %d/%d)" % (self.stage, self.tag, names, self.n_rows, k + 1, len(self.plan))
+            acc = _stage(name, lambda: self.launch(
+                rels, self.n_rows, wt[:, at:], self.N, root=self.root if with_root else None, bias=bias if last else None,
+                relu=self.relu and last, acc_in=acc, out_rows=out_rows if last else None, out=out if last else None,
+                kept=None if kept is None else kept[:, at:]))
+        return acc
+
+
+class _SageGroup(_HeteroGroup):
+    """The hetero SAGE layer's group: per relation block ``(row_ptr, col, x, ids, mean, src)`` (``src``: index of x among the
+    group's differentiable source tensors, None for a table read through a node list)."""
+    stage = "sage"
+
+    def __init__(self, blocks, hops, root, plan, n_rows, N, relu, tag):
+        super().__init__(blocks, hops, root, plan, n_rows, N, relu, tag)
         self.col0 = [0]
         for b in blocks:
             self.col0.append(self.col0[-1] + int(b[2].shape[1]))
         self.K = self.col0[-1] + (int(root[0].shape[1]) if root is not None else 0)
 
-    def run(self, wstack, bias, out=None, out_rows=None, c_out=None):
-        """The group's launches -> act(C @ wstack^T + bias), placed through ``out_rows`` into ``out`` when given."""
-        acc = None
-        for k, (lo, hi, with_root) in enumerate(self.plan):
-            last = k == len(self.plan) - 1
-            rels = [(b[0], b[1], b[2], b[3], None, b[4]) for b in self.blocks[lo:hi]]
-            at = self.col0[lo]
-            names = ",".join(str(h.edge_type[1]) for h in self.hops[lo:hi] if h is not None)
-            name = "sage%s:%s (%d rows, launch %d/%d)" % (self.tag, names, self.n_rows, k + 1, len(self.plan))
-            res = _stage(name, lambda: hetero_sage_launch(
-                rels, self.n_rows, wstack[:, at:], self.N, root=self.root if with_root else None, bias=bias if last else None,
-                relu=self.relu and last, acc_in=acc, out_rows=out_rows if last else None, out=out if last else None,
-                c_out=None if c_out is None else c_out[:, at:]))
-            acc = res
-        return acc
+    def launch(self, *args, kept=None, **kw):
+        return hetero_sage_launch(*args, c_out=kept, **kw)
+
+    def rels(self, lo, hi):
+        return [(b[0], b[1], b[2], b[3], None, b[4]) for b in self.blocks[lo:hi]]
+
+    def first_col(self, lo):
+        return self.col0[lo]
 
 
-def _relation_transpose(r: RelationHop, n_src: int, mean: bool):
-    """``(row_ptr_t, col_t, scale)`` of a relation hop seen from its ``n_src`` input rows (entries = the hop's frontier entries,
-    hop order inside a source row: deterministic sums; ``scale`` = 1 / degree of every frontier entry for a mean relation) —
-    computed once and kept on the ``RelationHop``."""
-    hit = getattr(r, "_sage_t", None)
+def _relation_transpose(r: RelationHop, n_src: int, want_perm: bool = False):
+    """``(row_ptr_t, col_t, scale | perm)`` of a relation hop with edges, seen from its ``n_src`` input rows (entries = the hop's
+    frontier entries, hop order inside a source row: deterministic sums).  The third item is ``scale`` = 1 / degree of every
+    frontier entry (a mean relation's factor), or with ``want_perm`` the hop's CSR edge of every transposed entry instead —
+    computed once per form and kept on the ``RelationHop``."""
+    cache = r.__dict__.setdefault("_transposed", {})
+    hit = cache.get(want_perm)
     if hit is None or hit[0] != n_src:
-        if r.n_edges > 0:
-            row_ptr_t, _, _, col_t = _csr_transpose(r.row_ptr, r.col, n_src, want_col_t=True)
-        else:
-            row_ptr_t, col_t = torch.zeros(n_src + 1, dtype=torch.int32, device=r.row_ptr.device), r.col
-        deg = (r.row_ptr[1:] - r.row_ptr[:-1]).clamp(min=1)
-        hit = (n_src, row_ptr_t, col_t, (1.0 / deg.float()).contiguous())
-        r._sage_t = hit
-    return hit[1], hit[2], (hit[3] if mean else None)
+        row_ptr_t, extra, _, col_t = _csr_transpose(r.row_ptr, r.col, n_src, want_perm=want_perm, want_col_t=True)
+        if not want_perm:
+            deg = (r.row_ptr[1:] - r.row_ptr[:-1]).clamp(min=1)
+            extra = (1.0 / deg.float()).contiguous()
+        hit = cache[want_perm] = (n_src, row_ptr_t, col_t, extra)
+    return hit[1:]
 
 
 class _HeteroSageGroup(torch.autograd.Function):
@@ -3373,7 +3399,7 @@ class _HeteroSageGroup(torch.autograd.Function):
     def forward(ctx, grp, wstack, bias, x_dst, *srcs):
         w, b = wstack.detach(), None if bias is None else bias.detach()
         c = _agg_pool.take((grp.n_rows, grp.K), torch.float32, w.device)
-        z = grp.run(w, b, c_out=c)
+        z = grp.run(w, b, kept=c)
         ctx.grp, ctx.c, ctx.n_srcs = grp, c, len(srcs)
         ctx.src_shapes = [tuple(t.shape) for t in srcs]
         ctx.dst_shape = None if x_dst is None else tuple(x_dst.shape)
@@ -3418,8 +3444,8 @@ class _HeteroSageGroup(torch.autograd.Function):
                 if fits:
                     rels = []
                     for k in now:
-                        row_ptr_t, col_t, scale = _relation_transpose(grp.hops[k], n_src, grp.blocks[k][4])
-                        rels.append((row_ptr_t, col_t, g, None, scale, False))
+                        row_ptr_t, col_t, scale = _relation_transpose(grp.hops[k], n_src)
+                        rels.append((row_ptr_t, col_t, g, None, scale if grp.blocks[k][4] else None, False))
                     wt = torch.cat([w[:, grp.col0[k]:grp.col0[k + 1]].t() for k in now], 1).contiguous()
                     gx = _stage("sage%s dX" % grp.tag, lambda: hetero_sage_launch(rels, n_src, wt, F_, acc_in=gx))
                 else:
@@ -3507,39 +3533,22 @@ def hetero_transformer_launch(rels, n_rows: int, wt, N: int, root=None, bias=Non
         d.edge_attr, d.u, d.ldu, d.w, d.ldw = _ptr(bufs[1]), u.data_ptr(), u.stride(0), _ptr(w), 0 if w is None else w.stride(0)
         d.alpha, d.F, d.ids_kind, d.D, d.H, d.col0 = _ptr(bufs[2]), F_, _sage_ids_kind(ids), D, int(H), at
         at += int(H) * transformer_block_width(F_, D)
-    x_dst, dst_rows, dst_ids = root if root is not None else (None, None, None)
-    if x_dst is not None:
-        assert x_dst.dtype == torch.float32 and x_dst.stride(1) == 1 and (dst_rows is None or dst_rows.dtype == torch.int64)
-        at += int(x_dst.shape[1])
-    assert wt.dtype == torch.float32 and wt.stride(1) == 1 and wt.shape[0] == N and wt.shape[1] >= at
-    if out is None:
-        out = torch.empty((n_rows, N), dtype=torch.float32, device=wt.device)
-    assert out.stride(1) == 1 and out.shape[1] == N and (acc_in is None or (acc_in.stride(1) == 1 and acc_in.shape == (n_rows, N)))
-    assert out_rows is None or (out_rows.dtype == torch.int64 and out_rows.is_contiguous())
-    common = (arr, len(rels), n_rows, _ptr(x_dst), 0 if x_dst is None else x_dst.stride(0), 0 if x_dst is None else int(x_dst.shape[1]),
-              _ptr(dst_rows), _ptr(dst_ids), _sage_ids_kind(dst_ids), wt.data_ptr(), wt.stride(0), N, _ptr(bias),
-              L.HETERO_TRANSFORMER_RELU if relu else 0, _ptr(acc_in), 0 if acc_in is None else acc_in.stride(0), _ptr(out_rows),
-              out.data_ptr(), out.stride(0))
-    if a_save is not None:
-        assert a_save.dtype == torch.float32 and a_save.stride(1) == 1 and a_save.shape[0] == n_rows and a_save.shape[1] >= at
-        L.check(L.lib().wgamd_hetero_transformer_layer_f32_train(*common, a_save.data_ptr(), a_save.stride(0), get_stream()),
-                "wgamd_hetero_transformer_layer_f32_train")
-    else:
-        L.check(L.lib().wgamd_hetero_transformer_layer_f32(*common, get_stream()), "wgamd_hetero_transformer_layer_f32")
+    assert a_save is None or a_save.dtype == torch.float32
+    out = _hetero_launch_tail("wgamd_hetero_transformer_layer_f32", L.HETERO_TRANSFORMER_RELU, arr, len(rels), at, n_rows, wt, N, root,
+                              bias, relu, acc_in, out_rows, out, a_save)
     hetero_transformer_launches += 1
     return out
 
 
-class _TconvGroup:
-    """What one (hop, destination type) group of the hetero transformer layer launches over: per relation block a dict
-    ``(row_ptr, col, x, ids, ea, src, n_edges)`` (``ea``: the hop's rows of the relation's edge attributes or None; ``src``:
-    index of x among the group's differentiable source tensors, None for a table read through a node list) next to the
-    relation's ``layout`` entry of ``hetero_transformer_stack``, the root ``(x_dst, dst_rows, dst_ids)`` or None, the plan, and
-    the ``RelationHop`` of every block (None: the hop lists no such relation) for the transposes of the backward pass."""
+class _TconvGroup(_HeteroGroup):
+    """The hetero transformer layer's group: per relation block a dict ``(row_ptr, col, x, ids, ea, src, n_edges)`` (``ea``: the
+    hop's rows of the relation's edge attributes or None; ``src``: index of x among the group's differentiable source tensors,
+    None for a table read through a node list) next to the relation's ``layout`` entry of ``hetero_transformer_stack``."""
+    stage = "tconv"
 
     def __init__(self, blocks, layout, hops, root, plan, n_rows, N, relu, tag):
-        self.blocks, self.layout, self.hops, self.root, self.plan = blocks, layout, hops, root, plan
-        self.n_rows, self.N, self.relu, self.tag = n_rows, N, relu, tag
+        super().__init__(blocks, hops, root, plan, n_rows, N, relu, tag)
+        self.layout = layout
         self.K_rel = layout[-1]["col0"] + layout[-1]["width"] if layout else 0
         self.K = self.K_rel + (int(root[0].shape[1]) if root is not None else 0)
 
@@ -3548,37 +3557,16 @@ class _TconvGroup:
         u = uw[:, lay["u0"]:lay["u0"] + lay["H"] * lay["F"]]
         return u, (uw[:, lay["w0"]:lay["w0"] + lay["H"] * lay["D"]] if lay["D"] else None)
 
-    def run(self, wt, bias, uw, out=None, out_rows=None, a_save=None, alphas=None):
-        """The group's launches -> act(A @ wt^T + bias), placed through ``out_rows`` into ``out`` when given."""
-        acc = None
-        for k, (lo, hi, with_root) in enumerate(self.plan):
-            last = k == len(self.plan) - 1
-            rels = []
-            for b in range(lo, hi):
-                blk, (u, w) = self.blocks[b], self.u_w(uw, b)
-                rels.append((blk["row_ptr"], blk["col"], blk["x"], blk["ids"], blk["ea"], u, w, self.layout[b]["H"],
-                             None if alphas is None else alphas[b]))
-            at = self.layout[lo]["col0"] if lo < len(self.layout) else self.K_rel
-            names = ",".join(str(h.edge_type[1]) for h in self.hops[lo:hi] if h is not None)
-            name = "tconv%s:%s (%d rows, launch %d/%d)" % (self.tag, names, self.n_rows, k + 1, len(self.plan))
-            res = _stage(name, lambda: hetero_transformer_launch(
-                rels, self.n_rows, wt[:, at:], self.N, root=self.root if with_root else None, bias=bias if last else None,
-                relu=self.relu and last, acc_in=acc, out_rows=out_rows if last else None, out=out if last else None,
-                a_save=None if a_save is None else a_save[:, at:]))
-            acc = res
-        return acc
+    def launch(self, *args, kept=None, **kw):
+        return hetero_transformer_launch(*args, a_save=kept, **kw)
 
+    def rels(self, lo, hi, uw, alphas=None):
+        """``uw``: the fold product; ``alphas``: every block's alpha buffer (training) or None."""
+        return [(blk["row_ptr"], blk["col"], blk["x"], blk["ids"], blk["ea"], *self.u_w(uw, b), self.layout[b]["H"],
+                 None if alphas is None else alphas[b]) for b, blk in enumerate(self.blocks[lo:hi], lo)]
 
-def _relation_transpose_perm(r: RelationHop, n_src: int):
-    """``(row_ptr_t, col_t, perm)`` of a relation hop seen from its ``n_src`` input rows (entries = the hop's frontier entries,
-    hop order inside a source row: deterministic sums; ``perm`` = the hop's CSR edge of every transposed entry) — computed once
-    and kept on the ``RelationHop``, like ``_relation_transpose``."""
-    hit = getattr(r, "_tconv_t", None)
-    if hit is None or hit[0] != n_src:
-        row_ptr_t, perm, _, col_t = _csr_transpose(r.row_ptr, r.col, n_src, want_perm=True, want_col_t=True)
-        hit = (n_src, row_ptr_t, col_t, perm)
-        r._tconv_t = hit
-    return hit[1], hit[2], hit[3]
+    def first_col(self, lo):
+        return self.layout[lo]["col0"] if lo < len(self.layout) else self.K_rel
 
 
 class _HeteroTconvGroup(torch.autograd.Function):
@@ -3597,7 +3585,7 @@ class _HeteroTconvGroup(torch.autograd.Function):
         dev = w.device
         A = torch.empty((grp.n_rows, grp.K), dtype=torch.float32, device=dev)
         alphas = [torch.empty((blk["n_edges"], lay["H"]), dtype=torch.float32, device=dev) for blk, lay in zip(grp.blocks, grp.layout)]
-        z = grp.run(w, b, uw_d, a_save=A, alphas=alphas)
+        z = grp.run(w, b, uw_d, alphas, kept=A)
         ctx.grp, ctx.A, ctx.alphas, ctx.n_srcs = grp, A, alphas, len(srcs)
         ctx.src_shapes = [tuple(t.shape) for t in srcs]
         ctx.dst_shape = None if x_dst is None else tuple(x_dst.shape)
@@ -3639,7 +3627,7 @@ class _HeteroTconvGroup(torch.autograd.Function):
                     guw[:, lay["w0"]:lay["w0"] + H * D] = dw
                 si = blk["src"]
                 if si is not None and need_src[si]:
-                    row_ptr_t, col_t, perm = _relation_transpose_perm(grp.hops[k], ctx.src_shapes[si][0])
+                    row_ptr_t, col_t, perm = _relation_transpose(grp.hops[k], ctx.src_shapes[si][0], want_perm=True)
                     transformer_bwd_src(row_ptr_t, col_t, perm, None, D, H, -1, alphas[k], ds, dA[:, c0:], grp.u_w(uw, k)[0], gsrcs[si])
             if need_dst and grp.root is not None:
                 gdst = torch.zeros(ctx.dst_shape, dtype=torch.float32, device=dev)
@@ -3896,6 +3884,38 @@ class HeteroConv(torch.nn.Module):
             out[et[2]] = y if et[2] not in out else out[et[2]] + y
         return {t: torch.relu(v) for t, v in out.items()} if act == "relu" else out
 
+    # ---- what the one-launch routes (_forward_layer_sage, _forward_layer_tconv) share -------------------------------------
+    @staticmethod
+    def _relu_of(act) -> bool:
+        if act not in (None, "relu"):
+            raise ValueError("HeteroConv: act is None or 'relu', not %r" % (act,))
+        return act == "relu"
+
+    @staticmethod
+    def _source_slot(srcs, x, ids):
+        """Index of ``x`` among the group's differentiable source tensors ``srcs`` (appended when new); None for a table read
+        through a node list ``ids``."""
+        if ids is not None:
+            return None
+        si = next((k for k, t in enumerate(srcs) if t is x), None)
+        if si is None:
+            srcs.append(x)
+            si = len(srcs) - 1
+        return si
+
+    @staticmethod
+    def _run_group(out, dt, grp, *, fn, place, needs_grad, args, srcs):
+        """The group's rows into ``out[dt]``: under autograd ``fn.apply(grp, *args, root_src, *srcs)`` (``root_src``: the
+        root's rows when they are resident) placed by ``_place_rows``, otherwise the group's launches ``grp.run(*args)``, the
+        last one writing ``out[dt]`` through ``place`` itself."""
+        if needs_grad:
+            root_src = grp.root[0] if grp.root is not None and grp.root[2] is None else None
+            _place_rows(out, dt, fn.apply(grp, *args, root_src, *srcs), place)
+        elif place is None:
+            out[dt] = grp.run(*args)
+        else:
+            grp.run(*args, out=out[dt], out_rows=place)
+
     # ---- SAGEConv relations: one launch per (hop, destination type) -----------------------------------------------------
     def _sage_weights(self, dt, grad: bool = False):
         """``(Wstack [N, K], bias sum [N] | None)`` of destination type ``dt``: ``[W_l^r1 | W_l^r2 | ... | sum_r W_r^r]`` over the
@@ -3921,9 +3941,7 @@ class HeteroConv(torch.nn.Module):
         ``hetero_sage_plan``), bias, ReLU and row placement folded in.  A ``LazyRows`` input (int64 ids, fp32 table, 16-B rows)
         is read through its node list, per node type.  Under autograd one ``_HeteroSageGroup`` per group.  Shapes outside the
         kernel's domain: ``_forward_sage_library``."""
-        if act not in (None, "relu"):
-            raise ValueError("HeteroConv: act is None or 'relu', not %r" % (act,))
-        relu = act == "relu"
+        relu = self._relu_of(act)
         X, ids = {}, {}
         for t, v in xs.items():
             if v is None:
@@ -3960,38 +3978,26 @@ class HeteroConv(torch.nn.Module):
                 if x.shape[1] != c.lin_l.weight.shape[1]:
                     raise ValueError("HeteroConv: x_dict[%r] has %d features, SAGEConv of %r takes %d"
                                      % (et[0], x.shape[1], et, c.lin_l.weight.shape[1]))
-                si = None
-                if ids[et[0]] is None:
-                    si = next((k for k, t in enumerate(srcs) if t is x), None)
-                    if si is None:
-                        srcs.append(x)
-                        si = len(srcs) - 1
+                si = self._source_slot(srcs, x, ids[et[0]])
                 if r is None:       # the hop lists no such relation: its root term and bias still count
                     row_ptr, col = torch.zeros(n_f + 1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
                 else:
                     row_ptr, col = r.row_ptr, r.col
                 blocks.append((row_ptr, col, x, ids[et[0]], c.aggr == "mean", si))
                 hops.append(r)
-            root = root_src = None
+            root = None
             roots = [self.conv(et).lin_r for et in self.edge_types if et[2] == dt and self.conv(et).lin_r is not None]
             if roots:
                 F_dst = roots[0].weight.shape[1]
                 if X[dt].shape[1] != F_dst:
                     raise ValueError("HeteroConv: x_dict[%r] has %d features, the root weights take %d" % (dt, X[dt].shape[1], F_dst))
                 root = (X[dt], mine[0].dst_rows, ids[dt])
-                root_src = X[dt] if ids[dt] is None else None
             plan = hetero_sage_plan([b[2].shape[1] for b in blocks], 0 if root is None else root[0].shape[1])
             grp = _SageGroup(blocks, hops, root, plan, n_f, self._width(dt), relu, self.stage_tag + " hop %d %s" % (hop + 1, dt))
-            place = mine[0].out_rows
             if dt not in weights:
                 weights[dt] = self._sage_weights(dt, grad=needs_grad)
-            wstack, bias = weights[dt]
-            if needs_grad:
-                _place_rows(out, dt, _HeteroSageGroup.apply(grp, wstack, bias, root_src, *srcs), place)
-            elif place is None:
-                out[dt] = grp.run(wstack, bias)
-            else:
-                grp.run(wstack, bias, out=out[dt], out_rows=place)
+            self._run_group(out, dt, grp, fn=_HeteroSageGroup, place=mine[0].out_rows, needs_grad=needs_grad, args=weights[dt],
+                            srcs=srcs)
         return out
 
     # ---- TransformerConv relations: one launch per (hop, destination type) ----------------------------------------------
@@ -4044,9 +4050,7 @@ class HeteroConv(torch.nn.Module):
         it.  A ``LazyRows`` input (int64 or int32 ids, fp32 table, 16-B rows) is read through its node list, per node type.
         Under autograd one ``_HeteroTconvGroup`` per group.  Shapes outside the kernel's domain, and CPU tensors:
         ``_forward_tconv_library``."""
-        if act not in (None, "relu"):
-            raise ValueError("HeteroConv: act is None or 'relu', not %r" % (act,))
-        relu = act == "relu"
+        relu = self._relu_of(act)
         for et in self.edge_types:
             c = self.conv(et)
             if c.dropout > 0 and c.training:
@@ -4120,12 +4124,7 @@ class HeteroConv(torch.nn.Module):
             blocks, hops, srcs = [], [], []
             for et in ends[dt]:
                 x, r = X[et[0]], listed.get(et)
-                si = None
-                if ids[et[0]] is None:
-                    si = next((k for k, t in enumerate(srcs) if t is x), None)
-                    if si is None:
-                        srcs.append(x)
-                        si = len(srcs) - 1
+                si = self._source_slot(srcs, x, ids[et[0]])
                 D = self.conv(et).edge_dim or 0
                 if r is None or r.n_edges == 0:      # no edge of the relation in this hop: zero blocks, its skip term still counts
                     row_ptr = torch.zeros(n_f + 1, dtype=torch.int32, device=dev)
@@ -4136,20 +4135,12 @@ class HeteroConv(torch.nn.Module):
                     ea = eas[et][r.edge_base:r.edge_base + n_e] if D else None
                 blocks.append(dict(row_ptr=row_ptr, col=col, x=x, ids=ids[et[0]], ea=ea, src=si, n_edges=n_e))
                 hops.append(r)
-            root = root_src = None
-            if any(self.conv(et).root_weight for et in ends[dt]):
-                root = (X[dt], dst_rows, ids[dt])
-                root_src = X[dt] if ids[dt] is None else None
+            root = (X[dt], dst_rows, ids[dt]) if any(self.conv(et).root_weight for et in ends[dt]) else None
             plan = hetero_sage_plan([lay["width"] for lay in layout], 0 if root is None else root[0].shape[1],
                                     max_k=HETERO_TRANSFORMER_MAX_K, max_rel=L.HETERO_TRANSFORMER_MAX_RELATIONS)
             grp = _TconvGroup(blocks, layout, hops, root, plan, n_f, self._width(dt), relu, self.stage_tag + " hop %d %s" % (hop + 1, dt))
-            place = mine[0].out_rows
-            if needs_grad:
-                _place_rows(out, dt, _HeteroTconvGroup.apply(grp, wt, bias, uw, root_src, *srcs), place)
-            elif place is None:
-                out[dt] = grp.run(wt, bias, uw)
-            else:
-                grp.run(wt, bias, uw, out=out[dt], out_rows=place)
+            self._run_group(out, dt, grp, fn=_HeteroTconvGroup, place=mine[0].out_rows, needs_grad=needs_grad, args=(wt, bias, uw),
+                            srcs=srcs)
         return out
 
     def _forward_tconv_library(self, x, graph: HeteroLayerGraph, relu: bool, eas):
