@@ -10,7 +10,8 @@
 //
 // hetero_sage_kernel — one workgroup of 256 threads per 16-row tile, as the other layer kernels.  Phase 1: the C row is K / 4
 // <= 256 float4 chunks, one chunk per thread (chunk -> relation block and feature float4), held in a register while the thread
-// walks its relation's edges of its rows, scaled and flushed to the LDS tile at each row boundary; sums run in CSR order.  The
+// walks its relation's edges of its rows, scaled and flushed to the LDS tile at each row boundary; sums run in CSR order, compensated
+// (Kahan): a row of thousands of edges is as close to float64 as a short one.  The
 // chain bounds -> column -> id -> row is what bounds such a walk, not bytes, so it is cut in two: the tile's edges (one range
 // of every relation's CSR) are resolved to row addresses by all 256 threads, one edge per thread, and staged in LDS piece by
 // piece; the walk then has the row loads alone in flight, 16 per thread.  When K / 4 <= 128 several rows are built at once
@@ -75,6 +76,7 @@ __global__ void __launch_bounds__(kThreads) hetero_sage_kernel(hsage_args a)
   int e = walks ? rpb[lr0] : 0;
   const int e_end = walks ? rpb[lr1] : 0;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 lost = {0.f, 0.f, 0.f, 0.f};          // Kahan: what the adds into acc rounded away so far (a 3000-edge mean row within 1e-6)
   const int cap = a.n_rel > 0 ? (kStage / a.n_rel) & ~15 : kStage;
   int n_pieces = 0;
   for (int r = 0; r < a.n_rel; ++r) n_pieces = std::max(n_pieces, (rp[r][rows_here] - rp[r][0] + cap - 1) / cap);
@@ -116,9 +118,13 @@ __global__ void __launch_bounds__(kThreads) hetero_sage_kernel(hsage_args a)
               if (mean && deg > 1) acc *= 1.f / (float)deg;
               reinterpret_cast<f32x4*>(tile + lr * a.SD)[q] = acc;
               acc     = f32x4{0.f, 0.f, 0.f, 0.f};
+              lost    = f32x4{0.f, 0.f, 0.f, 0.f};
               row_end = rpb[++lr + 1];
             }
-            acc += scaled ? w[u] * v[u] : v[u];
+            const f32x4 y = (scaled ? w[u] * v[u] : v[u]) - lost;
+            const f32x4 s = acc + y;
+            lost = (s - acc) - y;
+            acc  = s;
           }
         }
       }
@@ -132,7 +138,7 @@ __global__ void __launch_bounds__(kThreads) hetero_sage_kernel(hsage_args a)
         const int deg = rpb[lr + 1] - rpb[lr];
         if (mean && deg > 1) acc *= 1.f / (float)deg;
         reinterpret_cast<f32x4*>(tile + lr * a.SD)[q] = acc;
-        acc = f32x4{0.f, 0.f, 0.f, 0.f};
+        acc = lost = f32x4{0.f, 0.f, 0.f, 0.f};
       }
     }
     for (int lz = std::max(lr0, rows_here); lz < lr0 + rps; ++lz)   // tile rows past the last row: zero

@@ -700,6 +700,74 @@ def test_hetero_sage_layer(hiplib, far):
         _same(run(sx, None, vb, None), base, "strided x")
 
 
+def test_hetero_transformer_layer(hiplib, far):
+    """wgamd_hetero_transformer_layer_f32(_train) (wg_transformer_hetero.hip): two relations (H = 2 with edge attributes over F = 64,
+    H = 1 over F = 32) ending in one type, both read through node lists into the far buffer (kinds 1 and 2), the root rows through
+    a list as well, and ``out`` at band rows of a far view through ``out_rows``: output, kept A and every alpha bit for bit the
+    compact run's — which is within test_gpu_hetero_transformer.py's bound of the float64 restatement."""
+    import torch
+    from wholegraph_amd import nn
+    from hetero_launch_ref import block_width, hetero_transformer_launch_ref
+    Fa, Fb, Ha, Hb, D, N = 64, 32, 2, 1, 3, 32
+    rows_a, rows_b = fo.live_rows(Fa, 4), fo.live_rows(Fb, 4)
+    va, vb = _values(len(rows_a), Fa, 75), _values(len(rows_b), Fb, 76)
+    rpa, cola, dst_rows = _hop(len(rows_a), 77)
+    rpb, colb, _ = _hop(len(rows_b), 78)
+    g = torch.Generator(device="cuda").manual_seed(79)
+    rnd = lambda *s: torch.randn(s, generator=g, device="cuda")  # noqa: E731
+    ea = rnd(int(cola.shape[0]), D)
+    ua, wa, ub = rnd(N_DST, Ha * Fa) * 0.2, rnd(N_DST, Ha * D) * 0.5, rnd(N_DST, Hb * Fb) * 0.3
+    K = Ha * block_width(Fa, D) + Hb * block_width(Fb, 0) + Fa
+    wt, bias = rnd(N, K) * 0.2, rnd(N)
+
+    def run(xa, ida, xb, idb, out=None, out_rows=None):
+        A = torch.empty((N_DST, K), device="cuda")
+        al = [torch.empty((int(cola.shape[0]), Ha), device="cuda"), torch.empty((int(colb.shape[0]), Hb), device="cuda")]
+        rels = [(rpa, cola, xa, ida, ea, ua, wa, Ha, al[0]), (rpb, colb, xb, idb, None, ub, None, Hb, al[1])]
+        before = nn.hetero_transformer_launches
+        out = nn.hetero_transformer_launch(rels, N_DST, wt, N, root=(xa, dst_rows, ida), bias=bias, relu=True, out_rows=out_rows,
+                                           out=out, a_save=A)
+        assert nn.hetero_transformer_launches - before == 1
+        return out, A, al[0], al[1]
+
+    def same(got, what):
+        for a, c, part in zip(got, base, ("out", "A", "alpha a", "alpha b")):
+            _same(a, c, "%s %s" % (what, part))
+    base = run(va, None, vb, None)
+    rels64 = [(rpa, cola, va, None, ea, ua, wa, Ha, None), (rpb, colb, vb, None, None, ub, None, Hb, None)]
+    ref, _, mag, ralpha = hetero_transformer_launch_ref(rels64, N_DST, wt, N, root=(va, dst_rows, None), bias=bias, relu=True)
+    err = (base[0].double() - ref).abs()
+    print("hetero transformer layer max err / bound %.3f" % float((err / (1e-5 * mag)).max()))
+    assert bool(torch.isfinite(base[0]).all()) and bool((err <= 1e-5 * mag).all()), float(err.max())   # (test_gpu_hetero_transformer.py's bar)
+    assert all(float((a.double() - b).abs().max()) <= 1e-5 for a, b in zip(base[2:], ralpha))
+    ar = lambda n: torch.arange(n, device="cuda")  # noqa: E731
+    same(run(va, ar(len(rows_a)), vb, ar(len(rows_b))), "arange")
+    fa, fb = fo.view(far, Fa, torch.float32), fo.view(far, Fb, torch.float32)
+    # both views start at the buffer's first byte and their bands meet at every threshold: one relation's table at a time
+    with live(fa, rows_a, va):
+        for dt in (torch.int32, torch.int64):
+            same(run(fa, _ids(rows_a, dt), vb, None), "relation a %s" % dt)
+    with live(fb, rows_b, vb):
+        for dt in (torch.int32, torch.int64):
+            same(run(va, None, fb, _ids(rows_b, dt)), "relation b %s" % dt)
+    sx = fo.strided_view(far, len(rows_a), Fa, fo.spanning_ld(len(rows_a), Fa))
+    with live_strided(sx, va):
+        same(run(sx, None, vb, None), "strided x")
+    # out_rows: band row numbers of a [rows, N] view of the far buffer (as test_far_outputs_of_the_sage_and_gcn_layers)
+    v = fo.view(far, N, torch.float32)
+    rows = fo.live_rows(N, 4, per_band=44)
+    rows = np.concatenate([rows[:N_DST - 1], rows[-1:]])
+    assert len(rows) == N_DST and rows[-1] == v.shape[0] - 1
+    out_rows = torch.from_numpy(rows).cuda()
+    try:
+        got = run(va, None, vb, None, out=v, out_rows=out_rows)
+        torch.cuda.synchronize()
+        same((v[out_rows],) + got[1:], "out_rows")
+        assert fo.is_fill(v, fo.neighbours(rows, v.shape[0]))
+    finally:
+        fo.clear(v, rows)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # GAT (forward)
 # ---------------------------------------------------------------------------------------------------------------------
