@@ -22,7 +22,8 @@ Shared by ``GATConv`` and the routes of ``HeteroConv`` over a call group: ``_tab
 may read in place through its node list) with ``_terms_by_id`` (whose attention terms are then the table's rows') and
 ``_refuse_lazy_table_grad``; ``_sum_of`` (the relations' biases or root weights added up); ``_relation_groups`` /
 ``_group_outputs`` / ``_place_rows`` (a heterogeneous layer graph's relations per (hop, destination type), the per-type float32
-outputs and a group's rows placed in them); ``HeteroConv._cached`` (every derived parameter keyed on the parameters it is built from).
+outputs and a group's rows placed in them).  Shared by every layer: ``_derived`` (every derived form of the weights, keyed on the
+parameters it is built from).
 """
 import ctypes
 import math
@@ -202,11 +203,14 @@ def sage_layer_fused_preferred(F_: int, N: int) -> bool:
 
 
 # ---- derived-weight caches and HIP-graph capture ---------------------------------------------------------------------------
-# The transposed / padded / bf16-split forms of a layer's weights are cached against the weight tensor's version counter.  A
-# captured training step (cugraph_pyg_amd.loader.PerBatchStep) updates the weights INSIDE the graph: Python does not run on a
-# replay, so (a) while a stream is capturing the derived forms are rebuilt unconditionally — their kernels become part of the
-# graph and run on every replay — and nothing is cached, and (b) every replay bumps `_weights_gen`, which is part of every
-# cache key, so eager code that follows a replay never sees a form derived from the weights of an earlier step.
+# The transposed / padded / stacked / folded / bf16-split forms of a layer's weights all come from `_derived`, the one place
+# that knows the rule: a form is kept for as long as every parameter it is built from has the version, address and device it had,
+# and no `bump_weight_generation` happened since.  A captured training step (cugraph_pyg_amd.loader.PerBatchStep) updates the
+# weights INSIDE the graph: Python does not run on a replay, so (a) while a stream is capturing the derived forms are rebuilt
+# unconditionally — their kernels become part of the graph and run on every replay — and nothing is read or stored, and (b)
+# every replay bumps `_weights_gen`, which is part of every key, so eager code that follows a replay never sees a form derived
+# from the weights of an earlier step.  The per-graph forms of a hop (`HopGraph.with_self_loops`, `.transposed`) are keyed on
+# `_graph_epoch()` instead.
 _weights_gen = 0
 _capture_epoch = 0       # bumped by begin_capture(): per-capture caches (a hop's transpose) are keyed on it
 
@@ -235,43 +239,74 @@ def _refuse_capture(layer, caches: str):
                            "capture-safe; SAGEConv layers are" % (type(layer).__name__, caches))
 
 
+def _graph_epoch() -> int:
+    """Key of a hop's per-graph forms: under HIP-graph capture the hop's arrays are fixed buffers refilled before every replay,
+    so the forms are made once per capture (``begin_capture``) and become part of the graph; 0 in eager code."""
+    return _capture_epoch if _capturing() else 0
+
+
+def _detached(value):
+    """``value`` without autograd history and never a ``Parameter``: tensors detached, also inside a tuple or list."""
+    if torch.is_tensor(value):
+        return value.detach()
+    if isinstance(value, (tuple, list)):
+        return type(value)(_detached(v) for v in value)
+    return value
+
+
+def _derived(holder, name, params, build, extra=(), grad=False):
+    """``build()``: a form of the tensors ``params`` (None entries allowed) that the kernels read, kept on ``holder`` (a module
+    or a tensor) under ``name`` — the rule of the comment above.  A hit returns the stored object itself.  A miss runs ``build``
+    without autograd and stores the detached result; under capture it is built, never read or stored.  ``grad``: ``build()``
+    under autograd, nothing kept.  A holder that takes no attribute (a tensor subclass without ``__dict__``) builds on every call."""
+    if grad:
+        with torch.enable_grad():
+            return build()
+    eager = not _capturing()
+    if eager:
+        key = (tuple(None if p is None else (p._version, p.data_ptr(), p.device) for p in params), extra, _weights_gen)
+        store = getattr(holder, "_wgamd_derived", None)
+        if store is not None:
+            hit = store.get(name)
+            if hit is not None and hit[0] == key:
+                return hit[1]
+    with torch.no_grad():
+        value = _detached(build())
+    if eager:
+        if store is None:
+            store = {}
+            try:
+                holder._wgamd_derived = store
+            except AttributeError:
+                pass
+        store[name] = (key, value)
+    return value
+
+
 def _padded_head(w_t: torch.Tensor, bias, Np: int):
-    """``w_t`` [2F, N] and ``bias`` [N] with zero columns up to Np, cached on the weight tensor (version-checked)."""
-    hit = getattr(w_t, "_wgamd_padded", None) if not _capturing() else None
-    key = (w_t._version, w_t.data_ptr(), None if bias is None else (bias._version, bias.data_ptr()), Np, _weights_gen)
-    if hit is not None and hit[0] == key:
-        return hit[1], hit[2]
-    wp = torch.zeros((w_t.shape[0], Np), dtype=w_t.dtype, device=w_t.device)
-    wp[:, :w_t.shape[1]] = w_t
-    bp = None
-    if bias is not None:
-        bp = torch.zeros(Np, dtype=bias.dtype, device=bias.device)
-        bp[:bias.shape[0]] = bias
-    if not _capturing():
-        try:
-            w_t._wgamd_padded = (key, wp, bp)
-        except AttributeError:
-            pass
-    return wp, bp
+    """``w_t`` [2F, N] and ``bias`` [N] with zero columns up to Np, kept on the weight tensor like its planes."""
+    def build():
+        wp = torch.zeros((w_t.shape[0], Np), dtype=w_t.dtype, device=w_t.device)
+        wp[:, :w_t.shape[1]] = w_t
+        bp = None
+        if bias is not None:
+            bp = torch.zeros(Np, dtype=bias.dtype, device=bias.device)
+            bp[:bias.shape[0]] = bias
+        return wp, bp
+    return _derived(w_t, "padded", (w_t, bias), build, extra=Np)
 
 
 def sage_weight_planes(w_t: torch.Tensor) -> torch.Tensor:
     """``w_t`` [2F, N] fp32 -> the three bf16 planes ``wgamd_sage_layer_fused_bf16x3`` multiplies with (exact 3-way split:
-    hi + mid + lo == w).  Cached ON the weight tensor object together with its version counter, so a layer pays for the
-    split once per optimizer step and the cache can never outlive (or be confused with another tensor at) the same address."""
-    hit = getattr(w_t, "_wgamd_planes", None) if not _capturing() else None
-    if hit is not None and hit[0] == (w_t._version, _weights_gen) and hit[1] == w_t.data_ptr():
-        return hit[2]
-    K, N = w_t.shape
-    planes = torch.empty(L.lib().wgamd_sage_weight_planes_bytes(K, N), dtype=torch.uint8, device=w_t.device)
-    L.check(L.lib().wgamd_sage_split_weight_bf16x3(w_t.data_ptr(), w_t.stride(0), K, N, planes.data_ptr(), get_stream()),
-            "wgamd_sage_split_weight_bf16x3")
-    if not _capturing():
-        try:
-            w_t._wgamd_planes = ((w_t._version, _weights_gen), w_t.data_ptr(), planes)
-        except AttributeError:      # a tensor subclass without a __dict__: split on every call
-            pass
-    return planes
+    hi + mid + lo == w).  Kept ON the weight tensor object (``_derived``), so a layer pays for the split once per optimizer
+    step and the cache can never outlive (or be confused with another tensor at) the same address."""
+    def build():
+        K, N = w_t.shape
+        planes = torch.empty(L.lib().wgamd_sage_weight_planes_bytes(K, N), dtype=torch.uint8, device=w_t.device)
+        L.check(L.lib().wgamd_sage_split_weight_bf16x3(w_t.data_ptr(), w_t.stride(0), K, N, planes.data_ptr(), get_stream()),
+                "wgamd_sage_split_weight_bf16x3")
+        return planes
+    return _derived(w_t, "planes", (w_t,), build)
 
 
 SAGE_FULL_TILES = 2          # WGAMD_SAGE_FULL_TILES (include/wgamd_ext.h): or-ed into the relu argument of a small launch
@@ -316,24 +351,20 @@ def sage_layer_fused_forward(row_ptr, col, x, self_rows, w_t, bias=None, relu=Fa
     assert self_rows.dtype == torch.int64 and self_rows.is_contiguous()
     if prepared is not None:      # (planes, padded bias, N) of sage_layer_planes: the bf16x3 kernel's operand, ready made
         n_rows, F_, N = row_ptr.shape[0] - 1, x.shape[1], prepared[2]
-        assert sage_layer_fused_supported(F_, _padded_width(N)) and _pick_precision(F_, _padded_width(N), precision) == "bf16x3"
         bias = prepared[1]
     else:
         assert w_t.dtype == torch.float32 and w_t.dim() == 2 and w_t.stride(1) == 1 and w_t.shape[0] == 2 * x.shape[1]
         n_rows, F_, N = row_ptr.shape[0] - 1, x.shape[1], w_t.shape[1]
     Np = _padded_width(N) if sage_layer_fused_supported(F_, N) else N
     user_out = None
-    if Np != N and prepared is not None:
-        if out is not None and out.stride(0) != Np:
-            assert out.shape == (n_rows, N) and out.dtype == torch.float32, "out must be float32 [n_rows, N]"
-            user_out, out = out, None
-    elif Np != N:
-        # zero weight columns / bias entries up to the width the kernel runs at (cached on the weight like its planes); the
-        # kernel then WRITES Np columns per row.  A caller's `out` is written in place only when it is the [:, :N] view of
-        # an explicit [n_rows, Np] scratch (row stride == Np: columns N..Np-1 are the caller's padding by construction);
-        # any other `out` is filled from a temporary, so neither a wider buffer's own columns are overwritten nor a
-        # narrower one silently dropped.
-        w_t, bias = _padded_head(w_t, bias, Np)
+    if Np != N:
+        # zero weight columns / bias entries up to the width the kernel runs at (kept on the weight like its planes; a
+        # ``prepared`` operand is padded already); the kernel then WRITES Np columns per row.  A caller's `out` is written in
+        # place only when it is the [:, :N] view of an explicit [n_rows, Np] scratch (row stride == Np: columns N..Np-1 are the
+        # caller's padding by construction); any other `out` is filled from a temporary, so neither a wider buffer's own
+        # columns are overwritten nor a narrower one silently dropped.
+        if prepared is None:
+            w_t, bias = _padded_head(w_t, bias, Np)
         if out is not None and out.stride(0) != Np:
             assert out.shape == (n_rows, N) and out.dtype == torch.float32, "out must be float32 [n_rows, N]"
             user_out, out = out, None
@@ -341,57 +372,41 @@ def sage_layer_fused_forward(row_ptr, col, x, self_rows, w_t, bias=None, relu=Fa
         out = torch.empty((n_rows, Np), dtype=torch.float32, device=x.device)[:, :N]
     assert out.shape == (n_rows, N) and out.dtype == torch.float32 and out.stride(1) == 1
 
-    def done(res):
-        if user_out is None:
-            return res
-        user_out.copy_(res)
-        return user_out
     N = Np
     ids_ptr, ids_dt = _ids_args(x, src_ids)
     # (an edge-less hop: an empty tensor's null pointer is refused by the entry points; every row is empty, so the stand-in is not read)
     col_ptr = _nonempty(col, torch.int32).data_ptr()
-    if x16:
-        if ids_dt == L.IDS_BYTE_OFFSETS:
-            raise ValueError("a peer-mapped table (byte-offset ids) is read as float32 rows only, not as %s" % x.dtype)
-        if not (sage_layer_fused_supported(F_, N) and _pick_precision(F_, N, precision) == "bf16x3"
-                and out.stride(0) % 4 == 0 and out.data_ptr() % 16 == 0):
-            raise ValueError("a %s x is read by the bf16x3 layer kernel only (precision=%r, F=%d, N=%d): pass x.float()"
-                             % (x.dtype, precision or _FUSED_PRECISION, F_, N))
+    # the route, decided once (the bf16x3 kernel's epilogue stores 16 B per lane: rows of `out` 16-B aligned)
+    bf16x3 = (sage_layer_fused_supported(F_, N) and _pick_precision(F_, N, precision) == "bf16x3"
+              and out.stride(0) % 4 == 0 and out.data_ptr() % 16 == 0)
+    if x16 and ids_dt == L.IDS_BYTE_OFFSETS:
+        raise ValueError("a peer-mapped table (byte-offset ids) is read as float32 rows only, not as %s" % x.dtype)
+    if prepared is not None and not bf16x3:
+        raise ValueError("prepared: the operand of sage_layer_planes is read by the bf16x3 layer kernel only (precision=%r, F=%d, "
+                         "N=%d), which needs the rows of out 16-B aligned (out.stride(0) %% 4 == 0 and out.data_ptr() %% 16 == 0)"
+                         % (precision or _FUSED_PRECISION, F_, N))
+    if x16 and not bf16x3:
+        raise ValueError("a %s x is read by the bf16x3 layer kernel only (precision=%r, F=%d, N=%d): pass x.float()"
+                         % (x.dtype, precision or _FUSED_PRECISION, F_, N))
+    assert ids_dt != L.IDS_BYTE_OFFSETS or bf16x3, "a peer-mapped table is read by the bf16x3 layer kernel only"
+    if bf16x3:
         planes = prepared[0] if prepared is not None else sage_weight_planes(w_t)
         flags = int(bool(relu)) | (SAGE_FULL_TILES if prepared is not None and prepared[3] else 0)
         assert agg_out is None or (agg_out.shape == (n_rows, F_) and agg_out.dtype == torch.float32 and agg_out.stride(1) == 1)
         L.check(L.lib().wgamd_sage_layer_fused_bf16x3_x_train(
             row_ptr.data_ptr(), col_ptr, n_rows, x.data_ptr(), torch_dtype_to_wm(x.dtype), x.stride(0), x.shape[0], F_, ids_ptr,
-            ids_dt, self_rows.data_ptr(), int(bool(mean)), planes.data_ptr(), N, None if bias is None else bias.data_ptr(),
-            flags, out.data_ptr(), out.stride(0), _ptr(agg_out), 0 if agg_out is None else agg_out.stride(0), get_stream()),
-            "wgamd_sage_layer_fused_bf16x3_x_train")
-        return done(out)
-    assert ids_dt != L.IDS_BYTE_OFFSETS or (sage_layer_fused_supported(F_, N) and _pick_precision(F_, N, precision) == "bf16x3"), \
-        "a peer-mapped table is read by the bf16x3 layer kernel only"
-    if (sage_layer_fused_supported(F_, N) and _pick_precision(F_, N, precision) == "bf16x3"
-            and out.stride(0) % 4 == 0 and out.data_ptr() % 16 == 0):      # its epilogue stores 16 B per lane
-        planes = prepared[0] if prepared is not None else sage_weight_planes(w_t)
-        flags = int(bool(relu)) | (SAGE_FULL_TILES if prepared is not None and prepared[3] else 0)
-        if agg_out is not None:
-            assert agg_out.shape == (n_rows, F_) and agg_out.dtype == torch.float32 and agg_out.stride(1) == 1
-            L.check(L.lib().wgamd_sage_layer_fused_bf16x3_train(
-                row_ptr.data_ptr(), col_ptr, n_rows, x.data_ptr(), x.stride(0), x.shape[0], F_, ids_ptr, ids_dt,
-                self_rows.data_ptr(), int(bool(mean)), planes.data_ptr(), N, None if bias is None else bias.data_ptr(),
-                flags, out.data_ptr(), out.stride(0), agg_out.data_ptr(), agg_out.stride(0), get_stream()),
-                "wgamd_sage_layer_fused_bf16x3_train")
-            return done(out)
-        L.check(L.lib().wgamd_sage_layer_fused_bf16x3(
-            row_ptr.data_ptr(), col_ptr, n_rows, x.data_ptr(), x.stride(0), x.shape[0], F_, ids_ptr, ids_dt,
-            self_rows.data_ptr(), int(bool(mean)), planes.data_ptr(), N, None if bias is None else bias.data_ptr(),
-            flags, out.data_ptr(), out.stride(0), get_stream()), "wgamd_sage_layer_fused_bf16x3")
-        return done(out)
-    assert agg_out is None, "agg_out: only the bf16x3 layer kernel keeps the aggregate (sage_layer_train_supported)"
-    L.check(L.lib().wgamd_sage_layer_fused_f32(
-        row_ptr.data_ptr(), col_ptr, n_rows, x.data_ptr(), x.stride(0), x.shape[0], F_, ids_ptr, ids_dt,
-        self_rows.data_ptr(),
-        int(bool(mean)), w_t.data_ptr(), w_t.stride(0), N, None if bias is None else bias.data_ptr(), int(bool(relu)),
-        out.data_ptr(), out.stride(0), get_stream()), "wgamd_sage_layer_fused_f32")
-    return done(out)
+            ids_dt, self_rows.data_ptr(), int(bool(mean)), planes.data_ptr(), N, _ptr(bias), flags, out.data_ptr(), out.stride(0),
+            _ptr(agg_out), 0 if agg_out is None else agg_out.stride(0), get_stream()), "wgamd_sage_layer_fused_bf16x3_x_train")
+    else:
+        assert agg_out is None, "agg_out: only the bf16x3 layer kernel keeps the aggregate (sage_layer_train_supported)"
+        L.check(L.lib().wgamd_sage_layer_fused_f32(
+            row_ptr.data_ptr(), col_ptr, n_rows, x.data_ptr(), x.stride(0), x.shape[0], F_, ids_ptr, ids_dt, self_rows.data_ptr(),
+            int(bool(mean)), w_t.data_ptr(), w_t.stride(0), N, _ptr(bias), int(bool(relu)), out.data_ptr(), out.stride(0),
+            get_stream()), "wgamd_sage_layer_fused_f32")
+    if user_out is None:
+        return out
+    user_out.copy_(out)
+    return user_out
 
 
 def sage_layer_train_supported(F_: int, N: int) -> bool:
@@ -651,19 +666,14 @@ def gat_transform_supported(F_: int, heads: int, C: int) -> bool:
 
 
 def _gat_weight_tiles(w: torch.Tensor, heads: int) -> torch.Tensor:
-    """``w`` [F, H C] in the order ``wgamd_gat_transform_heads_bf16x3`` reads it; cached on the weight like ``sage_weight_planes``."""
-    hit = getattr(w, "_wgamd_gat_tiles", None)
-    if hit is not None and hit[0] == (w._version, _weights_gen) and hit[1] == w.data_ptr():
-        return hit[2]
-    F_, C = w.shape[0], w.shape[1] // heads
-    tiles = torch.empty(L.lib().wgamd_gat_transform_weight_bytes(F_, heads, C), dtype=torch.uint8, device=w.device)
-    L.check(L.lib().wgamd_gat_transform_weight_tiles(w.data_ptr(), w.stride(0), F_, heads, C, tiles.data_ptr(), get_stream()),
-            "wgamd_gat_transform_weight_tiles")
-    try:
-        w._wgamd_gat_tiles = ((w._version, _weights_gen), w.data_ptr(), tiles)
-    except AttributeError:
-        pass
-    return tiles
+    """``w`` [F, H C] in the order ``wgamd_gat_transform_heads_bf16x3`` reads it; kept on the weight like ``sage_weight_planes``."""
+    def build():
+        F_, C = w.shape[0], w.shape[1] // heads
+        tiles = torch.empty(L.lib().wgamd_gat_transform_weight_bytes(F_, heads, C), dtype=torch.uint8, device=w.device)
+        L.check(L.lib().wgamd_gat_transform_weight_tiles(w.data_ptr(), w.stride(0), F_, heads, C, tiles.data_ptr(), get_stream()),
+                "wgamd_gat_transform_weight_tiles")
+        return tiles
+    return _derived(w, "gat_tiles", (w,), build, extra=heads)
 
 
 def gat_transform_heads_fused(agg, w, heads, acc_in=None, bias=None, relu=False, out_rows=None, out=None):
@@ -1119,8 +1129,9 @@ class HopGraph:
     def with_self_loops(self):
         """``(row_ptr, col)`` of the hop with every destination's own input row in front of its sampled neighbours — what
         ``csr_add_self_loop`` (graph_op.h:44-48) does for a square CSR, here with ``self_rows`` as the diagonal; made once."""
-        if getattr(self, "_loops", None) is None or self._loops_key != (_capture_epoch if _capturing() else 0):
-            self._loops_key = _capture_epoch if _capturing() else 0
+        epoch = _graph_epoch()
+        if getattr(self, "_loops", None) is None or self._loops_key != epoch:
+            self._loops_key = epoch
             from . import graph_ops
             n = self.n_rows
             rp, col = graph_ops.add_csr_self_loop(self.row_ptr, self.col)     # row i = [i] ++ row i (csr_add_self_loop) ...
@@ -1139,7 +1150,7 @@ class HopGraph:
         has no edges)."""
         # (under HIP-graph capture the hop's arrays are fixed buffers REFILLED before every replay: the transpose must be part
         #  of the graph, once per capture)
-        key = (n_src, _capture_epoch if _capturing() else 0)
+        key = (n_src, _graph_epoch())
         t = self._t
         if t is None or t.key != key:
             t = self._t = _Transposed(key)
@@ -1438,7 +1449,7 @@ class SAGEConv(torch.nn.Module):
         self.in_channels, self.out_channels, self.aggr, self.root_weight = in_channels, out_channels, aggr, root_weight
         self.lin_l = torch.nn.Linear(in_channels[0], out_channels, bias=bias)
         self.lin_r = torch.nn.Linear(in_channels[1], out_channels, bias=False) if root_weight else None
-        self._w_t = self._w_bwd = None
+        self._wgamd_derived = {}       # (``_derived``'s store, here from the start: a forward adds no attribute to the module)
 
     def _weight_bwd(self):
         """``[W_l ; W_r]`` ([2 Nq, F], Nq = N rounded up to 4, zero rows between) — the weight of the layer kernel when it runs
@@ -1448,24 +1459,17 @@ class SAGEConv(torch.nn.Module):
         Nq = (N + 3) // 4 * 4
         if not sage_layer_fused_supported(Nq, F_):
             return None
-        key = (wl._version, wl.data_ptr(), wr._version, wr.data_ptr(), _weights_gen)
-        if _capturing() or self._w_bwd is None or self._w_bwd[0] != key:
+
+        def build():
             w = torch.zeros((2 * Nq, F_), dtype=torch.float32, device=wl.device)
-            w[:N], w[Nq:Nq + N] = wl.detach(), wr.detach()
-            if _capturing():
-                return w
-            self._w_bwd = (key, w)
-        return self._w_bwd[1]
+            w[:N], w[Nq:Nq + N] = wl, wr
+            return w
+        return _derived(self, "w_bwd", (wl, wr), build)
 
     def _weight_t(self):
-        """``cat([W_l, W_r], 1).t()`` ([2F, N]) for the one-kernel layer, rebuilt when a weight changed."""
+        """``cat([W_l, W_r], 1).t()`` ([2F, N]) for the one-kernel layer, rebuilt when a weight changed (``_derived``)."""
         wl, wr = self.lin_l.weight, self.lin_r.weight
-        key = (wl._version, wl.data_ptr(), wr._version, wr.data_ptr(), _weights_gen)
-        if _capturing():
-            return torch.cat([wl.detach(), wr.detach()], dim=1).t().contiguous()
-        if self._w_t is None or self._w_t[0] != key:
-            self._w_t = (key, torch.cat([wl.detach(), wr.detach()], dim=1).t().contiguous())
-        return self._w_t[1]
+        return _derived(self, "w_t", (wl, wr), lambda: torch.cat([wl, wr], dim=1).t().contiguous())
 
     def _forward_layer(self, x, graph: LayerGraph, act=None):
         lazy = isinstance(x, LazyRows)
@@ -2539,7 +2543,7 @@ class TransformerConv(torch.nn.Module):
         self.lin_value = torch.nn.Linear(self.in_src, HC)
         self.lin_edge = torch.nn.Linear(edge_dim, HC, bias=False) if edge_dim is not None else None
         self.lin_skip = torch.nn.Linear(self.in_dst, HC if concat else out_channels, bias=bias)
-        self._folded = None
+        self._wgamd_derived = {}       # (``_derived``'s store, here from the start: a forward adds no attribute to the module)
 
     def reset_parameters(self):
         for lin in (self.lin_key, self.lin_query, self.lin_value, self.lin_edge, self.lin_skip):
@@ -2552,16 +2556,11 @@ class TransformerConv(torch.nn.Module):
 
     def _folds(self):
         """``transformer_folds`` in float32: under autograd when a parameter needs a gradient, else cached against the
-        parameters' versions (as ``HeteroConv._rel``)."""
-        params = [p for p in self.parameters()]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
-            return [None if t is None else t.float() for t in transformer_folds(self)]
-        key = tuple((p._version, p.data_ptr(), p.device) for p in params) + (_weights_gen,)
-        if self._folded is None or self._folded[0] != key:
-            with torch.no_grad():
-                f = [None if t is None else t.float().contiguous() for t in transformer_folds(self)]
-            self._folded = (key, f)
-        return self._folded[1]
+        parameters (``_derived``), contiguous."""
+        params = list(self.parameters())
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        return _derived(self, "folds", params, grad=grad, build=lambda: [
+            None if t is None else (t.float() if grad else t.float().contiguous()) for t in transformer_folds(self)])
 
     def _check_edge_attr(self, edge_attr, n_edges: int, device):
         """The edge attribute as the kernels read it (float32 [E, D] contiguous), or None without edge_dim; ValueError on a
@@ -3664,7 +3663,7 @@ class HeteroConv(torch.nn.Module):
         assert aggr in ("sum", "add"), "aggr: sum"
         self.edge_types = sorted(convs)
         self.convs = torch.nn.ModuleDict({"__".join(et): convs[et] for et in self.edge_types})
-        self._folded = {}
+        self._wgamd_derived = {}       # (``_derived``'s store, here from the start: a forward adds no attribute to the module)
         self.stage_tag = ""        # suffix of this layer's stage names under set_stage_hook ("1": gat1:..., transform1, ...)
         # the one-kernel relation keeps 10 neighbours of a row in registers and continues longer rows one neighbour at a time:
         # hops with a larger fan-out take the two-kernel path (the fan-out-25 hop of the mag workload through the one-kernel
@@ -3683,18 +3682,7 @@ class HeteroConv(torch.nn.Module):
     def conv(self, edge_type):
         return self.convs["__".join(edge_type)]
 
-    # ---- parameters in the form the kernels read -----------------------------------------------------------------------
-    def _cached(self, name, params, build):
-        """``build()`` (run without autograd), kept under ``name`` for as long as ``params`` — every parameter it is built from —
-        are what they were: same storage, same version, and no ``bump_weight_generation`` since."""
-        key = tuple((p._version, p.data_ptr()) for p in params) + (_weights_gen,)
-        hit = self._folded.get(name)
-        if hit is None or hit[0] != key:
-            with torch.no_grad():
-                hit = (key, build())
-            self._folded[name] = hit
-        return hit[1]
-
+    # ---- parameters in the form the kernels read (``_derived``, kept on the module) --------------------------------------
     def _rel(self, et):
         """(w [in, H C] contiguous, fold(w, att_src) [in, H], fold(w, att_dst) [in, H]) of a relation, rebuilt when a parameter
         changed: ``alpha_src = ((x W).view(H, C) * att).sum(-1) = x (W . att)``."""
@@ -3705,7 +3693,7 @@ class HeteroConv(torch.nn.Module):
             w3 = w.view(w.shape[0], c.heads, c.out_channels)
             return (w, (w3 * c.att_src.view(1, c.heads, c.out_channels)).sum(-1).contiguous(),
                     (w3 * c.att_dst.view(1, c.heads, c.out_channels)).sum(-1).contiguous())
-        return self._cached(et, (c.lin.weight, c.att_src, c.att_dst), build)
+        return _derived(self, ("rel", et), (c.lin.weight, c.att_src, c.att_dst), build)
 
     def _term_keys(self, t):
         keys = []
@@ -3724,7 +3712,7 @@ class HeteroConv(torch.nn.Module):
         def build():
             mats = [self._rel(et)[1 if end == "src" else 2] for end, et in ends]
             return torch.cat(mats, 1).contiguous() if mats else None
-        return self._cached(("terms", t), [p for c in convs for p in (c.lin.weight, c.att_src, c.att_dst)], build)
+        return _derived(self, ("terms", t), [p for c in convs for p in (c.lin.weight, c.att_src, c.att_dst)], build)
 
     def _bias(self, dt):
         """Sum of the biases of the relations ending in ``dt`` (HeteroConv adds the relations' outputs, bias included)."""
@@ -3732,7 +3720,7 @@ class HeteroConv(torch.nn.Module):
         if rels and all(isinstance(self.conv(et), SAGEConv) for et in rels):
             return self._sage_weights(dt)[1]
         bs = [self.conv(et).bias for et in rels if self.conv(et).bias is not None]
-        return self._cached(("bias", dt), bs, lambda: _sum_of([b.detach() for b in bs]))
+        return _derived(self, ("bias", dt), bs, lambda: _sum_of(bs))
 
     # ---- call-group layer ----------------------------------------------------------------------------------------------
     def _attention_terms(self, xs, graph):
@@ -3921,18 +3909,14 @@ class HeteroConv(torch.nn.Module):
         """``(Wstack [N, K], bias sum [N] | None)`` of destination type ``dt``: ``[W_l^r1 | W_l^r2 | ... | sum_r W_r^r]`` over the
         relations ending in it (sorted edge types; the root block is absent when no relation has a root weight).  ``grad``:
         built by torch ops on the parameters (autograd hands each relation its slice and every ``lin_r`` the shared root
-        gradient); otherwise detached and cached against the parameters' versions."""
+        gradient); otherwise detached and kept (``_derived``)."""
         convs = [self.conv(et) for et in self.edge_types if et[2] == dt]
 
         def build():
             root = _sum_of([c.lin_r.weight for c in convs if c.lin_r is not None])
             wstack = torch.cat([c.lin_l.weight for c in convs] + ([] if root is None else [root]), 1)
             return wstack, _sum_of([c.lin_l.bias for c in convs if c.lin_l.bias is not None])
-        if grad:
-            with torch.enable_grad():
-                return build()
-        return self._cached(("sage", dt), [p for c in convs for p in c.parameters()],
-                            lambda: tuple(None if t is None else t.detach() for t in build()))
+        return _derived(self, ("sage", dt), [p for c in convs for p in c.parameters()], build, grad=grad)
 
     def _forward_layer_sage(self, xs, graph: HeteroLayerGraph, act=None):
         """``HeteroConv({edge_type: SAGEConv})`` over a call group's layer graph: per (hop, destination type) the sum over the
@@ -4004,17 +3988,13 @@ class HeteroConv(torch.nn.Module):
     def _tconv_weights(self, ets, grad: bool = False):
         """``hetero_transformer_stack`` of the relations ``ets`` (those ending in one node type whose source type has input
         rows) in float32.  ``grad``: built by torch ops on the parameters (autograd hands each relation its slice and every
-        ``lin_skip`` the shared skip gradient); otherwise detached and cached against the parameters' versions."""
+        ``lin_skip`` the shared skip gradient); otherwise detached and kept (``_derived``)."""
         convs = [self.conv(et) for et in ets]
 
         def build():
             wt, bias, fold, fold_b, layout = hetero_transformer_stack(convs)
             return (wt.float().contiguous(), None if bias is None else bias.float(), fold.float().contiguous(), fold_b.float(), layout)
-        if grad:
-            with torch.enable_grad():
-                return build()
-        return self._cached(("tconv", tuple(ets)), [p for c in convs for p in c.parameters()],
-                            lambda: tuple(t.detach() if torch.is_tensor(t) else t for t in build()))
+        return _derived(self, ("tconv", tuple(ets)), [p for c in convs for p in c.parameters()], build, grad=grad)
 
     def _tconv_edge_attrs(self, ets, graph: HeteroLayerGraph, edge_attr_dict, device):
         """{edge type: the edge type's hop-major edge attributes as the kernels read them (float32 [E, D] contiguous)} for the
@@ -4147,78 +4127,75 @@ class HeteroConv(torch.nn.Module):
         """The same layer out of library ops in PyG's formulation (``_tconv_library_ops`` per relation hop, summed, activation
         applied, placed through ``out_rows``), with ordinary autograd — what shapes outside the kernel's domain and CPU tensors
         take; correctness only."""
+        group = [None, None]       # the destination rows of the group being summed (``head``), made once per group
+
+        def relation(et, r, head):
+            if et[0] not in x:
+                return None
+            if group[0] is not head:
+                group[:] = head, x[et[2]][head.dst_rows].float()
+            c, xd = self.conv(et), group[1]
+            if r is not None and r.n_edges > 0:
+                ea = eas[et][r.edge_base:r.edge_base + r.n_edges] if c.edge_dim is not None else None
+                one = LayerGraph([HopGraph(r.row_ptr, r.col[:r.n_edges], None)])
+                return _tconv_library_ops(c, x[et[0]].float(), xd, one, ea, False)[0]
+            return c.lin_skip(xd) if c.root_weight else None
+        return self._library_groups(x, graph, relu, relation)
+
+    def _library_groups(self, x, graph: HeteroLayerGraph, relu: bool, relation):
+        """The frame of the two library routes: per (hop, destination type) the sum of ``relation(et, r, head)`` over the edge
+        types ending in the type — the relation's rows or None; ``r`` = the hop's ``RelationHop`` of ``et`` or None, ``head`` = the
+        group's first one (its ``n_rows``, ``dst_rows`` and ``out_rows`` are the group's) — zeros when none contributed, the
+        activation applied, placed through ``out_rows`` in an output of the rows' dtype (not ``_group_outputs``)."""
         dev = next(iter(x.values())).device
         out = {}
-        for (hop, dt), mine in _relation_groups(graph):
-            n_f = mine[0].n_rows
-            if n_f == 0:
+        for (_, dt), mine in _relation_groups(graph):
+            head = mine[0]
+            if head.n_rows == 0:
                 continue
             listed = {r.edge_type: r for r in mine}
-            xd = x[dt][mine[0].dst_rows].float()
             y = None
             for et in self.edge_types:
-                if et[2] != dt or et[0] not in x:
-                    continue
-                c, r = self.conv(et), listed.get(et)
-                if r is not None and r.n_edges > 0:
-                    ea = eas[et][r.edge_base:r.edge_base + r.n_edges] if c.edge_dim is not None else None
-                    one = LayerGraph([HopGraph(r.row_ptr, r.col[:r.n_edges], None)])
-                    o, _ = _tconv_library_ops(c, x[et[0]].float(), xd, one, ea, False)
-                elif c.root_weight:
-                    o = c.lin_skip(xd)
-                else:
-                    continue
-                y = o if y is None else y + o
+                o = relation(et, listed.get(et), head) if et[2] == dt else None
+                if o is not None:
+                    y = o if y is None else y + o
             if y is None:
-                y = torch.zeros((n_f, self._width(dt)), dtype=torch.float32, device=dev)
+                y = torch.zeros((head.n_rows, self._width(dt)), dtype=torch.float32, device=dev)
             if relu:
                 y = torch.relu(y)
-            if mine[0].out_rows is not None and dt not in out:
+            if head.out_rows is not None and dt not in out:
                 out[dt] = torch.zeros((graph.n_out[dt], y.shape[1]), dtype=y.dtype, device=dev)
-            _place_rows(out, dt, y, mine[0].out_rows)
+            _place_rows(out, dt, y, head.out_rows)
         return out
 
     def _forward_sage_library(self, x, graph: HeteroLayerGraph, relu: bool):
         """The same layer out of library ops in PyG's formulation, relation by relation, with ordinary autograd — what shapes
         outside the kernel's domain (F % 4 != 0, N > 256, other dtypes, CPU tensors, other aggregators) take; correctness only."""
         dev = next(iter(x.values())).device
-        out = {}
-        for (hop, dt), mine in _relation_groups(graph):
-            n_f = mine[0].n_rows
-            if n_f == 0:
-                continue
-            listed = {r.edge_type: r for r in mine}
-            y = None
-            for et in self.edge_types:
-                if et[2] != dt:
-                    continue
-                c, r, xs = self.conv(et), listed.get(et), x[et[0]]
-                agg = torch.zeros((n_f, xs.shape[1]), dtype=xs.dtype, device=dev)
-                if r is not None and r.n_edges > 0:
-                    if xs.is_cuda and xs.dtype == torch.float32 and c.aggr in ("mean", "sum", "add"):
-                        agg = spmm_csr(xs, r.row_ptr, r.col, "mean" if c.aggr == "mean" else "sum")
+
+        def relation(et, r, head):
+            c, xs, n_f = self.conv(et), x[et[0]], head.n_rows
+            agg = torch.zeros((n_f, xs.shape[1]), dtype=xs.dtype, device=dev)
+            if r is not None and r.n_edges > 0:
+                if xs.is_cuda and xs.dtype == torch.float32 and c.aggr in ("mean", "sum", "add"):
+                    agg = spmm_csr(xs, r.row_ptr, r.col, "mean" if c.aggr == "mean" else "sum")
+                else:
+                    deg = (r.row_ptr[1:] - r.row_ptr[:-1]).long()
+                    row = torch.repeat_interleave(torch.arange(n_f, device=dev), deg)
+                    rows = xs[r.col.long()[:r.n_edges]]
+                    if c.aggr in ("mean", "sum", "add"):
+                        agg = agg.index_add(0, row, rows)
+                        if c.aggr == "mean":
+                            agg = agg / deg.clamp(min=1).unsqueeze(1).to(agg.dtype)
+                    elif c.aggr in ("max", "min"):
+                        agg = agg.scatter_reduce(0, row.unsqueeze(1).expand_as(rows), rows, "a" + c.aggr, include_self=False)
                     else:
-                        deg = (r.row_ptr[1:] - r.row_ptr[:-1]).long()
-                        row = torch.repeat_interleave(torch.arange(n_f, device=dev), deg)
-                        rows = xs[r.col.long()[:r.n_edges]]
-                        if c.aggr in ("mean", "sum", "add"):
-                            agg = agg.index_add(0, row, rows)
-                            if c.aggr == "mean":
-                                agg = agg / deg.clamp(min=1).unsqueeze(1).to(agg.dtype)
-                        elif c.aggr in ("max", "min"):
-                            agg = agg.scatter_reduce(0, row.unsqueeze(1).expand_as(rows), rows, "a" + c.aggr, include_self=False)
-                        else:
-                            raise NotImplementedError("HeteroConv: SAGEConv aggr %r (mean, sum, max, min)" % (c.aggr,))
-                o = c.lin_l(agg)
-                if c.lin_r is not None:
-                    o = o + c.lin_r(x[dt][mine[0].dst_rows])
-                y = o if y is None else y + o
-            if relu:
-                y = torch.relu(y)
-            if mine[0].out_rows is not None and dt not in out:      # (whatever dtype the rows have: not ``_group_outputs``)
-                out[dt] = torch.zeros((graph.n_out[dt], y.shape[1]), dtype=y.dtype, device=dev)
-            _place_rows(out, dt, y, mine[0].out_rows)
-        return out
+                        raise NotImplementedError("HeteroConv: SAGEConv aggr %r (mean, sum, max, min)" % (c.aggr,))
+            o = c.lin_l(agg)
+            if c.lin_r is not None:
+                o = o + c.lin_r(x[et[2]][head.dst_rows])
+            return o
+        return self._library_groups(x, graph, relu, relation)
 
     def _forward_layer_train(self, xs, graph: HeteroLayerGraph, act=None):
         """The call-group layer under autograd, AGGREGATE-FIRST like the inference route: per relation the attention-weighted
