@@ -481,9 +481,57 @@ class HeteroCallGroup:
         return lg
 
 
-class CallGroupIterator:
-    """Software-pipelined: the walk of call group g + 1 is enqueued (on its own HIP stream) before group g is handed out, so
-    the device never waits for the host's read-back of group g's sizes."""
+def _enqueue_walk_sizes(res):
+    """Every size of a homogeneous walk result the host needs (``CallGroup._wait``), on its way to pinned memory:
+    (pinned int32 tensor, the event that says it has arrived).  Enqueues only."""
+    G_, H = res.n_batches, res.hops
+    pieces = [res.node_seg[G_:G_ + 1]] + [res.frontier_seg[k][G_:G_ + 1] for k in range(H + 1)]
+    pieces += [res.offsets[k][res.frontier_seg[k][G_:G_ + 1].long()] for k in range(H)]
+    sizes_d = torch.cat([p.to(torch.int32).reshape(-1) for p in pieces])
+    sizes_h = torch.empty(sizes_d.shape, dtype=torch.int32, pin_memory=True)
+    sizes_h.copy_(sizes_d, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record()
+    return sizes_h, ev
+
+
+class _PipelinedGroups:
+    """An epoch as a plan of call groups, software-pipelined: ``_launch(i)`` enqueues group i (``_on_walk_stream``: on the
+    iterator's own HIP stream when ``overlap``) and returns it, or None past the plan; group g + 1 is enqueued before group g is
+    handed out, so the device never waits for the host's read-back of group g's sizes."""
+
+    def _pipeline(self, plan, device, overlap: bool):
+        self._plan = plan
+        self._stream = torch.cuda.Stream(device=device) if overlap else None
+        self._at, self._pending = 0, None
+
+    def _on_walk_stream(self, enqueue):
+        if self._stream is None:
+            return enqueue()
+        self._stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self._stream):
+            return enqueue()
+
+    def __len__(self):
+        return len(self._plan)
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._at == 0 and self._pending is None:
+            self._pending = self._launch(0)
+        cur = self._pending
+        if cur is None:
+            raise StopIteration
+        self._at += 1
+        self._pending = self._launch(self._at)     # group g + 1 is on the device before the host blocks on group g
+        cur._wait()
+        return cur
+
+
+class CallGroupIterator(_PipelinedGroups):
+    """The call groups of a ``NeighborLoader`` epoch (node seeds)."""
 
     def __init__(self, data, core_sampler, input_data, random_state: int, batch_size: int, overlap: bool = True):
         from ..sampler.sampler import HeteroNeighborSampler
@@ -500,17 +548,10 @@ class CallGroupIterator:
         G = max(1, core_sampler.seeds_per_call(B) // B)
         n_full = n // B
         # (first batch, batches, seeds of the ragged last one or None)
-        self._plan = [(b, min(G, n_full - b), None) for b in range(0, n_full, G)]
+        plan = [(b, min(G, n_full - b), None) for b in range(0, n_full, G)]
         if n % B:
-            self._plan.append((n_full, 1, n - n_full * B))
-        self._stream = torch.cuda.Stream(device=self._seeds.device) if overlap else None
-        self._at, self._pending = 0, None
-
-    def __len__(self):
-        return len(self._plan)
-
-    def __iter__(self):
-        return self
+            plan.append((n_full, 1, n - n_full * B))
+        self._pipeline(plan, self._seeds.device, overlap)
 
     def _launch_hetero(self, i) -> Optional[HeteroCallGroup]:
         from ..sampler.sampler import _as_i64, hop_seed
@@ -553,12 +594,7 @@ class CallGroupIterator:
             ev.record()
             return rec, sizes_h, ev, n_seeds, cseg
 
-        if self._stream is None:
-            rec, sizes_h, ev, n_seeds, cseg = enqueue()
-        else:
-            self._stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self._stream):
-                rec, sizes_h, ev, n_seeds, cseg = enqueue()
+        rec, sizes_h, ev, n_seeds, cseg = self._on_walk_stream(enqueue)
         return HeteroCallGroup(rec, walk, self._fs, self._seed_type, b0, self._input_id[b0 * B:b0 * B + n_seeds], sizes_h, ev,
                                self._stream, cseg)
 
@@ -584,31 +620,7 @@ class CallGroupIterator:
                 seg = torch.tensor([0, ragged], dtype=torch.int32, device=dev)
                 res = walk.run(ids, rs, seg, torch.zeros(B, dtype=torch.int32, device=dev))
                 n_seeds = ragged
-            G_ = res.n_batches
-            pieces = [res.node_seg[G_:G_ + 1]] + [res.frontier_seg[k][G_:G_ + 1] for k in range(H + 1)]
-            pieces += [res.offsets[k][res.frontier_seg[k][G_:G_ + 1].long()] for k in range(H)]
-            sizes_d = torch.cat([p.to(torch.int32).reshape(-1) for p in pieces])
-            sizes_h = torch.empty(sizes_d.shape, dtype=torch.int32, pin_memory=True)
-            sizes_h.copy_(sizes_d, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            return res, sizes_h, ev, n_seeds
+            return (res,) + _enqueue_walk_sizes(res) + (n_seeds,)
 
-        if self._stream is None:
-            res, sizes_h, ev, n_seeds = enqueue()
-        else:
-            self._stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(self._stream):
-                res, sizes_h, ev, n_seeds = enqueue()
+        res, sizes_h, ev, n_seeds = self._on_walk_stream(enqueue)
         return CallGroup(res, self._fs, smp.graph, b0, self._input_id[b0 * B:b0 * B + n_seeds], sizes_h, ev, self._stream)
-
-    def __next__(self):
-        if self._at == 0 and self._pending is None:
-            self._pending = self._launch(0)
-        cur = self._pending
-        if cur is None:
-            raise StopIteration
-        self._at += 1
-        self._pending = self._launch(self._at)     # group g + 1 is on the device before the host blocks on group g
-        cur._wait()
-        return cur

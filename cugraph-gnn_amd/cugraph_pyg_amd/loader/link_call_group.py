@@ -1,0 +1,130 @@
+"""Call-group iteration of a ``LinkNeighborLoader`` epoch: G mini-batches of seed EDGES at a time as one block-diagonal graph.
+
+``LinkNeighborLoader`` samples in call groups already — negatives per batch, the endpoints of all batches de-duplicated row-wise
+(``_batched_first_unique``), ONE walk over the ragged per-batch seed lists — and then cuts the result into one ``Data`` per
+mini-batch.  ``loader.call_groups()`` hands the group out whole instead: a ``LinkCallGroup`` is a ``CallGroup`` (``x``,
+``layer_graph(j)``, ``batch_ptr``, ... unchanged) over that walk.  The seed rows of the last layer's output are each batch's unique
+endpoints in first-appearance order, so the group's ``edge_label_index`` is the batch-local one shifted by ``batch_ptr[b]`` and
+costs nothing to produce; ``wholegraph_amd.nn.link_bce_with_logits(h, h, grp.edge_label_index, grp.edge_label)`` is then the loss
+of all G mini-batches in one launch.  Every mini-batch inside is bit for bit what ``for batch in loader`` yields
+(``to_data_list()``; tests/test_gpu_link_call_groups.py).
+"""
+from typing import Optional
+
+import torch
+
+from .call_group import CallGroup, _PipelinedGroups, _enqueue_walk_sizes
+
+
+def link_group_index(local: torch.Tensor, batch_ptr: torch.Tensor, n_pos: int, n_neg: int):
+    """``(edge_label_index [2, G (n_pos + n_neg)], label_ptr [G + 1])`` of a link call group.  ``local`` [G, 2 (n_pos + n_neg)]:
+    per mini-batch the positions of its seed edges' endpoints — sources (positives, then negatives), then destinations — in
+    the batch's unique endpoint list; ``batch_ptr`` [G + 1]: the first row of every batch's list in the group numbering.  Pairs
+    are batch-major, positives first inside a batch, as the per-batch loader emits them."""
+    G, half = local.shape[0], n_pos + n_neg
+    assert local.shape[1] == 2 * half and batch_ptr.shape[0] == G + 1
+    shifted = local.to(torch.int64) + batch_ptr[:-1].to(torch.int64).view(G, 1)
+    index = torch.stack([shifted[:, :half].reshape(-1), shifted[:, half:].reshape(-1)])
+    label_ptr = torch.arange(G + 1, dtype=torch.int64, device=local.device) * half
+    return index, label_ptr
+
+
+class LinkCallGroup(CallGroup):
+    """G consecutive mini-batches of a ``LinkNeighborLoader`` epoch.  A ``CallGroup`` whose seeds are the mini-batches' unique
+    seed-edge endpoints; on top of it:
+
+    ``edge_label_index`` int64 [2, P]: the pairs of all mini-batches, batch-major, positives first inside a batch, as rows of
+    the last layer's output (the ``batch_ptr`` numbering) — ``batch[edge_label_index]`` are the global endpoint ids;
+    ``edge_label`` [P] (None where the per-batch loader gives none): the per-batch labels back to back;
+    ``label_ptr`` int64 [G + 1]: the pairs of mini-batch b; ``input_id``: the seed-edge ids, ``n_pos`` per mini-batch."""
+
+    def __init__(self, walk_result, feature_store, graph, first_batch, input_id, sizes_h, event, walk_stream, local, n_pos, n_neg,
+                 edge_label_index, label_ptr, edge_label, mode):
+        super().__init__(walk_result, feature_store, graph, first_batch, input_id, sizes_h, event, walk_stream)
+        self._local, self.n_pos, self.n_neg, self._mode = local, n_pos, n_neg, mode
+        self.edge_label_index, self.label_ptr, self.edge_label = edge_label_index, label_ptr, edge_label
+
+    def _wait(self):
+        if self._ready:
+            return
+        super()._wait()
+        if self._walk_stream is not None:     # the negatives and the de-duplication ran on the walk stream too
+            main = torch.cuda.current_stream()
+            for t in (self._local, self.edge_label_index, self.label_ptr, self.edge_label, self.input_id):
+                if t is not None:
+                    t.record_stream(main)
+
+    def to_data_list(self):
+        """The G mini-batches as the ``Data`` objects ``for batch in loader`` yields (same tensors, bit for bit)."""
+        from ..sampler.sampler import filter_store_from_group, group_attribute_views
+        self._wait()
+        outs = self._res.finalize_batches(self._graph.edge_id)
+        views = group_attribute_views(self._fs, self._res.group_context)
+        n_pos, n_neg = self.n_pos, self.n_neg
+        half = n_pos + n_neg
+        datas = []
+        for j, (node, row, col, edge, nn, ne) in enumerate(outs):
+            d = filter_store_from_group(self._fs, views, j, node, row, col, edge)
+            d.n_id, d.e_id = node, edge
+            d.num_sampled_nodes, d.num_sampled_edges = torch.tensor(nn), torch.tensor(ne)
+            d.input_id = self.input_id[j * n_pos:(j + 1) * n_pos]
+            d.batch_size = n_pos
+            inverse = self._local[j]
+            d.edge_label_index = torch.stack([inverse[:half], inverse[half:]])
+            if self.edge_label is not None:
+                d.edge_label = self.edge_label[j * half:(j + 1) * half]
+            if self._mode == "triplet":
+                d.src_index, d.dst_pos_index = inverse[:n_pos], inverse[half:half + n_pos]
+                neg = inverse[half + n_pos:]
+                d.dst_neg_index = neg.view(-1, n_pos).t() if n_neg % n_pos == 0 and n_neg > n_pos else neg
+            datas.append(d)
+        return datas
+
+
+class LinkCallGroupIterator(_PipelinedGroups):
+    """The call groups of a ``LinkNeighborLoader`` epoch.  ``batch_edges(b)`` is the loader's own per-batch recipe — the seed-edge
+    ids of mini-batch b, its endpoints with the negatives drawn by the batch's generator, its labels — so the epoch is the one
+    ``iter(loader)`` walks; with ``overlap`` the negatives, the de-duplication and the walk of group g + 1 are enqueued on the
+    iterator's own stream before group g is handed out."""
+
+    def __init__(self, data, sampler, batch_edges, n_edges: int, batch_size: int, batches_per_group: int, num_nodes: int,
+                 random_state: int, mode: Optional[str], device, overlap: bool = True):
+        self._fs, self._gs = data
+        self._smp, self._batch_edges, self._B, self._rs = sampler, batch_edges, int(batch_size), int(random_state)
+        self._num_nodes, self._mode = int(num_nodes), mode
+        n_full, G = n_edges // self._B, max(1, int(batches_per_group))
+        # (first batch, batches): the full batches in groups of G, then the ragged last batch as a one-batch group over its own list
+        plan = [(b, min(G, n_full - b)) for b in range(0, n_full, G)]
+        if n_edges % self._B:
+            plan.append((n_full, 1))
+        self._pipeline(plan, device, overlap)
+
+    def _launch(self, i):
+        from ..sampler.sampler import hop_seed
+        from .link_loader import _batched_first_unique
+        if i >= len(self._plan):
+            return None
+        b0, g = self._plan[i]
+        smp = self._smp
+        rs = [[hop_seed(self._rs + b0 + j, k) for j in range(g)] for k in range(len(smp.fanout))]
+
+        def enqueue():
+            ids, ends, labels, n_pos, n_neg = [], [], [], 0, 0
+            for j in range(g):
+                input_id, src_all, dst_all, n_neg, label = self._batch_edges(b0 + j, self._rs + b0 + j)
+                n_pos = input_id.numel()
+                ids.append(input_id)
+                ends.append(torch.cat([src_all, dst_all]))
+                labels.append(label)
+            ends = torch.stack(ends)                  # [g, 2 (n_pos + n_neg)]: the batches of a group are equally long
+            S = ends.shape[1]
+            uniq, seg, batch, local = _batched_first_unique(ends, self._num_nodes)
+            walk = smp._call_group_walk(S, g)
+            res = walk.run(uniq.to(smp.graph.col.dtype).contiguous(), rs, seg, batch)
+            edge_label = None if labels[0] is None else torch.cat(labels)
+            index, label_ptr = link_group_index(local, seg, n_pos, n_neg)
+            return (res,) + _enqueue_walk_sizes(res) + (torch.cat(ids), local, n_pos, n_neg, index, label_ptr, edge_label)
+
+        res, sizes_h, ev, input_id, local, n_pos, n_neg, index, label_ptr, edge_label = self._on_walk_stream(enqueue)
+        return LinkCallGroup(res, self._fs, smp.graph, b0, input_id, sizes_h, ev, self._stream, local, n_pos, n_neg, index, label_ptr,
+                             edge_label, self._mode)

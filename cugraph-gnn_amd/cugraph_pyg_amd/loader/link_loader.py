@@ -220,16 +220,20 @@ class LinkLoader:
         t_all = None if t_pos is None else torch.cat([t_pos, t_neg])
         return torch.cat([src, neg_src]), torch.cat([dst, neg_dst]), n_neg, t_all
 
-    def __emit(self, node, row, col, edge, nn, ne, ix, inverse, n_pos, n_neg, views=None, j=0, group=None):
-        """One homogeneous mini-batch as ``Data`` (features joined) or, in sampler mode, as ``SamplerOutput``."""
+    def __edge_label(self, ix, n_pos, n_neg):
+        """The labels of one mini-batch, positives first: 1 / 0 (given labels + 1 / 0) under negative sampling, else the given
+        labels or None."""
         dev = self.__eli.device
-        half = n_pos + n_neg
-        edge_label_index = torch.stack([inverse[:half], inverse[half:]])
         if self.__mode is not None:
             pos = torch.ones(n_pos, device=dev) if self.__label is None else (self.__label[ix] + 1)
-            edge_label = torch.cat([pos, torch.zeros(n_neg, device=dev, dtype=pos.dtype)])
-        else:
-            edge_label = None if self.__label is None else self.__label[ix]
+            return torch.cat([pos, torch.zeros(n_neg, device=dev, dtype=pos.dtype)])
+        return None if self.__label is None else self.__label[ix]
+
+    def __emit(self, node, row, col, edge, nn, ne, ix, inverse, n_pos, n_neg, views=None, j=0, group=None):
+        """One homogeneous mini-batch as ``Data`` (features joined) or, in sampler mode, as ``SamplerOutput``."""
+        half = n_pos + n_neg
+        edge_label_index = torch.stack([inverse[:half], inverse[half:]])
+        edge_label = self.__edge_label(ix, n_pos, n_neg)
         if self.__raw:
             out = SamplerOutput(node=node, row=row, col=col, edge=edge, batch=node[:nn[0]],
                                 num_sampled_nodes=torch.tensor(nn), num_sampled_edges=torch.tensor(ne),
@@ -257,13 +261,58 @@ class LinkLoader:
         n = self.__eli.shape[1]
         return n // self.__batch_size if self.__drop_last else (n + self.__batch_size - 1) // self.__batch_size
 
-    def __batches(self):
+    def __epoch(self):
+        """(the epoch's order of the seed edges, its random state)."""
         n = self.__eli.shape[1]
         dev = self.__eli.device
         perm = torch.randperm(n, device=dev) if self.__shuffle else torch.arange(n, device=dev)
         if self.__drop_last and n % self.__batch_size:
             perm = perm[: n - n % self.__batch_size]
         seed = self.__random_state if self.__random_state is not None else generate_seed()
+        return perm, seed
+
+    def call_groups(self, overlap: bool = True):
+        """The same epoch as ``iter(self)`` — same order, same negatives, same endpoint de-duplication, same samples — handed
+        out in CALL GROUPS: ``LinkCallGroup`` objects (``loader/link_call_group.py``), each the block-diagonal union of its
+        mini-batches with a lazy ``x``, per-layer trimmed graphs and ONE ``edge_label_index`` / ``edge_label`` over the seed
+        rows of the last layer's output — what ``wholegraph_amd.nn.link_bce_with_logits`` takes.  Homogeneous graphs, uniform
+        or positively-weighted sampling with positive fan-outs."""
+        from .link_call_group import LinkCallGroupIterator
+        smp = self.__sampler
+        reason = None
+        if self.__hetero:
+            reason = "heterogeneous graphs are not supported (link call groups are homogeneous)"
+        elif self.__raw:
+            reason = "sampler-output mode (as_sampler_output=True) hands out SamplerOutput objects, not call groups"
+        elif self.__time is not None or smp.temporal:
+            reason = "temporal seeds (edge_label_time / time_attr) are not supported"
+        elif smp.disjoint:
+            reason = "disjoint sampling is not supported"
+        elif getattr(smp, "with_replacement", False):
+            reason = "sampling with replacement is not supported"
+        elif not all(f > 0 for f in smp.fanout):
+            reason = "fan-out -1 (all neighbours) is not supported: the call-group walk needs positive fan-outs"
+        elif not smp.call_groups_ok():
+            reason = "this sampler configuration does not run on the call-group walk (biased sampling needs strictly positive weights and fan-outs <= 256)"
+        elif not self.__eli.is_cuda:
+            reason = "the call-group walk only exists on the GPU"
+        if reason is not None:
+            raise NotImplementedError("LinkNeighborLoader.call_groups(): " + reason)
+        perm, seed = self.__epoch()
+        dev, bs = self.__eli.device, self.__batch_size
+
+        def batch_edges(b, batch_seed):
+            ix = perm[b * bs:(b + 1) * bs]
+            gen = torch.Generator(device=dev).manual_seed(batch_seed & 0x7FFFFFFFFFFFFFFF)
+            src_all, dst_all, n_neg, _ = self.__with_negatives(self.__eli[0, ix], self.__eli[1, ix], ix, gen)
+            return self.__input_id[ix], src_all, dst_all, n_neg, self.__edge_label(ix, ix.numel(), n_neg)
+
+        return LinkCallGroupIterator(self.__data, smp, batch_edges, perm.numel(), bs, self.__batches_per_group(bs), self.__num_nodes,
+                                     seed, self.__mode, dev, overlap=overlap)
+
+    def __batches(self):
+        dev = self.__eli.device
+        perm, seed = self.__epoch()
         fs, gs = self.__data
         if self.__hetero:
             yield from self.__hetero_batches(perm, seed)

@@ -298,6 +298,17 @@ SYMBOLS = {
                                                c_void_p, c_void_p]),
     "wgamd_softmax_xent_backward_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, c_int64, c_void_p]),
+    # link-prediction head (wg_link.hip)
+    "wgamd_pair_bce_state_bytes": (c_size_t, [c_int64]),
+    "wgamd_pair_dot_forward_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                                           c_int64, c_void_p, c_void_p]),
+    "wgamd_pair_bce_forward_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                                           c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                           c_void_p]),
+    "wgamd_pair_grad_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "wgamd_pair_grad_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                    c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_int,
+                                    c_void_p]),
     # GCN layer (wg_gcn.hip)
     "wgamd_gcn_layer_supported": (c_int, [c_int, c_int]),
     "wgamd_gcn_layer_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,

@@ -572,6 +572,141 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor, row_weight: Option
     return _SoftmaxXent.apply(logits, target, row_weight)
 
 
+# ---- link-prediction head (csrc/wg_link.hip) ---------------------------------------------------------------------------------
+_LINK_STATE = {}      # (device index, stream) -> the reusable state of wgamd_pair_bce_forward_f32
+
+
+def _pair_side_grad(index_row, index_other, n_rows: int, x_other, coef, scale_num, scale_den, acc=None):
+    """One side's gradient of the pair head: ``out[r] = scale * sum_{p: index_row[p] = r} coef[p] x_other[index_other[p]]``
+    (``+ acc[r]``, in place) — the side's incidence list from the stable ``wgamd_coo_to_csr_i64`` over the indices clamped into
+    range (a row's pairs stay in pair order), then ONE ``wgamd_pair_grad_f32`` launch: no float atomics, bit-reproducible."""
+    lib, dev = L.lib(), x_other.device
+    P, C = index_row.shape[0], x_other.shape[1]
+    out = acc if acc is not None else torch.empty((n_rows, C), dtype=torch.float32, device=dev)
+    if n_rows == 0:
+        return out
+    rows = index_row.clamp(0, n_rows - 1)
+    other = index_other.clamp(0, max(x_other.shape[0] - 1, 0))
+    i32 = dict(dtype=torch.int32, device=dev)
+    row_ptr, col, pair = torch.empty(n_rows + 1, **i32), torch.empty(P, **i32), torch.empty(P, **i32)
+    need = lib.wgamd_coo_to_csr_workspace_bytes(P, n_rows)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    L.check(lib.wgamd_coo_to_csr_i64(other.data_ptr(), rows.data_ptr(), P, n_rows, row_ptr.data_ptr(), col.data_ptr(), pair.data_ptr(),
+                                     ws.data_ptr(), need, get_stream()), "wgamd_coo_to_csr_i64")
+    need = lib.wgamd_pair_grad_workspace_bytes(P, C)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    L.check(lib.wgamd_pair_grad_f32(row_ptr.data_ptr(), pair.data_ptr(), n_rows, P, index_row.data_ptr(), index_other.data_ptr(),
+                                    coef.data_ptr(), x_other.data_ptr(), x_other.stride(0), x_other.shape[0], C, _ptr(scale_num),
+                                    _ptr(scale_den), _ptr(acc), 0 if acc is None else acc.stride(0), out.data_ptr(), out.stride(0),
+                                    ws.data_ptr(), need, 0, get_stream()), "wgamd_pair_grad_f32")
+    return out
+
+
+def _pair_grads(ctx, x_src, x_dst, index, coef, scale_num, scale_den):
+    """(grad x_src, grad x_dst) of the pair head; one table on both sides: the two sides summed into the first, in a fixed order."""
+    i_src, i_dst = index[0], index[1]
+    if ctx.shared:
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        g = _pair_side_grad(i_dst, i_src, x_dst.shape[0], x_src, coef, scale_num, scale_den)
+        return _pair_side_grad(i_src, i_dst, x_src.shape[0], x_dst, coef, scale_num, scale_den, acc=g), None
+    g_src = _pair_side_grad(i_src, i_dst, x_src.shape[0], x_dst, coef, scale_num, scale_den) if ctx.needs_input_grad[0] else None
+    g_dst = _pair_side_grad(i_dst, i_src, x_dst.shape[0], x_src, coef, scale_num, scale_den) if ctx.needs_input_grad[1] else None
+    return g_src, g_dst
+
+
+def _pair_args(x_src, x_dst, index):
+    return (x_src.data_ptr(), x_src.stride(0), x_src.shape[0], x_dst.data_ptr(), x_dst.stride(0), x_dst.shape[0], x_src.shape[1],
+            index[0].data_ptr(), index[1].data_ptr(), index.shape[1])
+
+
+class _PairDot(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x_src, x_dst, index, shared):
+        score = torch.empty(index.shape[1], dtype=torch.float32, device=x_src.device)
+        L.check(L.lib().wgamd_pair_dot_forward_f32(*_pair_args(x_src, x_dst, index), score.data_ptr(), get_stream()),
+                "wgamd_pair_dot_forward_f32")
+        ctx.save_for_backward(x_src, x_dst, index)
+        ctx.shared = shared
+        return score
+
+    @staticmethod
+    def backward(ctx, grad_score):
+        x_src, x_dst, index = ctx.saved_tensors
+        g = grad_score.to(torch.float32).contiguous()
+        return _pair_grads(ctx, x_src, x_dst, index, g, None, None) + (None, None)
+
+
+class _LinkBce(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x_src, x_dst, index, label, weight, mean, shared):
+        lib, dev = L.lib(), x_src.device
+        P = index.shape[1]
+        key = (dev.index, get_stream().value)
+        state = _LINK_STATE.get(key)
+        if state is None:
+            state = _LINK_STATE[key] = torch.zeros((lib.wgamd_pair_bce_state_bytes(P) + 3) // 4, dtype=torch.float32, device=dev)
+        coef = torch.empty(P + 1, dtype=torch.float32, device=dev)       # [P]: the sum of weights
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        L.check(lib.wgamd_pair_bce_forward_f32(*_pair_args(x_src, x_dst, index), label.data_ptr(), _ptr(weight), int(mean), None,
+                                               coef.data_ptr(), state.data_ptr(), 1, loss.data_ptr(), get_stream()),
+                "wgamd_pair_bce_forward_f32")
+        ctx.save_for_backward(x_src, x_dst, index, coef)
+        ctx.mean, ctx.shared = mean, shared
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        x_src, x_dst, index, coef = ctx.saved_tensors
+        g = grad_loss.to(torch.float32).contiguous()
+        den = coef[index.shape[1]:] if ctx.mean else None
+        return _pair_grads(ctx, x_src, x_dst, index, coef, g, den) + (None, None, None, None, None)
+
+
+def _pair_kernel_ok(x_src, x_dst, index) -> bool:
+    if index.dim() != 2 or index.shape[0] != 2 or x_src.dim() != 2 or x_dst.dim() != 2 or x_src.shape[1] != x_dst.shape[1]:
+        raise ValueError("pair head: index [2, P] over two [rows, C] tables of one width")
+    return (all(t.dtype == torch.float32 and t.is_cuda and t.stride(1) == 1 and t.shape[1] >= 1 for t in (x_src, x_dst))
+            and index.is_cuda and index.dtype == torch.int64 and index.shape[1] > 0)
+
+
+def pair_dot(x_src: torch.Tensor, x_dst: torch.Tensor, index: torch.Tensor) -> torch.Tensor:
+    """``(x_src[index[0]] * x_dst[index[1]]).sum(-1)`` — the inner-product decoder of link prediction (the reference's
+    examples/mag_lp_mnmg.py, GAE's ``InnerProductDecoder``), and the score AUC / MRR are computed from — in ONE launch that
+    never forms the two gathered [P, C] copies, differentiable in both tables with an atomic-free, bit-reproducible backward
+    (one launch per side over its incidence list).  ``x_src is x_dst`` is the homogeneous case.  A pair whose index is outside its
+    table scores NaN and reads nothing.  float32 tables with unit column stride on the device; anything else goes to torch."""
+    if not _pair_kernel_ok(x_src, x_dst, index):
+        return (x_src[index[0]] * x_dst[index[1]]).sum(-1)
+    return _PairDot.apply(x_src, x_dst, index.contiguous(), x_src is x_dst)
+
+
+def link_bce_with_logits(x_src: torch.Tensor, x_dst: torch.Tensor, index: torch.Tensor, label: torch.Tensor,
+                         pair_weight: Optional[torch.Tensor] = None, reduction: str = "mean") -> torch.Tensor:
+    """``F.binary_cross_entropy_with_logits(pair_dot(x_src, x_dst, index), label, pair_weight)`` in ONE launch forward (score,
+    loss term and the backward's coefficient ``w (sigmoid(s) - y)`` per pair; the loss added up in a fixed order) and one launch
+    per side backward.  ``reduction``: "mean" = ``sum(w l) / sum(w)``, "sum" = ``sum(w l)`` (GAE's ``recon_loss`` is "sum" with
+    weights 1 / n_pos and 1 / n_neg).  ``label`` in [0, 1], soft labels allowed.  A pair whose index is outside its table makes
+    the loss NaN.  Weights that sum to zero give NaN under "mean", as the torch formulation does (nothing is read back to find
+    out).  float32 tables with unit column stride on the device and P > 0; anything else goes to torch."""
+    if reduction not in ("mean", "sum"):
+        raise ValueError("link_bce_with_logits: reduction is 'mean' or 'sum'")
+    if not _pair_kernel_ok(x_src, x_dst, index) or label.shape != index.shape[1:]:
+        s = (x_src[index[0]] * x_dst[index[1]]).sum(-1)
+        y = label.to(s.dtype)
+        if pair_weight is None:
+            return torch.nn.functional.binary_cross_entropy_with_logits(s, y, reduction=reduction)
+        w = pair_weight.to(s.dtype)
+        total = torch.nn.functional.binary_cross_entropy_with_logits(s, y, weight=w, reduction="sum")
+        return total / w.sum() if reduction == "mean" else total
+    label = label.to(device=x_src.device, dtype=torch.float32).contiguous()
+    if pair_weight is not None:
+        pair_weight = pair_weight.to(device=x_src.device, dtype=torch.float32).contiguous()
+        if pair_weight.shape != label.shape:
+            raise ValueError("link_bce_with_logits: one weight per pair")
+    return _LinkBce.apply(x_src, x_dst, index.contiguous(), label, pair_weight, reduction == "mean", x_src is x_dst)
+
+
 def spmm_csr(x, row_ptr, col, reduce: str = "mean"):
     """Differentiable segmented mean/sum aggregation over a destination-major CSR."""
     assert reduce in ("mean", "sum", "add")

@@ -764,6 +764,44 @@ wholememory_error_code_t wgamd_softmax_xent_backward_f32(const float* logits, in
                                                          const void* state, const float* grad_loss, float* grad_logits, int64_t ldg,
                                                          void* stream);
 
+/* ---- Link-prediction head (csrc/wg_link.hip) ---------------------------------------------------------------------------------
+ * The inner-product decoder of the reference's link examples (cugraph_pyg/examples/mag_lp_mnmg.py; GAE's InnerProductDecoder in
+ * rgcn_link_class_mnmg.py) and its binary cross-entropy, over P pairs (index_src[p], index_dst[p]) of rows of two float32 tables
+ * [n_src, n_cols] / [n_dst, n_cols] (row strides ld_*, unit column stride; the same table twice is the homogeneous case):
+ *   s_p  = sum_c x_src[index_src[p], c] x_dst[index_dst[p], c]
+ *   loss = sum_p w_p (max(s_p, 0) - s_p y_p + log1p(exp(-|s_p|)))  (`mean`: / sum_p w_p),  y_p = label[p] in [0, 1],
+ *          w_p = pair_weight[p] (nullable = 1)
+ *   c_p  = w_p (sigmoid(s_p) - y_p)   -> coef [n_pairs + 1]: the coefficients the backward multiplies with, then sum_p w_p
+ * A pair with an index outside its table reads nothing: s_p = NaN (so is the loss), c_p = 0.
+ * forward: ONE launch each.  16-byte row loads when n_cols, both strides and both bases allow it, scalar loads otherwise.
+ * _bce_: `score` is nullable; `state` (wgamd_pair_bce_state_bytes bytes, zeroed by the call unless state_is_zeroed, reusable as
+ * it is left by any later call on the same stream) holds the per-workgroup partial sums, added in workgroup order by the last
+ * workgroup to finish: the loss is run-to-run bit-identical.  *loss_out and coef[n_pairs] are device scalars.
+ * backward, ONE launch per side, no atomics on floats, run-to-run bit-identical:
+ *   out[r] = scale * sum_{k in row r} coef[pair[k]] x_other[index_other[pair[k]]]  (+ acc[r]),  scale = *scale_num / *scale_den
+ * (both nullable = 1: the upstream gradient, and coef + n_pairs for the mean) over the side's incidence list (row_ptr [n_rows + 1],
+ * pair [n_pairs]: the pair ids grouped by row in pair order — wgamd_coo_to_csr_i64's row_ptr and edge_perm over index_row clamped
+ * into [0, n_rows); n_pairs, n_rows, n_other < 2^31).  A pair whose index_row or index_other is out of range adds nothing; rows without pairs get zeros (acc[r]).
+ * The list is summed in chunks of 64 entries whatever rows they cover and the pieces of a row are added in chunk order, so the
+ * launch does not last as long as its longest row.  acc may be out itself.  workspace: wgamd_pair_grad_workspace_bytes bytes; its
+ * counters are zeroed by the call unless counters_are_zeroed, and left zeroed.  No host synchronisation, no allocation. */
+size_t wgamd_pair_bce_state_bytes(int64_t n_pairs);
+wholememory_error_code_t wgamd_pair_dot_forward_f32(const float* x_src, int64_t ld_src, int64_t n_src, const float* x_dst,
+                                                    int64_t ld_dst, int64_t n_dst, int n_cols, const int64_t* index_src,
+                                                    const int64_t* index_dst, int64_t n_pairs, float* score, void* stream);
+wholememory_error_code_t wgamd_pair_bce_forward_f32(const float* x_src, int64_t ld_src, int64_t n_src, const float* x_dst,
+                                                    int64_t ld_dst, int64_t n_dst, int n_cols, const int64_t* index_src,
+                                                    const int64_t* index_dst, int64_t n_pairs, const float* label,
+                                                    const float* pair_weight, int mean, float* score, float* coef, void* state,
+                                                    int state_is_zeroed, float* loss_out, void* stream);
+size_t wgamd_pair_grad_workspace_bytes(int64_t n_pairs, int n_cols);
+wholememory_error_code_t wgamd_pair_grad_f32(const int* row_ptr, const int* pair, int64_t n_rows, int64_t n_pairs,
+                                             const int64_t* index_row, const int64_t* index_other, const float* coef,
+                                             const float* x_other, int64_t ld_other, int64_t n_other, int n_cols,
+                                             const float* scale_num, const float* scale_den, const float* acc, int64_t ld_acc,
+                                             float* out, int64_t ld_out, void* workspace, size_t workspace_bytes,
+                                             int counters_are_zeroed, void* stream);
+
 /* ---- GCN layer (csrc/wg_gcn.hip): torch_geometric.nn.GCNConv over a sampled hop ---------------------------------------------
  * The model of the reference's headline cugraph-pyg example (python/cugraph-pyg/cugraph_pyg/examples/gcn_dist_mnmg.py):
  *   agg[i]  = s_i ( sum_{e = (j -> i), not a loop} w_e d_j X[j]  +  [loops] loopw_i d_self X[self_rows[i]] )
