@@ -260,11 +260,12 @@ __global__ void gcn_wgrad_reduce_kernel(const float* __restrict__ part, int grid
   }
 }
 
-constexpr int kWgradMaxGridX = 128;
+constexpr int kWgradMaxGridX     = 128;
+constexpr int kWgradMaxGridXWide = 1024;   // _split: operands of many more rows than a hop has (a link head's whole tables)
 
-int wgrad_grid_x(int64_t n_rows)
+int wgrad_grid_x(int64_t n_rows, int max_split = kWgradMaxGridX)
 {
-  return (int)std::max<int64_t>(1, std::min<int64_t>(kWgradMaxGridX, (n_rows + 511) / 512));
+  return (int)std::max<int64_t>(1, std::min<int64_t>(max_split, (n_rows + 511) / 512));
 }
 
 template <int KIND>
@@ -383,21 +384,26 @@ extern "C" wholememory_error_code_t wgamd_gcn_aggregate_f32(const int* row_ptr, 
   });
 }
 
-extern "C" size_t wgamd_gcn_wgrad_workspace_bytes(int64_t n_rows, int F, int N)
+extern "C" size_t wgamd_gcn_wgrad_split_workspace_bytes(int64_t n_rows, int F, int N, int max_split)
 {
   using namespace wgamd;
-  if (F <= 0 || N <= 0 || F > 256 || N > 256) return 0;
-  return (size_t)wgrad_grid_x(n_rows) * ((size_t)N * F + N) * 4;
+  if (F <= 0 || N <= 0 || F > 256 || N > 256 || max_split < 1 || max_split > kWgradMaxGridXWide) return 0;
+  return (size_t)wgrad_grid_x(n_rows, max_split) * ((size_t)N * F + N) * 4;
 }
 
-extern "C" wholememory_error_code_t wgamd_gcn_wgrad_f32(const float* agg, int64_t ld_agg, int64_t n_rows, int F,
-                                                        const float* grad_out, int64_t ldg, const float* act_out, int64_t ld_act,
-                                                        int N, float* grad_w, float* grad_bias, int accumulate, void* workspace,
-                                                        size_t workspace_bytes, void* stream)
+extern "C" size_t wgamd_gcn_wgrad_workspace_bytes(int64_t n_rows, int F, int N)
+{
+  return wgamd_gcn_wgrad_split_workspace_bytes(n_rows, F, N, wgamd::kWgradMaxGridX);
+}
+
+extern "C" wholememory_error_code_t wgamd_gcn_wgrad_split_f32(const float* agg, int64_t ld_agg, int64_t n_rows, int F,
+                                                              const float* grad_out, int64_t ldg, const float* act_out,
+                                                              int64_t ld_act, int N, float* grad_w, float* grad_bias, int accumulate,
+                                                              int max_split, void* workspace, size_t workspace_bytes, void* stream)
 {
   using namespace wgamd;
   return guarded("wgamd_gcn_wgrad_f32", [&] {
-    WG_REQUIRE_INPUT(n_rows >= 0 && F > 0 && N > 0, "bad sizes");
+    WG_REQUIRE_INPUT(n_rows >= 0 && F > 0 && N > 0 && max_split >= 1 && max_split <= kWgradMaxGridXWide, "bad sizes");
     if (F > 256 || N > 256) throw logic_error(fmt("unsupported shape: F=%d, N=%d (both <= 256)", F, N));
     WG_REQUIRE_INPUT(grad_w != nullptr, "null pointer");
     auto st = static_cast<hipStream_t>(stream);
@@ -410,8 +416,8 @@ extern "C" wholememory_error_code_t wgamd_gcn_wgrad_f32(const float* agg, int64_
     }
     WG_REQUIRE_INPUT(agg && grad_out && workspace, "null pointer");
     WG_REQUIRE_INPUT(ld_agg >= F && ldg >= N && (act_out == nullptr || ld_act >= N), "leading dimension too small");
-    WG_REQUIRE_INPUT(workspace_bytes >= wgamd_gcn_wgrad_workspace_bytes(n_rows, F, N), "workspace too small");
-    const int gx      = wgrad_grid_x(n_rows);
+    WG_REQUIRE_INPUT(workspace_bytes >= wgamd_gcn_wgrad_split_workspace_bytes(n_rows, F, N, max_split), "workspace too small");
+    const int gx      = wgrad_grid_x(n_rows, max_split);
     const int64_t rpb = ((n_rows + gx - 1) / gx + 3) / 4 * 4;
     const int gx_used = (int)((n_rows + rpb - 1) / rpb);
     float* part       = static_cast<float*>(workspace);
@@ -423,4 +429,13 @@ extern "C" wholememory_error_code_t wgamd_gcn_wgrad_f32(const float* agg, int64_
     gcn_wgrad_reduce_kernel<<<(int)((total + 255) / 256), 256, 0, st>>>(part, gx_used, N, F, grad_w, grad_bias, accumulate);
     WG_HIP_CHECK(hipGetLastError());
   });
+}
+
+extern "C" wholememory_error_code_t wgamd_gcn_wgrad_f32(const float* agg, int64_t ld_agg, int64_t n_rows, int F,
+                                                        const float* grad_out, int64_t ldg, const float* act_out, int64_t ld_act,
+                                                        int N, float* grad_w, float* grad_bias, int accumulate, void* workspace,
+                                                        size_t workspace_bytes, void* stream)
+{
+  return wgamd_gcn_wgrad_split_f32(agg, ld_agg, n_rows, F, grad_out, ldg, act_out, ld_act, N, grad_w, grad_bias, accumulate,
+                                   wgamd::kWgradMaxGridX, workspace, workspace_bytes, stream);
 }

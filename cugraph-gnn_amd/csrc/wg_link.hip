@@ -13,13 +13,12 @@
 // every sum has a fixed order: no float atomics, run-to-run bit-identical.
 // A pair with an index outside its table reads nothing: its score is NaN (so is the loss), its coefficient 0.
 #include "wg_common.hpp"
+#include "wg_link_parts.hpp"
 #include "wgamd_ext.h"
 
 namespace wgamd {
 namespace {
 
-constexpr int kLinkThreads   = 256;
-constexpr int kLinkMaxGrid   = 2048;
 constexpr int kPairsInFlight = 4;    // pairs a lane group of the forward has in flight
 constexpr int kChunkEntries  = 64;   // entries of an incidence list per lane group
 
@@ -51,15 +50,7 @@ __device__ __forceinline__ void store_cols(float* p, const cols<VEC>& r)
   }
 }
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
-// state (BCE only): [0] loss, [1] sum of weights, [2] the ticket (as int; at a fixed place: the state serves launches of any
-// grid), [3] unused, then per workgroup (loss, weight) pairs
+// state (BCE only): as bce_finish (wg_link_parts.hpp) lays it out
 template <int VEC, bool BCE>
 __global__ void __launch_bounds__(kLinkThreads)
 pair_fwd_kernel(const float* __restrict__ xs, int64_t lds, int64_t n_src, const float* __restrict__ xd, int64_t ldd, int64_t n_dst, int C,
@@ -117,69 +108,11 @@ pair_fwd_kernel(const float* __restrict__ xs, int64_t lds, int64_t n_src, const 
       if (u < U && p < P) {
         s = good ? s : __builtin_nanf("");
         if (score) score[p] = s;
-        if constexpr (BCE) {
-          const float y = label[p], w = weight ? weight[p] : 1.f;
-          const float e = expf(-fabsf(s));
-          loss += w * (fmaxf(s, 0.f) - s * y + log1pf(e));
-          wsum += w;
-          // sigmoid(s) - y without the cancellation of sigmoid - 1
-          const float num = s >= 0.f ? (1.f - y) - y * e : (1.f - y) * e - y;
-          coef[p]         = good ? w * num / (1.f + e) : 0.f;
-        }
+        if constexpr (BCE) coef[p] = bce_pair(s, good, label[p], weight ? weight[p] : 1.f, loss, wsum);
       }
     }
   }
-  if constexpr (BCE) {
-    constexpr int waves = kLinkThreads / 64;
-    __shared__ float s_loss[waves], s_w[waves];
-    __shared__ int s_last;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    loss = wave_sum(loss);
-    wsum = wave_sum(wsum);
-    if (lane == 0) {
-      s_loss[wave] = loss;
-      s_w[wave]    = wsum;
-    }
-    __syncthreads();
-    float* part = state + 4;
-    int* ticket = reinterpret_cast<int*>(state + 2);
-    if (threadIdx.x == 0) {
-      float a = 0.f, b = 0.f;
-      for (int k = 0; k < waves; k++) a += s_loss[k], b += s_w[k];
-      part[2 * blockIdx.x]     = a;
-      part[2 * blockIdx.x + 1] = b;
-      __threadfence();
-      s_last = atomicAdd(ticket, 1) == (int)gridDim.x - 1;
-    }
-    __syncthreads();
-    if (s_last) {   // thread k takes workgroups k, k + 256, ... in order, then a fixed tree
-      __shared__ float t_loss[kLinkThreads], t_w[kLinkThreads];
-      __threadfence();
-      float a = 0.f, b = 0.f;
-      for (unsigned k = threadIdx.x; k < gridDim.x; k += kLinkThreads) {
-        a += __hip_atomic_load(&part[2 * k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        b += __hip_atomic_load(&part[2 * k + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      t_loss[threadIdx.x] = a;
-      t_w[threadIdx.x]    = b;
-      __syncthreads();
-      for (int half = kLinkThreads / 2; half >= 1; half >>= 1) {
-        if ((int)threadIdx.x < half) {
-          t_loss[threadIdx.x] += t_loss[threadIdx.x + half];
-          t_w[threadIdx.x] += t_w[threadIdx.x + half];
-        }
-        __syncthreads();
-      }
-      if (threadIdx.x == 0) {
-        const float l = mean ? t_loss[0] / t_w[0] : t_loss[0];
-        state[0]  = l;
-        state[1]  = t_w[0];
-        coef[P]   = t_w[0];   // the sum of weights travels with the coefficients: the state is free for the next call
-        *loss_out = l;
-        *ticket   = 0;        // (the state is reusable without a memset)
-      }
-    }
-  }
+  if constexpr (BCE) bce_finish(loss, wsum, state, coef, P, loss_out, mean);
 }
 
 // One side's gradient over its incidence list (row_ptr, pair): the lane group (>= 16 lanes) of chunk ch sums entries

@@ -309,6 +309,14 @@ SYMBOLS = {
     "wgamd_pair_grad_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                     c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_size_t, c_int,
                                     c_void_p]),
+    # MLP edge decoder (wg_link_mlp.hip)
+    "wgamd_pair_mlp_supported": (c_int, [c_int, c_int, c_int]),
+    "wgamd_pair_mlp_forward_f32": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p,
+                                           c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                           c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "wgamd_pair_mlp_backward_workspace_bytes": (c_size_t, [c_int]),
+    "wgamd_pair_mlp_backward_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
     # GCN layer (wg_gcn.hip)
     "wgamd_gcn_layer_supported": (c_int, [c_int, c_int]),
     "wgamd_gcn_layer_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
@@ -324,6 +332,9 @@ SYMBOLS = {
     "wgamd_gcn_wgrad_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
     "wgamd_gcn_wgrad_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p,
                                     c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "wgamd_gcn_wgrad_split_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int]),
+    "wgamd_gcn_wgrad_split_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p,
+                                          c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     # RGCN layer (wg_rgcn.hip)
     "wgamd_rgcn_layer_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "wgamd_rgcn_edge_coef": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -707,6 +707,234 @@ def link_bce_with_logits(x_src: torch.Tensor, x_dst: torch.Tensor, index: torch.
     return _LinkBce.apply(x_src, x_dst, index.contiguous(), label, pair_weight, reduction == "mean", x_src is x_dst)
 
 
+# ---- MLP edge decoder (csrc/wg_link_mlp.hip) ---------------------------------------------------------------------------------
+_LINK_MLP_WS = {}     # (device index, stream) -> the reusable workspace of wgamd_pair_mlp_backward_f32
+_ONES = {}            # device -> a grow-only float32 vector of ones (the coefficients of a plain sum over an incidence list)
+
+
+def _ones(n: int, device) -> torch.Tensor:
+    buf = _ONES.get(device)
+    if buf is None or buf.shape[0] < n:
+        buf = _ONES[device] = torch.ones(max(n * 2, 1 << 16), dtype=torch.float32, device=device)
+    return buf[:n]
+
+
+def pair_mlp_supported(C_src: int, C_dst: int, H: int) -> bool:
+    """Shapes of the one-kernel MLP edge decoder (``wgamd_pair_mlp_forward_f32``): both widths multiples of 4, their sum <= 1024,
+    1 <= H <= 256."""
+    return bool(L.lib().wgamd_pair_mlp_supported(int(C_src), int(C_dst), int(H)))
+
+
+_LINK_WGRAD_SPLIT = 1024      # row ranges of the split-K over a whole table (a hop's 128 leave most of the chip idle there)
+
+
+def _wgrad_blocks(x, G):
+    """``G^T x`` ([H, C]) by ``gcn_wgrad`` over column blocks of x no wider than its 256, and ``colsum(G)`` from the first."""
+    H, C = G.shape[1], x.shape[1]
+    gb = torch.empty(H, dtype=torch.float32, device=G.device)
+    blocks = []
+    for c0 in range(0, C, 256):
+        gw = torch.empty((H, min(256, C - c0)), dtype=torch.float32, device=G.device)
+        gcn_wgrad(x[:, c0:c0 + 256], G, gw, gb if c0 == 0 else None, max_split=_LINK_WGRAD_SPLIT)
+        blocks.append(gw)
+    return (blocks[0] if len(blocks) == 1 else torch.cat(blocks, dim=1)), gb
+
+
+class _PairMlp(torch.autograd.Function):
+    """The one-kernel MLP edge decoder, with (``label`` given) or without its binary cross-entropy.  Backward: ONE launch turns
+    the kept hidden rows into dZ and sums dw2 / db2; the concatenation is linear, so each side's ``G[r] = sum of dZ over the pairs
+    of row r`` is ``wgamd_pair_grad_f32`` over that side's incidence list (dZ as the other table, read by pair), and
+    ``dx = G @ W1[:, side]`` (a library GEMM), ``dW1[:, side] = G^T x``, ``db1 = colsum(G_src)`` (``gcn_wgrad``).  No float
+    atomics anywhere."""
+
+    @staticmethod
+    def forward(ctx, x_src, x_dst, w1, b1, w2, b2, index, label, weight, mean, shared, keep):
+        lib, dev = L.lib(), x_src.device
+        P, H = index.shape[1], w1.shape[0]
+        bce = label is not None
+        w1k = w1.detach()
+        if w1k.stride(1) != 1 or w1k.stride(0) % 4 or w1k.data_ptr() % 16:
+            w1k = w1k.contiguous()
+        w2k = w2.detach().reshape(-1).contiguous()
+        b1k = None if b1 is None else b1.detach().contiguous()
+        hidden = torch.empty((P, (H + 3) // 4 * 4), dtype=torch.float32, device=dev) if keep else None
+        score = coef = state = loss = None
+        if bce:
+            key = (dev.index, get_stream().value)
+            state = _LINK_STATE.get(key)
+            if state is None:
+                state = _LINK_STATE[key] = torch.zeros((lib.wgamd_pair_bce_state_bytes(P) + 3) // 4, dtype=torch.float32, device=dev)
+            coef = torch.empty(P + 1, dtype=torch.float32, device=dev)       # [P]: the sum of weights
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+        else:
+            score = torch.empty(P, dtype=torch.float32, device=dev)
+        L.check(lib.wgamd_pair_mlp_forward_f32(
+            x_src.data_ptr(), x_src.stride(0), x_src.shape[0], x_dst.data_ptr(), x_dst.stride(0), x_dst.shape[0], x_src.shape[1],
+            x_dst.shape[1], index[0].data_ptr(), index[1].data_ptr(), P, w1k.data_ptr(), w1k.stride(0), H,
+            _ptr(b1k), w2k.data_ptr(), None if b2 is None else b2.detach().data_ptr(), _ptr(label), _ptr(weight), int(mean),
+            _ptr(score), _ptr(coef), _ptr(state), 1, _ptr(loss), _ptr(hidden), 0 if hidden is None else hidden.stride(0),
+            get_stream()),
+            "wgamd_pair_mlp_forward_f32")
+        if keep:
+            ctx.save_for_backward(x_src, x_dst, w1, w2, index, coef)
+            ctx.kept = hidden
+            ctx.mean, ctx.shared, ctx.bce = mean, shared, bce
+        return loss if bce else score
+
+    @staticmethod
+    def backward(ctx, g):
+        _released(ctx.kept, "EdgeDecoder", "hidden rows")
+        x_src, x_dst, w1, w2, index, coef = ctx.saved_tensors
+        hidden, ctx.kept = ctx.kept, None
+        lib, dev = L.lib(), hidden.device
+        need_xs, need_xd, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:6]
+        P, (H, K), Cs = index.shape[1], w1.shape, x_src.shape[1]
+        g = g.to(torch.float32).contiguous()
+        if ctx.bce:      # g_p = grad_loss * c_p (/ sum w): the scale stays on the device
+            per_pair, num, den = coef, g, (coef[P:] if ctx.mean else None)
+        else:
+            per_pair, num, den = g, None, None
+        key = (dev.index, get_stream().value)
+        ws = _LINK_MLP_WS.get(key)
+        if ws is None:
+            ws = _LINK_MLP_WS[key] = torch.zeros(lib.wgamd_pair_mlp_backward_workspace_bytes(H), dtype=torch.uint8, device=dev)
+        gw2 = torch.empty(H, dtype=torch.float32, device=dev) if need_w2 else None
+        gb2 = torch.empty(1, dtype=torch.float32, device=dev) if need_b2 else None
+        w2k = w2.detach().reshape(-1).contiguous()
+        L.check(lib.wgamd_pair_mlp_backward_f32(
+            hidden.data_ptr(), hidden.stride(0), P, H, w2k.data_ptr(), per_pair.data_ptr(),
+            _ptr(num), _ptr(den), index[0].data_ptr(), x_src.shape[0], index[1].data_ptr(), x_dst.shape[0], _ptr(gw2), _ptr(gb2),
+            ws.data_ptr(), ws.numel(), 1, get_stream()), "wgamd_pair_mlp_backward_f32")
+        dz = hidden[:, :H]
+        want_src = need_xs or need_w1 or need_b1
+        want_dst = need_xd or need_w1 or (ctx.shared and need_xs)
+        by_pair, one = _arange(P, dev), _ones(P, dev)
+        G_src = _pair_side_grad(index[0], by_pair, x_src.shape[0], dz, one, None, None) if want_src else None
+        G_dst = _pair_side_grad(index[1], by_pair, x_dst.shape[0], dz, one, None, None) if want_dst else None
+        w1d = w1.detach()
+        gxs = G_src @ w1d[:, :Cs] if need_xs else None
+        gxd = None
+        if ctx.shared and need_xs:      # one table on both sides: source side first, then destination side
+            gxs = torch.addmm(gxs, G_dst, w1d[:, Cs:])
+        elif need_xd:
+            gxd = G_dst @ w1d[:, Cs:]
+        gw1 = gb1 = None
+        if need_w1 or need_b1:
+            gw_src, gb1 = _wgrad_blocks(x_src.detach(), G_src)
+            if need_w1:
+                gw1 = torch.cat([gw_src, _wgrad_blocks(x_dst.detach(), G_dst)[0]], dim=1)
+            gb1 = gb1 if need_b1 else None
+        if gw2 is not None:
+            gw2 = gw2.reshape(w2.shape)
+        return gxs, gxd, gw1, gb1, gw2, gb2, None, None, None, None, None, None
+
+
+def _pair_mlp_check(x_src, x_dst, index, w1, b1, w2, b2, name):
+    """Shape checks of the MLP edge decoder (ValueError), then whether the kernel takes the call."""
+    if index.dim() != 2 or index.shape[0] != 2 or x_src.dim() != 2 or x_dst.dim() != 2:
+        raise ValueError("%s: index [2, P] over two [rows, C] tables" % name)
+    if w1.dim() != 2 or w1.shape[1] != x_src.shape[1] + x_dst.shape[1]:
+        raise ValueError("%s: w1 is [H, C_src + C_dst]" % name)
+    H = w1.shape[0]
+    if w2.numel() != H or (b1 is not None and b1.shape != (H,)) or (b2 is not None and b2.numel() != 1):
+        raise ValueError("%s: b1 [H], w2 [H] (or [1, H]), b2 one element" % name)
+    params = [t for t in (w1, b1, w2, b2) if t is not None]
+    return (all(t.dtype == torch.float32 and t.is_cuda for t in [x_src, x_dst] + params)
+            and all(t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0 for t in (x_src, x_dst))
+            and index.is_cuda and index.dtype == torch.int64 and index.shape[1] > 0 and index.shape[1] < 2 ** 31
+            and x_src.shape[0] < 2 ** 31 and x_dst.shape[0] < 2 ** 31 and H >= 1
+            and pair_mlp_supported(x_src.shape[1], x_dst.shape[1], H))
+
+
+def _pair_mlp_keeps(*tensors) -> bool:
+    """Whether a backward pass may follow: only then does the forward write the hidden rows out ([P, H])."""
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
+
+
+def _pair_mlp_torch(x_src, x_dst, index, w1, b1, w2, b2):
+    z = torch.cat([x_src[index[0]], x_dst[index[1]]], dim=-1)
+    h = torch.nn.functional.linear(z, w1, b1).relu()
+    return torch.nn.functional.linear(h, w2.reshape(1, -1), None if b2 is None else b2.reshape(1)).view(-1)
+
+
+def pair_mlp(x_src: torch.Tensor, x_dst: torch.Tensor, index: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor],
+             w2: torch.Tensor, b2: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``lin2(relu(lin1(cat([x_src[index[0]], x_dst[index[1]]], -1)))).view(-1)`` — the MLP edge decoder of link prediction (the
+    ``EdgeDecoder`` of the reference's examples/movielens_mnmg.py and taobao_mnmg.py): ``w1`` [H, C_src + C_dst] and ``b1`` [H]
+    are ``lin1``'s, ``w2`` [1, H] (or [H]) and ``b2`` [1] ``lin2``'s; either bias may be None.  ONE launch forward that forms
+    neither the gathered rows, nor their concatenation, nor (without grad mode) the hidden activation in memory; differentiable
+    in the tables and the four parameters with an atomic-free, bit-reproducible backward.  ``x_src is x_dst`` is the homogeneous
+    case.  A pair whose index is outside its table scores NaN, reads nothing and adds nothing to any gradient.  Kernel domain
+    (``pair_mlp_supported``): float32 on the device, unit column stride, 16-byte aligned rows, both widths multiples of 4 with
+    C_src + C_dst <= 1024, H <= 256; anything else goes to the torch formulation."""
+    if not _pair_mlp_check(x_src, x_dst, index, w1, b1, w2, b2, "pair_mlp"):
+        return _pair_mlp_torch(x_src, x_dst, index, w1, b1, w2, b2)
+    return _PairMlp.apply(x_src, x_dst, w1, b1, w2, b2, index.contiguous(), None, None, False, x_src is x_dst,
+                          _pair_mlp_keeps(x_src, x_dst, w1, b1, w2, b2))
+
+
+def link_mlp_bce_with_logits(x_src: torch.Tensor, x_dst: torch.Tensor, index: torch.Tensor, label: torch.Tensor, w1: torch.Tensor,
+                             b1: Optional[torch.Tensor], w2: torch.Tensor, b2: Optional[torch.Tensor] = None,
+                             pair_weight: Optional[torch.Tensor] = None, reduction: str = "mean") -> torch.Tensor:
+    """``F.binary_cross_entropy_with_logits(pair_mlp(x_src, x_dst, index, w1, b1, w2, b2), label, pair_weight)`` with the loss in
+    the decoder's ONE forward launch (score, loss term and the backward's coefficient per pair; the loss added up in a fixed
+    order).  ``reduction``, ``label``, ``pair_weight``, out-of-range pairs (the loss is NaN) and the torch fallback as
+    ``link_bce_with_logits``; the kernel domain as ``pair_mlp``."""
+    if reduction not in ("mean", "sum"):
+        raise ValueError("link_mlp_bce_with_logits: reduction is 'mean' or 'sum'")
+    kernel = _pair_mlp_check(x_src, x_dst, index, w1, b1, w2, b2, "link_mlp_bce_with_logits")
+    if label.shape != index.shape[1:]:
+        raise ValueError("link_mlp_bce_with_logits: one label per pair")
+    if pair_weight is not None and pair_weight.shape != label.shape:
+        raise ValueError("link_mlp_bce_with_logits: one weight per pair")
+    if not kernel:
+        s = _pair_mlp_torch(x_src, x_dst, index, w1, b1, w2, b2)
+        y = label.to(s.dtype)
+        if pair_weight is None:
+            return torch.nn.functional.binary_cross_entropy_with_logits(s, y, reduction=reduction)
+        w = pair_weight.to(s.dtype)
+        total = torch.nn.functional.binary_cross_entropy_with_logits(s, y, weight=w, reduction="sum")
+        return total / w.sum() if reduction == "mean" else total
+    label = label.to(device=x_src.device, dtype=torch.float32).contiguous()
+    if pair_weight is not None:
+        pair_weight = pair_weight.to(device=x_src.device, dtype=torch.float32).contiguous()
+    return _PairMlp.apply(x_src, x_dst, w1, b1, w2, b2, index.contiguous(), label, pair_weight, reduction == "mean", x_src is x_dst,
+                          _pair_mlp_keeps(x_src, x_dst, w1, b1, w2, b2))
+
+
+class EdgeDecoder(torch.nn.Module):
+    """The ``EdgeDecoder`` of the reference's examples/movielens_mnmg.py and taobao_mnmg.py on the one-kernel head:
+    ``lin2(relu(lin1(cat([z_src[row], z_dst[col]], -1)))).view(-1)`` with ``lin1 = Linear(C_src + C_dst, hidden_channels)`` and
+    ``lin2 = Linear(hidden_channels, 1)`` — the reference's parameter names, so its checkpoints load.  ``in_channels``: an int
+    or a ``(C_src, C_dst)`` pair; None = ``hidden_channels`` on both sides (the reference's class).  ``forward`` returns the
+    scores (``pair_mlp``); ``loss`` their binary cross-entropy in the same launch (``link_mlp_bce_with_logits``)."""
+
+    def __init__(self, hidden_channels: int, in_channels: Union[int, Tuple[int, int], None] = None, bias: bool = True):
+        super().__init__()
+        if in_channels is None:
+            in_channels = hidden_channels
+        if isinstance(in_channels, int):
+            in_channels = (in_channels, in_channels)
+        self.in_channels, self.hidden_channels = (int(in_channels[0]), int(in_channels[1])), int(hidden_channels)
+        self.lin1 = torch.nn.Linear(sum(self.in_channels), self.hidden_channels, bias=bias)
+        self.lin2 = torch.nn.Linear(self.hidden_channels, 1, bias=bias)
+
+    def reset_parameters(self):
+        self.lin1.reset_parameters()
+        self.lin2.reset_parameters()
+
+    def forward(self, z_src: torch.Tensor, z_dst: torch.Tensor, edge_label_index: torch.Tensor) -> torch.Tensor:
+        return pair_mlp(z_src, z_dst, edge_label_index, self.lin1.weight, self.lin1.bias, self.lin2.weight, self.lin2.bias)
+
+    def loss(self, z_src: torch.Tensor, z_dst: torch.Tensor, edge_label_index: torch.Tensor, edge_label: torch.Tensor,
+             pair_weight: Optional[torch.Tensor] = None, reduction: str = "mean") -> torch.Tensor:
+        return link_mlp_bce_with_logits(z_src, z_dst, edge_label_index, edge_label, self.lin1.weight, self.lin1.bias,
+                                        self.lin2.weight, self.lin2.bias, pair_weight=pair_weight, reduction=reduction)
+
+    def extra_repr(self) -> str:
+        return "in_channels=%s, hidden_channels=%d" % (self.in_channels, self.hidden_channels)
+
+
 def spmm_csr(x, row_ptr, col, reduce: str = "mean"):
     """Differentiable segmented mean/sum aggregation over a destination-major CSR."""
     assert reduce in ("mean", "sum", "add")
@@ -1842,18 +2070,24 @@ def gcn_aggregate(row_ptr, col, x, self_rows, dinv_src=None, dinv_dst=None, fill
     return out
 
 
-def gcn_wgrad(agg, grad_out, grad_w, grad_bias=None, act_out=None, accumulate=False):
+def gcn_wgrad(agg, grad_out, grad_w, grad_bias=None, act_out=None, accumulate=False, max_split=None):
     """``grad_w (+)= dZ^T agg``, ``grad_bias (+)= colsum(dZ)``, ``dZ = grad_out * (act_out > 0)`` (``wgamd_gcn_wgrad_f32``:
-    deterministic split-K)."""
+    deterministic split-K; ``max_split``: over up to that many row ranges, ``wgamd_gcn_wgrad_split_f32``)."""
     n, F_ = agg.shape
     N = grad_out.shape[1]
     assert agg.stride(1) == 1 and grad_out.stride(1) == 1 and grad_w.shape == (N, F_) and grad_w.is_contiguous()
     assert act_out is None or (act_out.shape == grad_out.shape and act_out.stride(1) == 1)
-    need = L.lib().wgamd_gcn_wgrad_workspace_bytes(int(n), F_, N)
+    lib = L.lib()
+    need = (lib.wgamd_gcn_wgrad_workspace_bytes(int(n), F_, N) if max_split is None
+            else lib.wgamd_gcn_wgrad_split_workspace_bytes(int(n), F_, N, int(max_split)))
     ws = torch.empty(max(int(need), 4), dtype=torch.uint8, device=agg.device)
-    L.check(L.lib().wgamd_gcn_wgrad_f32(agg.data_ptr(), agg.stride(0), n, F_, grad_out.data_ptr(), grad_out.stride(0), _ptr(act_out),
-                                        0 if act_out is None else act_out.stride(0), N, grad_w.data_ptr(), _ptr(grad_bias),
-                                        int(bool(accumulate)), ws.data_ptr(), ws.numel(), get_stream()), "wgamd_gcn_wgrad_f32")
+    head = (agg.data_ptr(), agg.stride(0), n, F_, grad_out.data_ptr(), grad_out.stride(0), _ptr(act_out),
+            0 if act_out is None else act_out.stride(0), N, grad_w.data_ptr(), _ptr(grad_bias), int(bool(accumulate)))
+    tail = (ws.data_ptr(), ws.numel(), get_stream())
+    if max_split is None:
+        L.check(lib.wgamd_gcn_wgrad_f32(*head, *tail), "wgamd_gcn_wgrad_f32")
+    else:
+        L.check(lib.wgamd_gcn_wgrad_split_f32(*head, int(max_split), *tail), "wgamd_gcn_wgrad_split_f32")
 
 
 def _dense_wgrad(lg: LayerGraph, a, gz, w, want_b: bool, act):

@@ -7,9 +7,14 @@ graph, forward and backward, the head is `wholegraph_amd.nn.link_bce_with_logits
 no float atomics — and the optimizer steps once per group.  The shape of the reference's link-prediction examples
 (python/cugraph-pyg/cugraph_pyg/examples/mag_lp_mnmg.py: encoder -> `(h[src] * h[dst]).sum(-1)` -> BCE).
 
-`--torch-ops` keeps the loop and swaps the head for the torch formulation (two gathered copies, `index_put` backward).
+`--decoder mlp` trains the MLP edge decoder of the reference's movielens_mnmg.py / taobao_mnmg.py instead
+(`wholegraph_amd.nn.EdgeDecoder`: `lin2(relu(lin1(cat([h[src], h[dst]], -1))))`, its BCE in the decoder's one forward launch
+through `EdgeDecoder.loss`), and prints the first step's loss ahead of the epochs.
 
-    python examples/sage_link_call_groups.py [--nodes 20000] [--epochs 3] [--torch-ops]
+`--torch-ops` keeps the loop and swaps the head for the torch formulation of either decoder (gathered copies, `index_put`
+backward).
+
+    python examples/sage_link_call_groups.py [--nodes 20000] [--epochs 3] [--decoder {dot,mlp}] [--torch-ops]
 """
 import argparse
 import os
@@ -49,7 +54,8 @@ def main(argv=None):
     ap.add_argument("--group", type=int, default=16, help="mini-batches per call group (= per optimizer step)")
     ap.add_argument("--fanout", type=int, nargs="+", default=[10, 5])
     ap.add_argument("--epochs", type=int, default=3)
-    ap.add_argument("--torch-ops", action="store_true", help="the head as torch ops instead of nn.link_bce_with_logits")
+    ap.add_argument("--decoder", choices=["dot", "mlp"], default="dot", help="inner product, or the MLP EdgeDecoder")
+    ap.add_argument("--torch-ops", action="store_true", help="the head as torch ops instead of the one-kernel head")
     args = ap.parse_args(argv)
     assert torch.cuda.is_available(), "needs an MI355X (there is no CPU fallback)"
     dev = torch.device("cuda")
@@ -68,8 +74,16 @@ def main(argv=None):
     L = len(args.fanout)
     dims = [32] + [64] * L
     convs = torch.nn.ModuleList(SAGEConv(dims[i], dims[i + 1]) for i in range(L)).to(dev)
-    opt = torch.optim.Adam(convs.parameters(), lr=0.01)
+    decoder = wnn.EdgeDecoder(dims[-1]).to(dev) if args.decoder == "mlp" else None
+    opt = torch.optim.Adam(list(convs.parameters()) + (list(decoder.parameters()) if decoder else []), lr=0.01)
+
+    def torch_scores(h, eli):
+        if decoder is None:
+            return (h[eli[0]] * h[eli[1]]).sum(-1)
+        return decoder.lin2(decoder.lin1(torch.cat([h[eli[0]], h[eli[1]]], dim=-1)).relu()).view(-1)
+
     loss_avg = acc = 0.0
+    first = decoder is not None
     for epoch in range(args.epochs):
         t0, edges, pairs = time.perf_counter(), 0, 0
         total = torch.zeros((), device=dev)               # (device-side running sums: no read-back per step)
@@ -80,14 +94,19 @@ def main(argv=None):
                 h = conv(h, grp.layer_graph(j), act="relu" if j + 1 < L else None)
             eli, label = grp.edge_label_index, (grp.edge_label > 0).float()
             if args.torch_ops:
-                loss = F.binary_cross_entropy_with_logits((h[eli[0]] * h[eli[1]]).sum(-1), label)
+                loss = F.binary_cross_entropy_with_logits(torch_scores(h, eli), label)
+            elif decoder is not None:
+                loss = decoder.loss(h, h, eli, label)
             else:
                 loss = wnn.link_bce_with_logits(h, h, eli, label)
+            if first:
+                print(f"step 0: loss {float(loss.detach()):.9g}")
+                first = False
             opt.zero_grad(set_to_none=True)
             loss.backward()
             opt.step()
             with torch.no_grad():
-                score = wnn.pair_dot(h.detach(), h.detach(), eli)
+                score = wnn.pair_dot(h.detach(), h.detach(), eli) if decoder is None else decoder(h.detach(), h.detach(), eli)
                 correct += ((score > 0).float() == label).sum()
                 total += loss.detach() * label.numel()
             pairs += label.numel()

@@ -802,6 +802,39 @@ wholememory_error_code_t wgamd_pair_grad_f32(const int* row_ptr, const int* pair
                                              float* out, int64_t ld_out, void* workspace, size_t workspace_bytes,
                                              int counters_are_zeroed, void* stream);
 
+/* ---- MLP edge decoder of link prediction (csrc/wg_link_mlp.hip) ---------------------------------------------------------------
+ * The EdgeDecoder of the reference's cugraph_pyg/examples/movielens_mnmg.py and taobao_mnmg.py over the pairs of the head above:
+ *   a_p = [x_src[index_src[p]] | x_dst[index_dst[p]]]   (K = c_src + c_dst columns)
+ *   h_p = relu(a_p W1^T + b1)                            W1 [hidden, ldw1] row-major (torch.nn.Linear.weight), b1 nullable
+ *   s_p = h_p . w2 + b2                                  w2 [hidden]; b2 nullable, ONE float on the device
+ * and, when `label` is given, the binary cross-entropy of the head above over s_p (label, pair_weight, mean, coef [n_pairs + 1],
+ * state of wgamd_pair_bce_state_bytes bytes, *loss_out: exactly as wgamd_pair_bce_forward_f32; `score` is then nullable).
+ * forward: ONE launch, 16 pairs per tile; neither the gathered rows nor their concatenation reach memory, and the hidden
+ * activation only when hidden_out is given ([n_pairs, ld_hidden], ld_hidden >= hidden rounded up to 4, rows 16-B aligned; the
+ * columns up to that width are written).  Product 1 runs on the exact fp32 matrix pipe (v_mfma_f32_16x16x4_f32).
+ * wgamd_pair_mlp_supported: c_src, c_dst multiples of 4, c_src + c_dst <= 1024, 1 <= hidden <= 256; x_src / x_dst / w1 rows
+ * 16-B aligned.  A pair with an index outside its table reads nothing: s_p = NaN (so is the loss), c_p = 0, hidden_out row 0.
+ * backward, ONE launch over the kept hidden rows: hidden_io[p] <- dZ_p = g_p w2 * [h_p > 0], grad_w2 = sum_p g_p h_p,
+ * grad_b2 = sum_p g_p (both nullable), g_p = g[p] * *scale_num / *scale_den (both nullable = 1), 0 for a pair with an index
+ * outside its table.  Per-workgroup partial sums added in workgroup order: no float atomics, run-to-run bit-identical.
+ * workspace: wgamd_pair_mlp_backward_workspace_bytes bytes, its ticket zeroed by the call unless workspace_is_zeroed, and left
+ * zeroed.  The sums of dZ over a row's pairs are wgamd_pair_grad_f32 (x_other = dZ, index_other = 0..n_pairs-1, coef = 1). */
+int wgamd_pair_mlp_supported(int c_src, int c_dst, int hidden);
+wholememory_error_code_t wgamd_pair_mlp_forward_f32(const float* x_src, int64_t ld_src, int64_t n_src, const float* x_dst,
+                                                    int64_t ld_dst, int64_t n_dst, int c_src, int c_dst, const int64_t* index_src,
+                                                    const int64_t* index_dst, int64_t n_pairs, const float* w1, int64_t ldw1,
+                                                    int hidden, const float* b1, const float* w2, const float* b2,
+                                                    const float* label, const float* pair_weight, int mean, float* score,
+                                                    float* coef, void* state, int state_is_zeroed, float* loss_out,
+                                                    float* hidden_out, int64_t ld_hidden, void* stream);
+size_t wgamd_pair_mlp_backward_workspace_bytes(int hidden);
+wholememory_error_code_t wgamd_pair_mlp_backward_f32(float* hidden_io, int64_t ld_hidden, int64_t n_pairs, int hidden,
+                                                     const float* w2, const float* g, const float* scale_num,
+                                                     const float* scale_den, const int64_t* index_src, int64_t n_src,
+                                                     const int64_t* index_dst, int64_t n_dst, float* grad_w2, float* grad_b2,
+                                                     void* workspace, size_t workspace_bytes, int workspace_is_zeroed,
+                                                     void* stream);
+
 /* ---- GCN layer (csrc/wg_gcn.hip): torch_geometric.nn.GCNConv over a sampled hop ---------------------------------------------
  * The model of the reference's headline cugraph-pyg example (python/cugraph-pyg/cugraph_pyg/examples/gcn_dist_mnmg.py):
  *   agg[i]  = s_i ( sum_{e = (j -> i), not a loop} w_e d_j X[j]  +  [loops] loopw_i d_self X[self_rows[i]] )
@@ -853,6 +886,13 @@ wholememory_error_code_t wgamd_gcn_wgrad_f32(const float* agg, int64_t ld_agg, i
                                              int64_t ldg, const float* act_out, int64_t ld_act, int N, float* grad_w,
                                              float* grad_bias, int accumulate, void* workspace, size_t workspace_bytes,
                                              void* stream);
+/* The same over up to max_split (1..1024) row ranges instead of the 128 a hop's rows ask for: operands of many more rows (the
+ * whole tables under a link head).  The ranges, hence the bits, depend on n_rows and max_split alone. */
+size_t wgamd_gcn_wgrad_split_workspace_bytes(int64_t n_rows, int F, int N, int max_split);
+wholememory_error_code_t wgamd_gcn_wgrad_split_f32(const float* agg, int64_t ld_agg, int64_t n_rows, int F, const float* grad_out,
+                                                   int64_t ldg, const float* act_out, int64_t ld_act, int N, float* grad_w,
+                                                   float* grad_bias, int accumulate, int max_split, void* workspace,
+                                                   size_t workspace_bytes, void* stream);
 
 /* ---- RGCN layer (csrc/wg_rgcn.hip): torch_geometric.nn.RGCNConv / FastRGCNConv over a sampled hop -----------------------------
  * The model of the reference's cugraph-pyg example rgcn_link_class_mnmg.py:

@@ -125,16 +125,12 @@ def example_loops(nodes):
     return out
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--group", type=int, default=188, help="mini-batches per call group")
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--nodes", type=int, default=20_000, help="vertices of the example's planted-partition graph")
-    args = ap.parse_args()
+def products_link_group(group):
+    """``(grp, loader, generator)``: the first call group of `group` mini-batches of the products-shaped link task (bench.py's RMAT graph,
+    fan-out [25, 10], bench.BATCH seed edges + as many negatives per mini-batch)."""
     import bench
     from cugraph_pyg_amd.data import FeatureStore, GraphStore
     from cugraph_pyg_amd.loader import LinkNeighborLoader
-    from cugraph_pyg_amd.loader.link_loader import _batched_first_unique
     dev = torch.device("cuda")
     V, E_und, _, _, fanout = bench.WORKLOADS["products"]
     B = bench.BATCH
@@ -143,15 +139,28 @@ def main():
     dst = torch.repeat_interleave(torch.arange(V, device=dev), row_ptr[1:] - row_ptr[:-1])
     gs[("n", "e", "n"), "coo", False, (V, V)] = torch.stack([col.to(torch.int64), dst])
     g = torch.Generator(device=dev).manual_seed(0)
-    pick = torch.randperm(col.shape[0], generator=g, device=dev)[:args.group * B]
+    pick = torch.randperm(col.shape[0], generator=g, device=dev)[:group * B]
     loader = LinkNeighborLoader((fs, gs), fanout, edge_label_index=torch.stack([col[pick].to(torch.int64), dst[pick]]), batch_size=B,
-                                shuffle=False, random_state=62, neg_sampling=("binary", 1.0), local_seeds_per_call=args.group * 4 * B)
+                                shuffle=False, random_state=62, neg_sampling=("binary", 1.0), local_seeds_per_call=group * 4 * B)
     del dst
-    grp = next(iter(loader.call_groups()))
+    return next(iter(loader.call_groups())), loader, g
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--group", type=int, default=188, help="mini-batches per call group")
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--nodes", type=int, default=20_000, help="vertices of the example's planted-partition graph")
+    args = ap.parse_args()
+    import bench
+    from cugraph_pyg_amd.loader.link_loader import _batched_first_unique
+    dev = torch.device("cuda")
+    V, B = bench.WORKLOADS["products"][0], bench.BATCH
+    grp, loader, g = products_link_group(args.group)
     heads = [head_timings(grp, C, args.iters, g) for C in (64, 256)]
     ends = torch.randint(0, V, (args.group, 4 * B), generator=g, device=dev)
     t_unique = timed(lambda: _batched_first_unique(ends, V), args.iters)
-    del grp, loader, gs
+    del grp, loader
     print(json.dumps({"metric": "link_head", "group": args.group, "heads": heads, "batched_first_unique_ms_per_group": round(t_unique, 4),
                       "example": example_loops(args.nodes)}))
 
