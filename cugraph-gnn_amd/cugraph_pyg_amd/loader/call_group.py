@@ -495,6 +495,34 @@ def _enqueue_walk_sizes(res):
     return sizes_h, ev
 
 
+def _enqueue_hetero_walk_sizes(rec, walk, seed_type):
+    """What a ``HeteroCallGroup`` needs of a finished ``HeteroPygWalk.run`` record besides the record: every size the host
+    needs (``HeteroCallGroup._wait``) on its way to pinned memory, the event that says it has arrived, and ``cseg`` — per hop
+    level and node type the batch-major offsets of "vertices discovered by the first k hops".  Sets ``rec["calls_seed_seg"]``
+    (``batch_ptr``: level 0 of ``seed_type``).  Enqueues only."""
+    state, G_, H, dev = rec["state"], walk.G, walk.hops, walk.dev
+    T = len(walk.ntypes)
+    pieces = [state[t]["seg"][G_:G_ + 1] for t in walk.ntypes]
+    # vertices per type after k hops as batch-major compact numberings — every (level, type) in ONE cumsum (the walk
+    # of a heterogeneous call group is a chain of ~170 small launches; glue that can be one launch is one launch)
+    sizes = torch.stack([rec["sizes"][k][t] for k in range(H) for t in walk.ntypes]).to(torch.int64)      # [H T, G]
+    cs_all = torch.zeros((H * T, G_ + 1), dtype=torch.int64, device=dev)
+    cs_all[:, 1:] = torch.cumsum(sizes, 1)
+    cseg = [{t: cs_all[k * T + i] for i, t in enumerate(walk.ntypes)} for k in range(H)]
+    totals = cs_all[:, G_].to(torch.int32)
+    pieces.append(totals)
+    for c in rec["calls"]:
+        if c is not None:
+            pieces += [c["f_seg"][G_:G_ + 1], c["counts"][0:1]]       # (frontier entries, sampled edges): views
+    rec["calls_seed_seg"] = cseg[0][seed_type].to(torch.int32)
+    sizes_d = torch.cat([p.to(torch.int32).reshape(-1) for p in pieces])
+    sizes_h = torch.empty(sizes_d.shape, dtype=torch.int32, pin_memory=True)
+    sizes_h.copy_(sizes_d, non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record()
+    return sizes_h, ev, cseg
+
+
 class _PipelinedGroups:
     """An epoch as a plan of call groups, software-pipelined: ``_launch(i)`` enqueues group i (``_on_walk_stream``: on the
     iterator's own HIP stream when ``overlap``) and returns it, or None past the plan; group g + 1 is enqueued before group g is
@@ -572,29 +600,9 @@ class CallGroupIterator(_PipelinedGroups):
                 rec = walk.run(None, None, rs, seed_lists={self._seed_type: (
                     ids, torch.tensor([0, ragged], dtype=torch.int32, device=dev), torch.zeros(ragged, dtype=torch.int32, device=dev))})
                 n_seeds = ragged
-            state, G_ = rec["state"], walk.G
-            T = len(walk.ntypes)
-            pieces = [state[t]["seg"][G_:G_ + 1] for t in walk.ntypes]
-            # vertices per type after k hops as batch-major compact numberings — every (level, type) in ONE cumsum (the walk
-            # of a heterogeneous call group is a chain of ~170 small launches; glue that can be one launch is one launch)
-            sizes = torch.stack([rec["sizes"][k][t] for k in range(H) for t in walk.ntypes]).to(torch.int64)      # [H T, G]
-            cs_all = torch.zeros((H * T, G_ + 1), dtype=torch.int64, device=dev)
-            cs_all[:, 1:] = torch.cumsum(sizes, 1)
-            cseg = [{t: cs_all[k * T + i] for i, t in enumerate(walk.ntypes)} for k in range(H)]
-            totals = cs_all[:, G_].to(torch.int32)
-            pieces.append(totals)
-            for c in rec["calls"]:
-                if c is not None:
-                    pieces += [c["f_seg"][G_:G_ + 1], c["counts"][0:1]]       # (frontier entries, sampled edges): views
-            rec["calls_seed_seg"] = cseg[0][self._seed_type].to(torch.int32)
-            sizes_d = torch.cat([p.to(torch.int32).reshape(-1) for p in pieces])
-            sizes_h = torch.empty(sizes_d.shape, dtype=torch.int32, pin_memory=True)
-            sizes_h.copy_(sizes_d, non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            return rec, sizes_h, ev, n_seeds, cseg
+            return (rec,) + _enqueue_hetero_walk_sizes(rec, walk, self._seed_type) + (n_seeds,)
 
-        rec, sizes_h, ev, n_seeds, cseg = self._on_walk_stream(enqueue)
+        rec, sizes_h, ev, cseg, n_seeds = self._on_walk_stream(enqueue)
         return HeteroCallGroup(rec, walk, self._fs, self._seed_type, b0, self._input_id[b0 * B:b0 * B + n_seeds], sizes_h, ev,
                                self._stream, cseg)
 

@@ -30,9 +30,10 @@ from wholegraph_amd import graph_ops
 
 from ..data.graph_store import GraphStore
 from ..sampler.sampler import (FetchPadder, HeteroNeighborSampler, NeighborSampler, build_hetero_data, filter_store,
-                               filter_store_from_group, group_attribute_views, _group_attribute_views, hetero_neighbor_sample,
+                               filter_store_from_group, group_attribute_views, hetero_neighbor_sample,
                                neighbor_sample)
 from .._compat import HeteroSamplerOutput, SamplerOutput
+from .link_call_group import hetero_group_data, hetero_link_data
 from .node_loader import generate_seed
 
 
@@ -93,7 +94,17 @@ def _batched_first_unique(ends: torch.Tensor, n_ids: int):
     """Row-wise first-appearance de-duplication of ``ends`` [G, S] (ids < n_ids), for a whole call group at once.
     -> (unique ids of all rows back to back, padded with zeros to G*S; int32 offsets [G+1]; int32 row of every live
     entry, padded; ``local`` [G, S] = position of every element in its row's unique list) — per row exactly what
-    ``graph_ops.append_unique`` with an empty target list returns."""
+    ``graph_ops.append_unique`` with an empty target list returns.  Device tensors inside the kernel's domain
+    (``graph_ops.rows_first_unique_supported``) take two launches and no read-back; everything else, and the CPU, the torch
+    formulation below — same results, bit for bit (tests/test_gpu_rows_first_unique.py)."""
+    if ends.is_cuda and ends.dtype == torch.int64 and graph_ops.rows_first_unique_supported(ends.shape[0], ends.shape[1], n_ids):
+        return graph_ops.rows_first_unique(ends, n_ids)
+    return _batched_first_unique_torch(ends, n_ids)
+
+
+def _batched_first_unique_torch(ends: torch.Tensor, n_ids: int):
+    """``_batched_first_unique`` in torch ops (a sort of G S keys inside ``torch.unique``, one size read-back): the CPU route, the
+    route of shapes outside the kernel's domain, and the yardstick the kernel is tested and timed against."""
     G, S = ends.shape
     dev = ends.device
     rows = torch.arange(G, device=dev).view(G, 1)
@@ -278,10 +289,33 @@ class LinkLoader:
         rows of the last layer's output — what ``wholegraph_amd.nn.link_bce_with_logits`` takes.  Homogeneous graphs, uniform
         or positively-weighted sampling with positive fan-outs."""
         from .link_call_group import LinkCallGroupIterator
+        self.__refuse_call_groups("call_groups", "heterogeneous graphs are not supported here (these link call groups are "
+                                  "homogeneous): use hetero_call_groups()" if self.__hetero else None)
+        perm, seed, batch_edges = self.__call_group_epoch()
+        dev, bs = self.__eli.device, self.__batch_size
+        return LinkCallGroupIterator(self.__data, self.__sampler, batch_edges, perm.numel(), bs, self.__batches_per_group(bs),
+                                     self.__num_nodes, seed, self.__mode, dev, overlap=overlap)
+
+    def hetero_call_groups(self, overlap: bool = True):
+        """``call_groups()`` of a HETEROGENEOUS graph: the same epoch as ``iter(self)`` handed out as ``HeteroLinkCallGroup``
+        objects (``loader/link_call_group.py``) — a ``HeteroCallGroup`` (``x_dict``, ``layer_graph(j)``, ...) whose seeds are the
+        mini-batches' unique seed-edge endpoints of the seed edge type's two node types, with ONE ``edge_label_index`` whose rows
+        index the last layer's output of the source and of the destination type: what ``nn.link_bce_with_logits(h[src_t],
+        h[dst_t], grp.edge_label_index, grp.edge_label)`` and ``nn.EdgeDecoder`` take.  Refuses what ``call_groups()`` refuses."""
+        from .link_call_group import HeteroLinkCallGroupIterator
+        self.__refuse_call_groups("hetero_call_groups", None if self.__hetero else
+                                  "this graph is homogeneous: use call_groups()")
+        perm, seed, batch_edges = self.__call_group_epoch()
+        dev, bs = self.__eli.device, self.__batch_size
+        return HeteroLinkCallGroupIterator(self.__data, self.__sampler, batch_edges, perm.numel(), bs, self.__batches_per_group(bs),
+                                           self.__etype, self.__num_src, self.__num_dst, seed, self.__mode, dev, overlap=overlap)
+
+    def __refuse_call_groups(self, method, reason):
+        """NotImplementedError for what neither call-group method can do (``reason``: the caller's own refusal, first)."""
         smp = self.__sampler
-        reason = None
-        if self.__hetero:
-            reason = "heterogeneous graphs are not supported (link call groups are homogeneous)"
+        fanouts = [f for v in smp.fanout.values() for f in v] if isinstance(smp.fanout, dict) else smp.fanout
+        if reason is not None:
+            pass
         elif self.__raw:
             reason = "sampler-output mode (as_sampler_output=True) hands out SamplerOutput objects, not call groups"
         elif self.__time is not None or smp.temporal:
@@ -290,14 +324,18 @@ class LinkLoader:
             reason = "disjoint sampling is not supported"
         elif getattr(smp, "with_replacement", False):
             reason = "sampling with replacement is not supported"
-        elif not all(f > 0 for f in smp.fanout):
+        elif not all(f > 0 for f in fanouts):
             reason = "fan-out -1 (all neighbours) is not supported: the call-group walk needs positive fan-outs"
         elif not smp.call_groups_ok():
             reason = "this sampler configuration does not run on the call-group walk (biased sampling needs strictly positive weights and fan-outs <= 256)"
         elif not self.__eli.is_cuda:
             reason = "the call-group walk only exists on the GPU"
         if reason is not None:
-            raise NotImplementedError("LinkNeighborLoader.call_groups(): " + reason)
+            raise NotImplementedError(f"LinkNeighborLoader.{method}(): " + reason)
+
+    def __call_group_epoch(self):
+        """(order, random state, ``batch_edges(b, batch_seed)``) of one epoch: the loader's own per-batch recipe — the seed-edge
+        ids of mini-batch b, its endpoints with the negatives of the batch's generator, its labels."""
         perm, seed = self.__epoch()
         dev, bs = self.__eli.device, self.__batch_size
 
@@ -307,8 +345,7 @@ class LinkLoader:
             src_all, dst_all, n_neg, _ = self.__with_negatives(self.__eli[0, ix], self.__eli[1, ix], ix, gen)
             return self.__input_id[ix], src_all, dst_all, n_neg, self.__edge_label(ix, ix.numel(), n_neg)
 
-        return LinkCallGroupIterator(self.__data, smp, batch_edges, perm.numel(), bs, self.__batches_per_group(bs), self.__num_nodes,
-                                     seed, self.__mode, dev, overlap=overlap)
+        return perm, seed, batch_edges
 
     def __batches(self):
         dev = self.__eli.device
@@ -449,19 +486,8 @@ class LinkLoader:
         pad.pad_singles()
 
     def __emit_hetero(self, data, ix, inv_src, inv_dst, n_pos, n_neg):
-        dev = self.__eli.device
-        st = data[self.__etype]
-        st.edge_label_index = torch.stack([inv_src, inv_dst])
-        st.input_id = self.__input_id[ix]
-        st.batch_size = n_pos
-        if self.__mode is not None:
-            pos = torch.ones(n_pos, device=dev) if self.__label is None else (self.__label[ix] + 1)
-            st.edge_label = torch.cat([pos, torch.zeros(n_neg, device=dev, dtype=pos.dtype)])
-            if self.__mode == "triplet":
-                st.src_index, st.dst_pos_index, st.dst_neg_index = inv_src[:n_pos], inv_dst[:n_pos], inv_dst[n_pos:]
-        elif self.__label is not None:
-            st.edge_label = self.__label[ix]
-        return data
+        return hetero_link_data(data, self.__etype, inv_src, inv_dst, self.__input_id[ix], n_pos,
+                                self.__edge_label(ix, n_pos, n_neg), self.__mode)
 
     def __hetero_group(self, perm, seed, b0, g):
         """Batches b0 .. b0+g-1 (all full) of a heterogeneous graph as one call group (see ``__group``): the source
@@ -489,13 +515,8 @@ class LinkLoader:
             ud, dseg, dbatch, inv_dst = _batched_first_unique(dsts, self.__num_dst)
             lists = {src_t: (us, sseg, sbatch), dst_t: (ud, dseg, dbatch)}
         outs, ctx = smp.sample_seed_lists(lists, g, seed + b0)
-        views = _group_attribute_views(fs, ctx)
-        for j, (node, row, col, edge, nn, ne) in enumerate(outs):
-            out = HeteroSamplerOutput(node=node, row=row, col=col, edge=edge,
-                                      batch={t: node[t][:nn[t][0]] for t in lists},
-                                      num_sampled_nodes={k: torch.tensor(v) for k, v in nn.items()},
-                                      num_sampled_edges={k: torch.tensor(v) for k, v in ne.items()}, metadata=None)
-            yield self.__emit_hetero(build_hetero_data(fs, out, views, j), ixs[j], inv_src[j], inv_dst[j], bs, n_negs[j])
+        for j, data in enumerate(hetero_group_data(fs, outs, ctx, list(lists))):
+            yield self.__emit_hetero(data, ixs[j], inv_src[j], inv_dst[j], bs, n_negs[j])
 
     def __iter__(self):
         return self.__batches()

@@ -317,6 +317,11 @@ SYMBOLS = {
     "wgamd_pair_mlp_backward_workspace_bytes": (c_size_t, [c_int]),
     "wgamd_pair_mlp_backward_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                             c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    # row-wise first-appearance de-duplication (wg_rows_unique.hip)
+    "wgamd_rows_first_unique_supported": (c_int, [c_int64, c_int64, c_int64]),
+    "wgamd_rows_first_unique_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "wgamd_rows_first_unique": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_size_t, c_int, c_void_p]),
     # GCN layer (wg_gcn.hip)
     "wgamd_gcn_layer_supported": (c_int, [c_int, c_int]),
     "wgamd_gcn_layer_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,

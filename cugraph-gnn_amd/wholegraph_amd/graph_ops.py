@@ -46,3 +46,36 @@ def add_csr_self_loop(csr_row_ptr_tensor: torch.Tensor, csr_col_ptr_tensor: torc
     handles = [wrap_torch_tensor(t) for t in (csr_row_ptr_tensor, csr_col_ptr_tensor, new_row_ptr, new_col)]
     L.check(L.lib().csr_add_self_loop(*(h.c for h in handles), get_stream()), "csr_add_self_loop")
     return new_row_ptr, new_col
+
+
+_ROWS_UNIQUE_WS = {}   # (device index, stream) -> the reusable workspace of wgamd_rows_first_unique (its ticket stays zeroed)
+
+
+def rows_first_unique_supported(n_rows: int, row_len: int, n_ids: int) -> bool:
+    """The domain of the row-wise de-duplication kernel (``wgamd_rows_first_unique_supported``, include/wgamd_ext.h)."""
+    return bool(L.lib().wgamd_rows_first_unique_supported(int(n_rows), int(row_len), int(n_ids)))
+
+
+def rows_first_unique(ends: torch.Tensor, n_ids: int):
+    """Row-wise first-appearance de-duplication of ``ends`` int64 [G, S] (device, values in [0, n_ids)) in two launches, with no
+    host synchronisation (``wgamd_rows_first_unique``): ``(uniq int64 [G S], seg int32 [G + 1], batch int32 [G S], local int64
+    [G, S])`` — row g's distinct values in order of first position from ``seg[g]`` on, the row of every live entry, the position
+    of every element in its row's list; both tails are zero.  Outside ``rows_first_unique_supported`` this is an error."""
+    assert ends.dim() == 2 and ends.dtype == torch.int64 and ends.is_cuda, "ends: int64 [G, S] on the device"
+    G, S = ends.shape
+    if not rows_first_unique_supported(G, S, n_ids):
+        raise ValueError(f"rows_first_unique: [{G}, {S}] with {n_ids} ids is outside the kernel's domain")
+    ends = ends.contiguous()
+    dev, lib, stream = ends.device, L.lib(), get_stream()
+    uniq = torch.empty(G * S, dtype=torch.int64, device=dev)
+    seg = torch.empty(G + 1, dtype=torch.int32, device=dev)
+    batch = torch.empty(G * S, dtype=torch.int32, device=dev)
+    local = torch.empty((G, S), dtype=torch.int64, device=dev)
+    need = lib.wgamd_rows_first_unique_workspace_bytes(G, S)
+    key = (dev.index, stream.value)
+    ws = _ROWS_UNIQUE_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _ROWS_UNIQUE_WS[key] = torch.zeros(need, dtype=torch.uint8, device=dev)
+    L.check(lib.wgamd_rows_first_unique(ends.data_ptr(), G, S, int(n_ids), uniq.data_ptr(), seg.data_ptr(), batch.data_ptr(),
+                                        local.data_ptr(), ws.data_ptr(), ws.numel(), 1, stream), "wgamd_rows_first_unique")
+    return uniq, seg, batch, local

@@ -835,6 +835,27 @@ wholememory_error_code_t wgamd_pair_mlp_backward_f32(float* hidden_io, int64_t l
                                                      void* workspace, size_t workspace_bytes, int workspace_is_zeroed,
                                                      void* stream);
 
+/* ---- Row-wise first-appearance de-duplication (csrc/wg_rows_unique.hip) --------------------------------------------------------
+ * The endpoints of a link call group's seed edges, ends int64 [n_rows, row_len] (contiguous; one row per mini-batch, values
+ * promised in [0, n_ids), id 0 a real id), de-duplicated row by row in order of first position:
+ *   uniq  int64 [n_rows row_len]: row g's distinct values, in order of first position, back to back from seg[g]; 0 from seg[n_rows] on
+ *   seg   int32 [n_rows + 1]:     prefix sum of the rows' distinct counts
+ *   batch int32 [n_rows row_len]: batch[seg[g] + r] = g; 0 from seg[n_rows] on
+ *   local int64 [n_rows, row_len]: local[g, s] = position of ends[g, s] in row g's list
+ * Two launches, no host synchronisation, no allocation; every first position is a minimum, so the result does not depend on
+ * scheduling.  wgamd_rows_first_unique_supported: n_rows >= 1, 1 <= row_len <= WGAMD_ROWS_FIRST_UNIQUE_MAX_S (one workgroup's
+ * LDS table: 2 row_len slots of 8 bytes, 128 KiB of the CU's 160 KiB at the bound), n_rows row_len < 2^31, 1 <= n_ids <= 2^40
+ * (an id and a position share a 64-bit word, 40 + 24 bits).  Whatever ends holds, nothing is written outside the outputs and the
+ * workspace: a value outside [0, 2^40) is de-duplicated by its low 40 bits.  workspace: wgamd_rows_first_unique_workspace_bytes
+ * bytes; its ticket (the first 256 bytes after rounding the pointer up to 256) is zeroed by the call unless
+ * workspace_is_zeroed, and left zeroed. */
+#define WGAMD_ROWS_FIRST_UNIQUE_MAX_S 8192
+int wgamd_rows_first_unique_supported(int64_t n_rows, int64_t row_len, int64_t n_ids);
+size_t wgamd_rows_first_unique_workspace_bytes(int64_t n_rows, int64_t row_len);
+wholememory_error_code_t wgamd_rows_first_unique(const int64_t* ends, int64_t n_rows, int64_t row_len, int64_t n_ids, int64_t* uniq,
+                                                 int* seg, int* batch, int64_t* local, void* workspace, size_t workspace_bytes,
+                                                 int workspace_is_zeroed, void* stream);
+
 /* ---- GCN layer (csrc/wg_gcn.hip): torch_geometric.nn.GCNConv over a sampled hop ---------------------------------------------
  * The model of the reference's headline cugraph-pyg example (python/cugraph-pyg/cugraph_pyg/examples/gcn_dist_mnmg.py):
  *   agg[i]  = s_i ( sum_{e = (j -> i), not a loop} w_e d_j X[j]  +  [loops] loopw_i d_self X[self_rows[i]] )

@@ -2,11 +2,13 @@
 """The link-prediction head (`nn.link_bce_with_logits`, csrc/wg_link.hip) against its torch formulation, on the pairs of one
 products-shaped link call group (bench.py's RMAT graph, fan-out [25, 10], 1024 seed edges + 1024 negatives per mini-batch,
 G = 188 mini-batches: P = 188 * 2048 pairs over the group's seed rows), C = 64 and 256, timed with HIP events after warm-up:
-forward and forward + backward through `nn`, the same as torch ops, and `_batched_first_unique` per group.  GB by the byte
+forward and forward + backward through `nn`, the same as torch ops, and the row-wise endpoint de-duplication per group — the
+torch formulation and the kernel of csrc/wg_rows_unique.hip side by side, at [G, 4096] and [G, 2048].  GB by the byte
 model of the BCE forward,
     reads P (8 C + 16 + 4)  +  writes 4 P
 (two rows, two int64 indices and a label per pair; the coefficient), and its share of the 8 TB/s HBM peak.  Then the example's
-loop (examples/sage_link_call_groups.py) in sampled edges/s through `call_groups()` against `for batch in loader`, same run.
+loop (examples/sage_link_call_groups.py) in sampled edges/s through `call_groups()` against `for batch in loader`, same run, and
+the heterogeneous example's (examples/hetero_link_call_groups.py) through `hetero_call_groups()` against its `--per-batch` loop.
 Prints one JSON line.
 
     python tools/bench_link_head.py [--iters 20] [--nodes 20000]
@@ -146,6 +148,40 @@ def products_link_group(group):
     return next(iter(loader.call_groups())), loader, g
 
 
+def unique_timings(group, S, V, iters, gen):
+    """The row-wise endpoint de-duplication of one call group at [group, S] (ids below V): the torch formulation and the kernel
+    (csrc/wg_rows_unique.hip) side by side — three rounds of `iters` timed calls each, alternating, after their warm-up; the
+    median round and the spread.  Bytes the kernel moves: reads 8 G S, writes 8 G S (local) + 8 U (lists) + 4 G, then the
+    compaction reads 8 U + 4 G and writes 12 G S (uniq and batch with their zero tails)."""
+    from cugraph_pyg_amd.loader.link_loader import _batched_first_unique_torch
+    from wholegraph_amd import graph_ops
+    ends = torch.randint(0, V, (group, S), generator=gen, device="cuda")
+    want, got = _batched_first_unique_torch(ends, V), graph_ops.rows_first_unique(ends, V)
+    assert all(torch.equal(a, b) for a, b in zip(want, got)), "the kernel and the torch formulation disagree"
+    rounds = {"torch": [], "kernel": []}
+    for _ in range(3):
+        rounds["torch"].append(timed(lambda: _batched_first_unique_torch(ends, V), iters))
+        rounds["kernel"].append(timed(lambda: graph_ops.rows_first_unique(ends, V), iters))
+    U = int(want[1][-1])
+    out = {"shape": [group, S], "unique": U, "kernel_GB": round((8 * group * S * 2 + 16 * U + 8 * group + 12 * group * S) / 1e9, 4)}
+    for k, v in rounds.items():
+        v = sorted(v)
+        out.update({k + "_ms": round(v[1], 4), k + "_ms_min_max": [round(v[0], 4), round(v[-1], 4)]})
+    return out
+
+
+def hetero_example_loops():
+    """Sampled edges/s of the last of two epochs of examples/hetero_link_call_groups.py at its defaults: through
+    `hetero_call_groups()` with the one-kernel MLP head, and through `for batch in loader` with torch ops."""
+    import hetero_link_call_groups as ex
+    out = {}
+    for name, extra in (("hetero_call_groups", []), ("per_batch", ["--per-batch"])):
+        ex.main(["--epochs", "2"] + extra)
+        out[name + "_sampled_edges_per_s"] = round(ex.LAST_EPOCH["sampled_edges_per_s"], 1)
+        out[name + "_epoch_s"] = round(ex.LAST_EPOCH["seconds"], 4)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--group", type=int, default=188, help="mini-batches per call group")
@@ -153,16 +189,14 @@ def main():
     ap.add_argument("--nodes", type=int, default=20_000, help="vertices of the example's planted-partition graph")
     args = ap.parse_args()
     import bench
-    from cugraph_pyg_amd.loader.link_loader import _batched_first_unique
-    dev = torch.device("cuda")
     V, B = bench.WORKLOADS["products"][0], bench.BATCH
     grp, loader, g = products_link_group(args.group)
     heads = [head_timings(grp, C, args.iters, g) for C in (64, 256)]
-    ends = torch.randint(0, V, (args.group, 4 * B), generator=g, device=dev)
-    t_unique = timed(lambda: _batched_first_unique(ends, V), args.iters)
     del grp, loader
-    print(json.dumps({"metric": "link_head", "group": args.group, "heads": heads, "batched_first_unique_ms_per_group": round(t_unique, 4),
-                      "example": example_loops(args.nodes)}))
+    # [G, 4 B]: both endpoints of B positives + B negatives in one list; [G, 2 B]: one endpoint type of a bipartite group
+    unique = [unique_timings(args.group, S, V, args.iters, g) for S in (4 * B, 2 * B)]
+    print(json.dumps({"metric": "link_head", "group": args.group, "heads": heads, "batched_first_unique": unique,
+                      "example": example_loops(args.nodes), "hetero_example": hetero_example_loops()}))
 
 
 if __name__ == "__main__":
