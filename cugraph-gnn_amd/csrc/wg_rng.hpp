@@ -120,6 +120,36 @@ struct Pcg32 {
     jump_table(subsequence + extra_draws);
   }
 
+  // The same jump in two parts, for a caller that positions several streams whose numbers differ only in their low byte
+  // (the draws of one seed: streams 32 i .. 32 i + 31).  jump_high(n) composes the entries of bytes 1..3 of n once; the
+  // constructor finishes with the entry of byte 0:  t[0][c0] o (t[1][c1] o t[2][c2] o t[3][c3]).  Composing affine maps is
+  // associative modulo 2^64 and an entry skipped for c == 0 is the identity, so the state equals jump_table's bit for bit.
+  static __device__ __forceinline__ PcgJump jump_high(uint32_t n)
+  {
+    PcgJump h = g_pcg_jump.t[1][(n >> 8) & 255u];
+#pragma unroll
+    for (int k = 2; k < 4; k++) {
+      const uint32_t c = (n >> (8 * k)) & 255u;
+      if (c) {
+        const PcgJump m = g_pcg_jump.t[k][c];
+        h.s             = h.s * m.a + m.s;
+        h.a             = h.a * m.a;
+      }
+    }
+    return h;
+  }
+  // Same generator as Pcg32(seed, subsequence, table_tag{}) given high = jump_high(subsequence)
+  struct split_tag {};
+  __device__ __forceinline__ Pcg32(uint64_t seed, uint32_t subsequence, split_tag, const PcgJump& high)
+  {
+    inc       = ((uint64_t)subsequence << 1u) | 1u;
+    state     = (inc + seed) * kMult + inc;
+    PcgJump j = g_pcg_jump.t[0][subsequence & 255u];
+    j.s       = j.s * high.a + high.s;
+    j.a       = j.a * high.a;
+    state     = j.a * state + inc * j.s;
+  }
+
   __host__ __device__ __forceinline__ int32_t next_i31() { return (int32_t)(next_u32() & 0x7fffffffu); }
   __host__ __device__ __forceinline__ uint64_t next_u64()
   {

@@ -8,7 +8,11 @@
 // reference's host oracle (cpp/tests/wholegraph_ops/graph_sampling_test_utils.cu:312-401); the
 // way it is computed is not the reference's:
 //
-//  * M <= 32 (every fan-out of the BASELINE configs): the reference runs one 32-thread block per
+//  * M <= 32 in the no-sync walk (the hops of a call group): for the fan-outs 5 / 10 / 15 / 25 one seed per LANE, its M
+//    draws and the Fisher-Yates table in registers, the picks handed over in LDS to the lanes that load and store them
+//    in output order (sample_uniform_lane_kernel);
+//    other fan-outs and the vertex-grouped order use lane groups as wide as the fan-out (sample_uniform_multi_kernel).
+//  * M <= 32 in the ABI op (every fan-out of the BASELINE configs): the reference runs one 32-thread block per
 //    seed = half an idle wave64.  Here a wave carries TWO seeds, one per 32-lane half; lane t
 //    draws r_t from PCG stream (i*32+t) — the stream numbering the reference fixes — and the
 //    sequential Fisher-Yates table is resolved in registers with wave ballots: step t needs
@@ -512,6 +516,126 @@ sample_uniform_multi_kernel(const ColT* __restrict__ col, dev_count n_, int M_rt
   for (int k = 0; k < K; k++)
     if (on[k]) emit<ColT>(dst, src_lid, edge_gid, (int64_t)base[k] + hl, v[k], i[k], start[k] + a[k]);
   }   // chunk
+}
+
+// ---- the same hop with ONE SEED PER LANE: the walk's default for the fan-outs a kernel is built for ---------------------
+// In the lane-group layout above everything that is per seed is done once per lane of the group: the row record is loaded
+// M times, the part of the PCG jump that depends on the seed alone (bytes 1..3 of the stream number 32 i_local + t) is
+// composed M times, and the Fisher-Yates steps of a seed find each other through ds_bpermute (the all-pairs loop and the
+// pointer jumping).  Here lane l of a wave owns seed 64 w + l outright: one coalesced load per row field and wave, the high
+// bytes of the jump composed once (Pcg32::jump_high), and the M draws, the M (position, value) records of the swap table and
+// the M picks in registers — step t looks its two positions up with a fully unrolled compare / select chain over the t
+// earlier records, no cross-lane traffic, every instruction serving 64 seeds.  The wave then has its 64 M picks in flight at
+// once.  Same draws (first next_i31() of stream 32 i_local + t), same Fisher-Yates, same output positions: bit-identical.
+// Measured on the products hop 2 (1.8 M seeds x fan-out 10; profiles/r11): 2.7x fewer VALU instructions than the lane groups
+// (20 M against 54 M per launch), and yet the launch with every lane loading and storing its own picks was no faster (270
+// against 265 us): what bounds it is not VALU issue but the picks — the same launch without the pick loads takes 106 us.
+// With the outputs staged through LDS it took 241 us, with the picks themselves handed over in LDS (below) 231 against the
+// lane groups' 253 in the same job; the hop-1 launch (fan-out 25, 0.19 M seeds) goes from 57 to 27 us.  64 VGPRs at M = 10
+// (8 waves per SIMD, 14.5 KB of LDS per workgroup), 166 at M = 25 (3 waves); no scratch.
+template <typename SeedT, typename ColT, int M>
+__global__ void __launch_bounds__(256)
+sample_uniform_lane_kernel(const ColT* __restrict__ col, dev_count n_, rng_plan rng, const int* __restrict__ offsets,
+                           ColT* __restrict__ dst, int* __restrict__ src_lid, int64_t* __restrict__ edge_gid,
+                           const int64_t* __restrict__ row_start, const int* __restrict__ row_deg)
+{
+  const int n    = n_.get();
+  const int lane = threadIdx.x & 63;
+  // bounded grid striding over the live seeds, 64 consecutive seeds per wave (see sample_uniform_multi_kernel)
+  for (int64_t w = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64; w < n; w += (int64_t)gridDim.x * 256) {
+    const int i = (int)min(w + lane, (int64_t)n);
+    int N = 0, base = 0, batch = 0, i_local = i;
+    int64_t start = 0;
+    if (i < n) {
+      start = row_start[i];
+      N     = row_deg[i];
+      base  = offsets[i];
+      if (rng.target_batch) {
+        batch   = rng.target_batch[i];
+        i_local = i - rng.target_seg[batch];
+      }
+    }
+    int a[M];
+#pragma unroll
+    for (int t = 0; t < M; t++) a[t] = t;   // rows of up to M neighbours are copied whole
+    const bool pick = N > M;
+    if (__ballot(pick) != 0ull && pick) {   // (the ballot is wave-uniform: a wave of short rows skips the draws)
+      const uint64_t random_seed = rng.seeds_dev ? rng.seeds_dev[rng.target_batch ? batch : 0] : rng.seed;
+      const bool tabled          = i_local < (1 << 26);   // stream numbers below 2^31: the table jump
+      PcgJump high{1, 0};
+      if (tabled) high = Pcg32::jump_high((uint32_t)i_local * 32u);
+      // Fisher-Yates, a_t = Q[j_t]; Q[j_t] = Q[N-t-1]: step t records (pos_t = j_t, val_t = what it found at N-t-1), and what
+      // a step finds at a position is the value of the latest earlier record of that position, else the position itself
+      int pos[M], val[M];
+#pragma unroll
+      for (int t = 0; t < M; t++) {
+        uint32_t r;
+        if (tabled) {
+          Pcg32 g(random_seed, (uint32_t)i_local * 32u + t, Pcg32::split_tag{}, high);   // stream layout: 32 per seed, always
+          r = (uint32_t)g.next_i31();
+        } else {
+          Pcg32 g(random_seed, stream_id(i_local, 32, t));
+          r = (uint32_t)g.next_i31();
+        }
+        const int j    = (int)(r % (uint32_t)(N - t));
+        const int tail = N - t - 1;
+        int at_j = j, at_tail = tail;
+#pragma unroll
+        for (int s = 0; s < t; s++) {
+          at_j    = pos[s] == j ? val[s] : at_j;
+          at_tail = pos[s] == tail ? val[s] : at_tail;
+        }
+        a[t]   = at_j;
+        pos[t] = j;
+        val[t] = at_tail;
+      }
+    }
+    const int cnt = N > M ? M : N;   // (0 for the lanes past the live count)
+    // The wave's outputs are one contiguous stretch of dst / src_lid (consecutive seeds, offsets = the running count), so the
+    // picks change hands through LDS: every lane posts its M row positions, then lane l takes the output positions
+    // 64 k + l.  The M picks of a seed are then loaded by neighbouring lanes in ONE instruction (a short row is one line),
+    // and every store instruction writes whole lines — a lane's own M positions are 4 M bytes from its neighbour's, per-lane
+    // stores touch every line of the stretch M times over.
+    __shared__ int s_a[4][64 * M];
+    __shared__ unsigned char s_l[4][64 * M];
+    __shared__ int64_t s_start[4][64];
+    const int wv    = threadIdx.x >> 6;
+    const int last  = (int)min((int64_t)63, (int64_t)n - 1 - w);   // last live lane (wave-uniform)
+    const int wbase = __shfl(base, 0, 64);
+    const int total = min(__shfl(base + cnt, last, 64) - wbase, 64 * M);
+    const int rel   = base - wbase;
+    s_start[wv][lane] = start;
+#pragma unroll
+    for (int t = 0; t < M; t++)
+      if (t < cnt && (unsigned)(rel + t) < 64u * M) {
+        s_a[wv][rel + t] = a[t];
+        s_l[wv][rel + t] = (unsigned char)lane;
+      }
+    // (one wave writes and reads its own part: a wave barrier orders it, the trip counts of the waves differ)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    int64_t at[M];
+    int owner[M];
+    ColT v[M];
+#pragma unroll
+    for (int k = 0; k < M; k++) {
+      const int idx = k * 64 + lane;
+      owner[k] = 0, at[k] = 0, v[k] = (ColT)0;
+      if (idx < total) {
+        owner[k] = s_l[wv][idx] & 63;
+        at[k]    = s_start[wv][owner[k]] + s_a[wv][idx];
+        v[k]     = col_at<ColT>(col, at[k]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < M; k++) {
+      const int idx = k * 64 + lane;
+      if (idx < total) emit<ColT>(dst, src_lid, edge_gid, (int64_t)wbase + idx, v[k], (int)w + owner[k], at[k]);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();   // (the next trip writes the same LDS)
+  }
 }
 
 // ---- 32 < M <= 1024: one workgroup per seed ------------------------------------------------
@@ -1587,8 +1711,10 @@ void uniform_launch(const int64_t* row_ptr, const ColT* col, const SeedT* seeds,
   const int cap = n.host;
   if (cap <= 0) return;
   if (M > 0 && M <= 32 && row_start != nullptr) {
-    // the no-sync walk: K seeds per lane group (WGAMD_SAMPLE_K = 1 | 2 | 4 | 8, default 4), optionally in vertex-grouped
-    // order (see loc_rec): two short launches build the records, the sampling kernel walks them
+    // the no-sync walk.  List order (the default) and a fan-out of 5 / 10 / 15 / 25: one seed per lane
+    // (sample_uniform_lane_kernel).  Otherwise lane groups with K seeds per group (WGAMD_SAMPLE_K = 1 | 2 | 4, default 4; it
+    // means nothing to the lane kernel), optionally in vertex-grouped order (see loc_rec): two short launches build the
+    // records, the sampling kernel walks them
     static const int K = [] {
       const char* e = getenv("WGAMD_SAMPLE_K");
       const int k   = e ? atoi(e) : 4;
@@ -1613,6 +1739,17 @@ void uniform_launch(const int64_t* row_ptr, const ColT* col, const SeedT* seeds,
   } while (0)
     // group width = the fan-out where a kernel is built for it (the BASELINE fan-outs), else the next of 8 / 16 / 32
     static const bool exact = getenv("WGAMD_SAMPLE_EXACT_WIDTH") == nullptr || atoi(getenv("WGAMD_SAMPLE_EXACT_WIDTH")) != 0;
+    // list order: one seed per lane for the fan-outs it is built for (WGAMD_SAMPLE_EXACT_WIDTH=0 keeps the lane groups)
+#define WG_LANE(MM)                                                                                                   \
+  sample_uniform_lane_kernel<SeedT, ColT, MM>                                                                         \
+    <<<(int)std::min<int64_t>(ceil_div((int64_t)cap, 256), kWalkGrid), 256, 0, stream>>>(col, n, random_seed, offsets, dst, lid, \
+                                                                                         gid, row_start, row_deg)
+    const bool lane_layout = exact && recs == nullptr;
+    if (lane_layout && M == 5) WG_LANE(5);
+    else if (lane_layout && M == 10) WG_LANE(10);
+    else if (lane_layout && M == 15) WG_LANE(15);
+    else if (lane_layout && M == 25) WG_LANE(25);
+    else
 #define WG_EXACT true
     if (exact && M == 5) WG_MULTI_K(5);
     else if (exact && M == 10) WG_MULTI_K(10);
@@ -1628,6 +1765,7 @@ void uniform_launch(const int64_t* row_ptr, const ColT* col, const SeedT* seeds,
 #undef WG_EXACT
 #undef WG_MULTI_K
 #undef WG_MULTI
+#undef WG_LANE
     WG_HIP_CHECK(hipGetLastError());
     return;
   }
