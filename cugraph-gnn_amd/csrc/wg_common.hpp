@@ -329,6 +329,34 @@ void weighted_sample_enqueue(const int64_t* row_ptr, const void* col, bool col64
                              const void* seeds, bool seeds64, dev_count n, int M, rng_plan random_seed, const int* offsets,
                              int* big_list, uint32_t* slab, int64_t slab_len, void* dst, int* src_lid,
                              int64_t* edge_gid, hipStream_t stream);
+// TEMPORAL hop: candidate slot s of a frontier row reached at time t_v qualifies when `comparison` holds between csr_time[s]
+// and t_v (1: strictly increasing, t_e > t_v; 2: monotonically increasing, >=; 3: strictly decreasing, <; 4: monotonically
+// decreasing, <=) and its weight, rounded to float, is positive.  The weighted kernels draw with the EFFECTIVE weight (the
+// weight, or 1 without weights, of a qualifying slot; 0 otherwise): every slot still consumes its draws, so the keys are
+// the ones a call of the biased sampler over an array of effective weights produces.
+struct time_filter {
+  const int64_t* csr_time;        // [slots]
+  const int64_t* frontier_time;   // [frontier] time every sampled row was reached at
+  int comparison;
+  __device__ __forceinline__ int64_t row_time(int row) const { return frontier_time[row]; }
+  __device__ __forceinline__ bool passes(int64_t slot, int64_t t_v) const
+  {
+    const int64_t t_e = csr_time[slot];
+    return comparison == 1 ? t_e > t_v : comparison == 2 ? t_e >= t_v : comparison == 3 ? t_e < t_v : t_e <= t_v;
+  }
+  template <typename WeightT>
+  __device__ __forceinline__ float weight(const WeightT* w, int64_t slot, int64_t t_v) const
+  {
+    const float x = w ? (float)w[slot] : 1.0f;
+    return (passes(slot, t_v) && x > 0.f) ? x : 0.f;
+  }
+};
+// the picks of weighted_sample_enqueue drawn with the effective weights of `tf` (`weights` may be NULL: 1 per qualifying
+// slot): min(row length, M) picks per row at `offsets`, non-qualifying ones included — the caller drops those
+void weighted_temporal_sample_enqueue(const int64_t* row_ptr, const void* col, bool col64, const void* weights, bool weights64,
+                                      const void* seeds, bool seeds64, dev_count n, int M, rng_plan random_seed,
+                                      const int* offsets, int* big_list, uint32_t* slab, int64_t slab_len, void* dst,
+                                      int* src_lid, int64_t* edge_gid, time_filter tf, hipStream_t stream);
 // renumbering: table of `slots` (power of two >= 2*(T.host+E.host)) entries, slot_of[T.host+E.host],
 // rank[E.host+1], scan_tmp[scan_tmp_ints(E.host+1)].  unique_out may be NULL for `prepare`.
 int64_t append_unique_slots(int64_t capacity);

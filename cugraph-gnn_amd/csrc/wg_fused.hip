@@ -20,12 +20,15 @@ namespace {
 inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct hop_workspace {
-  size_t cnt, scan_tmp, nbr, keys, minpos, slot_of, rank, big_list, slab, row_start, row_deg, loc_hist, total;
+  size_t cnt, scan_tmp, nbr, keys, minpos, slot_of, rank, big_list, slab, row_start, row_deg, loc_hist, pad_off, pad_nbr, pad_gid,
+    total;
   int64_t slots, slab_len;
 };
 
 // max_row_len > 0: biased hop — also the long-row list and the key slabs of the persistent workgroups
-hop_workspace plan(int64_t target_cap, int64_t edge_cap, size_t id_bytes, bool batched, int64_t max_row_len = 0)
+// temporal: also the picks before the time filter (min(row length, M) per row: offsets, neighbours, CSR slots)
+hop_workspace plan(int64_t target_cap, int64_t edge_cap, size_t id_bytes, bool batched, int64_t max_row_len = 0,
+                   bool temporal = false)
 {
   hop_workspace w{};
   size_t off = 0;
@@ -51,6 +54,11 @@ hop_workspace plan(int64_t target_cap, int64_t edge_cap, size_t id_bytes, bool b
     w.big_list = take(sizeof(int) * (size_t)weighted_list_ints(target_cap));
     w.slab     = take(sizeof(uint32_t) * (size_t)kWeightedBlocks * (size_t)w.slab_len);
   }
+  if (temporal) {
+    w.pad_off = take(sizeof(int) * (size_t)(target_cap + 1));
+    w.pad_nbr = take(id_bytes * (size_t)edge_cap);
+    w.pad_gid = take(sizeof(int64_t) * (size_t)edge_cap);
+  }
   w.total        = off;
   return w;
 }
@@ -73,6 +81,11 @@ struct hop_args {
   const void* csr_weight  = nullptr;
   bool weight64           = false;
   int64_t max_row_len     = 0;
+  // temporal hop (PyG-style walk, on the biased path whether or not weights are given): null csr_time = not temporal
+  const int64_t* csr_time       = nullptr;
+  const int64_t* frontier_time  = nullptr;
+  int64_t* frontier_time_out    = nullptr;
+  int comparison                = 0;
   // PyG-style walk: the sampled list (frontier) differs from the renumber target list; null = same list
   const void* sample_targets = nullptr;
   const int* n_sample_dev    = nullptr;
@@ -99,6 +112,82 @@ struct hop_args {
   hipStream_t stream;
 };
 
+// ---- temporal hop: the time filter between sampling and renumbering -----------------------------------------------------------
+// The weighted kernels leave min(row length, M) <= 256 picks per frontier row at pad_off (CSR order inside a row), drawn with
+// the effective weights; the picks that do not qualify (a row with fewer than M qualifying slots) are dropped here BY THE
+// PREDICATE — time against the row's reach time, weight > 0 — and never by the key's value: a qualifying slot can have the
+// key -inf.  Two passes of 16 lanes per row around one scan: survivors per row, then the survivors compacted (neighbour, row,
+// CSR slot) at the scanned offsets.  A candidate's time is read once when it is keyed and once per pick here.
+template <typename WeightT>
+__global__ void __launch_bounds__(256)
+temporal_count_kernel(const int* __restrict__ pad_off, const int64_t* __restrict__ pad_gid, const WeightT* __restrict__ weight,
+                      time_filter tf, dev_count n_, int* __restrict__ cnt)
+{
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = (int)(t >> 4), hl = (int)(t & 15);
+  if (i >= n_.host) return;
+  const int n_live = n_.get();
+  if (i >= n_live) {   // capacity slack: zero the rest of the live scan tile only (exclusive_scan_i32)
+    if (hl == 0 && i < (n_live / kScanTile + 1) * kScanTile) cnt[i] = 0;
+    return;
+  }
+  const int s = pad_off[i], e = pad_off[i + 1];
+  const int64_t t_v = tf.row_time(i);
+  int c = 0;
+  for (int j = s + hl; j < e; j += 16) c += tf.weight(weight, pad_gid[j], t_v) > 0.f ? 1 : 0;
+#pragma unroll
+  for (int d = 8; d >= 1; d >>= 1) c += __shfl_xor(c, d, 16);
+  if (hl == 0) cnt[i] = c;
+}
+
+template <typename WeightT, typename NbrT>
+__global__ void __launch_bounds__(256)
+temporal_compact_kernel(const int* __restrict__ pad_off, const NbrT* __restrict__ pad_nbr, const int64_t* __restrict__ pad_gid,
+                        const WeightT* __restrict__ weight, time_filter tf, dev_count n_, const int* __restrict__ offsets,
+                        NbrT* __restrict__ nbr, int* __restrict__ center_row, int64_t* __restrict__ edge_gid, int edge_cap)
+{
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int i = (int)(t >> 4), hl = (int)(t & 15);
+  if (i >= n_.get()) return;
+  const int lane = threadIdx.x & 63;
+  const int s = pad_off[i], e = pad_off[i + 1];
+  const int64_t t_v = tf.row_time(i);
+  int out = offsets[i];
+  for (int j0 = s; j0 < e; j0 += 16) {   // (the same trips in the 16 lanes of a row)
+    const int j       = j0 + hl;
+    const int64_t gid = j < e ? pad_gid[j] : 0;
+    const bool keep   = j < e && tf.weight(weight, gid, t_v) > 0.f;
+    const uint32_t m  = (uint32_t)(__ballot(keep) >> (lane & ~15)) & 0xffffu;
+    const int at      = out + __popc(m & ((1u << hl) - 1u));
+    if (keep && at < edge_cap) {
+      nbr[at]        = pad_nbr[j];
+      center_row[at] = i;
+      edge_gid[at]   = gid;
+    }
+    out += __popc(m);
+  }
+}
+
+// Reach time of the next frontier: frontier_out is ordered by (batch, first appearance), and the edge that put a vertex
+// there is the one the renumbering found FIRST for its id (slot_of[T + e] == T + e, the test of the three emit kernels in
+// wg_append_unique.hip) = the lowest position in the hop's edge list.  Its entry is the edge's neighbour_local minus the
+// batch's first new local id; every entry is written by exactly that one edge.
+__global__ void __launch_bounds__(256)
+frontier_time_kernel(const int* __restrict__ slot_of, const int* __restrict__ n_targets_dev, const int* __restrict__ n_edges_dev,
+                     const int* __restrict__ center_row, const int* __restrict__ frontier_batch,
+                     const int* __restrict__ neighbor_local, const int* __restrict__ f_out_seg, const int* __restrict__ f_out_local0,
+                     const int64_t* __restrict__ edge_gid, const int64_t* __restrict__ csr_time, int64_t* __restrict__ time_out,
+                     int edge_cap)
+{
+  const int T = *n_targets_dev, E = min(*n_edges_dev, edge_cap);
+  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += gridDim.x * blockDim.x) {
+    if (slot_of[T + e] != T + e) continue;
+    const int b = frontier_batch[center_row[e]];
+    const int f = f_out_seg[b] + neighbor_local[e] - f_out_local0[b];
+    if ((unsigned)f < (unsigned)edge_cap) time_out[f] = csr_time[edge_gid[e]];
+  }
+}
+
 void run_hop(hop_args a)
 {
   WG_REQUIRE_INPUT(a.id_dtype == WHOLEMEMORY_DT_INT || a.id_dtype == WHOLEMEMORY_DT_INT64, "id dtype must be INT|INT64");
@@ -115,8 +204,17 @@ void run_hop(hop_args a)
   const bool col64   = i64 && !a.col32;   // width of the column array = width of the sampled neighbour list
   const bool batched = a.bv.target_batch != nullptr;
   WG_REQUIRE_INPUT(a.csr_weight == nullptr || a.max_row_len > 0, "a biased hop needs max_row_len (the graph's maximum degree)");
+  const bool temporal = a.csr_time != nullptr;
+  WG_REQUIRE_INPUT(!temporal || (a.frontier_time && a.frontier_time_out && a.comparison >= 1 && a.comparison <= 4),
+                   "a temporal hop needs frontier_time, frontier_time_out and a comparison in 1..4");
+  WG_REQUIRE_INPUT(!temporal || (a.M <= 256 && a.max_row_len > 0 && a.edge_gid && a.center_row),
+                   "a temporal hop needs a fan-out <= 256, max_row_len (the graph's maximum degree) and edge_gid");
+  WG_REQUIRE_INPUT(!temporal || (batched && a.bv.sample_batch && a.bv.frontier_out && a.bv.frontier_seg_out &&
+                                 a.bv.frontier_local0_out && a.bv.neighbor_local_out),
+                   "a temporal hop is a hop of the PyG-style call-group walk");
   // (the plan is sized for the id width whatever the column width: a caller need not know which one a hop will take)
-  hop_workspace w    = plan(std::max(a.target_cap, s_cap), a.edge_cap, i64 ? 8 : 4, batched, a.csr_weight ? a.max_row_len : 0);
+  hop_workspace w    = plan(std::max(a.target_cap, s_cap), a.edge_cap, i64 ? 8 : 4, batched,
+                            (a.csr_weight || temporal) ? a.max_row_len : 0, temporal);
   WG_REQUIRE_INPUT(a.workspace_bytes >= w.total, "workspace too small: need %zu bytes", w.total);
   WG_REQUIRE_INPUT((reinterpret_cast<uintptr_t>(a.workspace) & 255) == 0, "workspace must be 256-byte aligned");
   char* base    = static_cast<char*>(a.workspace);
@@ -131,7 +229,37 @@ void run_hop(hop_args a)
 
   dev_count T{(int)a.target_cap, a.n_targets_dev};
   dev_count S{(int)s_cap, s_n_dev};
-  if (a.csr_weight != nullptr) {
+  if (temporal) {
+    // count + scan + the exact weighted kernels into the padded scratch, then count + scan + compact of the survivors
+    int* big_list    = reinterpret_cast<int*>(base + w.big_list);
+    int* pad_off     = reinterpret_cast<int*>(base + w.pad_off);
+    void* pad_nbr    = base + w.pad_nbr;
+    int64_t* pad_gid = reinterpret_cast<int64_t*>(base + w.pad_gid);
+    const time_filter tf{a.csr_time, a.frontier_time, a.comparison};
+    weighted_count_enqueue(a.csr_row_ptr, s_targets, i64, S, a.M, cnt, big_list, st);
+    exclusive_scan_i32(cnt, pad_off, s_cap, scan_tmp, st, s_n_dev);
+    weighted_temporal_sample_enqueue(a.csr_row_ptr, a.csr_col, col64, a.csr_weight, a.weight64, s_targets, i64, S, a.M, a.rng,
+                                     pad_off, big_list, reinterpret_cast<uint32_t*>(base + w.slab), w.slab_len, pad_nbr, nullptr,
+                                     pad_gid, tf, st);
+    const int grid = (int)ceil_div(s_cap * 16, (int64_t)256);
+    if (a.weight64)
+      temporal_count_kernel<double><<<grid, 256, 0, st>>>(pad_off, pad_gid, static_cast<const double*>(a.csr_weight), tf, S, cnt);
+    else
+      temporal_count_kernel<float><<<grid, 256, 0, st>>>(pad_off, pad_gid, static_cast<const float*>(a.csr_weight), tf, S, cnt);
+    exclusive_scan_i32(cnt, a.offsets, s_cap, scan_tmp, st, s_n_dev);  // offsets[cap] = #edges
+    auto compact = [&](auto* wt, auto* nt) {
+      using WT = std::remove_cv_t<std::remove_pointer_t<decltype(wt)>>;
+      using NT = std::remove_cv_t<std::remove_pointer_t<decltype(nt)>>;
+      temporal_compact_kernel<WT, NT><<<grid, 256, 0, st>>>(pad_off, static_cast<const NT*>(pad_nbr), pad_gid,
+                                                            static_cast<const WT*>(a.csr_weight), tf, S, a.offsets,
+                                                            static_cast<NT*>(nbr), a.center_row, a.edge_gid, (int)a.edge_cap);
+    };
+    if (a.weight64 && col64) compact((const double*)nullptr, (int64_t*)nullptr);
+    else if (a.weight64) compact((const double*)nullptr, (int32_t*)nullptr);
+    else if (col64) compact((const float*)nullptr, (int64_t*)nullptr);
+    else compact((const float*)nullptr, (int32_t*)nullptr);
+    WG_HIP_CHECK(hipGetLastError());
+  } else if (a.csr_weight != nullptr) {
     int* big_list = reinterpret_cast<int*>(base + w.big_list);
     weighted_count_enqueue(a.csr_row_ptr, s_targets, i64, S, a.M, cnt, big_list, st);
     exclusive_scan_i32(cnt, a.offsets, s_cap, scan_tmp, st, s_n_dev);  // offsets[cap] = #edges
@@ -160,6 +288,13 @@ void run_hop(hop_args a)
   append_unique_prepare_enqueue(a.targets, T, i64, nbr, E, col64, bv, keys, minpos, w.slots, slot_of, rank, scan_tmp, st);
   append_unique_emit_enqueue(a.targets, T, i64, nbr, E, col64, bv, minpos, slot_of, rank, w.slots, a.unique, a.neighbor_row,
                              a.counts_dev, st);
+  if (temporal) {
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(a.edge_cap, (int64_t)256), 256 * 8));
+    frontier_time_kernel<<<grid, 256, 0, st>>>(slot_of, a.n_targets_dev, a.offsets + s_cap, a.center_row, bv.sample_batch,
+                                               bv.neighbor_local_out, bv.frontier_seg_out, bv.frontier_local0_out, a.edge_gid,
+                                               a.csr_time, a.frontier_time_out, (int)a.edge_cap);
+    WG_HIP_CHECK(hipGetLastError());
+  }
 }
 
 __global__ void __launch_bounds__(256)
@@ -656,49 +791,85 @@ wholememory_error_code_t wgamd_call_group_hop_rows_batched(const int* offsets, c
   });
 }
 
+}  // extern "C"
+
+namespace wgamd {
+namespace {
+// the hop of a wgamd_pyg_hop_t block; `t` (nullable): its times = the temporal hop
+void run_pyg_hop(const wgamd_pyg_hop_t* p, const wgamd_pyg_hop_time_t* t, bool temporal, void* stream)
+{
+  WG_REQUIRE_INPUT(p != nullptr, "null parameter block");
+  WG_REQUIRE_INPUT(!temporal || (t != nullptr && t->csr_time && t->frontier_time && t->frontier_time_out),
+                   "null time block / null times");
+  WG_REQUIRE_INPUT(!temporal || (t->comparison >= 1 && t->comparison <= 4), "comparison must be 1..4");
+  WG_REQUIRE_INPUT(!temporal || (p->max_sample_count >= 1 && p->max_sample_count <= 256), "a temporal hop needs 0 < fan-out <= 256");
+  WG_REQUIRE_INPUT(!temporal || p->max_row_len > 0, "a temporal hop needs max_row_len (the graph's maximum degree)");
+  WG_REQUIRE_INPUT(!temporal || p->edge_gid != nullptr, "a temporal hop needs edge_gid");
+  WG_REQUIRE_INPUT(p->nodes && p->node_batch && p->node_seg && p->frontier && p->frontier_batch && p->frontier_seg &&
+                     p->frontier_local0 && p->random_seeds_dev && p->center_local && p->neighbor_local &&
+                     p->nodes_out && p->nodes_out_batch && p->nodes_out_seg && p->frontier_out &&
+                     p->frontier_out_batch && p->frontier_out_seg && p->frontier_out_local0 && p->counts_dev &&
+                     p->center_row_scratch,
+                   "null pointer");
+  WG_REQUIRE_INPUT(p->n_batches >= 1 && p->n_batches < (1 << 20), "bad batch count");
+  hop_args a{};
+  a.csr_row_ptr = p->csr_row_ptr; a.csr_col = p->csr_col; a.id_dtype = p->id_dtype;
+  a.targets = p->nodes; a.n_targets_dev = p->node_seg + p->n_batches; a.target_cap = p->node_cap;
+  a.sample_targets = p->frontier; a.n_sample_dev = p->frontier_seg + p->n_batches; a.sample_cap = p->frontier_cap;
+  a.M = p->max_sample_count;
+  a.rng = rng_plan{0, p->random_seeds_dev, p->frontier_batch, p->frontier_seg};
+  a.bv.target_batch = p->node_batch; a.bv.target_seg = p->node_seg; a.bv.G = p->n_batches;
+  a.bv.id_bound = p->n_vertices > 0 ? p->n_vertices : 0;
+  a.bv.sample_batch = p->frontier_batch; a.bv.sample_seg = p->frontier_seg; a.bv.sample_local0 = p->frontier_local0;
+  a.bv.unique_batch = p->nodes_out_batch; a.bv.unique_seg = p->nodes_out_seg;
+  a.bv.frontier_out = p->frontier_out; a.bv.frontier_batch_out = p->frontier_out_batch;
+  a.bv.frontier_seg_out = p->frontier_out_seg; a.bv.frontier_local0_out = p->frontier_out_local0;
+  a.bv.neighbor_local_out = p->neighbor_local; a.bv.center_local_out = p->center_local;
+  WG_REQUIRE_INPUT((p->flags & ~(WGAMD_HOP_NO_UNIQUE_PAD | WGAMD_HOP_COL_INT32 | WGAMD_HOP_UNIFORM_BATCHES)) == 0, "unknown flag bits");
+  WG_REQUIRE_INPUT(!(p->flags & WGAMD_HOP_COL_INT32) || (p->id_dtype == WHOLEMEMORY_DT_INT64 && p->n_vertices > 0 &&
+                                                         p->n_vertices < ((int64_t)1 << 31)),
+                   "WGAMD_HOP_COL_INT32 needs INT64 ids and 0 < n_vertices < 2^31");
+  a.bv.no_pad = (p->flags & WGAMD_HOP_NO_UNIQUE_PAD) ? 1 : 0;
+  a.bv.batch_edge_cap = (p->flags & WGAMD_HOP_UNIFORM_BATCHES) ? (int)ceil_div(p->edge_cap, (int64_t)p->n_batches) : 0;
+  a.col32     = (p->flags & WGAMD_HOP_COL_INT32) != 0;
+  a.offsets = p->offsets; a.neighbor_row = p->neighbor_row_scratch; a.center_row = p->center_row_scratch;
+  a.edge_gid = p->edge_gid; a.edge_cap = p->edge_cap; a.unique = p->nodes_out; a.counts_dev = p->counts_dev;
+  a.workspace = p->workspace; a.workspace_bytes = p->workspace_bytes; a.stream = static_cast<hipStream_t>(stream);
+  if (p->csr_weight != nullptr) {
+    WG_REQUIRE_INPUT(p->weight_dtype == WHOLEMEMORY_DT_FLOAT || p->weight_dtype == WHOLEMEMORY_DT_DOUBLE,
+                     "csr_weight must be FLOAT or DOUBLE");
+    a.csr_weight = p->csr_weight; a.weight64 = p->weight_dtype == WHOLEMEMORY_DT_DOUBLE; a.max_row_len = p->max_row_len;
+  }
+  if (temporal) {
+    a.csr_time = t->csr_time; a.frontier_time = t->frontier_time; a.frontier_time_out = t->frontier_time_out;
+    a.comparison = t->comparison; a.max_row_len = p->max_row_len;
+  }
+  WG_REQUIRE_INPUT(a.neighbor_row != nullptr, "neighbor_row_scratch is NULL");
+  run_hop(a);
+}
+}  // namespace
+}  // namespace wgamd
+
+extern "C" {
+
 wholememory_error_code_t wgamd_sample_hop_pyg_nosync(const wgamd_pyg_hop_t* p, void* stream)
 {
   using namespace wgamd;
-  return guarded("wgamd_sample_hop_pyg_nosync", [&] {
-    WG_REQUIRE_INPUT(p != nullptr, "null parameter block");
-    WG_REQUIRE_INPUT(p->nodes && p->node_batch && p->node_seg && p->frontier && p->frontier_batch && p->frontier_seg &&
-                       p->frontier_local0 && p->random_seeds_dev && p->center_local && p->neighbor_local &&
-                       p->nodes_out && p->nodes_out_batch && p->nodes_out_seg && p->frontier_out &&
-                       p->frontier_out_batch && p->frontier_out_seg && p->frontier_out_local0 && p->counts_dev &&
-                       p->center_row_scratch,
-                     "null pointer");
-    WG_REQUIRE_INPUT(p->n_batches >= 1 && p->n_batches < (1 << 20), "bad batch count");
-    hop_args a{};
-    a.csr_row_ptr = p->csr_row_ptr; a.csr_col = p->csr_col; a.id_dtype = p->id_dtype;
-    a.targets = p->nodes; a.n_targets_dev = p->node_seg + p->n_batches; a.target_cap = p->node_cap;
-    a.sample_targets = p->frontier; a.n_sample_dev = p->frontier_seg + p->n_batches; a.sample_cap = p->frontier_cap;
-    a.M = p->max_sample_count;
-    a.rng = rng_plan{0, p->random_seeds_dev, p->frontier_batch, p->frontier_seg};
-    a.bv.target_batch = p->node_batch; a.bv.target_seg = p->node_seg; a.bv.G = p->n_batches;
-    a.bv.id_bound = p->n_vertices > 0 ? p->n_vertices : 0;
-    a.bv.sample_batch = p->frontier_batch; a.bv.sample_seg = p->frontier_seg; a.bv.sample_local0 = p->frontier_local0;
-    a.bv.unique_batch = p->nodes_out_batch; a.bv.unique_seg = p->nodes_out_seg;
-    a.bv.frontier_out = p->frontier_out; a.bv.frontier_batch_out = p->frontier_out_batch;
-    a.bv.frontier_seg_out = p->frontier_out_seg; a.bv.frontier_local0_out = p->frontier_out_local0;
-    a.bv.neighbor_local_out = p->neighbor_local; a.bv.center_local_out = p->center_local;
-    WG_REQUIRE_INPUT((p->flags & ~(WGAMD_HOP_NO_UNIQUE_PAD | WGAMD_HOP_COL_INT32 | WGAMD_HOP_UNIFORM_BATCHES)) == 0, "unknown flag bits");
-    WG_REQUIRE_INPUT(!(p->flags & WGAMD_HOP_COL_INT32) || (p->id_dtype == WHOLEMEMORY_DT_INT64 && p->n_vertices > 0 &&
-                                                           p->n_vertices < ((int64_t)1 << 31)),
-                     "WGAMD_HOP_COL_INT32 needs INT64 ids and 0 < n_vertices < 2^31");
-    a.bv.no_pad = (p->flags & WGAMD_HOP_NO_UNIQUE_PAD) ? 1 : 0;
-    a.bv.batch_edge_cap = (p->flags & WGAMD_HOP_UNIFORM_BATCHES) ? (int)ceil_div(p->edge_cap, (int64_t)p->n_batches) : 0;
-    a.col32     = (p->flags & WGAMD_HOP_COL_INT32) != 0;
-    a.offsets = p->offsets; a.neighbor_row = p->neighbor_row_scratch; a.center_row = p->center_row_scratch;
-    a.edge_gid = p->edge_gid; a.edge_cap = p->edge_cap; a.unique = p->nodes_out; a.counts_dev = p->counts_dev;
-    a.workspace = p->workspace; a.workspace_bytes = p->workspace_bytes; a.stream = static_cast<hipStream_t>(stream);
-    if (p->csr_weight != nullptr) {
-      WG_REQUIRE_INPUT(p->weight_dtype == WHOLEMEMORY_DT_FLOAT || p->weight_dtype == WHOLEMEMORY_DT_DOUBLE,
-                       "csr_weight must be FLOAT or DOUBLE");
-      a.csr_weight = p->csr_weight; a.weight64 = p->weight_dtype == WHOLEMEMORY_DT_DOUBLE; a.max_row_len = p->max_row_len;
-    }
-    WG_REQUIRE_INPUT(a.neighbor_row != nullptr, "neighbor_row_scratch is NULL");
-    run_hop(a);
-  });
+  return guarded("wgamd_sample_hop_pyg_nosync", [&] { run_pyg_hop(p, nullptr, false, stream); });
+}
+
+wholememory_error_code_t wgamd_sample_hop_pyg_temporal_nosync(const wgamd_pyg_hop_t* p, const wgamd_pyg_hop_time_t* t, void* stream)
+{
+  using namespace wgamd;
+  return guarded("wgamd_sample_hop_pyg_temporal_nosync", [&] { run_pyg_hop(p, t, true, stream); });
+}
+
+size_t wgamd_sample_hop_temporal_workspace_bytes(int64_t target_cap, int64_t edge_cap, wholememory_dtype_t id_dtype,
+                                                 int64_t max_row_len)
+{
+  if (target_cap < 0 || edge_cap < 0 || max_row_len <= 0) return 0;
+  size_t idb = id_dtype == WHOLEMEMORY_DT_INT64 ? 8 : 4;
+  return wgamd::plan(target_cap, edge_cap, idb, true, max_row_len, true).total;
 }
 
 }  // extern "C"

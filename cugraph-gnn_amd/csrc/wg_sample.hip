@@ -781,6 +781,15 @@ __device__ __forceinline__ float ares_key(float w, Pcg32& g, bool* redrawn = nul
   return (log1pf(u) / logf(2.0f)) * (1.0f / w);
 }
 
+// Where the exact weighted kernels take a candidate's weight from: the weight array as it is (every instantiation but the
+// temporal hop's: the same code as a plain load), or the EFFECTIVE weight of a `time_filter` (wg_common.hpp), which is 0 for
+// a slot whose time does not qualify against the time its row was reached at.
+struct no_time_filter {
+  __device__ __forceinline__ int64_t row_time(int) const { return 0; }
+  template <typename WeightT>
+  __device__ __forceinline__ float weight(const WeightT* __restrict__ w, int64_t slot, int64_t) const { return (float)w[slot]; }
+};
+
 constexpr int kWaveRowCap = 1024;  // rows the one-wave weighted kernel keeps in registers (16 keys per lane)
 static_assert(kWaveRowCap == kWaveRowCapDecl, "keep the two in step");
 
@@ -800,7 +809,7 @@ __device__ __forceinline__ uint32_t key_bits(float k)
 // sequential way, which keeps the result exact.  Keys live in LDS when the row fits (kLdsKeys), else in scratch.
 constexpr int kLdsKeys = kWeightedLdsKeys;  // 48 KB of the 64 KB static LDS a workgroup may declare
 
-template <typename SeedT, typename ColT, typename WeightT, int B, int T>
+template <typename SeedT, typename ColT, typename WeightT, int B, int T, typename TF = no_time_filter>
 __global__ void __launch_bounds__(T) sample_weighted_kernel(const int64_t* __restrict__ row_ptr,
                                                             const ColT* __restrict__ col,
                                                             const WeightT* __restrict__ weight,
@@ -816,7 +825,8 @@ __global__ void __launch_bounds__(T) sample_weighted_kernel(const int64_t* __res
                                                             int64_t* __restrict__ edge_gid,
                                                             int* __restrict__ lists /*nullable*/,
                                                             int list_cap,
-                                                            int redo = 0 /*1: the rows the pruned kernels handed back*/)
+                                                            int redo = 0 /*1: the rows the pruned kernels handed back*/,
+                                                            TF tf = TF{})
 {
   static_assert(T % B == 0 && T % 64 == 0, "threads must be a multiple of the stream layout and of the wave");
   __shared__ uint32_t lds_keys[kLdsKeys];
@@ -855,6 +865,7 @@ __global__ void __launch_bounds__(T) sample_weighted_kernel(const int64_t* __res
   const int N         = (int)(row_ptr[nid + 1] - start);
   if (N <= 0) continue;
   const int64_t base = offsets[i];
+  const int64_t t_v  = tf.row_time(i);
   if (M <= 0 || N <= M) {
     for (int j = threadIdx.x; j < N; j += T)
       emit<ColT>(dst, src_lid, edge_gid, base + j, col_at<ColT>(col, start + j), i, start + j);
@@ -887,7 +898,7 @@ __global__ void __launch_bounds__(T) sample_weighted_kernel(const int64_t* __res
       if (sid >= (1ll << 31)) g.skipahead(3u * (uint64_t)m0);
       for (int m = m0; m < m1; m++) {
         const int id = lane + m * B;
-        put(id, key_bits(ares_key((float)weight[start + id], g, &redrawn)));
+        put(id, key_bits(ares_key(tf.weight(weight, start + id, t_v), g, &redrawn)));
       }
     }
     if (redrawn) sh_redo = 1;
@@ -896,7 +907,7 @@ __global__ void __launch_bounds__(T) sample_weighted_kernel(const int64_t* __res
   if (T > B && sh_redo) {  // a 64-bit draw was 0 somewhere: redo the row with the sequential stream walk
     if (threadIdx.x < B) {
       Pcg32 g = stream_generator(random_seed, i_rng, B, threadIdx.x);
-      for (int id = threadIdx.x; id < N; id += B) put(id, key_bits(ares_key((float)weight[start + id], g)));
+      for (int id = threadIdx.x; id < N; id += B) put(id, key_bits(ares_key(tf.weight(weight, start + id, t_v), g)));
     }
     __syncthreads();
   }
@@ -987,7 +998,7 @@ __global__ void __launch_bounds__(T) sample_weighted_kernel(const int64_t* __res
 // lane hl of a group draws exactly that key; the 31-step bitwise search for the M-th largest key and the ballot prefix sums
 // of the emission are shared by the rows of the wave (masked to the lane group), which is what the short rows of a
 // mini-batch frontier were paying a whole wave each for.
-template <typename SeedT, typename ColT, typename WeightT, int LANES>
+template <typename SeedT, typename ColT, typename WeightT, int LANES, typename TF = no_time_filter>
 __global__ void __launch_bounds__(256) sample_weighted_group_kernel(const int64_t* __restrict__ row_ptr,
                                                                     const ColT* __restrict__ col,
                                                                     const WeightT* __restrict__ weight,
@@ -1000,7 +1011,8 @@ __global__ void __launch_bounds__(256) sample_weighted_group_kernel(const int64_
                                                                     int64_t* __restrict__ edge_gid,
                                                                     const int* __restrict__ lists,
                                                                     int list_cap,
-                                                                    int cls)
+                                                                    int cls,
+                                                                    TF tf = TF{})
 {
   const int lane = threadIdx.x & 63;
   const int hl = lane & (LANES - 1), hb = lane & ~(LANES - 1);
@@ -1021,7 +1033,7 @@ __global__ void __launch_bounds__(256) sample_weighted_group_kernel(const int64_
     base              = offsets[i];
     if (hl < N) {
       Pcg32 g = stream_generator(random_seed, i_rng, 128, hl);
-      k       = key_bits(ares_key((float)weight[start + hl], g));
+      k       = key_bits(ares_key(tf.weight(weight, start + hl, tf.row_time(i)), g));
     }
   }
   const uint64_t gm = LANES == 64 ? ~0ull : (((1ull << LANES) - 1ull) << hb);
@@ -1048,7 +1060,7 @@ __global__ void __launch_bounds__(256) sample_weighted_group_kernel(const int64_
 // key is found by a bitwise search whose counts are wave ballots, and the picks are emitted in CSR order with ballot
 // prefix sums.  No LDS, no scratch, no barrier.  The slot count is a compile-time constant per class, so nothing in the
 // search is under a per-row condition (an empty slot holds 0, which is below every real key and matches no candidate).
-template <typename SeedT, typename ColT, typename WeightT, int KMAX>
+template <typename SeedT, typename ColT, typename WeightT, int KMAX, typename TF = no_time_filter>
 __global__ void __launch_bounds__(256) sample_weighted_wave_kernel(const int64_t* __restrict__ row_ptr,
                                                                    const ColT* __restrict__ col,
                                                                    const WeightT* __restrict__ weight,
@@ -1061,7 +1073,8 @@ __global__ void __launch_bounds__(256) sample_weighted_wave_kernel(const int64_t
                                                                    int64_t* __restrict__ edge_gid,
                                                                    const int* __restrict__ lists,
                                                                    int list_cap,
-                                                                   int cls)
+                                                                   int cls,
+                                                                   TF tf = TF{})
 {
   const int lane   = threadIdx.x & 63;
   const int64_t li = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1075,6 +1088,7 @@ __global__ void __launch_bounds__(256) sample_weighted_wave_kernel(const int64_t
   // (one row per wave: make that visible to the compiler, so that `s * 64 < N` below is a scalar branch)
   const int N         = __builtin_amdgcn_readfirstlane((int)(row_ptr[nid + 1] - start));   // M < N <= 64 * KMAX (list)
   const int64_t base  = offsets[i];
+  const int64_t t_v   = tf.row_time(i);
   uint32_t k[KMAX];
   {
     Pcg32 ga = stream_generator(random_seed, i_rng, 128, lane);
@@ -1086,7 +1100,7 @@ __global__ void __launch_bounds__(256) sample_weighted_wave_kernel(const int64_t
       // the wave-uniform branch keeps the KMAX key computations in separate blocks: as straight-line predicated code the
       // scheduler interleaves them all (238 VGPRs at KMAX = 16, one wave per SIMD)
       if (s * 64 < N) {
-        if (id < N) k[s] = key_bits(ares_key((float)weight[start + id], (s & 1) ? gb : ga));
+        if (id < N) k[s] = key_bits(ares_key(tf.weight(weight, start + id, t_v), (s & 1) ? gb : ga));
       }
     }
   }
@@ -1892,6 +1906,43 @@ void weighted_sample_launch(const int64_t* row_ptr, const ColT* col, const Weigh
       row_ptr, col, weights, seeds, n, M, rng, offsets, slab, slab_len, dst, lid, gid, lists, cap, 1);
 }
 
+// The temporal hop of the no-sync walk (0 < M <= 256): the launches of weighted_sample_launch without threshold pruning,
+// drawing with the effective weights of `tf`.  A frontier row has zero-weight candidates as a rule (every slot whose time
+// does not qualify), and a pruned kernel hands any such row back to the exact workgroup kernel: the exact one-wave kernels
+// select the same picks (M largest keys, ties to the lower slot — a zero weight's key is -inf) in one pass.
+template <typename SeedT, typename ColT, typename WeightT>
+void weighted_temporal_launch(const int64_t* row_ptr, const ColT* col, const WeightT* weights, const SeedT* seeds, dev_count n,
+                              int M, rng_plan rng, const int* offsets, int* lists, int blocks, uint32_t* slab,
+                              int64_t slab_len, ColT* dst, int* lid, int64_t* gid, time_filter tf, hipStream_t stream)
+{
+  if (n.host <= 0) return;
+  const int cap = n.host;
+  using TF      = time_filter;
+  sample_weighted_kernel<SeedT, ColT, WeightT, 128, 512, TF><<<blocks, 512, 0, stream>>>(
+    row_ptr, col, weights, seeds, n, M, rng, offsets, slab, slab_len, dst, lid, gid, lists, cap, 0, tf);
+  if (M < 16)
+    sample_weighted_group_kernel<SeedT, ColT, WeightT, 16, TF><<<ceil_div((int64_t)cap * 16, 256), 256, 0, stream>>>(
+      row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 0, tf);
+  if (M < 32)
+    sample_weighted_group_kernel<SeedT, ColT, WeightT, 32, TF><<<ceil_div((int64_t)cap * 32, 256), 256, 0, stream>>>(
+      row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 1, tf);
+  if (M < 64)
+    sample_weighted_group_kernel<SeedT, ColT, WeightT, 64, TF><<<ceil_div((int64_t)cap * 64, 256), 256, 0, stream>>>(
+      row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 2, tf);
+  if (M < 128)
+    sample_weighted_wave_kernel<SeedT, ColT, WeightT, 2, TF><<<ceil_div(cap, 4), 256, 0, stream>>>(
+      row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 3, tf);
+  sample_weighted_wave_kernel<SeedT, ColT, WeightT, 4, TF><<<ceil_div(cap, 4), 256, 0, stream>>>(
+    row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 4, tf);
+  sample_weighted_wave_kernel<SeedT, ColT, WeightT, 8, TF><<<ceil_div(cap, 4), 256, 0, stream>>>(
+    row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 5, tf);
+  sample_weighted_wave_kernel<SeedT, ColT, WeightT, 16, TF><<<ceil_div(cap, 4), 256, 0, stream>>>(
+    row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 6, tf);
+  // rows copied whole: every slot is a pick, whatever its time
+  copy_short_rows_kernel<SeedT, ColT><<<ceil_div((int64_t)cap * 16, 256), 256, 0, stream>>>(row_ptr, col, seeds, n, M, offsets,
+                                                                                          dst, lid, gid);
+}
+
 // ------------------------------------------------------------------------------------------
 struct sample_args {
   wholememory_tensor_t row_ptr, col, weight, seeds, out_offsets;
@@ -2152,6 +2203,26 @@ void weighted_sample_enqueue(const int64_t* row_ptr, const void* col, bool col64
   weighted_sample_launch<ST, CT, WT>(row_ptr, static_cast<const CT*>(col), static_cast<const WT*>(weights),              \
                                      static_cast<const ST*>(seeds), n, M, random_seed, offsets, big_list, kWeightedBlocks, \
                                      slab, slab_len, static_cast<CT*>(dst), src_lid, edge_gid, stream)
+#define WG_WW(ST, CT) do { if (weights64) WG_W(ST, CT, double); else WG_W(ST, CT, float); } while (0)
+  if (seeds64 && col64) WG_WW(int64_t, int64_t);
+  else if (seeds64) WG_WW(int64_t, int32_t);
+  else if (col64) WG_WW(int32_t, int64_t);
+  else WG_WW(int32_t, int32_t);
+#undef WG_WW
+#undef WG_W
+  WG_HIP_CHECK(hipGetLastError());
+}
+
+void weighted_temporal_sample_enqueue(const int64_t* row_ptr, const void* col, bool col64, const void* weights, bool weights64,
+                                      const void* seeds, bool seeds64, dev_count n, int M, rng_plan random_seed,
+                                      const int* offsets, int* big_list, uint32_t* slab, int64_t slab_len, void* dst,
+                                      int* src_lid, int64_t* edge_gid, time_filter tf, hipStream_t stream)
+{
+  WG_REQUIRE_INPUT(M > 0 && M <= 256, "the no-sync temporal hop needs 0 < fan-out <= 256");
+#define WG_W(ST, CT, WT)                                                                                                    \
+  weighted_temporal_launch<ST, CT, WT>(row_ptr, static_cast<const CT*>(col), static_cast<const WT*>(weights),              \
+                                       static_cast<const ST*>(seeds), n, M, random_seed, offsets, big_list, kWeightedBlocks, \
+                                       slab, slab_len, static_cast<CT*>(dst), src_lid, edge_gid, tf, stream)
 #define WG_WW(ST, CT) do { if (weights64) WG_W(ST, CT, double); else WG_W(ST, CT, float); } while (0)
   if (seeds64 && col64) WG_WW(int64_t, int64_t);
   else if (seeds64) WG_WW(int64_t, int32_t);

@@ -566,9 +566,18 @@ class CallGroupIterator(_PipelinedGroups):
         self._fs, self._gs = data
         self._smp, self._B, self._rs = core_sampler, int(batch_size), int(random_state)
         self._hetero = isinstance(core_sampler, HeteroNeighborSampler)
-        if input_data.time is not None or not core_sampler.call_groups_ok() or not input_data.node.is_cuda:
+        # seed times go with a temporal sampler on a homogeneous graph (NeighborSampler.temporal_call_groups_ok), and only
+        # with one: input_time without time_attr, heterogeneous temporal and disjoint stay refused
+        if input_data.time is not None:
+            ok = (not self._hetero) and core_sampler.temporal_call_groups_ok()
+        else:
+            ok = core_sampler.call_groups_ok()
+        if not ok or not input_data.node.is_cuda:
             raise NotImplementedError("call_groups(): uniform or positively-weighted sampling with positive fan-outs, no "
-                                      "replacement, not disjoint / temporal, seeds on the device")
+                                      "replacement, not disjoint, seeds on the device; temporal sampling (time_attr and "
+                                      "input_time together) on homogeneous graphs with fan-outs <= 256")
+        self._seed_time = None if input_data.time is None else input_data.time.to(device=input_data.node.device,
+                                                                                  dtype=torch.int64)
         self._seed_type = input_data.input_type
         self._seeds = input_data.node.to(torch.int64 if self._hetero else core_sampler.graph.col.dtype)
         self._input_id = input_data.input_id
@@ -619,14 +628,20 @@ class CallGroupIterator(_PipelinedGroups):
         walk = smp._call_group_walk(B, g)
 
         def enqueue():
+            st = self._seed_time   # (sliced and padded with the seeds)
             if ragged is None:
-                res = walk.run(self._seeds[b0 * B:(b0 + g) * B].contiguous(), rs)
+                res = walk.run(self._seeds[b0 * B:(b0 + g) * B].contiguous(), rs,
+                               seed_time=None if st is None else st[b0 * B:(b0 + g) * B].contiguous())
                 n_seeds = g * B
             else:   # the last, short mini-batch: a one-batch group over a ragged seed list
                 ids = torch.zeros(B, dtype=self._seeds.dtype, device=dev)
                 ids[:ragged] = self._seeds[b0 * B:b0 * B + ragged]
                 seg = torch.tensor([0, ragged], dtype=torch.int32, device=dev)
-                res = walk.run(ids, rs, seg, torch.zeros(B, dtype=torch.int32, device=dev))
+                times = None
+                if st is not None:
+                    times = torch.zeros(B, dtype=torch.int64, device=dev)
+                    times[:ragged] = st[b0 * B:b0 * B + ragged]
+                res = walk.run(ids, rs, seg, torch.zeros(B, dtype=torch.int32, device=dev), seed_time=times)
                 n_seeds = ragged
             return (res,) + _enqueue_walk_sizes(res) + (n_seeds,)
 

@@ -86,7 +86,12 @@ class NodeLoader:
         """The same epoch as ``iter(self)`` — same shuffle, same seeds, same samples — handed out in CALL GROUPS:
         ``local_seeds_per_call`` seeds (by default sized from device memory) per ``CallGroup``, each the block-diagonal
         union of its mini-batches with a lazy ``x`` and per-layer trimmed graphs (``loader/call_group.py``).  For loops
-        that want the device's speed rather than one ``Data`` per 1024 seeds.  Homogeneous graphs."""
+        that want the device's speed rather than one ``Data`` per 1024 seeds.  Homogeneous graphs.
+
+        TEMPORAL loaders (``time_attr`` with ``input_time``) on homogeneous graphs run here too: the walk's temporal hop
+        gives every mini-batch, bit for bit, the sample of the per-batch route — not disjoint, no replacement, fan-outs in
+        1..256, biased weights strictly positive (``NeighborSampler.temporal_call_groups_ok``).  Anything else raises
+        ``NotImplementedError``: ``input_time`` without ``time_attr``, disjoint, heterogeneous temporal, host seeds."""
         from .call_group import CallGroupIterator
         n = self.__input_data.node.numel()
         perm = torch.randperm(n) if self.__shuffle else torch.arange(n)

@@ -246,7 +246,8 @@ def _temporal_hop(graph: CSRGraph, frontier, frontier_time, fan, seed, biased, c
     pos = torch.repeat_interleave(start - first, deg, output_size=total) + torch.arange(total, device=dev)
     t_v = torch.repeat_interleave(frontier_time.to(dev).long(), deg, output_size=total)
     ok = _TEMPORAL_OK[comparison](graph.time[pos], t_v)
-    scratch[pos] = ok.float() * (graph.weight[pos] if biased else 1.0)
+    # (float64 weights: the product is rounded to the scratch's float32, which is what the kernel draws with)
+    scratch[pos] = (ok.float() * (graph.weight[pos] if biased else 1.0)).to(scratch.dtype)
     try:
         off, nbr, lid, gid = wholegraph_ops.weighted_sample_without_replacement(
             graph.row_ptr, graph.col, scratch, frontier, int(fan), seed, True, True)
@@ -620,7 +621,9 @@ class NeighborSampler:
         key = (batch_size, n_batches)
         if key not in self._walks:
             self._walks[key] = PygNoSyncWalk(self.graph.row_ptr, self.graph.col, batch_size, self.fanout, n_batches,
-                                             csr_weight=self.graph.weight if self.biased else None, pad_unique=False)
+                                             csr_weight=self.graph.weight if self.biased else None, pad_unique=False,
+                                             csr_time=self.graph.time.long() if self.temporal else None,
+                                             temporal_comparison=self.temporal_comparison if self.temporal else None)
         return self._walks[key]
 
     def call_groups_ok(self) -> bool:
@@ -630,6 +633,19 @@ class NeighborSampler:
         biased_ok = (not self.biased) or (self._positive_weights and all(f <= 256 for f in self.fanout))
         return (biased_ok and (not self.disjoint) and (not self.temporal) and (not self.with_replacement)
                 and all(f > 0 for f in self.fanout))
+
+    def temporal_call_groups_ok(self) -> bool:
+        """Can this TEMPORAL configuration run as call groups (``NeighborLoader.call_groups()`` with ``input_time``)?  The
+        temporal hop of the no-sync walk draws on the biased kernels: not disjoint, no replacement, every fan-out in
+        1..256, biased weights strictly positive.  ``call_groups_ok()`` stays False for a temporal sampler: the routes that
+        read it (``sample_batches``, ``fetch_plan``, the link loaders) keep the one-batch-at-a-time temporal path."""
+        if not self.temporal or self.disjoint or self.with_replacement:
+            return False
+        if not all(0 < f <= 256 for f in self.fanout):
+            return False
+        if self.biased and self._positive_weights is None:
+            self._positive_weights = bool((self.graph.weight > 0).all())
+        return (not self.biased) or bool(self._positive_weights)
 
     def seeds_per_call(self, batch_size: int) -> int:
         """``local_seeds_per_call`` as given, else sized from device memory (``default_local_seeds_per_call``)."""

@@ -378,6 +378,17 @@ class _PygHop(_ct.Structure):
                 ("n_vertices", _ct.c_int64), ("flags", _ct.c_uint)]
 
 
+class _PygHopTime(_ct.Structure):
+    """ctypes mirror of ``wgamd_pyg_hop_time_t`` (include/wgamd_ext.h)."""
+    _fields_ = [("csr_time", _ct.c_void_p), ("frontier_time", _ct.c_void_p), ("frontier_time_out", _ct.c_void_p),
+                ("comparison", _ct.c_int)]
+
+
+# wgamd_pyg_hop_time_t.comparison (the names are cugraph_pyg's ``temporal_comparison``)
+TEMPORAL_COMPARISONS = {"strictly_increasing": 1, "monotonically_increasing": 2, "strictly_decreasing": 3,
+                        "monotonically_decreasing": 4}
+
+
 @dataclass
 class PygWalkResult:
     """Capacity-sized outputs of one PyG-style walk over a call group (everything on the device).
@@ -465,10 +476,14 @@ class PygNoSyncWalk:
     (SURVEY.md §8 row a14)."""
 
     def __init__(self, csr_row_ptr, csr_col_ind, batch_size: int, fanout: List[int], n_batches: int = 1,
-                 csr_weight: torch.Tensor = None, pad_unique: bool = True, compact_col: bool = True):
+                 csr_weight: torch.Tensor = None, pad_unique: bool = True, compact_col: bool = True,
+                 csr_time: torch.Tensor = None, temporal_comparison: str = None):
         """``csr_weight`` (float32 | float64, one per CSR slot): BIASED sampling — every hop is then what
         ``wholegraph_csr_weighted_sample_without_replacement`` draws (fan-outs <= 256).  ``pad_unique`` / ``compact_col``:
-        see ``NoSyncWalk``."""
+        see ``NoSyncWalk``.  ``csr_time`` (int64, one per CSR slot): TEMPORAL sampling on
+        ``wgamd_sample_hop_pyg_temporal_nosync`` (fan-outs <= 256, with or without weights) — a slot of a vertex reached at
+        time t qualifies when ``temporal_comparison`` (default ``monotonically_decreasing``) holds between its time and t;
+        ``run`` then takes the seeds' times."""
         self.flags = 0 if pad_unique else HOP_NO_UNIQUE_PAD
         assert csr_row_ptr.is_cuda and csr_col_ind.is_cuda and csr_col_ind.dtype in (torch.int32, torch.int64)
         assert all(0 < f for f in fanout), "the no-sync walk needs positive fan-outs"
@@ -478,6 +493,16 @@ class PygNoSyncWalk:
             assert csr_weight.shape[0] == csr_col_ind.shape[0]
             self.weight = csr_weight.contiguous()
             self.max_row_len = max(int((csr_row_ptr[1:] - csr_row_ptr[:-1]).max()), 1) if csr_row_ptr.shape[0] > 1 else 1
+        self.time, self.comparison = None, 0
+        if csr_time is not None:
+            assert csr_time.is_cuda and csr_time.dtype == torch.int64 and csr_time.shape[0] == csr_col_ind.shape[0]
+            assert all(f <= 256 for f in fanout), "the temporal walk needs fan-outs <= 256"
+            name = temporal_comparison or "monotonically_decreasing"
+            if name not in TEMPORAL_COMPARISONS:
+                raise ValueError(f"unknown temporal_comparison {name!r}; expected one of {sorted(TEMPORAL_COMPARISONS)}")
+            self.time, self.comparison = csr_time.contiguous(), TEMPORAL_COMPARISONS[name]
+            if self.weight is None:   # (the temporal hop runs on the biased path, with or without weights)
+                self.max_row_len = max(int((csr_row_ptr[1:] - csr_row_ptr[:-1]).max()), 1) if csr_row_ptr.shape[0] > 1 else 1
         self.row_ptr, self.col = csr_row_ptr, csr_col_ind
         self.id_dtype, self.wm_dtype = csr_col_ind.dtype, torch_dtype_to_wm(csr_col_ind.dtype)
         c32 = compact_columns(csr_col_ind, int(csr_row_ptr.shape[0]) - 1) if compact_col else None
@@ -494,7 +519,10 @@ class PygNoSyncWalk:
             n, f = n + f * m, f * m
         assert n < (1 << 30), "call group too large: lower n_batches"
         lib = L.lib()
-        if self.weight is None:
+        if self.time is not None:
+            ws = max(lib.wgamd_sample_hop_temporal_workspace_bytes(max(nc, fc), ec, self.wm_dtype, self.max_row_len)
+                     for nc, fc, ec in zip(self.node_caps, self.frontier_caps, self.edge_caps))
+        elif self.weight is None:
             ws = max(lib.wgamd_sample_hop_workspace_bytes(max(nc, fc), ec, self.wm_dtype)
                      for nc, fc, ec in zip(self.node_caps, self.frontier_caps, self.edge_caps))
         else:
@@ -506,12 +534,19 @@ class PygNoSyncWalk:
         self.seed_batch = torch.arange(self.G, dtype=torch.int32, device=dev).repeat_interleave(self.B).contiguous()
         self.zeros_g = torch.zeros(self.G, dtype=torch.int32, device=dev)
 
-    def run(self, seeds: torch.Tensor, random_seeds, seed_seg: torch.Tensor = None, seed_batch: torch.Tensor = None) -> PygWalkResult:
+    def run(self, seeds: torch.Tensor, random_seeds, seed_seg: torch.Tensor = None, seed_batch: torch.Tensor = None,
+            seed_time: torch.Tensor = None) -> PygWalkResult:
         """``seeds`` [G*B] (batch b = seeds[b*B:(b+1)*B]); ``random_seeds`` int64 tensor / nested list [hops, G].
         Ragged seed lists (link prediction: the de-duplicated endpoints of a batch's seed edges): ``seeds`` holds the lists
         back to back, padded to the capacity G*B, ``seed_seg`` int32 [G+1] their offsets and ``seed_batch`` int32 [G*B]
-        the batch of every live entry — the kernels only read below ``seed_seg[G]``."""
+        the batch of every live entry — the kernels only read below ``seed_seg[G]``.  ``seed_time`` int64 [G*B]: the time of
+        every seed, required exactly when the walk is temporal; the times of the later frontiers stay on the device."""
         assert seeds.dtype == self.id_dtype and seeds.shape[0] == self.G * self.B
+        if (seed_time is not None) != (self.time is not None):
+            raise ValueError("seed_time goes with a temporal walk (csr_time=...), and only with one")
+        if seed_time is not None:
+            assert seed_time.is_cuda and seed_time.dtype == torch.int64 and seed_time.shape[0] == self.G * self.B
+            seed_time = seed_time.contiguous()
         assert (seed_seg is None) == (seed_batch is None)
         lib, dev, G = L.lib(), self.dev, self.G
         hops = len(self.fanout)
@@ -532,6 +567,7 @@ class PygNoSyncWalk:
             assert seed_batch.dtype == torch.int32 and seed_batch.shape[0] == G * self.B and seed_batch.is_contiguous()
         nodes, n_batch, n_seg = seeds, seed_batch, seed_seg
         front, f_batch, f_seg, f_local0 = seeds, seed_batch, seed_seg, self.zeros_g
+        f_time = seed_time
         i32 = dict(dtype=torch.int32, device=dev)
         for k, (m, fc, nc, ec) in enumerate(zip(self.fanout, self.frontier_caps, self.node_caps, self.edge_caps)):
             offsets = torch.empty(fc + 1, **i32)
@@ -553,7 +589,15 @@ class PygNoSyncWalk:
                         None if self.weight is None else self.weight.data_ptr(),
                         0 if self.weight is None else torch_dtype_to_wm(self.weight.dtype), self.max_row_len,
                         int(self.row_ptr.shape[0]) - 1, flags)
-            L.check(lib.wgamd_sample_hop_pyg_nosync(_ct.byref(p), get_stream()), "wgamd_sample_hop_pyg_nosync")
+            if self.time is None:
+                L.check(lib.wgamd_sample_hop_pyg_nosync(_ct.byref(p), get_stream()), "wgamd_sample_hop_pyg_nosync")
+            else:
+                f_time_out = torch.empty(ec, dtype=torch.int64, device=dev)
+                t = _PygHopTime(self.time.data_ptr(), f_time.data_ptr(), f_time_out.data_ptr(), self.comparison)
+                L.check(lib.wgamd_sample_hop_pyg_temporal_nosync(_ct.byref(p), _ct.byref(t), get_stream()),
+                        "wgamd_sample_hop_pyg_temporal_nosync")
+                res._keepalive.append(f_time)
+                f_time = f_time_out
             res.offsets.append(offsets)
             res.row_local.append(row_l)
             res.col_local.append(col_l)

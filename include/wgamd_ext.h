@@ -366,6 +366,35 @@ typedef struct wgamd_pyg_hop_t {
 
 wholememory_error_code_t wgamd_sample_hop_pyg_nosync(const wgamd_pyg_hop_t* p, void* stream);
 
+/* The TEMPORAL hop of the PyG-style walk for a call group: wgamd_sample_hop_pyg_nosync restricted to the CSR slots whose
+ * time qualifies against the time their frontier vertex was reached at.  `p` is the block of the plain hop (its layout is
+ * unchanged), `t` the times:
+ *   csr_time          int64 per CSR slot
+ *   frontier_time     int64[frontier_cap]  time every frontier entry was reached at (hop 0: the seeds' input time)
+ *   frontier_time_out int64[edge_cap]      time of every entry of frontier_out = time of the FIRST sampled edge (lowest
+ *                                          position in the hop's edge list) that reached it: the next hop's frontier_time
+ *   comparison        slot s of a row reached at t_v qualifies when
+ *                       1 strictly increasing  time[s] >  t_v      2 monotonically increasing  time[s] >= t_v
+ *                       3 strictly decreasing  time[s] <  t_v      4 monotonically decreasing  time[s] <= t_v
+ * and, with p->csr_weight, when its weight rounded to float is > 0.  Per row: A-Res over the whole row on the key stream of
+ * the biased hop with the effective weight (the weight, or 1.0f when p->csr_weight is NULL = uniform temporal, of a
+ * qualifying slot; 0 otherwise) — every slot consumes its draws —, the picks that do not qualify dropped, the others in CSR
+ * order: min(qualifying slots, max_sample_count) edges.  Renumbering as in the plain hop, over the surviving edges.  Per
+ * mini-batch the result equals the biased ABI op over an array of effective weights + graph_append_unique.
+ * Needs 0 < max_sample_count <= 256, max_row_len > 0 (the graph's maximum degree), edge_gid; workspace:
+ * wgamd_sample_hop_temporal_workspace_bytes(max(node_cap, frontier_cap), edge_cap, id_dtype, max_row_len).  A bad block is
+ * WHOLEMEMORY_INVALID_INPUT before anything touches the device. */
+typedef struct wgamd_pyg_hop_time_t {
+  const int64_t* csr_time;
+  const int64_t* frontier_time;
+  int64_t* frontier_time_out;
+  int comparison;
+} wgamd_pyg_hop_time_t;
+size_t wgamd_sample_hop_temporal_workspace_bytes(int64_t target_cap, int64_t edge_cap, wholememory_dtype_t id_dtype,
+                                                 int64_t max_row_len);
+wholememory_error_code_t wgamd_sample_hop_pyg_temporal_nosync(const wgamd_pyg_hop_t* p, const wgamd_pyg_hop_time_t* t,
+                                                              void* stream);
+
 /* Rows of the hop's targets inside its block-diagonal `unique` list — the "x[:num_dst]" of a single mini-batch becomes
  * an index list for a call group:  rows[i] = i + unique_seg[b] - target_seg[b],  b = target_batch[i],  for i < n_targets.
  * One launch (the SAGEConv root term and the next layer's row list read it); everything is device memory. */
