@@ -16,6 +16,9 @@
 // Memory safety does not rest on the promise about the values: an id is masked to 40 bits before it is hashed or packed, every
 // store is addressed by a position or by a rank (< S by construction), and a row inserts at most S ids into >= 2 S slots, so a
 // probe always ends.  Values outside [0, 2^40) give a de-duplication of their low 40 bits, nothing worse.
+//
+// wgamd_rows_first_values (further down) carries a value per element to the lists: the value at an id's first position, e.g. the
+// seed time of a de-duplicated endpoint of a temporal link call group.
 #include "wg_common.hpp"
 #include "wgamd_ext.h"
 
@@ -177,6 +180,60 @@ rows_compact_kernel(const int64_t* __restrict__ lists, const int* __restrict__ s
   }
 }
 
+// wgamd_rows_first_values: a value per distinct id of a row, taken at the id's first position.  The lists are numbered in order
+// of first position, so s is a first position exactly when local[g, s] is larger than every earlier local[g, .]: one workgroup
+// per row walks it 256 positions at a time with an exclusive prefix maximum (a wave scan, the waves' maxima in LDS, the running
+// maximum of the row carried from pass to pass) and stores once per first position, at seg[g] + local[g, s].  A local outside
+// [0, S) counts as no position at all, and a store needs its slot below seg[G] <= G S: nothing lands outside `out`.  The tail
+// from seg[G] on is zeroed by the whole grid.
+constexpr int kRowsValThreads = 256;
+
+__global__ void __launch_bounds__(kRowsValThreads)
+rows_first_values_kernel(const int64_t* __restrict__ local, const int* __restrict__ seg, const int64_t* __restrict__ values,
+                         int64_t G, int S, int64_t* __restrict__ out)
+{
+  constexpr int T = kRowsValThreads, NW = T / 64;
+  __shared__ int s_wave[NW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t total = G * S;
+  const int64_t live  = min(max((int64_t)seg[G], (int64_t)0), total);
+  for (int64_t i = live + (int64_t)blockIdx.x * T + tid; i < total; i += (int64_t)gridDim.x * T) out[i] = 0;
+
+  for (int64_t g = blockIdx.x; g < G; g += gridDim.x) {
+    const int64_t base = (int64_t)seg[g];
+    int carry = -1;   // the running maximum of the row before this pass: the same in every thread
+    for (int s0 = 0; s0 < S; s0 += T) {
+      const int s     = s0 + tid;
+      const int64_t l = s < S ? local[g * S + s] : -1;
+      const int mine  = (l >= 0 && l < S) ? (int)l : -1;
+      int incl        = mine;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(incl, d, 64);
+        if (lane >= d) incl = max(incl, up);
+      }
+      int before = __shfl_up(incl, 1, 64);
+      if (lane == 0) before = -1;
+      if (lane == 63) s_wave[wave] = incl;
+      __syncthreads();
+      int all = carry;
+      before  = max(before, carry);
+#pragma unroll
+      for (int w = 0; w < NW; w++) {
+        const int t = s_wave[w];
+        if (w < wave) before = max(before, t);
+        all = max(all, t);
+      }
+      if (mine > before) {
+        const int64_t at = base + mine;
+        if (at >= 0 && at < live) out[at] = values[g * S + s];
+      }
+      carry = all;
+      __syncthreads();   // s_wave is the next pass's
+    }
+  }
+}
+
 struct rows_ws {
   int* ticket;
   int* counts;
@@ -244,6 +301,20 @@ wholememory_error_code_t wgamd_rows_first_unique(const int64_t* ends, int64_t n_
     const int64_t total = n_rows * row_len;
     const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
     rows_compact_kernel<<<grid, 256, 0, st>>>(w.lists, seg, n_rows, S, uniq, batch);
+    WG_HIP_CHECK(hipGetLastError());
+  });
+}
+
+wholememory_error_code_t wgamd_rows_first_values(const int64_t* local, const int* seg, const int64_t* values, int64_t n_rows,
+                                                 int64_t row_len, int64_t* out, void* stream)
+{
+  using namespace wgamd;
+  return guarded("wgamd_rows_first_values", [&] {
+    WG_REQUIRE_INPUT(wgamd_rows_first_unique_supported(n_rows, row_len, 1), "outside the domain (wgamd_rows_first_unique_supported)");
+    WG_REQUIRE_INPUT(local && seg && values && out, "null pointer");
+    const unsigned grid = (unsigned)std::min<int64_t>(n_rows, kRowsMaxGrid);
+    rows_first_values_kernel<<<grid, kRowsValThreads, 0, static_cast<hipStream_t>(stream)>>>(local, seg, values, n_rows, (int)row_len,
+                                                                                             out);
     WG_HIP_CHECK(hipGetLastError());
   });
 }

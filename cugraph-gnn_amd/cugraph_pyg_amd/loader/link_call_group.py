@@ -19,6 +19,8 @@ from typing import Optional
 
 import torch
 
+from wholegraph_amd import graph_ops
+
 from .call_group import CallGroup, HeteroCallGroup, _PipelinedGroups, _enqueue_hetero_walk_sizes, _enqueue_walk_sizes
 
 
@@ -87,12 +89,14 @@ class LinkCallGroup(CallGroup):
     ``edge_label_index`` int64 [2, P]: the pairs of all mini-batches, batch-major, positives first inside a batch, as rows of
     the last layer's output (the ``batch_ptr`` numbering) — ``batch[edge_label_index]`` are the global endpoint ids;
     ``edge_label`` [P] (None where the per-batch loader gives none): the per-batch labels back to back;
-    ``label_ptr`` int64 [G + 1]: the pairs of mini-batch b; ``input_id``: the seed-edge ids, ``n_pos`` per mini-batch."""
+    ``label_ptr`` int64 [G + 1]: the pairs of mini-batch b; ``input_id``: the seed-edge ids, ``n_pos`` per mini-batch;
+    ``seed_time`` int64, one per seed row, batch-major (a TEMPORAL loader; None otherwise): the time every unique endpoint
+    starts the walk at — the ``edge_label_time`` of the first pair of its mini-batch that names it."""
 
     def __init__(self, walk_result, feature_store, graph, first_batch, input_id, sizes_h, event, walk_stream, local, n_pos, n_neg,
-                 edge_label_index, label_ptr, edge_label, mode):
+                 edge_label_index, label_ptr, edge_label, mode, seed_time=None):
         super().__init__(walk_result, feature_store, graph, first_batch, input_id, sizes_h, event, walk_stream)
-        self._local, self.n_pos, self.n_neg, self._mode = local, n_pos, n_neg, mode
+        self._local, self.n_pos, self.n_neg, self._mode, self._seed_time = local, n_pos, n_neg, mode, seed_time
         self.edge_label_index, self.label_ptr, self.edge_label = edge_label_index, label_ptr, edge_label
 
     def _wait(self):
@@ -101,9 +105,16 @@ class LinkCallGroup(CallGroup):
         super()._wait()
         if self._walk_stream is not None:     # the negatives and the de-duplication ran on the walk stream too
             main = torch.cuda.current_stream()
-            for t in (self._local, self.edge_label_index, self.label_ptr, self.edge_label, self.input_id):
+            for t in (self._local, self.edge_label_index, self.label_ptr, self.edge_label, self.input_id, self._seed_time):
                 if t is not None:
                     t.record_stream(main)
+
+    @property
+    def seed_time(self):
+        if self._seed_time is None:
+            return None
+        self._wait()
+        return self._seed_time[:self.num_seeds]
 
     def to_data_list(self):
         """The G mini-batches as the ``Data`` objects ``for batch in loader`` yields (same tensors, bit for bit)."""
@@ -160,25 +171,30 @@ class LinkCallGroupIterator(_PipelinedGroups):
         rs = [[hop_seed(self._rs + b0 + j, k) for j in range(g)] for k in range(len(smp.fanout))]
 
         def enqueue():
-            ids, ends, labels, n_pos, n_neg = [], [], [], 0, 0
+            ids, ends, labels, times, n_pos, n_neg = [], [], [], [], 0, 0
             for j in range(g):
-                input_id, src_all, dst_all, n_neg, label = self._batch_edges(b0 + j, self._rs + b0 + j)
+                input_id, src_all, dst_all, n_neg, label, t_all = self._batch_edges(b0 + j, self._rs + b0 + j)
                 n_pos = input_id.numel()
                 ids.append(input_id)
                 ends.append(torch.cat([src_all, dst_all]))
                 labels.append(label)
+                times.append(t_all)
             ends = torch.stack(ends)                  # [g, 2 (n_pos + n_neg)]: the batches of a group are equally long
             S = ends.shape[1]
             uniq, seg, batch, local = _batched_first_unique(ends, self._num_nodes)
+            seed_time = None
+            if smp.temporal:   # both endpoints of pair i start at time i; a unique endpoint at the time of its first pair
+                t = torch.stack(times)
+                seed_time = graph_ops.rows_first_values(local, seg, torch.cat([t, t], 1))
             walk = smp._call_group_walk(S, g)
-            res = walk.run(uniq.to(smp.graph.col.dtype).contiguous(), rs, seg, batch)
+            res = walk.run(uniq.to(smp.graph.col.dtype).contiguous(), rs, seg, batch, seed_time=seed_time)
             edge_label = None if labels[0] is None else torch.cat(labels)
             index, label_ptr = link_group_index(local, seg, n_pos, n_neg)
-            return (res,) + _enqueue_walk_sizes(res) + (torch.cat(ids), local, n_pos, n_neg, index, label_ptr, edge_label)
+            return (res,) + _enqueue_walk_sizes(res) + (torch.cat(ids), local, n_pos, n_neg, index, label_ptr, edge_label, seed_time)
 
-        res, sizes_h, ev, input_id, local, n_pos, n_neg, index, label_ptr, edge_label = self._on_walk_stream(enqueue)
+        res, sizes_h, ev, input_id, local, n_pos, n_neg, index, label_ptr, edge_label, seed_time = self._on_walk_stream(enqueue)
         return LinkCallGroup(res, self._fs, smp.graph, b0, input_id, sizes_h, ev, self._stream, local, n_pos, n_neg, index, label_ptr,
-                             edge_label, self._mode)
+                             edge_label, self._mode, seed_time)
 
 
 class HeteroLinkCallGroup(HeteroCallGroup):
@@ -191,15 +207,25 @@ class HeteroLinkCallGroup(HeteroCallGroup):
     layer's output of type t (level 0 of the walk, batch-major); ``batch_ptr`` is the source type's; ``num_seeds_dict``;
     ``edge_label_index`` int64 [2, P]: row 0 indexes rows of ``out[src_t]``, row 1 rows of ``out[dst_t]`` — batch-major, positives
     first inside a batch; ``n_id[t][edge_label_index[i]]`` are the global endpoint ids;
-    ``edge_label`` [P] (None where the per-batch loader gives none), ``label_ptr`` int64 [G + 1], ``input_id``, ``n_pos``, ``n_neg``."""
+    ``edge_label`` [P] (None where the per-batch loader gives none), ``label_ptr`` int64 [G + 1], ``input_id``, ``n_pos``, ``n_neg``;
+    ``seed_time_dict`` {t: int64, one per seed row of type t, batch-major} (a TEMPORAL loader; None otherwise): the time every
+    unique endpoint starts the walk at — the ``edge_label_time`` of the first pair of its mini-batch that names it."""
 
     def __init__(self, rec, walk, feature_store, edge_type, first_batch, input_id, sizes_h, event, walk_stream, cseg, batch_ptr_dict,
-                 local_src, local_dst, n_pos, n_neg, edge_label_index, label_ptr, edge_label, mode):
+                 local_src, local_dst, n_pos, n_neg, edge_label_index, label_ptr, edge_label, mode, seed_time=None):
         super().__init__(rec, walk, feature_store, edge_type[0], first_batch, input_id, sizes_h, event, walk_stream, cseg)
         self.edge_type, self.seed_types = tuple(edge_type), (edge_type[0], edge_type[2])
         self.batch_ptr_dict = batch_ptr_dict
         self._local_src, self._local_dst, self.n_pos, self.n_neg, self._mode = local_src, local_dst, n_pos, n_neg, mode
         self.edge_label_index, self.label_ptr, self.edge_label = edge_label_index, label_ptr, edge_label
+        self._seed_time = seed_time
+
+    @property
+    def seed_time_dict(self):
+        if self._seed_time is None:
+            return None
+        self._wait()
+        return {t: v[:self.num_seeds_dict[t]] for t, v in self._seed_time.items()}
 
     def _wait(self):
         if self._ready:
@@ -209,7 +235,7 @@ class HeteroLinkCallGroup(HeteroCallGroup):
         if self._walk_stream is not None:     # the negatives and the de-duplications ran on the walk stream too
             main = torch.cuda.current_stream()
             for t in (self._local_src, self._local_dst, self.edge_label_index, self.label_ptr, self.edge_label, self.input_id,
-                      *self.batch_ptr_dict.values()):
+                      *self.batch_ptr_dict.values(), *(self._seed_time or {}).values()):
                 if t is not None:
                     t.record_stream(main)
 
@@ -254,14 +280,15 @@ class HeteroLinkCallGroupIterator(_PipelinedGroups):
         rs = torch.tensor([[_as_i64(hop_seed(self._rs + b0 + j, k)) for j in range(g)] for k in range(H * n_et)], dtype=torch.int64)
 
         def enqueue():
-            ids, srcs, dsts, labels, n_pos, n_neg = [], [], [], [], 0, 0
+            ids, srcs, dsts, labels, times, n_pos, n_neg = [], [], [], [], [], 0, 0
             for j in range(g):
-                input_id, src_all, dst_all, n_neg, label = self._batch_edges(b0 + j, self._rs + b0 + j)
+                input_id, src_all, dst_all, n_neg, label, t_all = self._batch_edges(b0 + j, self._rs + b0 + j)
                 n_pos = input_id.numel()
                 ids.append(input_id)
                 srcs.append(src_all)
                 dsts.append(dst_all)
                 labels.append(label)
+                times.append(t_all)
             srcs, dsts = torch.stack(srcs), torch.stack(dsts)       # [g, n_pos + n_neg] each: the batches of a group are equally long
             half = srcs.shape[1]
             if src_t == dst_t:
@@ -272,15 +299,25 @@ class HeteroLinkCallGroupIterator(_PipelinedGroups):
                 us, sseg, sbatch, local_src = _batched_first_unique(srcs, self._num_src)
                 ud, dseg, dbatch, local_dst = _batched_first_unique(dsts, self._num_dst)
                 lists = {src_t: (us, sseg, sbatch), dst_t: (ud, dseg, dbatch)}
+            seed_time = None
+            if smp.temporal:   # both endpoints of pair i start at time i; a unique endpoint at the time of its first pair
+                t = torch.stack(times)
+                if src_t == dst_t:
+                    seed_time = {src_t: graph_ops.rows_first_values(local, seg, torch.cat([t, t], 1))}
+                else:
+                    seed_time = {src_t: graph_ops.rows_first_values(local_src, sseg, t),
+                                 dst_t: graph_ops.rows_first_values(local_dst, dseg, t)}
+                lists = {k: v + (seed_time[k],) for k, v in lists.items()}
             walk = smp._call_group_walk(max(int(v[0].shape[0]) for v in lists.values()) // g or 1, g)
             rec = walk.run(None, None, rs, seed_lists=lists)
             sizes_h, ev, cseg = _enqueue_hetero_walk_sizes(rec, walk, src_t)
             ptrs = {t: v[1] for t, v in lists.items()}
             index, label_ptr = hetero_link_group_index(local_src, local_dst, ptrs[src_t], ptrs[dst_t], n_pos, n_neg)
             edge_label = None if labels[0] is None else torch.cat(labels)
-            return rec, walk, sizes_h, ev, cseg, ptrs, torch.cat(ids), local_src, local_dst, n_pos, n_neg, index, label_ptr, edge_label
+            return (rec, walk, sizes_h, ev, cseg, ptrs, torch.cat(ids), local_src, local_dst, n_pos, n_neg, index, label_ptr, edge_label,
+                    seed_time)
 
-        rec, walk, sizes_h, ev, cseg, ptrs, input_id, local_src, local_dst, n_pos, n_neg, index, label_ptr, edge_label = \
+        rec, walk, sizes_h, ev, cseg, ptrs, input_id, local_src, local_dst, n_pos, n_neg, index, label_ptr, edge_label, seed_time = \
             self._on_walk_stream(enqueue)
         return HeteroLinkCallGroup(rec, walk, self._fs, self._etype, b0, input_id, sizes_h, ev, self._stream, cseg, ptrs, local_src,
-                                   local_dst, n_pos, n_neg, index, label_ptr, edge_label, self._mode)
+                                   local_dst, n_pos, n_neg, index, label_ptr, edge_label, self._mode, seed_time)

@@ -287,7 +287,8 @@ class LinkLoader:
         out in CALL GROUPS: ``LinkCallGroup`` objects (``loader/link_call_group.py``), each the block-diagonal union of its
         mini-batches with a lazy ``x``, per-layer trimmed graphs and ONE ``edge_label_index`` / ``edge_label`` over the seed
         rows of the last layer's output — what ``wholegraph_amd.nn.link_bce_with_logits`` takes.  Homogeneous graphs, uniform
-        or positively-weighted sampling with positive fan-outs."""
+        or positively-weighted sampling with positive fan-outs; TEMPORAL loaders (``time_attr`` with ``edge_label_time``) inside
+        ``NeighborSampler.temporal_call_groups_ok()`` — every unique endpoint starts at the time of its first seed edge."""
         from .link_call_group import LinkCallGroupIterator
         self.__refuse_call_groups("call_groups", "heterogeneous graphs are not supported here (these link call groups are "
                                   "homogeneous): use hetero_call_groups()" if self.__hetero else None)
@@ -301,7 +302,9 @@ class LinkLoader:
         objects (``loader/link_call_group.py``) — a ``HeteroCallGroup`` (``x_dict``, ``layer_graph(j)``, ...) whose seeds are the
         mini-batches' unique seed-edge endpoints of the seed edge type's two node types, with ONE ``edge_label_index`` whose rows
         index the last layer's output of the source and of the destination type: what ``nn.link_bce_with_logits(h[src_t],
-        h[dst_t], grp.edge_label_index, grp.edge_label)`` and ``nn.EdgeDecoder`` take.  Refuses what ``call_groups()`` refuses."""
+        h[dst_t], grp.edge_label_index, grp.edge_label)`` and ``nn.EdgeDecoder`` take.  TEMPORAL loaders (``time_attr`` with
+        ``edge_label_time``) inside ``HeteroNeighborSampler.temporal_call_groups_ok()`` run on the temporal walk
+        (``seed_time_dict``).  Refuses what ``call_groups()`` refuses."""
         from .link_call_group import HeteroLinkCallGroupIterator
         self.__refuse_call_groups("hetero_call_groups", None if self.__hetero else
                                   "this graph is homogeneous: use call_groups()")
@@ -318,15 +321,20 @@ class LinkLoader:
             pass
         elif self.__raw:
             reason = "sampler-output mode (as_sampler_output=True) hands out SamplerOutput objects, not call groups"
-        elif self.__time is not None or smp.temporal:
-            reason = "temporal seeds (edge_label_time / time_attr) are not supported"
+        elif self.__time is not None and not smp.temporal:
+            reason = ("temporal seeds: edge_label_time without time_attr is not supported (the call-group walk samples "
+                      "temporally when both are given)")
         elif smp.disjoint:
             reason = "disjoint sampling is not supported"
         elif getattr(smp, "with_replacement", False):
             reason = "sampling with replacement is not supported"
         elif not all(f > 0 for f in fanouts):
             reason = "fan-out -1 (all neighbours) is not supported: the call-group walk needs positive fan-outs"
-        elif not smp.call_groups_ok():
+        elif smp.temporal and not smp.temporal_call_groups_ok():
+            reason = ("this temporal sampler configuration does not run on the call-group walk: temporal call groups need "
+                      "time_attr together with edge_label_time, int64 edge times, fan-outs 1..256, no replacement, not disjoint, "
+                      "and strictly positive weights when biased")
+        elif not smp.temporal and not smp.call_groups_ok():
             reason = "this sampler configuration does not run on the call-group walk (biased sampling needs strictly positive weights and fan-outs <= 256)"
         elif not self.__eli.is_cuda:
             reason = "the call-group walk only exists on the GPU"
@@ -335,15 +343,16 @@ class LinkLoader:
 
     def __call_group_epoch(self):
         """(order, random state, ``batch_edges(b, batch_seed)``) of one epoch: the loader's own per-batch recipe — the seed-edge
-        ids of mini-batch b, its endpoints with the negatives of the batch's generator, its labels."""
+        ids of mini-batch b, its endpoints with the negatives of the batch's generator, its labels, and the time of every
+        pair (negatives included; None without ``edge_label_time``)."""
         perm, seed = self.__epoch()
         dev, bs = self.__eli.device, self.__batch_size
 
         def batch_edges(b, batch_seed):
             ix = perm[b * bs:(b + 1) * bs]
             gen = torch.Generator(device=dev).manual_seed(batch_seed & 0x7FFFFFFFFFFFFFFF)
-            src_all, dst_all, n_neg, _ = self.__with_negatives(self.__eli[0, ix], self.__eli[1, ix], ix, gen)
-            return self.__input_id[ix], src_all, dst_all, n_neg, self.__edge_label(ix, ix.numel(), n_neg)
+            src_all, dst_all, n_neg, t_all = self.__with_negatives(self.__eli[0, ix], self.__eli[1, ix], ix, gen)
+            return self.__input_id[ix], src_all, dst_all, n_neg, self.__edge_label(ix, ix.numel(), n_neg), t_all
 
         return perm, seed, batch_edges
 

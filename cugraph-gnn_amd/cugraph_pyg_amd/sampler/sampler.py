@@ -466,7 +466,8 @@ class HeteroNeighborSampler:
         if key not in self._walks:
             # (the readers slice every list by the sizes read back: no -1 padding of the capacity slack)
             self._walks[key] = HeteroPygWalk(self.graphs, batch_size, self.fanout, n_batches, biased=self.biased,
-                                             num_nodes=self.num_nodes, pad_unique=False)
+                                             num_nodes=self.num_nodes, pad_unique=False,
+                                             temporal_comparison=self.temporal_comparison if self.temporal else None)
         return self._walks[key]
 
     def call_groups_ok(self) -> bool:
@@ -477,17 +478,40 @@ class HeteroNeighborSampler:
         return biased_ok and (not self.temporal) and (not self.disjoint) and (not self.with_replacement) and all(
             g.col.dtype == torch.int64 for g in self.graphs.values())
 
+    def temporal_call_groups_ok(self) -> bool:
+        """Can this TEMPORAL configuration run as call groups (``LinkNeighborLoader.call_groups()`` /
+        ``hetero_call_groups()`` with ``edge_label_time``)?  ``NeighborSampler.temporal_call_groups_ok`` for the heterogeneous
+        walk: temporal, not disjoint, no replacement, every fan-out in 0..256 (a 0 skips that hop of the edge type; the
+        loaders ask for positive fan-outs on top), biased weights strictly positive, int64 columns and times.
+        ``call_groups_ok()`` stays False for a temporal sampler: ``sample_batches``, ``fetch_plan``, ``FetchPadder`` and
+        ``for batch in loader`` keep the one-batch-at-a-time temporal path."""
+        if not self.temporal or self.disjoint or self.with_replacement:
+            return False
+        if not all(0 <= f <= 256 for v in self.fanout.values() for f in v):
+            return False
+        if not all(g.col.dtype == torch.int64 and g.time is not None and g.time.dtype == torch.int64 for g in self.graphs.values()):
+            return False
+        if self.biased and self._positive_weights is None:
+            self._positive_weights = all(bool((g.weight > 0).all()) for g in self.graphs.values())
+        return (not self.biased) or bool(self._positive_weights)
+
     def _walk_capacity_per_seed(self):
         """(device bytes, largest node + edge slots of one call, node rows) ONE seed of a call group costs in the heterogeneous
         walk (``wholegraph_amd.fused.HeteroPygWalk``): its buffers are capacity-sized — a hop's frontier of a node type is
         everything the previous hop could have added to that type, an edge type's call holds frontier x fan-out edge slots —
         and all calls of a group stay alive until the group is consumed.  The worst seed type counts (the sampler does not
-        know which type a loader seeds).  None when a fan-out is not positive (sample-all: no capacity bound)."""
+        know which type a loader seeds).  None when a fan-out is not positive (sample-all: no capacity bound).  A TEMPORAL
+        sampler pays the temporal hop's workspace and the time lists on top: 8 bytes per node slot (the type's reach times
+        after the call) and per edge slot (the call's ``frontier_time_out``) of capacity."""
         from wholegraph_amd import _lib as L
         hops = len(next(iter(self.fanout.values())))
         if any(f <= 0 for v in self.fanout.values() for f in v):
             return None
         types = sorted({t for et in self.graphs for t in (et[0], et[2])})
+        max_row_len = {}
+        if self.temporal:   # (sizes the key slabs of the temporal hop, as in HeteroPygWalk)
+            for et, g in self.graphs.items():
+                max_row_len[et] = max(int((g.row_ptr[1:] - g.row_ptr[:-1]).max()), 1) if g.row_ptr.shape[0] > 1 else 1
         worst = None
         for seed_type in types:
             gained = {t: 0 for t in types}
@@ -504,7 +528,12 @@ class HeteroNeighborSampler:
                     # per edge slot: local row / col + two scratch columns (int32), edge id, new node, its batch, next frontier
                     # entry, its batch; per node slot of the source type's list: id + batch; the frontier's offsets
                     total += ec * (4 * 4 + 8 + 8 + 4 + 8 + 4) + nc * (8 + 4) + (fc + 1) * 4
-                    ws = max(ws, L.lib().wgamd_sample_hop_workspace_bytes(4096 * max(nc, fc), 4096 * ec, L.DT_INT64) / 4096.0)
+                    if self.temporal:   # the type's reach times after the call, the call's frontier_time_out; the temporal plan
+                        total += (nc + ec) * 8 + ec * 8
+                        ws = max(ws, L.lib().wgamd_sample_hop_temporal_workspace_bytes(4096 * max(nc, fc), 4096 * ec, L.DT_INT64,
+                                                                                       max_row_len[et]) / 4096.0)
+                    else:
+                        ws = max(ws, L.lib().wgamd_sample_hop_workspace_bytes(4096 * max(nc, fc), 4096 * ec, L.DT_INT64) / 4096.0)
                     slots = max(slots, nc + ec)
                     cap[et[0]] += ec
                     nxt[et[0]] += ec

@@ -322,6 +322,10 @@ SYMBOLS = {
     "wgamd_rows_first_unique_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "wgamd_rows_first_unique": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_size_t, c_int, c_void_p]),
+    "wgamd_rows_first_values": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    # reach times of the temporal heterogeneous call-group walk (wg_reach_time.hip)
+    "wgamd_reach_time_append": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int64,
+                                        c_void_p, c_void_p]),
     # GCN layer (wg_gcn.hip)
     "wgamd_gcn_layer_supported": (c_int, [c_int, c_int]),
     "wgamd_gcn_layer_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,

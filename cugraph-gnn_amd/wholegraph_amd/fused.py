@@ -623,9 +623,13 @@ class HeteroPygWalk:
     No host synchronisation inside ``run``; sizes are read once in ``finalize_batches``."""
 
     def __init__(self, graphs, batch_size: int, fanout, n_batches: int, biased: bool = False, num_nodes=None,
-                 pad_unique: bool = True):
+                 pad_unique: bool = True, temporal_comparison: str = None):
         """``num_nodes``: {node type: vertex count} — with it the renumber table of every hop packs (batch, id, position)
-        into one word (ids of a type are then known to be below its count).  ``pad_unique``: see ``NoSyncWalk``."""
+        into one word (ids of a type are then known to be below its count).  ``pad_unique``: see ``NoSyncWalk``.
+        ``temporal_comparison`` (a name of ``TEMPORAL_COMPARISONS``): the walk is TEMPORAL — every (hop, edge type) call goes
+        through ``wgamd_sample_hop_pyg_temporal_nosync`` on the edge type's ``time`` (int64 per CSR slot, fan-outs 0..256,
+        with or without weights), ``run`` takes the seeds' times and a reach-time list is kept per node type, parallel to
+        its vertex list (``wgamd_reach_time_append`` after every call)."""
         self.flags = 0 if pad_unique else HOP_NO_UNIQUE_PAD
         self.biased = bool(biased)
         self.num_nodes = dict(num_nodes) if num_nodes else {}
@@ -651,15 +655,33 @@ class HeteroPygWalk:
         # 32-bit twins of the column arrays (type-local ids of the SOURCE type) where that type's vertex count is known
         self.col32 = {et: compact_columns(graphs[et].col, int(self.num_nodes.get(et[0], 0))) for et in self.etypes}
         self.max_row_len = {}
+        self.comparison, self.time = 0, {}
+        if temporal_comparison is not None:
+            if temporal_comparison not in TEMPORAL_COMPARISONS:
+                raise ValueError(f"unknown temporal_comparison {temporal_comparison!r}; expected one of "
+                                 f"{sorted(TEMPORAL_COMPARISONS)}")
+            self.comparison = TEMPORAL_COMPARISONS[temporal_comparison]
+            for et in self.etypes:
+                g = graphs[et]
+                assert g.time is not None and g.time.is_cuda and g.time.dtype == torch.int64, \
+                    "the temporal walk needs an int64 time per CSR slot on every edge type"
+                assert g.time.shape[0] == g.col.shape[0]
+                assert all(f <= 256 for f in self.fanout[et]), "the temporal walk needs fan-outs <= 256"
+                self.time[et] = g.time.contiguous()
         if self.biased:   # per edge type: weights + maximum degree (sizes the key slabs of the biased hop)
             for et in self.etypes:
                 g = graphs[et]
                 assert g.weight is not None and g.weight.dtype in (torch.float32, torch.float64)
                 assert all(f <= 256 for f in self.fanout[et])
+        if self.biased or self.comparison:   # (the temporal hop runs on the biased path, with or without weights)
+            for et in self.etypes:
+                g = graphs[et]
                 self.max_row_len[et] = max(int((g.row_ptr[1:] - g.row_ptr[:-1]).max()), 1) if g.row_ptr.shape[0] > 1 else 1
 
     def _workspace(self, node_cap, edge_cap, max_row_len=0):
-        if max_row_len > 0:
+        if self.comparison:
+            need = L.lib().wgamd_sample_hop_temporal_workspace_bytes(node_cap, edge_cap, self.wm_dtype, max_row_len)
+        elif max_row_len > 0:
             need = L.lib().wgamd_sample_hop_weighted_workspace_bytes(node_cap, edge_cap, self.wm_dtype, max_row_len)
         else:
             need = L.lib().wgamd_sample_hop_workspace_bytes(node_cap, edge_cap, self.wm_dtype)
@@ -680,7 +702,15 @@ class HeteroPygWalk:
             f_seg = torch.empty(G + 1, dtype=torch.int32, device=dev)
             L.check(L.lib().wgamd_frontier_list(nodes.data_ptr(), int(nodes.shape[0]), seg.data_ptr(), begin.data_ptr(), G, int(cap),
                                                 ids.data_ptr(), b.data_ptr(), f_seg.data_ptr(), get_stream()), "wgamd_frontier_list")
-            return ids, b, f_seg, begin
+            if not self.comparison:
+                return ids, b, f_seg, begin
+            # the frontier's reach times: the same gather over the type's time list (both int64, parallel lists)
+            time = st["time"].contiguous()
+            assert time.shape[0] >= nodes.shape[0]
+            f_time = torch.empty(cap, dtype=torch.int64, device=dev)
+            L.check(L.lib().wgamd_frontier_list(time.data_ptr(), int(nodes.shape[0]), seg.data_ptr(), begin.data_ptr(), G, int(cap),
+                                                f_time.data_ptr(), b.data_ptr(), f_seg.data_ptr(), get_stream()), "wgamd_frontier_list")
+            return ids, b, f_seg, begin, f_time
         size_b = st["seg"][1:] - st["seg"][:-1]
         cnt = (size_b - st["begin"]).to(torch.int32)
         f_seg = torch.zeros(G + 1, dtype=torch.int32, device=dev)
@@ -688,17 +718,28 @@ class HeteroPygWalk:
         p = torch.arange(cap, dtype=torch.int32, device=dev)
         b = torch.searchsorted(f_seg[1:].contiguous(), p, right=True).clamp_(max=G - 1)
         src = st["seg"][:-1][b].long() + st["begin"][b].long() + (p - f_seg[:-1][b]).long()
-        ids = st["nodes"][src.clamp_(0, st["nodes"].shape[0] - 1)]
-        return ids.contiguous(), b.to(torch.int32).contiguous(), f_seg, st["begin"].contiguous()
+        src = src.clamp_(0, st["nodes"].shape[0] - 1)
+        ids = st["nodes"][src]
+        out = (ids.contiguous(), b.to(torch.int32).contiguous(), f_seg, st["begin"].contiguous())
+        return out + (st["time"][src].contiguous(),) if self.comparison else out
 
-    def run(self, seed_type: str, seeds: torch.Tensor, random_seeds: torch.Tensor, seed_lists=None):
+    def run(self, seed_type: str, seeds: torch.Tensor, random_seeds: torch.Tensor, seed_lists=None,
+            seed_time: torch.Tensor = None):
         """``seeds`` [G*B] type-local ids of ``seed_type``; ``random_seeds`` int64 [hops * n_etypes, G]: row
         ``h * n_etypes + t`` holds the per-batch seeds of hop h / edge type t (sorted order).
         ``seed_lists`` (link prediction: both endpoint types of the seed edges start the walk, with ragged per-batch lists):
         {node type: (ids padded to a capacity, int32 offsets [G+1], int32 batch of every live entry)} replaces
-        ``seed_type`` / ``seeds``."""
+        ``seed_type`` / ``seeds``.  A TEMPORAL walk (``temporal_comparison=``) takes the seeds' times too, and only it does:
+        ``seed_time`` int64 [G*B] beside ``seeds``, or a fourth entry per type of ``seed_lists`` (int64, padded like the ids).
+        ``rec["state"][t]["time"]`` is then the reach time of every vertex of ``rec["state"][t]["nodes"]``."""
         lib, dev, G = L.lib(), self.dev, self.G
         assert seed_lists is not None or (seeds.dtype == torch.int64 and seeds.shape[0] == G * self.B and seeds.is_cuda)
+        temporal = bool(self.comparison)
+        given = seed_time is not None if seed_lists is None else all(len(v) == 4 for v in seed_lists.values())
+        if seed_lists is not None and (seed_time is not None or len({len(v) for v in seed_lists.values()}) > 1):
+            raise ValueError("seed_lists carry their times as a fourth entry per type, for every type or for none")
+        if given != temporal:
+            raise ValueError("seed times go with a temporal walk (temporal_comparison=...), and only with one")
         rs = random_seeds.to(device=dev, dtype=torch.int64).contiguous()
         assert rs.shape == (self.hops * len(self.etypes), G)
         i32 = dict(dtype=torch.int32, device=dev)
@@ -710,11 +751,20 @@ class HeteroPygWalk:
             state[seed_type] = dict(nodes=seeds, batch=self.seed_batch, seg=self.seed_seg, cap=G * self.B,
                                     begin=self.zeros_g, gained_cap=G * self.B)
         else:
-            for t, (ids, seg, batch) in seed_lists.items():
+            for t, (ids, seg, batch, *_) in seed_lists.items():
                 assert ids.dtype == torch.int64 and seg.dtype == torch.int32 and batch.dtype == torch.int32
                 assert seg.shape[0] == G + 1 and batch.shape[0] == ids.shape[0]
                 state[t] = dict(nodes=ids.contiguous(), batch=batch.contiguous(), seg=seg.contiguous(), cap=int(ids.shape[0]),
                                 begin=self.zeros_g, gained_cap=int(ids.shape[0]))
+        if temporal:   # per node type: the time every vertex of its list was reached at (a type without seeds: an empty list)
+            times = {seed_type: seed_time} if seed_lists is None else {t: v[3] for t, v in seed_lists.items()}
+            for t in self.ntypes:
+                tt = times.get(t)
+                if tt is None:
+                    state[t]["time"] = torch.zeros(1, dtype=torch.int64, device=dev)
+                    continue
+                assert tt.is_cuda and tt.dtype == torch.int64 and tt.shape[0] == state[t]["nodes"].shape[0]
+                state[t]["time"] = tt.contiguous()
         rec = dict(calls=[], sizes=[{t: (state[t]["seg"][1:] - state[t]["seg"][:-1]) for t in self.ntypes}])
         keep = [rs]
         # B seeds per batch: a batch's share of every later frontier and edge capacity bounds what it can hold
@@ -734,7 +784,7 @@ class HeteroPygWalk:
                     rec["calls"].append(None)
                     continue
                 g = self.graphs[et]
-                f_ids, f_batch, f_seg, f_l0 = fr
+                f_ids, f_batch, f_seg, f_l0 = fr[:4]
                 fc = f_caps[dst_t]
                 ec = fc * m
                 st = state[src_t]
@@ -763,7 +813,23 @@ class HeteroPygWalk:
                             torch_dtype_to_wm(g.weight.dtype) if self.biased else 0, mrl,
                             int(self.num_nodes.get(src_t, 0)),   # the renumbered ids are type-local ids of the SOURCE type
                             flags | (0 if c32 is None else HOP_COL_INT32))
-                L.check(lib.wgamd_sample_hop_pyg_nosync(_ct.byref(p), get_stream()), "wgamd_sample_hop_pyg_nosync")
+                if not temporal:
+                    L.check(lib.wgamd_sample_hop_pyg_nosync(_ct.byref(p), get_stream()), "wgamd_sample_hop_pyg_nosync")
+                else:
+                    # the call's own frontier_time_out is not the type's next frontier time list (other edge types of the hop
+                    # add to the same list, and every call rebuilds it batch-major): the old list's times move with their
+                    # batch, the vertices this call saw first take the call's times
+                    f_time_out = torch.empty(ec, dtype=torch.int64, device=dev)
+                    time_out = torch.empty(nc + ec, dtype=torch.int64, device=dev)
+                    tb = _PygHopTime(self.time[et].data_ptr(), fr[4].data_ptr(), f_time_out.data_ptr(), self.comparison)
+                    L.check(lib.wgamd_sample_hop_pyg_temporal_nosync(_ct.byref(p), _ct.byref(tb), get_stream()),
+                            "wgamd_sample_hop_pyg_temporal_nosync")
+                    L.check(lib.wgamd_reach_time_append(st["time"].data_ptr(), int(st["time"].shape[0]), st["seg"].data_ptr(),
+                                                        f_time_out.data_ptr(), ec, f_out_seg.data_ptr(), nodes_out_batch.data_ptr(),
+                                                        nodes_out_seg.data_ptr(), G, nc + ec, time_out.data_ptr(), get_stream()),
+                            "wgamd_reach_time_append")
+                    keep += [fr[4], f_time_out, st["time"]]
+                    st["time"] = time_out
                 keep += [scratch_r, scratch_c, f_out, f_out_batch, f_out_seg, f_out_l0, counts, f_ids, f_batch, f_l0,
                          st["nodes"], st["batch"], st["seg"]]
                 # (f_batch / f_local0 / frontier_cap: what a call-group consumer needs to place the hop's rows in the node list

@@ -79,3 +79,26 @@ def rows_first_unique(ends: torch.Tensor, n_ids: int):
     L.check(lib.wgamd_rows_first_unique(ends.data_ptr(), G, S, int(n_ids), uniq.data_ptr(), seg.data_ptr(), batch.data_ptr(),
                                         local.data_ptr(), ws.data_ptr(), ws.numel(), 1, stream), "wgamd_rows_first_unique")
     return uniq, seg, batch, local
+
+
+def rows_first_values(local: torch.Tensor, seg: torch.Tensor, values: torch.Tensor) -> torch.Tensor:
+    """``values`` int64 [G, S] taken at the FIRST position of every distinct id of a row: with ``local`` [G, S] / ``seg`` int32
+    [G + 1] as ``rows_first_unique`` returns them, int64 [G S] parallel to ``uniq`` — ``out[seg[g] + r]`` = the value at the
+    first position s of row g with ``local[g, s] == r``; zero from ``seg[G]`` on.  (The seed time of a de-duplicated endpoint of
+    a temporal link call group: the time of the first seed edge that names it.)  One launch and no read-back
+    (``wgamd_rows_first_values``) on the device inside ``rows_first_unique_supported``; the torch formulation otherwise, with
+    the same result."""
+    assert local.dim() == 2 and local.shape == values.shape and values.dtype == torch.int64 and seg.shape[0] == local.shape[0] + 1
+    G, S = local.shape
+    dev = local.device
+    if local.is_cuda and local.dtype == torch.int64 and seg.dtype == torch.int32 and rows_first_unique_supported(G, S, 1):
+        local, seg, values = local.contiguous(), seg.contiguous(), values.contiguous()
+        out = torch.empty(G * S, dtype=torch.int64, device=dev)
+        L.check(L.lib().wgamd_rows_first_values(local.data_ptr(), seg.data_ptr(), values.data_ptr(), G, S, out.data_ptr(),
+                                                get_stream()), "wgamd_rows_first_values")
+        return out
+    n = G * S
+    at = (seg[:-1].to(torch.int64).view(G, 1) + local.to(torch.int64)).reshape(-1)
+    first = torch.full((n,), n, dtype=torch.int64, device=dev).scatter_reduce_(0, at, torch.arange(n, device=dev), reduce="amin")
+    picked = values.reshape(-1)[first.clamp(max=max(n - 1, 0))]
+    return torch.where(first < n, picked, torch.zeros_like(picked))

@@ -409,6 +409,22 @@ wholememory_error_code_t wgamd_call_group_target_rows(const int* unique_seg, con
 wholememory_error_code_t wgamd_frontier_list(const int64_t* nodes, int64_t n_nodes, const int* seg, const int* begin, int n_batches,
                                              int64_t capacity, int64_t* ids, int* batch, int* f_seg, void* stream);
 
+/* Reach times of a node type's batch-major list across one TEMPORAL call of a heterogeneous call-group walk
+ * (csrc/wg_reach_time.hip).  The call appended to the list `nodes` (offsets node_seg [n_batches + 1], times time_in
+ * [time_in_cap], parallel to it) and left nodes_out: per batch the old list, then the vertices first seen by this call in
+ * first-appearance order (offsets nodes_out_seg, batch of every entry nodes_out_batch), whose times are the call's
+ * frontier_time_out (offsets frontier_out_seg).  For entry i of batch b at position l = i - nodes_out_seg[b], with
+ * n_old = node_seg[b + 1] - node_seg[b]:
+ *   time_out[i] = l < n_old ? time_in[node_seg[b] + l] : frontier_time_out[frontier_out_seg[b] + l - n_old]
+ * for i < min(nodes_out_seg[n_batches], capacity).  One launch, a thread per entry, no atomics, every size read from the
+ * device; a source index outside its capacity (time_in_cap / frontier_cap) or a batch outside [0, n_batches) writes nothing.
+ * time_in may be NULL when time_in_cap is 0 (a type that had no vertices yet). */
+wholememory_error_code_t wgamd_reach_time_append(const int64_t* time_in, int64_t time_in_cap, const int* node_seg,
+                                                 const int64_t* frontier_time_out, int64_t frontier_cap,
+                                                 const int* frontier_out_seg, const int* nodes_out_batch,
+                                                 const int* nodes_out_seg, int n_batches, int64_t capacity, int64_t* time_out,
+                                                 void* stream);
+
 /* One (hop, edge type) of a heterogeneous call group (wgamd_sample_hop_pyg_nosync outputs) in the form the layers consume:
  * dst_full[j] / dst_compact[j] = row of frontier entry j in the destination type's batch-major node list — all vertices of
  * the walk (segments seg_dst [G+1]) / the vertices discovered by hops 0-1 only (compact_seg_dst [G+1], int64; NULL with
@@ -884,6 +900,17 @@ size_t wgamd_rows_first_unique_workspace_bytes(int64_t n_rows, int64_t row_len);
 wholememory_error_code_t wgamd_rows_first_unique(const int64_t* ends, int64_t n_rows, int64_t row_len, int64_t n_ids, int64_t* uniq,
                                                  int* seg, int* batch, int64_t* local, void* workspace, size_t workspace_bytes,
                                                  int workspace_is_zeroed, void* stream);
+
+/* A value per distinct id of every row, taken at the id's FIRST position (the seed time of a de-duplicated endpoint is the time
+ * of the first seed edge that names it): with local / seg as wgamd_rows_first_unique leaves them and values int64
+ * [n_rows, row_len] parallel to ends,
+ *   out int64 [n_rows row_len]: out[seg[g] + local[g, s]] = values[g, s] for every first position s of row g; 0 from seg[n_rows] on
+ * — parallel to uniq.  Position s is a first position exactly when local[g, s] exceeds every earlier local[g, .] (the lists
+ * are numbered in order of first position).  One launch, one workgroup per row with the running maximum of the row in LDS,
+ * one store per first position, no atomics, nothing read back.  Domain: wgamd_rows_first_unique_supported(n_rows, row_len, 1).
+ * Whatever local and seg hold, nothing is written outside out. */
+wholememory_error_code_t wgamd_rows_first_values(const int64_t* local, const int* seg, const int64_t* values, int64_t n_rows,
+                                                 int64_t row_len, int64_t* out, void* stream);
 
 /* ---- GCN layer (csrc/wg_gcn.hip): torch_geometric.nn.GCNConv over a sampled hop ---------------------------------------------
  * The model of the reference's headline cugraph-pyg example (python/cugraph-pyg/cugraph_pyg/examples/gcn_dist_mnmg.py):
