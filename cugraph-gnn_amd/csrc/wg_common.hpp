@@ -266,6 +266,29 @@ struct rng_plan {
   }
 };
 
+// Run-time width flags -> types: `f` is a generic lambda called with one tag per flag, tag_t<decltype(tag)> is the type.
+template <typename T>
+struct type_tag {
+  using type = T;
+};
+template <typename Tag>
+using tag_t = typename Tag::type;
+template <typename F>
+void with_id_type(bool is64, F&& f)
+{
+  if (is64) f(type_tag<int64_t>{}); else f(type_tag<int32_t>{});
+}
+template <typename F>
+void with_id_types(bool seeds64, bool col64, F&& f)
+{
+  with_id_type(seeds64, [&](auto s) { with_id_type(col64, [&](auto c) { f(s, c); }); });
+}
+template <typename F>
+void with_weight_type(bool weights64, F&& f)
+{
+  if (weights64) f(type_tag<double>{}); else f(type_tag<float>{});
+}
+
 // ---- device-side utilities implemented in wg_scan.hip ---------------------------------------
 // out[0..n] (n+1 entries) = exclusive scan of in[0..n-1]; out[n] = total. in/out may alias.
 // `tmp` needs scan_tmp_ints(n) ints.  With `n_live_dev` (device int, <= n) the inputs past the live
@@ -325,10 +348,6 @@ inline int64_t weighted_list_ints(int64_t cap)
 }
 void weighted_count_enqueue(const int64_t* row_ptr, const void* seeds, bool seeds64, dev_count n, int M, int* cnt,
                             int* big_list, hipStream_t stream);
-void weighted_sample_enqueue(const int64_t* row_ptr, const void* col, bool col64, const void* weights, bool weights64,
-                             const void* seeds, bool seeds64, dev_count n, int M, rng_plan random_seed, const int* offsets,
-                             int* big_list, uint32_t* slab, int64_t slab_len, void* dst, int* src_lid,
-                             int64_t* edge_gid, hipStream_t stream);
 // TEMPORAL hop: candidate slot s of a frontier row reached at time t_v qualifies when `comparison` holds between csr_time[s]
 // and t_v (1: strictly increasing, t_e > t_v; 2: monotonically increasing, >=; 3: strictly decreasing, <; 4: monotonically
 // decreasing, <=) and its weight, rounded to float, is positive.  The weighted kernels draw with the EFFECTIVE weight (the
@@ -351,12 +370,13 @@ struct time_filter {
     return (passes(slot, t_v) && x > 0.f) ? x : 0.f;
   }
 };
-// the picks of weighted_sample_enqueue drawn with the effective weights of `tf` (`weights` may be NULL: 1 per qualifying
-// slot): min(row length, M) picks per row at `offsets`, non-qualifying ones included — the caller drops those
-void weighted_temporal_sample_enqueue(const int64_t* row_ptr, const void* col, bool col64, const void* weights, bool weights64,
-                                      const void* seeds, bool seeds64, dev_count n, int M, rng_plan random_seed,
-                                      const int* offsets, int* big_list, uint32_t* slab, int64_t slab_len, void* dst,
-                                      int* src_lid, int64_t* edge_gid, time_filter tf, hipStream_t stream);
+// the biased hop's picks at `offsets`.  With `tf` (nullable: the temporal hop) they are drawn with its effective weights
+// (`weights` may then be NULL: 1 per qualifying slot): min(row length, M) picks per row, non-qualifying ones included — the
+// caller drops those
+void weighted_sample_enqueue(const int64_t* row_ptr, const void* col, bool col64, const void* weights, bool weights64,
+                             const void* seeds, bool seeds64, dev_count n, int M, rng_plan random_seed, const int* offsets,
+                             int* big_list, uint32_t* slab, int64_t slab_len, void* dst, int* src_lid,
+                             int64_t* edge_gid, const time_filter* tf, hipStream_t stream);
 // renumbering: table of `slots` (power of two >= 2*(T.host+E.host)) entries, slot_of[T.host+E.host],
 // rank[E.host+1], scan_tmp[scan_tmp_ints(E.host+1)].  unique_out may be NULL for `prepare`.
 int64_t append_unique_slots(int64_t capacity);

@@ -238,9 +238,8 @@ void run_hop(hop_args a)
     const time_filter tf{a.csr_time, a.frontier_time, a.comparison};
     weighted_count_enqueue(a.csr_row_ptr, s_targets, i64, S, a.M, cnt, big_list, st);
     exclusive_scan_i32(cnt, pad_off, s_cap, scan_tmp, st, s_n_dev);
-    weighted_temporal_sample_enqueue(a.csr_row_ptr, a.csr_col, col64, a.csr_weight, a.weight64, s_targets, i64, S, a.M, a.rng,
-                                     pad_off, big_list, reinterpret_cast<uint32_t*>(base + w.slab), w.slab_len, pad_nbr, nullptr,
-                                     pad_gid, tf, st);
+    weighted_sample_enqueue(a.csr_row_ptr, a.csr_col, col64, a.csr_weight, a.weight64, s_targets, i64, S, a.M, a.rng, pad_off,
+                            big_list, reinterpret_cast<uint32_t*>(base + w.slab), w.slab_len, pad_nbr, nullptr, pad_gid, &tf, st);
     const int grid = (int)ceil_div(s_cap * 16, (int64_t)256);
     if (a.weight64)
       temporal_count_kernel<double><<<grid, 256, 0, st>>>(pad_off, pad_gid, static_cast<const double*>(a.csr_weight), tf, S, cnt);
@@ -265,7 +264,7 @@ void run_hop(hop_args a)
     exclusive_scan_i32(cnt, a.offsets, s_cap, scan_tmp, st, s_n_dev);  // offsets[cap] = #edges
     weighted_sample_enqueue(a.csr_row_ptr, a.csr_col, col64, a.csr_weight, a.weight64, s_targets, i64, S, a.M, a.rng, a.offsets,
                             big_list, reinterpret_cast<uint32_t*>(base + w.slab), w.slab_len, nbr, a.center_row, a.edge_gid,
-                            st);
+                            nullptr, st);
   } else {
     int64_t* row_start = reinterpret_cast<int64_t*>(base + w.row_start);
     int* row_deg       = reinterpret_cast<int*>(base + w.row_deg);

@@ -172,6 +172,7 @@ __device__ __forceinline__ ColT col_at(const ColT* __restrict__ col, int64_t at)
 }
 
 constexpr int kWalkGrid = 256 * 16;   // workgroups of the walk's bounded, grid-striding launches (16 per CU: 8 resident, 8 queued)
+constexpr int kMultiK   = 4;          // seeds a lane group of sample_uniform_multi_kernel keeps in flight
 
 template <typename ColT>
 __device__ __forceinline__ void emit(ColT* dst, int* src_lid, int64_t* edge_gid, int64_t out, ColT v,
@@ -291,27 +292,13 @@ __global__ void __launch_bounds__(256) sample_uniform_halfwave_kernel(const int6
                                                                       int* __restrict__ src_lid,
                                                                       int64_t* __restrict__ edge_gid,
                                                                       const int64_t* __restrict__ row_start,
-                                                                      const int* __restrict__ row_deg,
-                                                                      const loc_rec* __restrict__ recs = nullptr)
+                                                                      const int* __restrict__ row_deg)
 {
   const int n    = n_.get();
   const int lane = threadIdx.x & 63;
   const int hl   = lane & (LANES - 1);   // lane inside my group
   const int hb   = lane & ~(LANES - 1);  // first lane of my group
-  int i          = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / LANES);  // seed index
-  loc_rec rec{};
-  if (recs) {
-    // vertex-grouped order: XCD x (workgroups are dealt to the XCDs round-robin) walks the x-th eighth of the records
-    constexpr int kGroups = 256 / LANES;   // entries per workgroup
-    const int per_x = ((n + 7) / 8 + kGroups - 1) / kGroups * kGroups;
-    const int k     = (int)(blockIdx.x >> 3) * kGroups + (int)threadIdx.x / LANES;
-    const int j     = (int)(blockIdx.x & 7) * per_x + k;
-    i               = n;   // (nothing to do)
-    if (k < per_x && j < n) {
-      rec = recs[j];
-      i   = rec.i;
-    }
-  }
+  const int i    = (int)(((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / LANES);  // seed index
   // The draw of lane t depends only on (seed index, t), not on the row: it is computed FIRST, so that the ~60 ALU
   // instructions of the table jump run under the latency of the dependent seeds -> row_ptr loads issued right after
   // (rows that turn out to be copied whole waste the draw, which is cheaper than putting it on the critical path).
@@ -319,11 +306,7 @@ __global__ void __launch_bounds__(256) sample_uniform_halfwave_kernel(const int6
   if (i < n && hl < M) {
     uint64_t random_seed;
     int i_local;
-    if (recs) {
-      i_local     = rec.i_local;
-      random_seed = rng.seeds_dev ? rng.seeds_dev[rec.batch] : rng.seed;
-    } else
-      rng.resolve(i, random_seed, i_local);
+    rng.resolve(i, random_seed, i_local);
     // stream index = i_local*32 + lane; the table jump covers every index below 2^31, the generic
     // loop keeps the reference's sign-extension semantics beyond that
     if (i_local < (1 << 26)) {
@@ -336,11 +319,7 @@ __global__ void __launch_bounds__(256) sample_uniform_halfwave_kernel(const int6
   }
   int64_t start = 0;
   int N = 0, base = 0;
-  if (i < n && recs) {
-    start = rec.start;
-    N     = rec.deg;
-    base  = rec.base;
-  } else if (i < n) {
+  if (i < n) {
     if (row_start) {   // written by the count kernel: one coalesced read instead of the seeds -> row_ptr chain
       start = row_start[i];
       N     = row_deg[i];
@@ -388,21 +367,23 @@ __global__ void __launch_bounds__(256) sample_uniform_halfwave_kernel(const int6
   }
 }
 
-// ---- the same hop for the no-sync walk: lane groups as wide as the fan-out, K seeds per group ----------------------------
-// (row_start / row_deg come from the count kernel.)  What round 6 measured on the products hop 2 (1.6 M seeds x fan-out 10):
-// the launch is bound by VALU issue, not by memory — the vertex-grouped order below cut the lines it fetches 2.7x (PMC) and
-// its duration by 2 %, four seeds in flight per group instead of one (K) bought 14 %; a wave spends ~2,000 cycles on four
-// seeds, a third of them in the quarter-rate 64-bit multiplies of the PCG jump.  So the lanes are what is scarce: a group is
-// GW = the fan-out lanes wide (10 -> six seeds per wave where the 16-lane groups of sample_uniform_halfwave_kernel hold
-// four with six lanes idle; fan-out 5 -> twelve), and takes K consecutive seeds whose loads are issued stage by stage.
-// Same draws (stream 32 i_local + t), same output positions.
-template <typename SeedT, typename ColT, int GW, int K, bool EXACT>
+// ---- the same hop for the no-sync walk: lane groups of 8 / 16 / 32 lanes, K = 4 seeds per group -------------------------------
+// (row_start / row_deg come from the count kernel.)  What round 6 measured on the products hop 2 (1.6 M seeds x fan-out 10;
+// profiles/r06): the launch is bound by VALU issue, not by memory — four seeds in flight per group instead of one bought
+// 14 %, the vertex-grouped order above cut the lines it fetches 2.7x (PMC) and its duration by 2 %; a wave spends ~2,000 cycles
+// on four seeds, a third of them in the quarter-rate 64-bit multiplies of the PCG jump.  So the lanes are what is scarce: a
+// group is GW lanes wide — the next of 8 / 16 / 32 at or above the fan-out, or (EXACT, the grouped order at the BASELINE
+// fan-outs 5 / 10 / 15 / 25) the fan-out itself: 10 -> six seeds per wave instead of four — and takes K consecutive seeds
+// whose loads are issued stage by stage.  Same draws (stream 32 i_local + t), same output positions as
+// sample_uniform_halfwave_kernel.
+template <typename SeedT, typename ColT, int GW, bool EXACT>
 __global__ void __launch_bounds__(256)
 sample_uniform_multi_kernel(const ColT* __restrict__ col, dev_count n_, int M_rt, rng_plan rng, const int* __restrict__ offsets,
                             ColT* __restrict__ dst, int* __restrict__ src_lid, int64_t* __restrict__ edge_gid,
                             const int64_t* __restrict__ row_start, const int* __restrict__ row_deg,
                             const loc_rec* __restrict__ recs)
 {
+  constexpr int K       = kMultiK;
   constexpr int kGPW    = 64 / GW;        // lane groups per wave (the lanes past kGPW * GW idle)
   constexpr int kGroups = 4 * kGPW;       // lane groups per workgroup
   constexpr int kRounds = GW <= 2 ? 1 : GW <= 4 ? 2 : GW <= 8 ? 3 : GW <= 16 ? 4 : 5;   // pointer jumping: ceil(log2 GW)
@@ -775,9 +756,6 @@ __device__ __forceinline__ float ares_key(float w, Pcg32& g, bool* redrawn = nul
   if (redrawn != nullptr && zero_draws > 0) *redrawn = true;   // more than three draws for this key
   int one_bit = __clzll((long long)x) + zero_draws * 64;
   u *= exp2f((float)(-one_bit));
-#ifdef WG_TUNE_CHEAP_KEY   // sizing experiment only: what the hop costs without log1pf and the two IEEE divisions
-  return u * 1.442695f * __builtin_amdgcn_rcpf(w);
-#endif
   return (log1pf(u) / logf(2.0f)) * (1.0f / w);
 }
 
@@ -1725,15 +1703,9 @@ void uniform_launch(const int64_t* row_ptr, const ColT* col, const SeedT* seeds,
   const int cap = n.host;
   if (cap <= 0) return;
   if (M > 0 && M <= 32 && row_start != nullptr) {
-    // the no-sync walk.  List order (the default) and a fan-out of 5 / 10 / 15 / 25: one seed per lane
-    // (sample_uniform_lane_kernel).  Otherwise lane groups with K seeds per group (WGAMD_SAMPLE_K = 1 | 2 | 4, default 4; it
-    // means nothing to the lane kernel), optionally in vertex-grouped order (see loc_rec): two short launches build the
-    // records, the sampling kernel walks them
-    static const int K = [] {
-      const char* e = getenv("WGAMD_SAMPLE_K");
-      const int k   = e ? atoi(e) : 4;
-      return k == 1 || k == 2 ? k : 4;
-    }();
+    // the no-sync walk.  The fan-outs a kernel is built for (the BASELINE fan-outs 5 / 10 / 15 / 25): one seed per lane in list
+    // order, lane groups exactly as wide as the fan-out in vertex-grouped order (see loc_rec: two short launches build the
+    // records, the lane groups walk them).  Every other fan-out: lane groups of the next width of 8 / 16 / 32, in either order.
     const loc_rec* recs = nullptr;
     if (loc != nullptr) {
       auto* r = static_cast<loc_rec*>(loc->recs);
@@ -1743,41 +1715,26 @@ void uniform_launch(const int64_t* row_ptr, const ColT* col, const SeedT* seeds,
       recs = r;
     }
     // (grid: a multiple of 8 — the grouped order deals chunk c to XCD c % 8 — bounded by kWalkGrid, striding over the seeds)
-#define WG_MULTI(GW, KK)                                                                                             \
-  sample_uniform_multi_kernel<SeedT, ColT, GW, KK, WG_EXACT>                                                          \
-    <<<(int)std::min<int64_t>((ceil_div((int64_t)cap, 4 * (64 / GW) * KK) + 15) / 8 * 8, kWalkGrid), 256, 0, stream>>>(           \
+#define WG_MULTI(GW, EXACT)                                                                                          \
+  sample_uniform_multi_kernel<SeedT, ColT, GW, EXACT>                                                                 \
+    <<<(int)std::min<int64_t>((ceil_div((int64_t)cap, 4 * (64 / GW) * kMultiK) + 15) / 8 * 8, kWalkGrid), 256, 0, stream>>>(      \
       col, n, M, random_seed, offsets, dst, lid, gid, row_start, row_deg, recs)
-#define WG_MULTI_K(GW)                                                                                               \
-  do {                                                                                                               \
-    if (K == 1) WG_MULTI(GW, 1); else if (K == 2) WG_MULTI(GW, 2); else WG_MULTI(GW, 4);                              \
-  } while (0)
-    // group width = the fan-out where a kernel is built for it (the BASELINE fan-outs), else the next of 8 / 16 / 32
-    static const bool exact = getenv("WGAMD_SAMPLE_EXACT_WIDTH") == nullptr || atoi(getenv("WGAMD_SAMPLE_EXACT_WIDTH")) != 0;
-    // list order: one seed per lane for the fan-outs it is built for (WGAMD_SAMPLE_EXACT_WIDTH=0 keeps the lane groups)
 #define WG_LANE(MM)                                                                                                   \
   sample_uniform_lane_kernel<SeedT, ColT, MM>                                                                         \
     <<<(int)std::min<int64_t>(ceil_div((int64_t)cap, 256), kWalkGrid), 256, 0, stream>>>(col, n, random_seed, offsets, dst, lid, \
                                                                                          gid, row_start, row_deg)
-    const bool lane_layout = exact && recs == nullptr;
-    if (lane_layout && M == 5) WG_LANE(5);
-    else if (lane_layout && M == 10) WG_LANE(10);
-    else if (lane_layout && M == 15) WG_LANE(15);
-    else if (lane_layout && M == 25) WG_LANE(25);
-    else
-#define WG_EXACT true
-    if (exact && M == 5) WG_MULTI_K(5);
-    else if (exact && M == 10) WG_MULTI_K(10);
-    else if (exact && M == 15) WG_MULTI_K(15);
-    else if (exact && M == 25) WG_MULTI_K(25);
-    else {
-#undef WG_EXACT
-#define WG_EXACT false
-      if (M <= 8) WG_MULTI_K(8);
-      else if (M <= 16) WG_MULTI_K(16);
-      else WG_MULTI_K(32);
-    }
-#undef WG_EXACT
-#undef WG_MULTI_K
+#define WG_BUILT_FOR(MM)                                                                                              \
+  do {                                                                                                                \
+    if (recs == nullptr) WG_LANE(MM); else WG_MULTI(MM, true);                                                        \
+  } while (0)
+    if (M == 5) WG_BUILT_FOR(5);
+    else if (M == 10) WG_BUILT_FOR(10);
+    else if (M == 15) WG_BUILT_FOR(15);
+    else if (M == 25) WG_BUILT_FOR(25);
+    else if (M <= 8) WG_MULTI(8, false);
+    else if (M <= 16) WG_MULTI(16, false);
+    else WG_MULTI(32, false);
+#undef WG_BUILT_FOR
 #undef WG_MULTI
 #undef WG_LANE
     WG_HIP_CHECK(hipGetLastError());
@@ -1804,15 +1761,10 @@ void uniform_launch(const int64_t* row_ptr, const ColT* col, const SeedT* seeds,
   WG_HIP_CHECK(hipGetLastError());
 }
 
-// Weighted hop over n seeds (live count n.get()).  M in 1..256: the one-wave kernel covers rows of up to kWaveRowCap
-// candidates, the persistent workgroup kernel the listed longer ones (long rows first: their tail then drains while the
-// wave kernel fills the GPU); otherwise (256-thread stream layout / sample-all) the workgroup kernel walks all seeds.
-// `slab` holds `blocks` slabs of slab_len keys (slab_len >= the longest row above kLdsKeys candidates).
-// switches of the biased sampler (wgamd_set_weighted_sampling_mode; initial values from the environment, read once)
+// switches of the biased sampler (wgamd_set_weighted_sampling_mode): threshold pruning on, forced hand-back off
 inline int& weighted_mode(int which)
 {
-  static int mode[2] = {[] { const char* e = getenv("WGAMD_WEIGHTED_PRUNING"); return e && e[0] == '0' ? 0 : 1; }(),
-                        [] { const char* e = getenv("WGAMD_WEIGHTED_FORCE_REDO"); return e && e[0] == '1' ? 1 : 0; }()};
+  static int mode[2] = {1, 0};
   return mode[which];
 }
 inline bool weighted_pruning_off() { return weighted_mode(0) == 0; }
@@ -1844,19 +1796,30 @@ inline side_stream& weighted_side_stream()
   return s;
 }
 
-template <typename SeedT, typename ColT, typename WeightT>
+// Weighted hop over n seeds (live count n.get()).  M in 1..256: the one-wave kernel covers rows of up to kWaveRowCap
+// candidates, the persistent workgroup kernel the listed longer ones (long rows first: their tail then drains while the
+// wave kernel fills the GPU); otherwise (256-thread stream layout / sample-all) the workgroup kernel walks all seeds.
+// `slab` holds `blocks` slabs of slab_len keys (slab_len >= the longest row above kLdsKeys candidates).
+// With a `time_filter` (the temporal hop of the no-sync walk, 0 < M <= 256) the same launches draw with its effective weights,
+// never pruned: a frontier row has zero-weight candidates as a rule (every slot whose time does not qualify), and a pruned
+// kernel hands any such row back to the exact workgroup kernel; the exact one-wave kernels select the same picks (M largest
+// keys, ties to the lower slot — a zero weight's key is -inf) in one pass.
+template <typename SeedT, typename ColT, typename WeightT, typename TF = no_time_filter>
 void weighted_sample_launch(const int64_t* row_ptr, const ColT* col, const WeightT* weights, const SeedT* seeds, dev_count n,
                             int M, rng_plan rng, const int* offsets, int* lists, int blocks, uint32_t* slab,
-                            int64_t slab_len, ColT* dst, int* lid, int64_t* gid, hipStream_t stream)
+                            int64_t slab_len, ColT* dst, int* lid, int64_t* gid, hipStream_t stream, TF tf = TF{})
 {
   if (n.host <= 0) return;
   const int cap = n.host;
-  if (M <= 0 || M > 256) {
-    sample_weighted_kernel<SeedT, ColT, WeightT, 256, 256><<<std::max(blocks, 1), 256, 0, stream>>>(
-      row_ptr, col, weights, seeds, n, M, rng, offsets, slab, slab_len, dst, lid, gid, nullptr, 0);
-    return;
+  bool pruned   = false;   // threshold pruning: exact keys only for the candidates near the cut
+  if constexpr (std::is_same_v<TF, no_time_filter>) {
+    if (M <= 0 || M > 256) {
+      sample_weighted_kernel<SeedT, ColT, WeightT, 256, 256><<<std::max(blocks, 1), 256, 0, stream>>>(
+        row_ptr, col, weights, seeds, n, M, rng, offsets, slab, slab_len, dst, lid, gid, nullptr, 0);
+      return;
+    }
+    pruned = M <= 32 && !weighted_pruning_off();
   }
-  const bool pruned = M <= 32 && !weighted_pruning_off();   // threshold pruning: exact keys only for the candidates near the cut
   bool forked = false;
   side_stream* side = nullptr;
   if (blocks > 0 && pruned) {
@@ -1868,58 +1831,9 @@ void weighted_sample_launch(const int64_t* row_ptr, const ColT* col, const Weigh
     WG_HIP_CHECK(hipEventRecord(side->join, side->stream));
     forked = true;
   } else if (blocks > 0)
-    sample_weighted_kernel<SeedT, ColT, WeightT, 128, 512><<<blocks, 512, 0, stream>>>(
-      row_ptr, col, weights, seeds, n, M, rng, offsets, slab, slab_len, dst, lid, gid, lists, cap);
+    sample_weighted_kernel<SeedT, ColT, WeightT, 128, 512, TF><<<blocks, 512, 0, stream>>>(
+      row_ptr, col, weights, seeds, n, M, rng, offsets, slab, slab_len, dst, lid, gid, lists, cap, 0, tf);
   // short rows, one key per lane: 4 / 2 / 1 rows per wave (grids sized for the capacity; waves past the list end exit)
-  if (M < 16)
-    sample_weighted_group_kernel<SeedT, ColT, WeightT, 16><<<ceil_div((int64_t)cap * 16, 256), 256, 0, stream>>>(
-      row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 0);
-  if (M < 32)
-    sample_weighted_group_kernel<SeedT, ColT, WeightT, 32><<<ceil_div((int64_t)cap * 32, 256), 256, 0, stream>>>(
-      row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 1);
-  if (M < 64)
-    sample_weighted_group_kernel<SeedT, ColT, WeightT, 64><<<ceil_div((int64_t)cap * 64, 256), 256, 0, stream>>>(
-      row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 2);
-  // 65 .. 1024 candidates: one wave per row, 2 / 4 / 8 / 16 keys per lane in registers
-#define WG_WAVE(KM, CLS)                                                                                               \
-  do {                                                                                                                 \
-    if (pruned)                                                                                                        \
-      sample_weighted_wave_pruned_kernel<SeedT, ColT, WeightT, KM><<<ceil_div(cap, 4), 256, 0, stream>>>(              \
-        row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, CLS, weighted_force_redo());          \
-    else                                                                                                               \
-      sample_weighted_wave_kernel<SeedT, ColT, WeightT, KM><<<ceil_div(cap, 4), 256, 0, stream>>>(                     \
-        row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, CLS);                                \
-  } while (0)
-  if (M < 128) WG_WAVE(2, 3);
-  WG_WAVE(4, 4);
-  WG_WAVE(8, 5);
-  WG_WAVE(16, 6);
-#undef WG_WAVE
-  // rows copied whole
-  copy_short_rows_kernel<SeedT, ColT><<<ceil_div((int64_t)cap * 16, 256), 256, 0, stream>>>(row_ptr, col, seeds, n, M, offsets,
-                                                                                          dst, lid, gid);
-  // rows the pruned kernels handed back (a third draw of 0, odd weights, too many candidates near the cut): exact
-  // workgroup kernel, fed from the redo list; a slab exists whenever a row longer than the LDS key array does
-  if (forked) WG_HIP_CHECK(hipStreamWaitEvent(stream, side->join, 0));
-  if (pruned)
-    sample_weighted_kernel<SeedT, ColT, WeightT, 128, 512><<<blocks > 0 ? std::min(blocks, 128) : 64, 512, 0, stream>>>(
-      row_ptr, col, weights, seeds, n, M, rng, offsets, slab, slab_len, dst, lid, gid, lists, cap, 1);
-}
-
-// The temporal hop of the no-sync walk (0 < M <= 256): the launches of weighted_sample_launch without threshold pruning,
-// drawing with the effective weights of `tf`.  A frontier row has zero-weight candidates as a rule (every slot whose time
-// does not qualify), and a pruned kernel hands any such row back to the exact workgroup kernel: the exact one-wave kernels
-// select the same picks (M largest keys, ties to the lower slot — a zero weight's key is -inf) in one pass.
-template <typename SeedT, typename ColT, typename WeightT>
-void weighted_temporal_launch(const int64_t* row_ptr, const ColT* col, const WeightT* weights, const SeedT* seeds, dev_count n,
-                              int M, rng_plan rng, const int* offsets, int* lists, int blocks, uint32_t* slab,
-                              int64_t slab_len, ColT* dst, int* lid, int64_t* gid, time_filter tf, hipStream_t stream)
-{
-  if (n.host <= 0) return;
-  const int cap = n.host;
-  using TF      = time_filter;
-  sample_weighted_kernel<SeedT, ColT, WeightT, 128, 512, TF><<<blocks, 512, 0, stream>>>(
-    row_ptr, col, weights, seeds, n, M, rng, offsets, slab, slab_len, dst, lid, gid, lists, cap, 0, tf);
   if (M < 16)
     sample_weighted_group_kernel<SeedT, ColT, WeightT, 16, TF><<<ceil_div((int64_t)cap * 16, 256), 256, 0, stream>>>(
       row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 0, tf);
@@ -1929,18 +1843,30 @@ void weighted_temporal_launch(const int64_t* row_ptr, const ColT* col, const Wei
   if (M < 64)
     sample_weighted_group_kernel<SeedT, ColT, WeightT, 64, TF><<<ceil_div((int64_t)cap * 64, 256), 256, 0, stream>>>(
       row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 2, tf);
-  if (M < 128)
-    sample_weighted_wave_kernel<SeedT, ColT, WeightT, 2, TF><<<ceil_div(cap, 4), 256, 0, stream>>>(
-      row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 3, tf);
-  sample_weighted_wave_kernel<SeedT, ColT, WeightT, 4, TF><<<ceil_div(cap, 4), 256, 0, stream>>>(
-    row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 4, tf);
-  sample_weighted_wave_kernel<SeedT, ColT, WeightT, 8, TF><<<ceil_div(cap, 4), 256, 0, stream>>>(
-    row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 5, tf);
-  sample_weighted_wave_kernel<SeedT, ColT, WeightT, 16, TF><<<ceil_div(cap, 4), 256, 0, stream>>>(
-    row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, 6, tf);
-  // rows copied whole: every slot is a pick, whatever its time
+  // 65 .. 1024 candidates: one wave per row, 2 / 4 / 8 / 16 keys per lane in registers
+#define WG_WAVE(KM, CLS)                                                                                               \
+  do {                                                                                                                 \
+    if (pruned)                                                                                                        \
+      sample_weighted_wave_pruned_kernel<SeedT, ColT, WeightT, KM><<<ceil_div(cap, 4), 256, 0, stream>>>(              \
+        row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, CLS, weighted_force_redo());          \
+    else                                                                                                               \
+      sample_weighted_wave_kernel<SeedT, ColT, WeightT, KM, TF><<<ceil_div(cap, 4), 256, 0, stream>>>(                 \
+        row_ptr, col, weights, seeds, M, rng, offsets, dst, lid, gid, lists, cap, CLS, tf);                            \
+  } while (0)
+  if (M < 128) WG_WAVE(2, 3);
+  WG_WAVE(4, 4);
+  WG_WAVE(8, 5);
+  WG_WAVE(16, 6);
+#undef WG_WAVE
+  // rows copied whole (with a time filter too: every slot is a pick, whatever its time)
   copy_short_rows_kernel<SeedT, ColT><<<ceil_div((int64_t)cap * 16, 256), 256, 0, stream>>>(row_ptr, col, seeds, n, M, offsets,
                                                                                           dst, lid, gid);
+  // rows the pruned kernels handed back (a third draw of 0, odd weights, too many candidates near the cut): exact
+  // workgroup kernel, fed from the redo list; a slab exists whenever a row longer than the LDS key array does
+  if (forked) WG_HIP_CHECK(hipStreamWaitEvent(stream, side->join, 0));
+  if (pruned)
+    sample_weighted_kernel<SeedT, ColT, WeightT, 128, 512><<<blocks > 0 ? std::min(blocks, 128) : 64, 512, 0, stream>>>(
+      row_ptr, col, weights, seeds, n, M, rng, offsets, slab, slab_len, dst, lid, gid, lists, cap, 1);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2158,10 +2084,7 @@ void dispatch(const sample_args& a, bool weighted)
   const bool s64 = a.seeds->desc.dtype == WHOLEMEMORY_DT_INT64;
   const bool c64 = a.col->desc.dtype == WHOLEMEMORY_DT_INT64;
   if (!weighted && (a.row_ptr->handle || a.col->handle)) return c64 ? run_partitioned<int64_t>(a) : run_partitioned<int32_t>(a);
-  if (s64 && c64) return run<int64_t, int64_t, WeightT>(a, weighted);
-  if (s64 && !c64) return run<int64_t, int32_t, WeightT>(a, weighted);
-  if (!s64 && c64) return run<int32_t, int64_t, WeightT>(a, weighted);
-  return run<int32_t, int32_t, WeightT>(a, weighted);
+  with_id_types(s64, c64, [&](auto s, auto c) { run<tag_t<decltype(s)>, tag_t<decltype(c)>, WeightT>(a, weighted); });
 }
 
 }  // namespace
@@ -2170,12 +2093,11 @@ void sample_count_enqueue(const int64_t* row_ptr, const void* seeds, bool seeds6
                           int* big_deg, hipStream_t stream, int64_t* row_start, int* row_deg)
 {
   if (n.host <= 0) return;
-  if (seeds64)
-    sample_count_kernel<int64_t><<<std::min(ceil_div(n.host, 256), kWalkGrid), 256, 0, stream>>>(
-      row_ptr, static_cast<const int64_t*>(seeds), n, M, cnt, big_deg, nullptr, 0, 0, row_start, row_deg);
-  else
-    sample_count_kernel<int32_t><<<std::min(ceil_div(n.host, 256), kWalkGrid), 256, 0, stream>>>(
-      row_ptr, static_cast<const int32_t*>(seeds), n, M, cnt, big_deg, nullptr, 0, 0, row_start, row_deg);
+  with_id_type(seeds64, [&](auto s) {
+    using ST = tag_t<decltype(s)>;
+    sample_count_kernel<ST><<<std::min(ceil_div(n.host, 256), kWalkGrid), 256, 0, stream>>>(
+      row_ptr, static_cast<const ST*>(seeds), n, M, cnt, big_deg, nullptr, 0, 0, row_start, row_deg);
+  });
   WG_HIP_CHECK(hipGetLastError());
 }
 
@@ -2184,52 +2106,41 @@ void weighted_count_enqueue(const int64_t* row_ptr, const void* seeds, bool seed
 {
   if (n.host <= 0) return;
   WG_HIP_CHECK(hipMemsetAsync(big_list, 0, kWeightedListHead * sizeof(int), stream));
-  if (seeds64)
-    sample_count_kernel<int64_t><<<ceil_div(n.host, 256), 256, 0, stream>>>(row_ptr, static_cast<const int64_t*>(seeds), n, M,
-                                                                           cnt, nullptr, big_list, n.host, kLdsKeys);
-  else
-    sample_count_kernel<int32_t><<<ceil_div(n.host, 256), 256, 0, stream>>>(row_ptr, static_cast<const int32_t*>(seeds), n, M,
-                                                                           cnt, nullptr, big_list, n.host, kLdsKeys);
+  with_id_type(seeds64, [&](auto s) {
+    using ST = tag_t<decltype(s)>;
+    sample_count_kernel<ST><<<ceil_div(n.host, 256), 256, 0, stream>>>(row_ptr, static_cast<const ST*>(seeds), n, M, cnt, nullptr,
+                                                                      big_list, n.host, kLdsKeys);
+  });
   WG_HIP_CHECK(hipGetLastError());
 }
 
 void weighted_sample_enqueue(const int64_t* row_ptr, const void* col, bool col64, const void* weights, bool weights64,
                              const void* seeds, bool seeds64, dev_count n, int M, rng_plan random_seed, const int* offsets,
                              int* big_list, uint32_t* slab, int64_t slab_len, void* dst, int* src_lid,
-                             int64_t* edge_gid, hipStream_t stream)
+                             int64_t* edge_gid, const time_filter* tf, hipStream_t stream)
 {
-  WG_REQUIRE_INPUT(M > 0 && M <= 256, "the no-sync biased hop needs 0 < fan-out <= 256");
-#define WG_W(ST, CT, WT)                                                                                                  \
-  weighted_sample_launch<ST, CT, WT>(row_ptr, static_cast<const CT*>(col), static_cast<const WT*>(weights),              \
-                                     static_cast<const ST*>(seeds), n, M, random_seed, offsets, big_list, kWeightedBlocks, \
-                                     slab, slab_len, static_cast<CT*>(dst), src_lid, edge_gid, stream)
-#define WG_WW(ST, CT) do { if (weights64) WG_W(ST, CT, double); else WG_W(ST, CT, float); } while (0)
-  if (seeds64 && col64) WG_WW(int64_t, int64_t);
-  else if (seeds64) WG_WW(int64_t, int32_t);
-  else if (col64) WG_WW(int32_t, int64_t);
-  else WG_WW(int32_t, int32_t);
-#undef WG_WW
-#undef WG_W
-  WG_HIP_CHECK(hipGetLastError());
-}
-
-void weighted_temporal_sample_enqueue(const int64_t* row_ptr, const void* col, bool col64, const void* weights, bool weights64,
-                                      const void* seeds, bool seeds64, dev_count n, int M, rng_plan random_seed,
-                                      const int* offsets, int* big_list, uint32_t* slab, int64_t slab_len, void* dst,
-                                      int* src_lid, int64_t* edge_gid, time_filter tf, hipStream_t stream)
-{
-  WG_REQUIRE_INPUT(M > 0 && M <= 256, "the no-sync temporal hop needs 0 < fan-out <= 256");
-#define WG_W(ST, CT, WT)                                                                                                    \
-  weighted_temporal_launch<ST, CT, WT>(row_ptr, static_cast<const CT*>(col), static_cast<const WT*>(weights),              \
-                                       static_cast<const ST*>(seeds), n, M, random_seed, offsets, big_list, kWeightedBlocks, \
-                                       slab, slab_len, static_cast<CT*>(dst), src_lid, edge_gid, tf, stream)
-#define WG_WW(ST, CT) do { if (weights64) WG_W(ST, CT, double); else WG_W(ST, CT, float); } while (0)
-  if (seeds64 && col64) WG_WW(int64_t, int64_t);
-  else if (seeds64) WG_WW(int64_t, int32_t);
-  else if (col64) WG_WW(int32_t, int64_t);
-  else WG_WW(int32_t, int32_t);
-#undef WG_WW
-#undef WG_W
+  if (tf) {
+    WG_REQUIRE_INPUT(M > 0 && M <= 256, "the no-sync temporal hop needs 0 < fan-out <= 256");
+  } else {
+    WG_REQUIRE_INPUT(M > 0 && M <= 256, "the no-sync biased hop needs 0 < fan-out <= 256");
+  }
+  with_id_types(seeds64, col64, [&](auto s, auto c) {
+    with_weight_type(weights64, [&](auto w) {
+      using ST = tag_t<decltype(s)>;
+      using CT = tag_t<decltype(c)>;
+      using WT = tag_t<decltype(w)>;
+      const auto* col_t = static_cast<const CT*>(col);
+      const auto* w_t   = static_cast<const WT*>(weights);
+      const auto* s_t   = static_cast<const ST*>(seeds);
+      auto* dst_t       = static_cast<CT*>(dst);
+      if (tf)
+        weighted_sample_launch(row_ptr, col_t, w_t, s_t, n, M, random_seed, offsets, big_list, kWeightedBlocks, slab, slab_len,
+                               dst_t, src_lid, edge_gid, stream, *tf);
+      else
+        weighted_sample_launch(row_ptr, col_t, w_t, s_t, n, M, random_seed, offsets, big_list, kWeightedBlocks, slab, slab_len,
+                               dst_t, src_lid, edge_gid, stream);
+    });
+  });
   WG_HIP_CHECK(hipGetLastError());
 }
 
@@ -2245,17 +2156,15 @@ int sample_locality_shift(int64_t id_bound)
 
 void uniform_sample_enqueue(const int64_t* row_ptr, const void* col, bool col64, const void* seeds, bool seeds64,
                             dev_count n, int M, rng_plan random_seed, const int* offsets, void* dst, int* src_lid,
-                            int64_t* edge_gid, hipStream_t stream, const int64_t* row_start,
-                            const int* row_deg, const sample_locality* loc)
+                            int64_t* edge_gid, hipStream_t stream, const int64_t* row_start, const int* row_deg,
+                            const sample_locality* loc)
 {
-#define WG_U(ST, CT)                                                                                               \
-  uniform_launch<ST, CT>(row_ptr, static_cast<const CT*>(col), static_cast<const ST*>(seeds), n, M, random_seed, \
-                         offsets, static_cast<CT*>(dst), src_lid, edge_gid, stream, row_start, row_deg, loc)
-  if (seeds64 && col64) WG_U(int64_t, int64_t);
-  else if (seeds64) WG_U(int64_t, int32_t);
-  else if (col64) WG_U(int32_t, int64_t);
-  else WG_U(int32_t, int32_t);
-#undef WG_U
+  with_id_types(seeds64, col64, [&](auto s, auto c) {
+    using ST = tag_t<decltype(s)>;
+    using CT = tag_t<decltype(c)>;
+    uniform_launch<ST, CT>(row_ptr, static_cast<const CT*>(col), static_cast<const ST*>(seeds), n, M, random_seed, offsets,
+                           static_cast<CT*>(dst), src_lid, edge_gid, stream, row_start, row_deg, loc);
+  });
 }
 
 }  // namespace wgamd

@@ -112,13 +112,10 @@ extern "C" wholememory_error_code_t wgamd_csr_uniform_sample_with_replacement(
     int* offsets      = static_cast<int*>(tensor_data(output_sample_offset_tensor));
     auto st           = static_cast<hipStream_t>(stream);
     const bool s64 = sd.dtype == WHOLEMEMORY_DT_INT64, c64 = cd.dtype == WHOLEMEMORY_DT_INT64;
-#define WG_GO(S, C)                                                                                                        \
-  run<S, C>(rp, col, seeds, n, sample_count, offsets, output_dest_memory_context, output_center_localid_memory_context,    \
-            output_edge_gid_memory_context, (uint64_t)random_seed, cd.dtype, p_env_fns, st)
-    if (s64 && c64) WG_GO(int64_t, int64_t);
-    else if (s64) WG_GO(int64_t, int32_t);
-    else if (c64) WG_GO(int32_t, int64_t);
-    else WG_GO(int32_t, int32_t);
-#undef WG_GO
+    with_id_types(s64, c64, [&](auto s, auto c) {
+      run<tag_t<decltype(s)>, tag_t<decltype(c)>>(rp, col, seeds, n, sample_count, offsets, output_dest_memory_context,
+                                                  output_center_localid_memory_context, output_edge_gid_memory_context,
+                                                  (uint64_t)random_seed, cd.dtype, p_env_fns, st);
+    });
   });
 }

@@ -717,11 +717,10 @@ wholememory_error_code_t wgamd_sage_wgrad_bf16x3(const float* agg, int64_t ld_ag
 #define WGAMD_IDS_BYTE_OFFSETS ((wholememory_dtype_t)64)
 
 /* Biased (A-Res) sampling, fan-out <= 32: how wholegraph_csr_weighted_sample_without_replacement and the biased call-group
- * hop find the M largest keys.  pruning = 1 (default; env WGAMD_WEIGHTED_PRUNING=0 turns it off): a cheap lower bound of
- * every |key| first, exact keys (log1pf, two divisions) only for the candidates that can still reach the M-th largest one —
- * same picks as computing every key (csrc/wg_sample.hip, "threshold pruning").  force_redo = 1 (env
- * WGAMD_WEIGHTED_FORCE_REDO=1) sends every row through the hand-back path the pruned kernels take for a row they cannot
- * decide: a test switch.  A negative argument leaves that setting as it is. */
+ * hop find the M largest keys.  pruning = 1 (default): a cheap lower bound of every |key| first, exact keys (log1pf, two
+ * divisions) only for the candidates that can still reach the M-th largest one — same picks as computing every key
+ * (csrc/wg_sample.hip, "threshold pruning").  force_redo = 1 (default 0) sends every row through the hand-back path the pruned
+ * kernels take for a row they cannot decide: a test switch.  A negative argument leaves that setting as it is. */
 void wgamd_set_weighted_sampling_mode(int pruning, int force_redo);
 /* Uniform hops of a call group whose frontier capacity is at least `min_capacity` entries (and whose fan-out is at most 32)
  * walk the frontier grouped by vertex-id range instead of in list order: identical results (every entry keeps its own PCG

@@ -50,6 +50,25 @@ def test_temporal_hop_is_exported_and_refuses_bad_blocks_on_the_host(hiplib):
     assert hiplib.wgamd_sample_hop_temporal_workspace_bytes(1000, 10000, dt, 0) == 0
 
 
+def test_hop_workspace_sizes_are_pinned(hiplib):
+    """The three workspace queries feed ``call_group_bytes_per_seed`` and ``HeteroNeighborSampler._walk_capacity_per_seed``
+    and through them ``default_local_seeds_per_call``: the memory-sized call group of every loader that is given none, and
+    the benchmark's ``--call-group`` default.  A change of these numbers changes what the loaders and the benchmark launch, so
+    they are literals, taken from the library as it stood before this test; a change that means to move the default call group
+    updates them knowingly."""
+    from wholegraph_amd import _lib as L
+    plain = hiplib.wgamd_sample_hop_workspace_bytes
+    assert plain(4096, 102400, L.DT_INT64) == 6963968
+    assert plain(4096, 102400, L.DT_INT) == 6554368
+    assert plain(106496, 1024000, L.DT_INT64) == 70945280
+    assert plain(106496, 1024000, L.DT_INT) == 66849280
+    weighted, temporal = hiplib.wgamd_sample_hop_weighted_workspace_bytes, hiplib.wgamd_sample_hop_temporal_workspace_bytes
+    assert weighted(106496, 1024000, L.DT_INT64, 500) == 75209472
+    assert temporal(106496, 1024000, L.DT_INT64, 500) == 92019712
+    assert weighted(106496, 1024000, L.DT_INT64, 20000) == 157125376
+    assert temporal(106496, 1024000, L.DT_INT64, 20000) == 173935616
+
+
 def _sampler(fanout, weights=None, **kw):
     from cugraph_pyg_amd.data.graph_store import CSRGraph
     from cugraph_pyg_amd.sampler.sampler import NeighborSampler
