@@ -391,6 +391,16 @@ SYMBOLS = {
     "wgamd_gin_aggregate_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                         c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "wgamd_segment_sum_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    # GATv2 attention (wg_gatv2.hip)
+    "wgamd_gatv2_supported": (c_int, [c_int, c_int]),
+    "wgamd_gatv2_bwd_blocks": (c_int64, [c_int64]),
+    "wgamd_gatv2_attention_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int,
+                                          c_int, c_float, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "wgamd_gatv2_bwd_dst_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int,
+                                        c_int, c_float, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wgamd_gatv2_bwd_src_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                        c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                        c_int, c_void_p]),
     "wgamd_bias_act_rows_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "wgamd_gat_transform_heads_supported": (c_int, [c_int, c_int, c_int]),
     "wgamd_gat_transform_weight_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -4,11 +4,12 @@ names, parameter names and maths, so they drop into the reference's models (pyli
 and into its cugraph-pyg examples.  Six layers run ONE kernel per hop of a call group's ``LayerGraph``, forward and backward
 (each an autograd Function over the hops): ``SAGEConv``, ``GCNConv``, ``RGCNConv``, ``TransformerConv``, ``GINConv``, and
 ``HeteroConv`` over SAGEConv relations (one kernel per hop and destination type).  ``GATConv`` and ``HeteroConv`` over GATConv
-relations are aggregate kernels with a dense tail.
+relations are aggregate kernels with a dense tail.  ``GATv2Conv`` is two library GEMMs and ONE attention kernel per hop on
+the transformed rows (its logit is not linear in the neighbour row: no aggregate-first form).
 
 Order of the file: ctypes helpers and the plumbing the one-kernel layers share; the SAGE-era kernel wrappers, derived-weight
 caches and GAT kernel wrappers; graph forms (``_single_hop``, ``LazyRows``, ``HopGraph``, ``LayerGraph``) and the helpers that
-walk a layer graph; then a section per layer — SAGE and GAT, GCN, RGCN, transformer, GIN, heterogeneous — each with its kernel
+walk a layer graph; then a section per layer — SAGE and GAT, GCN, RGCN, transformer, GIN, GATv2, heterogeneous — each with its kernel
 wrappers, its autograd Function(s) and its module.
 
 Shared by the one-kernel layers, so that they cannot drift apart: ``_hop_args`` (the eight leading arguments of a launch over a
@@ -3436,6 +3437,339 @@ def global_add_pool(x: torch.Tensor, batch: Optional[torch.Tensor], size: Option
         offsets = torch.searchsorted(batch.contiguous(), torch.arange(size + 1, device=batch.device))
         return _SegmentSum.apply(x, offsets.contiguous(), batch)
     return torch.zeros((size, x.shape[1]), dtype=x.dtype, device=x.device).index_add_(0, batch, x)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# GATv2 (torch_geometric.nn.GATv2Conv) — csrc/wg_gatv2.hip
+# ---------------------------------------------------------------------------------------------------------------------
+def gatv2_supported(H: int, C: int) -> bool:
+    """Shapes of the GATv2 attention kernels (``wgamd_gatv2_supported``, answered on the host): 1 <= H <= 8, C % 4 == 0,
+    H C <= 256."""
+    return bool(L.lib().wgamd_gatv2_supported(int(H), int(C)))
+
+
+def _gatv2_operands(row_ptr, col, xl, xr, att, heads: int, xr_rows):
+    """The leading arguments the three GATv2 launches share, checked: ``row_ptr, col, n_rows, xl, ldxl, xr, ldxr, xr_rows, att,
+    H, C`` (``col`` may be the transposed hop's; an empty one goes in as one element)."""
+    H, HC = int(heads), int(xl.shape[1])
+    assert HC % H == 0 and gatv2_supported(H, HC // H), "outside gatv2_supported"
+    assert _kernel_rows_ok(xl) and _kernel_rows_ok(xr) and xr.shape[1] == HC, "xl / xr: float32 rows, 16-B aligned, unit column stride"
+    assert att.dtype == torch.float32 and att.is_cuda and att.is_contiguous() and att.numel() == HC
+    assert xr_rows is None or (xr_rows.dtype == torch.int64 and xr_rows.is_contiguous() and xr_rows.is_cuda)
+    return (row_ptr.data_ptr(), _nonempty(col, torch.int32).data_ptr(), row_ptr.shape[0] - 1, xl.data_ptr(), xl.stride(0), xr.data_ptr(),
+            xr.stride(0), _ptr(xr_rows), att.data_ptr(), H, HC // H)
+
+
+def gatv2_attention(row_ptr, col, xl, xr, att, heads: int, negative_slope: float = 0.2, xr_rows=None, bias=None, relu=False, out=None,
+                    need_alpha=False, mean=False):
+    """The whole GATv2 attention of one hop in ONE launch (``wgamd_gatv2_attention_f32``, include/wgamd_ext.h): ``xl`` [n_src,
+    H C] = lin_l(x_src) with ``col`` its rows, ``xr`` = lin_r over the destination rows, dense [n_rows, H C] or read at
+    ``xr_rows`` (shared weights: ``xr = xl``, ``xr_rows`` = the destinations' input rows), ``att`` [1, H, C].  ``out``
+    [n_rows, H C] — with ``mean`` (concat=False) [n_rows, C], the head mean taken in the launch — gets ``bias`` and ReLU fused;
+    pass a slice of the layer's output to have the hop written in place.  Self loops are entries of the CSR.  With
+    ``need_alpha`` returns ``(out, alpha [E, H], agg [n_rows, H C])``, what the backward reads.  An empty hop (no rows, or no
+    entries at all) is filled without a launch: zeros plus bias."""
+    _check_csr(row_ptr, col)
+    H, HC, n_rows, E, dev = int(heads), int(xl.shape[1]), row_ptr.shape[0] - 1, int(col.shape[0]), row_ptr.device
+    args = _gatv2_operands(row_ptr, col, xl, xr, att, H, xr_rows)
+    N = HC // H if mean else HC
+    assert xr_rows is not None or xr.shape[0] == n_rows
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N)
+    out = _out_rows(out, n_rows, N, dev)
+    alpha = torch.empty((E, H), dtype=torch.float32, device=dev) if need_alpha else None
+    agg = torch.empty((n_rows, HC), dtype=torch.float32, device=dev) if need_alpha else None
+    if n_rows > 0 and E == 0:
+        out.zero_()
+        if bias is not None:
+            out.add_(bias)
+        if relu:
+            out.relu_()
+        if agg is not None:
+            agg.zero_()
+    elif n_rows > 0:
+        L.check(L.lib().wgamd_gatv2_attention_f32(*args, float(negative_slope), _ptr(bias), int(bool(relu)), int(bool(mean)),
+                                                  out.data_ptr(), out.stride(0), _ptr(alpha), _ptr(agg), get_stream()),
+                "wgamd_gatv2_attention_f32")
+    return (out, alpha, agg) if need_alpha else out
+
+
+def gatv2_bwd_dst(row_ptr, col, xl, xr, att, heads: int, alpha, g, agg, negative_slope: float = 0.2, xr_rows=None, dxr=None):
+    """The destination-major backward launch of one hop (``wgamd_gatv2_bwd_dst_f32``): from ``g`` = dL/d agg [n_rows, H C] and
+    the forward's ``alpha`` and ``agg`` returns ``(dxr [n_rows, H C], de [E, H], datt_part [blocks, H C])`` — the gradient of
+    att is the sum of the partial rows."""
+    H, HC, n_rows, dev = int(heads), int(xl.shape[1]), row_ptr.shape[0] - 1, row_ptr.device
+    args = _gatv2_operands(row_ptr, col, xl, xr, att, H, xr_rows)
+    assert _kernel_rows_ok(g) and g.shape == (n_rows, HC) and agg.is_contiguous() and alpha.is_contiguous()
+    dxr = _out_rows(dxr, n_rows, HC, dev)
+    assert dxr.is_contiguous()
+    de = torch.empty((int(col.shape[0]), H), dtype=torch.float32, device=dev)
+    part = torch.empty((int(L.lib().wgamd_gatv2_bwd_blocks(n_rows)), HC), dtype=torch.float32, device=dev)
+    L.check(L.lib().wgamd_gatv2_bwd_dst_f32(*args, float(negative_slope), _nonempty(alpha, torch.float32).data_ptr(), g.data_ptr(),
+                                            g.stride(0), agg.data_ptr(), dxr.data_ptr(), _nonempty(de, torch.float32).data_ptr(),
+                                            part.data_ptr(), get_stream()), "wgamd_gatv2_bwd_dst_f32")
+    return dxr, de, part
+
+
+def gatv2_bwd_src(row_ptr_t, col_t, perm, xl, xr, att, heads: int, alpha, de, g, gx, negative_slope: float = 0.2, xr_rows=None,
+                  accumulate=True):
+    """The source-major backward launch of one hop over its transpose (``wgamd_gatv2_bwd_src_f32``): ``gx`` [n_src, H C] (+)= the
+    hop's part of dL/d xl; ``row_ptr_t, col_t, perm`` as ``HopGraph.transposed(n_src, need_self=False, need_perm=True)`` gives them
+    for the CSR the forward walked (self loops included)."""
+    H = int(heads)
+    args = _gatv2_operands(row_ptr_t, col_t, xl, xr, att, H, xr_rows)
+    assert _kernel_rows_ok(g) and _kernel_rows_ok(gx) and gx.shape == xl.shape and row_ptr_t.shape[0] - 1 == xl.shape[0]
+    L.check(L.lib().wgamd_gatv2_bwd_src_f32(args[0], args[1], perm.data_ptr(), *args[2:], float(negative_slope),
+                                            _nonempty(alpha, torch.float32).data_ptr(), _nonempty(de, torch.float32).data_ptr(),
+                                            g.data_ptr(), g.stride(0), gx.data_ptr(), gx.stride(0), int(bool(accumulate)), get_stream()),
+            "wgamd_gatv2_bwd_src_f32")
+    return gx
+
+
+def _gatv2_hop(h: HopGraph, loops: bool) -> HopGraph:
+    """The hop whose CSR the GATv2 kernels walk: ``h``, or — with self loops — ``h.with_self_loops()`` as a ``HopGraph`` of its
+    own (kept on ``h``), whose ``transposed`` is then the transpose WITH the loops."""
+    if not loops:
+        return h
+    rp, col = h.with_self_loops()
+    hit = getattr(h, "_looped", None)
+    if hit is None or hit.row_ptr is not rp:
+        hit = h._looped = HopGraph(rp, col, h.self_rows)
+    return hit
+
+
+class _Gatv2Layer(torch.autograd.Function):
+    """The GATv2 attention over a ``LayerGraph`` from the transformed rows: ONE ``wgamd_gatv2_attention_f32`` launch per hop, each
+    writing its slice of the output in place (bias, ReLU and the head mean fused).  ``xr`` None = shared weights: XR[i] is
+    ``xl[self_rows[i]]`` and its gradient is added into ``xl``'s at ``self_rows`` (injective: a plain indexed add).  When
+    training the forward keeps alpha and agg per hop; the backward is ``wgamd_gatv2_bwd_dst_f32`` and ``wgamd_gatv2_bwd_src_f32``
+    per hop, without atomics.  ``lin_l`` / ``lin_r`` and their gradients are ordinary autograd around this function."""
+
+    @staticmethod
+    def forward(ctx, xl, xr, att, bias, graph, loops, H, slope, relu, mean):
+        lg, dev, HC = graph, xl.device, xl.shape[1]
+        n = lg.n_rows
+        train = any(ctx.needs_input_grad[:4])
+        out = torch.empty((n, HC // H if mean else HC), dtype=torch.float32, device=dev)
+        xl_d, xr_d = xl.detach(), None if xr is None else xr.detach()
+        att_d, b_d = att.detach().contiguous(), None if bias is None else bias.detach().contiguous()
+        kept = []
+        for h, rows, _ in _hops(lg):
+            res = None
+            if h.n_rows > 0:
+                hop = _gatv2_hop(h, loops)
+                res = gatv2_attention(hop.row_ptr, hop.col, xl_d, xl_d if xr is None else xr_d[rows], att_d, H, slope,
+                                      xr_rows=h.self_rows if xr is None else None, bias=b_d, relu=relu, out=out[rows],
+                                      need_alpha=train, mean=mean)
+            kept.append(res[1:] if train and res is not None else None)
+        ctx.set_materialize_grads(False)
+        if train:
+            ctx.save_for_backward(xl_d, xr_d, att_d, out)
+            ctx.kept, ctx.graph, ctx.conf = kept, lg, (loops, H, slope, relu, mean)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        _released(ctx.kept, "GATv2Conv", "attention weights")
+        xl, xr, att, out = ctx.saved_tensors
+        need_xl, need_xr, need_att, need_b = ctx.needs_input_grad[:4]
+        loops, H, slope, relu, mean = ctx.conf
+        lg, dev, HC = ctx.graph, xl.device, xl.shape[1]
+        n, n_src = lg.n_rows, xl.shape[0]
+        gxl = gxr = gatt = gb = None
+        if g is None:
+            g = torch.zeros_like(out)
+        gz = g.contiguous().float()
+        if relu:
+            gz = torch.ops.aten.threshold_backward(gz, out, 0)
+        if need_b:
+            gb = gz.sum(0)
+        if need_xl or need_xr or need_att:
+            G = (gz * (1.0 / H)).repeat(1, H) if mean else gz                # dL/d agg [n, H C]
+            gxl = torch.zeros((n_src, HC), dtype=torch.float32, device=dev)
+            gxr = None if xr is None else torch.zeros((n, HC), dtype=torch.float32, device=dev)
+            parts = []
+            for k, (h, rows, _) in enumerate(_hops(lg)):
+                if h.n_rows == 0:
+                    continue
+                hop = _gatv2_hop(h, loops)
+                if hop.col.shape[0] == 0:
+                    continue
+                alpha, agg = ctx.kept[k]
+                xr_h, xr_rows = (xl, h.self_rows) if xr is None else (xr[rows], None)
+                dxr, de, part = gatv2_bwd_dst(hop.row_ptr, hop.col, xl, xr_h, att, H, alpha, G[rows], agg, slope, xr_rows=xr_rows,
+                                              dxr=None if xr is None else gxr[rows])
+                parts.append(part)
+                row_ptr_t, col_t, _, perm = hop.transposed(n_src, need_self=False, need_perm=True)
+                gatv2_bwd_src(row_ptr_t, col_t, perm, xl, xr_h, att, H, alpha, de, G[rows], gxl, slope, xr_rows=xr_rows)
+                if xr is None:
+                    gxl[h.self_rows] += dxr
+            gatt = (torch.cat(parts).sum(0) if parts else torch.zeros(HC, dtype=torch.float32, device=dev)).view(1, H, HC // H)
+        ctx.kept = None
+        return gxl, gxr, gatt, gb, None, None, None, None, None, None
+
+
+def _gatv2_torch_ops(conv, xs, x_dst, lg: LayerGraph, relu: bool):
+    """The layer in PyG's own formulation, composed of torch ops under ordinary autograd in the parameters' dtype: the route of
+    shapes outside the kernel's domain and of CPU tensors (correctness, not speed — [E, H, C] is materialised three times)."""
+    H, C, dt = conv.heads, conv.out_channels, conv.att.dtype
+    xs = xs.to(dt)
+    XL = conv.lin_l(xs).view(-1, H, C)
+    outs = []
+    for h, rows, _ in _hops(lg):
+        n, E = h.n_rows, int(h.col.shape[0])
+        XR = conv.lin_r(x_dst[rows].to(dt) if x_dst is not None else xs[h.self_rows]).view(n, H, C)
+        src, dst = h.col.long(), _edge_dst(h.row_ptr, E)
+        if conv.add_self_loops:
+            src, dst = torch.cat([h.self_rows, src]), torch.cat([torch.arange(n, device=dst.device), dst])
+        xj = XL[src]
+        e = (torch.nn.functional.leaky_relu(xj + XR[dst], conv.negative_slope) * conv.att).sum(-1)       # [E', H]
+        emax = e.new_full((n, H), -math.inf).scatter_reduce(0, dst.unsqueeze(1).expand(-1, H), e, "amax", include_self=True)
+        ex = (e - emax[dst]).exp()
+        alpha = ex / e.new_zeros((n, H)).index_add(0, dst, ex)[dst]
+        o = e.new_zeros((n, H, C)).index_add(0, dst, alpha.unsqueeze(2) * xj)
+        outs.append(o.reshape(n, H * C) if conv.concat else o.mean(1))
+    out = torch.cat(outs) if outs else xs.new_zeros((0, H * C if conv.concat else C))
+    if conv.bias is not None:
+        out = out + conv.bias
+    return torch.relu(out) if relu else out
+
+
+class GATv2Conv(torch.nn.Module):
+    """PyG ``GATv2Conv`` (flow source_to_target):
+        e_ijh = att_h . LeakyReLU(lin_l(x_j) + lin_r(x_i))_h,   alpha = softmax_j(e_ijh),   out_i = sum_j alpha_ijh lin_l(x_j)_h
+    per head; ``concat=True`` concatenates the heads ([N, H C]), ``concat=False`` averages them ([N, C]); then ``bias``.
+    Parameters as PyG names them (``lin_l``, ``lin_r``: ``weight`` [H C, in] and ``bias``; ``att`` [1, H, C]; ``bias``), glorot
+    weights and zero biases, so a PyG ``state_dict`` loads; ``share_weights=True``: ``lin_r is lin_l``.  Self loops follow
+    ``GATConv`` here: the destination's own input row is one extra leading neighbour, sampled loops and duplicate edges stay
+    ordinary edges; a destination without any entry gets zeros plus bias.
+
+    ``forward(x, graph, act=None)``: ``graph`` = a COO ``edge_index`` (output rows = x's rows, or x_dst's for a pair), a
+    ``[csr_row_ptr, csr_col_ind]`` pair (destinations = the first rows of x), or a call group's ``LayerGraph`` with x a tensor or
+    ``LazyRows`` (materialised once; 16-bit tables arrive as float32 rows) and ``act=None | "relu"`` — the output rows are the
+    hops' destination lists back to back, every hop written in place into its slice.  ``x`` may be a pair ``(x_src, x_dst)``:
+    the sampler layout (x_dst = the first rows of x_src in the same storage) keeps self loops, any other pair needs
+    ``add_self_loops=False`` (ValueError otherwise: a foreign destination row is no row of lin_l's input).
+
+    The logit's nonlinearity sits inside the dot product with ``att``, so there is no aggregate-first form (as ``GATConv`` and
+    ``TransformerConv`` have): ``XL = lin_l(x)`` is one library GEMM over all input rows of the layer, ``XR = lin_r`` one over
+    the destination rows (none with shared weights: the kernel reads ``XL[self_rows]``), and ONE kernel per hop
+    (``wgamd_gatv2_attention_f32``) scores, soft-maxes and sums the transformed neighbour rows, reading each once; bias, ReLU and
+    the head mean of ``concat=False`` are done IN that launch.  The backward is two more kernels per hop, without atomics (the
+    same bits from run to run).  ``route``: ``"kernel"`` inside ``gatv2_supported`` (heads <= 8, out_channels % 4 == 0,
+    heads x out_channels <= 256) with float32 tensors on the device, else ``"torch"`` — the same layer out of torch ops with
+    ordinary autograd, CPU tensors included, for correctness only (``torch_ops = True`` forces it).
+
+    Not supported: ``edge_dim``, ``fill_value``, ``residual`` and any other keyword (TypeError), attention dropout (``dropout >
+    0`` raises NotImplementedError in training mode; in eval mode it is the identity), a ``HeteroLayerGraph``
+    (NotImplementedError), ``HeteroConv`` relations, HIP-graph capture."""
+
+    def __init__(self, in_channels: Union[int, Tuple[int, int]], out_channels: int, heads: int = 1, concat: bool = True,
+                 negative_slope: float = 0.2, dropout: float = 0.0, add_self_loops: bool = True, bias: bool = True,
+                 share_weights: bool = False, **kwargs):
+        super().__init__()
+        if kwargs:
+            raise TypeError("GATv2Conv: unsupported keyword argument(s) %s" % ", ".join(sorted(kwargs)))
+        if heads < 1 or out_channels < 1:
+            raise ValueError("GATv2Conv: heads and out_channels must be positive")
+        if isinstance(in_channels, int):
+            in_channels = (in_channels, in_channels)
+        self.in_channels, self.out_channels, self.heads, self.concat = in_channels, out_channels, heads, concat
+        self.in_src, self.in_dst = int(in_channels[0]), int(in_channels[1])
+        self.negative_slope, self.dropout, self.add_self_loops = float(negative_slope), float(dropout), add_self_loops
+        self.share_weights = share_weights
+        self.torch_ops = False
+        HC = heads * out_channels
+        self.lin_l = torch.nn.Linear(self.in_src, HC, bias=bias)
+        self.lin_r = self.lin_l if share_weights else torch.nn.Linear(self.in_dst, HC, bias=bias)
+        self.att = torch.nn.Parameter(torch.empty(1, heads, out_channels))
+        self.bias = torch.nn.Parameter(torch.empty(HC if concat else out_channels)) if bias else None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        def glorot(t):
+            bound = math.sqrt(6.0 / (t.shape[-2] + t.shape[-1]))
+            torch.nn.init.uniform_(t, -bound, bound)
+        for lin in (self.lin_l, self.lin_r):
+            glorot(lin.weight)
+            if lin.bias is not None:
+                torch.nn.init.zeros_(lin.bias)
+        glorot(self.att)
+        if self.bias is not None:
+            torch.nn.init.zeros_(self.bias)
+
+    @property
+    def route(self) -> str:
+        """``"kernel"`` or ``"torch"``: what the shapes and the parameters' dtype and device select for float32 device inputs."""
+        ok = (not self.torch_ops and self.att.is_cuda and self.att.dtype == torch.float32
+              and gatv2_supported(self.heads, self.out_channels))
+        return "kernel" if ok else "torch"
+
+    def _forward_layer(self, x, lg: LayerGraph, act=None, x_dst=None):
+        assert act in (None, "relu"), "act: None or 'relu'"
+        x = _x16_as_rows(x)
+        if isinstance(x, LazyRows):
+            _refuse_lazy_table_grad(x.table)
+            x = x.materialize()
+        if x.shape[1] != self.in_src:
+            raise ValueError("GATv2Conv: x has %d features, the layer takes %d" % (x.shape[1], self.in_src))
+        if x_dst is not None and x_dst.shape[1] != (self.in_src if self.share_weights else self.in_dst):
+            raise ValueError("GATv2Conv: x_dst has %d features, the layer takes %d"
+                             % (x_dst.shape[1], self.in_src if self.share_weights else self.in_dst))
+        if x_dst is None and self.in_src != self.in_dst and not self.share_weights:
+            raise ValueError("GATv2Conv: in_channels = %s needs an (x_src, x_dst) pair" % (self.in_channels,))
+        on_device = all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in (x, x_dst))
+        if self.route != "kernel" or not on_device:
+            return _gatv2_torch_ops(self, x, x_dst, lg, act == "relu")
+        XL = self.lin_l(x)
+        if x_dst is not None:
+            XR = self.lin_r(x_dst)
+        elif self.share_weights:
+            XR = None
+        else:
+            dev = x.device
+            self_all = torch.cat([h.self_rows for h in lg.hops]) if lg.hops else torch.zeros(0, dtype=torch.int64, device=dev)
+            XR = self.lin_r(x[self_all])
+        return _Gatv2Layer.apply(XL, XR, self.att, self.bias, lg, bool(self.add_self_loops), self.heads, self.negative_slope,
+                                 act == "relu", not self.concat)
+
+    def forward(self, x, graph, act=None):
+        if self.dropout > 0 and self.training:
+            raise NotImplementedError("GATv2Conv: attention dropout (dropout > 0 in training mode) is not supported")
+        _refuse_capture(self, "per-graph caches")              # (the hops' self-looped CSR and transposes, kept on the graph object)
+        if isinstance(graph, HeteroLayerGraph):
+            raise NotImplementedError("GATv2Conv over a heterogeneous call group's layer graph is not supported")
+        x_dst, pair = None, False
+        if isinstance(x, (tuple, list)):
+            (x, x_dst), pair = x, True
+        _refuse_featureless(self, x)
+        if pair:
+            _refuse_featureless(self, x_dst)
+        if isinstance(graph, LayerGraph):
+            if pair:
+                raise NotImplementedError("GATv2Conv: an (x_src, x_dst) pair over a LayerGraph is not supported")
+            return self._forward_layer(x, graph, act)
+        if isinstance(x, LazyRows):
+            x = _x16_as_rows(x)
+            x = x.materialize() if isinstance(x, LazyRows) else x
+        if isinstance(x_dst, LazyRows):
+            x_dst = _x16_as_rows(x_dst)
+            x_dst = x_dst.materialize() if isinstance(x_dst, LazyRows) else x_dst
+        if pair:
+            # the sampler layout: the destinations are the first rows of x_src, in the same storage
+            own = x_dst is x or (x_dst.data_ptr() == x.data_ptr() and x_dst.dtype == x.dtype and x_dst.stride() == x.stride()
+                                 and x_dst.shape[0] <= x.shape[0] and x_dst.shape[1] == x.shape[1])
+            if not own and self.add_self_loops:
+                raise ValueError("GATv2Conv: an (x_src, x_dst) pair whose destinations are not the first rows of x_src needs "
+                                 "add_self_loops=False (a self loop reads the destination's own row of x_src)")
+        if isinstance(graph, (tuple, list)):
+            n_dst = int(graph[0].shape[0]) - 1
+        else:
+            n_dst = x_dst.shape[0] if pair else x.shape[0]
+        have = x_dst.shape[0] if pair else x.shape[0]
+        if have < n_dst:
+            raise ValueError("GATv2Conv: %d destination rows for %d destinations" % (have, n_dst))
+        lg = _single_hop(graph, n_dst)[0]
+        return self._forward_layer(x, lg, act, x_dst=x_dst[:n_dst] if pair and not own else None)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1179,6 +1179,42 @@ wholememory_error_code_t wgamd_gin_aggregate_f32(const int* row_ptr, const int* 
 wholememory_error_code_t wgamd_segment_sum_f32(const float* x, int64_t ldx, int F, const int64_t* offsets, int64_t n_segments,
                                                float* out, int64_t ldo, void* stream);
 
+/* ---- GATv2 attention (csrc/wg_gatv2.hip): torch_geometric.nn.GATv2Conv over a sampled hop, on the TRANSFORMED rows ----------------
+ *   e[k, h]  = sum_c att[h C + c] LeakyReLU(XL[j, h C + c] + XR[i, h C + c])       (k = (j -> i), j = col[k] a row of xl)
+ *   alpha    = softmax over the edges of row i of e[:, h]
+ *   agg[i]   = sum_k alpha[k, h] XL[j, h C : (h + 1) C]  per head                  [n_rows, H C]
+ *   out[i]   = act( agg[i] + bias )  [H C wide],  or with mean  act( mean_h agg[i, h C :] + bias )  [C wide]
+ * XL[j] = xl[j] (the caller's lin_l(x_src)), XR[i] = xr[xr_rows ? xr_rows[i] : i] (lin_r over the destination rows; with shared
+ * weights xr = xl and xr_rows = the destinations' input rows).  The logit is not linear in the neighbour row, so there is no
+ * aggregate-first form: the transformed row is read once per edge.  Self loops are ordinary entries of the CSR.  A row without
+ * edges gets a zero aggregate (out = act(bias)).  alpha (optional, [E, H]) and agg (optional, [n_rows, H C] row-major) are what
+ * the backward reads.  One launch; sums run in CSR order: run-to-run deterministic.  Domain: wgamd_gatv2_supported (answers on
+ * the host: 1 <= H <= 8, C % 4 == 0, H C <= 256); float32, unit column stride, xl / xr / out / att / bias / agg rows 16-B aligned.
+ * wgamd_gatv2_bwd_dst_f32 (destination-major, given g = dL/d agg [n_rows, ldg] and the kept alpha, agg): per edge and head
+ *   dalpha = g[i, h] . XL[j, h],  de = alpha (dalpha - g[i, h] . agg[i, h])                            de [E, H]
+ *   dxr[i] = sum_k de att * LeakyReLU'(XL[j] + XR[i])                                                   [n_rows, H C]
+ *   datt_part[b] = sum over the 16 rows of workgroup b of de LeakyReLU(XL[j] + XR[i])                   [wgamd_gatv2_bwd_blocks, H C]
+ * (datt is the sum of the partial rows, taken by the caller in a fixed order).
+ * wgamd_gatv2_bwd_src_f32 (source-major over the hop's transpose: row_ptr_t / col_t = destination rows / perm = CSR edge of
+ * every transposed entry, over n_src rows of xl):
+ *   gx[j] (+)= sum_k (alpha[k, h] g[i, h C :] + de[k, h] att * LeakyReLU'(XL[j] + XR[i]))
+ * entries added in transposed-CSR order.  No atomics in any of the three. */
+int wgamd_gatv2_supported(int H, int C);
+int64_t wgamd_gatv2_bwd_blocks(int64_t n_rows);
+wholememory_error_code_t wgamd_gatv2_attention_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* xl, int64_t ldxl,
+                                                   const float* xr, int64_t ldxr, const int64_t* xr_rows, const float* att, int H,
+                                                   int C, float negative_slope, const float* bias, int relu, int mean, float* out,
+                                                   int64_t ldo, float* alpha, float* agg, void* stream);
+wholememory_error_code_t wgamd_gatv2_bwd_dst_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* xl, int64_t ldxl,
+                                                 const float* xr, int64_t ldxr, const int64_t* xr_rows, const float* att, int H, int C,
+                                                 float negative_slope, const float* alpha, const float* g, int64_t ldg,
+                                                 const float* agg, float* dxr, float* de, float* datt_part, void* stream);
+wholememory_error_code_t wgamd_gatv2_bwd_src_f32(const int* row_ptr_t, const int* col_t, const int* perm, int64_t n_src,
+                                                 const float* xl, int64_t ldxl, const float* xr, int64_t ldxr,
+                                                 const int64_t* xr_rows, const float* att, int H, int C, float negative_slope,
+                                                 const float* alpha, const float* de, const float* g, int64_t ldg, float* gx,
+                                                 int64_t ldgx, int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
