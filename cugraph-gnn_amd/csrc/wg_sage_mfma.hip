@@ -42,6 +42,19 @@
 //     ks+1 dealt between the MFMAs of k-step ks by sched_group_barrier) and the weight planes run two k-steps ahead:
 //     256 -> 256 layer 1.69 -> 1.51 ms (no weight loads at all: 1.34; the multiplying waves alone: 0.90, of which 0.43 is
 //     the matrix pipe; the fetching waves alone: 0.73 = the HBM floor of the shape).
+//   * THE 64-COLUMN HEAD IN HALF-TILE MODE (256 -> 47, run at 64) has four multiplying waves too, one 32 x 32 accumulator each:
+//     wave w owns row tile w >> 1 and column tile w & 1 of the 64 x 64 output tile and runs, for that accumulator, the k-steps,
+//     the six products and the weight stream of the wider layers — every output element goes through the chain of MFMAs it goes
+//     through as a column of an N = 256 launch, bit for bit (tests/test_gpu_sage_head_tiles.py).  Until round 12 ONE wave owned
+//     the whole tile (CW = N / 64 = 1): 768 MFMAs per tile and the fragment splits on the one SIMD it shared with a fetching
+//     wave, which it held back for the whole multiply while the other three matrix pipes idled — and a step ends at a barrier
+//     that waits for all four fetching waves.  Dealt over the four SIMDs each fetching wave is held back by a quarter of it.  The
+//     two waves of a row tile read the same self rows (64 KB of L2 hits per tile against ~600 KB of row fetches), each wave only
+//     its own 32 columns of the weight planes.  Stand-alone harness at 192,512 rows: whole 0.417-0.433 -> 0.370-0.374 ms, the
+//     multiplying waves alone 0.233 -> 0.152, the fetching waves alone 0.267 either way (profiles/r12/README.md).  A head wave's
+//     k-step is 6 MFMAs instead of 24, so "two k-steps ahead" covers a quarter of the time; a weight ring of six (five k-steps
+//     ahead) and self rows six k-steps ahead were tried for that and bought nothing (whole 0.358-0.385, multiplying waves
+//     alone 0.154-0.162): not kept.
 //   * one s_barrier per step behind an LDS-only wait (s_waitcnt lgkmcnt(0)): neither side's global loads are drained.
 //   * TILES ARE HANDED OUT BY TICKET, not by a fixed stride.  A workgroup's first tile is its block index; every later one is
 //     gridDim.x + atomicAdd(ticket, 1) on the launch's slot in device memory (`mfma_args::tickets`, `ticket_slot` below), so a
@@ -120,13 +133,16 @@ __device__ __forceinline__ void mfma_valu_interleave()
 // rotated back to position 0 when a range ends, so every range starts with b[0] = its first k-step, b[1] = its second.
 // RawT: the A fragment as it travels — fp32 (`araw_t`), or the 16-bit self rows of a float16 / bfloat16 table (`araw16_t`),
 // which become fp32 where they are split, a k-step or two after their load was requested.
-template <int RT, int AD, typename RawT = araw_t<RT>, typename LoadA>
-__device__ __forceinline__ void consume_range(const mfma_args& a, f32x16 (&c)[RT][2], bfrag_t (&b)[3], int ks0, int ks1, int cw,
-                                              int lane, LoadA load_a)
+// The wave multiplies RT row tiles by the CT column tiles that start at column col0: 2 x 2 for a wave that owns 64 columns of a
+// 64-row tile, 1 x 1 for a head wave (N = 64: one accumulator per wave, see the kernel).  An accumulator sees the same k-steps
+// and the same six products in the same order either way.
+template <int RT, int AD, typename RawT = araw_t<RT>, int CT, typename LoadA>
+__device__ __forceinline__ void consume_range(const mfma_args& a, f32x16 (&c)[RT][CT], bfrag_n<CT> (&b)[3], int ks0, int ks1,
+                                              int col0, int lane, LoadA load_a)
 {
   const int lm = lane & 31, lh = lane >> 5;
   const int64_t b_plane_dw = (int64_t)a.KS * a.N * 8;
-  const uint32_t* b_lane   = reinterpret_cast<const uint32_t*>(a.w_tiles) + ((int64_t)(cw * 64 + lm)) * 8 + lh * 4;
+  const uint32_t* b_lane   = reinterpret_cast<const uint32_t*>(a.w_tiles) + ((int64_t)(col0 + lm)) * 8 + lh * 4;
   RawT raw[AD];
   afrag_t<RT> fa[2];
   const int kl = ks1 - 1;
@@ -141,7 +157,9 @@ __device__ __forceinline__ void consume_range(const mfma_args& a, f32x16 (&c)[RT
     load_b_planes(b[(i + 2) % 3], b_lane, b_plane_dw, a.N, kb);
     mma_frags<RT>(c, fa[i & 1], b[i % 3]);
     split_raw<RT>(raw[(i + 1) % AD], fa[(i + 1) & 1]);
-    mfma_valu_interleave<4, 6 * RT * 2 - 4, 5>();
+    // (one accumulator: its six MFMAs depend on each other, the split of one row tile — ~55 VALU — goes between them)
+    if constexpr (RT * CT == 1) mfma_valu_interleave<0, 6, 9>();
+    else mfma_valu_interleave<4, 6 * RT * CT - 4, 5>();
     __builtin_amdgcn_sched_barrier(0);
   };
   int ks = ks0;
@@ -161,10 +179,10 @@ __device__ __forceinline__ void consume_range(const mfma_args& a, f32x16 (&c)[RT
   if (r > 4) step(std::integral_constant<int, 4>{}, ks + 4);
   const int rot = (ks1 - ks0) % 3;
   if (rot == 1) {
-    const bfrag_t t = b[0];
+    const bfrag_n<CT> t = b[0];
     b[0] = b[1], b[1] = b[2], b[2] = t;
   } else if (rot == 2) {
-    const bfrag_t t = b[0];
+    const bfrag_n<CT> t = b[0];
     b[0] = b[2], b[2] = b[1], b[1] = t;
   }
 }
@@ -286,12 +304,15 @@ struct static_consumer {
 // table changes the ROW LOADS only — 8 B per lane instead of 16, converted to fp32 exactly where the value is summed or split
 // (wg_x16.hpp) — so the lane mapping, the LDS image, the sums' order and every bit of the result are those of the float32 table
 // holding the same values.
+// HEAD (half-tile mode, N = 64): CW = 4 multiplying waves that own ONE 32 x 32 accumulator of the 64 x 64 output tile each — wave
+// w row tile w >> 1 and column tile w & 1 — instead of one wave owning all four.
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename IdT, int LG, int TR, int CW, bool OFF32, int FC, bool HALF = false, typename XT = float>
+template <typename IdT, int LG, int TR, int CW, bool OFF32, int FC, bool HALF = false, typename XT = float, bool HEAD = false>
 __global__ void __launch_bounds__((CW + kProducerWaves) * 64)
 sage_layer_mfma_kernel(mfma_args a)
 {
   static_assert(!HALF || FC == 0, "the half-tile mode runs the runtime-shape consumer");
+  static_assert(!HEAD || (HALF && CW == 4 && TR == 64), "one accumulator per wave: four waves over a 64 x 64 tile in half-tile mode");
   // [2 tiles][TR][SD] fp32 + 16 floats of slack + [CW][8][64] epilogue scratch + role keys
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tile_dw = TR * a.SD;
@@ -403,13 +424,21 @@ sage_layer_mfma_kernel(mfma_args a)
         advance(t_next);
       }
     } else {
-      constexpr int RT = TR / 32;
+      // this wave's share of the 64-row tile: RT row tiles from row tile rt0 on, CT column tiles from column col0 on — all of
+      // the rows and 64 columns, or (HEAD) one 32 x 32 accumulator.  The four head waves sit one per SIMD beside one fetching
+      // wave each (waves are dealt to the SIMDs in order), a quarter of the tile's MFMAs and fragment splits on each: the single
+      // wave that owned the whole tile held the fetching wave of ITS SIMD back for the whole multiply, and the step's barrier
+      // waits for that wave.  The two waves of a row tile read the same A — LDS for the mean half, the same self rows from global
+      // memory (L2 hits) — and each wave only its own 32 columns of the weight planes.
+      constexpr int RT = HEAD ? 1 : TR / 32, CT = HEAD ? 1 : 2;
+      const int rt0    = HEAD ? wave >> 1 : 0;
+      const int col0   = HEAD ? (wave & 1) * 32 : wave * 64;
       float* scratch = lds + 2 * tile_dw + 16 + wave * kScratchDw;
-      f32x16 c[RT][2];
-      bfrag_t b[3];   // the weight stream, two k-steps ahead (consume_range)
+      f32x16 c[RT][CT];
+      bfrag_n<CT> b[3];   // the weight stream, two k-steps ahead (consume_range)
       {
         const uint32_t* b_lane =
-          reinterpret_cast<const uint32_t*>(a.w_tiles) + ((int64_t)(wave * 64 + (lane & 31))) * 8 + (lane >> 5) * 4;
+          reinterpret_cast<const uint32_t*>(a.w_tiles) + ((int64_t)(col0 + (lane & 31))) * 8 + (lane >> 5) * 4;
         load_b_planes(b[0], b_lane, (int64_t)a.KS * a.N * 8, a.N, 0);
         load_b_planes(b[1], b_lane, (int64_t)a.KS * a.N * 8, a.N, 1);
       }
@@ -425,7 +454,7 @@ sage_layer_mfma_kernel(mfma_args a)
           const self_t* self_ptr[RT];
 #pragma unroll
           for (int rt = 0; rt < RT; rt++) {
-            const int64_t row  = row0 + rt * 32 + (lane & 31);
+            const int64_t row  = row0 + (rt0 + rt) * 32 + (lane & 31);
             const int64_t srow = a.self_rows[row < a.n_rows ? row : a.n_rows - 1];
             self_ptr[rt]       = reinterpret_cast<const self_t*>(reinterpret_cast<const char*>(a.x) + table_row<IdT>(src_ids, srow) * a.row_scale) +
                            (lane >> 5) * 8;
@@ -433,14 +462,14 @@ sage_layer_mfma_kernel(mfma_args a)
 #pragma unroll
           for (int rt = 0; rt < RT; rt++)
 #pragma unroll
-            for (int ct = 0; ct < 2; ct++)
+            for (int ct = 0; ct < CT; ct++)
 #pragma unroll
               for (int i = 0; i < 16; i++) c[rt][ct][i] = 0.f;
           store_agg<TR, CW>(a, lds + ((n - 1) & 1) * tile_dw, row0, wave, lane);
-          const float* a_lane = lds + ((n - 1) & 1) * tile_dw + (lane & 31) * a.SD + (lane >> 5) * 8;
-          consume_range<RT, 1>(a, c, b, 0, KSh, wave, lane, [&](araw_t<RT>& f, int ks) { load_a_raw<RT>(f, a_lane, a.SD, ks); });
+          const float* a_lane = lds + ((n - 1) & 1) * tile_dw + (rt0 * 32 + (lane & 31)) * a.SD + (lane >> 5) * 8;
+          consume_range<RT, 1>(a, c, b, 0, KSh, col0, lane, [&](araw_t<RT>& f, int ks) { load_a_raw<RT>(f, a_lane, a.SD, ks); });
           if constexpr (kEB == 4) {
-            consume_range<RT, 2>(a, c, b, KSh, a.KS, wave, lane, [&](araw_t<RT>& f, int ks) {
+            consume_range<RT, 2>(a, c, b, KSh, a.KS, col0, lane, [&](araw_t<RT>& f, int ks) {
 #pragma unroll
               for (int rt = 0; rt < RT; rt++) {
                 const float* p = self_ptr[rt] + (ks - KSh) * 16;
@@ -451,13 +480,14 @@ sage_layer_mfma_kernel(mfma_args a)
           } else {
             // a 16-bit table: the lane's half k-step is 16 contiguous bytes (8-B aligned: rows are), ONE load, kept as it
             // came until the k-step is split
-            consume_range<RT, 2, araw16_t<XT, RT>>(a, c, b, KSh, a.KS, wave, lane, [&](araw16_t<XT, RT>& f, int ks) {
+            consume_range<RT, 2, araw16_t<XT, RT>>(a, c, b, KSh, a.KS, col0, lane, [&](araw16_t<XT, RT>& f, int ks) {
 #pragma unroll
               for (int rt = 0; rt < RT; rt++)
                 f.v[rt] = *reinterpret_cast<const x16::u32x4_a8*>(self_ptr[rt] + (ks - KSh) * 16);
             });
           }
-          epilogue<RT>(a, c, row0, wave, lane, scratch);
+          if constexpr (HEAD) epilogue_head(a, c[0][0], row0 + rt0 * 32, col0, lane, scratch);
+          else epilogue<RT>(a, c, row0, wave, lane, scratch);
         }
         lds_barrier();
         if (t_cur >= n_tiles) break;
@@ -702,9 +732,12 @@ __host__ inline bool use_half_tiles(int F)
   return F % 16 == 0 && lds_bytes(F, 64) > kLdsBudget && lds_bytes_half(F) <= kLdsBudget;
 }
 
-template <typename IdT, int LG, int CW, typename XT = float>
+// NW = N / 64.  N = 64 is the HEAD layout of the kernel: four multiplying waves, one 32 x 32 accumulator each.
+template <typename IdT, int LG, int NW, typename XT = float>
 void launch_half(mfma_args a, hipStream_t st)
 {
+  constexpr bool HEAD = NW == 1;
+  constexpr int CW    = HEAD ? 4 : NW;
   const int cus         = stream_cu_count(st);
   a.tickets             = ticket_slot(st);
   a.SD                  = row_stride_half_dw(a.F);
@@ -716,8 +749,8 @@ void launch_half(mfma_args a, hipStream_t st)
     kern<<<grid, (CW + kProducerWaves) * 64, lds, st>>>(a);
     WG_HIP_CHECK(hipGetLastError());
   };
-  if (a.x_bytes != 0) go(sage_layer_mfma_kernel<IdT, LG, 64, CW, true, 0, true, XT>);
-  else go(sage_layer_mfma_kernel<IdT, LG, 64, CW, false, 0, true, XT>);
+  if (a.x_bytes != 0) go(sage_layer_mfma_kernel<IdT, LG, 64, CW, true, 0, true, XT, HEAD>);
+  else go(sage_layer_mfma_kernel<IdT, LG, 64, CW, false, 0, true, XT, HEAD>);
 }
 
 template <typename IdT, int LG, int TR, int CW, int FC = 0, typename XT = float>

@@ -460,9 +460,11 @@ template <int RT>
 struct afrag_t {
   u32x4 v[RT][3];  // [row tile][plane]
 };
-struct bfrag_t {
-  u32x4 v[2][3];  // [col tile][plane]
+template <int CT>
+struct bfrag_n {
+  u32x4 v[CT][3];  // [col tile][plane]
 };
+using bfrag_t = bfrag_n<2>;   // a wave's 64 columns; bfrag_n<1>: the 32 columns of a head wave (half-tile mode, N = 64)
 struct braw_t {
   f32x4 v[2][2];  // [col tile][k 0-3 | k 4-7 of this lane's half k-step]: the fp32 weight as it travels
 };
@@ -539,13 +541,14 @@ __device__ __forceinline__ void load_b(braw_t& f, const float* b_lane, int n_col
 // HALF mode (F > 148, K = 512: the multiplying waves are the busier side there and the split of the weight in registers
 // costs more than the bytes it saves: 1.74 vs 1.69 ms at 256 -> 256 in round 2; with the round-3 loop there are no
 // registers left for fp32 fragments two k-steps ahead AND split planes) keeps the pre-split planes [3][KS][N][8 dwords]
-__device__ __forceinline__ void load_b_planes(bfrag_t& f, const uint32_t* b_lane, int64_t b_plane_dw, int n_cols, int ks)
+template <int CT>
+__device__ __forceinline__ void load_b_planes(bfrag_n<CT>& f, const uint32_t* b_lane, int64_t b_plane_dw, int n_cols, int ks)
 {
 #ifdef WG_ABL_NO_B
   return;
 #endif
 #pragma unroll
-  for (int ct = 0; ct < 2; ct++)
+  for (int ct = 0; ct < CT; ct++)
 #pragma unroll
     for (int p = 0; p < 3; p++)
       f.v[ct][p] = *reinterpret_cast<const u32x4*>(b_lane + p * b_plane_dw + ((int64_t)ks * n_cols + ct * 32) * 8);
@@ -569,8 +572,8 @@ __device__ __forceinline__ void split_b(const braw_t& r, bfrag_t& f)
   }
 }
 
-template <int RT>
-__device__ __forceinline__ void mma_frags(f32x16 (&c)[RT][2], const afrag_t<RT>& fa, const bfrag_t& fb)
+template <int RT, int CT>
+__device__ __forceinline__ void mma_frags(f32x16 (&c)[RT][CT], const afrag_t<RT>& fa, const bfrag_n<CT>& fb)
 {
   // smallest terms first; per accumulator tile the six products are independent MFMAs on the same accumulator
   constexpr int pa[6] = {2, 0, 1, 1, 0, 0};
@@ -580,7 +583,7 @@ __device__ __forceinline__ void mma_frags(f32x16 (&c)[RT][2], const afrag_t<RT>&
 #pragma unroll
     for (int rt = 0; rt < RT; rt++)
 #pragma unroll
-      for (int ct = 0; ct < 2; ct++)
+      for (int ct = 0; ct < CT; ct++)
         c[rt][ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fa.v[rt][pa[t]]),
                                                             __builtin_bit_cast(bf16x8, fb.v[ct][pb[t]]), c[rt][ct], 0, 0, 0);
 }
@@ -626,6 +629,32 @@ __device__ __forceinline__ void epilogue(const mfma_args& a, f32x16 (&c)[RT][2],
         if (full || row0 + r + rl < a.n_rows) *reinterpret_cast<f32x4*>(obase + (int64_t)r * a.ldo) = v;
       }
     }
+}
+
+// The same for ONE 32 x 32 accumulator (a head wave of the half-tile mode: rows [row0, row0 + 32), columns [col0, col0 + 32)):
+// eight rows of 32 columns per trip through the wave's scratch [8][32], out as 16 B per lane = 128 B per row, one store
+// instruction per trip.  The same sum c + bias and the same maximum per element as above.
+__device__ __forceinline__ void epilogue_head(const mfma_args& a, const f32x16& c, int64_t row0, int col0, int lane, float* scratch)
+{
+  const int lm = lane & 31, lh = lane >> 5;
+  const float bj = a.bias ? a.bias[col0 + lm] : 0.f;
+  if (a.debug & 4) {
+    if (c[0] == 12345.678f) a.out[0] = c[3] + c[5];
+    return;
+  }
+  const bool full = row0 + 32 <= a.n_rows;
+  const int rl = lane >> 3, cl = (lane & 7) * 4;
+  float* obase = a.out + (row0 + rl) * a.ldo + col0 + cl;
+#pragma unroll
+  for (int g = 0; g < 4; g++) {
+#pragma unroll
+    for (int jj = 0; jj < 4; jj++) {
+      const float v = c[4 * g + jj] + bj;
+      scratch[(jj + 4 * lh) * 32 + lm] = a.relu ? fmaxf(v, 0.f) : v;
+    }
+    const f32x4 v = *reinterpret_cast<const f32x4*>(scratch + rl * 32 + cl);
+    if (full || row0 + 8 * g + rl < a.n_rows) *reinterpret_cast<f32x4*>(obase + (int64_t)(8 * g) * a.ldo) = v;
+  }
 }
 
 // Training: the multiplying waves copy the aggregate half of the tile they are about to multiply (complete behind the barrier,

@@ -192,9 +192,9 @@ def sage_layer_fused_supported(F_: int, N: int) -> bool:
 
 def sage_layer_fused_preferred(F_: int, N: int) -> bool:
     """Shapes where the one-kernel layer beats aggregate kernel + library GEMM.  bf16x3 kernel: every shape it supports,
-    a padded head included (the 47-class layer of the products model runs as N = 64 with one multiplying wave per CU: with
-    the round-3 half-tile kernel 0.38 ms against 0.54 ms for aggregate + GEMM at 196 k rows, 256 -> 64; 0.043 against 0.052
-    at 16 k rows; the round-2 kernel lost there, 0.46 against 0.20 at 65 k rows).  fp32-MFMA kernel: only when two operand
+    a padded head included (the 47-class layer of the products model runs as N = 64, since round 12 with four multiplying
+    waves of one 32 x 32 accumulator each; with one multiplying wave per CU the round-3 half-tile kernel took 0.38 ms
+    against 0.54 ms for aggregate + GEMM at 196 k rows, 256 -> 64; 0.043 against 0.052 at 16 k rows; the round-2 kernel lost there, 0.46 against 0.20 at 65 k rows).  fp32-MFMA kernel: only when two operand
     tiles fit the 160 KB of LDS and the width needs no padding."""
     if not sage_layer_fused_supported(F_, N):
         return False
