@@ -51,6 +51,17 @@ class HeteroTransformerRelation(Structure):
                 ("F", c_int), ("ids_kind", c_int), ("D", c_int), ("H", c_int), ("col0", c_int)]
 
 
+NORM_ACT_MAX_SEGMENTS, NORM_ACT_NORM, NORM_ACT_RELU, NORM_ACT_SAVE_STATS = 8, 1, 2, 4   # WGAMD_NORM_ACT_* (include/wgamd_ext.h)
+
+
+class NormActSegment(Structure):
+    """wgamd_norm_act_segment (include/wgamd_ext.h)."""
+    _fields_ = [("x", c_void_p), ("ldx", c_int64), ("residual", c_void_p), ("ld_res", c_int64), ("out", c_void_p), ("ldo", c_int64),
+                ("weight", c_void_p), ("bias", c_void_p), ("stats", c_void_p), ("n_rows", c_int64), ("C", c_int), ("seed_index", c_int),
+                ("grad_out", c_void_p), ("ldg", c_int64), ("grad_in", c_void_p), ("ld_gi", c_int64), ("partials", c_void_p),
+                ("dweight", c_void_p), ("dbias", c_void_p)]
+
+
 class WholeGraphLibraryError(RuntimeError):
     pass
 
@@ -401,6 +412,13 @@ SYMBOLS = {
     "wgamd_gatv2_bwd_src_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                         c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                         c_int, c_void_p]),
+    # NormDropoutAct (wg_norm_act.hip)
+    "wgamd_norm_act_supported": (c_int, [c_int]),
+    "wgamd_norm_act_segment_seed": (c_ulonglong, [c_ulonglong, c_int]),
+    "wgamd_norm_act_bwd_blocks": (c_int64, [c_int64, c_int]),
+    "wgamd_norm_act_f32": (c_int, [c_void_p, c_int, c_float, c_float, c_ulonglong, c_int, c_void_p]),
+    "wgamd_norm_act_bwd_f32": (c_int, [c_void_p, c_int, c_float, c_float, c_ulonglong, c_int, c_void_p]),
+    "wgamd_norm_act_wgrad_f32": (c_int, [c_void_p, c_int, c_void_p]),
     "wgamd_bias_act_rows_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "wgamd_gat_transform_heads_supported": (c_int, [c_int, c_int, c_int]),
     "wgamd_gat_transform_weight_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -5,12 +5,14 @@ and into its cugraph-pyg examples.  Six layers run ONE kernel per hop of a call 
 (each an autograd Function over the hops): ``SAGEConv``, ``GCNConv``, ``RGCNConv``, ``TransformerConv``, ``GINConv``, and
 ``HeteroConv`` over SAGEConv relations (one kernel per hop and destination type).  ``GATConv`` and ``HeteroConv`` over GATConv
 relations are aggregate kernels with a dense tail.  ``GATv2Conv`` is two library GEMMs and ONE attention kernel per hop on
-the transformed rows (its logit is not linear in the neighbour row: no aggregate-first form).
+the transformed rows (its logit is not linear in the neighbour row: no aggregate-first form).  ``NormDropoutAct`` /
+``HeteroNormDropoutAct`` are what the reference's models put BETWEEN two layers (residual add, LayerNorm, dropout, ReLU): one
+launch forward and two backward for all node types of a layer.
 
 Order of the file: ctypes helpers and the plumbing the one-kernel layers share; the SAGE-era kernel wrappers, derived-weight
 caches and GAT kernel wrappers; graph forms (``_single_hop``, ``LazyRows``, ``HopGraph``, ``LayerGraph``) and the helpers that
-walk a layer graph; then a section per layer — SAGE and GAT, GCN, RGCN, transformer, GIN, GATv2, heterogeneous — each with its kernel
-wrappers, its autograd Function(s) and its module.
+walk a layer graph; then a section per layer — SAGE and GAT, GCN, RGCN, transformer, GIN, GATv2, heterogeneous, NormDropoutAct —
+each with its kernel wrappers, its autograd Function(s) and its module.
 
 Shared by the one-kernel layers, so that they cannot drift apart: ``_hop_args`` (the eight leading arguments of a launch over a
 hop, with their checks), ``_out_rows`` (a launch's output: the caller's or a fresh one), ``_hops`` / ``_sum_over_hops`` (a layer
@@ -233,11 +235,11 @@ def _capturing() -> bool:
 
 
 def _refuse_capture(layer, caches: str):
-    """RuntimeError under HIP-graph capture for a layer that keeps ``caches`` in Python (derived weights against the parameters'
+    """RuntimeError under HIP-graph capture for a layer (a module, or its name) that keeps ``caches`` in Python (derived weights against the parameters'
     versions, or per-graph forms against the graph object): a replayed graph would keep using the ones of the capture."""
     if _capturing():
         raise RuntimeError("wholegraph_amd.nn.%s is not supported under HIP-graph capture (loader.PerBatchStep): its %s are not "
-                           "capture-safe; SAGEConv layers are" % (type(layer).__name__, caches))
+                           "capture-safe; SAGEConv layers are" % (layer if isinstance(layer, str) else type(layer).__name__, caches))
 
 
 def _graph_epoch() -> int:
@@ -4990,3 +4992,315 @@ class HeteroConv(torch.nn.Module):
             rows = r.out_rows if r.out_rows is not None else torch.arange(r.n_rows, device=dev)
             out[et[2]] = out[et[2]].index_add(0, rows, y)
         return {t: torch.relu(v) for t, v in out.items()} if act == "relu" else out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# NormDropoutAct: the row-wise block between two layers (LayerNorm, dropout, ReLU, residual) — csrc/wg_norm_act.hip
+# ---------------------------------------------------------------------------------------------------------------------
+_M64 = (1 << 64) - 1
+norm_act_launches = 0        # forward launches of wgamd_norm_act_f32 so far (tests: a dict call is ONE launch per 8 types)
+
+
+def norm_dropout_act_supported(C: int) -> bool:
+    """Widths of the NormDropoutAct kernels (``wgamd_norm_act_supported``, answered on the host): C % 4 == 0, 4 <= C <= 1024."""
+    return bool(L.lib().wgamd_norm_act_supported(int(C)))
+
+
+def segment_seed(seed: int, k: int) -> int:
+    """The dropout seed of segment ``k`` (the k-th node type of a dict call) under ``seed``: the host twin of the kernel
+    launch's ``wgamd_norm_act_segment_seed`` — the splitmix64 output function of ``seed + (k + 1) * 0x9E3779B97F4A7C15``."""
+    z = (int(seed) + 0x9E3779B97F4A7C15 * (int(k) + 1)) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def _norm_act_auto_seed() -> int:
+    """The seed of a training call that passes none: ``torch.initial_seed()`` mixed with one draw of torch's default CPU
+    generator, which counts the calls since ``torch.manual_seed`` — host only (no device sync), and the same sequence after
+    every ``torch.manual_seed(s)``, also when ``s`` was the seed before.  The draw advances the global CPU random stream."""
+    count = int(torch.empty((), dtype=torch.int64).random_())
+    return segment_seed((torch.initial_seed() ^ count) & _M64, 0)
+
+
+def _norm_act_chunks(n: int):
+    """``range`` objects of at most ``NORM_ACT_MAX_SEGMENTS`` consecutive segments: the launches of an ``n``-type dict call."""
+    return [range(a, min(a + L.NORM_ACT_MAX_SEGMENTS, n)) for a in range(0, n, L.NORM_ACT_MAX_SEGMENTS)]
+
+
+def _norm_act_flags(norm: bool, relu: bool, save: bool = False) -> int:
+    return (L.NORM_ACT_NORM if norm else 0) | (L.NORM_ACT_RELU if relu else 0) | (L.NORM_ACT_SAVE_STATS if save and norm else 0)
+
+
+def _norm_act_vec_ok(v, C: int) -> bool:
+    return v is None or (v.dtype == torch.float32 and v.is_cuda and v.dim() == 1 and v.numel() == C and v.is_contiguous()
+                         and v.data_ptr() % 16 == 0)
+
+
+def _norm_act_rows_ok(t) -> bool:
+    """``_kernel_rows_ok`` and rows that do not overlap: at least C floats apart (an expanded tensor's are 0 apart)."""
+    return _kernel_rows_ok(t) and t.stride(0) >= t.shape[1]
+
+
+def _norm_act_kernel_ok(x, weight, bias, residual) -> bool:
+    """The kernel's domain: float32 device rows with unit column stride and 16-B alignment, a supported width, ``weight`` /
+    ``bias`` of that width."""
+    if not (torch.is_tensor(x) and x.dim() == 2 and _norm_act_rows_ok(x) and norm_dropout_act_supported(x.shape[1])):
+        return False
+    if residual is not None and not (residual.dim() == 2 and residual.shape == x.shape and _norm_act_rows_ok(residual)):
+        return False
+    return _norm_act_vec_ok(weight, x.shape[1]) and _norm_act_vec_ok(bias, x.shape[1])
+
+
+def norm_act_forward(segs, norm=True, relu=True, eps=1e-5, p=0.0, seed=0, seed_indices=None, save_stats=False):
+    """``wgamd_norm_act_f32`` over ``segs = [(x, residual, weight, bias), ...]`` (include/wgamd_ext.h): ONE launch per 8
+    segments.  ``seed_indices[k]``: the segment's index under ``seed`` (``segment_seed``), negative = ``seed`` itself is the
+    segment's seed.  Returns ``(outs, stats)``; ``stats[k]`` [n, 2] = (mean, rstd) per row with ``save_stats`` and ``norm``."""
+    global norm_act_launches
+    outs = [torch.empty(x.shape, dtype=torch.float32, device=x.device) for x, _, _, _ in segs]
+    stats = [torch.empty((x.shape[0], 2), dtype=torch.float32, device=x.device) if save_stats and norm else None for x, _, _, _ in segs]
+    flags = _norm_act_flags(norm, relu, save_stats)
+    for chunk in _norm_act_chunks(len(segs)):
+        arr = (L.NormActSegment * len(chunk))()
+        for d, k in zip(arr, chunk):
+            x, res, w, b = segs[k]
+            d.x, d.ldx, d.residual, d.ld_res = x.data_ptr(), x.stride(0), _ptr(res), 0 if res is None else res.stride(0)
+            d.out, d.ldo, d.weight, d.bias, d.stats = outs[k].data_ptr(), outs[k].stride(0), _ptr(w), _ptr(b), _ptr(stats[k])
+            d.n_rows, d.C, d.seed_index = x.shape[0], x.shape[1], -1 if seed_indices is None else seed_indices[k]
+        L.check(L.lib().wgamd_norm_act_f32(arr, len(chunk), float(eps), float(p), int(seed) & _M64, flags, get_stream()),
+                "wgamd_norm_act_f32")
+        norm_act_launches += 1
+    return outs, stats
+
+
+def norm_act_backward(segs, grads, stats, norm=True, relu=True, eps=1e-5, p=0.0, seed=0, seed_indices=None, need_w=None,
+                      need_b=None):
+    """``wgamd_norm_act_bwd_f32`` and ``wgamd_norm_act_wgrad_f32`` over the forward's ``segs`` and ``stats``: two launches per 8
+    segments.  Returns ``(dz, dweight, dbias)`` lists; ``dz[k]`` is the gradient of segment k's ``x`` and of its residual,
+    ``dweight[k]`` / ``dbias[k]`` are None where ``need_w[k]`` / ``need_b[k]`` is false (or without ``norm``)."""
+    n = len(segs)
+    need_w = [False] * n if need_w is None or not norm else need_w
+    need_b = [False] * n if need_b is None or not norm else need_b
+    dz = [torch.empty(x.shape, dtype=torch.float32, device=x.device) for x, _, _, _ in segs]
+    dw = [torch.empty(x.shape[1], dtype=torch.float32, device=x.device) if need_w[k] else None for k, (x, _, _, _) in enumerate(segs)]
+    db = [torch.empty(x.shape[1], dtype=torch.float32, device=x.device) if need_b[k] else None for k, (x, _, _, _) in enumerate(segs)]
+    lib, flags, keep = L.lib(), _norm_act_flags(norm, relu), []
+    for chunk in _norm_act_chunks(n):
+        arr = (L.NormActSegment * len(chunk))()
+        for d, k in zip(arr, chunk):
+            x, res, w, b = segs[k]
+            g = grads[k]
+            assert _norm_act_rows_ok(g) and g.shape == x.shape
+            d.x, d.ldx, d.residual, d.ld_res = x.data_ptr(), x.stride(0), _ptr(res), 0 if res is None else res.stride(0)
+            d.weight, d.bias, d.stats = _ptr(w), _ptr(b), _ptr(stats[k])
+            d.n_rows, d.C, d.seed_index = x.shape[0], x.shape[1], -1 if seed_indices is None else seed_indices[k]
+            d.grad_out, d.ldg, d.grad_in, d.ld_gi = g.data_ptr(), g.stride(0), dz[k].data_ptr(), dz[k].stride(0)
+            if need_w[k] or need_b[k]:
+                part = torch.empty((int(lib.wgamd_norm_act_bwd_blocks(x.shape[0], x.shape[1])), 2 * x.shape[1]), dtype=torch.float32,
+                                   device=x.device)
+                keep.append(part)
+                d.partials, d.dweight, d.dbias = (part.data_ptr() if part.numel() else None), _ptr(dw[k]), _ptr(db[k])
+        L.check(lib.wgamd_norm_act_bwd_f32(arr, len(chunk), float(eps), float(p), int(seed) & _M64, flags, get_stream()),
+                "wgamd_norm_act_bwd_f32")
+        if any(need_w[k] or need_b[k] for k in chunk):
+            L.check(lib.wgamd_norm_act_wgrad_f32(arr, len(chunk), get_stream()), "wgamd_norm_act_wgrad_f32")
+    return dz, dw, db
+
+
+def _norm_act_torch(x, weight, bias, residual, norm, eps, p, training, relu, mask=None):
+    """The same formula out of torch ops under ordinary autograd.  ``mask`` None: ``torch.nn.functional.dropout`` (torch's
+    own random stream); else the keep factors (0 or 1 / (1 - p)) to multiply with."""
+    z = x if residual is None else x + residual
+    if norm:
+        z = torch.nn.functional.layer_norm(z, (z.shape[-1],), weight, bias, eps)
+    if mask is not None:
+        z = z * mask
+    elif training and p > 0:
+        z = torch.nn.functional.dropout(z, p, True)
+    return torch.relu(z) if relu else z
+
+
+class _NormAct(torch.autograd.Function):
+    """``norm_dropout_act`` on the kernel route over n segments: ``tensors`` = the n ``x``, then the n residuals, weights and
+    biases (None where absent).  Keeps x, residual, weight, the row statistics and the seed — no mask and not the output; the
+    backward is ``norm_act_backward``.  A backward under ``create_graph=True`` (double backward) runs the formula out of torch
+    ops with the kernel's own mask instead."""
+
+    @staticmethod
+    def forward(ctx, conf, n, *tensors):
+        norm, relu, eps, p, seed, seed_indices = conf
+        segs = [tuple(None if t is None else t.detach() for t in tensors[k::n]) for k in range(n)]
+        outs, stats = norm_act_forward(segs, norm, relu, eps, p, seed, seed_indices, save_stats=True)
+        ctx.conf, ctx.n, ctx.stats = conf, n, stats
+        ctx.save_for_backward(*tensors)
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        norm, relu, eps, p, seed, seed_indices = ctx.conf
+        n, tensors = ctx.n, ctx.saved_tensors
+        if torch.is_grad_enabled():
+            return (None, None) + _norm_act_double_backward(ctx, tensors, grads)
+        segs = [tuple(None if t is None else t.detach() for t in tensors[k::n]) for k in range(n)]
+        gs = []
+        for (x, _, _, _), g in zip(segs, grads):
+            if g is None:
+                g = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
+            elif not _norm_act_rows_ok(g):        # (an expanded or 16-bit gradient: one copy into rows the kernel reads)
+                g = torch.empty(x.shape, dtype=torch.float32, device=x.device).copy_(g)
+            gs.append(g)
+        need = ctx.needs_input_grad[2:]
+        dz, dw, db = norm_act_backward(segs, gs, ctx.stats, norm, relu, eps, p, seed, seed_indices,
+                                       need_w=[bool(need[2 * n + k]) for k in range(n)],
+                                       need_b=[bool(need[3 * n + k]) for k in range(n)])
+        out = [dz[k] if need[k] else None for k in range(n)]
+        out += [dz[k] if need[n + k] else None for k in range(n)]
+        return (None, None) + tuple(out + dw + db)
+
+
+def _norm_act_double_backward(ctx, tensors, grads):
+    """The gradients as differentiable torch expressions of the saved inputs and ``grads``, with the kernel's keep mask."""
+    norm, relu, eps, p, seed, seed_indices = ctx.conf
+    n = ctx.n
+    res = [None] * (4 * n)
+    with torch.enable_grad():
+        for k in range(n):
+            x, r, w, b = tensors[k::n]
+            mask = None
+            if p > 0:
+                ones = torch.ones(x.shape, dtype=torch.float32, device=x.device)
+                s = seed if seed_indices is None or seed_indices[k] < 0 else segment_seed(seed, seed_indices[k])
+                mask = norm_act_forward([(ones, None, None, None)], False, False, eps, p, s)[0][0]
+            ins = [(i, t) for i, t in ((k, x), (n + k, r), (2 * n + k, w), (3 * n + k, b)) if t is not None and t.requires_grad]
+            if not ins or grads[k] is None:
+                continue
+            y = _norm_act_torch(x, w, b, r, norm, eps, p, True, relu, mask=mask)
+            for (i, _), gr in zip(ins, torch.autograd.grad(y, [t for _, t in ins], grads[k], create_graph=True, allow_unused=True)):
+                res[i] = gr
+    return tuple(res)
+
+
+def norm_dropout_act(x, weight=None, bias=None, *, residual=None, norm=True, eps=1e-5, p=0.0, training=False, relu=True, seed=None):
+    """The block between two message-passing layers in one pass over the rows:
+        z = x (+ residual);  y = LayerNorm(z; weight, bias, eps) if norm;  y = y * keep / (1 - p) if training and p > 0;
+        out = relu(y) if relu
+    — ``torch.nn.LayerNorm`` (biased variance), then dropout, then ReLU: the reference's ``norm -> dropout -> relu``
+    (mag_lp_mnmg.py), and with ``norm=False`` its ``relu -> dropout`` (gnn_model.py; the two commute).  ``residual`` is the
+    encoder's ``+ lin1(x)`` term; its gradient is ``x``'s.
+
+    ``x``: a [n, C] tensor, or a dict of them keyed by node type — then ``weight``, ``bias`` and ``residual`` are dicts too (a
+    missing key = None), the result is a dict, and all types run in ONE launch forward and two backward per 8 types; type k (in
+    the dict's order) gets bit for bit what the tensor form gives with ``seed=segment_seed(seed, k)``.
+
+    ``route``: the kernels (``wgamd_norm_act_f32``, include/wgamd_ext.h) run for float32 device tensors with unit column stride,
+    16-B aligned rows, ``norm_dropout_act_supported(C)`` and ``weight`` / ``bias`` of width C; a dict takes them when every type
+    does.  The dropout mask is then a stateless function of ``(seed, row, column)`` — nothing is stored for the backward, and the
+    same inputs give the same bits on every run.  ``seed=None`` draws one on the host from ``torch.initial_seed()`` and torch's
+    default CPU generator (no device sync; the same sequence after every ``torch.manual_seed``) — every such call therefore
+    advances the global CPU random stream by one draw, as a CPU dropout would: a later ``torch.randperm`` or shuffle sees other
+    values than without the call; pass ``seed`` to leave the stream alone.  A dropped element is exactly 0 also where ``y`` is NaN
+    or infinite (torch's dropout gives ``NaN * 0 = NaN`` there); a kept NaN stays NaN through the ReLU, as ``torch.relu``'s.
+    Everything else (CPU tensors, other dtypes and widths, rows less than C floats apart such as an expanded tensor's, a
+    broadcast ``weight``) runs the same formula out of torch ops, and so does a double backward; there dropout is
+    ``torch.nn.functional.dropout``, which draws from torch's own random stream: ``seed`` is not used.
+    ``norm=False`` without a residual and without active dropout is ``torch.relu`` (no launch).  Under HIP-graph capture,
+    training with ``p > 0`` is refused (a captured host seed would replay one mask); every other mode may be captured."""
+    return _norm_dropout_act(x, weight, bias, residual, norm, eps, p, training, relu, seed)[0]
+
+
+def _norm_dropout_act(x, weight, bias, residual, norm, eps, p, training, relu, seed):
+    """``(result, route)`` of ``norm_dropout_act``."""
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("norm_dropout_act: dropout probability has to be between 0 and 1, but got %r" % (p,))
+    is_dict = isinstance(x, dict)
+    if is_dict:
+        keys = list(x)
+        pick = lambda d, t: None if d is None else d.get(t)      # noqa: E731
+        segs = [(x[t], pick(residual, t), pick(weight, t), pick(bias, t)) for t in keys]
+    else:
+        keys, segs = [None], [(x, residual, weight, bias)]
+    segs = [(xs, r, w if norm else None, b if norm else None) for xs, r, w, b in segs]
+    drop = bool(training) and p > 0
+    p_eff = float(p) if drop else 0.0
+
+    def wrap(outs):
+        return dict(zip(keys, outs)) if is_dict else outs[0]
+
+    if not norm and not drop and all(r is None for _, r, _, _ in segs):
+        return wrap([torch.relu(xs) if relu else xs.clone() for xs, _, _, _ in segs]), "torch"      # (always a fresh tensor)
+    if not segs or not all(_norm_act_kernel_ok(xs, w, b, r) for xs, r, w, b in segs):
+        return wrap([_norm_act_torch(xs, w, b, r, norm, eps, p_eff, drop, relu) for xs, r, w, b in segs]), "torch"
+    if drop:
+        _refuse_capture("norm_dropout_act", "host-side dropout seeds (training with p > 0: a replay would repeat one mask)")
+    if seed is None:
+        seed = _norm_act_auto_seed() if drop else 0
+    n = len(segs)
+    seed_indices = list(range(n)) if is_dict else None
+    flat = [s[i] for i in (0, 1, 2, 3) for s in segs]
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in flat):
+        outs = _NormAct.apply((bool(norm), bool(relu), float(eps), p_eff, int(seed) & _M64, seed_indices), n, *flat)
+    else:
+        outs = norm_act_forward([tuple(None if t is None else t.detach() for t in s) for s in segs], norm, relu, eps, p_eff, seed,
+                                seed_indices)[0]
+    return wrap(list(outs)), "kernel"
+
+
+class NormDropoutAct(torch.nn.Module):
+    """``norm_dropout_act`` as a module: ``forward(x, residual=None, seed=None)`` = relu(dropout(LayerNorm(x + residual))) with
+    each stage optional (``norm``, ``p``, ``relu``).  The parameters are ``torch.nn.LayerNorm``'s — ``weight`` and ``bias``
+    [channels], ones and zeros — under the same state-dict keys, so a reference checkpoint's ``norm1.*`` loads;
+    ``elementwise_affine=False`` has neither, ``bias=False`` no bias.  ``self.training`` drives dropout.  ``route``:
+    ``"kernel"`` or ``"torch"``, what the last forward took (see ``norm_dropout_act``)."""
+
+    def __init__(self, channels: int, norm: bool = True, p: float = 0.0, relu: bool = True, eps: float = 1e-5,
+                 elementwise_affine: bool = True, bias: bool = True):
+        super().__init__()
+        if not 0.0 <= p <= 1.0:
+            raise ValueError("NormDropoutAct: dropout probability has to be between 0 and 1, but got %r" % (p,))
+        self.channels, self.norm, self.p, self.relu, self.eps = int(channels), bool(norm), float(p), bool(relu), float(eps)
+        self.elementwise_affine = bool(elementwise_affine)
+        affine = self.norm and self.elementwise_affine
+        self.weight = torch.nn.Parameter(torch.empty(self.channels)) if affine else None
+        self.bias = torch.nn.Parameter(torch.empty(self.channels)) if affine and bias else None
+        self.route = None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        if self.weight is not None:
+            torch.nn.init.ones_(self.weight)
+        if self.bias is not None:
+            torch.nn.init.zeros_(self.bias)
+
+    def forward(self, x, residual=None, seed=None):
+        out, self.route = _norm_dropout_act(x, self.weight, self.bias, residual, self.norm, self.eps, self.p, self.training,
+                                            self.relu, seed)
+        return out
+
+    def extra_repr(self):
+        return "%d, norm=%s, p=%g, relu=%s, eps=%g" % (self.channels, self.norm, self.p, self.relu, self.eps)
+
+
+class HeteroNormDropoutAct(torch.nn.Module):
+    """One ``NormDropoutAct`` per node type (``norms``: a ModuleDict, state-dict keys ``norms.<type>.weight`` / ``.bias``) run
+    as ONE launch over all types of ``x_dict`` — what ``to_hetero`` makes of the reference encoder's ``norm -> dropout -> relu``.
+    ``channels``: ``{node_type: width}``; the other arguments are ``NormDropoutAct``'s.  ``forward(x_dict, residual_dict=None,
+    seed=None)`` returns a dict over the types of ``x_dict`` (types without rows in this call are simply absent from it; a type
+    of ``x_dict`` the module does not know is a KeyError)."""
+
+    def __init__(self, channels, norm: bool = True, p: float = 0.0, relu: bool = True, eps: float = 1e-5,
+                 elementwise_affine: bool = True, bias: bool = True):
+        super().__init__()
+        self.norms = torch.nn.ModuleDict({t: NormDropoutAct(c, norm, p, relu, eps, elementwise_affine, bias) for t, c in channels.items()})
+        self.norm, self.p, self.relu, self.eps = bool(norm), float(p), bool(relu), float(eps)
+        self.route = None
+
+    def reset_parameters(self):
+        for m in self.norms.values():
+            m.reset_parameters()
+
+    def forward(self, x_dict, residual_dict=None, seed=None):
+        mods = {t: self.norms[t] for t in x_dict}
+        out, self.route = _norm_dropout_act(x_dict, {t: m.weight for t, m in mods.items()}, {t: m.bias for t, m in mods.items()},
+                                            residual_dict, self.norm, self.eps, self.p, self.training, self.relu, seed)
+        return out

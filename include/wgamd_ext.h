@@ -1215,6 +1215,65 @@ wholememory_error_code_t wgamd_gatv2_bwd_src_f32(const int* row_ptr_t, const int
                                                  const float* alpha, const float* de, const float* g, int64_t ldg, float* gx,
                                                  int64_t ldgx, int accumulate, void* stream);
 
+/* ---- NormDropoutAct (csrc/wg_norm_act.hip): the row-wise block between two message-passing layers -------------------------------
+ * What the reference's models put after a conv (mag_lp_mnmg.py: norm -> dropout -> relu, with the `+ lin1(x)` residual in the
+ * encoder; gnn_model.py / rgcn / gin: relu -> dropout), over [n_rows, C] float32, for up to WGAMD_NORM_ACT_MAX_SEGMENTS node types
+ * (segments) in ONE launch:
+ *   z   = x (+ residual)                                       residual nullable
+ *   y   = (z - mean) rstd * weight + bias                      WGAMD_NORM_ACT_NORM: torch.nn.LayerNorm (biased variance,
+ *                                                              rstd = 1 / sqrt(var + eps)); weight, bias nullable (1, 0)
+ *   y   = keep ? y / (1 - p) : 0                               p > 0 (p = 1: zeros); a dropped element is exactly 0, also
+ *                                                              where y is NaN or infinite (torch's dropout: NaN * 0 = NaN)
+ *   out = relu(y)                                              WGAMD_NORM_ACT_RELU
+ * stats [n_rows][2] = (mean, rstd) per row is written with WGAMD_NORM_ACT_SAVE_STATS (NORM only) and read by the backward.
+ * keep(r, c) <=> word (c % 4) of Philox4x32-10(key = segment seed, counter = (c / 4, r low, r high, 0)) >= floor(p 2^32): it
+ * depends on (segment seed, row within the segment, c) only — not on strides, flags, the launch's other segments or how rows map
+ * to lanes.  The segment seed is wgamd_norm_act_segment_seed(seed, seed_index), or `seed` itself when seed_index < 0
+ * (seed_index = the segment's position in the caller's list, which keeps counting when the list is split over launches).
+ * wgamd_norm_act_bwd_f32 (same segments, eps, p, seed, flags): from grad_out recomputes z, x^, y, the ReLU sign and the mask —
+ * it reads neither out nor a stored mask — and writes grad_in = dz, the gradient of x AND of residual:
+ *   gy = grad_out * keep / (1 - p) * [y > 0],   dz = rstd (w gy - mean_c(w gy) - x^ mean_c(w gy x^))      (NORM off: dz = gy)
+ * and, with NORM and partials given, partials[b][0][:] = sum gy x^ and partials[b][1][:] = sum gy over the rows of workgroup b
+ * (wgamd_norm_act_bwd_blocks(n_rows, C) rows of 2 C floats).  wgamd_norm_act_wgrad_f32 adds the partial rows in a fixed order:
+ * dweight, dbias [C] (either nullable; zeros for an empty segment; a segment with neither is skipped and needs no partials).  No atomics: the same bits on every run.
+ * Domain: wgamd_norm_act_supported(C) (C % 4 == 0, 4 <= C <= 1024); 1 <= n_segs <= 8, empty segments allowed; every ld >= C and a
+ * multiple of 4, rows / weight / bias / partials 16-B aligned, stats 8-B aligned (WHOLEMEMORY_LOGIC_ERROR otherwise). */
+#define WGAMD_NORM_ACT_MAX_SEGMENTS 8
+#define WGAMD_NORM_ACT_NORM 1
+#define WGAMD_NORM_ACT_RELU 2
+#define WGAMD_NORM_ACT_SAVE_STATS 4
+typedef struct {
+  const float* x;
+  int64_t ldx;
+  const float* residual;
+  int64_t ld_res;
+  float* out;
+  int64_t ldo;
+  const float* weight;
+  const float* bias;
+  float* stats;
+  int64_t n_rows;
+  int C;
+  int seed_index;
+  /* the backward's (null / 0 in the forward) */
+  const float* grad_out;
+  int64_t ldg;
+  float* grad_in;
+  int64_t ld_gi;
+  float* partials;
+  /* the weight-gradient launch's */
+  float* dweight;
+  float* dbias;
+} wgamd_norm_act_segment;
+int wgamd_norm_act_supported(int C);
+uint64_t wgamd_norm_act_segment_seed(uint64_t seed, int k);
+int64_t wgamd_norm_act_bwd_blocks(int64_t n_rows, int C);
+wholememory_error_code_t wgamd_norm_act_f32(const wgamd_norm_act_segment* segs, int n_segs, float eps, float p, uint64_t seed,
+                                            int flags, void* stream);
+wholememory_error_code_t wgamd_norm_act_bwd_f32(const wgamd_norm_act_segment* segs, int n_segs, float eps, float p, uint64_t seed,
+                                                int flags, void* stream);
+wholememory_error_code_t wgamd_norm_act_wgrad_f32(const wgamd_norm_act_segment* segs, int n_segs, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
