@@ -3,7 +3,7 @@
 Public surface (same names as /root/reference/python/pylibwholegraph/pylibwholegraph/torch/__init__.py
 for the files SURVEY.md §8 puts on the path): ``GraphStructure``, ``WholeMemoryTensor``,
 ``create_wholememory_tensor``, ``wholegraph_ops``, ``graph_ops``; plus ``nn`` (SAGEConv / GATConv / GATv2Conv / GCNConv /
-RGCNConv / TransformerConv / GINConv over the sampler CSR, global_add_pool, NormDropoutAct / HeteroNormDropoutAct between them) and ``fused`` (no-host-sync walk), which have no reference counterpart.
+RGCNConv / TransformerConv / GINConv over the sampler CSR, global_add_pool, NormDropoutAct / HeteroNormDropoutAct between them, RowLinear around them) and ``fused`` (no-host-sync walk), which have no reference counterpart.
 
 Everything computes through ``lib/libwholegraph_amd.so`` (HIP, gfx950); a missing library raises
 ``WholeGraphLibraryError`` — there is no CPU fallback.

@@ -52,6 +52,7 @@ class HeteroTransformerRelation(Structure):
 
 
 NORM_ACT_MAX_SEGMENTS, NORM_ACT_NORM, NORM_ACT_RELU, NORM_ACT_SAVE_STATS = 8, 1, 2, 4   # WGAMD_NORM_ACT_* (include/wgamd_ext.h)
+ROW_LINEAR_NORM_NONE, ROW_LINEAR_NORM_LAYER, ROW_LINEAR_NORM_L2 = 0, 1, 2                # WGAMD_ROW_LINEAR_NORM_* (include/wgamd_ext.h)
 
 
 class NormActSegment(Structure):
@@ -419,6 +420,15 @@ SYMBOLS = {
     "wgamd_norm_act_f32": (c_int, [c_void_p, c_int, c_float, c_float, c_ulonglong, c_int, c_void_p]),
     "wgamd_norm_act_bwd_f32": (c_int, [c_void_p, c_int, c_float, c_float, c_ulonglong, c_int, c_void_p]),
     "wgamd_norm_act_wgrad_f32": (c_int, [c_void_p, c_int, c_void_p]),
+    # RowLinear (wg_row_linear.hip)
+    "wgamd_row_linear_supported": (c_int, [c_int, c_int]),
+    "wgamd_row_linear_bwd_blocks": (c_int64, [c_int64, c_int]),
+    "wgamd_row_linear_f32": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p,
+                                     c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                     c_int64, c_void_p, c_int64, c_void_p]),
+    "wgamd_row_linear_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_float,
+                                         c_void_p, c_int64, c_void_p, c_void_p]),
+    "wgamd_row_linear_affine_grad_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "wgamd_bias_act_rows_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "wgamd_gat_transform_heads_supported": (c_int, [c_int, c_int, c_int]),
     "wgamd_gat_transform_weight_bytes": (c_size_t, [c_int, c_int, c_int]),

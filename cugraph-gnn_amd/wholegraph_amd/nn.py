@@ -7,11 +7,13 @@ and into its cugraph-pyg examples.  Six layers run ONE kernel per hop of a call 
 relations are aggregate kernels with a dense tail.  ``GATv2Conv`` is two library GEMMs and ONE attention kernel per hop on
 the transformed rows (its logit is not linear in the neighbour row: no aggregate-first form).  ``NormDropoutAct`` /
 ``HeteroNormDropoutAct`` are what the reference's models put BETWEEN two layers (residual add, LayerNorm, dropout, ReLU): one
-launch forward and two backward for all node types of a layer.
+launch forward and two backward for all node types of a layer.  ``RowLinear`` is the dense product AROUND the layers (input
+projection over the stored features, skip term, normalised tail, plain heads): gathered rows times a weight with a row-wise
+epilogue, one launch.
 
 Order of the file: ctypes helpers and the plumbing the one-kernel layers share; the SAGE-era kernel wrappers, derived-weight
 caches and GAT kernel wrappers; graph forms (``_single_hop``, ``LazyRows``, ``HopGraph``, ``LayerGraph``) and the helpers that
-walk a layer graph; then a section per layer — SAGE and GAT, GCN, RGCN, transformer, GIN, GATv2, heterogeneous, NormDropoutAct —
+walk a layer graph; then a section per layer — SAGE and GAT, GCN, RGCN, transformer, GIN, GATv2, heterogeneous, NormDropoutAct, RowLinear —
 each with its kernel wrappers, its autograd Function(s) and its module.
 
 Shared by the one-kernel layers, so that they cannot drift apart: ``_hop_args`` (the eight leading arguments of a launch over a
@@ -5304,3 +5306,318 @@ class HeteroNormDropoutAct(torch.nn.Module):
         out, self.route = _norm_dropout_act(x_dict, {t: m.weight for t, m in mods.items()}, {t: m.bias for t, m in mods.items()},
                                             residual_dict, self.norm, self.eps, self.p, self.training, self.relu, seed)
         return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# RowLinear: a Linear over gathered rows with a row-wise epilogue (ReLU, LayerNorm or L2 norm, add) — csrc/wg_row_linear.hip
+# ---------------------------------------------------------------------------------------------------------------------
+row_linear_launches = 0      # forward launches of wgamd_row_linear_f32 so far (tests: the kernel route ran, once per call)
+_ROW_LINEAR_NORMS = {None: L.ROW_LINEAR_NORM_NONE, "layer": L.ROW_LINEAR_NORM_LAYER, "l2": L.ROW_LINEAR_NORM_L2}
+_WGRAD_MAX_F = 256           # columns of the kept rows one wgamd_gcn_wgrad_f32 call takes
+
+
+def linear_rows_supported(K: int, N: int) -> bool:
+    """Widths of the RowLinear kernels (``wgamd_row_linear_supported``, answered on the host): K % 4 == 0, 4 <= K <= 1024,
+    N % 4 == 0, 4 <= N <= 256."""
+    return bool(L.lib().wgamd_row_linear_supported(int(K), int(N)))
+
+
+def _row_linear_eps(norm, eps) -> float:
+    return float(eps) if eps is not None else (1e-12 if norm == "l2" else 1e-5)
+
+
+def row_linear_forward(src, ids, weight, bias=None, relu=False, norm=None, gamma=None, beta=None, eps=None, add=None, out=None,
+                       keep_x=False, keep_y=False):
+    """``wgamd_row_linear_f32`` (include/wgamd_ext.h), ONE launch: ``src`` a float32 / float16 / bfloat16 ``[m, K]`` table read by
+    row or through ``ids`` (int32 / int64), ``weight`` [N, K].  Returns ``(out, kept_x, kept_y)``: the float32 input rows and the
+    rows after the ReLU and before the norm, where asked for (else None)."""
+    global row_linear_launches
+    n = int(src.shape[0] if ids is None else ids.shape[0])
+    K, N = int(src.shape[1]), int(weight.shape[0])
+    out = _out_rows(out, n, N, src.device)
+    kept_x = torch.empty((n, K), dtype=torch.float32, device=src.device) if keep_x else None
+    kept_y = torch.empty((n, N), dtype=torch.float32, device=src.device) if keep_y else None
+    L.check(L.lib().wgamd_row_linear_f32(src.data_ptr(), torch_dtype_to_wm(src.dtype), src.stride(0), _ptr(ids),
+                                         0 if ids is None else torch_dtype_to_wm(ids.dtype), n, K, weight.data_ptr(),
+                                         weight.stride(0), N, _ptr(bias), int(bool(relu)), _ROW_LINEAR_NORMS[norm], _ptr(gamma),
+                                         _ptr(beta), _row_linear_eps(norm, eps), _ptr(add), 0 if add is None else add.stride(0),
+                                         out.data_ptr(), out.stride(0), _ptr(kept_x), K, _ptr(kept_y), N, get_stream()),
+            "wgamd_row_linear_f32")
+    if n > 0:
+        row_linear_launches += 1
+    return out, kept_x, kept_y
+
+
+def row_linear_backward(kept_y, grad_out, relu=False, norm=None, gamma=None, eps=None, need_gamma=False, need_beta=False):
+    """``wgamd_row_linear_bwd_f32`` and, for LayerNorm's affine gradients, ``wgamd_row_linear_affine_grad_f32``: ``(dy, dgamma,
+    dbeta)`` — ``grad_out`` through the norm (statistics recomputed from ``kept_y``) and the ReLU mask ``kept_y > 0``; the affine
+    gradients through per-workgroup partial rows added in a fixed order (None where not asked for, or without ``norm="layer"``)."""
+    n, N = grad_out.shape
+    lib, dev = L.lib(), grad_out.device
+    dy = torch.empty((n, N), dtype=torch.float32, device=dev)
+    affine = norm == "layer" and (need_gamma or need_beta)
+    part = torch.empty((int(lib.wgamd_row_linear_bwd_blocks(n, N)), 2 * N), dtype=torch.float32, device=dev) if affine else None
+    L.check(lib.wgamd_row_linear_bwd_f32(_ptr(kept_y), 0 if kept_y is None else kept_y.stride(0), grad_out.data_ptr(),
+                                         grad_out.stride(0), n, N, int(bool(relu)), _ROW_LINEAR_NORMS[norm], _ptr(gamma),
+                                         _row_linear_eps(norm, eps), dy.data_ptr(), dy.stride(0),
+                                         part.data_ptr() if affine and part.numel() else None, get_stream()),
+            "wgamd_row_linear_bwd_f32")
+    dg = torch.empty(N, dtype=torch.float32, device=dev) if affine and need_gamma else None
+    db = torch.empty(N, dtype=torch.float32, device=dev) if affine and need_beta else None
+    if affine:
+        L.check(lib.wgamd_row_linear_affine_grad_f32(part.data_ptr() if part.numel() else None, n, N, _ptr(dg), _ptr(db), get_stream()),
+                "wgamd_row_linear_affine_grad_f32")
+    return dy, dg, db
+
+
+def _row_linear_wgrad(kept_x, dy, want_bias: bool):
+    """``(dW, db)`` = ``(dy^T kept_x, colsum(dy))`` through ``gcn_wgrad`` (deterministic split-K), 256 columns of ``kept_x`` per
+    call."""
+    N, K = dy.shape[1], kept_x.shape[1]
+    gb = torch.empty(N, dtype=torch.float32, device=dy.device) if want_bias else None
+    if K <= _WGRAD_MAX_F:
+        gw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
+        gcn_wgrad(kept_x, dy, gw, gb)
+        return gw, gb
+    parts = []
+    for k0 in range(0, K, _WGRAD_MAX_F):
+        k1 = min(k0 + _WGRAD_MAX_F, K)
+        parts.append(torch.empty((N, k1 - k0), dtype=torch.float32, device=dy.device))
+        gcn_wgrad(kept_x[:, k0:k1], dy, parts[-1], gb if k0 == 0 else None)
+    return torch.cat(parts, dim=1), gb
+
+
+def _linear_rows_torch(xr, weight, bias, relu, norm, gamma, beta, eps, add):
+    """The same formula out of torch ops under ordinary autograd, over the gathered float32 rows ``xr``."""
+    y = torch.nn.functional.linear(xr, weight, bias)
+    if relu:
+        y = y.relu()
+    if norm == "layer":
+        y = torch.nn.functional.layer_norm(y, (y.shape[-1],), gamma, beta, eps)
+    elif norm == "l2":
+        y = torch.nn.functional.normalize(y, p=2.0, dim=-1, eps=eps)
+    return y if add is None else y + add
+
+
+class _RowLinear(torch.autograd.Function):
+    """``linear_rows`` on the kernel route.  ``src`` is the input tensor (``x_grad``: it may want a gradient) or the detached
+    table of a ``LazyRows``; ``ids`` what the kernel reads it through.  Kept for the backward: the float32 input rows (only when
+    they are not ``src`` itself) and the rows before the norm (with a norm, or with ReLU and ``add``; with ReLU alone the output
+    is the mask).  The backward is ``row_linear_backward``, ``gcn_wgrad`` and one library GEMM for dX; a backward under
+    ``create_graph=True`` runs the formula out of torch ops instead."""
+
+    @staticmethod
+    def forward(ctx, conf, src, ids, weight, bias, gamma, beta, add):
+        relu, norm, eps, x_grad = conf
+        d = lambda t: None if t is None else t.detach()      # noqa: E731
+        need = ctx.needs_input_grad
+        direct = ids is None and src.dtype == torch.float32
+        keep_y = norm is not None or (relu and add is not None)
+        res, kept_x, kept_y = row_linear_forward(d(src), ids, d(weight), d(bias), relu, norm, d(gamma), d(beta), eps, d(add),
+                                                 keep_x=(need[3] or need[4]) and not direct, keep_y=keep_y)
+        if relu and not keep_y:
+            kept_y = res
+        ctx.conf, ctx.direct = conf, direct
+        ctx.save_for_backward(src, ids, weight, bias, gamma, beta, add, kept_x, kept_y)
+        ctx.set_materialize_grads(False)
+        return res
+
+    @staticmethod
+    def backward(ctx, g):
+        relu, norm, eps, x_grad = ctx.conf
+        src, ids, weight, bias, gamma, beta, add, kept_x, kept_y = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        if g is None:
+            return (None,) * 8
+        if torch.is_grad_enabled():
+            return _row_linear_double_backward(ctx, g)
+        if not _norm_act_rows_ok(g):              # (an expanded or 16-bit gradient: one copy into rows the kernel reads)
+            g = torch.empty(g.shape, dtype=torch.float32, device=g.device).copy_(g)
+        dy, dg, db = g, None, None
+        if relu or norm is not None:
+            dy, dg, db = row_linear_backward(kept_y, g, relu, norm, None if gamma is None else gamma.detach(), eps,
+                                             need_gamma=need[5], need_beta=need[6])
+        gw = gb = gx = None
+        if need[3] or need[4]:
+            gw, gb = _row_linear_wgrad(src.detach() if ctx.direct else kept_x, dy, need[4])
+        if need[1] and x_grad:
+            gx = dy @ weight.detach()
+            if ids is not None:
+                gx = torch.zeros(src.shape, dtype=torch.float32, device=g.device).index_add_(0, ids.long(), gx)
+        return (None, gx, None, gw if need[3] else None, gb, dg, db, g if need[7] else None)
+
+
+def _row_linear_double_backward(ctx, g):
+    """The gradients as differentiable torch expressions of the saved inputs and ``g``."""
+    relu, norm, eps, x_grad = ctx.conf
+    src, ids, weight, bias, gamma, beta, add, _, _ = ctx.saved_tensors
+    res = [None] * 8
+    with torch.enable_grad():
+        xr = src if ids is None else src[ids.long()]
+        y = _linear_rows_torch(xr.float(), weight, bias, relu, norm, gamma, beta, _row_linear_eps(norm, eps), add)
+        ins = [(i, t) for i, t in ((1, src), (3, weight), (4, bias), (5, gamma), (6, beta), (7, add))
+               if t is not None and t.requires_grad and ctx.needs_input_grad[i]]
+        if ins:
+            for (i, _), gr in zip(ins, torch.autograd.grad(y, [t for _, t in ins], g, create_graph=True, allow_unused=True)):
+                res[i] = gr
+    return tuple(res)
+
+
+def _row_vec_ok(v, N: int) -> bool:
+    return v is None or (torch.is_tensor(v) and v.dtype == torch.float32 and v.is_cuda and v.dim() == 1 and v.numel() == N
+                         and v.is_contiguous() and v.data_ptr() % 16 == 0)
+
+
+def linear_rows(x, weight, bias=None, *, rows=None, relu=False, norm=None, norm_weight=None, norm_bias=None, eps=None, add=None,
+                out=None):
+    """A Linear over gathered rows with a row-wise epilogue, in one pass:
+        y = x[rows] @ weight^T + bias;  y = relu(y) if relu
+        z = layer_norm(y; norm_weight, norm_bias, eps) if norm == "layer";  y / max(||y||_2, eps) if norm == "l2";  y otherwise
+        out = z + add
+    — the dense products around the reference's layers: ``paper_norm(paper_lin(x))`` over the stored features, ``lin1(x)`` on a
+    layer's output rows (``rows``), ``normalize(lin2(x).relu()) + x_paper``, and the plain ``lin(x)`` heads.  ``eps=None`` is 1e-5
+    for ``"layer"`` (``torch.nn.LayerNorm``'s) and 1e-12 for ``"l2"`` (``torch.nn.functional.normalize``'s).
+
+    ``x``: a float32 ``[m, K]`` tensor, or ``LazyRows`` over a float32 / float16 / bfloat16 table — row ``i`` is
+    ``table[ids[i]]`` converted to float32 exactly, so a 16-bit table gives bit for bit the result over ``table.float()``.
+    ``rows`` (int64 or int32, optional): the ``n`` rows of ``x`` to take, repeats allowed; for ``LazyRows`` it is composed with the
+    id list by one index op on the ids (``ids[rows]``) — the rows themselves are never gathered.  ``add``: ``[n, N]``.  ``out``
+    (optional): a float32 ``[n, N]`` tensor or column-sliced view with 16-B aligned rows to write into (the kernel writes it
+    directly; a result that carries a gradient is copied into it once).
+
+    ``route``: the kernel (``wgamd_row_linear_f32``, include/wgamd_ext.h: ONE launch; the ``[n, K]`` float32 copy of a lazy
+    input's rows and the ``[n, N]`` intermediates between the product, the norm and the add never exist) runs when the tensors
+    are on the device, ``linear_rows_supported(K, N)``, ``weight`` / ``add`` / ``out`` and a float32 ``x`` are float32 with unit
+    column stride and 16-B aligned rows (a 16-bit table: 8-B aligned rows), and a ``LazyRows`` table is a ``torch.Tensor``.  In
+    training it keeps the float32 input rows only when they are not ``x`` itself (``rows`` or a ``LazyRows``), and the rows
+    before the norm; the backward is one launch for ``dy`` (two with LayerNorm's affine gradients: per-workgroup partial rows
+    added in a fixed order), ``gcn_wgrad`` for ``dW`` / ``db`` and one library GEMM for ``dX`` — no float atomics in the
+    kernels, so the same call gives the same gradient bits.  ``dX`` with ``rows`` is scattered with ``index_add_`` into zeros:
+    exact and reproducible when ``rows`` are distinct, as a layer's output rows are (repeats add up in an order the library does
+    not fix).  A ``LazyRows`` input never gets a gradient.  ``rows`` are not range-checked on this route.
+    Everything else — CPU tensors, a ``MappedTable``-backed ``LazyRows``, float64, widths outside the domain — runs the same
+    formula out of torch ops under ordinary autograd (a ``LazyRows`` materialises there; ``rows`` out of range is a
+    ValueError), and so does a double backward."""
+    return _linear_rows(x, weight, bias, rows, relu, norm, norm_weight, norm_bias, eps, add, out)[0]
+
+
+def _linear_rows(x, weight, bias, rows, relu, norm, gamma, beta, eps, add, out):
+    """``(result, route)`` of ``linear_rows``."""
+    if norm not in _ROW_LINEAR_NORMS:
+        raise ValueError("linear_rows: norm must be None, 'layer' or 'l2', got %r" % (norm,))
+    lazy = isinstance(x, LazyRows)
+    if not lazy and not torch.is_tensor(x):
+        raise ValueError("linear_rows: x must be a tensor or LazyRows, got %s" % type(x).__name__)
+    if x.dim() != 2 or weight.dim() != 2 or x.shape[1] != weight.shape[1]:
+        raise ValueError("linear_rows: x %s does not match weight %s" % (tuple(x.shape), tuple(weight.shape)))
+    if rows is not None and (rows.dim() != 1 or rows.dtype not in (torch.int32, torch.int64)):
+        raise ValueError("linear_rows: rows must be a 1-d int64 (or int32) tensor")
+    if norm != "layer":
+        gamma = beta = None
+    m, K = int(x.shape[0]), int(x.shape[1])
+    n, N = (m if rows is None else int(rows.shape[0])), int(weight.shape[0])
+    if add is not None and tuple(add.shape) != (n, N):
+        raise ValueError("linear_rows: add has shape %s, the result has (%d, %d)" % (tuple(add.shape), n, N))
+    if out is not None and tuple(out.shape) != (n, N):
+        raise ValueError("linear_rows: out has shape %s, the result has (%d, %d)" % (tuple(out.shape), n, N))
+    eps_v = _row_linear_eps(norm, eps)
+    if lazy:
+        _refuse_lazy_table_grad(x.table)
+    src = x.table if lazy else x
+    kernel = (torch.is_tensor(src) and src.is_cuda and src.dim() == 2 and src.stride(1) == 1 and src.stride(0) % 4 == 0
+              and linear_rows_supported(K, N)
+              and (src.dtype == torch.float32 and src.data_ptr() % 16 == 0 or lazy and src.dtype in _X16 and src.data_ptr() % 8 == 0)
+              and _kernel_rows_ok(weight) and _row_vec_ok(bias, N) and _row_vec_ok(gamma, N) and _row_vec_ok(beta, N)
+              and (rows is None or rows.is_cuda) and (not lazy or x.ids.is_cuda) and (add is None or _norm_act_rows_ok(add))
+              and (out is None or _norm_act_rows_ok(out)))
+    if not kernel:
+        if rows is not None and rows.numel() and (int(rows.min()) < 0 or int(rows.max()) >= m):
+            raise ValueError("linear_rows: rows out of range for an input of %d rows" % m)
+        if lazy and torch.is_tensor(x.table) and not x.table.is_cuda:
+            ids = x.ids if rows is None else x.ids[rows.long()]      # (a host table: only the n rows are gathered, by torch,
+            xr = x.table[ids.long()].float()                         # and converted exactly)
+        else:
+            xr = x.materialize() if lazy else x
+            if rows is not None:
+                xr = xr[rows.long()]
+        res = _linear_rows_torch(xr, weight, bias, relu, norm, gamma, beta, eps_v, add)
+        return (res if out is None else out.copy_(res)), "torch"
+    if lazy:
+        assert x.ids.dtype in (torch.int32, torch.int64) and x.ids.is_contiguous()      # (what LazyRows guarantees and the kernel reads)
+        ids = x.ids if rows is None else x.ids[rows.long()]
+    else:
+        ids = None if rows is None else rows.contiguous()
+    tensors = (src, weight, bias, gamma, beta, add)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        res = _RowLinear.apply((bool(relu), norm, eps_v, not lazy), src.detach() if lazy else src, ids, weight, bias, gamma, beta,
+                               add)
+        if out is not None:       # (a result that carries a gradient is written once more, into the caller's rows)
+            res = out.copy_(res)
+    else:
+        d = lambda t: None if t is None else t.detach()      # noqa: E731
+        res = row_linear_forward(d(src), ids, d(weight), d(bias), relu, norm, d(gamma), d(beta), eps_v, d(add), out)[0]
+    return res, "kernel"
+
+
+class RowLinear(torch.nn.Module):
+    """``linear_rows`` as a module: ``forward(x, rows=None, add=None)`` = ``norm(act(lin(x[rows]))) + add``.  The submodules are
+    ``lin`` (``torch.nn.Linear``) and, for ``norm="layer"``, ``norm`` (``torch.nn.LayerNorm``) — their parameters, their
+    initialisation and their state-dict keys (``lin.weight``, ``lin.bias``, ``norm.weight``, ``norm.bias``).  ``norm="l2"`` is
+    ``torch.nn.functional.normalize`` and has no parameters; ``elementwise_affine`` (None: LayerNorm's default, True) given with it
+    is a ValueError.  ``RowLinear.wrap(lin, norm=None, relu=False, l2=False)`` adopts
+    existing modules (parameters shared, not copied): a model's ``paper_lin`` / ``paper_norm`` pair or its ``lin2`` run through
+    the kernel without touching a checkpoint.  ``route``: ``"kernel"`` or ``"torch"``, what the last forward took (see
+    ``linear_rows``)."""
+
+    def __init__(self, in_channels: int, out_channels: int, bias: bool = True, relu: bool = False, norm: Optional[str] = None,
+                 eps: Optional[float] = None, elementwise_affine: Optional[bool] = None):
+        super().__init__()
+        self._configure(relu, norm, eps, elementwise_affine)
+        self.lin = torch.nn.Linear(int(in_channels), int(out_channels), bias=bool(bias))
+        if norm == "layer":
+            self.norm = torch.nn.LayerNorm(int(out_channels), eps=self.eps,
+                                           elementwise_affine=True if elementwise_affine is None else bool(elementwise_affine))
+
+    def _configure(self, relu, norm, eps, elementwise_affine=None):
+        if norm not in _ROW_LINEAR_NORMS:
+            raise ValueError("RowLinear: norm must be None, 'layer' or 'l2', got %r" % (norm,))
+        if norm != "layer" and elementwise_affine is not None:
+            raise ValueError("RowLinear: elementwise_affine belongs to norm='layer' (norm=%r has no parameters)" % (norm,))
+        self.relu, self.norm_kind, self.eps, self.route = bool(relu), norm, _row_linear_eps(norm, eps), None
+
+    @classmethod
+    def wrap(cls, lin: torch.nn.Linear, norm: Optional[torch.nn.LayerNorm] = None, relu: bool = False, l2: bool = False):
+        """A ``RowLinear`` over the existing ``lin`` (and ``norm``) modules themselves."""
+        if not isinstance(lin, torch.nn.Linear) or not (norm is None or isinstance(norm, torch.nn.LayerNorm)):
+            raise ValueError("RowLinear.wrap: lin must be a torch.nn.Linear and norm a torch.nn.LayerNorm (or None)")
+        if norm is not None and (l2 or tuple(norm.normalized_shape) != (lin.out_features,)):
+            raise ValueError("RowLinear.wrap: a LayerNorm over lin's %d output channels, or l2=True, not both" % lin.out_features)
+        m = cls.__new__(cls)
+        torch.nn.Module.__init__(m)
+        m._configure(relu, "layer" if norm is not None else "l2" if l2 else None, norm.eps if norm is not None else None)
+        m.lin = lin
+        if norm is not None:
+            m.norm = norm
+        return m
+
+    @property
+    def in_channels(self):
+        return self.lin.in_features
+
+    @property
+    def out_channels(self):
+        return self.lin.out_features
+
+    def reset_parameters(self):
+        self.lin.reset_parameters()
+        if self.norm_kind == "layer":
+            self.norm.reset_parameters()
+
+    def forward(self, x, rows=None, add=None):
+        ln = self.norm if self.norm_kind == "layer" else None
+        out, self.route = _linear_rows(x, self.lin.weight, self.lin.bias, rows, self.relu, self.norm_kind,
+                                       None if ln is None else ln.weight, None if ln is None else ln.bias, self.eps, add, None)
+        return out
+
+    def extra_repr(self):
+        return "relu=%s, norm=%r, eps=%g" % (self.relu, self.norm_kind, self.eps)

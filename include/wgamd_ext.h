@@ -1274,6 +1274,45 @@ wholememory_error_code_t wgamd_norm_act_bwd_f32(const wgamd_norm_act_segment* se
                                                 int flags, void* stream);
 wholememory_error_code_t wgamd_norm_act_wgrad_f32(const wgamd_norm_act_segment* segs, int n_segs, void* stream);
 
+/* ---- RowLinear (csrc/wg_row_linear.hip): a Linear over gathered rows with a row-wise epilogue, ONE launch ------------------------
+ * The dense products around the reference's layers (mag_lp_mnmg.py: paper_norm(paper_lin(x)), lin1(x) on the output rows,
+ * normalize(lin2(x).relu()) + x_paper; taobao / movielens: lin(x)), over n_rows rows:
+ *   y   = X[i] @ weight^T + bias                               X[i] = x[ids[i]] (ids nullable: x[i]); weight [N, ldw], bias nullable
+ *   y   = relu(y)                                              relu != 0
+ *   z   = (y - mean) rstd * gamma + beta                       WGAMD_ROW_LINEAR_NORM_LAYER: biased variance, two-pass,
+ *                                                              rstd = 1 / sqrt(var + eps); gamma, beta nullable (1, 0)
+ *       = y / max(||y||_2, eps)                                WGAMD_ROW_LINEAR_NORM_L2
+ *   out = z + add                                              add nullable, [n_rows, ld_add]
+ * x is a table of x_dtype FLOAT, HALF or BF16 with rows ldx ELEMENTS apart; 16-bit values are converted to float32 exactly, so the
+ * result is bit for bit that of the float32 table.  ids are INT or INT64 (ids_dtype; ignored when ids is null) and are not
+ * range-checked.  kept_x (nullable, [n_rows, ld_kx]) receives the float32 input rows, kept_y (nullable, [n_rows, ld_ky]) the rows
+ * after the ReLU and before the norm: what the backward reads.  Rows at or past n_rows are neither read from add nor written.
+ * wgamd_row_linear_bwd_f32: dy [n_rows, ld_dy] = grad_out through the norm (statistics recomputed from kept_y), zero where relu
+ * and kept_y <= 0; for the L2 norm with ||y|| < eps, dy = grad_out / eps.  kept_y may be null without relu and norm.  With
+ * NORM_LAYER and partials given (wgamd_row_linear_bwd_blocks(n_rows, N) rows of 2 N floats) workgroup b writes partials[b][0][:]
+ * = sum grad_out x^ and partials[b][1][:] = sum grad_out over its rows; wgamd_row_linear_affine_grad_f32 adds the partial rows in
+ * a fixed order into dgamma, dbeta [N] (either nullable; zeros for n_rows = 0).  No atomics: the same bits on every run.
+ * Domain: wgamd_row_linear_supported(K, N) (K % 4 == 0, 4 <= K <= 1024, N % 4 == 0, 4 <= N <= 256); every leading dimension a
+ * multiple of 4 and at least the width; float32 rows, gamma, beta and partials 16-B aligned, 16-bit table rows 8-B aligned
+ * (WHOLEMEMORY_LOGIC_ERROR otherwise; null pointers, small leading dimensions, other dtypes: WHOLEMEMORY_INVALID_INPUT).  All
+ * checks come before any device call; n_rows = 0 is success without a launch. */
+#define WGAMD_ROW_LINEAR_NORM_NONE 0
+#define WGAMD_ROW_LINEAR_NORM_LAYER 1
+#define WGAMD_ROW_LINEAR_NORM_L2 2
+int wgamd_row_linear_supported(int K, int N);
+int64_t wgamd_row_linear_bwd_blocks(int64_t n_rows, int N);
+wholememory_error_code_t wgamd_row_linear_f32(const void* x, wholememory_dtype_t x_dtype, int64_t ldx, const void* ids,
+                                              wholememory_dtype_t ids_dtype, int64_t n_rows, int K, const float* weight,
+                                              int64_t ldw, int N, const float* bias, int relu, int norm, const float* gamma,
+                                              const float* beta, float eps, const float* add, int64_t ld_add, float* out,
+                                              int64_t ldo, float* kept_x, int64_t ld_kx, float* kept_y, int64_t ld_ky,
+                                              void* stream);
+wholememory_error_code_t wgamd_row_linear_bwd_f32(const float* kept_y, int64_t ld_ky, const float* grad_out, int64_t ldg,
+                                                  int64_t n_rows, int N, int relu, int norm, const float* gamma, float eps,
+                                                  float* dy, int64_t ld_dy, float* partials, void* stream);
+wholememory_error_code_t wgamd_row_linear_affine_grad_f32(const float* partials, int64_t n_rows, int N, float* dgamma,
+                                                          float* dbeta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
