@@ -11,7 +11,10 @@
 //     agg_out).  Phase 2: tile A times W1^T (tile_times_wt, wg_layer_parts.hpp) with b1 and ReLU -> LDS tile B, the hidden
 //     activation (and hidden_out).  Phase 3: tile B times W2^T with b2 and the output ReLU -> global memory.  With a null W2
 //     phase 2 writes to global memory and the kernel ends: the one-product form, also what runs the input gradient over the
-//     hop's transpose (W1^T as the weight).
+//     hop's transpose (W1^T as the weight).  STATS (a compile-time variant of the one-product form, the training forward of the
+//     batch-norm route, wg_batch_norm.hip): phase 2 writes z = agg W1^T + b1 to LDS tile B, stores the rows to z_out, and one
+//     thread per column writes the tile's (mean, M2) over its valid rows to partials[tile0 + tile][2][H], the row count to
+//     counts[tile0 + tile].
 //   * gin_aggregate_kernel — agg alone for any F (shapes outside the layer kernel's domain, or an nn that does not start with
 //     a Linear).
 //   * segment_sum_kernel — global_add_pool over a sorted batch vector given as segment offsets: one wave per (segment,
@@ -53,6 +56,9 @@ struct gin_args {
   int64_t ld_hidden;
   int F16, SD;                // tile A: F rounded up to 16, floats per row
   int H16, SH;                // tile B
+  float* partials;            // STATS: [tiles of the layer][2][H], this launch's tiles from tile0 on
+  int* counts;                // STATS: [tiles of the layer]
+  int64_t tile0;
 };
 
 // the self row of destination i as float4 chunks, or null
@@ -89,7 +95,7 @@ __device__ __forceinline__ f32x4 aggregate_chunk(const gin_args& a, int64_t i, i
   return acc;
 }
 
-template <int KIND, int LG>
+template <int KIND, int LG, bool STATS>
 __global__ void __launch_bounds__(kThreads) gin_layer_kernel(gin_args a)
 {
   extern __shared__ __attribute__((aligned(16))) float tile[];
@@ -114,6 +120,22 @@ __global__ void __launch_bounds__(kThreads) gin_layer_kernel(gin_args a)
   __syncthreads();
 
   // ---- phase 2: [16 x F16] tile A @ W1^T ----
+  if constexpr (STATS) {
+    float* zt = tile + kTileRows * a.SD;    // tile B: z of all 16 rows (rows past n_rows hold b1: neither stored nor counted)
+    tile_times_wt(tile, a.SD, a.F, a.F16, a.w1, a.ldw1, a.H, a.b1, 0, zt, a.SH, 0, kTileRows);
+    __syncthreads();
+    const int rows_here = (int)std::min<int64_t>(kTileRows, a.n_rows - row0);
+    keep_tile_rows(zt, a.SH, a.H, rows_here, a.out, a.ldo, row0);
+    const int64_t t = a.tile0 + blockIdx.x;
+    if (tid < a.H) {
+      float mean, m2;
+      column_mean_m2(zt + tid, a.SH, rows_here, mean, m2);
+      a.partials[t * 2 * a.H + tid] = mean;
+      a.partials[(t * 2 + 1) * a.H + tid] = m2;
+    }
+    if (tid == 0) a.counts[t] = rows_here;
+    return;
+  }
   if (a.w2 == nullptr) {
     tile_times_wt(tile, a.SD, a.F, a.F16, a.w1, a.ldw1, a.H, a.b1, a.relu1, a.out, a.ldo, row0, a.n_rows);
     return;
@@ -175,24 +197,24 @@ __global__ void __launch_bounds__(256) segment_sum_kernel(const float* __restric
   out[g * ldo + f] = acc;
 }
 
-template <int KIND, int LG>
+template <int KIND, int LG, bool STATS>
 void launch_one(const gin_args& a, hipStream_t st)
 {
-  auto kern = gin_layer_kernel<KIND, LG>;
+  auto kern = gin_layer_kernel<KIND, LG, STATS>;
   const dim3 grid((unsigned)((a.n_rows + kTileRows - 1) / kTileRows));
-  const size_t lds = (size_t)kTileRows * (a.SD + (a.w2 ? a.SH : 0)) * 4;      // at most 2 x 16 x 260 floats = 33 KB
+  const size_t lds = (size_t)kTileRows * (a.SD + (a.w2 || STATS ? a.SH : 0)) * 4;      // at most 2 x 16 x 260 floats = 33 KB
   kern<<<grid, kThreads, lds, st>>>(a);
 }
 
-template <int KIND>
+template <int KIND, bool STATS = false>
 void launch_layer(const gin_args& a, hipStream_t st)
 {
   const int c4 = a.F / 4;
-  if (c4 <= 4) launch_one<KIND, 4>(a, st);
-  else if (c4 <= 8) launch_one<KIND, 8>(a, st);
-  else if (c4 <= 16) launch_one<KIND, 16>(a, st);
-  else if (c4 <= 32) launch_one<KIND, 32>(a, st);
-  else launch_one<KIND, 64>(a, st);
+  if (c4 <= 4) launch_one<KIND, 4, STATS>(a, st);
+  else if (c4 <= 8) launch_one<KIND, 8, STATS>(a, st);
+  else if (c4 <= 16) launch_one<KIND, 16, STATS>(a, st);
+  else if (c4 <= 32) launch_one<KIND, 32, STATS>(a, st);
+  else launch_one<KIND, 64, STATS>(a, st);
 }
 
 gin_args make_args(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx, int F, const void* src_ids,
@@ -262,6 +284,39 @@ extern "C" wholememory_error_code_t wgamd_gin_layer_f32(const int* row_ptr, cons
 {
   return wgamd_gin_layer_f32_train(row_ptr, col, n_rows, x, ldx, F, src_ids, src_ids_dtype, self_rows, x_dst, ldx_dst, eps, w1,
                                    ldw1, H, b1, w2, ldw2, N, b2, flags, out, ldo, nullptr, 0, nullptr, 0, stream);
+}
+
+extern "C" wholememory_error_code_t wgamd_gin_layer_f32_stats(const int* row_ptr, const int* col, int64_t n_rows, const float* x,
+                                                              int64_t ldx, int F, const void* src_ids,
+                                                              wholememory_dtype_t src_ids_dtype, const int64_t* self_rows,
+                                                              const float* x_dst, int64_t ldx_dst, const float* eps,
+                                                              const float* w1, int64_t ldw1, int H, const float* b1, float* z_out,
+                                                              int64_t ldz, float* agg_out, int64_t ld_agg, float* partials,
+                                                              int* counts, int64_t tile0, void* stream)
+{
+  using namespace wgamd;
+  return guarded("wgamd_gin_layer_f32_stats", [&] {
+    WG_REQUIRE_INPUT(n_rows >= 0 && tile0 >= 0, "bad sizes");
+    if (!wgamd_gin_layer_supported(F, H, 0) || H % 4 != 0)
+      throw logic_error(fmt("unsupported shape: F=%d (multiple of 4, <= 256), H=%d (multiple of 4, <= 256)", F, H));
+    if (n_rows == 0) return;
+    WG_REQUIRE_INPUT(row_ptr && col && x && w1 && z_out && partials && counts, "null pointer");
+    WG_REQUIRE_INPUT(ldw1 >= F && ldz >= H && (agg_out == nullptr || ld_agg >= F) && (x_dst == nullptr || ldx_dst >= F),
+                     "leading dimension too small");
+    const int kind = ids_kind(src_ids, src_ids_dtype);
+    WG_REQUIRE_INPUT(kind == 3 || ldx >= F, "leading dimension too small");
+    if (!aligned_rows(x, kind == 3 ? 0 : ldx) || !aligned_rows(w1, ldw1) || !aligned_rows(z_out, ldz) ||
+        (x_dst && !aligned_rows(x_dst, ldx_dst)) || (agg_out && !aligned_rows(agg_out, ld_agg)))
+      throw logic_error("x / x_dst / w1 / z_out / agg_out rows must be 16-B aligned");
+    gin_args a = make_args(row_ptr, col, n_rows, x, ldx, F, src_ids, self_rows, x_dst, ldx_dst, eps);
+    a.w1 = w1, a.ldw1 = ldw1, a.H = H, a.b1 = b1;
+    a.out = z_out, a.ldo = ldz, a.agg_out = agg_out, a.ld_agg = ld_agg;
+    a.partials = partials, a.counts = counts, a.tile0 = tile0;
+    a.F16 = (F + 15) / 16 * 16, a.SD = a.F16 + 4;
+    a.H16 = (H + 15) / 16 * 16, a.SH = a.H16 + 4;
+    with_kind(kind, [&](auto k) { launch_layer<decltype(k)::value, true>(a, static_cast<hipStream_t>(stream)); });
+    WG_HIP_CHECK(hipGetLastError());
+  });
 }
 
 extern "C" wholememory_error_code_t wgamd_gin_aggregate_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* x,

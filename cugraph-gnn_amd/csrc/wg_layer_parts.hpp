@@ -80,6 +80,20 @@ __device__ __forceinline__ void keep_tile_rows(const float* tile, int SD, int K,
     reinterpret_cast<f32x4*>(kept + (row0 + p / K4) * ld)[p % K4] = reinterpret_cast<const f32x4*>(tile + (p / K4) * SD)[p % K4];
 }
 
+// (mean, M2 = sum of squared distances from that mean) of `rows` values `stride` floats apart, two passes (never E[v^2] -
+// mean^2): one column of a row tile, in LDS or in global memory — a batch-norm partial (wg_gin.hip, wg_batch_norm.hip)
+__device__ __forceinline__ void column_mean_m2(const float* p, int64_t stride, int rows, float& mean, float& m2)
+{
+  float s = 0.f;
+  for (int r = 0; r < rows; ++r) s += p[r * stride];
+  mean = rows > 0 ? s / (float)rows : 0.f;
+  m2 = 0.f;
+  for (int r = 0; r < rows; ++r) {
+    const float d = p[r * stride] - mean;
+    m2 = __builtin_fmaf(d, d, m2);
+  }
+}
+
 // ---- the frame of a heterogeneous layer launch (wg_sage_hetero.hip, wg_transformer_hetero.hip): n_rel relations' blocks side by
 // side in the tile, then the root block; one stacked weight; the running sum of an earlier launch and the row placement ----
 

@@ -403,6 +403,21 @@ SYMBOLS = {
     "wgamd_gin_aggregate_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                         c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "wgamd_segment_sum_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    # batch norm between the Linears of a GIN layer (wg_batch_norm.hip; the layer kernel's STATS variant: wg_gin.hip)
+    "wgamd_batch_norm_supported": (c_int, [c_int]),
+    "wgamd_bn_bwd_blocks": (c_int64, [c_int64, c_int]),
+    "wgamd_gin_layer_f32_stats": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                          c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                          c_void_p, c_void_p, c_int64, c_void_p]),
+    "wgamd_bn_partials_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "wgamd_bn_finalize_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wgamd_bn_act_linear_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                                        c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "wgamd_bn_bwd_reduce_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p]),
+    "wgamd_bn_bwd_apply_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     # GATv2 attention (wg_gatv2.hip)
     "wgamd_gatv2_supported": (c_int, [c_int, c_int]),
     "wgamd_gatv2_bwd_blocks": (c_int64, [c_int64]),

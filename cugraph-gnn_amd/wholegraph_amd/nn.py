@@ -3269,6 +3269,301 @@ def _gin_aggregate_torch(x, x_dst, eps, lg: LayerGraph, no_root: bool):
     return aggs[0] if len(aggs) == 1 else torch.cat(aggs)
 
 
+class _MLPBatchNorm(torch.nn.Module):
+    """PyG's ``BatchNorm`` wrapper as ``MLP`` holds it: the ``torch.nn.BatchNorm1d`` lives under ``module``."""
+
+    def __init__(self, channels: int, eps: float = 1e-5, momentum=0.1):
+        super().__init__()
+        self.module = torch.nn.BatchNorm1d(channels, eps=eps, momentum=momentum)
+
+    def reset_parameters(self):
+        self.module.reset_parameters()
+
+    def forward(self, x):
+        return self.module(x)
+
+
+class MLP(torch.nn.Module):
+    """PyG ``MLP(channel_list)`` by name and state dict: ``torch.nn.Linear`` layers under ``lins`` and, with
+    ``norm="batch_norm"``, ``torch.nn.BatchNorm1d`` under ``norms[i].module`` (keys ``lins.{i}.weight/bias``,
+    ``norms.{i}.module.weight/bias/running_mean/running_var/num_batches_tracked``), so a PyG state dict of ``MLP([...])`` loads
+    with ``strict=True``.  ``forward`` is PyG's order in torch ops — per layer ``lin -> [act if act_first] -> norm -> [act] ->
+    dropout``, the last layer plain with ``plain_last`` — on any device.  ``norm``: ``"batch_norm"`` or None (``norm_kwargs``:
+    ``eps``, ``momentum``); ``act``: ``"relu"`` or None.  Inside ``GINConv`` a three-channel ``MLP`` runs on the layer kernels
+    (routes ``"mlp_bn"`` and ``"mlp"``)."""
+
+    def __init__(self, channel_list, dropout: float = 0.0, act="relu", act_first: bool = False, norm="batch_norm",
+                 norm_kwargs=None, plain_last: bool = True, bias: bool = True):
+        super().__init__()
+        if not isinstance(channel_list, (tuple, list)) or len(channel_list) < 2 or not all(
+                isinstance(c, int) and c > 0 for c in channel_list):
+            raise ValueError("MLP: channel_list must hold at least two positive ints, got %r" % (channel_list,))
+        if norm not in ("batch_norm", None):
+            raise ValueError("MLP: norm=%r is not supported ('batch_norm' or None)" % (norm,))
+        if act not in ("relu", None):
+            raise ValueError("MLP: act=%r is not supported ('relu' or None)" % (act,))
+        norm_kwargs = dict(norm_kwargs or {})
+        unknown = sorted(set(norm_kwargs) - {"eps", "momentum"})
+        if unknown:
+            raise ValueError("MLP: norm_kwargs %s not supported ('eps', 'momentum')" % unknown)
+        if not isinstance(dropout, (int, float)) or isinstance(dropout, bool) or not 0.0 <= dropout <= 1.0:
+            raise ValueError("MLP: dropout must be a number in [0, 1], got %r" % (dropout,))
+        if not isinstance(bias, bool):
+            raise ValueError("MLP: bias must be a bool, got %r" % (bias,))
+        self.channel_list = [int(c) for c in channel_list]
+        self.act, self.act_first, self.plain_last, self.norm = act, bool(act_first), bool(plain_last), norm
+        n_lins = len(self.channel_list) - 1
+        self.dropout = [float(dropout)] * n_lins
+        if self.plain_last:
+            self.dropout[-1] = 0.0
+        self.lins = torch.nn.ModuleList(torch.nn.Linear(a, b, bias=bias) for a, b in zip(self.channel_list[:-1], self.channel_list[1:]))
+        widths = self.channel_list[1:-1] if self.plain_last else self.channel_list[1:]
+        self.norms = torch.nn.ModuleList(_MLPBatchNorm(c, **norm_kwargs) if norm == "batch_norm" else torch.nn.Identity()
+                                         for c in widths)
+
+    @property
+    def in_channels(self) -> int:
+        return self.channel_list[0]
+
+    @property
+    def out_channels(self) -> int:
+        return self.channel_list[-1]
+
+    @property
+    def num_layers(self) -> int:
+        return len(self.channel_list) - 1
+
+    def reset_parameters(self):
+        for m in list(self.lins) + list(self.norms):
+            if hasattr(m, "reset_parameters"):
+                m.reset_parameters()
+
+    def flat_modules(self):
+        """The equivalent flat list of torch modules, in ``forward``'s order (the Linears and BatchNorm1ds are this module's own;
+        ReLU and Dropout are fresh, Dropout in this module's training mode): what ``GINConv`` applies its rules to."""
+        mods = []
+        for i, (lin, norm) in enumerate(zip(self.lins, self.norms)):
+            mods.append(lin)
+            if self.act is not None and self.act_first:
+                mods.append(torch.nn.ReLU())
+            if self.norm is not None:
+                mods.append(norm.module)
+            if self.act is not None and not self.act_first:
+                mods.append(torch.nn.ReLU())
+            if self.dropout[i] > 0.0:
+                mods.append(torch.nn.Dropout(self.dropout[i]).train(self.training))
+        if self.plain_last:
+            mods.append(self.lins[-1])
+        return mods
+
+    def forward(self, x):
+        for i, (lin, norm) in enumerate(zip(self.lins, self.norms)):
+            x = lin(x)
+            if self.act is not None and self.act_first:
+                x = torch.relu(x)
+            x = norm(x)
+            if self.act is not None and not self.act_first:
+                x = torch.relu(x)
+            x = torch.nn.functional.dropout(x, p=self.dropout[i], training=self.training)
+        if self.plain_last:
+            x = self.lins[-1](x)
+        return x
+
+    def extra_repr(self) -> str:
+        return str(self.channel_list)[1:-1]
+
+
+def batch_norm_supported(H: int) -> bool:
+    """Widths of the batch-norm kernels (``wgamd_batch_norm_supported``): H % 4 == 0, 4 <= H <= 256."""
+    return bool(L.lib().wgamd_batch_norm_supported(int(H)))
+
+
+def _tiles(n_rows: int) -> int:
+    return (int(n_rows) + 15) // 16
+
+
+def gin_layer_stats(row_ptr, col, x, self_rows, w1, b1, z_out, partials, counts, tile0: int, eps=None, src_ids=None, x_dst=None,
+                    agg_out=None):
+    """Launch A of the batch-norm route over one hop (``wgamd_gin_layer_f32_stats``): ``z = agg @ w1^T + b1`` into ``z_out``
+    (``agg`` into ``agg_out`` when given) and the hop's per-tile ``(mean, M2)`` records into ``partials[tile0:]`` /
+    ``counts[tile0:]`` (``partials`` float32 [T, 2, H], ``counts`` int32 [T])."""
+    hop = _hop_args(row_ptr, col, x, src_ids) + _gin_hop_args(row_ptr, x, self_rows, x_dst, eps)
+    n_rows, F_, H = row_ptr.shape[0] - 1, x.shape[1], w1.shape[0]
+    assert w1.dtype == torch.float32 and w1.stride(1) == 1 and w1.shape[1] == F_
+    assert z_out.shape == (n_rows, H) and z_out.stride(1) == 1 and (agg_out is None or (agg_out.shape == (n_rows, F_) and agg_out.stride(1) == 1))
+    assert partials.dtype == torch.float32 and partials.is_contiguous() and partials.shape[1:] == (2, H)
+    assert counts.dtype == torch.int32 and counts.is_contiguous() and counts.shape[0] == partials.shape[0] >= tile0 + _tiles(n_rows)
+    L.check(L.lib().wgamd_gin_layer_f32_stats(*hop, w1.data_ptr(), w1.stride(0), H, _ptr(b1), z_out.data_ptr(), z_out.stride(0),
+                                              _ptr(agg_out), 0 if agg_out is None else agg_out.stride(0), partials.data_ptr(),
+                                              counts.data_ptr(), int(tile0), get_stream()), "wgamd_gin_layer_f32_stats")
+    return z_out
+
+
+def bn_finalize(partials, counts, gamma=None, beta=None, eps: float = 1e-5, momentum: float = 0.1, running_mean=None,
+                running_var=None):
+    """Launch B (``wgamd_bn_finalize_f32``): the per-tile records combined in a fixed order -> ``(mean, var, rstd, scale, shift)``
+    (biased ``var``; ``scale = gamma rstd``, ``shift = beta - mean scale``), ``running_mean`` / ``running_var`` updated in place
+    with ``momentum`` and the unbiased variance."""
+    T, _, H = partials.shape
+    stats = torch.empty((5, H), dtype=torch.float32, device=partials.device)
+    for t in (gamma, beta, running_mean, running_var):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.shape == (H,))
+    L.check(L.lib().wgamd_bn_finalize_f32(partials.data_ptr(), counts.data_ptr(), T, H, _ptr(gamma), _ptr(beta), float(eps),
+                                          float(momentum), _ptr(running_mean), _ptr(running_var), *(stats[k].data_ptr() for k in range(5)),
+                                          get_stream()), "wgamd_bn_finalize_f32")
+    return tuple(stats[k] for k in range(5))
+
+
+def bn_act_linear(z, scale, shift, w2, b2=None, relu_out=False, keep=False):
+    """Launch C (``wgamd_bn_act_linear_f32``): ``act(relu(z scale + shift) @ w2^T + b2)`` over all rows -> ``(out, hidden)``
+    (``hidden`` None unless ``keep``)."""
+    n, H = z.shape
+    N = w2.shape[0]
+    assert w2.dtype == torch.float32 and w2.stride(1) == 1 and w2.shape[1] == H and z.stride(1) == 1
+    out = torch.empty((n, N), dtype=torch.float32, device=z.device)
+    hidden = torch.empty((n, H), dtype=torch.float32, device=z.device) if keep else None
+    L.check(L.lib().wgamd_bn_act_linear_f32(z.data_ptr(), z.stride(0), n, H, scale.data_ptr(), shift.data_ptr(), w2.data_ptr(),
+                                            w2.stride(0), N, _ptr(b2), int(bool(relu_out)), out.data_ptr(), out.stride(0),
+                                            _ptr(hidden), 0 if hidden is None else hidden.stride(0), get_stream()),
+            "wgamd_bn_act_linear_f32")
+    return out, hidden
+
+
+def bn_column_stats(z):
+    """``(mean, biased variance)`` of the columns of ``z`` [n, H] (float32 on the device, ``batch_norm_supported(H)``): the
+    per-tile records of ``wgamd_bn_partials_f32`` combined by ``wgamd_bn_finalize_f32`` — the statistics of the batch-norm
+    route on their own."""
+    assert z.dim() == 2 and z.dtype == torch.float32 and z.is_cuda and z.stride(1) == 1
+    n, H = z.shape
+    T = _tiles(n)
+    partials = torch.empty((T, 2, H), dtype=torch.float32, device=z.device)
+    counts = torch.empty(T, dtype=torch.int32, device=z.device)
+    L.check(L.lib().wgamd_bn_partials_f32(z.data_ptr(), z.stride(0), n, H, partials.data_ptr(), counts.data_ptr(), 0, get_stream()),
+            "wgamd_bn_partials_f32")
+    mean, var = bn_finalize(partials, counts)[:2]
+    return mean, var
+
+
+def bn_relu_backward(dhidden, hidden, z, mean, rstd, gamma):
+    """``(dz, dgamma, dbeta)`` of ``hidden = relu((z - mean) rstd gamma + beta)`` over all rows (``wgamd_bn_bwd_reduce_f32`` then
+    ``wgamd_bn_bwd_apply_f32``; no atomics); ``dz`` overwrites ``dhidden``."""
+    n, H = z.shape
+    assert dhidden.shape == (n, H) and dhidden.is_contiguous() and dhidden.dtype == torch.float32
+    dev = z.device
+    lib = L.lib()
+    part = torch.empty((max(int(lib.wgamd_bn_bwd_blocks(n, H)), 1), 2, H), dtype=torch.float32, device=dev)
+    dgb = torch.empty((2, H), dtype=torch.float32, device=dev)
+    head = (dhidden.data_ptr(), dhidden.stride(0), hidden.data_ptr(), hidden.stride(0), z.data_ptr(), z.stride(0), n, H,
+            mean.data_ptr(), rstd.data_ptr())
+    L.check(lib.wgamd_bn_bwd_reduce_f32(*head, part.data_ptr(), dgb[0].data_ptr(), dgb[1].data_ptr(), get_stream()),
+            "wgamd_bn_bwd_reduce_f32")
+    L.check(lib.wgamd_bn_bwd_apply_f32(*head, _ptr(gamma), dgb[0].data_ptr(), dgb[1].data_ptr(), dhidden.data_ptr(),
+                                       dhidden.stride(0), get_stream()), "wgamd_bn_bwd_apply_f32")
+    return dhidden, dgb[0], dgb[1]
+
+
+def gin_bn_forward(hops, x, w1, b1, gamma, beta, w2, b2=None, bn_eps: float = 1e-5, momentum: float = 0.1, running_mean=None,
+                   running_var=None, eps=None, relu_out=False, src_ids=None, keep=False):
+    """The training forward of ``GINConv(MLP([F, H, N]))`` over ``hops`` — a list of ``(row_ptr, col, self_rows, x_dst)``, rows back
+    to back: ``wgamd_gin_layer_f32_stats`` per hop, ONE ``wgamd_bn_finalize_f32`` (it updates the running statistics in place),
+    ONE ``wgamd_bn_act_linear_f32``.  -> ``out``, or with ``keep`` ``(out, agg, z, hidden, mean, rstd)``."""
+    H, F_ = w1.shape
+    dev = w1.device
+    sizes = [int(h[0].shape[0]) - 1 for h in hops]
+    n, T = sum(sizes), sum(_tiles(s) for s in sizes)
+    z = torch.empty((n, H), dtype=torch.float32, device=dev)
+    agg = torch.empty((n, F_), dtype=torch.float32, device=dev) if keep else None
+    partials = torch.empty((T, 2, H), dtype=torch.float32, device=dev)
+    counts = torch.empty(T, dtype=torch.int32, device=dev)
+    at = tile0 = 0
+    for (row_ptr, col, self_rows, x_dst), s in zip(hops, sizes):
+        if s > 0:
+            rows = slice(at, at + s)
+            gin_layer_stats(row_ptr, col, x, self_rows, w1, b1, z[rows], partials, counts, tile0, eps=eps, src_ids=src_ids,
+                            x_dst=x_dst, agg_out=None if agg is None else agg[rows])
+        at += s
+        tile0 += _tiles(s)
+    mean, _, rstd, scale, shift = bn_finalize(partials, counts, gamma, beta, bn_eps, momentum, running_mean, running_var)
+    out, hidden = bn_act_linear(z, scale, shift, w2, b2, relu_out=relu_out, keep=keep)
+    return (out, agg, z, hidden, mean, rstd) if keep else out
+
+
+class _GinBnLayer(torch.autograd.Function):
+    """The training-mode ``"mlp_bn"`` route over a ``LayerGraph`` (``gin_bn_forward``).  Backward, no atomics: dW2, db2 from the
+    kept hidden activation, dHidden = dOut W2 (one library GEMM), the batch norm's own backward (``bn_relu_backward``: dgamma,
+    dbeta, dz), then ``_GinLayer``'s lower half fed with dz."""
+
+    @staticmethod
+    def forward(ctx, src, x_dst, eps, w1, b1, gamma, beta, w2, b2, graph, ids, relu_out, n_src, no_root, bn):
+        det = lambda t: None if t is None else t.detach()      # noqa: E731
+        keep = any(ctx.needs_input_grad[:9])
+        hops = []
+        for h, rows, _ in _hops(graph):
+            self_rows, xd = _gin_hop_self(h, rows, det(x_dst), no_root)
+            hops.append((h.row_ptr, h.col, self_rows, xd))
+        res = gin_bn_forward(hops, src, det(w1), det(b1), det(gamma), det(beta), det(w2), det(b2), bn_eps=bn.eps,
+                             momentum=bn.momentum, running_mean=bn.running_mean, running_var=bn.running_var, eps=det(eps),
+                             relu_out=relu_out, src_ids=ids, keep=keep)
+        bn.num_batches_tracked.add_(1)
+        if not keep:
+            return res
+        out, agg, z, hidden, mean, rstd = res
+        ctx.save_for_backward(w1, w2, eps, out, x_dst, gamma)
+        ctx.kept = (agg, z, hidden, mean, rstd)
+        ctx.src = src if ctx.needs_input_grad[2] else None
+        ctx.graph, ctx.ids, ctx.relu_out, ctx.n_src, ctx.no_root = graph, ids, relu_out, n_src, no_root
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        _released(ctx.kept, "GINConv", "activations")
+        w1, w2, eps, out, x_dst, gamma = ctx.saved_tensors
+        agg, z, hidden, mean, rstd = ctx.kept
+        need_x, need_xd, need_eps, need_w1, need_b1, need_gamma, need_beta, need_w2, need_b2 = ctx.needs_input_grad[:9]
+        H, F_ = w1.shape
+        graph = ctx.graph
+        g = g.contiguous().float()
+        if ctx.relu_out:
+            g = torch.ops.aten.threshold_backward(g, out, 0)
+        gw1 = gb1 = gw2 = gb2 = None
+        if need_w2 or need_b2:
+            gw2, gb2 = _dense_wgrad(graph, hidden, g, w2, need_b2, None)
+            gw2 = gw2 if need_w2 else None
+        dz, dgamma, dbeta = bn_relu_backward(g @ w2, hidden, z, mean, rstd, gamma)      # dHidden: one library GEMM
+        if need_w1 or need_b1:
+            gw1, gb1 = _dense_wgrad(graph, agg, dz, w1, need_b1, None)
+            gw1 = gw1 if need_w1 else None
+        gx = gxd = geps = None
+        has_self = not ctx.no_root and x_dst is None
+        if need_x:
+            gx = _gin_input_grad(graph, dz, ctx.n_src, eps, has_self, weight=_padded_wt(w1, H))
+        if (need_xd or need_eps) and not ctx.no_root:
+            d_agg = dz @ w1
+            if need_xd:
+                gxd = torch.zeros_like(x_dst, dtype=torch.float32)
+                gxd[:d_agg.shape[0]] = (1.0 + eps) * d_agg
+            if need_eps:
+                geps = (d_agg * _gin_self_rows(ctx.src, ctx.ids, x_dst, graph)).sum().reshape(eps.shape)
+        elif need_eps:
+            geps = torch.zeros_like(eps)
+        ctx.kept = None
+        return (gx, gxd, geps, gw1, gb1, dgamma if need_gamma else None, dbeta if need_beta else None, gw2, gb2, None, None, None,
+                None, None, None)
+
+
+def _bn_folded_linear(lin1, bn, grad: bool):
+    """``(W1', b1')`` with the eval-mode BatchNorm folded into the Linear before it: ``W1' = diag(s) W1``, ``b1' = s b1 + t``,
+    ``s = gamma / sqrt(running_var + eps)``, ``t = beta - running_mean s`` — built once per weight change (``_derived``), or
+    under autograd when a gradient is wanted."""
+    def build():
+        s = bn.weight * torch.rsqrt(bn.running_var + bn.eps)
+        t = bn.bias - bn.running_mean * s
+        return (lin1.weight * s[:, None]).contiguous(), (t if lin1.bias is None else lin1.bias * s + t).contiguous()
+    params = (lin1.weight, lin1.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+    return _derived(bn, "folded_linear", params, build, extra=float(bn.eps), grad=grad)
+
+
 class GINConv(torch.nn.Module):
     """PyG ``GINConv`` (``flow="source_to_target"``): ``x'_i = nn((1 + eps) x_i + sum_{j -> i} x_j)`` — every edge is summed,
     loop edges and duplicates too.  ``eps`` is a Parameter with ``train_eps`` and a buffer otherwise, ``nn`` any module
@@ -3280,9 +3575,17 @@ class GINConv(torch.nn.Module):
     layer in the reference's model.  What runs depends on ``nn`` (``route``):
 
     * ``"mlp"`` — ``Sequential(Linear(F, H), ReLU(), Linear(H, N))``, the GIN paper's MLP: the whole layer is ONE kernel per hop
-      (``wgamd_gin_layer_f32``: aggregate, both products, biases, ReLUs; the hidden activation never leaves LDS);
+      (``wgamd_gin_layer_f32``: aggregate, both products, biases, ReLUs; the hidden activation never leaves LDS); an
+      ``MLP([F, H, N], norm=None)`` is the same layer;
+    * ``"mlp_bn"`` — ``MLP([F, H, N])`` with its defaults (``Linear -> BatchNorm1d -> ReLU -> Linear``, no dropout), the layer the
+      reference's example trains.  Eval mode: the running statistics fold into ``W1``, ``b1`` and the layer is the ``"mlp"``
+      kernel, ONE launch per hop.  Training mode: the layer kernel per hop with per-tile statistics
+      (``wgamd_gin_layer_f32_stats``), one finalize launch (``wgamd_bn_finalize_f32``, which updates the running statistics) and
+      one fused normalise -> ReLU -> ``W2`` launch (``wgamd_bn_act_linear_f32``); fewer than 2 rows: ValueError, as
+      ``BatchNorm1d`` does;
     * ``"linear"`` — a ``Linear``, or a ``Sequential`` that starts with one (a ``ReLU`` right behind it included): one kernel for
-      the aggregate and that product, the remaining modules run as they are (a BatchNorm between the Linears lands here);
+      the aggregate and that product, the remaining modules run as they are (a ``Sequential`` with a BatchNorm between the
+      Linears lands here, and any ``MLP`` outside the two routes above goes by its ``flat_modules()``);
     * ``"aggregate"`` — anything else, and shapes outside the kernel's domain (F % 4 == 0; F, H, N <= 256; H % 4 == 0 for
       ``"mlp"``): the aggregate kernel, then ``nn``.  CPU tensors run PyG's formulation in torch ops."""
 
@@ -3308,7 +3611,16 @@ class GINConv(torch.nn.Module):
 
     def _plan(self):
         """``(route, lin1, relu1, lin2, rest)``: the leading modules the kernel runs and the ones that follow it."""
-        mods = list(self.nn) if isinstance(self.nn, torch.nn.Sequential) else [self.nn]
+        if isinstance(self.nn, MLP):
+            m = self.nn
+            bn = m.norms[0].module if m.norm == "batch_norm" and len(m.norms) == 1 else None
+            if (bn is not None and len(m.lins) == 2 and m.act == "relu" and not m.act_first and m.plain_last and m.dropout[0] == 0.0
+                    and bn.affine and bn.track_running_stats and isinstance(bn.momentum, float)
+                    and gin_layer_supported(*m.channel_list)):
+                return "mlp_bn", m.lins[0], True, m.lins[1], []
+            mods = m.flat_modules()
+        else:
+            mods = list(self.nn) if isinstance(self.nn, torch.nn.Sequential) else [self.nn]
         if not mods or type(mods[0]) is not torch.nn.Linear:
             return "aggregate", None, False, None, [self.nn]
         lin1 = mods[0]
@@ -3323,7 +3635,7 @@ class GINConv(torch.nn.Module):
 
     @property
     def route(self) -> str:
-        """``"mlp"``, ``"linear"`` or ``"aggregate"``: what ``nn``'s form and shapes select on the device."""
+        """``"mlp"``, ``"mlp_bn"``, ``"linear"`` or ``"aggregate"``: what ``nn``'s form and shapes select on the device."""
         return self._plan()[0]
 
     def _forward_layer(self, x, lg: LayerGraph, act=None, x_dst=None, no_root=False):
@@ -3339,10 +3651,14 @@ class GINConv(torch.nn.Module):
             return torch.relu(out) if relu else out
         eps = self.eps if self.eps.dtype == torch.float32 else self.eps.float()
         route, lin1, relu1, lin2, rest = self._plan()
+        bn = self.nn.norms[0].module if route == "mlp_bn" else None
         if route != "aggregate":
             ws = [t for t in (lin1.weight, lin1.bias, lin2 and lin2.weight, lin2 and lin2.bias) if t is not None]
+            if bn is not None:
+                ws += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
             ok = all(t.dtype == torch.float32 and t.is_cuda for t in ws) and _kernel_rows_ok(lin1.weight) and (
-                lin2 is None or _kernel_rows_ok(lin2.weight)) and all(t.is_contiguous() for t in ws if t.dim() == 1)
+                lin2 is None or _kernel_rows_ok(lin2.weight)) and all(t.is_contiguous() for t in ws if t.dim() == 1) and (
+                bn is None or all(t.data_ptr() % 16 == 0 for t in ws[-4:]))      # (the batch-norm kernels read [H] vectors as float4)
             if ok and lazy and not _kernel_rows_ok(src):
                 x, lazy = x.materialize(), False
                 src, ids = x, None
@@ -3359,6 +3675,15 @@ class GINConv(torch.nn.Module):
             out = self.nn(out)
             return torch.relu(out) if relu else out
         fuse_act = relu and not rest                            # the layer's ReLU rides in the kernel when nothing follows it
+        if bn is not None and bn.training and lg.n_rows > 0:
+            if lg.n_rows < 2:
+                raise ValueError("GINConv: the batch norm of nn needs more than 1 row in training mode, got %d" % lg.n_rows)
+            return _GinBnLayer.apply(src, x_dst, eps, lin1.weight, lin1.bias, bn.weight, bn.bias, lin2.weight, lin2.bias, lg, ids,
+                                     fuse_act, n_src, no_root, bn)
+        if bn is not None:                                      # eval mode (or no row at all): the "mlp" kernel on the folded W1, b1
+            w1, b1 = (lin1.weight, lin1.bias) if bn.training else _bn_folded_linear(
+                lin1, bn, torch.is_grad_enabled() and any(t.requires_grad for t in (lin1.weight, lin1.bias, bn.weight, bn.bias) if t is not None))
+            return _GinLayer.apply(src, x_dst, eps, w1, b1, lin2.weight, lin2.bias, lg, ids, True, fuse_act, n_src, no_root)
         if lin2 is None:
             out = _GinLayer.apply(src, x_dst, eps, lin1.weight, lin1.bias, None, None, lg, ids, relu1 or fuse_act, False, n_src,
                                   no_root)

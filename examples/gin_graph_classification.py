@@ -3,14 +3,17 @@
 `GINConv(MLP([in, hidden, hidden]), train_eps=False)` with `.relu()` after each, `global_add_pool`, then an MLP head and
 `cross_entropy`.  Here every layer is `wholegraph_amd.nn.GINConv(Sequential(Linear, ReLU, Linear))` — ONE kernel per layer
 forward (aggregate, both products, biases, both ReLUs) — and the pooling is `wholegraph_amd.nn.global_add_pool` over the sorted
-batch vector (one kernel, no atomics).
+batch vector (one kernel, no atomics).  With `--batch-norm` every layer is `GINConv(wholegraph_amd.nn.MLP([in, hidden, hidden]))`,
+PyG's `MLP` with its default `norm="batch_norm"` — the layer the reference trains (Linear -> BatchNorm1d -> ReLU -> Linear; route
+"mlp_bn": the layer kernel with per-tile statistics, one finalize launch and one fused tail in training, ONE kernel on the folded
+weights in eval mode).
 
 The data is synthetic: a few thousand small random graphs of two classes that differ in edge density, node features = the
 one-hot degree (padded to a multiple of 4, as the TU datasets without features get `OneHotDegree`).  A mini-batch is a set of
 whole graphs concatenated as PyG's `Batch` does: node ids shifted per graph, one COO `edge_index`, a sorted `batch` vector
 and its `ptr`.
 
-    python examples/gin_graph_classification.py [--graphs 4000] [--epochs 10] [--torch-ops [--float64] [--device cpu]]
+    python examples/gin_graph_classification.py [--graphs 4000] [--epochs 10] [--batch-norm] [--torch-ops [--float64] [--device cpu]]
 
 `--torch-ops` runs the same model on the same data in plain torch ops (`index_add_`, `F.linear`, `relu`) — the yardstick of
 the accuracy (tests/test_gpu_gin_example.py), on any device.  Prints the loss per epoch, the test accuracy, and one JSON line.
@@ -76,13 +79,16 @@ def collate(data, gids):
 
 
 class GIN(torch.nn.Module):
-    def __init__(self, in_channels, hidden, classes, num_layers, dropout, torch_ops):
+    def __init__(self, in_channels, hidden, classes, num_layers, dropout, torch_ops, batch_norm=False):
         super().__init__()
-        from wholegraph_amd.nn import GINConv
+        from wholegraph_amd.nn import MLP, GINConv
         self.torch_ops = torch_ops
         self.convs = torch.nn.ModuleList()
         for _ in range(num_layers):
-            mlp = torch.nn.Sequential(torch.nn.Linear(in_channels, hidden), torch.nn.ReLU(), torch.nn.Linear(hidden, hidden))
+            if batch_norm:
+                mlp = MLP([in_channels, hidden, hidden])
+            else:
+                mlp = torch.nn.Sequential(torch.nn.Linear(in_channels, hidden), torch.nn.ReLU(), torch.nn.Linear(hidden, hidden))
             self.convs.append(GINConv(mlp, train_eps=False))
             in_channels = hidden
         self.head = torch.nn.Sequential(torch.nn.Linear(hidden, hidden), torch.nn.ReLU(), torch.nn.Dropout(dropout),
@@ -94,8 +100,11 @@ class GIN(torch.nn.Module):
         if self.torch_ops:                                 # the same model restated in plain torch ops
             for conv in self.convs:
                 agg = torch.zeros_like(x).index_add_(0, edge_index[1], x[edge_index[0]]) + (1.0 + conv.eps.to(x.dtype)) * x
-                lin1, _, lin2 = conv.nn
-                x = F.relu(F.linear(F.relu(F.linear(agg, lin1.weight, lin1.bias)), lin2.weight, lin2.bias))
+                if isinstance(conv.nn, torch.nn.Sequential):
+                    lin1, _, lin2 = conv.nn
+                    x = F.relu(F.linear(F.relu(F.linear(agg, lin1.weight, lin1.bias)), lin2.weight, lin2.bias))
+                else:                                      # --batch-norm: the MLP's own forward is torch ops
+                    x = F.relu(conv.nn(agg))
             pooled = torch.zeros((n_graphs, x.shape[1]), dtype=x.dtype, device=x.device).index_add_(0, batch, x)
         else:
             for conv in self.convs:
@@ -116,6 +125,7 @@ def main():
     ap.add_argument("--dropout", type=float, default=0.5)
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--train-split", type=float, default=0.9)
+    ap.add_argument("--batch-norm", action="store_true", help="layers GINConv(nn.MLP([in, hidden, hidden])): a BatchNorm1d between the Linears")
     ap.add_argument("--torch-ops", action="store_true", help="plain torch ops instead of the HIP layer (the accuracy yardstick)")
     ap.add_argument("--float64", action="store_true", help="with --torch-ops: float64")
     ap.add_argument("--device", default="cuda")
@@ -129,7 +139,7 @@ def main():
     data = (data[0].to(dev, dtype),) + tuple(t.to(dev) for t in data[1:])
     n_train = int(args.train_split * args.graphs)
     torch.manual_seed(0)                                   # (parameters are drawn on the CPU: the same on every route)
-    model = GIN(data[0].shape[1], args.hidden, 2, args.num_layers, args.dropout, args.torch_ops).to(dev, dtype)
+    model = GIN(data[0].shape[1], args.hidden, 2, args.num_layers, args.dropout, args.torch_ops, args.batch_norm).to(dev, dtype)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
     order = torch.Generator().manual_seed(1)
     losses = []

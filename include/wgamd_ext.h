@@ -1179,6 +1179,58 @@ wholememory_error_code_t wgamd_gin_aggregate_f32(const int* row_ptr, const int* 
 wholememory_error_code_t wgamd_segment_sum_f32(const float* x, int64_t ldx, int F, const int64_t* offsets, int64_t n_segments,
                                                float* out, int64_t ldo, void* stream);
 
+/* ---- Batch norm between the Linears of a GIN layer (csrc/wg_batch_norm.hip, csrc/wg_gin.hip): training mode ----------------------
+ * The layer the reference's dist_gin_sg.py trains, GINConv(MLP([in, hidden, hidden])) with PyG's default norm="batch_norm":
+ *   z      = agg @ W1^T + b1                                           [n, H]  (agg as in the GIN section above)
+ *   hidden = relu((z - mean) rstd gamma + beta)                        mean, biased var over ALL n rows; rstd = 1 / sqrt(var + eps)
+ *   out    = act2(hidden @ W2^T + b2)                                  [n, N]
+ * The statistics need every row, so the forward is three kinds of launch:
+ *  A wgamd_gin_layer_f32_stats, one per hop: the GIN layer kernel's one-product form, z kept in the LDS tile, stored to z_out
+ *    (and agg to agg_out, nullable), plus a record per 16-row tile t = tile0 + (row / 16): partials[t][0][:] = the columns' mean
+ *    over the tile's valid rows, partials[t][1][:] = M2 (sum of squared distances from that mean, two passes), counts[t] = valid
+ *    rows.  tile0 = the tiles of the layer's earlier hops.  Domain: wgamd_gin_layer_supported(F, H, 0) and H % 4 == 0.
+ *    wgamd_bn_partials_f32 writes the same records from rows z in memory.
+ *  B wgamd_bn_finalize_f32, one per layer: the n_tiles records combined per column with the pairwise update of (count, mean, M2)
+ *    (Chan, Golub, LeVeque 1979) in a fixed order (a contiguous chunk of tiles per thread, then a fixed tree) -> mean, var
+ *    (biased), rstd, scale = gamma rstd, shift = beta - mean scale (each [H]; all but mean nullable; gamma, beta nullable = 1, 0),
+ *    and running_mean / running_var (nullable) updated in place: r = (1 - momentum) r + momentum s, s = mean or the unbiased
+ *    variance M2 / (n - 1).  No atomics, no sum of squares.
+ *  C wgamd_bn_act_linear_f32, one per layer over all rows: 16-row tiles, hidden = relu(z scale + shift) into LDS (and hidden_out,
+ *    nullable), times W2^T on the fp32 matrix pipe with b2 (nullable) and the output ReLU (relu_out).  N <= 256.
+ * Backward of the normalisation and its ReLU, given dhidden = dOut W2 [n, H] and the kept hidden, z, mean, rstd:
+ *   dy = dhidden [hidden > 0],  x^ = (z - mean) rstd
+ *   wgamd_bn_bwd_reduce_f32: dbeta = sum dy, dgamma = sum dy x^ — wgamd_bn_bwd_blocks(n, H) partial rows of 2 H floats (the
+ *     caller's workspace), each a workgroup's rows added in a fixed order, then the partial rows added in a fixed order
+ *   wgamd_bn_bwd_apply_f32:  dz = gamma rstd (dy - dbeta / n - x^ dgamma / n), one pass; dz may be dhidden itself
+ * No atomics: the same bits on every run.  Domain: wgamd_batch_norm_supported(H) (H % 4 == 0, 4 <= H <= 256); float32, every
+ * ld >= its width and a multiple of 4, rows and the [H] vectors and partials 16-B aligned (WHOLEMEMORY_LOGIC_ERROR otherwise;
+ * null pointers and short leading dimensions WHOLEMEMORY_INVALID_INPUT) — checked on the host before any launch. */
+int wgamd_batch_norm_supported(int H);
+int64_t wgamd_bn_bwd_blocks(int64_t n_rows, int H);
+wholememory_error_code_t wgamd_gin_layer_f32_stats(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx,
+                                                   int F, const void* src_ids, wholememory_dtype_t src_ids_dtype,
+                                                   const int64_t* self_rows, const float* x_dst, int64_t ldx_dst, const float* eps,
+                                                   const float* w1, int64_t ldw1, int H, const float* b1, float* z_out, int64_t ldz,
+                                                   float* agg_out, int64_t ld_agg, float* partials, int* counts, int64_t tile0,
+                                                   void* stream);
+wholememory_error_code_t wgamd_bn_partials_f32(const float* z, int64_t ldz, int64_t n_rows, int H, float* partials, int* counts,
+                                               int64_t tile0, void* stream);
+wholememory_error_code_t wgamd_bn_finalize_f32(const float* partials, const int* counts, int64_t n_tiles, int H, const float* gamma,
+                                               const float* beta, float eps, float momentum, float* running_mean,
+                                               float* running_var, float* mean, float* var, float* rstd, float* scale, float* shift,
+                                               void* stream);
+wholememory_error_code_t wgamd_bn_act_linear_f32(const float* z, int64_t ldz, int64_t n_rows, int H, const float* scale,
+                                                 const float* shift, const float* w2, int64_t ldw2, int N, const float* b2,
+                                                 int relu_out, float* out, int64_t ldo, float* hidden_out, int64_t ld_hidden,
+                                                 void* stream);
+wholememory_error_code_t wgamd_bn_bwd_reduce_f32(const float* dhidden, int64_t ld_dh, const float* hidden, int64_t ld_hidden,
+                                                 const float* z, int64_t ldz, int64_t n_rows, int H, const float* mean,
+                                                 const float* rstd, float* partials, float* dgamma, float* dbeta, void* stream);
+wholememory_error_code_t wgamd_bn_bwd_apply_f32(const float* dhidden, int64_t ld_dh, const float* hidden, int64_t ld_hidden,
+                                                const float* z, int64_t ldz, int64_t n_rows, int H, const float* mean,
+                                                const float* rstd, const float* gamma, const float* dgamma, const float* dbeta,
+                                                float* dz, int64_t ld_dz, void* stream);
+
 /* ---- GATv2 attention (csrc/wg_gatv2.hip): torch_geometric.nn.GATv2Conv over a sampled hop, on the TRANSFORMED rows ----------------
  *   e[k, h]  = sum_c att[h C + c] LeakyReLU(XL[j, h C + c] + XR[i, h C + c])       (k = (j -> i), j = col[k] a row of xl)
  *   alpha    = softmax over the edges of row i of e[:, h]
