@@ -76,7 +76,9 @@ struct wholememory_handle_ {
   wgamd::mapped_view* d_view = nullptr;
   // WHOLEMEMORY_ML_HOST: the partition is pinned host memory the GPU reads and writes in place over PCIe.  A partition
   // that other PROCESSES map (peer-mapped types) is a POSIX shared-memory segment registered with the runtime on
-  // both sides; everything else is a hipHostMalloc block.
+  // both sides; everything else is a hipHostMalloc block.  Where the machine cannot register memory a process already has
+  // (wgamd_host_register_supported), the partition of a peer-mapped type is a hipHostMalloc block too: ranks that are threads
+  // of ONE process still reach it by its pointer, another process cannot map it and the allocation fails on every rank.
   bool host_shm = false;                // local_ptr is an mmap'ed + registered segment of `local_map_bytes`
   size_t local_map_bytes = 0;
   std::vector<void*> peer_host_map;     // [W]; the peers' segments as mapped into THIS process (unregistered + unmapped on free)
@@ -199,6 +201,24 @@ uint64_t host_identity()
   uint64_t h = 1469598103934665603ull;
   for (size_t i = 0; i < len; i++) h = (h ^ (unsigned char)buf[i]) * 1099511628211ull;
   return h;
+}
+
+// Can the runtime pin memory this process already has?  A shared segment that several processes map becomes GPU-visible only
+// through hipHostRegister, and some machines (virtual ones, for instance) refuse it.  Asked once, of one shared page.
+bool host_register_supported()
+{
+  static bool ok = false;
+  static std::once_flag once;
+  std::call_once(once, [] {
+    const size_t bytes = (size_t)sysconf(_SC_PAGESIZE);
+    void* m            = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_SHARED | MAP_ANONYMOUS, -1, 0);
+    if (m == MAP_FAILED) return;
+    ok = hipHostRegister(m, bytes, hipHostRegisterPortable | hipHostRegisterMapped) == hipSuccess;
+    if (ok) (void)hipHostUnregister(m);
+    else (void)hipGetLastError();   // (a refused registration must not be what the next launch reports)
+    munmap(m, bytes);
+  });
+  return ok;
 }
 
 // ---- kernels ---------------------------------------------------------------------------------------
@@ -878,10 +898,12 @@ wholememory_error_code_t wholememory_malloc(wholememory_handle_t* handle_ptr, si
     if (local > 0 && host) {
       // memory_handle.cpp:432-520 (host memory of the mapped types = one shared segment every process maps) /
       // :233-262 (distributed host memory = pinned memory of the owning process).  Pinned either way, so the GPU's loads
-      // and stores reach it in place.
+      // and stores reach it in place.  A machine that cannot register a mapped segment gets pinned memory of the owning
+      // process for the mapped types as well: ranks of this process use it through its pointer, and a rank of ANOTHER process
+      // finds no segment name in the exchange below and fails the allocation for everybody.
       bool ok = !inject;
       if (!ok) {
-      } else if (mapped) {
+      } else if (mapped && host_register_supported()) {
         static std::atomic<unsigned> seq{0};
         timespec now{};
         clock_gettime(CLOCK_MONOTONIC, &now);   // pid + counter + time: containers that share /dev/shm may share pids
@@ -968,6 +990,9 @@ wholememory_error_code_t wholememory_malloc(wholememory_handle_t* handle_ptr, si
             h->peer_ptr[r] = reinterpret_cast<void*>(rec.ptr);
           } else if (host) {
             // the peer's segment, mapped and registered here as well
+            if (rec.shm[0] == 0)
+              throw logic_error("host peer mapping: this machine cannot register a shared-memory segment (hipHostRegister), so "
+                                "a peer's host partition is reachable only from ranks of its own process");
             const int fd = shm_open(rec.shm, O_RDWR, 0600);
             void* m      = fd >= 0 ? mmap(nullptr, rec.bytes, PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0) : MAP_FAILED;
             if (fd >= 0) close(fd);
@@ -1180,6 +1205,8 @@ wholememory_error_code_t wgamd_mapped_row_offsets(wholememory_tensor_t table, co
     WG_HIP_CHECK(hipGetLastError());
   });
 }
+
+bool wgamd_host_register_supported(void) { return host_register_supported(); }
 
 /* the two HIP IPC steps on their own (what wholememory_malloc does per peer): a 64-byte handle of a hipMalloc'ed block,
  * and mapping such a handle exported by ANOTHER process of this node */

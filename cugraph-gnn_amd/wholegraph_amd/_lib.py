@@ -186,6 +186,7 @@ SYMBOLS = {
     "wgamd_communicator_rccl_info": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
     "wgamd_get_peer_pointers": (c_int, [POINTER(c_void_p), c_void_p]),
     "wgamd_mapped_row_offsets": (c_int, [_T, c_void_p, c_int, c_int64, c_void_p, POINTER(c_void_p), c_void_p]),
+    "wgamd_host_register_supported": (c_bool, []),
     "wgamd_ipc_export": (c_int, [c_void_p, c_void_p]),
     "wgamd_ipc_open": (c_int, [c_void_p, POINTER(c_void_p)]),
     "wgamd_ipc_close": (c_int, [c_void_p]),

@@ -18,7 +18,8 @@
  * WHOLEMEMORY_ML_HOST (memory_handle.cpp:233-262, :432-520): the same three types with every partition in PINNED HOST
  * memory, which the GPU's loads and stores reach in place over PCIe — a hipHostMalloc block of the owning process for
  * DISTRIBUTED (and for any type on a single-rank communicator), a POSIX shared-memory segment mapped and registered by
- * every process for the peer-mapped types.  Meant for tables that outgrow HBM, behind the READWRITE device cache of
+ * every process for the peer-mapped types (where hipHostRegister is refused: a hipHostMalloc block again, shared by the
+ * ranks of one process only — wgamd_host_register_supported).  Meant for tables that outgrow HBM, behind the READWRITE device cache of
  * wgamd_embedding.h.  HIERARCHY and NVSHMEM are not reproduced and return WHOLEMEMORY_NOT_SUPPORTED.  RCCL is resolved at run time (dlopen "librccl.so"), so the library loads on a CPU-only box
  * and inside a PyTorch process shares torch's RCCL.  One collective per communicator at a time (as RCCL requires): the
  * communicator's pinned count buffer is shared by its calls, so two gathers on ONE communicator from two host threads race.
@@ -126,6 +127,10 @@ wholememory_error_code_t wgamd_get_peer_pointers(void** pointers, wholememory_ha
  * peer-mapped (DISTRIBUTED rows are not addressable; a single-partition handle is read through its local tensor). */
 wholememory_error_code_t wgamd_mapped_row_offsets(wholememory_tensor_t table, const void* ids, wholememory_dtype_t ids_dtype,
                                                   int64_t n, int64_t* offsets, void** base, void* stream);
+/* whether the runtime can pin memory the process already has (hipHostRegister; probed once, needs a device).  Peer-mapped
+ * HOST memory shared by several PROCESSES depends on it; without it such a partition is a hipHostMalloc block that only the
+ * ranks of the owning process can reach, and wholememory_malloc fails on every rank when the ranks span processes. */
+bool wgamd_host_register_supported(void);
 /* the HIP IPC steps on their own: a 64-byte handle of a hipMalloc'ed block / mapping one exported by another process */
 wholememory_error_code_t wgamd_ipc_export(void* device_ptr, void* handle64);
 wholememory_error_code_t wgamd_ipc_open(const void* handle64, void** device_ptr);

@@ -423,6 +423,9 @@ def shim():
 def test_rw_cache_world_gt1(shim, W, n, dim, mtype, ratio, kind):
     env = dict(os.environ, WGAMD_RCCL_LIBRARY=shim)
     if mtype.endswith("+shm"):
+        from wholegraph_amd import _lib as L
+        if not L.lib().wgamd_host_register_supported():
+            pytest.skip("hipHostRegister is not supported here: a shared-memory segment cannot be made visible to the GPU")
         mtype, env["WGAMD_HOST_SHM_MAP_ALWAYS"] = mtype[:-4], "1"
     p = subprocess.run([sys.executable, "-c", WORKER, ROOT, str(W), str(n), str(dim), mtype, str(ratio), kind],
                        env=env, capture_output=True, text=True, timeout=300)
