@@ -1,5 +1,5 @@
 // Shared pieces of the one-kernel layers over a sampled hop (wg_gcn.hip, wg_rgcn.hip, wg_transformer.hip, wg_sage_hetero.hip,
-// wg_transformer_hetero.hip, wg_gin.hip): an input row read through the layer's node list, the kind of that list, the launch for
+// wg_transformer_hetero.hip, wg_gin.hip, wg_sage_max.hip): an input row read through the layer's node list, the kind of that list, the launch for
 // the kind found at run time, the 16-B row test, the dynamic-LDS launch of a layer kernel, the zeroing of the tile's k padding
 // and the copy of a finished tile to kept rows, the frame of a heterogeneous launch (row_of, hetero_frame and its host check,
 // the relations' row_ptr windows), and phase 2 of every layer kernel — the [16 x K16] LDS tile times wt^T on the exact fp32
@@ -214,6 +214,55 @@ __device__ __forceinline__ void tile_times_wt(const float* tile, int SD, int K, 
         if (acc_in) y += acc_in[i * ld_acc + n];
         if (relu) y = fmaxf(y, 0.f);
         out[(out_rows ? out_rows[i] : i) * ldo + n] = y;
+      }
+    }
+  }
+}
+
+// Phase 2 with the weight in two pieces, each in its torch.nn.Linear layout: column k of the tile meets wa[n, k] for k < Ka
+// and wb[n, k - Ka] for Ka <= k < K (wb is not read when K == Ka); Ka a multiple of 4, so no float4 of k straddles the two.
+// Otherwise tile_times_wt: the same ownership of column tiles, the same fragment reads, bias and ReLU fused, one store.  No
+// stacked or transposed copy of the two weights exists: what a training step under HIP-graph capture would have to rebuild
+// on every replay.
+__device__ __forceinline__ void tile_times_two_wt(const float* tile, int SD, int Ka, int K, int K16, const float* wa, int64_t ldwa,
+                                                  const float* wb, int64_t ldwb, int N, const float* bias, int relu, float* out,
+                                                  int64_t ldo, int64_t row0, int64_t n_rows)
+{
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int n_ct = (N + 15) / 16;
+  if (wave >= n_ct) return;
+  const int m = lane & 15, g = lane >> 4;
+  f32x4 acc[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int kb = 0; kb < K16; kb += 16) {
+    const int k = kb + 4 * g;
+    const f32x4 av = *reinterpret_cast<const f32x4*>(tile + m * SD + k);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int ct = wave + 4 * q;
+      if (ct < n_ct) {
+        const int n = ct * 16 + m;
+        f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+        if (n < N && k < Ka) bv = *reinterpret_cast<const f32x4*>(wa + (int64_t)n * ldwa + k);
+        else if (n < N && k < K) bv = *reinterpret_cast<const f32x4*>(wb + (int64_t)n * ldwb + (k - Ka));
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], bv[kk], acc[q], 0, 0, 0);
+      }
+    }
+  }
+  // C/D map of the 16x16 MFMA: col = lane & 15, row = 4 (lane >> 4) + reg
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int n = (wave + 4 * q) * 16 + m;
+    if (wave + 4 * q >= n_ct || n >= N) continue;
+    const float b = bias ? bias[n] : 0.f;
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int64_t i = row0 + 4 * g + reg;
+      if (i < n_rows) {
+        const float y = acc[q][reg] + b;
+        out[i * ldo + n] = relu ? fmaxf(y, 0.f) : y;
       }
     }
   }

@@ -404,6 +404,15 @@ SYMBOLS = {
     "wgamd_gin_aggregate_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                         c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
     "wgamd_segment_sum_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    # SAGE layer with the max / min aggregator (wg_sage_max.hip)
+    "wgamd_sage_max_layer_supported": (c_int, [c_int, c_int, c_int]),
+    "wgamd_sage_max_layer_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                         c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "wgamd_sage_max_layer_f32_train": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p,
+                                               c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64,
+                                               c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "wgamd_sage_max_bwd_src_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int,
+                                           c_void_p, c_int64, c_void_p]),
     # batch norm between the Linears of a GIN layer (wg_batch_norm.hip; the layer kernel's STATS variant: wg_gin.hip)
     "wgamd_batch_norm_supported": (c_int, [c_int]),
     "wgamd_bn_bwd_blocks": (c_int64, [c_int64, c_int]),

@@ -1794,8 +1794,191 @@ class _SageLayer(torch.autograd.Function):
         return gx, gwl, gwr, gb, None, None, None, None, None
 
 
+SAGE_MAX_RELU, SAGE_MAX_MIN = 1, 2     # WGAMD_SAGE_MAX_* (include/wgamd_ext.h)
+
+
+def sage_max_layer_supported(F_: int, N: int, has_root: bool = True) -> bool:
+    """The domain of ``sage_max_layer_forward``: F % 4 == 0, 4 <= F, tile width (2 F with a root weight, else F) <= 1024,
+    1 <= N <= 256 (``wgamd_sage_max_layer_supported``)."""
+    return bool(L.lib().wgamd_sage_max_layer_supported(int(F_), int(N), int(bool(has_root))))
+
+
+def sage_max_layer_forward(row_ptr, col, x, self_rows, w_l, w_r=None, bias=None, relu=False, minimum=False, src_ids=None, out=None,
+                           keep=False):
+    """A whole SAGE layer with the max (``minimum``: min) aggregator over one hop in ONE kernel (``wgamd_sage_max_layer_f32``,
+    include/wgamd_ext.h): ``act(red @ w_l^T + x[self_rows] @ w_r^T + bias)`` with ``red[i]`` the element-wise max of the rows
+    ``x[col[e]]`` of row i's edges, 0 for an empty row; ``w_l`` / ``w_r`` [N, F] in ``torch.nn.Linear`` layout, read as they are.
+    ``w_r`` and ``self_rows`` None together: no root term.  Ties: the lowest CSR edge slot holding the value wins.  +-inf inputs
+    compare as IEEE says; NaN inputs are outside the contract (the result is then unspecified).  ``keep``: the launch also
+    stores ``red`` and the int32 edge slot every value came from (-1: empty row), and ``(out, red, arg)`` is returned."""
+    hop = _hop_args(row_ptr, col, x, src_ids)
+    n_rows, F_, N, dev = row_ptr.shape[0] - 1, x.shape[1], w_l.shape[0], row_ptr.device
+    assert (w_r is None) == (self_rows is None), "self_rows is given exactly when w_r is"
+    for w in (w_l, w_r):
+        assert w is None or (w.dtype == torch.float32 and w.stride(1) == 1 and w.shape == (N, F_))
+    assert self_rows is None or (self_rows.dtype == torch.int64 and self_rows.is_contiguous() and self_rows.shape[0] == n_rows)
+    out = _out_rows(out, n_rows, N, dev)
+    flags = (SAGE_MAX_RELU if relu else 0) | (SAGE_MAX_MIN if minimum else 0)
+    common = hop + (_ptr(self_rows), w_l.data_ptr(), w_l.stride(0), _ptr(w_r), 0 if w_r is None else w_r.stride(0), N, _ptr(bias),
+                    flags, out.data_ptr(), out.stride(0))
+    if not keep:
+        L.check(L.lib().wgamd_sage_max_layer_f32(*common, get_stream()), "wgamd_sage_max_layer_f32")
+        return out
+    agg = torch.empty((n_rows, F_), dtype=torch.float32, device=dev)
+    arg = torch.empty((n_rows, F_), dtype=torch.int32, device=dev)
+    L.check(L.lib().wgamd_sage_max_layer_f32_train(*common, agg.data_ptr(), agg.stride(0), arg.data_ptr(), arg.stride(0),
+                                                   get_stream()), "wgamd_sage_max_layer_f32_train")
+    return out, agg, arg
+
+
+def sage_max_bwd_src(row_ptr_t, col_t, perm, arg, dagg, n_src: int):
+    """``gx[j, f] = sum_{t in row j of the transposed hop} [arg[col_t[t], f] == perm[t]] dagg[col_t[t], f]`` — the gradient of the
+    max / min reduce w.r.t. the layer's input rows (``wgamd_sage_max_bwd_src_f32``): every (row, feature) of ``dagg`` goes to the
+    ONE edge slot ``arg`` names.  No atomics, a fixed summation order: the same bits from run to run."""
+    assert arg.dtype == torch.int32 and arg.stride(1) == 1 and dagg.dtype == torch.float32 and dagg.stride(1) == 1
+    assert arg.shape == dagg.shape and perm.dtype == torch.int32 and row_ptr_t.shape[0] == n_src + 1
+    F_ = arg.shape[1]
+    gx = torch.empty((n_src, F_), dtype=torch.float32, device=dagg.device)
+    L.check(L.lib().wgamd_sage_max_bwd_src_f32(row_ptr_t.data_ptr(), _nonempty(col_t, torch.int32).data_ptr(), perm.data_ptr(), n_src,
+                                               arg.data_ptr(), arg.stride(0), dagg.data_ptr(), dagg.stride(0), F_, gx.data_ptr(),
+                                               gx.stride(0), get_stream()), "wgamd_sage_max_bwd_src_f32")
+    return gx
+
+
+def _sage_max_reduce_torch(x, h: HopGraph, minimum: bool):
+    """``red`` of one hop out of torch ops, differentiable in ``x``, with the KERNEL's tie rule: the value of (i, f) is gathered
+    from the lowest CSR edge slot holding the extreme, so its gradient goes wholly there (torch's ``amax`` backward would split
+    it evenly among tied edges); an empty row is 0."""
+    n, E, F_ = h.n_rows, int(h.col.shape[0]), x.shape[1]
+    if n == 0 or E == 0:
+        return x.new_zeros((n, F_))
+    with torch.no_grad():
+        col, dst = h.col.long(), _edge_dst(h.row_ptr, E)
+        rows, at = x.detach()[col], dst.unsqueeze(1).expand(E, F_)
+        best = rows.new_zeros((n, F_)).scatter_reduce(0, at, rows, "amin" if minimum else "amax", include_self=False)
+        slot = torch.arange(E, device=x.device).unsqueeze(1).expand(E, F_)
+        arg = torch.full((n, F_), E, dtype=torch.int64, device=x.device).scatter_reduce(
+            0, at, torch.where(rows == best[dst], slot, E), "amin", include_self=True)
+        has = arg < E
+        src = col[arg.clamp(max=E - 1)]
+    return torch.where(has, torch.gather(x, 0, src), x.new_zeros(()))
+
+
+def _sage_max_torch(xd, x_root, w_l, w_r, bias, lg: LayerGraph, minimum: bool, relu: bool):
+    """The max / min SAGE layer out of torch ops (shapes outside the kernel's domain, CPU tensors, the bipartite call form, a
+    double backward): the kernel route's formula and tie rule, ordinary autograd."""
+    outs = []
+    for h in lg.hops:
+        o = torch.nn.functional.linear(_sage_max_reduce_torch(xd, h, minimum), w_l, bias)
+        if w_r is not None:
+            o = o + torch.nn.functional.linear(x_root[h.self_rows], w_r)
+        outs.append(o)
+    out = outs[0] if len(outs) == 1 else torch.cat(outs)
+    return torch.relu(out) if relu else out
+
+
+def _sage_max_launch(ctx, src, w_l, w_r, bias, graph, ids, relu, minimum):
+    """The layer's launches (one per hop of ``graph``); ``ctx`` = the autograd context of ``_SageMaxLayer`` (then the reduce and
+    its edge slots are kept per hop) or None."""
+    keep = ctx is not None
+    out = torch.empty((graph.n_rows, w_l.shape[0]), dtype=torch.float32, device=src.device)
+    kept = []
+    for h, rows, _ in _hops(graph):
+        res = None
+        if h.n_rows > 0:
+            res = sage_max_layer_forward(h.row_ptr, h.col, src, None if w_r is None else h.self_rows, w_l, w_r, bias, relu=relu,
+                                         minimum=minimum, src_ids=ids, out=out[rows], keep=keep)
+        kept.append(res[1:] if keep and res is not None else None)
+    if keep:
+        if ctx.needs_input_grad[0] and ids is not None:
+            raise _lazy_table_grad_error()
+        ctx.save_for_backward(src, w_l, w_r, bias, out)
+        ctx.graph, ctx.ids, ctx.relu, ctx.minimum, ctx.kept = graph, ids, relu, minimum, kept
+    return out
+
+
+def _sage_max_dx(hop: HopGraph, gz, arg, w_l, w_r, n_src: int):
+    """Gradient of one hop of the max / min SAGE layer w.r.t. its input rows: ``dAgg = dZ W_l`` (one library GEMM) routed to
+    the edge slots the forward kept, over the hop's transpose (made once per hop), plus the root term at ``self_rows`` (injective:
+    one add per row)."""
+    row_ptr_t, col_t, _, perm = hop.transposed(n_src, need_self=False, need_perm=True)
+    gx = sage_max_bwd_src(row_ptr_t, col_t, perm, arg, gz @ w_l, n_src)
+    return gx if w_r is None else gx.index_add_(0, hop.self_rows, gz @ w_r)
+
+
+class _SageMaxLayer(torch.autograd.Function):
+    """The one-kernel max / min SAGE layer over a ``LayerGraph`` with its backward pass on the HIP kernels.  Forward: the
+    ``_train`` launch per hop, which keeps the reduced rows and the edge slot of every value.  Backward: the weight gradients of
+    the mean / sum layer with the kept reduce as their operand (``sage_wgrad``; ``gcn_wgrad`` without a root weight; ReLU mask
+    folded in when the input needs no gradient) and, when the input rows need a gradient, ``_sage_max_dx``.  A backward under
+    ``create_graph=True`` runs the formula out of torch ops instead."""
+
+    @staticmethod
+    def forward(ctx, src, w_l, w_r, bias, graph, ids, relu, minimum):
+        return _sage_max_launch(ctx, src, w_l, w_r, bias, graph, ids, relu, minimum)
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            return _sage_max_double_backward(ctx, g)
+        _released(ctx.kept, "SAGEConv", "reduced rows and edge slots", "; run the forward again, or sum the losses before calling backward")
+        src, w_l, w_r, bias, out = ctx.saved_tensors
+        graph, ids, relu, need = ctx.graph, ctx.ids, ctx.relu, ctx.needs_input_grad
+        N = w_l.shape[0]
+        if g.stride(1) != 1 or g.dtype != torch.float32:
+            g = g.contiguous().float()
+        act = out if relu else None
+        if relu and need[0]:
+            g, act = torch.ops.aten.threshold_backward(g, out, 0), None      # dZ once, read by both gradients
+        want_w = any(need[1:4])
+        gwl = torch.empty_like(w_l, memory_format=torch.contiguous_format) if want_w else None
+        gwr = torch.empty_like(w_r, memory_format=torch.contiguous_format) if want_w and w_r is not None else None
+        gb = torch.empty(N, dtype=torch.float32, device=g.device) if want_w and bias is not None else None
+        gx, first = None, True
+        for (h, rows, _), k in zip(_hops(graph), ctx.kept):
+            if h.n_rows > 0:
+                agg, arg = k
+                act_h = None if act is None else act[rows]
+                if want_w and w_r is not None:
+                    sage_wgrad(agg, src, h.self_rows, g[rows], gwl, gwr, gb, act_h, src_ids=ids, accumulate=not first)
+                elif want_w:
+                    gcn_wgrad(agg, g[rows], gwl, gb, act_h, accumulate=not first)
+                first = False
+                if need[0]:
+                    gh = _sage_max_dx(h, g[rows], arg, w_l, w_r, src.shape[0])
+                    gx = gh if gx is None else gx.add_(gh)
+        if first:
+            for t in (gwl, gwr, gb):
+                if t is not None:
+                    t.zero_()
+        if need[0] and gx is None:
+            gx = torch.zeros_like(src)
+        ctx.kept = None
+        return gx, gwl, gwr, gb, None, None, None, None
+
+
+def _sage_max_double_backward(ctx, g):
+    """The gradients as differentiable torch expressions of the saved inputs and ``g``."""
+    src, w_l, w_r, bias, _ = ctx.saved_tensors
+    res = [None] * 8
+    with torch.enable_grad():
+        xd = src if ctx.ids is None else src[ctx.ids.long()]
+        y = _sage_max_torch(xd, xd, w_l, w_r, bias, ctx.graph, ctx.minimum, ctx.relu)
+        ins = [(i, t) for i, t in enumerate((src, w_l, w_r, bias)) if t is not None and t.requires_grad and ctx.needs_input_grad[i]]
+        if ins:
+            for (i, _), gr in zip(ins, torch.autograd.grad(y, [t for _, t in ins], g, create_graph=True, allow_unused=True)):
+                res[i] = gr
+    return tuple(res)
+
+
+def _sage_max_wgrad_supported(F_: int, N: int, has_root: bool) -> bool:
+    """The weight-gradient kernels the max / min layer reuses take the shape (F, N <= 256)."""
+    lib = L.lib()
+    return (lib.wgamd_sage_wgrad_workspace_bytes(1, F_, N) if has_root else lib.wgamd_gcn_wgrad_workspace_bytes(1, F_, N)) > 0
+
+
 class SAGEConv(torch.nn.Module):
-    """``out = lin_l(mean_{j in N(i)} x_j) + lin_r(x_i)`` (PyG ``SAGEConv``, aggr mean|sum).
+    """``out = lin_l(aggr_{j in N(i)} x_j) + lin_r(x_i)`` (PyG ``SAGEConv``, aggr mean|sum|max|min).
 
     ``forward(x, graph)``: ``graph`` = the hop's ``[csr_row_ptr, csr_col_ind]`` or a COO ``edge_index`` (the reference's call
     shapes, gnn_model.py:178-199), or a ``LayerGraph`` of a loader call group — then the whole layer (feature fetch when
@@ -1807,13 +1990,27 @@ class SAGEConv(torch.nn.Module):
     to float32 exactly, so output, kept aggregate and gradients are those of the float32 layer over ``table.float()`` — the
     forward bit for bit.  The weight gradient gets the hop's self rows as float32 from one converting gather.  Every other
     route (an unsupported shape, ``root_weight=False``, aggregate + GEMM) receives float32 rows from one converting gather.  A
-    gradient into the table stays refused."""
+    gradient into the table stays refused.
+
+    ``aggr="max"`` / ``"min"`` (the GraphSAGE paper's pooling aggregator without its projection): the element-wise extreme of
+    the neighbour rows, 0 for a row without neighbours.  On all three graph forms, with a tensor or a float32 ``LazyRows``
+    (every id kind), ``act="relu"`` and ``root_weight=False``, the layer is ONE kernel per hop, forward
+    (``wgamd_sage_max_layer_f32``; F % 4 == 0, tile width 2 F — F without a root weight — <= 1024, N <= 256) and backward
+    (``_SageMaxLayer``; under autograd F <= 256, the weight-gradient kernels' domain); ``route`` is then ``"max_kernel"``.
+    Other shapes, CPU tensors, the bipartite ``(x_src, x_dst)`` form and a double backward run the same formula out of torch ops
+    (``route == "torch"``); a 16-bit ``LazyRows`` is converted by one gather first.  TIES: the gradient of a tied extreme goes
+    wholly to the lowest CSR edge slot holding it (the edge order of the graph as given, per destination) — a valid
+    subgradient, deterministic, and the same on both routes; torch's ``amax`` backward would split it evenly instead.  The two
+    rules agree whenever the extreme is unique or the tied edges share one source.  NaN inputs are outside the contract."""
 
     def __init__(self, in_channels: Union[int, Tuple[int, int]], out_channels: int, aggr: str = "mean",
                  root_weight: bool = True, bias: bool = True):
         super().__init__()
         if isinstance(in_channels, int):
             in_channels = (in_channels, in_channels)
+        if aggr not in ("mean", "sum", "add", "max", "min"):
+            raise ValueError("SAGEConv: aggr must be 'mean', 'sum', 'max' or 'min' ('add' = 'sum'; got %r)" % (aggr,))
+        self.route = None              # "max_kernel" | "torch": what the last max / min forward ran on
         self.in_channels, self.out_channels, self.aggr, self.root_weight = in_channels, out_channels, aggr, root_weight
         self.lin_l = torch.nn.Linear(in_channels[0], out_channels, bias=bias)
         self.lin_r = torch.nn.Linear(in_channels[1], out_channels, bias=False) if root_weight else None
@@ -1881,7 +2078,41 @@ class SAGEConv(torch.nn.Module):
         out = outs[0] if len(outs) == 1 else torch.cat(outs)
         return torch.relu_(out) if relu else out
 
+    def _forward_max(self, x, graph, act=None):
+        """``aggr="max"`` / ``"min"`` on every graph form: the one-kernel layer where it applies, torch ops otherwise."""
+        assert act in (None, "relu"), "act: None or 'relu'"
+        w_l, bias = self.lin_l.weight, self.lin_l.bias
+        w_r = None if self.lin_r is None else self.lin_r.weight
+        x_root = None
+        if not isinstance(graph, LayerGraph):
+            if isinstance(x, LazyRows):
+                x = x.materialize()
+            x, x_dst = (x, x) if isinstance(x, torch.Tensor) else x
+            if isinstance(graph, (tuple, list)) and graph[0].dim() == 1:
+                graph = LayerGraph([HopGraph(graph[0], graph[1], _arange(graph[0].shape[0] - 1, graph[0].device))])
+            else:
+                graph = _single_hop(graph, x_dst.shape[0])[0]
+            if not (x is x_dst or (x_dst.data_ptr() == x.data_ptr() and x_dst.stride() == x.stride())):
+                x_root = x_dst                # (the bipartite form: destination rows of their own)
+        x = _x16_as_rows(x)
+        src, ids, _, _ = _layer_input(self, x, graph, self.in_channels[0])
+        F_, N = self.in_channels[0], self.out_channels
+        wants_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
+                                                  or (torch.is_tensor(x) and x.requires_grad))
+        kernel = (x_root is None and isinstance(src, torch.Tensor) and _kernel_rows_ok(src) and _kernel_rows_ok(w_l)
+                  and (w_r is None or _kernel_rows_ok(w_r)) and sage_max_layer_supported(F_, N, w_r is not None)
+                  and (not wants_grad or _sage_max_wgrad_supported(F_, N, w_r is not None))
+                  and all(h.row_ptr.is_cuda and h.row_ptr.dtype == torch.int32 and h.col.dtype == torch.int32 for h in graph.hops))
+        self.route = "max_kernel" if kernel else "torch"
+        if kernel:
+            args = (src, w_l, w_r, bias, graph, ids, act == "relu", self.aggr == "min")
+            return _SageMaxLayer.apply(*args) if wants_grad else _sage_max_launch(None, *args)
+        xd = x.materialize() if isinstance(x, LazyRows) else x
+        return _sage_max_torch(xd, xd if x_root is None else x_root, w_l, w_r, bias, graph, self.aggr == "min", act == "relu")
+
     def forward(self, x, graph, act=None):
+        if self.aggr in ("max", "min"):
+            return self._forward_max(x, graph, act)
         if isinstance(graph, LayerGraph):
             return self._forward_layer(x, graph, act)
         if isinstance(x, LazyRows):
@@ -4693,6 +4924,10 @@ class HeteroConv(torch.nn.Module):
     def __init__(self, convs, aggr: str = "sum"):
         super().__init__()
         assert aggr in ("sum", "add"), "aggr: sum"
+        for et, c in convs.items():
+            if isinstance(c, SAGEConv) and c.aggr in ("max", "min"):
+                raise NotImplementedError("HeteroConv: the SAGEConv relation %r has aggr=%r; relations take 'mean' or 'sum' (the max / "
+                                          "min aggregator runs in SAGEConv on a homogeneous graph only)" % (et, c.aggr))
         self.edge_types = sorted(convs)
         self.convs = torch.nn.ModuleDict({"__".join(et): convs[et] for et in self.edge_types})
         self._wgamd_derived = {}       # (``_derived``'s store, here from the start: a forward adds no attribute to the module)
@@ -5215,14 +5450,9 @@ class HeteroConv(torch.nn.Module):
                     deg = (r.row_ptr[1:] - r.row_ptr[:-1]).long()
                     row = torch.repeat_interleave(torch.arange(n_f, device=dev), deg)
                     rows = xs[r.col.long()[:r.n_edges]]
-                    if c.aggr in ("mean", "sum", "add"):
-                        agg = agg.index_add(0, row, rows)
-                        if c.aggr == "mean":
-                            agg = agg / deg.clamp(min=1).unsqueeze(1).to(agg.dtype)
-                    elif c.aggr in ("max", "min"):
-                        agg = agg.scatter_reduce(0, row.unsqueeze(1).expand_as(rows), rows, "a" + c.aggr, include_self=False)
-                    else:
-                        raise NotImplementedError("HeteroConv: SAGEConv aggr %r (mean, sum, max, min)" % (c.aggr,))
+                    agg = agg.index_add(0, row, rows)      # (mean | sum | add: max / min relations are refused at construction)
+                    if c.aggr == "mean":
+                        agg = agg / deg.clamp(min=1).unsqueeze(1).to(agg.dtype)
             o = c.lin_l(agg)
             if c.lin_r is not None:
                 o = o + c.lin_r(x[et[2]][head.dst_rows])

@@ -15,7 +15,9 @@ fixed-size buffers with one launch and replays the whole step (forward, loss, ba
 `--node_feat_format float16`, `--dtype bfloat16`): half the HBM for the table; the first layer's kernel reads the 16-bit rows and
 converts them to float32 exactly, the model runs in float32.  (Call groups only: `--per-batch` stages float32 rows.)
 
-    python examples/sage_call_group_training.py [--nodes 200000] [--epochs 3] [--per-batch] [--feat-dtype float16]
+`--aggr max|min` trains the pooling aggregator instead of the mean: one kernel per layer and hop as well (`wholegraph_amd.nn._SageMaxLayer`).
+
+    python examples/sage_call_group_training.py [--nodes 200000] [--epochs 3] [--per-batch] [--feat-dtype float16] [--aggr max]
 """
 import argparse
 import os
@@ -47,6 +49,8 @@ def main():
                                                              "loader.PerBatchStep instead of one per call group")
     ap.add_argument("--feat-dtype", choices=["float32", "float16", "bfloat16"], default="float32",
                     help="dtype the feature table is stored in (16-bit: read as it is by the first layer's kernel)")
+    ap.add_argument("--aggr", choices=["mean", "sum", "max", "min"], default="mean",
+                    help="the layers' aggregator (max / min: the one-kernel layer of csrc/wg_sage_max.hip, float32 features)")
     args = ap.parse_args()
     if args.per_batch and args.feat_dtype != "float32":
         ap.error("--per-batch takes a float32 feature table")
@@ -71,7 +75,7 @@ def main():
                             batch_size=args.batch_size, shuffle=True, local_seeds_per_call=args.group * args.batch_size)
     L = len(args.fanout)
     dims = [args.features] + [128] * (L - 1) + [args.classes]
-    convs = torch.nn.ModuleList(SAGEConv(dims[i], dims[i + 1]) for i in range(L)).to(dev)
+    convs = torch.nn.ModuleList(SAGEConv(dims[i], dims[i + 1], aggr=args.aggr) for i in range(L)).to(dev)
     opt = torch.optim.Adam(convs.parameters(), lr=0.01, capturable=args.per_batch)
     if args.per_batch:
         return train_per_batch(args, loader, convs, opt, community, x, L)

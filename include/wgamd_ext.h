@@ -1179,6 +1179,43 @@ wholememory_error_code_t wgamd_gin_aggregate_f32(const int* row_ptr, const int* 
 wholememory_error_code_t wgamd_segment_sum_f32(const float* x, int64_t ldx, int F, const int64_t* offsets, int64_t n_segments,
                                                float* out, int64_t ldo, void* stream);
 
+/* ---- SAGE layer with the max / min aggregator (csrc/wg_sage_max.hip): torch_geometric.nn.SAGEConv(aggr="max" | "min") ------------
+ *   red[i] = element-wise max (min with WGAMD_SAGE_MAX_MIN) over the edges e of row i of X[col[e]]; an empty row gives 0
+ *   out[i] = act(red[i] @ W_l^T + XS[i] @ W_r^T + b)                   act = ReLU with WGAMD_SAGE_MAX_RELU
+ * X[r] = x[src_ids ? src_ids[r] : r] (INT, INT64 or WGAMD_IDS_BYTE_OFFSETS), XS[i] = X[self_rows[i]] (a zero row where
+ * self_rows[i] < 0).  W_l [N, ldwl] and W_r [N, ldwr] are row-major (torch.nn.Linear.weight) and read as they are: no stacked or
+ * transposed copy.  w_r and self_rows are null together: no root term.  bias nullable.
+ * Ties: the compare is strict and walks the row in CSR order, so the LOWEST edge slot holding the extreme value wins; +-inf
+ * inputs behave as IEEE compares do; NaN inputs are outside the contract.
+ * Domain: wgamd_sage_max_layer_supported(F, N, has_root) (F % 4 == 0, F >= 4, tile width (has_root ? 2 F : F) <= 1024,
+ * 1 <= N <= 256), x / w_l / w_r rows 16-B aligned; the product runs on the exact fp32 matrix pipe (v_mfma_f32_16x16x4_f32).
+ * _train also writes (each nullable, 16-B aligned rows) agg_out [n_rows, F] = red, the same bits as the product's operand (for
+ * wgamd_sage_wgrad_bf16x3 / wgamd_gcn_wgrad_f32), and arg_out [n_rows, F] int32 = the CSR edge slot e (an index into col) the
+ * value of (i, f) came from, -1 for an empty row.
+ * wgamd_sage_max_bwd_src_f32: the gradient of red w.r.t. the input rows, over the hop's transpose (wgamd_csr_transpose_i32:
+ * row_ptr_t [n_src + 1], col_t = destination row and perm = CSR edge slot of every entry):
+ *   gx[j, f] = sum over the entries t of row j of [arg[col_t[t], f] == perm[t]] dagg[col_t[t], f],     dagg = dZ W_l
+ * Every row of gx [n_src, F] is written.  The compare is against the edge slot, not the source id: of two sampled copies of
+ * one edge only the first receives the gradient.  No atomics; rows of more than 64 entries are summed in 64-entry pieces by
+ * all lane groups of a workgroup and the groups' sums added in a fixed order: the same bits from run to run.  F % 4 == 0,
+ * 4 <= F <= 1024, arg / dagg / gx rows 16-B aligned. */
+#define WGAMD_SAGE_MAX_RELU 1
+#define WGAMD_SAGE_MAX_MIN 2
+int wgamd_sage_max_layer_supported(int F, int N, int has_root);
+wholememory_error_code_t wgamd_sage_max_layer_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx,
+                                                  int F, const void* src_ids, wholememory_dtype_t src_ids_dtype,
+                                                  const int64_t* self_rows, const float* w_l, int64_t ldwl, const float* w_r,
+                                                  int64_t ldwr, int N, const float* bias, int flags, float* out, int64_t ldo,
+                                                  void* stream);
+wholememory_error_code_t wgamd_sage_max_layer_f32_train(const int* row_ptr, const int* col, int64_t n_rows, const float* x,
+                                                        int64_t ldx, int F, const void* src_ids, wholememory_dtype_t src_ids_dtype,
+                                                        const int64_t* self_rows, const float* w_l, int64_t ldwl, const float* w_r,
+                                                        int64_t ldwr, int N, const float* bias, int flags, float* out, int64_t ldo,
+                                                        float* agg_out, int64_t ld_agg, int* arg_out, int64_t ld_arg, void* stream);
+wholememory_error_code_t wgamd_sage_max_bwd_src_f32(const int* row_ptr_t, const int* col_t, const int* perm, int64_t n_src,
+                                                    const int* arg, int64_t ld_arg, const float* dagg, int64_t ld_dagg, int F,
+                                                    float* gx, int64_t ldgx, void* stream);
+
 /* ---- Batch norm between the Linears of a GIN layer (csrc/wg_batch_norm.hip, csrc/wg_gin.hip): training mode ----------------------
  * The layer the reference's dist_gin_sg.py trains, GINConv(MLP([in, hidden, hidden])) with PyG's default norm="batch_norm":
  *   z      = agg @ W1^T + b1                                           [n, H]  (agg as in the GIN section above)
