@@ -342,7 +342,7 @@ extern "C" wholememory_error_code_t wgamd_bn_act_linear_f32(const float* z, int6
         !vec_ok(shift))
       throw logic_error("z / w2 / hidden_out rows, scale and shift must be 16-B aligned");
     tail_args a{};
-    a.z = z, a.ldz = ldz, a.n_rows = n_rows, a.H = H, a.H16 = (H + 15) / 16 * 16, a.SH = a.H16 + 4;
+    a.z = z, a.ldz = ldz, a.n_rows = n_rows, a.H = H, tile_geometry(H, a.H16, a.SH);
     a.scale = scale, a.shift = shift, a.w2 = w2, a.ldw2 = ldw2, a.N = N, a.b2 = b2, a.relu_out = relu_out != 0;
     a.out = out, a.ldo = ldo, a.hidden_out = hidden_out, a.ld_hidden = ld_hidden;
     const unsigned tiles = (unsigned)((n_rows + kTileRows - 1) / kTileRows);

@@ -344,8 +344,7 @@ extern "C" wholememory_error_code_t wgamd_gcn_layer_f32_train(const int* row_ptr
       throw logic_error("x / w / agg_out rows must be 16-B aligned");
     gcn_args a = make_args(row_ptr, col, n_rows, x, ldx, F, src_ids, self_rows, edge_weight, dinv_src, dinv_dst, fill, flags);
     a.w = w, a.ldw = ldw, a.N = N, a.bias = bias, a.out = out, a.ldo = ldo, a.agg_out = agg_out, a.ld_agg = ld_agg;
-    a.F16 = (F + 15) / 16 * 16;
-    a.SD  = a.F16 + 4;      // rows 4 banks apart: the 16 rows of a fragment read spread over the 64 banks
+    tile_geometry(F, a.F16, a.SD);
     with_kind(kind, [&](auto k) { launch_layer<decltype(k)::value>(a, static_cast<hipStream_t>(stream)); });
     WG_HIP_CHECK(hipGetLastError());
   });

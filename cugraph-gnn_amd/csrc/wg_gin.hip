@@ -268,8 +268,7 @@ extern "C" wholememory_error_code_t wgamd_gin_layer_f32_train(const int* row_ptr
     a.w2 = w2, a.ldw2 = ldw2, a.N = N, a.b2 = b2, a.relu2 = (flags & WGAMD_GIN_RELU_OUT) != 0;
     a.out = out, a.ldo = ldo, a.agg_out = agg_out, a.ld_agg = ld_agg;
     a.hidden_out = w2 ? hidden_out : nullptr, a.ld_hidden = ld_hidden;
-    a.F16 = (F + 15) / 16 * 16, a.SD = a.F16 + 4;      // rows 4 banks apart, as the GCN tile
-    a.H16 = (H + 15) / 16 * 16, a.SH = a.H16 + 4;
+    tile_geometry(F, a.F16, a.SD), tile_geometry(H, a.H16, a.SH);
     with_kind(kind, [&](auto k) { launch_layer<decltype(k)::value>(a, static_cast<hipStream_t>(stream)); });
     WG_HIP_CHECK(hipGetLastError());
   });
@@ -312,8 +311,7 @@ extern "C" wholememory_error_code_t wgamd_gin_layer_f32_stats(const int* row_ptr
     a.w1 = w1, a.ldw1 = ldw1, a.H = H, a.b1 = b1;
     a.out = z_out, a.ldo = ldz, a.agg_out = agg_out, a.ld_agg = ld_agg;
     a.partials = partials, a.counts = counts, a.tile0 = tile0;
-    a.F16 = (F + 15) / 16 * 16, a.SD = a.F16 + 4;
-    a.H16 = (H + 15) / 16 * 16, a.SH = a.H16 + 4;
+    tile_geometry(F, a.F16, a.SD), tile_geometry(H, a.H16, a.SH);
     with_kind(kind, [&](auto k) { launch_layer<decltype(k)::value, true>(a, static_cast<hipStream_t>(stream)); });
     WG_HIP_CHECK(hipGetLastError());
   });

@@ -2,8 +2,9 @@
 // wg_transformer_hetero.hip, wg_gin.hip, wg_sage_max.hip): an input row read through the layer's node list, the kind of that list, the launch for
 // the kind found at run time, the 16-B row test, the dynamic-LDS launch of a layer kernel, the zeroing of the tile's k padding
 // and the copy of a finished tile to kept rows, the frame of a heterogeneous launch (row_of, hetero_frame and its host check,
-// the relations' row_ptr windows), and phase 2 of every layer kernel — the [16 x K16] LDS tile times wt^T on the exact fp32
-// matrix pipe (v_mfma_f32_16x16x4_f32), bias and ReLU fused.
+// the relations' row_ptr windows), the host's tile geometry (tile_geometry: K16 and the row stride), and phase 2 of every layer
+// kernel — the [16 x K16] LDS tile times wt^T on the exact fp32 matrix pipe (v_mfma_f32_16x16x4_f32), bias and ReLU fused:
+// tile_times, behind tile_times_wt (one weight) and tile_times_two_wt (the weight in two pieces).
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -62,6 +63,14 @@ void launch_tiles(void (*kern)(Args), const Args& a, hipStream_t st)
   const size_t lds = (size_t)kTileRows * a.SD * 4;
   WG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   kern<<<grid, kThreads, lds, st>>>(a);
+}
+
+// The geometry of a layer tile K floats wide: K16 = K rounded up to the MFMA's 16 k, and SD, the floats between two tile rows
+// in LDS = K16 + 4 — rows 4 banks apart: the 16 rows of a fragment read spread over the 64 banks.
+inline void tile_geometry(int K, int& K16, int& SD)
+{
+  K16 = (K + 15) / 16 * 16;
+  SD  = K16 + 4;
 }
 
 // the tile's k padding [K, K16) is zero (all threads of the workgroup)
@@ -151,8 +160,7 @@ inline void fill_hetero_frame(hetero_frame& a, int n_rel, int64_t n_rows, int k_
   a.wt = wt, a.ldw = ldw, a.N = N, a.bias = bias, a.relu = relu ? 1 : 0;
   a.acc_in = acc_in, a.ld_acc = ld_acc, a.out_rows = out_rows, a.out = out, a.ldo = ldo, a.kept = kept, a.ld_kept = ld_kept;
   a.K   = at;
-  a.K16 = (a.K + 15) / 16 * 16;
-  a.SD  = a.K16 + 4;      // rows 4 banks apart: the 16 rows of a fragment read spread over the 64 banks
+  tile_geometry(a.K, a.K16, a.SD);
   WG_REQUIRE_INPUT(ldw >= a.K && ldo >= N && (acc_in == nullptr || ld_acc >= N), "leading dimension too small");
   if (!aligned_rows(wt, ldw)) throw logic_error("wt rows must be 16-B aligned");
   if (kept != nullptr && (ld_kept < a.K || !aligned_rows(kept, ld_kept))) throw logic_error(kept_error);
@@ -169,14 +177,16 @@ __device__ __forceinline__ void load_row_windows(int (&rp)[NR][kTileRows + 1], c
   }
 }
 
-// Phase 2: out[row0 + r, n] = act(sum_k tile[r, k] wt[n, k] + bias[n]) for r < 16 (rows below n_rows), n < N, k < K16.  The
-// tile's columns [K, K16) are zero and wt is read for k < K only.  Wave w owns the 16-column tiles w, w + 4, w + 8, w + 12; a
-// lane reads one float4 of the tile (ds_read_b128) and one float4 of a wt row per 16 k — the four k of a float4 are four MFMA
-// k-steps.  Rows SD floats apart in the tile.  acc_in (nullable, rows ld_acc apart): a running sum added before the activation;
-// out_rows (nullable): row i is written to out[out_rows[i]].
-__device__ __forceinline__ void tile_times_wt(const float* tile, int SD, int K, int K16, const float* wt, int64_t ldw, int N,
-                                              const float* bias, int relu, float* out, int64_t ldo, int64_t row0, int64_t n_rows,
-                                              const float* acc_in = nullptr, int64_t ld_acc = 0, const int64_t* out_rows = nullptr)
+// Phase 2: out[row0 + r, n] = act(sum_k tile[r, k] w[n, k] + bias[n]) for r < 16 (rows below n_rows), n < N, k < K16.  The
+// tile's columns [K, K16) are zero and the weight is read for k < K only: load_w(bv, n, k) puts the float4 w[n, k .. k + 3] into
+// bv, or leaves its zeros (the two wrappers below).  Wave w owns the 16-column tiles w, w + 4, w + 8, w + 12; a lane reads one
+// float4 of the tile (ds_read_b128) and one float4 of a weight row per 16 k — the four k of a float4 are four MFMA k-steps.
+// Rows SD floats apart in the tile.  PLACED: the epilogue takes acc_in (nullable, rows ld_acc apart), a running sum added
+// before the activation, and out_rows (nullable): row i is written to out[out_rows[i]].
+template <bool PLACED, typename LoadW>
+__device__ __forceinline__ void tile_times(const float* tile, int SD, int K16, LoadW load_w, int N, const float* bias, int relu,
+                                           float* out, int64_t ldo, int64_t row0, int64_t n_rows, const float* acc_in = nullptr,
+                                           int64_t ld_acc = 0, const int64_t* out_rows = nullptr)
 {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n_ct = (N + 15) / 16;
@@ -194,7 +204,7 @@ __device__ __forceinline__ void tile_times_wt(const float* tile, int SD, int K, 
       if (ct < n_ct) {
         const int n = ct * 16 + m;
         f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-        if (n < N && k < K) bv = *reinterpret_cast<const f32x4*>(wt + (int64_t)n * ldw + k);
+        if (n < N) load_w(bv, n, k);
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], bv[kk], acc[q], 0, 0, 0);
       }
@@ -211,61 +221,41 @@ __device__ __forceinline__ void tile_times_wt(const float* tile, int SD, int K, 
       const int64_t i = row0 + 4 * g + reg;
       if (i < n_rows) {
         float y = acc[q][reg] + b;
-        if (acc_in) y += acc_in[i * ld_acc + n];
-        if (relu) y = fmaxf(y, 0.f);
-        out[(out_rows ? out_rows[i] : i) * ldo + n] = y;
+        if constexpr (PLACED) {
+          if (acc_in) y += acc_in[i * ld_acc + n];
+          if (relu) y = fmaxf(y, 0.f);
+          out[(out_rows ? out_rows[i] : i) * ldo + n] = y;
+        } else {
+          out[i * ldo + n] = relu ? fmaxf(y, 0.f) : y;
+        }
       }
     }
   }
 }
 
+__device__ __forceinline__ void tile_times_wt(const float* tile, int SD, int K, int K16, const float* wt, int64_t ldw, int N,
+                                              const float* bias, int relu, float* out, int64_t ldo, int64_t row0, int64_t n_rows,
+                                              const float* acc_in = nullptr, int64_t ld_acc = 0, const int64_t* out_rows = nullptr)
+{
+  const auto one_wt = [=](f32x4& bv, int n, int k) {
+    if (k < K) bv = *reinterpret_cast<const f32x4*>(wt + (int64_t)n * ldw + k);
+  };
+  tile_times<true>(tile, SD, K16, one_wt, N, bias, relu, out, ldo, row0, n_rows, acc_in, ld_acc, out_rows);
+}
+
 // Phase 2 with the weight in two pieces, each in its torch.nn.Linear layout: column k of the tile meets wa[n, k] for k < Ka
 // and wb[n, k - Ka] for Ka <= k < K (wb is not read when K == Ka); Ka a multiple of 4, so no float4 of k straddles the two.
-// Otherwise tile_times_wt: the same ownership of column tiles, the same fragment reads, bias and ReLU fused, one store.  No
-// stacked or transposed copy of the two weights exists: what a training step under HIP-graph capture would have to rebuild
+// No stacked or transposed copy of the two weights exists: what a training step under HIP-graph capture would have to rebuild
 // on every replay.
 __device__ __forceinline__ void tile_times_two_wt(const float* tile, int SD, int Ka, int K, int K16, const float* wa, int64_t ldwa,
                                                   const float* wb, int64_t ldwb, int N, const float* bias, int relu, float* out,
                                                   int64_t ldo, int64_t row0, int64_t n_rows)
 {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n_ct = (N + 15) / 16;
-  if (wave >= n_ct) return;
-  const int m = lane & 15, g = lane >> 4;
-  f32x4 acc[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int kb = 0; kb < K16; kb += 16) {
-    const int k = kb + 4 * g;
-    const f32x4 av = *reinterpret_cast<const f32x4*>(tile + m * SD + k);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int ct = wave + 4 * q;
-      if (ct < n_ct) {
-        const int n = ct * 16 + m;
-        f32x4 bv = {0.f, 0.f, 0.f, 0.f};
-        if (n < N && k < Ka) bv = *reinterpret_cast<const f32x4*>(wa + (int64_t)n * ldwa + k);
-        else if (n < N && k < K) bv = *reinterpret_cast<const f32x4*>(wb + (int64_t)n * ldwb + (k - Ka));
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[kk], bv[kk], acc[q], 0, 0, 0);
-      }
-    }
-  }
-  // C/D map of the 16x16 MFMA: col = lane & 15, row = 4 (lane >> 4) + reg
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int n = (wave + 4 * q) * 16 + m;
-    if (wave + 4 * q >= n_ct || n >= N) continue;
-    const float b = bias ? bias[n] : 0.f;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg) {
-      const int64_t i = row0 + 4 * g + reg;
-      if (i < n_rows) {
-        const float y = acc[q][reg] + b;
-        out[i * ldo + n] = relu ? fmaxf(y, 0.f) : y;
-      }
-    }
-  }
+  const auto two_wt = [=](f32x4& bv, int n, int k) {
+    if (k < Ka) bv = *reinterpret_cast<const f32x4*>(wa + (int64_t)n * ldwa + k);
+    else if (k < K) bv = *reinterpret_cast<const f32x4*>(wb + (int64_t)n * ldwb + (k - Ka));
+  };
+  tile_times<false>(tile, SD, K16, two_wt, N, bias, relu, out, ldo, row0, n_rows);
 }
 
 }  // namespace wgamd

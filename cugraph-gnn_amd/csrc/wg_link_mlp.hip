@@ -259,8 +259,7 @@ wholememory_error_code_t wgamd_pair_mlp_forward_f32(const float* x_src, int64_t 
     a.w1 = w1, a.ldw1 = ldw1, a.H = hidden, a.b1 = b1, a.w2 = w2, a.b2 = b2;
     a.label = label, a.weight = pair_weight, a.score = score, a.coef = coef, a.state = static_cast<float*>(state);
     a.loss_out = loss_out, a.mean = mean, a.hidden_out = hidden_out, a.ld_hidden = ld_hidden;
-    a.K = K, a.K16 = (K + 15) / 16 * 16, a.SD = a.K16 + 4;      // rows 4 banks apart, as every layer tile
-    a.H16 = (hidden + 15) / 16 * 16, a.SH = a.H16 + 4;
+    a.K = K, tile_geometry(K, a.K16, a.SD), tile_geometry(hidden, a.H16, a.SH);
     const size_t lds = (size_t)kTileRows * (a.SD + a.SH) * 4;   // at most 16 x (1028 + 260) floats = 82 KB: above the 64 KB default
     auto kern = bce ? pair_mlp_fwd_kernel<true> : pair_mlp_fwd_kernel<false>;
     WG_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -291,8 +291,7 @@ extern "C" wholememory_error_code_t wgamd_rgcn_layer_f32(const int* row_ptr, con
     a.self_rows = self_rows, a.rel = rel, a.coef = coef, a.comp = comp, a.B = B, a.has_root = has_root ? 1 : 0;
     a.wt = wt, a.ldw = ldw, a.N = N, a.bias = bias, a.relu = relu ? 1 : 0, a.out = out, a.ldo = ldo;
     a.K   = (B + a.has_root) * F;
-    a.K16 = (a.K + 15) / 16 * 16;
-    a.SD  = a.K16 + 4;      // rows 4 banks apart: the 16 rows of a fragment read spread over the 64 banks
+    tile_geometry(a.K, a.K16, a.SD);
     a.Q   = a.K / 4;
     a.P   = 1;
     while (a.P < kTileRows && 2 * a.P * a.Q <= kThreads) a.P *= 2;

@@ -375,8 +375,7 @@ extern "C" wholememory_error_code_t wgamd_row_linear_f32(const void* x, wholemem
     a.relu = relu ? 1 : 0, a.norm = norm, a.gamma = norm == WGAMD_ROW_LINEAR_NORM_LAYER ? gamma : nullptr;
     a.beta = norm == WGAMD_ROW_LINEAR_NORM_LAYER ? beta : nullptr, a.eps = eps;
     a.add = add, a.ld_add = ld_add, a.out = out, a.ldo = ldo, a.kept_x = kept_x, a.ld_kx = ld_kx, a.kept_y = kept_y, a.ld_ky = ld_ky;
-    a.K16 = (K + 15) / 16 * 16, a.SD = a.K16 + 4;      // rows 4 banks apart, as the GCN tile
-    a.N16 = (N + 15) / 16 * 16, a.SN = a.N16 + 4;
+    tile_geometry(K, a.K16, a.SD), tile_geometry(N, a.N16, a.SN);
     a.use_b = norm != WGAMD_ROW_LINEAR_NORM_NONE || add != nullptr || kept_y != nullptr;
     const int kind = ids == nullptr ? 0 : ids_dtype == WHOLEMEMORY_DT_INT ? 1 : 2;
     auto st = static_cast<hipStream_t>(stream);

@@ -268,8 +268,7 @@ extern "C" wholememory_error_code_t wgamd_sage_max_layer_f32_train(const int* ro
     a.out = out, a.ldo = ldo, a.agg_out = agg_out, a.ld_agg = ld_agg, a.arg_out = arg_out, a.ld_arg = ld_arg;
     a.lg_shift = lane_group_shift(F);
     a.K   = has_root ? 2 * F : F;
-    a.K16 = (a.K + 15) / 16 * 16;
-    a.SD  = a.K16 + 4;      // rows 4 banks apart, as the GCN tile
+    tile_geometry(a.K, a.K16, a.SD);
     auto st = static_cast<hipStream_t>(stream);
     with_kind(kind, [&](auto k) {
       if (flags & WGAMD_SAGE_MAX_MIN) launch_layer<decltype(k)::value, true>(a, st);

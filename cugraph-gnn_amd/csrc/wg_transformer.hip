@@ -255,8 +255,7 @@ extern "C" wholememory_error_code_t wgamd_transformer_layer_f32(
     a.alpha = alpha, a.a_save = a_save;
     a.W4  = block_width(F_src, D);
     a.K   = H * a.W4 + F_dst;
-    a.K16 = (a.K + 15) / 16 * 16;
-    a.SD  = a.K16 + 4;      // rows 4 banks apart: the 16 rows of a fragment read spread over the 64 banks
+    tile_geometry(a.K, a.K16, a.SD);
     WG_REQUIRE_INPUT(kind == 3 || ldx >= F_src, "leading dimension too small");
     WG_REQUIRE_INPUT(F_dst == 0 || (x_dst_ids && kind == 3) || ldx_dst >= F_dst, "leading dimension too small");
     WG_REQUIRE_INPUT(ldwt >= a.K, "leading dimension too small");

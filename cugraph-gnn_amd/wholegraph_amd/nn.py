@@ -20,8 +20,11 @@ Shared by the one-kernel layers, so that they cannot drift apart: ``_hop_args`` 
 hop, with their checks), ``_out_rows`` (a launch's output: the caller's or a fresh one), ``_hops`` / ``_sum_over_hops`` (a layer
 graph's hops with their row and edge slices; the sum of the hops' input gradients), ``_layer_input`` / ``_kernel_rows_ok`` (a
 tensor or ``LazyRows`` input as the kernels read it), ``_padded_wt`` / ``_pad_cols`` (the operands of an input gradient run as
-the layer kernel over ``HopGraph.transposed``), ``_dense_wgrad`` (``gcn_wgrad`` per hop: dW, db of a dense product), and
-``_released`` (the RuntimeError of a second backward through a layer whose kept tensors the first one released).
+the layer kernel over ``HopGraph.transposed``), ``_dense_wgrad`` (``gcn_wgrad`` per hop: dW, db of a dense product),
+``_released`` (the RuntimeError of a second backward through a layer whose kept tensors the first one released), ``_dz`` /
+``_grad_rows`` (the upstream gradient as rows a kernel reads, masked by the ReLU once), ``_sage_backward`` (the hop loop of both
+SAGE backward passes), ``_zero_grads``, ``_grads_from_torch`` (a double backward out of torch ops), ``_needs_grad`` (does a
+forward call build an autograd node) and ``_round4``.
 
 Shared by ``GATConv`` and the routes of ``HeteroConv`` over a call group: ``_table_through_ids`` (a ``LazyRows`` input the kernels
 may read in place through its node list) with ``_terms_by_id`` (whose attention terms are then the table's rows') and
@@ -762,7 +765,7 @@ class _PairMlp(torch.autograd.Function):
             w1k = w1k.contiguous()
         w2k = w2.detach().reshape(-1).contiguous()
         b1k = None if b1 is None else b1.detach().contiguous()
-        hidden = torch.empty((P, (H + 3) // 4 * 4), dtype=torch.float32, device=dev) if keep else None
+        hidden = torch.empty((P, _round4(H)), dtype=torch.float32, device=dev) if keep else None
         score = coef = state = loss = None
         if bce:
             key = (dev.index, get_stream().value)
@@ -1586,6 +1589,87 @@ def _sum_over_hops(lg: LayerGraph, zeros_shape, device, per_hop):
     return torch.zeros(zeros_shape, dtype=torch.float32, device=device) if total is None else total
 
 
+def _round4(n: int) -> int:
+    """``n`` rounded up to a multiple of 4: the float4 columns of a kernel operand."""
+    return (n + 3) // 4 * 4
+
+
+def _needs_grad(params, *inputs) -> bool:
+    """Whether a forward call needs an autograd node: autograd is on and one of ``params`` or of the tensors among ``inputs``
+    (a ``LazyRows`` never gets a gradient) requires one."""
+    return torch.is_grad_enabled() and (any(p.requires_grad for p in params)
+                                        or any(torch.is_tensor(x) and x.requires_grad for x in inputs))
+
+
+def _dz(g, out, relu: bool, now: bool = True, views: bool = False):
+    """``(gz, act)`` of a layer's upstream gradient ``g``: ``gz`` = ``g`` as float32 rows with unit column stride, masked to
+    ``dZ = g * (out > 0)`` once, for every gradient that reads it, when the layer ends in a ReLU and ``now``; ``act`` = ``out``
+    when the mask is left to the weight-gradient kernel (a ReLU layer, not ``now``), else None.  ``views``: everything that
+    reads ``gz`` takes rows any distance apart — ``sage_wgrad`` and ``gcn_wgrad`` pass the row stride of ``grad_out`` to
+    their kernels, ``_sage_dx`` and ``_sage_max_dx`` read it through library GEMMs and torch ops — so a float32 ``g`` with unit
+    column stride stays the view it is.  Otherwise ``g`` is made contiguous, for readers that reshape it or hand it to a
+    kernel as 16-B aligned rows (both are no-ops on a contiguous float32 ``g``)."""
+    if not views or g.stride(1) != 1 or g.dtype != torch.float32:
+        g = g.contiguous().float()
+    if relu and now:
+        return torch.ops.aten.threshold_backward(g, out, 0), None
+    return g, (out if relu else None)
+
+
+def _zero_grads(*grads):
+    """Zeros in place in every tensor of ``grads``: the parameter gradients of a layer graph none of whose hops has rows, where
+    no accumulating launch wrote them."""
+    for t in grads:
+        if t is not None:
+            t.zero_()
+
+
+def _sage_backward(graph: LayerGraph, kept, g, out, relu: bool, src, w_l, w_r, has_bias: bool, want_w: bool, need_x: bool,
+                   operand, dx):
+    """``(gx, gwl, gwr, gb)`` of a SAGE layer (``_SageLayer``, ``_SageMaxLayer``) over the hops of ``graph``: per hop with rows
+    the weight-gradient launch — ``sage_wgrad``, ``gcn_wgrad`` without a root weight; accumulating from the second hop on; the
+    ReLU mask folded in when the input needs no gradient; none at all without ``want_w`` — and RIGHT AFTER it (not
+    ``_sum_over_hops``: x may need no gradient) that hop's input gradient ``dx(hop, dZ rows, kept[k])``, summed in hop order.
+    ``operand(hop, kept[k])`` = ``(agg, x, self_rows, src_ids)``, what the weight-gradient kernel reads.  No hop with rows:
+    zeros."""
+    g, act = _dz(g, out, relu, now=need_x, views=True)
+    gwl = torch.empty_like(w_l, memory_format=torch.contiguous_format) if want_w else None
+    gwr = torch.empty_like(w_r, memory_format=torch.contiguous_format) if want_w and w_r is not None else None
+    gb = torch.empty(w_l.shape[0], dtype=torch.float32, device=g.device) if want_w and has_bias else None
+    gx, first = None, True
+    for (h, rows, _), k in zip(_hops(graph), kept):
+        if h.n_rows > 0:
+            act_h = None if act is None else act[rows]
+            if want_w and w_r is not None:
+                agg, xs, self_rows, xs_ids = operand(h, k)
+                sage_wgrad(agg, xs, self_rows, g[rows], gwl, gwr, gb, act_h, src_ids=xs_ids, accumulate=not first)
+            elif want_w:
+                gcn_wgrad(operand(h, k)[0], g[rows], gwl, gb, act_h, accumulate=not first)
+            first = False
+            if need_x:
+                gh = dx(h, g[rows], k)
+                gx = gh if gx is None else gx.add_(gh)
+    if first:
+        _zero_grads(gwl, gwr, gb)
+    if need_x and gx is None:
+        gx = torch.zeros_like(src)
+    return gx, gwl, gwr, gb
+
+
+def _grads_from_torch(make_y, ins, g, res):
+    """A double backward out of torch ops: ``res``, a list of the backward's return slots, with the slots of
+    ``ins = [(slot, tensor), ...]`` whose tensor is there and requires a gradient set to the gradient of ``make_y()`` — the
+    layer's formula built under ``torch.enable_grad()`` from the saved inputs — against ``g``, itself differentiable
+    (``create_graph=True``)."""
+    ins = [(i, t) for i, t in ins if t is not None and t.requires_grad]
+    if ins and g is not None:
+        with torch.enable_grad():
+            grads = torch.autograd.grad(make_y(), [t for _, t in ins], g, create_graph=True, allow_unused=True)
+        for (i, _), gr in zip(ins, grads):
+            res[i] = gr
+    return res
+
+
 def _edge_dst(row_ptr, n_edges: int, first: int = 0):
     """int64 [n_edges]: the destination row of every CSR edge, rows numbered from ``first``."""
     n = row_ptr.shape[0] - 1
@@ -1593,9 +1677,10 @@ def _edge_dst(row_ptr, n_edges: int, first: int = 0):
                                    output_size=int(n_edges))
 
 
-def _kernel_rows_ok(t) -> bool:
-    """``t`` [rows, F] is what the layer kernels read in place: float32 on the device, unit column stride, 16-B aligned rows."""
-    return (t.dtype == torch.float32 and t.is_cuda and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0)
+def _kernel_rows_ok(t, dtypes=(torch.float32,), align: int = 16) -> bool:
+    """``t`` [rows, F] is what the layer kernels read in place: float32 on the device, unit column stride, 16-B aligned rows
+    (a 16-bit table where a kernel reads one: ``dtypes=_X16`` and 8-B aligned rows, ``align=8``)."""
+    return (t.dtype in dtypes and t.is_cuda and t.stride(1) == 1 and t.stride(0) % 4 == 0 and t.data_ptr() % align == 0)
 
 
 def _table_through_ids(x):
@@ -1679,7 +1764,7 @@ def _sage_dx(hop: HopGraph, gz: torch.Tensor, w_l: torch.Tensor, w_r: torch.Tens
     that kernel does not take go through the segmented transposed SpMM + library GEMMs."""
     n, N = gz.shape
     F_ = w_l.shape[1]
-    Nq = (N + 3) // 4 * 4
+    Nq = _round4(N)
     # A SMALL hop (one mini-batch: PerBatchStep) goes through the dense products + the segmented transposed SpMM instead: in the
     # transposed hop a popular source is a row of hundreds of entries, which one lane group of the layer kernel walks as a
     # chain of dependent loads — hidden inside a call group's millisecond launch, 250 us of a mini-batch's step when exposed
@@ -1756,42 +1841,24 @@ class _SageLayer(torch.autograd.Function):
     def backward(ctx, g):
         _released(ctx.aggs, "SAGEConv", "aggregates", "; run the forward again, or sum the losses before calling backward")
         src, w_l, w_r, out = ctx.saved_tensors if len(ctx.saved_tensors) == 4 else (ctx.src_obj,) + tuple(ctx.saved_tensors)
-        graph, ids, relu, mean = ctx.graph, ctx.ids, ctx.relu, ctx.mean
-        N, F_ = w_l.shape
+        graph, ids, mean = ctx.graph, ctx.ids, ctx.mean
+        F_ = w_l.shape[1]
         need_x = ctx.needs_input_grad[0]
-        if g.stride(1) != 1 or g.dtype != torch.float32:
-            g = g.contiguous().float()
-        act = out if relu else None
-        if relu and need_x:
-            g, act = torch.ops.aten.threshold_backward(g, out, 0), None      # dZ once, read by both gradients
-        gwl, gwr = torch.empty_like(w_l, memory_format=torch.contiguous_format), torch.empty_like(w_r, memory_format=torch.contiguous_format)
-        gb = torch.empty(N, dtype=torch.float32, device=g.device) if ctx.has_bias else None
         w_bwd = ctx.conv._weight_bwd() if need_x and any(h.n_rows > _SAGE_DX_SMALL_ROWS for h in graph.hops) else None
-        # (not _sum_over_hops: a hop's weight gradient launch goes right before its input gradient, and x may need none)
-        gx, first = None, True
-        for (h, rows, _), agg in zip(_hops(graph), ctx.aggs):
-            if h.n_rows > 0:
-                xs, self_rows, xs_ids = src, h.self_rows, ids
-                if src.dtype in _X16:
-                    # a 16-bit table: the weight-gradient kernel reads float32 rows — the hop's self rows, one converting gather
-                    from .tensor import local_gather
-                    xs = local_gather(src, h.self_rows if ids is None else ids[h.self_rows],
-                                      torch.empty((h.n_rows, F_), dtype=torch.float32, device=g.device))
-                    self_rows, xs_ids = _arange(h.n_rows, g.device), None
-                sage_wgrad(agg, xs, self_rows, g[rows], gwl, gwr, gb, None if act is None else act[rows], src_ids=xs_ids,
-                           accumulate=not first)
-                first = False
-                if need_x:
-                    gh = _sage_dx(h, g[rows], w_l, w_r, w_bwd, mean, src.shape[0])
-                    gx = gh if gx is None else gx.add_(gh)
-        if first:
-            gwl.zero_(), gwr.zero_()
-            if gb is not None:
-                gb.zero_()
-        if need_x and gx is None:
-            gx = torch.zeros_like(src)
+
+        def operand(h, agg):
+            if src.dtype not in _X16:
+                return agg, src, h.self_rows, ids
+            # a 16-bit table: the weight-gradient kernel reads float32 rows — the hop's self rows, one converting gather
+            from .tensor import local_gather
+            xs = local_gather(src, h.self_rows if ids is None else ids[h.self_rows],
+                              torch.empty((h.n_rows, F_), dtype=torch.float32, device=g.device))
+            return agg, xs, _arange(h.n_rows, g.device), None
+
+        grads = _sage_backward(graph, ctx.aggs, g, out, ctx.relu, src, w_l, w_r, ctx.has_bias, True, need_x, operand,
+                               lambda h, gz, _: _sage_dx(h, gz, w_l, w_r, w_bwd, mean, src.shape[0]))
         ctx.aggs = None
-        return gx, gwl, gwr, gb, None, None, None, None, None
+        return grads + (None, None, None, None, None)
 
 
 SAGE_MAX_RELU, SAGE_MAX_MIN = 1, 2     # WGAMD_SAGE_MAX_* (include/wgamd_ext.h)
@@ -1923,52 +1990,23 @@ class _SageMaxLayer(torch.autograd.Function):
             return _sage_max_double_backward(ctx, g)
         _released(ctx.kept, "SAGEConv", "reduced rows and edge slots", "; run the forward again, or sum the losses before calling backward")
         src, w_l, w_r, bias, out = ctx.saved_tensors
-        graph, ids, relu, need = ctx.graph, ctx.ids, ctx.relu, ctx.needs_input_grad
-        N = w_l.shape[0]
-        if g.stride(1) != 1 or g.dtype != torch.float32:
-            g = g.contiguous().float()
-        act = out if relu else None
-        if relu and need[0]:
-            g, act = torch.ops.aten.threshold_backward(g, out, 0), None      # dZ once, read by both gradients
-        want_w = any(need[1:4])
-        gwl = torch.empty_like(w_l, memory_format=torch.contiguous_format) if want_w else None
-        gwr = torch.empty_like(w_r, memory_format=torch.contiguous_format) if want_w and w_r is not None else None
-        gb = torch.empty(N, dtype=torch.float32, device=g.device) if want_w and bias is not None else None
-        gx, first = None, True
-        for (h, rows, _), k in zip(_hops(graph), ctx.kept):
-            if h.n_rows > 0:
-                agg, arg = k
-                act_h = None if act is None else act[rows]
-                if want_w and w_r is not None:
-                    sage_wgrad(agg, src, h.self_rows, g[rows], gwl, gwr, gb, act_h, src_ids=ids, accumulate=not first)
-                elif want_w:
-                    gcn_wgrad(agg, g[rows], gwl, gb, act_h, accumulate=not first)
-                first = False
-                if need[0]:
-                    gh = _sage_max_dx(h, g[rows], arg, w_l, w_r, src.shape[0])
-                    gx = gh if gx is None else gx.add_(gh)
-        if first:
-            for t in (gwl, gwr, gb):
-                if t is not None:
-                    t.zero_()
-        if need[0] and gx is None:
-            gx = torch.zeros_like(src)
+        ids, need = ctx.ids, ctx.needs_input_grad
+        grads = _sage_backward(ctx.graph, ctx.kept, g, out, ctx.relu, src, w_l, w_r, bias is not None, any(need[1:4]), need[0],
+                               lambda h, k: (k[0], src, h.self_rows, ids),
+                               lambda h, gz, k: _sage_max_dx(h, gz, k[1], w_l, w_r, src.shape[0]))
         ctx.kept = None
-        return gx, gwl, gwr, gb, None, None, None, None
+        return grads + (None, None, None, None)
 
 
 def _sage_max_double_backward(ctx, g):
     """The gradients as differentiable torch expressions of the saved inputs and ``g``."""
     src, w_l, w_r, bias, _ = ctx.saved_tensors
-    res = [None] * 8
-    with torch.enable_grad():
+
+    def make_y():
         xd = src if ctx.ids is None else src[ctx.ids.long()]
-        y = _sage_max_torch(xd, xd, w_l, w_r, bias, ctx.graph, ctx.minimum, ctx.relu)
-        ins = [(i, t) for i, t in enumerate((src, w_l, w_r, bias)) if t is not None and t.requires_grad and ctx.needs_input_grad[i]]
-        if ins:
-            for (i, _), gr in zip(ins, torch.autograd.grad(y, [t for _, t in ins], g, create_graph=True, allow_unused=True)):
-                res[i] = gr
-    return tuple(res)
+        return _sage_max_torch(xd, xd, w_l, w_r, bias, ctx.graph, ctx.minimum, ctx.relu)
+    ins = [(i, t) for i, t in enumerate((src, w_l, w_r, bias)) if ctx.needs_input_grad[i]]
+    return tuple(_grads_from_torch(make_y, ins, g, [None] * 8))
 
 
 def _sage_max_wgrad_supported(F_: int, N: int, has_root: bool) -> bool:
@@ -2021,7 +2059,7 @@ class SAGEConv(torch.nn.Module):
         the input gradient over the transposed hop (``_sage_dx``); None when that kernel does not take the shape."""
         wl, wr = self.lin_l.weight, self.lin_r.weight
         N, F_ = wl.shape
-        Nq = (N + 3) // 4 * 4
+        Nq = _round4(N)
         if not sage_layer_fused_supported(Nq, F_):
             return None
 
@@ -2043,9 +2081,8 @@ class SAGEConv(torch.nn.Module):
         relu = act == "relu"
         assert act in (None, "relu"), "act: None or 'relu'"
         x16 = lazy and src.dtype in _X16
-        if x16 and not (self.lin_r is not None and self.aggr in ("mean", "sum") and isinstance(src, torch.Tensor) and src.is_cuda
-                        and src.stride(1) == 1 and src.stride(0) % 4 == 0 and src.data_ptr() % 8 == 0
-                        and sage_layer_fused_supported(F_, N) and _FUSED_PRECISION == "bf16x3"
+        if x16 and not (self.lin_r is not None and self.aggr in ("mean", "sum") and isinstance(src, torch.Tensor)
+                        and _kernel_rows_ok(src, _X16, 8) and sage_layer_fused_supported(F_, N) and _FUSED_PRECISION == "bf16x3"
                         and L.lib().wgamd_sage_layer_x16_supported(F_, _padded_width(N), torch_dtype_to_wm(src.dtype))):
             # a 16-bit table on a route that is not the bf16x3 layer kernel's: float32 rows from ONE converting gather, then
             # whatever a float32 tensor input takes
@@ -2057,13 +2094,12 @@ class SAGEConv(torch.nn.Module):
         if one_kernel and not sage_layer_train_supported(F_, N):
             # (a shape only the fp32-MFMA layer kernel takes has no backward kernels: under autograd it runs as aggregation
             #  kernel + library GEMM, whose autograd pieces exist for every shape)
-            one_kernel = not (torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
-                                                           or (not lazy and x.requires_grad)))
+            one_kernel = not _needs_grad(self.parameters(), x)
         if one_kernel:
             args = (src, self.lin_l.weight, self.lin_r.weight, self.lin_l.bias, self, graph, x.ids if lazy else None, relu,
                     self.aggr == "mean")
-            if not (torch.is_grad_enabled() and (self.lin_l.weight.requires_grad or self.lin_r.weight.requires_grad
-                                                 or (not lazy and x.requires_grad))):
+            # (the two weights, not the bias: a call in which the bias alone requires a gradient has never built a node)
+            if not _needs_grad((self.lin_l.weight, self.lin_r.weight), x):
                 return _sage_layer_launch(None, *args)       # same launches; no autograd node to build (~10 us per call)
             return _SageLayer.apply(*args)
         # aggregation kernel(s) + library GEMM: every hop's [mean | self] rows, then lin_l / lin_r as torch modules
@@ -2097,8 +2133,7 @@ class SAGEConv(torch.nn.Module):
         x = _x16_as_rows(x)
         src, ids, _, _ = _layer_input(self, x, graph, self.in_channels[0])
         F_, N = self.in_channels[0], self.out_channels
-        wants_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
-                                                  or (torch.is_tensor(x) and x.requires_grad))
+        wants_grad = _needs_grad(self.parameters(), x)
         kernel = (x_root is None and isinstance(src, torch.Tensor) and _kernel_rows_ok(src) and _kernel_rows_ok(w_l)
                   and (w_r is None or _kernel_rows_ok(w_r)) and sage_max_layer_supported(F_, N, w_r is not None)
                   and (not wants_grad or _sage_max_wgrad_supported(F_, N, w_r is not None))
@@ -2338,9 +2373,7 @@ def _dense_wgrad(lg: LayerGraph, a, gz, w, want_b: bool, act):
             gcn_wgrad(a[rows], gz[rows], gw, gb, None if act is None else act[rows], accumulate=not first)
             first = False
     if first:
-        gw.zero_()
-        if gb is not None:
-            gb.zero_()
+        _zero_grads(gw, gb)
     return gw, gb
 
 
@@ -2401,17 +2434,14 @@ class _GcnLayer(torch.autograd.Function):
         N, F_ = weight.shape
         graph, n_src, dev = ctx.graph, ctx.n_src, g.device
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
-        g = g.contiguous().float()
-        act = out if ctx.relu else None
-        if ctx.relu and need_x:
-            g, act = torch.ops.aten.threshold_backward(g, out, 0), None      # dZ once, read by both gradients
+        g, act = _dz(g, out, ctx.relu, now=need_x)
         gx = gw = gb = None
         if need_w:
             gw, gb = _dense_wgrad(graph, agg, g, weight, need_b, act)
         elif need_b:      # (no aggregate was kept: the hops' column sums in torch)
             gb = _sum_over_hops(graph, (N,), dev, lambda h, rows, _, k: (g[rows] if act is None else g[rows] * (act[rows] > 0)).sum(0))
         if need_x:
-            Nq = (N + 3) // 4 * 4
+            Nq = _round4(N)
             w_bwd, gq, ew = _padded_wt(weight, Nq), _pad_cols(g, Nq), ctx.edge_weights
             gx = _sum_over_hops(graph, (n_src, F_), dev, lambda h, rows, _, k: _gcn_input_grad(
                 h, gq[rows], n_src, ctx.dinv_in, ctx.conv, None if ew is None else ew[k], weight=w_bwd))
@@ -2669,9 +2699,7 @@ class _RgcnLayer(torch.autograd.Function):
         B, F_, N = weight.shape
         R, dev = ctx.R, g.device
         need_x, need_w, need_c, need_r, need_b = ctx.needs_input_grad[:5]
-        gz = g.contiguous().float()
-        if ctx.relu:
-            gz = torch.ops.aten.threshold_backward(gz, out, 0)
+        gz, _ = _dz(g, out, ctx.relu)
         gx = gw = gc = gr = gb = None
         if need_w or need_c or need_r:
             ps, pd, pc, sg = [], [], [], []
@@ -2698,7 +2726,7 @@ class _RgcnLayer(torch.autograd.Function):
         if need_b:
             gb = gz.sum(0)
         if need_x:
-            Nq = (N + 3) // 4 * 4
+            Nq = _round4(N)
             w_bwd, gq, coefs, n_src = _rgcn_stacked(weight, root, Nq), _pad_cols(gz, Nq), ctx.coefs, ctx.n_src
             c = None if comp is None else comp.detach().contiguous()
 
@@ -2826,7 +2854,7 @@ class RGCNConv(torch.nn.Module):
         coefs = self._coefs(lg, edge_type)
         has_root, B = self.root is not None, self._b_eff
         need_x = torch.is_grad_enabled() and ids is None and x.requires_grad
-        Nq = (N + 3) // 4 * 4
+        Nq = _round4(N)
         if (rgcn_layer_supported(F_, N, B, has_root) and (not need_x or rgcn_layer_supported(Nq, F_, B, has_root))
                 and _kernel_rows_ok(src)):
             return _RgcnLayer.apply(src, self.weight, self.comp, self.root, self.bias, self, lg, coefs, ids, relu, n_src)
@@ -2867,7 +2895,7 @@ def transformer_layer_supported(F_src: int, F_dst: int, D: int, H: int, N: int) 
 
 def transformer_block_width(F_src: int, D: int) -> int:
     """Width of one head's block of the layer's rows A: ``[x_j | a_ij | 1]`` padded to a multiple of 4."""
-    return (F_src + D + 1 + 3) // 4 * 4
+    return _round4(F_src + D + 1)
 
 
 def transformer_folds(conv):
@@ -3018,9 +3046,7 @@ class _TconvLayer(torch.autograd.Function):
         gx = gxd = gu = gw = gea = gwt = gb = None
         if g is None:
             g = torch.zeros_like(out)
-        gz = g.contiguous().float()
-        if ctx.relu:
-            gz = torch.ops.aten.threshold_backward(gz, out, 0)
+        gz, _ = _dz(g, out, ctx.relu)
         if need_wt:
             gwt = gz.t() @ A
         if need_b:
@@ -3392,11 +3418,10 @@ class _GinLayer(torch.autograd.Function):
         out = torch.empty((n, w2.shape[0] if two else H), dtype=torch.float32, device=dev)
         agg = torch.empty((n, F_), dtype=torch.float32, device=dev) if keep else None
         hidden = torch.empty((n, H), dtype=torch.float32, device=dev) if keep and two else None
-        det = lambda t: None if t is None else t.detach()      # noqa: E731
         for h, rows, _ in _hops(graph):
             if h.n_rows > 0:
-                self_rows, xd = _gin_hop_self(h, rows, det(x_dst), no_root)
-                gin_layer_forward(h.row_ptr, h.col, src, self_rows, det(w1), det(b1), det(w2), det(b2), eps=det(eps),
+                self_rows, xd = _gin_hop_self(h, rows, _detached(x_dst), no_root)
+                gin_layer_forward(h.row_ptr, h.col, src, self_rows, *_detached((w1, b1, w2, b2)), eps=_detached(eps),
                                   relu_hidden=relu_hidden, relu_out=relu_out, src_ids=ids, x_dst=xd, out=out[rows],
                                   agg_out=None if agg is None else agg[rows], hidden_out=None if hidden is None else hidden[rows])
         if keep:
@@ -3417,28 +3442,24 @@ class _GinLayer(torch.autograd.Function):
         H, F_ = w1.shape
         dev = g.device
         graph = ctx.graph
-        g = g.contiguous().float()
         gw1 = gb1 = gw2 = gb2 = None
         some = any(h.n_rows > 0 for h in graph.hops)
+        lower = need_x or need_xd or need_eps      # (then dZ1 is made once, read by every gradient below)
         if w2 is not None:
-            if relu_out:
-                g = torch.ops.aten.threshold_backward(g, out, 0)
+            g, _ = _dz(g, out, relu_out)
             if need_w2 or need_b2:      # (a bias gradient alone: the product's launches all the same, dW dropped)
                 gw2, gb2 = _dense_wgrad(graph, hidden, g, w2, need_b2, None)
                 gw2 = gw2 if need_w2 else None
-            g1, act1 = g @ w2.detach(), hidden if relu_hidden else None          # dHidden: one library GEMM
+            g1, act1 = _dz(g @ w2.detach(), hidden, relu_hidden, now=lower)          # dHidden: one library GEMM
         else:
-            g1, act1 = g, out if relu_hidden else None
-        lower = need_x or need_xd or need_eps
-        if act1 is not None and lower:
-            g1, act1 = torch.ops.aten.threshold_backward(g1, act1, 0), None      # dZ1 once, read by every gradient below
+            g1, act1 = _dz(g, out, relu_hidden, now=lower)
         if need_w1 or need_b1:
             gw1, gb1 = _dense_wgrad(graph, agg, g1, w1, need_b1, act1)
             gw1 = gw1 if need_w1 else None
         gx = gxd = geps = None
         has_self = not ctx.no_root and x_dst is None
         if need_x:
-            Hq = (H + 3) // 4 * 4
+            Hq = _round4(H)
             gx = _gin_input_grad(graph, _pad_cols(g1, Hq), ctx.n_src, eps.detach(), has_self, weight=_padded_wt(w1, Hq))
         if (need_xd or need_eps) and not ctx.no_root:
             d_agg = g1 @ w1.detach() if some else torch.zeros((0, F_), dtype=torch.float32, device=dev)
@@ -3726,15 +3747,14 @@ class _GinBnLayer(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, src, x_dst, eps, w1, b1, gamma, beta, w2, b2, graph, ids, relu_out, n_src, no_root, bn):
-        det = lambda t: None if t is None else t.detach()      # noqa: E731
         keep = any(ctx.needs_input_grad[:9])
         hops = []
         for h, rows, _ in _hops(graph):
-            self_rows, xd = _gin_hop_self(h, rows, det(x_dst), no_root)
+            self_rows, xd = _gin_hop_self(h, rows, _detached(x_dst), no_root)
             hops.append((h.row_ptr, h.col, self_rows, xd))
-        res = gin_bn_forward(hops, src, det(w1), det(b1), det(gamma), det(beta), det(w2), det(b2), bn_eps=bn.eps,
-                             momentum=bn.momentum, running_mean=bn.running_mean, running_var=bn.running_var, eps=det(eps),
-                             relu_out=relu_out, src_ids=ids, keep=keep)
+        res = gin_bn_forward(hops, src, *_detached((w1, b1, gamma, beta, w2, b2)), bn_eps=bn.eps, momentum=bn.momentum,
+                             running_mean=bn.running_mean, running_var=bn.running_var, eps=_detached(eps), relu_out=relu_out,
+                             src_ids=ids, keep=keep)
         bn.num_batches_tracked.add_(1)
         if not keep:
             return res
@@ -3754,9 +3774,7 @@ class _GinBnLayer(torch.autograd.Function):
         need_x, need_xd, need_eps, need_w1, need_b1, need_gamma, need_beta, need_w2, need_b2 = ctx.needs_input_grad[:9]
         H, F_ = w1.shape
         graph = ctx.graph
-        g = g.contiguous().float()
-        if ctx.relu_out:
-            g = torch.ops.aten.threshold_backward(g, out, 0)
+        g, _ = _dz(g, out, ctx.relu_out)
         gw1 = gb1 = gw2 = gb2 = None
         if need_w2 or need_b2:
             gw2, gb2 = _dense_wgrad(graph, hidden, g, w2, need_b2, None)
@@ -4138,9 +4156,7 @@ class _Gatv2Layer(torch.autograd.Function):
         gxl = gxr = gatt = gb = None
         if g is None:
             g = torch.zeros_like(out)
-        gz = g.contiguous().float()
-        if relu:
-            gz = torch.ops.aten.threshold_backward(gz, out, 0)
+        gz, _ = _dz(g, out, relu)
         if need_b:
             gb = gz.sum(0)
         if need_xl or need_xr or need_att:
@@ -4674,9 +4690,7 @@ class _HeteroSageGroup(torch.autograd.Function):
         grp, c = ctx.grp, ctx.c
         w, z = ctx.saved_tensors
         N, K = grp.N, grp.K
-        g = g.contiguous().float()
-        if grp.relu:
-            g = torch.ops.aten.threshold_backward(g, z, 0)          # dZ once, read by every gradient
+        g, _ = _dz(g, z, grp.relu)
         need_w, need_b, need_dst = ctx.needs_input_grad[1:4]
         gw = gb = gdst = None
         if need_w or need_b:
@@ -4860,9 +4874,7 @@ class _HeteroTconvGroup(torch.autograd.Function):
         grp, A, alphas = ctx.grp, ctx.A, ctx.alphas
         w, uw, z = ctx.saved_tensors
         n, dev = grp.n_rows, w.device
-        g = g.contiguous().float()
-        if grp.relu:
-            g = torch.ops.aten.threshold_backward(g, z, 0)          # dZ once, read by every gradient
+        g, _ = _dz(g, z, grp.relu)
         need_w, need_b, need_uw, need_dst = ctx.needs_input_grad[1:5]
         need_src = [ctx.needs_input_grad[5 + si] for si in range(ctx.n_srcs)]
         gw = g.t() @ A if need_w else None
@@ -5210,8 +5222,7 @@ class HeteroConv(torch.nn.Module):
         if not in_domain:
             return self._forward_sage_library({t: (v.materialize() if isinstance(v, LazyRows) else v) for t, v in xs.items()
                                                if v is not None}, graph, relu)
-        needs_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
-                                                  or any(ids[t] is None and v.requires_grad for t, v in X.items()))
+        needs_grad = _needs_grad(self.parameters(), *(v for t, v in X.items() if ids[t] is None))
         dev = next(iter(X.values())).device
         groups = _relation_groups(graph)
         out = _group_outputs(graph, groups, self._width, dev, make=torch.zeros if needs_grad else torch.empty)
@@ -5352,8 +5363,7 @@ class HeteroConv(torch.nn.Module):
         for t in X:       # rows as the kernel reads them (float32, unit column stride, 16-B aligned rows): copied when they are not
             if ids[t] is None:
                 X[t] = _tconv_rows(X[t])
-        needs_grad = torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
-                                                  or any(ids[t] is None and v.requires_grad for t, v in X.items()))
+        needs_grad = _needs_grad(self.parameters(), *(v for t, v in X.items() if ids[t] is None))
         out = _group_outputs(graph, groups, self._width, dev, make=torch.zeros if needs_grad else torch.empty)
         weights = {}
         for (hop, dt), mine in groups:
@@ -5590,13 +5600,20 @@ def _norm_act_flags(norm: bool, relu: bool, save: bool = False) -> int:
 
 
 def _norm_act_vec_ok(v, C: int) -> bool:
-    return v is None or (v.dtype == torch.float32 and v.is_cuda and v.dim() == 1 and v.numel() == C and v.is_contiguous()
-                         and v.data_ptr() % 16 == 0)
+    """``v`` is None or a per-column vector the kernels read: float32 [C] on the device, contiguous, 16-B aligned."""
+    return v is None or (torch.is_tensor(v) and v.dtype == torch.float32 and v.is_cuda and v.dim() == 1 and v.numel() == C
+                         and v.is_contiguous() and v.data_ptr() % 16 == 0)
 
 
 def _norm_act_rows_ok(t) -> bool:
     """``_kernel_rows_ok`` and rows that do not overlap: at least C floats apart (an expanded tensor's are 0 apart)."""
     return _kernel_rows_ok(t) and t.stride(0) >= t.shape[1]
+
+
+def _grad_rows(g):
+    """The upstream gradient ``g`` as rows the kernels read (``_norm_act_rows_ok``): ``g`` itself, or — an expanded or 16-bit
+    gradient — one copy."""
+    return g if _norm_act_rows_ok(g) else torch.empty(g.shape, dtype=torch.float32, device=g.device).copy_(g)
 
 
 def _norm_act_kernel_ok(x, weight, bias, residual) -> bool:
@@ -5686,7 +5703,7 @@ class _NormAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, conf, n, *tensors):
         norm, relu, eps, p, seed, seed_indices = conf
-        segs = [tuple(None if t is None else t.detach() for t in tensors[k::n]) for k in range(n)]
+        segs = [_detached(tuple(tensors[k::n])) for k in range(n)]
         outs, stats = norm_act_forward(segs, norm, relu, eps, p, seed, seed_indices, save_stats=True)
         ctx.conf, ctx.n, ctx.stats = conf, n, stats
         ctx.save_for_backward(*tensors)
@@ -5699,14 +5716,10 @@ class _NormAct(torch.autograd.Function):
         n, tensors = ctx.n, ctx.saved_tensors
         if torch.is_grad_enabled():
             return (None, None) + _norm_act_double_backward(ctx, tensors, grads)
-        segs = [tuple(None if t is None else t.detach() for t in tensors[k::n]) for k in range(n)]
+        segs = [_detached(tuple(tensors[k::n])) for k in range(n)]
         gs = []
         for (x, _, _, _), g in zip(segs, grads):
-            if g is None:
-                g = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
-            elif not _norm_act_rows_ok(g):        # (an expanded or 16-bit gradient: one copy into rows the kernel reads)
-                g = torch.empty(x.shape, dtype=torch.float32, device=x.device).copy_(g)
-            gs.append(g)
+            gs.append(torch.zeros(x.shape, dtype=torch.float32, device=x.device) if g is None else _grad_rows(g))
         need = ctx.needs_input_grad[2:]
         dz, dw, db = norm_act_backward(segs, gs, ctx.stats, norm, relu, eps, p, seed, seed_indices,
                                        need_w=[bool(need[2 * n + k]) for k in range(n)],
@@ -5721,20 +5734,15 @@ def _norm_act_double_backward(ctx, tensors, grads):
     norm, relu, eps, p, seed, seed_indices = ctx.conf
     n = ctx.n
     res = [None] * (4 * n)
-    with torch.enable_grad():
-        for k in range(n):
-            x, r, w, b = tensors[k::n]
-            mask = None
-            if p > 0:
-                ones = torch.ones(x.shape, dtype=torch.float32, device=x.device)
-                s = seed if seed_indices is None or seed_indices[k] < 0 else segment_seed(seed, seed_indices[k])
-                mask = norm_act_forward([(ones, None, None, None)], False, False, eps, p, s)[0][0]
-            ins = [(i, t) for i, t in ((k, x), (n + k, r), (2 * n + k, w), (3 * n + k, b)) if t is not None and t.requires_grad]
-            if not ins or grads[k] is None:
-                continue
-            y = _norm_act_torch(x, w, b, r, norm, eps, p, True, relu, mask=mask)
-            for (i, _), gr in zip(ins, torch.autograd.grad(y, [t for _, t in ins], grads[k], create_graph=True, allow_unused=True)):
-                res[i] = gr
+    for k in range(n):
+        x, r, w, b = tensors[k::n]
+        mask = None
+        if p > 0:
+            ones = torch.ones(x.shape, dtype=torch.float32, device=x.device)
+            s = seed if seed_indices is None or seed_indices[k] < 0 else segment_seed(seed, seed_indices[k])
+            mask = norm_act_forward([(ones, None, None, None)], False, False, eps, p, s)[0][0]
+        _grads_from_torch(lambda: _norm_act_torch(x, w, b, r, norm, eps, p, True, relu, mask=mask),
+                          ((k, x), (n + k, r), (2 * n + k, w), (3 * n + k, b)), grads[k], res)
     return tuple(res)
 
 
@@ -5798,7 +5806,7 @@ def _norm_dropout_act(x, weight, bias, residual, norm, eps, p, training, relu, s
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in flat):
         outs = _NormAct.apply((bool(norm), bool(relu), float(eps), p_eff, int(seed) & _M64, seed_indices), n, *flat)
     else:
-        outs = norm_act_forward([tuple(None if t is None else t.detach() for t in s) for s in segs], norm, relu, eps, p_eff, seed,
+        outs = norm_act_forward([_detached(tuple(s)) for s in segs], norm, relu, eps, p_eff, seed,
                                 seed_indices)[0]
     return wrap(list(outs)), "kernel"
 
@@ -5964,11 +5972,11 @@ class _RowLinear(torch.autograd.Function):
     @staticmethod
     def forward(ctx, conf, src, ids, weight, bias, gamma, beta, add):
         relu, norm, eps, x_grad = conf
-        d = lambda t: None if t is None else t.detach()      # noqa: E731
         need = ctx.needs_input_grad
         direct = ids is None and src.dtype == torch.float32
         keep_y = norm is not None or (relu and add is not None)
-        res, kept_x, kept_y = row_linear_forward(d(src), ids, d(weight), d(bias), relu, norm, d(gamma), d(beta), eps, d(add),
+        src_d, weight_d, bias_d, gamma_d, beta_d, add_d = _detached((src, weight, bias, gamma, beta, add))
+        res, kept_x, kept_y = row_linear_forward(src_d, ids, weight_d, bias_d, relu, norm, gamma_d, beta_d, eps, add_d,
                                                  keep_x=(need[3] or need[4]) and not direct, keep_y=keep_y)
         if relu and not keep_y:
             kept_y = res
@@ -5986,8 +5994,7 @@ class _RowLinear(torch.autograd.Function):
             return (None,) * 8
         if torch.is_grad_enabled():
             return _row_linear_double_backward(ctx, g)
-        if not _norm_act_rows_ok(g):              # (an expanded or 16-bit gradient: one copy into rows the kernel reads)
-            g = torch.empty(g.shape, dtype=torch.float32, device=g.device).copy_(g)
+        g = _grad_rows(g)
         dy, dg, db = g, None, None
         if relu or norm is not None:
             dy, dg, db = row_linear_backward(kept_y, g, relu, norm, None if gamma is None else gamma.detach(), eps,
@@ -6006,21 +6013,12 @@ def _row_linear_double_backward(ctx, g):
     """The gradients as differentiable torch expressions of the saved inputs and ``g``."""
     relu, norm, eps, x_grad = ctx.conf
     src, ids, weight, bias, gamma, beta, add, _, _ = ctx.saved_tensors
-    res = [None] * 8
-    with torch.enable_grad():
+
+    def make_y():
         xr = src if ids is None else src[ids.long()]
-        y = _linear_rows_torch(xr.float(), weight, bias, relu, norm, gamma, beta, _row_linear_eps(norm, eps), add)
-        ins = [(i, t) for i, t in ((1, src), (3, weight), (4, bias), (5, gamma), (6, beta), (7, add))
-               if t is not None and t.requires_grad and ctx.needs_input_grad[i]]
-        if ins:
-            for (i, _), gr in zip(ins, torch.autograd.grad(y, [t for _, t in ins], g, create_graph=True, allow_unused=True)):
-                res[i] = gr
-    return tuple(res)
-
-
-def _row_vec_ok(v, N: int) -> bool:
-    return v is None or (torch.is_tensor(v) and v.dtype == torch.float32 and v.is_cuda and v.dim() == 1 and v.numel() == N
-                         and v.is_contiguous() and v.data_ptr() % 16 == 0)
+        return _linear_rows_torch(xr.float(), weight, bias, relu, norm, gamma, beta, _row_linear_eps(norm, eps), add)
+    ins = ((1, src), (3, weight), (4, bias), (5, gamma), (6, beta), (7, add))
+    return tuple(_grads_from_torch(make_y, [(i, t) for i, t in ins if ctx.needs_input_grad[i]], g, [None] * 8))
 
 
 def linear_rows(x, weight, bias=None, *, rows=None, relu=False, norm=None, norm_weight=None, norm_bias=None, eps=None, add=None,
@@ -6079,10 +6077,9 @@ def _linear_rows(x, weight, bias, rows, relu, norm, gamma, beta, eps, add, out):
     if lazy:
         _refuse_lazy_table_grad(x.table)
     src = x.table if lazy else x
-    kernel = (torch.is_tensor(src) and src.is_cuda and src.dim() == 2 and src.stride(1) == 1 and src.stride(0) % 4 == 0
-              and linear_rows_supported(K, N)
-              and (src.dtype == torch.float32 and src.data_ptr() % 16 == 0 or lazy and src.dtype in _X16 and src.data_ptr() % 8 == 0)
-              and _kernel_rows_ok(weight) and _row_vec_ok(bias, N) and _row_vec_ok(gamma, N) and _row_vec_ok(beta, N)
+    kernel = (torch.is_tensor(src) and src.dim() == 2 and linear_rows_supported(K, N)
+              and (_kernel_rows_ok(src) or lazy and _kernel_rows_ok(src, _X16, 8))
+              and _kernel_rows_ok(weight) and _norm_act_vec_ok(bias, N) and _norm_act_vec_ok(gamma, N) and _norm_act_vec_ok(beta, N)
               and (rows is None or rows.is_cuda) and (not lazy or x.ids.is_cuda) and (add is None or _norm_act_rows_ok(add))
               and (out is None or _norm_act_rows_ok(out)))
     if not kernel:
@@ -6109,8 +6106,8 @@ def _linear_rows(x, weight, bias, rows, relu, norm, gamma, beta, eps, add, out):
         if out is not None:       # (a result that carries a gradient is written once more, into the caller's rows)
             res = out.copy_(res)
     else:
-        d = lambda t: None if t is None else t.detach()      # noqa: E731
-        res = row_linear_forward(d(src), ids, d(weight), d(bias), relu, norm, d(gamma), d(beta), eps_v, d(add), out)[0]
+        src_d, weight_d, bias_d, gamma_d, beta_d, add_d = _detached(tensors)
+        res = row_linear_forward(src_d, ids, weight_d, bias_d, relu, norm, gamma_d, beta_d, eps_v, add_d, out)[0]
     return res, "kernel"
 
 

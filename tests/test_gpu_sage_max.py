@@ -89,31 +89,57 @@ def test_layer_forward_vs_fp64(hiplib, launches, F, N, relu, root, aggr, ids):
         _close(out[rows], ref.detach(), lin64(*_abs(red, xd[s], w_l, w_r, b)), (F, N, aggr, ids))
 
 
-@pytest.mark.parametrize("F,N,relu,root", [(100, 47, False, True), (128, 256, True, False)])
+def _hops_of(sizes, seed):
+    """One hop per entry of ``sizes``.  A small hop has degrees 0 .. 70, rows of 0, 1 and 70 edges among them: its transpose
+    crosses the 64-entry piece of the input gradient and the 8- and 16-edge unrolls.  0 rows: a hop without rows."""
+    import torch
+    none = (torch.zeros(1, dtype=torch.int32, device="cuda"), torch.zeros(0, dtype=torch.int32, device="cuda"),
+            torch.zeros(0, dtype=torch.int64, device="cuda"))
+    return [_hop(n, N_SRC, 24 if n == N_DST else 70, seed=seed + k) if n > 0 else none for k, n in enumerate(sizes)]
+
+
+# beside the two large shapes: hops of 17, 0 and 33 rows (ragged 16- and 32-row tiles around a hop without rows) with the
+# upstream gradient a column-sliced view, rows N + 4 floats apart — without ReLU it reaches the kernels as that view —, and a
+# layer graph none of whose hops has rows: no launch, every gradient exact zeros of its input's shape
+@pytest.mark.parametrize("F,N,relu,root,sizes,view", [
+    pytest.param(100, 47, False, True, (N_DST,), False, id="100-47-False-True"),
+    pytest.param(128, 256, True, False, (N_DST,), False, id="128-256-True-False"),
+    pytest.param(8, 4, False, True, (17, 0, 33), True, id="8-4-False-True-view"),
+    pytest.param(8, 4, True, False, (17, 0, 33), True, id="8-4-True-False-view"),
+    pytest.param(8, 4, True, True, (0, 0), False, id="8-4-True-True-no-rows"),
+    pytest.param(8, 4, False, False, (0, 0), True, id="8-4-False-False-no-rows-view")])
 @pytest.mark.parametrize("aggr", ["max", "min"])
-def test_gradients_vs_fp64_autograd(hiplib, launches, F, N, relu, root, aggr):
+def test_gradients_vs_fp64_autograd(hiplib, launches, F, N, relu, root, sizes, view, aggr):
     """dW_l, dW_r, db, dX; random normal inputs, so ties are duplicate edges of one source (both tie rules give the same sum)."""
     import torch
-    rp, col, self_rows = _hop(N_DST, N_SRC, 24, seed=F)
+    hops = _hops_of(sizes, seed=F)
+    self_rows, n = torch.cat([h[2] for h in hops]), sum(sizes)
     from wholegraph_amd import nn
-    lg = nn.LayerGraph([nn.HopGraph(rp, col, self_rows)])
+    lg = nn.LayerGraph([nn.HopGraph(*h) for h in hops])
     conv = _conv(F, N, aggr, root, seed=F)
     x = torch.randn((N_SRC, F), device="cuda", requires_grad=True)
-    g = torch.randn((N_DST, N), device="cuda")
+    g = torch.randn((n, N + 4), device="cuda")[:, :N] if view else torch.randn((n, N), device="cuda")
     params = [p for p in (conv.lin_l.weight, conv.lin_r.weight if root else None, conv.lin_l.bias) if p is not None]
     got = torch.autograd.grad(conv(x, lg, act="relu" if relu else None), [x] + params, g)
     again = torch.autograd.grad(conv(x, lg, act="relu" if relu else None), [x], g)[0]
-    assert conv.route == "max_kernel" and len(launches) == 2
+    assert conv.route == "max_kernel" and len(launches) == 2 * sum(k > 0 for k in sizes)
     assert torch.equal(got[0], again)                       # no atomics, a fixed order: the same bits
+    for p in params:                                        # no parameter wants a gradient: no weight-gradient launch, the same dX
+        p.requires_grad_(False)
+    assert torch.equal(got[0], torch.autograd.grad(conv(x, lg, act="relu" if relu else None), [x], g)[0])
+    if n == 0:
+        for a, t in zip(got, [x] + params):
+            assert a.shape == t.shape and a.dtype == torch.float32 and not bool(a.any())
     x64 = x.detach().double().requires_grad_(True)
     w_l, w_r, b = _params64(conv)
-    red = red64(x64, rp, col, aggr)
+    red = torch.cat([red64(x64, rp, col, aggr) for rp, col, _ in hops])
     ref = lin64(red, x64[self_rows], w_l, w_r, b, relu)
     want = torch.autograd.grad(ref, [x64] + [p for p in (w_l, w_r, b) if p is not None], g.double())
     # the magnitude sums: the same linear maps with |dZ|, |W| and |x| (the selection stays the real one)
     dz = (g.double() * (ref > 0)).abs() if relu else g.double().abs()
     xa = x.detach().double().requires_grad_(True)
-    sx = torch.autograd.grad(lin64(red64(xa, rp, col, aggr), xa[self_rows], *_abs(w_l, w_r), None), xa, dz)[0]
+    sx = torch.autograd.grad(lin64(torch.cat([red64(xa, rp, col, aggr) for rp, col, _ in hops]), xa[self_rows], *_abs(w_l, w_r), None),
+                             xa, dz)[0]
     scales = [sx, dz.t() @ red.detach().abs()] + ([dz.t() @ x64.detach()[self_rows].abs()] if root else []) + [dz.sum(0)]
     for a, b, s, what in zip(got, want, scales, ["dX", "dW_l"] + (["dW_r"] if root else []) + ["db"]):
         _close(a, b, s, (what, F, N, aggr))

@@ -13,7 +13,7 @@ def _hop(n_dst, n_src, max_deg, seed, hubs=True):
     import torch
     g = torch.Generator(device="cuda").manual_seed(seed)
     deg = torch.randint(0, max_deg + 1, (n_dst,), generator=g, device="cuda")
-    deg[:3] = torch.tensor([0, 1, max_deg], device="cuda")
+    deg[:3] = torch.tensor([0, 1, max_deg], device="cuda")[:n_dst]
     rp = torch.zeros(n_dst + 1, dtype=torch.int32, device="cuda")
     rp[1:] = torch.cumsum(deg, 0)
     E = int(rp[-1])
@@ -107,10 +107,24 @@ def _ref_layer(x64, hops, wl, wr, b, relu, mean):
     return torch.relu(out) if relu else out
 
 
-@pytest.mark.parametrize("F,N,relu,mean,lazy", [(100, 256, True, True, "int64"), (100, 256, True, True, "int32"),
-                                                 (256, 47, False, True, None), (128, 128, True, False, None),
-                                                 (256, 256, True, True, None), (64, 64, True, True, None)])
-def test_sage_layer_autograd_vs_fp64(hiplib, F, N, relu, mean, lazy):
+# beside the two-hop shapes: hops of 17, 0 and 33 rows (ragged 16- and 32-row tiles around a hop without rows; degrees 0 .. 70)
+# with the upstream gradient a column-sliced view, rows N + 4 floats apart — without ReLU, or for a LazyRows input, it reaches
+# the kernels as that view —, and a layer graph none of whose hops has rows: every gradient exact zeros of its input's shape
+BIG, SMALL, NONE = ((1500, 10), (700, 25)), ((17, 70), (0, 0), (33, 70)), ((0, 0), (0, 0))
+
+
+@pytest.mark.parametrize("F,N,relu,mean,lazy,hop_sizes,view", [
+    pytest.param(100, 256, True, True, "int64", BIG, False, id="100-256-True-True-int64"),
+    pytest.param(100, 256, True, True, "int32", BIG, False, id="100-256-True-True-int32"),
+    pytest.param(256, 47, False, True, None, BIG, False, id="256-47-False-True-None"),
+    pytest.param(128, 128, True, False, None, BIG, False, id="128-128-True-False-None"),
+    pytest.param(256, 256, True, True, None, BIG, False, id="256-256-True-True-None"),
+    pytest.param(64, 64, True, True, None, BIG, False, id="64-64-True-True-None"),
+    pytest.param(64, 64, False, True, None, SMALL, True, id="64-64-False-True-None-small-view"),
+    pytest.param(64, 64, True, False, "int64", SMALL, True, id="64-64-True-False-int64-small-view"),
+    pytest.param(64, 64, True, True, None, NONE, False, id="64-64-True-True-None-no-rows"),
+    pytest.param(64, 64, False, True, "int64", NONE, True, id="64-64-False-True-int64-no-rows-view")])
+def test_sage_layer_autograd_vs_fp64(hiplib, F, N, relu, mean, lazy, hop_sizes, view):
     """``nn.SAGEConv`` over a two-hop LayerGraph under autograd: the output is bit for bit the no-grad (inference) launch, and
     d/d{lin_l.weight, lin_r.weight, bias, x} match the fp64 autograd of the dense formula — x as a resident tensor (its
     gradient runs the layer kernel over the transposed hops, hub rows included) or as LazyRows (table read through ids: no
@@ -118,7 +132,7 @@ def test_sage_layer_autograd_vs_fp64(hiplib, F, N, relu, mean, lazy):
     import torch
     from wholegraph_amd import nn
     n_src = 6000
-    hops = [_hop(1500, n_src, 10, F + N), _hop(700, n_src, 25, F + N + 1)]
+    hops = [_hop(n, n_src, max_deg, F + N + k) for k, (n, max_deg) in enumerate(hop_sizes)]
     lg = nn.LayerGraph([nn.HopGraph(*h) for h in hops])
     g = torch.Generator(device="cuda").manual_seed(F + 3 * N)
     torch.manual_seed(F * 7 + N)      # (the layer's initial weights)
@@ -135,7 +149,12 @@ def test_sage_layer_autograd_vs_fp64(hiplib, F, N, relu, mean, lazy):
     out = conv(x_in, lg, act="relu" if relu else None)
     assert out.requires_grad and torch.equal(out, want), "training forward differs from the inference launch"
     gout = torch.randn(out.shape, generator=g, device="cuda")
+    if view:
+        gout = torch.randn((out.shape[0], N + 4), generator=g, device="cuda")[:, :N]
     out.backward(gout)
+    if out.shape[0] == 0:
+        for p in list(conv.parameters()) + ([] if lazy else [x_in]):
+            assert p.grad.shape == p.shape and p.grad.dtype == torch.float32 and not bool(p.grad.any())
 
     wl, wr, b = (p.detach().double().requires_grad_(True) for p in (conv.lin_l.weight, conv.lin_r.weight, conv.lin_l.bias))
     pre = _ref_layer(x64, hops, wl, wr, b, False, mean)
