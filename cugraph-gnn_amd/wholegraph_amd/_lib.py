@@ -438,6 +438,18 @@ SYMBOLS = {
     "wgamd_gatv2_bwd_src_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                         c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
                                         c_int, c_void_p]),
+    # GATv2 attention with edge features (wg_gatv2_edge.hip)
+    "wgamd_gatv2_edge_supported": (c_int, [c_int, c_int, c_int]),
+    "wgamd_gatv2_edge_bwd_blocks": (c_int64, [c_int64, c_int]),
+    "wgamd_gatv2_edge_attention_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                               c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+                                               c_int64, c_void_p, c_void_p, c_void_p]),
+    "wgamd_gatv2_edge_bwd_dst_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                             c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "wgamd_gatv2_edge_bwd_src_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                             c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_int64, c_void_p, c_int64, c_int, c_void_p]),
     # NormDropoutAct (wg_norm_act.hip)
     "wgamd_norm_act_supported": (c_int, [c_int]),
     "wgamd_norm_act_segment_seed": (c_ulonglong, [c_ulonglong, c_int]),

@@ -4184,21 +4184,29 @@ class _Gatv2Layer(torch.autograd.Function):
         return gxl, gxr, gatt, gb, None, None, None, None, None, None
 
 
-def _gatv2_torch_ops(conv, xs, x_dst, lg: LayerGraph, relu: bool):
+def _gatv2_torch_ops(conv, xs, x_dst, lg: LayerGraph, relu: bool, edge_attr=None):
     """The layer in PyG's own formulation, composed of torch ops under ordinary autograd in the parameters' dtype: the route of
-    shapes outside the kernel's domain and of CPU tensors (correctness, not speed — [E, H, C] is materialised three times)."""
+    shapes outside the kernel's domain and of CPU tensors (correctness, not speed — [E, H, C] is materialised three times).
+    ``edge_attr`` (``GATv2EdgeConv``: hop-major [E, D]) adds ``lin_edge`` of every edge's row — of ``conv._fill_rows`` for a self
+    loop — inside the LeakyReLU."""
     H, C, dt = conv.heads, conv.out_channels, conv.att.dtype
     xs = xs.to(dt)
     XL = conv.lin_l(xs).view(-1, H, C)
     outs = []
-    for h, rows, _ in _hops(lg):
+    for h, rows, edges in _hops(lg):
         n, E = h.n_rows, int(h.col.shape[0])
         XR = conv.lin_r(x_dst[rows].to(dt) if x_dst is not None else xs[h.self_rows]).view(n, H, C)
         src, dst = h.col.long(), _edge_dst(h.row_ptr, E)
         if conv.add_self_loops:
             src, dst = torch.cat([h.self_rows, src]), torch.cat([torch.arange(n, device=dst.device), dst])
         xj = XL[src]
-        e = (torch.nn.functional.leaky_relu(xj + XR[dst], conv.negative_slope) * conv.att).sum(-1)       # [E', H]
+        s = xj + XR[dst]
+        if edge_attr is not None:
+            ea = edge_attr[edges].to(dt)
+            if conv.add_self_loops:
+                ea = torch.cat([conv._fill_rows(h, ea), ea])
+            s = s + conv.lin_edge(ea).view(-1, H, C)
+        e = (torch.nn.functional.leaky_relu(s, conv.negative_slope) * conv.att).sum(-1)                  # [E', H]
         emax = e.new_full((n, H), -math.inf).scatter_reduce(0, dst.unsqueeze(1).expand(-1, H), e, "amax", include_self=True)
         ex = (e - emax[dst]).exp()
         alpha = ex / e.new_zeros((n, H)).index_add(0, dst, ex)[dst]
@@ -4280,7 +4288,16 @@ class GATv2Conv(torch.nn.Module):
               and gatv2_supported(self.heads, self.out_channels))
         return "kernel" if ok else "torch"
 
-    def _forward_layer(self, x, lg: LayerGraph, act=None, x_dst=None):
+    def _checked_edge_attr(self, edge_attr, n_edges: int, device):
+        """What ``forward`` hands on as the per-edge rows: None here (``GATv2EdgeConv`` checks and returns its tensor)."""
+        return None
+
+    def _attention(self, XL, XR, lg: LayerGraph, relu: bool, edge_attr):
+        """The kernel route from the transformed rows on."""
+        return _Gatv2Layer.apply(XL, XR, self.att, self.bias, lg, bool(self.add_self_loops), self.heads, self.negative_slope,
+                                 relu, not self.concat)
+
+    def _forward_layer(self, x, lg: LayerGraph, act=None, x_dst=None, edge_attr=None):
         assert act in (None, "relu"), "act: None or 'relu'"
         x = _x16_as_rows(x)
         if isinstance(x, LazyRows):
@@ -4293,9 +4310,9 @@ class GATv2Conv(torch.nn.Module):
                              % (x_dst.shape[1], self.in_src if self.share_weights else self.in_dst))
         if x_dst is None and self.in_src != self.in_dst and not self.share_weights:
             raise ValueError("GATv2Conv: in_channels = %s needs an (x_src, x_dst) pair" % (self.in_channels,))
-        on_device = all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in (x, x_dst))
-        if self.route != "kernel" or not on_device:
-            return _gatv2_torch_ops(self, x, x_dst, lg, act == "relu")
+        on_device = all(t is None or (t.is_cuda and t.dtype == torch.float32) for t in (x, x_dst, edge_attr))
+        if self.route != "kernel" or not on_device or (edge_attr is not None and edge_attr.requires_grad):
+            return _gatv2_torch_ops(self, x, x_dst, lg, act == "relu", edge_attr)
         XL = self.lin_l(x)
         if x_dst is not None:
             XR = self.lin_r(x_dst)
@@ -4305,10 +4322,12 @@ class GATv2Conv(torch.nn.Module):
             dev = x.device
             self_all = torch.cat([h.self_rows for h in lg.hops]) if lg.hops else torch.zeros(0, dtype=torch.int64, device=dev)
             XR = self.lin_r(x[self_all])
-        return _Gatv2Layer.apply(XL, XR, self.att, self.bias, lg, bool(self.add_self_loops), self.heads, self.negative_slope,
-                                 act == "relu", not self.concat)
+        return self._attention(XL, XR, lg, act == "relu", edge_attr)
 
     def forward(self, x, graph, act=None):
+        return self._run(x, graph, act, None)
+
+    def _run(self, x, graph, act, edge_attr):
         if self.dropout > 0 and self.training:
             raise NotImplementedError("GATv2Conv: attention dropout (dropout > 0 in training mode) is not supported")
         _refuse_capture(self, "per-graph caches")              # (the hops' self-looped CSR and transposes, kept on the graph object)
@@ -4323,7 +4342,10 @@ class GATv2Conv(torch.nn.Module):
         if isinstance(graph, LayerGraph):
             if pair:
                 raise NotImplementedError("GATv2Conv: an (x_src, x_dst) pair over a LayerGraph is not supported")
-            return self._forward_layer(x, graph, act)
+            total = getattr(graph, "num_group_edges", None)       # (a call group's: every layer reads the prefix of its hops)
+            ea = self._checked_edge_attr(edge_attr, sum(int(h.col.shape[0]) for h in graph.hops) if total is None else total,
+                                         graph.hops[0].row_ptr.device if graph.hops else None)
+            return self._forward_layer(x, graph, act, edge_attr=ea)
         if isinstance(x, LazyRows):
             x = _x16_as_rows(x)
             x = x.materialize() if isinstance(x, LazyRows) else x
@@ -4344,8 +4366,271 @@ class GATv2Conv(torch.nn.Module):
         have = x_dst.shape[0] if pair else x.shape[0]
         if have < n_dst:
             raise ValueError("GATv2Conv: %d destination rows for %d destinations" % (have, n_dst))
-        lg = _single_hop(graph, n_dst)[0]
-        return self._forward_layer(x, lg, act, x_dst=x_dst[:n_dst] if pair and not own else None)
+        ea = self._checked_edge_attr(edge_attr, graph[1].shape[0], graph[0].device)
+        lg, _, ea = _single_hop(graph, n_dst, ea)
+        return self._forward_layer(x, lg, act, x_dst=x_dst[:n_dst] if pair and not own else None, edge_attr=ea)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# GATv2 with edge features (torch_geometric.nn.GATv2Conv(edge_dim=D)) — csrc/wg_gatv2_edge.hip
+# ---------------------------------------------------------------------------------------------------------------------
+def gatv2_edge_supported(H: int, C: int, D: int) -> bool:
+    """Shapes of the GATv2 kernels with edge features (``wgamd_gatv2_edge_supported``): ``gatv2_supported(H, C)`` and
+    1 <= D <= 16."""
+    return bool(L.lib().wgamd_gatv2_edge_supported(int(H), int(C), int(D)))
+
+
+def _gatv2_edge_operands(row_ptr, col, xl, xr, att, heads: int, xr_rows, negative_slope, edge_attr, w_edge_t, n_entries: int):
+    """``_gatv2_operands`` plus ``negative_slope, edge_attr, w_edge_t, D``, checked: ``edge_attr`` [n_entries, D] — one row per
+    entry of the CSR the forward walks — and ``w_edge_t`` = lin_edge.weight^T [D, H C], both float32 and contiguous."""
+    args = _gatv2_operands(row_ptr, col, xl, xr, att, heads, xr_rows)
+    D, HC = int(w_edge_t.shape[0]), int(xl.shape[1])
+    assert gatv2_edge_supported(args[-2], args[-1], D), "outside gatv2_edge_supported"
+    for t, shape in ((edge_attr, (n_entries, D)), (w_edge_t, (D, HC))):
+        assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape, (tuple(t.shape), shape)
+    return args + (float(negative_slope), _nonempty(edge_attr, torch.float32).data_ptr(), w_edge_t.data_ptr(), D)
+
+
+def gatv2_edge_attention(row_ptr, col, xl, xr, att, heads: int, edge_attr, w_edge_t, negative_slope: float = 0.2, xr_rows=None,
+                         bias=None, relu=False, out=None, need_alpha=False, mean=False):
+    """``gatv2_attention`` with ``w_edge_t^T edge_attr[k]`` added to ``xl[col[k]] + xr[i]`` inside the LeakyReLU, in ONE launch
+    (``wgamd_gatv2_edge_attention_f32``): ``edge_attr`` [E, D] in CSR slot order (the rows of self-loop entries included),
+    ``w_edge_t`` [D, H C].  The projected edge rows are never written.  Everything else as there."""
+    _check_csr(row_ptr, col)
+    H, HC, n_rows, E, dev = int(heads), int(xl.shape[1]), row_ptr.shape[0] - 1, int(col.shape[0]), row_ptr.device
+    args = _gatv2_edge_operands(row_ptr, col, xl, xr, att, H, xr_rows, negative_slope, edge_attr, w_edge_t, E)
+    N = HC // H if mean else HC
+    assert xr_rows is not None or xr.shape[0] == n_rows
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == N)
+    out = _out_rows(out, n_rows, N, dev)
+    alpha = torch.empty((E, H), dtype=torch.float32, device=dev) if need_alpha else None
+    agg = torch.empty((n_rows, HC), dtype=torch.float32, device=dev) if need_alpha else None
+    if n_rows > 0 and E == 0:
+        out.zero_()
+        if bias is not None:
+            out.add_(bias)
+        if relu:
+            out.relu_()
+        if agg is not None:
+            agg.zero_()
+    elif n_rows > 0:
+        L.check(L.lib().wgamd_gatv2_edge_attention_f32(*args, _ptr(bias), int(bool(relu)), int(bool(mean)), out.data_ptr(),
+                                                       out.stride(0), _ptr(alpha), _ptr(agg), get_stream()),
+                "wgamd_gatv2_edge_attention_f32")
+    return (out, alpha, agg) if need_alpha else out
+
+
+def gatv2_edge_bwd_dst(row_ptr, col, xl, xr, att, heads: int, edge_attr, w_edge_t, alpha, g, agg, negative_slope: float = 0.2,
+                       xr_rows=None, dxr=None, max_blocks=None):
+    """The destination-major backward launch of one hop (``wgamd_gatv2_edge_bwd_dst_f32``): ``gatv2_bwd_dst`` with the edge term
+    in the logit, returning ``(dxr, de, datt_part [blocks, H C], dwe_part [blocks, D, H C])`` — the gradient of ``w_edge_t`` is
+    the sum of ``dwe_part`` over the blocks.  The grid is bounded (``wgamd_gatv2_edge_bwd_blocks``: at most 4 workgroups per
+    compute unit, each walking its tiles of 16 rows at a fixed stride); ``max_blocks`` forces a smaller one."""
+    H, HC, n_rows, dev = int(heads), int(xl.shape[1]), row_ptr.shape[0] - 1, row_ptr.device
+    args = _gatv2_edge_operands(row_ptr, col, xl, xr, att, H, xr_rows, negative_slope, edge_attr, w_edge_t, int(col.shape[0]))
+    assert _kernel_rows_ok(g) and g.shape == (n_rows, HC) and agg.is_contiguous() and alpha.is_contiguous()
+    assert tuple(alpha.shape) == (int(col.shape[0]), H) and tuple(agg.shape) == (n_rows, HC)
+    dxr = _out_rows(dxr, n_rows, HC, dev)
+    assert dxr.is_contiguous()
+    de = torch.empty((int(col.shape[0]), H), dtype=torch.float32, device=dev)
+    blocks = int(L.lib().wgamd_gatv2_edge_bwd_blocks(n_rows, 0 if max_blocks is None else int(max_blocks)))
+    part = torch.empty((blocks, HC), dtype=torch.float32, device=dev)
+    dwe = torch.empty((blocks, args[-1], HC), dtype=torch.float32, device=dev)
+    if n_rows > 0:
+        L.check(L.lib().wgamd_gatv2_edge_bwd_dst_f32(*args, _nonempty(alpha, torch.float32).data_ptr(), g.data_ptr(), g.stride(0),
+                                                     agg.data_ptr(), dxr.data_ptr(), _nonempty(de, torch.float32).data_ptr(),
+                                                     part.data_ptr(), dwe.data_ptr(), blocks, get_stream()),
+                "wgamd_gatv2_edge_bwd_dst_f32")
+    return dxr, de, part, dwe
+
+
+def gatv2_edge_bwd_src(row_ptr_t, col_t, perm, xl, xr, att, heads: int, edge_attr, w_edge_t, alpha, de, g, gx,
+                       negative_slope: float = 0.2, xr_rows=None, accumulate=True):
+    """The source-major backward launch of one hop over its transpose (``wgamd_gatv2_edge_bwd_src_f32``): ``gatv2_bwd_src`` with
+    the edge term recomputed per transposed entry, ``edge_attr`` (the forward's, in CSR slot order) read through ``perm``."""
+    H = int(heads)
+    args = _gatv2_edge_operands(row_ptr_t, col_t, xl, xr, att, H, xr_rows, negative_slope, edge_attr, w_edge_t, int(col_t.shape[0]))
+    assert _kernel_rows_ok(g) and _kernel_rows_ok(gx) and gx.shape == xl.shape and row_ptr_t.shape[0] - 1 == xl.shape[0]
+    assert perm.dtype == torch.int32 and tuple(alpha.shape) == tuple(de.shape) == (int(col_t.shape[0]), H)
+    L.check(L.lib().wgamd_gatv2_edge_bwd_src_f32(args[0], args[1], perm.data_ptr(), *args[2:],
+                                                 _nonempty(alpha, torch.float32).data_ptr(), _nonempty(de, torch.float32).data_ptr(),
+                                                 g.data_ptr(), g.stride(0), gx.data_ptr(), gx.stride(0), int(bool(accumulate)),
+                                                 get_stream()), "wgamd_gatv2_edge_bwd_src_f32")
+    return gx
+
+
+def _gatv2_edge_rows(h: HopGraph, ea, fill):
+    """``ea`` [E, D] (the hop's edges in CSR order) as the rows of ``h.with_self_loops()``'s E + n entries: one indexed copy, and
+    the loop's row — ``fill`` — at the first slot ``row_ptr[i] + i`` of every row."""
+    n, E = h.n_rows, int(ea.shape[0])
+    out = ea.new_empty((E + n, ea.shape[1]))
+    out[torch.arange(E, device=ea.device) + _edge_dst(h.row_ptr, E) + 1] = ea
+    out[h.row_ptr[:n].long() + torch.arange(n, device=ea.device)] = fill
+    return out
+
+
+class _Gatv2EdgeLayer(torch.autograd.Function):
+    """``_Gatv2Layer`` with edge features: ONE ``wgamd_gatv2_edge_attention_f32`` launch per hop forward,
+    ``wgamd_gatv2_edge_bwd_dst_f32`` and ``wgamd_gatv2_edge_bwd_src_f32`` per hop backward, without atomics.  ``ea`` is the
+    hop-major [E, D] tensor (no gradient); every hop's rows in the slot order of the CSR it walks (self loops: ``fills[k]`` in
+    front, ``_gatv2_edge_rows``) are made once per forward and kept with alpha and agg.  ``wet`` = lin_edge.weight^T [D, H C];
+    its gradient is the sum of the launches' partials in hop and block order."""
+
+    @staticmethod
+    def forward(ctx, xl, xr, att, bias, wet, ea, fills, graph, loops, H, slope, relu, mean):
+        lg, dev, HC = graph, xl.device, xl.shape[1]
+        train = any(ctx.needs_input_grad[:5])
+        out = torch.empty((lg.n_rows, HC // H if mean else HC), dtype=torch.float32, device=dev)
+        xl_d, xr_d, wet_d = xl.detach(), None if xr is None else xr.detach(), wet.detach().contiguous()
+        att_d, b_d = att.detach().contiguous(), None if bias is None else bias.detach().contiguous()
+        kept = []
+        for k, (h, rows, edges) in enumerate(_hops(lg)):
+            res = ea_h = None
+            if h.n_rows > 0:
+                hop = _gatv2_hop(h, loops)
+                ea_h = _gatv2_edge_rows(h, ea[edges], fills[k]) if loops else ea[edges].contiguous()
+                res = gatv2_edge_attention(hop.row_ptr, hop.col, xl_d, xl_d if xr is None else xr_d[rows], att_d, H, ea_h, wet_d,
+                                           slope, xr_rows=h.self_rows if xr is None else None, bias=b_d, relu=relu, out=out[rows],
+                                           need_alpha=train, mean=mean)
+            kept.append(res[1:] + (ea_h,) if train and res is not None else None)
+        ctx.set_materialize_grads(False)
+        if train:
+            ctx.save_for_backward(xl_d, xr_d, att_d, wet_d, out)
+            ctx.kept, ctx.graph, ctx.conf = kept, lg, (loops, H, slope, relu, mean)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        _released(ctx.kept, "GATv2EdgeConv", "attention weights")
+        xl, xr, att, wet, out = ctx.saved_tensors
+        need_xl, need_xr, need_att, need_b, need_w = ctx.needs_input_grad[:5]
+        loops, H, slope, relu, mean = ctx.conf
+        lg, dev, HC = ctx.graph, xl.device, xl.shape[1]
+        n, n_src = lg.n_rows, xl.shape[0]
+        gxl = gxr = gatt = gb = gw = None
+        if g is None:
+            g = torch.zeros_like(out)
+        gz, _ = _dz(g, out, relu)
+        if need_b:
+            gb = gz.sum(0)
+        if need_xl or need_xr or need_att or need_w:
+            G = (gz * (1.0 / H)).repeat(1, H) if mean else gz                # dL/d agg [n, H C]
+            gxl = torch.zeros((n_src, HC), dtype=torch.float32, device=dev)
+            gxr = None if xr is None else torch.zeros((n, HC), dtype=torch.float32, device=dev)
+            gatt, gw = torch.zeros(HC, dtype=torch.float32, device=dev), torch.zeros_like(wet)
+            for k, (h, rows, _) in enumerate(_hops(lg)):
+                if h.n_rows == 0:
+                    continue
+                hop = _gatv2_hop(h, loops)
+                if hop.col.shape[0] == 0:
+                    continue
+                alpha, agg, ea_h = ctx.kept[k]
+                xr_h, xr_rows = (xl, h.self_rows) if xr is None else (xr[rows], None)
+                dxr, de, part, dwe = gatv2_edge_bwd_dst(hop.row_ptr, hop.col, xl, xr_h, att, H, ea_h, wet, alpha, G[rows], agg, slope,
+                                                        xr_rows=xr_rows, dxr=None if xr is None else gxr[rows])
+                gatt += part.sum(0)
+                gw += dwe.sum(0)
+                row_ptr_t, col_t, _, perm = hop.transposed(n_src, need_self=False, need_perm=True)
+                gatv2_edge_bwd_src(row_ptr_t, col_t, perm, xl, xr_h, att, H, ea_h, wet, alpha, de, G[rows], gxl, slope,
+                                   xr_rows=xr_rows)
+                if xr is None:
+                    gxl[h.self_rows] += dxr
+            gatt = gatt.view(1, H, HC // H)
+        ctx.kept = None
+        return (gxl, gxr, gatt, gb, gw) + (None,) * 8
+
+
+class GATv2EdgeConv(GATv2Conv):
+    """PyG ``GATv2Conv(in_channels, out_channels, heads, edge_dim=D)``: ``GATv2Conv`` whose logit takes the edge's features,
+        s_ij = lin_l(x_j) + lin_r(x_i) + lin_edge(e_ij),   e_ijh = att_h . LeakyReLU(s_ij)_h,   alpha = softmax_j(e_ijh),
+        out_i = sum_j alpha_ijh lin_l(x_j)_h                                  (the message carries no edge term)
+    — a class of its own, as ``GINEConv`` is next to ``GINConv``.  It adds ``lin_edge = Linear(edge_dim, heads x out_channels,
+    bias=False)`` (glorot), so a state dict of PyG's ``GATv2Conv(edge_dim=D)`` loads with ``strict=True``.
+
+    ``forward(x, graph, act=None, edge_attr=None)``: ``x``, ``graph`` and ``act`` as ``GATv2Conv`` takes them; ``edge_attr``
+    (required, keyword) is [E, edge_dim] floating point — [E] with ``edge_dim == 1`` — on the graph's device, in the order of the
+    graph's edges: COO order for an ``edge_index``, CSR order for a ``[csr_row_ptr, csr_col_ind]`` pair, hop-major for a
+    ``LayerGraph`` (``CallGroup.edge_attr(name)``: every layer takes the same tensor and reads the prefix of its hops).
+    ValueError for a missing tensor or a wrong dtype, width, length or device; a tensor in the ``act`` position is a TypeError.
+
+    Self loops keep this package's rule — the destination's own input row is one extra leading entry, sampled loops and
+    duplicates stay ordinary edges — and the loop's edge row is ``fill_value``: ``"mean"`` = the mean of the ``edge_attr`` rows
+    of the row's sampled edges (zeros for a row without any), or a Python float = that constant.  This differs from PyG, which
+    REMOVES the loops already in ``edge_index`` before it takes the mean and adds its own: here a sampled loop stays an edge
+    with its own attributes and counts in the mean.
+
+    ``route``: ``"kernel"`` inside ``gatv2_edge_supported`` (``gatv2_supported`` and edge_dim <= 16) for float32 device tensors
+    and an ``edge_attr`` that needs no gradient: per hop ONE launch forward (``wgamd_gatv2_edge_attention_f32``) and two backward,
+    without atomics; ``lin_edge(edge_attr)`` [E, H C] is never written — the kernels keep ``lin_edge.weight^T`` in LDS and form
+    the term in registers —, only the hop's [E', D] rows in slot order are made (one indexed copy and a segment mean per hop and
+    forward).  Otherwise ``"torch"``: torch ops under ordinary autograd (CPU tensors, edge_dim > 16, ``edge_attr.requires_grad``,
+    ``torch_ops = True``).  Refusals as ``GATv2Conv``: attention dropout in training mode, ``HeteroLayerGraph``, ``HeteroConv``
+    relations, HIP-graph capture."""
+
+    def __init__(self, in_channels: Union[int, Tuple[int, int]], out_channels: int, edge_dim: int, heads: int = 1, concat: bool = True,
+                 negative_slope: float = 0.2, dropout: float = 0.0, add_self_loops: bool = True, bias: bool = True,
+                 share_weights: bool = False, fill_value: Union[float, str] = "mean"):
+        if isinstance(edge_dim, bool) or not isinstance(edge_dim, int) or edge_dim < 1:
+            raise ValueError("GATv2EdgeConv: edge_dim must be a positive int")
+        if fill_value != "mean" and (isinstance(fill_value, bool) or not isinstance(fill_value, (int, float))):
+            raise ValueError("GATv2EdgeConv: fill_value is 'mean' or a float, not %r" % (fill_value,))
+        self.edge_dim, self.fill_value = edge_dim, fill_value
+        super().__init__(in_channels, out_channels, heads=heads, concat=concat, negative_slope=negative_slope, dropout=dropout,
+                         add_self_loops=add_self_loops, bias=bias, share_weights=share_weights)
+
+    def reset_parameters(self):
+        if not hasattr(self, "lin_edge"):                          # (the base constructor's call: the modules exist from here on)
+            self.lin_edge = torch.nn.Linear(self.edge_dim, self.heads * self.out_channels, bias=False)
+        super().reset_parameters()
+        bound = math.sqrt(6.0 / sum(self.lin_edge.weight.shape))
+        torch.nn.init.uniform_(self.lin_edge.weight, -bound, bound)
+
+    @property
+    def route(self) -> str:
+        ok = super().route == "kernel" and gatv2_edge_supported(self.heads, self.out_channels, self.edge_dim)
+        return "kernel" if ok else "torch"
+
+    def _checked_edge_attr(self, edge_attr, n_edges: int, device):
+        D = self.edge_dim
+        if edge_attr is None:
+            raise ValueError("GATv2EdgeConv: edge_dim=%d needs edge_attr" % D)
+        if not torch.is_tensor(edge_attr) or not edge_attr.is_floating_point():
+            raise ValueError("GATv2EdgeConv: edge_attr must be a floating-point tensor")
+        if edge_attr.dim() == 1 and D == 1:
+            edge_attr = edge_attr.unsqueeze(1)
+        if edge_attr.dim() != 2 or edge_attr.shape[1] != D:
+            raise ValueError("GATv2EdgeConv: edge_attr has shape %s, the layer takes [E, %d]" % (tuple(edge_attr.shape), D))
+        if device is not None and edge_attr.device != torch.device(device):
+            raise ValueError("GATv2EdgeConv: edge_attr is on %s, the graph on %s" % (edge_attr.device, torch.device(device)))
+        if edge_attr.shape[0] != n_edges:
+            raise ValueError("GATv2EdgeConv: edge_attr has %d rows for %d edges" % (edge_attr.shape[0], n_edges))
+        return edge_attr
+
+    def _fill_rows(self, h: HopGraph, ea):
+        """[n, D]: the self loops' edge rows of hop ``h`` whose edges carry ``ea`` [E, D] (CSR order)."""
+        n, E = h.n_rows, int(ea.shape[0])
+        if self.fill_value != "mean":
+            return ea.new_full((n, ea.shape[1]), float(self.fill_value))
+        if E == 0:
+            return ea.new_zeros((n, ea.shape[1]))
+        if ea.is_cuda and ea.dtype == torch.float32 and not ea.requires_grad:        # a deterministic segment mean, one launch
+            return spmm_csr_forward(h.row_ptr, torch.arange(E, dtype=torch.int32, device=ea.device), ea.contiguous(), mean=True)
+        deg = (h.row_ptr[1:] - h.row_ptr[:-1]).clamp(min=1).to(ea.dtype).unsqueeze(1)
+        return ea.new_zeros((n, ea.shape[1])).index_add(0, _edge_dst(h.row_ptr, E), ea) / deg
+
+    def _attention(self, XL, XR, lg: LayerGraph, relu: bool, edge_attr):
+        loops = bool(self.add_self_loops)
+        ea = edge_attr.detach()
+        fills = [self._fill_rows(h, ea[edges]) if loops and h.n_rows > 0 else None for h, _, edges in _hops(lg)]
+        wet = _derived(self, "lin_edge_t", (self.lin_edge.weight,), lambda: self.lin_edge.weight.t().contiguous(),
+                       grad=_needs_grad((self.lin_edge.weight,)))
+        return _Gatv2EdgeLayer.apply(XL, XR, self.att, self.bias, wet, ea, fills, lg, loops, self.heads, self.negative_slope, relu,
+                                     not self.concat)
+
+    def forward(self, x, graph, act=None, edge_attr=None):
+        if torch.is_tensor(act):
+            raise TypeError("GATv2EdgeConv: the third positional argument is act; pass the edge attributes as edge_attr=")
+        return self._run(x, graph, act, edge_attr)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

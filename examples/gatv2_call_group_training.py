@@ -9,6 +9,9 @@ group's trimmed layer graph — forward; two more per hop backward —, ReLU bet
 
     python examples/gatv2_call_group_training.py [--nodes 200000] [--epochs 3]
     ... --torch-ops                          the same layers out of torch ops (GATv2Conv's "torch" route)
+    ... --edge-dim 8                         GATv2EdgeConv layers: a float edge attribute (one raised column where the edge stays
+                                             inside its community) planted in the feature store, fetched per group with
+                                             CallGroup.edge_attr and read by both layers
     ... --torch-ops --float64 --device cpu   the accuracy yardstick: float64 torch ops on the CPU, over mini-batches sampled by a
                                              torch restatement of the loader (same fan-outs, without replacement, one
                                              optimizer step per group)
@@ -25,7 +28,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "cugraph-gnn_amd")]
 import torch  # noqa: E402
 
 from wholegraph_amd import nn as wnn  # noqa: E402
-from wholegraph_amd.nn import GATv2Conv  # noqa: E402
+from wholegraph_amd.nn import GATv2Conv, GATv2EdgeConv  # noqa: E402
 
 
 def planted_communities(V, avg_degree, features, classes, seed=0):
@@ -84,6 +87,7 @@ def main(argv=None):
     ap.add_argument("--fanout", type=int, nargs="+", default=[25, 10])
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--torch-ops", action="store_true", help="run the layers out of torch ops (GATv2Conv's 'torch' route)")
+    ap.add_argument("--edge-dim", type=int, default=0, help="> 0: GATv2EdgeConv layers over a planted edge attribute this wide")
     ap.add_argument("--float64", action="store_true")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
@@ -92,6 +96,7 @@ def main(argv=None):
     on_host = dev.type == "cpu"
     if on_host:
         assert args.torch_ops, "the HIP kernels need an MI355X: --device cpu runs with --torch-ops"
+        assert args.edge_dim == 0, "--edge-dim reads CallGroup.edge_attr: it runs on the device"
     else:
         assert torch.cuda.is_available(), "needs an MI355X (or --torch-ops --device cpu)"
     dtype = torch.float64 if args.float64 else torch.float32
@@ -99,15 +104,20 @@ def main(argv=None):
     src, dst, x, community, train_ids = planted_communities(V, args.avg_degree, args.features, args.classes)
     community = community.to(dev)
     torch.manual_seed(0)
-    convs = torch.nn.ModuleList([GATv2Conv(args.features, args.hidden, heads=args.heads, concat=True),
-                                 GATv2Conv(args.heads * args.hidden, args.classes, heads=1, concat=False)]).to(dev).to(dtype)
+    D = args.edge_dim
+
+    def layer(fin, fout, **kw):
+        return GATv2EdgeConv(fin, fout, D, **kw) if D else GATv2Conv(fin, fout, **kw)
+    convs = torch.nn.ModuleList([layer(args.features, args.hidden, heads=args.heads, concat=True),
+                                 layer(args.heads * args.hidden, args.classes, heads=1, concat=False)]).to(dev).to(dtype)
     for conv in convs:
         conv.torch_ops = args.torch_ops
     opt = torch.optim.Adam(convs.parameters(), lr=0.01)
 
-    def forward(h, layer_graph):
+    def forward(h, layer_graph, edge_attr=None):
         for j, conv in enumerate(convs):
-            h = conv(h, layer_graph(j), act="relu" if j + 1 < L else None)
+            kw = {} if edge_attr is None else {"edge_attr": edge_attr}        # (hop-major: every layer reads the prefix of its hops)
+            h = conv(h, layer_graph(j), act="relu" if j + 1 < L else None, **kw)
         return h
 
     if on_host:
@@ -133,13 +143,17 @@ def main(argv=None):
         graph_store, feature_store = GraphStore(), FeatureStore()
         graph_store[("node", "to", "node"), "coo", False, (V, V)] = torch.stack([src, dst]).to(dev)
         feature_store["node", "x", None] = x.to(dev).to(dtype)
+        if D:
+            attr = torch.randn((src.shape[0], D), generator=torch.Generator().manual_seed(2))
+            attr[community[src.to(dev)].cpu() == community[dst.to(dev)].cpu(), 0] += 1.0
+            feature_store[("node", "to", "node"), "attr", None] = attr.to(dev).to(dtype)
         loader = NeighborLoader((feature_store, graph_store), num_neighbors=args.fanout, input_nodes=train_ids.to(dev),
                                 batch_size=args.batch_size, shuffle=True, local_seeds_per_call=args.group * args.batch_size)
 
         def groups():
             for grp in loader.call_groups():
                 # (grp.x is LazyRows: the layer gathers the group's rows once)
-                yield forward(grp.x, grp.layer_graph), community[grp.batch], grp.num_edges
+                yield forward(grp.x, grp.layer_graph, grp.edge_attr("attr") if D else None), community[grp.batch], grp.num_edges
 
     losses, ms, acc = [], [], 0.0
     for epoch in range(args.epochs):

@@ -1304,6 +1304,40 @@ wholememory_error_code_t wgamd_gatv2_bwd_src_f32(const int* row_ptr_t, const int
                                                  const float* alpha, const float* de, const float* g, int64_t ldg, float* gx,
                                                  int64_t ldgx, int accumulate, void* stream);
 
+/* ---- GATv2 attention with edge features (csrc/wg_gatv2_edge.hip): torch_geometric.nn.GATv2Conv(edge_dim = D) ------------------------
+ * The three launches above with the projected edge attributes inside the logit's nonlinearity:
+ *   e[k, h] = sum_c att[h C + c] LeakyReLU(XL[j] + XR[i] + W_e edge_attr[k])[h C + c]
+ * edge_attr [E, D] float32, contiguous, one row per CSR slot (self-loop entries included: the caller puts their fill rows in);
+ * w_edge_t = W_e^T [D, H C] contiguous, 16-B aligned.  The message carries no edge term, so alpha, agg, out, dxr, de and gx mean
+ * what they mean above; lin_edge(edge_attr) [E, H C] is never written — every workgroup keeps W_e^T in LDS and the lanes form
+ * their columns of the product in registers.  wgamd_gatv2_edge_bwd_dst_f32 also makes
+ *   dW_e^T[d, hc] = sum_k edge_attr[k, d] de[k, h] att[hc] LeakyReLU'(s_k[hc])
+ * as dwe_part [n_blocks, D, H C] next to datt_part [n_blocks, H C]: workgroup b walks the tiles of 16 rows b, b + n_blocks, ... at a
+ * fixed stride, n_blocks = wgamd_gatv2_edge_bwd_blocks(n_rows, max_blocks) = min(tiles, max_blocks > 0 ? max_blocks : 4 x the
+ * device's compute units) — any 1 <= n_blocks <= tiles is taken; the caller sums the partials in a fixed order.
+ * wgamd_gatv2_edge_bwd_src_f32 reads edge_attr through perm.  No atomics.  Domain: wgamd_gatv2_edge_supported
+ * (wgamd_gatv2_supported(H, C) and 1 <= D <= 16). */
+int wgamd_gatv2_edge_supported(int H, int C, int D);
+int64_t wgamd_gatv2_edge_bwd_blocks(int64_t n_rows, int max_blocks);
+wholememory_error_code_t wgamd_gatv2_edge_attention_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* xl,
+                                                        int64_t ldxl, const float* xr, int64_t ldxr, const int64_t* xr_rows,
+                                                        const float* att, int H, int C, float negative_slope,
+                                                        const float* edge_attr, const float* w_edge_t, int D, const float* bias,
+                                                        int relu, int mean, float* out, int64_t ldo, float* alpha, float* agg,
+                                                        void* stream);
+wholememory_error_code_t wgamd_gatv2_edge_bwd_dst_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* xl,
+                                                      int64_t ldxl, const float* xr, int64_t ldxr, const int64_t* xr_rows,
+                                                      const float* att, int H, int C, float negative_slope, const float* edge_attr,
+                                                      const float* w_edge_t, int D, const float* alpha, const float* g, int64_t ldg,
+                                                      const float* agg, float* dxr, float* de, float* datt_part, float* dwe_part,
+                                                      int64_t n_blocks, void* stream);
+wholememory_error_code_t wgamd_gatv2_edge_bwd_src_f32(const int* row_ptr_t, const int* col_t, const int* perm, int64_t n_src,
+                                                      const float* xl, int64_t ldxl, const float* xr, int64_t ldxr,
+                                                      const int64_t* xr_rows, const float* att, int H, int C, float negative_slope,
+                                                      const float* edge_attr, const float* w_edge_t, int D, const float* alpha,
+                                                      const float* de, const float* g, int64_t ldg, float* gx, int64_t ldgx,
+                                                      int accumulate, void* stream);
+
 /* ---- NormDropoutAct (csrc/wg_norm_act.hip): the row-wise block between two message-passing layers -------------------------------
  * What the reference's models put after a conv (mag_lp_mnmg.py: norm -> dropout -> relu, with the `+ lin1(x)` residual in the
  * encoder; gnn_model.py / rgcn / gin: relu -> dropout), over [n_rows, C] float32, for up to WGAMD_NORM_ACT_MAX_SEGMENTS node types
