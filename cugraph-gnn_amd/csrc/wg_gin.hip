@@ -19,57 +19,13 @@
 //     a Linear).
 //   * segment_sum_kernel — global_add_pool over a sorted batch vector given as segment offsets: one wave per (segment,
 //     64-feature block), rows added in order (no atomics: the same bits from run to run), an empty segment gives zeros.
-#include "wg_layer_parts.hpp"
+// The argument block, the self row and phases 2 and 3 live in wg_gin_parts.hpp, which wg_gine.hip (GINEConv) shares.
+#include "wg_gin_parts.hpp"
 
 namespace wgamd {
 namespace {
 
-constexpr int kUnroll = 8;
-
-struct gin_args {
-  const int* row_ptr;
-  const int* col;
-  int64_t n_rows;
-  const float* x;
-  int64_t ldx;
-  int F;
-  const void* src_ids;
-  const int64_t* self_rows;   // nullable; input row of destination i itself, < 0 = none
-  const float* x_dst;         // nullable; when set the self row of destination i is x_dst[i] (self_rows is not read)
-  int64_t ldx_dst;
-  const float* eps;           // nullable (0): ONE float on the device
-  const float* w1;            // [H, ldw1] row-major
-  int64_t ldw1;
-  int H;
-  const float* b1;
-  int relu1;
-  const float* w2;            // nullable: [N, ldw2] row-major
-  int64_t ldw2;
-  int N;
-  const float* b2;
-  int relu2;
-  float* out;                 // [n_rows, N], or [n_rows, H] when w2 is null
-  int64_t ldo;
-  float* agg_out;             // nullable
-  int64_t ld_agg;
-  float* hidden_out;          // nullable
-  int64_t ld_hidden;
-  int F16, SD;                // tile A: F rounded up to 16, floats per row
-  int H16, SH;                // tile B
-  float* partials;            // STATS: [tiles of the layer][2][H], this launch's tiles from tile0 on
-  int* counts;                // STATS: [tiles of the layer]
-  int64_t tile0;
-};
-
-// the self row of destination i as float4 chunks, or null
-template <int KIND>
-__device__ __forceinline__ const f32x4* self_row(const gin_args& a, int64_t i)
-{
-  if (a.x_dst) return reinterpret_cast<const f32x4*>(a.x_dst + i * a.ldx_dst);
-  if (a.self_rows == nullptr) return nullptr;
-  const int64_t self = a.self_rows[i];
-  return self >= 0 ? reinterpret_cast<const f32x4*>(x_row<KIND>(a.x, a.ldx, a.src_ids, self)) : nullptr;
-}
+constexpr int kUnroll = kGinUnroll;
 
 // The aggregate of destination row i, features [4 c, 4 c + 4) (c < F / 4)
 template <int KIND>
@@ -106,7 +62,7 @@ __global__ void __launch_bounds__(kThreads) gin_layer_kernel(gin_args a)
   // ---- phase 1: the aggregate rows of the tile -> LDS tile A (and agg_out) ----
   constexpr int kGroups = kThreads / LG;
   const int grp = tid / LG, c = tid % LG;
-  const int C4 = a.F / 4, C16 = a.F16 / 4;
+  const int C4 = a.F / 4;
   for (int r = grp; r < kTileRows; r += kGroups) {
     const int64_t i = row0 + r;
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
@@ -114,8 +70,7 @@ __global__ void __launch_bounds__(kThreads) gin_layer_kernel(gin_args a)
       v = aggregate_chunk<KIND>(a, i, c, c < C4, self_coef);
       if (a.agg_out && c < C4) reinterpret_cast<f32x4*>(a.agg_out + i * a.ld_agg)[c] = v;
     }
-    if (c < C16) reinterpret_cast<f32x4*>(tile + r * a.SD)[c] = c < C4 ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int cc = c + LG; cc < C16; cc += LG) reinterpret_cast<f32x4*>(tile + r * a.SD)[cc] = f32x4{0.f, 0.f, 0.f, 0.f};
+    store_agg_chunk<LG>(tile, a, r, c, v);
   }
   __syncthreads();
 
@@ -136,28 +91,7 @@ __global__ void __launch_bounds__(kThreads) gin_layer_kernel(gin_args a)
     if (tid == 0) a.counts[t] = rows_here;
     return;
   }
-  if (a.w2 == nullptr) {
-    tile_times_wt(tile, a.SD, a.F, a.F16, a.w1, a.ldw1, a.H, a.b1, a.relu1, a.out, a.ldo, row0, a.n_rows);
-    return;
-  }
-  float* hid = tile + kTileRows * a.SD;     // tile B: all 16 rows are computed (rows past n_rows hold act1(b1): never written out)
-  for (int idx = tid; idx < kTileRows * (a.H16 - a.H); idx += kThreads) {
-    const int r = idx / (a.H16 - a.H), n = a.H + idx % (a.H16 - a.H);
-    hid[r * a.SH + n] = 0.f;
-  }
-  tile_times_wt(tile, a.SD, a.F, a.F16, a.w1, a.ldw1, a.H, a.b1, a.relu1, hid, a.SH, 0, kTileRows);
-  __syncthreads();
-  if (a.hidden_out) {
-    const int H4 = a.H / 4;                 // (H % 4 == 0 with a second product: W2's rows are read as float4)
-    for (int idx = tid; idx < kTileRows * H4; idx += kThreads) {
-      const int r = idx / H4, q = idx % H4;
-      if (row0 + r < a.n_rows)
-        reinterpret_cast<f32x4*>(a.hidden_out + (row0 + r) * a.ld_hidden)[q] = reinterpret_cast<const f32x4*>(hid + r * a.SH)[q];
-    }
-  }
-
-  // ---- phase 3: [16 x H16] tile B @ W2^T ----
-  tile_times_wt(hid, a.SH, a.H, a.H16, a.w2, a.ldw2, a.N, a.b2, a.relu2, a.out, a.ldo, row0, a.n_rows);
+  gin_tile_products(a, tile, row0);
 }
 
 // aggregate only, any F: one wave per row, one feature per lane and 64-feature block
@@ -209,21 +143,7 @@ void launch_one(const gin_args& a, hipStream_t st)
 template <int KIND, bool STATS = false>
 void launch_layer(const gin_args& a, hipStream_t st)
 {
-  const int c4 = a.F / 4;
-  if (c4 <= 4) launch_one<KIND, 4, STATS>(a, st);
-  else if (c4 <= 8) launch_one<KIND, 8, STATS>(a, st);
-  else if (c4 <= 16) launch_one<KIND, 16, STATS>(a, st);
-  else if (c4 <= 32) launch_one<KIND, 32, STATS>(a, st);
-  else launch_one<KIND, 64, STATS>(a, st);
-}
-
-gin_args make_args(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx, int F, const void* src_ids,
-                   const int64_t* self_rows, const float* x_dst, int64_t ldx_dst, const float* eps)
-{
-  gin_args a{};
-  a.row_ptr = row_ptr, a.col = col, a.n_rows = n_rows, a.x = x, a.ldx = ldx, a.F = F, a.src_ids = src_ids;
-  a.self_rows = self_rows, a.x_dst = x_dst, a.ldx_dst = ldx_dst, a.eps = eps;
-  return a;
+  with_lane_group(a.F, [&](auto lg) { launch_one<KIND, decltype(lg)::value, STATS>(a, st); });
 }
 
 }  // namespace
@@ -263,7 +183,7 @@ extern "C" wholememory_error_code_t wgamd_gin_layer_f32_train(const int* row_ptr
         (x_dst && !aligned_rows(x_dst, ldx_dst)) || (agg_out && !aligned_rows(agg_out, ld_agg)) ||
         (hidden_out && !aligned_rows(hidden_out, ld_hidden)))
       throw logic_error("x / x_dst / w1 / w2 / agg_out / hidden_out rows must be 16-B aligned");
-    gin_args a = make_args(row_ptr, col, n_rows, x, ldx, F, src_ids, self_rows, x_dst, ldx_dst, eps);
+    gin_args a = make_gin_args(row_ptr, col, n_rows, x, ldx, F, src_ids, self_rows, x_dst, ldx_dst, eps);
     a.w1 = w1, a.ldw1 = ldw1, a.H = H, a.b1 = b1, a.relu1 = (flags & WGAMD_GIN_RELU_HIDDEN) != 0;
     a.w2 = w2, a.ldw2 = ldw2, a.N = N, a.b2 = b2, a.relu2 = (flags & WGAMD_GIN_RELU_OUT) != 0;
     a.out = out, a.ldo = ldo, a.agg_out = agg_out, a.ld_agg = ld_agg;
@@ -307,7 +227,7 @@ extern "C" wholememory_error_code_t wgamd_gin_layer_f32_stats(const int* row_ptr
     if (!aligned_rows(x, kind == 3 ? 0 : ldx) || !aligned_rows(w1, ldw1) || !aligned_rows(z_out, ldz) ||
         (x_dst && !aligned_rows(x_dst, ldx_dst)) || (agg_out && !aligned_rows(agg_out, ld_agg)))
       throw logic_error("x / x_dst / w1 / z_out / agg_out rows must be 16-B aligned");
-    gin_args a = make_args(row_ptr, col, n_rows, x, ldx, F, src_ids, self_rows, x_dst, ldx_dst, eps);
+    gin_args a = make_gin_args(row_ptr, col, n_rows, x, ldx, F, src_ids, self_rows, x_dst, ldx_dst, eps);
     a.w1 = w1, a.ldw1 = ldw1, a.H = H, a.b1 = b1;
     a.out = z_out, a.ldo = ldz, a.agg_out = agg_out, a.ld_agg = ld_agg;
     a.partials = partials, a.counts = counts, a.tile0 = tile0;
@@ -332,7 +252,7 @@ extern "C" wholememory_error_code_t wgamd_gin_aggregate_f32(const int* row_ptr, 
     WG_REQUIRE_INPUT((kind == 3 || ldx >= F) && ldo >= F && (x_dst == nullptr || ldx_dst >= F), "leading dimension too small");
     if ((reinterpret_cast<uintptr_t>(x) & 3) || (x_dst && (reinterpret_cast<uintptr_t>(x_dst) & 3)))
       throw logic_error("x / x_dst must be 4-B aligned");
-    gin_args a = make_args(row_ptr, col, n_rows, x, ldx, F, src_ids, self_rows, x_dst, ldx_dst, eps);
+    gin_args a = make_gin_args(row_ptr, col, n_rows, x, ldx, F, src_ids, self_rows, x_dst, ldx_dst, eps);
     a.out = out, a.ldo = ldo;
     auto st = static_cast<hipStream_t>(stream);
     const unsigned blocks = (unsigned)((n_rows + 3) / 4);

@@ -450,6 +450,20 @@ SYMBOLS = {
     "wgamd_gatv2_edge_bwd_src_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                              c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                              c_int64, c_void_p, c_int64, c_int, c_void_p]),
+    # GIN layer with edge features (wg_gine.hip)
+    "wgamd_gine_layer_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "wgamd_gine_bwd_blocks": (c_int64, [c_int64, c_int]),
+    "wgamd_gine_layer_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                     c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p,
+                                     c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "wgamd_gine_layer_f32_train": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                           c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p,
+                                           c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                           c_int64, c_void_p, c_void_p]),
+    "wgamd_gine_bwd_dst_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64,
+                                       c_void_p]),
+    "wgamd_gine_bwd_src_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_int64, c_void_p]),
     # NormDropoutAct (wg_norm_act.hip)
     "wgamd_norm_act_supported": (c_int, [c_int]),
     "wgamd_norm_act_segment_seed": (c_ulonglong, [c_ulonglong, c_int]),

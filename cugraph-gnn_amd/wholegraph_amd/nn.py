@@ -3858,11 +3858,12 @@ class GINConv(torch.nn.Module):
                 m.reset_parameters()
         self.eps.data.fill_(self.initial_eps)
 
-    def _plan(self):
-        """``(route, lin1, relu1, lin2, rest)``: the leading modules the kernel runs and the ones that follow it."""
+    def _plan(self, bn_route: bool = True):
+        """``(route, lin1, relu1, lin2, rest)``: the leading modules the kernel runs and the ones that follow it (``bn_route``
+        False: no ``"mlp_bn"`` — such an ``MLP`` goes by its ``flat_modules()``)."""
         if isinstance(self.nn, MLP):
             m = self.nn
-            bn = m.norms[0].module if m.norm == "batch_norm" and len(m.norms) == 1 else None
+            bn = m.norms[0].module if bn_route and m.norm == "batch_norm" and len(m.norms) == 1 else None
             if (bn is not None and len(m.lins) == 2 and m.act == "relu" and not m.act_first and m.plain_last and m.dropout[0] == 0.0
                     and bn.affine and bn.track_running_stats and isinstance(bn.momentum, float)
                     and gin_layer_supported(*m.channel_list)):
@@ -4631,6 +4632,391 @@ class GATv2EdgeConv(GATv2Conv):
         if torch.is_tensor(act):
             raise TypeError("GATv2EdgeConv: the third positional argument is act; pass the edge attributes as edge_attr=")
         return self._run(x, graph, act, edge_attr)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# GIN with edge features (torch_geometric.nn.GINEConv) — csrc/wg_gine.hip
+# ---------------------------------------------------------------------------------------------------------------------
+def gine_layer_supported(F_: int, H: int, N: int = 0, D: int = 0) -> bool:
+    """Shapes of the one-kernel GINE layer (``wgamd_gine_layer_supported``): ``gin_layer_supported(F, H, N)`` and D == 0 (edge
+    rows of width F, no edge Linear) or 1 <= D <= 16."""
+    return bool(L.lib().wgamd_gine_layer_supported(int(F_), int(H), int(N), int(D)))
+
+
+def _gine_edge_args(edge_attr, w_edge_t, b_edge, F_: int, n_edges: int):
+    """``edge_attr, w_edge_t, b_edge, D`` of the layer launch, checked: ``edge_attr`` [E, D] in CSR slot order with ``w_edge_t``
+    [D, F] (the edge Linear's weight transposed) and ``b_edge`` [F] or None; [E, F] and D = 0 without a weight."""
+    D = 0 if w_edge_t is None else int(w_edge_t.shape[0])
+    assert edge_attr.dtype == torch.float32 and edge_attr.is_cuda and edge_attr.is_contiguous()
+    assert tuple(edge_attr.shape) == (n_edges, D or F_), (tuple(edge_attr.shape), (n_edges, D or F_))
+    assert w_edge_t is None or (w_edge_t.dtype == torch.float32 and w_edge_t.is_contiguous() and tuple(w_edge_t.shape) == (D, F_))
+    assert b_edge is None or (w_edge_t is not None and b_edge.dtype == torch.float32 and b_edge.is_contiguous()
+                              and b_edge.numel() == F_)
+    return _nonempty(edge_attr, torch.float32).data_ptr(), _ptr(w_edge_t), _ptr(b_edge), D
+
+
+def _gine_mask_words(F_: int) -> int:
+    return (F_ + 31) // 32
+
+
+def gine_layer_forward(row_ptr, col, x, self_rows, edge_attr, w_edge_t=None, b_edge=None, w1=None, b1=None, w2=None, b2=None,
+                       eps=None, relu_hidden=True, relu_out=False, src_ids=None, x_dst=None, out=None, keep=False):
+    """A whole GINE layer over one hop in ONE kernel (``wgamd_gine_layer_f32``, include/wgamd_ext.h): ``gin_layer_forward`` whose
+    aggregate is ``sum_e relu(x[col[e]] + b_edge + edge_attr[e] @ w_edge_t) + (1 + eps) self row`` — ``edge_attr`` [E, D] in CSR
+    slot order, ``w_edge_t`` [D, F]; without ``w_edge_t`` the rows are F wide and added as they are.  ``w1 = None``: the launch
+    ends after the aggregate (output [n_rows, F]).  ``keep``: the ``_train`` launch, returning ``(out, agg, hidden, mask)`` — the
+    aggregate (``out`` itself without ``w1``), the hidden activation (None without ``w2``) and the ReLU mask as bits, int32
+    [E, ceil(F / 32)]: bit f of slot e is set where the message's feature f was positive."""
+    hop = _hop_args(row_ptr, col, x, src_ids) + _gin_hop_args(row_ptr, x, self_rows, x_dst, eps)
+    n_rows, F_, E, dev = row_ptr.shape[0] - 1, x.shape[1], int(col.shape[0]), row_ptr.device
+    assert w1 is not None or w2 is None
+    H = 0 if w1 is None else w1.shape[0]
+    N = 0 if w2 is None else w2.shape[0]
+    for w, k in ((w1, F_), (w2, H)):
+        assert w is None or (w.dtype == torch.float32 and w.stride(1) == 1 and w.shape[1] == k)
+    out = _out_rows(out, n_rows, N or H or F_, dev)
+    flags = (GIN_RELU_HIDDEN if relu_hidden else 0) | (GIN_RELU_OUT if relu_out else 0)
+    common = hop + _gine_edge_args(edge_attr, w_edge_t, b_edge, F_, E) + (
+        _ptr(w1), 0 if w1 is None else w1.stride(0), H, _ptr(b1), _ptr(w2), 0 if w2 is None else w2.stride(0), N, _ptr(b2), flags,
+        out.data_ptr(), out.stride(0))
+    if not keep:
+        L.check(L.lib().wgamd_gine_layer_f32(*common, get_stream()), "wgamd_gine_layer_f32")
+        return out
+    agg = torch.empty((n_rows, F_), dtype=torch.float32, device=dev) if w1 is not None else None
+    hidden = torch.empty((n_rows, H), dtype=torch.float32, device=dev) if w2 is not None else None
+    mask = torch.empty((E, _gine_mask_words(F_)), dtype=torch.int32, device=dev)
+    L.check(L.lib().wgamd_gine_layer_f32_train(*common, _ptr(agg), F_, _ptr(hidden), H, _nonempty(mask, torch.int32).data_ptr(),
+                                               get_stream()), "wgamd_gine_layer_f32_train")
+    return out, (out if agg is None else agg), hidden, mask
+
+
+def gine_bwd_dst(row_ptr, edge_attr, mask, dagg, max_blocks=None):
+    """The destination-major backward launch of one hop (``wgamd_gine_bwd_dst_f32``): per-workgroup partials [blocks, D + 1, F] of
+    the edge Linear's gradient — rows 0 .. D - 1 = d ``w_edge_t``, row D = d ``b_edge`` — from ``edge_attr`` [E, D], the forward's
+    ``mask`` and ``dagg`` [n_rows, F] alone; the gradient is their sum over the blocks.  The grid is bounded
+    (``wgamd_gine_bwd_blocks``: at most 4 workgroups per compute unit, tiles of 16 rows at a fixed stride); ``max_blocks`` forces
+    a smaller one."""
+    n_rows, F_, D, E = row_ptr.shape[0] - 1, int(dagg.shape[1]), int(edge_attr.shape[1]), int(edge_attr.shape[0])
+    assert row_ptr.dtype == torch.int32 and row_ptr.is_cuda and row_ptr.is_contiguous() and gine_layer_supported(F_, 1, 0, D) and D >= 1
+    assert edge_attr.dtype == torch.float32 and edge_attr.is_contiguous() and _kernel_rows_ok(dagg) and dagg.shape[0] == n_rows
+    assert mask.dtype == torch.int32 and mask.is_contiguous() and tuple(mask.shape) == (E, _gine_mask_words(F_))
+    blocks = int(L.lib().wgamd_gine_bwd_blocks(n_rows, 0 if max_blocks is None else int(max_blocks)))
+    part = torch.empty((blocks, D + 1, F_), dtype=torch.float32, device=dagg.device)
+    if n_rows > 0:
+        L.check(L.lib().wgamd_gine_bwd_dst_f32(row_ptr.data_ptr(), n_rows, _nonempty(edge_attr, torch.float32).data_ptr(), D,
+                                               _nonempty(mask, torch.int32).data_ptr(), dagg.data_ptr(), dagg.stride(0), F_,
+                                               part.data_ptr(), blocks, get_stream()), "wgamd_gine_bwd_dst_f32")
+    return part
+
+
+def gine_bwd_src(row_ptr_t, col_t, perm, mask, dagg, self_t=None, eps=None, gx=None):
+    """The source-major backward launch of one hop over its transpose (``wgamd_gine_bwd_src_f32``): ``gx[j]`` = the sum over the
+    entries of input row j of ``dagg[col_t]`` where the bit of the entry's CSR slot (``perm``) is set, plus ``(1 + eps)
+    dagg[self_t[j]]`` where ``self_t`` (int64 [n_src], None: nowhere) is >= 0.  Every row of ``gx`` [n_src, F] is written."""
+    n_src, F_ = row_ptr_t.shape[0] - 1, int(dagg.shape[1])
+    assert row_ptr_t.dtype == col_t.dtype == perm.dtype == torch.int32 and gine_layer_supported(F_, 1, 0, 0) and _kernel_rows_ok(dagg)
+    assert mask.dtype == torch.int32 and mask.is_contiguous() and tuple(mask.shape) == (int(col_t.shape[0]), _gine_mask_words(F_))
+    assert self_t is None or (self_t.dtype == torch.int64 and self_t.is_contiguous() and self_t.shape[0] == n_src)
+    gx = _out_rows(gx, n_src, F_, dagg.device)
+    assert _kernel_rows_ok(gx)
+    L.check(L.lib().wgamd_gine_bwd_src_f32(row_ptr_t.data_ptr(), _nonempty(col_t, torch.int32).data_ptr(), perm.data_ptr(), n_src,
+                                           _nonempty(mask, torch.int32).data_ptr(), _nonempty(dagg, torch.float32).data_ptr(),
+                                           dagg.stride(0), F_, _ptr(self_t), _ptr(eps), gx.data_ptr(), gx.stride(0), get_stream()),
+            "wgamd_gine_bwd_src_f32")
+    return gx
+
+
+def _gine_aggregate_torch(x, x_dst, eps, wet, be, ea, lg: LayerGraph, no_root: bool):
+    """PyG's formulation of the GINE aggregate in torch ops: ``ea`` hop-major [E, D] with ``wet`` [D, F] (and ``be``), or [E, F]."""
+    aggs = []
+    for h, rows, edges in _hops(lg):
+        n, E = h.n_rows, int(h.col.shape[0])
+        agg = torch.zeros((n, x.shape[1]), dtype=x.dtype, device=x.device)
+        if E > 0:
+            e = ea[edges].to(x.dtype)
+            if wet is not None:
+                e = e @ wet.to(x.dtype) if be is None else torch.addmm(be.to(x.dtype), e, wet.to(x.dtype))
+            agg = agg.index_add(0, _edge_dst(h.row_ptr, E), torch.relu(x[h.col.long()] + e))
+        if not no_root:
+            agg = agg + (1.0 + eps.to(x.dtype)) * (x_dst[rows] if x_dst is not None else x[h.self_rows])
+        aggs.append(agg)
+    if not aggs:
+        return torch.zeros((0, x.shape[1]), dtype=x.dtype, device=x.device)
+    return aggs[0] if len(aggs) == 1 else torch.cat(aggs)
+
+
+class _GineLayer(torch.autograd.Function):
+    """The one-kernel GINE layer over a ``LayerGraph``: one ``wgamd_gine_layer_f32`` launch per hop; under autograd the ``_train``
+    form keeps the aggregate, the hidden activation and the messages' ReLU mask as bits.  ``ea``: the hop-major edge rows (no
+    gradient), ``wet`` / ``be``: the edge Linear's weight transposed [D, F] and bias, or None (rows of width F).  ``w1 = None``:
+    the aggregate alone.  Backward, no atomics: the dense half as ``_GinLayer`` (``_dz``, ``wgamd_gcn_wgrad_f32``, library GEMMs
+    down to ``dAgg = dZ1 W1``), then per hop ``wgamd_gine_bwd_dst_f32`` (d wet, d be: partials added in hop and block order) and
+    ``wgamd_gine_bwd_src_f32`` over the hop's transpose (the input rows); a ReLU sits on every edge, so — unlike GIN — the input
+    gradient is no layer kernel over the transpose.  A backward under ``create_graph=True`` runs out of torch ops."""
+
+    @staticmethod
+    def forward(ctx, src, x_dst, eps, w1, b1, w2, b2, wet, be, ea, graph, ids, relu_hidden, relu_out, n_src, no_root):
+        F_ = src.shape[1]
+        keep = any(ctx.needs_input_grad[:9])
+        dev = ea.device
+        n = graph.n_rows
+        out = torch.empty((n, w2.shape[0] if w2 is not None else (w1.shape[0] if w1 is not None else F_)), dtype=torch.float32, device=dev)
+        agg = torch.empty((n, F_), dtype=torch.float32, device=dev) if keep and w1 is not None else None
+        hidden = torch.empty((n, w1.shape[0]), dtype=torch.float32, device=dev) if keep and w2 is not None else None
+        masks = []
+        for h, rows, edges in _hops(graph):
+            mask = None
+            if h.n_rows > 0:
+                self_rows, xd = _gin_hop_self(h, rows, _detached(x_dst), no_root)
+                res = gine_layer_forward(h.row_ptr, h.col, src, self_rows, ea[edges], *_detached((wet, be, w1, b1, w2, b2)),
+                                         eps=_detached(eps), relu_hidden=relu_hidden, relu_out=relu_out, src_ids=ids, x_dst=xd,
+                                         out=out[rows], keep=keep)
+                if keep:
+                    mask = res[3]
+                    if agg is not None:
+                        agg[rows] = res[1]
+                    if hidden is not None:
+                        hidden[rows] = res[2]
+            masks.append(mask)
+        if keep:
+            ctx.save_for_backward(src if ids is None else None, w1, b1, w2, b2, wet, be, eps, out, x_dst)
+            ctx.kept = (out if w1 is None else agg, hidden, masks, ea)
+            ctx.src = src
+            ctx.graph, ctx.ids, ctx.flags, ctx.n_src, ctx.no_root = graph, ids, (relu_hidden, relu_out), n_src, no_root
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            return _gine_double_backward(ctx, g)
+        _released(ctx.kept, "GINEConv", "activations and mask bits")
+        _, w1, _, w2, _, wet, _, eps, out, x_dst = ctx.saved_tensors
+        agg, hidden, masks, ea = ctx.kept
+        relu_hidden, relu_out = ctx.flags
+        need_x, need_xd, need_eps, need_w1, need_b1, need_w2, need_b2, need_wet, need_be = ctx.needs_input_grad[:9]
+        graph, dev, F_ = ctx.graph, g.device, agg.shape[1]
+        gw1 = gb1 = gw2 = gb2 = gx = gxd = geps = gwet = gbe = None
+        if w1 is None:
+            d_agg = g.contiguous().float()
+        else:
+            if w2 is not None:
+                g, _ = _dz(g, out, relu_out)
+                if need_w2 or need_b2:
+                    gw2, gb2 = _dense_wgrad(graph, hidden, g, w2, need_b2, None)
+                    gw2 = gw2 if need_w2 else None
+                g1, _ = _dz(g @ w2, hidden, relu_hidden)                        # dHidden: one library GEMM
+            else:
+                g1, _ = _dz(g, out, relu_hidden)
+            if need_w1 or need_b1:
+                gw1, gb1 = _dense_wgrad(graph, agg, g1, w1, need_b1, None)
+                gw1 = gw1 if need_w1 else None
+            d_agg = g1 @ w1 if graph.n_rows > 0 else torch.zeros((0, F_), dtype=torch.float32, device=dev)
+        if (need_wet or need_be) and wet is not None:
+            total = torch.zeros((wet.shape[0] + 1, F_), dtype=torch.float32, device=dev)
+            for k, (h, rows, edges) in enumerate(_hops(graph)):
+                if h.n_rows > 0 and h.col.shape[0] > 0:
+                    total += gine_bwd_dst(h.row_ptr, ea[edges], masks[k], d_agg[rows]).sum(0)
+            gwet, gbe = (total[:-1] if need_wet else None), (total[-1] if need_be else None)
+        has_self = not ctx.no_root and x_dst is None
+        if need_x:
+            def per_hop(h, rows, _, k):
+                row_ptr_t, col_t, _, perm = h.transposed(ctx.n_src, need_self=False, need_perm=True)
+                return gine_bwd_src(row_ptr_t, col_t, perm, masks[k], d_agg[rows], h.input_dst(ctx.n_src) if has_self else None, eps)
+            gx = _sum_over_hops(graph, (ctx.n_src, F_), dev, per_hop)
+        if need_xd:
+            gxd = torch.zeros_like(x_dst, dtype=torch.float32)
+            gxd[:d_agg.shape[0]] = (1.0 + eps) * d_agg
+        if need_eps:
+            geps = torch.zeros_like(eps) if ctx.no_root else (d_agg * _gin_self_rows(ctx.src, ctx.ids, x_dst, graph)).sum().reshape(eps.shape)
+        ctx.kept = ctx.src = None
+        return (gx, gxd, geps, gw1, gb1, gw2, gb2, gwet, gbe) + (None,) * 7
+
+
+def _gine_double_backward(ctx, g):
+    """The gradients as differentiable torch expressions of the saved inputs and ``g``."""
+    src, w1, b1, w2, b2, wet, be, eps, _, x_dst = ctx.saved_tensors
+    relu_hidden, relu_out = ctx.flags
+    if src is None:
+        raise _lazy_table_grad_error()
+
+    def make_y():
+        y = _gine_aggregate_torch(src, x_dst, eps, wet, be, ctx.kept[3], ctx.graph, ctx.no_root)
+        for w, b, relu in ((w1, b1, relu_hidden), (w2, b2, relu_out)):
+            if w is not None:
+                y = torch.nn.functional.linear(y, w, b)
+                y = torch.relu(y) if relu else y
+        return y
+    ins = [(i, t) for i, t in enumerate((src, x_dst, eps, w1, b1, w2, b2, wet, be)) if ctx.needs_input_grad[i]]
+    return tuple(_grads_from_torch(make_y, ins, g, [None] * 16))
+
+
+class GINEConv(GINConv):
+    """PyG ``GINEConv`` (``flow="source_to_target"``): ``x'_i = nn((1 + eps) x_i + sum_{j -> i} ReLU(x_j + lin(e_ji)))`` — GIN
+    whose message takes the edge's features; loops and duplicate edges are ordinary edges, the root term carries no edge row.
+    A class of its own next to ``GINConv`` (which keeps refusing every extra keyword).  ``eps`` and ``nn.*`` as ``GINConv``;
+    with ``edge_dim=D`` the layer owns ``lin = Linear(D, in_channels)`` (``lin.weight``, ``lin.bias``; ``in_channels`` from the
+    first ``Linear`` of ``nn`` or ``channel_list[0]`` of an ``MLP``, ValueError when it cannot be inferred), so a state dict of
+    PyG's ``GINEConv(nn, edge_dim=D)`` loads with ``strict=True``; with ``edge_dim=None`` there is no ``lin`` and the edge rows
+    are as wide as x.
+
+    ``forward(x, graph, act=None, edge_attr=None)``: ``x``, ``graph`` and ``act`` as ``GINConv`` takes them; ``edge_attr``
+    (required, keyword) is [E, edge_dim] floating point — [E] with ``edge_dim == 1`` — on the graph's device, in the order of the
+    graph's edges: COO order for an ``edge_index``, CSR order for a ``[csr_row_ptr, csr_col_ind]`` pair, hop-major for a
+    ``LayerGraph`` (``CallGroup.edge_attr(name)``: every layer takes the same tensor and reads the prefix of its hops).
+    ValueError for a missing tensor or a wrong dtype, width, length or device; a tensor in the ``act`` position is a TypeError.
+
+    ``route`` names what runs for float32 device tensors inside ``gine_layer_supported`` (``gin_layer_supported`` and
+    edge_dim <= 16) — per hop ONE launch forward (``wgamd_gine_layer_f32``: the edge weight in LDS, the [E, F] projected rows and
+    messages never written) and two backward over mask bits, without atomics:
+    * ``"mlp"`` — ``Sequential(Linear, ReLU, Linear)`` or ``MLP([F, H, N], norm=None)``: the whole layer in the kernel;
+    * ``"linear"`` — ``nn`` starts with a ``Linear`` (a ``ReLU`` behind it folded in): the aggregate and that product in the
+      kernel, the rest runs as it is (an ``MLP`` with batch norm lands here: there is no fused batch-norm route);
+    * ``"aggregate"`` — any other ``nn``: the kernel ends after the aggregate, then ``nn`` runs;
+    * ``"torch"`` — the same formula out of torch ops under ordinary autograd: CPU tensors, shapes outside the domain,
+      ``edge_attr.requires_grad``, non-float32 parameters or inputs, a double backward.
+    Refused as ``GINConv`` refuses them: ``HeteroLayerGraph`` and ``HeteroConv`` relations, an ``(x_src, x_dst)`` pair over a
+    ``LayerGraph``, HIP-graph capture, a gradient into a lazily read table."""
+
+    def __init__(self, nn: torch.nn.Module, eps: float = 0.0, train_eps: bool = False, edge_dim: Optional[int] = None):
+        super().__init__(nn, eps=eps, train_eps=train_eps)
+        if edge_dim is not None and (isinstance(edge_dim, bool) or not isinstance(edge_dim, int) or edge_dim < 1):
+            raise ValueError("GINEConv: edge_dim must be a positive int or None")
+        self.edge_dim = edge_dim
+        self.lin = None
+        if edge_dim is not None:
+            if self.in_channels is None:
+                raise ValueError("GINEConv: could not infer the input channels from nn (its first module is no Linear or MLP); "
+                                 "edge_dim needs them for lin = Linear(edge_dim, in_channels)")
+            self.lin = torch.nn.Linear(edge_dim, self.in_channels)
+
+    @property
+    def in_channels(self):
+        """The layer's input width as PyG infers it — the first ``Linear`` of ``nn`` or an ``MLP``'s ``channel_list[0]`` — or None."""
+        first = self.nn[0] if isinstance(self.nn, torch.nn.Sequential) and len(self.nn) > 0 else self.nn
+        if isinstance(first, MLP):
+            return int(first.channel_list[0])
+        return int(first.in_features) if isinstance(first, torch.nn.Linear) else None
+
+    def reset_parameters(self):
+        super().reset_parameters()
+        if self.lin is not None:
+            self.lin.reset_parameters()
+
+    def _route(self, F_):
+        """``(route, lin1, relu1, lin2, rest)`` for an input ``F_`` wide (None: not known before the first call)."""
+        route, lin1, relu1, lin2, rest = self._plan(bn_route=False)
+        params = [p for p in self.parameters()] + [self.eps]
+        D = self.edge_dim or 0
+        H, N = (lin1.out_features, lin2.out_features if lin2 is not None else 0) if lin1 is not None else (1, 0)
+        F_ = lin1.in_features if lin1 is not None else F_
+        if (not all(p.is_cuda and p.dtype == torch.float32 for p in params)
+                or (F_ is not None and not gine_layer_supported(F_, H, N, D)) or D > 16):
+            return "torch", None, False, None, [self.nn]
+        return route, lin1, relu1, lin2, rest
+
+    @property
+    def route(self) -> str:
+        """``"mlp"``, ``"linear"``, ``"aggregate"`` or ``"torch"``: what ``nn``'s form, the shapes and the parameters select."""
+        return self._route(self.in_channels)[0]
+
+    def _checked_edge_attr(self, edge_attr, n_edges: int, device, F_: int):
+        D = self.edge_dim
+        if edge_attr is None:
+            raise ValueError("GINEConv: the layer needs edge_attr")
+        if not torch.is_tensor(edge_attr) or not edge_attr.is_floating_point():
+            raise ValueError("GINEConv: edge_attr must be a floating-point tensor")
+        if edge_attr.dim() == 1 and D == 1:
+            edge_attr = edge_attr.unsqueeze(1)
+        if edge_attr.dim() != 2 or edge_attr.shape[1] != (D or F_):
+            raise ValueError("GINEConv: edge_attr has shape %s, the layer takes [E, %d]" % (tuple(edge_attr.shape), D or F_))
+        if device is not None and edge_attr.device != torch.device(device):
+            raise ValueError("GINEConv: edge_attr is on %s, the graph on %s" % (edge_attr.device, torch.device(device)))
+        if edge_attr.shape[0] != n_edges:
+            raise ValueError("GINEConv: edge_attr has %d rows for %d edges" % (edge_attr.shape[0], n_edges))
+        return edge_attr
+
+    def _forward_layer(self, x, lg: LayerGraph, act=None, x_dst=None, no_root=False, edge_attr=None):
+        assert act in (None, "relu"), "act: None or 'relu'"
+        relu = act == "relu"
+        x = _x16_as_rows(x)
+        lazy = isinstance(x, LazyRows)
+        F_ = x.shape[1]
+        if x_dst is not None and x_dst.shape[1] != F_:
+            raise ValueError("GINEConv: x_dst has %d features, x_src %d" % (x_dst.shape[1], F_))
+        if self.lin is not None and self.lin.out_features != F_:
+            raise ValueError("GINEConv: x has %d features, lin gives the edges %d" % (F_, self.lin.out_features))
+        src, ids, n_src, _ = _layer_input(self, x, lg, F_)
+        ea = edge_attr
+        route, lin1, relu1, lin2, rest = self._route(F_)
+        ws = [t for m in (lin1, lin2) if m is not None for t in (m.weight, m.bias) if t is not None]
+        ok = (route != "torch" and all(t.is_cuda and t.dtype == torch.float32 for t in (src, x_dst, ea) if t is not None)
+              and not (ea.requires_grad and torch.is_grad_enabled()) and (lin1 is None or lin1.in_features == F_)
+              and all(_kernel_rows_ok(t) if t.dim() == 2 else t.is_contiguous() for t in ws))
+        if not ok:
+            wet, be = (None, None) if self.lin is None else (self.lin.weight.t(), self.lin.bias)
+            xs = x.materialize() if lazy else x
+            out = self.nn(_gine_aggregate_torch(xs, x_dst, self.eps, wet, be, ea, lg, no_root))
+            return torch.relu(out) if relu else out
+        if lazy and not _kernel_rows_ok(src):
+            x, lazy = x.materialize(), False
+            src, ids = x, None
+        if not lazy and not _kernel_rows_ok(src):
+            src = x = x.contiguous()
+        if x_dst is not None and not _kernel_rows_ok(x_dst):
+            x_dst = x_dst.contiguous()
+        wet = be = None
+        if self.lin is not None:
+            wet = _derived(self, "lin_t", (self.lin.weight,), lambda: self.lin.weight.t().contiguous(),
+                           grad=_needs_grad((self.lin.weight,)))
+            be = self.lin.bias
+        fuse_act = relu and not rest                            # the layer's ReLU rides in the kernel when nothing follows it
+        tail = (lg, ids, True if lin2 is not None else (relu1 or fuse_act), fuse_act and lin2 is not None, n_src, no_root)
+        if lin1 is None:                                        # "aggregate": nothing to fuse
+            fuse_act, tail = False, (lg, ids, False, False, n_src, no_root)
+        out = _GineLayer.apply(src, x_dst, self.eps, lin1 and lin1.weight, lin1 and lin1.bias, lin2 and lin2.weight, lin2 and lin2.bias,
+                               wet, be, ea.detach().contiguous(), *tail)
+        for m in rest:
+            out = m(out)
+        return torch.relu(out) if relu and not fuse_act else out
+
+    def forward(self, x, graph, act=None, edge_attr=None):
+        if torch.is_tensor(act):
+            raise TypeError("GINEConv: the third positional argument is act; pass the edge attributes as edge_attr=")
+        _refuse_capture(self, "per-graph caches")              # (the hops' transposes, cached against the graph object)
+        x_dst, pair = None, False
+        if isinstance(x, (tuple, list)):
+            (x, x_dst), pair = x, True
+        _refuse_featureless(self, x)
+        if x_dst is not None:
+            _refuse_featureless(self, x_dst)
+        if isinstance(graph, HeteroLayerGraph):
+            raise NotImplementedError("GINEConv over a heterogeneous call group's layer graph is not supported")
+        if isinstance(graph, LayerGraph):
+            if pair:
+                raise NotImplementedError("GINEConv: an (x_src, x_dst) pair over a LayerGraph is not supported")
+            total = getattr(graph, "num_group_edges", None)       # (a call group's: every layer reads the prefix of its hops)
+            ea = self._checked_edge_attr(edge_attr, sum(int(h.col.shape[0]) for h in graph.hops) if total is None else total,
+                                         graph.hops[0].row_ptr.device if graph.hops else None, x.shape[1])
+            return self._forward_layer(x, graph, act, edge_attr=ea)
+        if isinstance(x, LazyRows):
+            x = x.materialize()
+        if isinstance(x_dst, LazyRows):
+            x_dst = x_dst.materialize()
+        if isinstance(graph, (tuple, list)):
+            n_dst = int(graph[0].shape[0]) - 1
+        elif not pair:
+            n_dst = x.shape[0]
+        elif x_dst is not None:
+            n_dst = x_dst.shape[0]
+        else:                                                   # (x_src, None): as many rows as the edges reach (one read-back)
+            n_dst = int(graph[1].max()) + 1 if graph.shape[1] > 0 else 0
+        have = x.shape[0] if not pair else (x_dst.shape[0] if x_dst is not None else n_dst)
+        if have < n_dst:
+            raise ValueError("GINEConv: %d destination rows for %d destinations" % (have, n_dst))
+        ea = self._checked_edge_attr(edge_attr, graph[1].shape[0], graph[0].device, x.shape[1])
+        lg, _, ea = _single_hop(graph, n_dst, ea)
+        return self._forward_layer(x, lg, act, x_dst=None if x_dst is None else x_dst[:n_dst], no_root=pair and x_dst is None,
+                                   edge_attr=ea)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -13,8 +13,10 @@ one-hot degree (padded to a multiple of 4, as the TU datasets without features g
 whole graphs concatenated as PyG's `Batch` does: node ids shifted per graph, one COO `edge_index`, a sorted `batch` vector
 and its `ptr`.
 
-    python examples/gin_graph_classification.py [--graphs 4000] [--epochs 10] [--batch-norm] [--torch-ops [--float64] [--device cpu]]
+    python examples/gin_graph_classification.py [--graphs 4000] [--epochs 10] [--batch-norm] [--edge-dim D] [--torch-ops [--float64] [--device cpu]]
 
+`--edge-dim D` plants random edge attributes [E, D] and builds every layer as
+`wholegraph_amd.nn.GINEConv(Sequential(Linear, ReLU, Linear), edge_dim=D)` (ONE kernel per layer too).
 `--torch-ops` runs the same model on the same data in plain torch ops (`index_add_`, `F.linear`, `relu`) — the yardstick of
 the accuracy (tests/test_gpu_gin_example.py), on any device.  Prints the loss per epoch, the test accuracy, and one JSON line.
 """
@@ -75,13 +77,13 @@ def collate(data, gids):
     nodes, edges = _ranges(node_ptr[gids], n_nodes), _ranges(edge_ptr[gids], n_edges)
     shift = torch.repeat_interleave(ptr[:-1] - node_ptr[gids], n_edges, output_size=edges.shape[0])
     batch = torch.repeat_interleave(torch.arange(gids.shape[0], device=gids.device), n_nodes, output_size=nodes.shape[0])
-    return x[nodes], edge_index[:, edges] + shift, batch, ptr, y[gids]
+    return x[nodes], edge_index[:, edges] + shift, batch, ptr, y[gids], edges
 
 
 class GIN(torch.nn.Module):
-    def __init__(self, in_channels, hidden, classes, num_layers, dropout, torch_ops, batch_norm=False):
+    def __init__(self, in_channels, hidden, classes, num_layers, dropout, torch_ops, batch_norm=False, edge_dim=0):
         super().__init__()
-        from wholegraph_amd.nn import MLP, GINConv
+        from wholegraph_amd.nn import MLP, GINConv, GINEConv
         self.torch_ops = torch_ops
         self.convs = torch.nn.ModuleList()
         for _ in range(num_layers):
@@ -89,17 +91,20 @@ class GIN(torch.nn.Module):
                 mlp = MLP([in_channels, hidden, hidden])
             else:
                 mlp = torch.nn.Sequential(torch.nn.Linear(in_channels, hidden), torch.nn.ReLU(), torch.nn.Linear(hidden, hidden))
-            self.convs.append(GINConv(mlp, train_eps=False))
+            self.convs.append(GINEConv(mlp, train_eps=False, edge_dim=edge_dim) if edge_dim else GINConv(mlp, train_eps=False))
             in_channels = hidden
         self.head = torch.nn.Sequential(torch.nn.Linear(hidden, hidden), torch.nn.ReLU(), torch.nn.Dropout(dropout),
                                         torch.nn.Linear(hidden, classes))
 
-    def forward(self, x, edge_index, batch, ptr):
+    def forward(self, x, edge_index, batch, ptr, edge_attr=None):
         from wholegraph_amd.nn import global_add_pool
         n_graphs = ptr.shape[0] - 1
         if self.torch_ops:                                 # the same model restated in plain torch ops
             for conv in self.convs:
-                agg = torch.zeros_like(x).index_add_(0, edge_index[1], x[edge_index[0]]) + (1.0 + conv.eps.to(x.dtype)) * x
+                msg = x[edge_index[0]]
+                if edge_attr is not None:                  # GINEConv: the [E, F] projected rows and messages, written out
+                    msg = F.relu(msg + F.linear(edge_attr, conv.lin.weight, conv.lin.bias))
+                agg = torch.zeros_like(x).index_add_(0, edge_index[1], msg) + (1.0 + conv.eps.to(x.dtype)) * x
                 if isinstance(conv.nn, torch.nn.Sequential):
                     lin1, _, lin2 = conv.nn
                     x = F.relu(F.linear(F.relu(F.linear(agg, lin1.weight, lin1.bias)), lin2.weight, lin2.bias))
@@ -107,8 +112,8 @@ class GIN(torch.nn.Module):
                     x = F.relu(conv.nn(agg))
             pooled = torch.zeros((n_graphs, x.shape[1]), dtype=x.dtype, device=x.device).index_add_(0, batch, x)
         else:
-            for conv in self.convs:
-                x = conv(x, edge_index, act="relu")        # one kernel: conv(x, edge_index).relu() of the reference's model
+            for conv in self.convs:                        # one kernel: conv(x, edge_index).relu() of the reference's model
+                x = conv(x, edge_index, act="relu") if edge_attr is None else conv(x, edge_index, act="relu", edge_attr=edge_attr)
             pooled = global_add_pool(x, batch, size=n_graphs, ptr=ptr)
         return self.head(pooled)
 
@@ -126,6 +131,8 @@ def main():
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--train-split", type=float, default=0.9)
     ap.add_argument("--batch-norm", action="store_true", help="layers GINConv(nn.MLP([in, hidden, hidden])): a BatchNorm1d between the Linears")
+    ap.add_argument("--edge-dim", type=int, default=0, help="D > 0: random edge attributes [E, D] and layers GINEConv(Sequential(Linear, "
+                    "ReLU, Linear), edge_dim=D)")
     ap.add_argument("--torch-ops", action="store_true", help="plain torch ops instead of the HIP layer (the accuracy yardstick)")
     ap.add_argument("--float64", action="store_true", help="with --torch-ops: float64")
     ap.add_argument("--device", default="cuda")
@@ -139,7 +146,9 @@ def main():
     data = (data[0].to(dev, dtype),) + tuple(t.to(dev) for t in data[1:])
     n_train = int(args.train_split * args.graphs)
     torch.manual_seed(0)                                   # (parameters are drawn on the CPU: the same on every route)
-    model = GIN(data[0].shape[1], args.hidden, 2, args.num_layers, args.dropout, args.torch_ops, args.batch_norm).to(dev, dtype)
+    assert not (args.edge_dim and args.batch_norm), "--edge-dim builds Sequential(Linear, ReLU, Linear) layers"
+    edge_attr = torch.randn((data[1].shape[1], args.edge_dim), generator=torch.Generator().manual_seed(2)).to(dev, dtype) if args.edge_dim else None
+    model = GIN(data[0].shape[1], args.hidden, 2, args.num_layers, args.dropout, args.torch_ops, args.batch_norm, args.edge_dim).to(dev, dtype)
     opt = torch.optim.Adam(model.parameters(), lr=args.lr)
     order = torch.Generator().manual_seed(1)
     losses = []
@@ -148,8 +157,8 @@ def main():
         t0, total = time.perf_counter(), 0.0
         perm = torch.randperm(n_train, generator=order).to(dev)
         for at in range(0, n_train, args.batch_size):
-            x, ei, batch, ptr, y = collate(data, perm[at:at + args.batch_size])
-            loss = F.cross_entropy(model(x, ei, batch, ptr), y)
+            x, ei, batch, ptr, y, edges = collate(data, perm[at:at + args.batch_size])
+            loss = F.cross_entropy(model(x, ei, batch, ptr, None if edge_attr is None else edge_attr[edges]), y)
             opt.zero_grad(set_to_none=True)
             loss.backward()
             opt.step()
@@ -161,8 +170,8 @@ def main():
     with torch.no_grad():
         for at in range(n_train, args.graphs, args.batch_size):
             gids = torch.arange(at, min(at + args.batch_size, args.graphs), device=dev)
-            x, ei, batch, ptr, y = collate(data, gids)
-            correct += int((model(x, ei, batch, ptr).argmax(1) == y).sum())
+            x, ei, batch, ptr, y, edges = collate(data, gids)
+            correct += int((model(x, ei, batch, ptr, None if edge_attr is None else edge_attr[edges]).argmax(1) == y).sum())
     acc = correct / max(args.graphs - n_train, 1)
     print(f"test accuracy {acc:.4f} over {args.graphs - n_train} graphs")
     print(json.dumps({"first_loss": losses[0], "last_loss": losses[-1], "test_accuracy": acc}))

@@ -1338,6 +1338,47 @@ wholememory_error_code_t wgamd_gatv2_edge_bwd_src_f32(const int* row_ptr_t, cons
                                                       const float* de, const float* g, int64_t ldg, float* gx, int64_t ldgx,
                                                       int accumulate, void* stream);
 
+/* ---- GIN layer with edge features (csrc/wg_gine.hip): torch_geometric.nn.GINEConv with the GIN paper's MLP over a sampled hop --------
+ *   m_e    = X[j] + b_edge + w_edge_t^T edge_attr[e]                   e = (j -> i), edge_attr [E, D] in CSR slot order
+ *   agg[i] = sum_e max(m_e, 0)  +  (1 + eps) XS[i]                     (every edge: loops and duplicates too; no edge row at the root)
+ *   out[i] = act2(act1(agg[i] @ W1^T + b1) @ W2^T + b2)                everything else as wgamd_gin_layer_f32 takes it
+ * w_edge_t [D, F] = the edge Linear's weight transposed, b_edge [F] nullable, both contiguous.  D == 0: edge_attr is [E, F] (16-B
+ * aligned rows) and m_e = X[j] + edge_attr[e]; w_edge_t and b_edge are not read.  The projected edge rows and the messages are
+ * never written: the weight sits in LDS, a lane forms its four columns in registers.  With w1 null (H = N = 0, w2 null) the launch
+ * ends after the aggregate: out = agg [n_rows, F].  _train also writes agg_out / hidden_out (nullable, as wgamd_gin_layer_f32_train)
+ * and mask_out (nullable): per CSR slot ceil(F / 32) 32-bit words, bit f of slot e set where m_e[f] > 0.
+ * wgamd_gine_bwd_dst_f32: part[b] [D + 1, F] = the sums of workgroup b over its tiles of 16 rows (a fixed stride) of
+ *   dW_e^T[d, f] = sum_e edge_attr[e, d] bit_e[f] dagg[dst(e), f]  (rows 0 .. D - 1)   and   db_e[f] = sum_e bit_e[f] dagg[dst(e), f]
+ * (row D); D >= 1; n_blocks = wgamd_gine_bwd_blocks(n_rows, max_blocks) = min(tiles, max_blocks > 0 ? max_blocks : 4 x the
+ * device's compute units); the gradient is the sum of the partials in block order.
+ * wgamd_gine_bwd_src_f32, over the hop's transpose (wgamd_csr_transpose_i32: col_t = destination row, perm = CSR slot):
+ *   gx[j, f] = sum over the entries t of row j of bit_{perm[t]}[f] dagg[col_t[t], f]  +  (1 + eps) dagg[self_t[j], f]
+ * (the second term where self_t, nullable, is >= 0); every row of gx [n_src, F] is written; rows of more than 64 entries are
+ * summed in 64-entry pieces by all lane groups of a workgroup, the groups' sums added in a fixed order.  No atomics anywhere.
+ * Domain: wgamd_gine_layer_supported(F, H, N, D) = wgamd_gin_layer_supported(F, H, N) and 0 <= D <= 16. */
+int wgamd_gine_layer_supported(int F, int H, int N, int D);
+int64_t wgamd_gine_bwd_blocks(int64_t n_rows, int max_blocks);
+wholememory_error_code_t wgamd_gine_layer_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx, int F,
+                                              const void* src_ids, wholememory_dtype_t src_ids_dtype, const int64_t* self_rows,
+                                              const float* x_dst, int64_t ldx_dst, const float* eps, const float* edge_attr,
+                                              const float* w_edge_t, const float* b_edge, int D, const float* w1, int64_t ldw1,
+                                              int H, const float* b1, const float* w2, int64_t ldw2, int N, const float* b2,
+                                              int flags, float* out, int64_t ldo, void* stream);
+wholememory_error_code_t wgamd_gine_layer_f32_train(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx,
+                                                    int F, const void* src_ids, wholememory_dtype_t src_ids_dtype,
+                                                    const int64_t* self_rows, const float* x_dst, int64_t ldx_dst, const float* eps,
+                                                    const float* edge_attr, const float* w_edge_t, const float* b_edge, int D,
+                                                    const float* w1, int64_t ldw1, int H, const float* b1, const float* w2,
+                                                    int64_t ldw2, int N, const float* b2, int flags, float* out, int64_t ldo,
+                                                    float* agg_out, int64_t ld_agg, float* hidden_out, int64_t ld_hidden,
+                                                    uint32_t* mask_out, void* stream);
+wholememory_error_code_t wgamd_gine_bwd_dst_f32(const int* row_ptr, int64_t n_rows, const float* edge_attr, int D,
+                                                const uint32_t* mask, const float* dagg, int64_t ld_dagg, int F, float* part,
+                                                int64_t n_blocks, void* stream);
+wholememory_error_code_t wgamd_gine_bwd_src_f32(const int* row_ptr_t, const int* col_t, const int* perm, int64_t n_src,
+                                                const uint32_t* mask, const float* dagg, int64_t ld_dagg, int F,
+                                                const int64_t* self_t, const float* eps, float* gx, int64_t ldgx, void* stream);
+
 /* ---- NormDropoutAct (csrc/wg_norm_act.hip): the row-wise block between two message-passing layers -------------------------------
  * What the reference's models put after a conv (mag_lp_mnmg.py: norm -> dropout -> relu, with the `+ lin1(x)` residual in the
  * encoder; gnn_model.py / rgcn / gin: relu -> dropout), over [n_rows, C] float32, for up to WGAMD_NORM_ACT_MAX_SEGMENTS node types
