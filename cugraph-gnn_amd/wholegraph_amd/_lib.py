@@ -464,6 +464,19 @@ SYMBOLS = {
                                        c_void_p]),
     "wgamd_gine_bwd_src_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
                                        c_void_p, c_int64, c_void_p]),
+    # GEN layer, per-channel softmax aggregation (wg_gen.hip)
+    "wgamd_gen_layer_supported": (c_int, [c_int, c_int, c_int]),
+    "wgamd_gen_bwd_blocks": (c_int64, [c_int64, c_int]),
+    "wgamd_gen_layer_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                    c_int64, c_void_p, c_float, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int,
+                                    c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "wgamd_gen_layer_f32_train": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                          c_int64, c_void_p, c_float, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_int,
+                                          c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                          c_int64, c_void_p, c_int64, c_void_p]),
+    "wgamd_gen_bwd_src_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_float,
+                                      c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                      c_void_p, c_int64, c_void_p]),
     # NormDropoutAct (wg_norm_act.hip)
     "wgamd_norm_act_supported": (c_int, [c_int]),
     "wgamd_norm_act_segment_seed": (c_ulonglong, [c_ulonglong, c_int]),

@@ -13,7 +13,7 @@ epilogue, one launch.
 
 Order of the file: ctypes helpers and the plumbing the one-kernel layers share; the SAGE-era kernel wrappers, derived-weight
 caches and GAT kernel wrappers; graph forms (``_single_hop``, ``LazyRows``, ``HopGraph``, ``LayerGraph``) and the helpers that
-walk a layer graph; then a section per layer — SAGE and GAT, GCN, RGCN, transformer, GIN, GATv2, heterogeneous, NormDropoutAct, RowLinear —
+walk a layer graph; then a section per layer — SAGE and GAT, GCN, RGCN, transformer, GIN, GATv2, GINE, GEN, heterogeneous, NormDropoutAct, RowLinear —
 each with its kernel wrappers, its autograd Function(s) and its module.
 
 Shared by the one-kernel layers, so that they cannot drift apart: ``_hop_args`` (the eight leading arguments of a launch over a
@@ -5017,6 +5017,396 @@ class GINEConv(GINConv):
         lg, _, ea = _single_hop(graph, n_dst, ea)
         return self._forward_layer(x, lg, act, x_dst=None if x_dst is None else x_dst[:n_dst], no_root=pair and x_dst is None,
                                    edge_attr=ea)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# GEN layer: per-channel softmax aggregation (torch_geometric.nn.GENConv, DeeperGCN) — csrc/wg_gen.hip
+# ---------------------------------------------------------------------------------------------------------------------
+def gen_layer_supported(C: int, H: int, N: int = 0) -> bool:
+    """Shapes of the one-kernel GEN layer (``wgamd_gen_layer_supported``): the GIN layer's domain — C % 4 == 0; C, H, N <= 256;
+    H % 4 == 0 with the mlp (N > 0; ``(C, 1, 0)``: the launch that ends after ``agg + x_dst``)."""
+    return bool(L.lib().wgamd_gen_layer_supported(int(C), int(H), int(N)))
+
+
+def gen_layer_forward(row_ptr, col, x, self_rows, t, w1=None, b1=None, w2=None, b2=None, msg_eps=1e-7, relu_out=False, src_ids=None,
+                      x_dst=None, out=None, keep=False, kept=None):
+    """A whole GEN layer over one hop in ONE kernel (``wgamd_gen_layer_f32``, include/wgamd_ext.h):
+    ``act(relu(A @ w1^T + b1) @ w2^T + b2)`` with ``A = agg + self row`` and ``agg[i, c] = sum_j softmax_j(t m_jc) m_jc`` over the
+    row's edges, ``m_j = relu(x[col]) + msg_eps`` — the softmax per channel, online, in registers.  ``t``: a one-element float32
+    device tensor.  The self row of destination i is ``x_dst[i]`` when ``x_dst`` is given, else row ``self_rows[i]`` of x; neither:
+    none.  ``w1 = w2 = None``: the launch ends after ``A`` (output [n_rows, C]).  ``keep`` (or ``kept``, the four buffers, None
+    entries allowed): the ``_train`` launch, returning ``(out, A, hidden, agg, lse)`` — ``A`` is ``out`` itself and ``hidden`` None
+    without the mlp; ``lse`` [n_rows, C] is the base-2 log-sum-exp every edge's weight is recomputed from in the backward."""
+    hop = _hop_args(row_ptr, col, x, src_ids) + _gin_hop_args(row_ptr, x, self_rows, x_dst, None)[:3]
+    n_rows, C, dev = row_ptr.shape[0] - 1, x.shape[1], row_ptr.device
+    assert t.dtype == torch.float32 and t.is_cuda and t.numel() == 1 and (w1 is None) == (w2 is None)
+    H = 0 if w1 is None else w1.shape[0]
+    N = 0 if w2 is None else w2.shape[0]
+    for w, k in ((w1, C), (w2, H)):
+        assert w is None or (w.dtype == torch.float32 and w.stride(1) == 1 and w.shape[1] == k)
+    out = _out_rows(out, n_rows, N or C, dev)
+    common = hop + (t.data_ptr(), float(msg_eps), _ptr(w1), 0 if w1 is None else w1.stride(0), H, _ptr(b1), _ptr(w2),
+                    0 if w2 is None else w2.stride(0), N, _ptr(b2), GIN_RELU_OUT if relu_out else 0, out.data_ptr(), out.stride(0))
+    if not keep and kept is None:
+        L.check(L.lib().wgamd_gen_layer_f32(*common, get_stream()), "wgamd_gen_layer_f32")
+        return out
+    if kept is None:
+        new = lambda width: torch.empty((n_rows, width), dtype=torch.float32, device=dev)      # noqa: E731
+        kept = (new(C) if w1 is not None else None, new(H) if w1 is not None else None, new(C), new(C))
+    for buf, width in zip(kept, (C, H, C, C)):
+        assert buf is None or (buf.shape == (n_rows, width) and buf.stride(1) == 1 and buf.dtype == torch.float32)
+    a, hidden, agg, lse = kept
+    L.check(L.lib().wgamd_gen_layer_f32_train(*common, *(v for buf in kept for v in (_ptr(buf), 0 if buf is None else buf.stride(0))),
+                                              get_stream()), "wgamd_gen_layer_f32_train")
+    return out, (out if w1 is None else a), hidden, agg, lse
+
+
+def gen_bwd_src(row_ptr_t, col_t, x, t, lse, agg, dagg, self_t=None, msg_eps=1e-7, src_ids=None, gx=None, max_blocks=None):
+    """The backward launch of one hop over its transpose (``wgamd_gen_bwd_src_f32``): ``(gx, dt_part)`` — ``gx`` [n_src, C], the
+    gradient of the layer's input rows ``x`` (read by row or through ``src_ids``) from the forward's ``lse`` and ``agg`` and
+    ``dagg = dL/dA`` [n_dst, C], every row written, ``dagg[self_t[j]]`` added where ``self_t`` (int64 [n_src], None: nowhere) is
+    >= 0; ``dt_part`` [blocks]: per-workgroup partials of ``dL/dt``, their sum in block order is the gradient.  The grid is bounded
+    (``wgamd_gen_bwd_blocks``: at most 4 workgroups per compute unit, tiles of 16 input rows at a fixed stride); ``max_blocks``
+    forces a smaller one."""
+    n_src, C, dev = row_ptr_t.shape[0] - 1, int(dagg.shape[1]), dagg.device
+    assert row_ptr_t.dtype == col_t.dtype == torch.int32 and row_ptr_t.is_contiguous() and col_t.is_contiguous()
+    assert gen_layer_supported(C, 1, 0) and x.dtype == torch.float32 and x.stride(1) == 1 and x.shape[1] == C
+    assert t.dtype == torch.float32 and t.is_cuda and t.numel() == 1
+    assert all(_kernel_rows_ok(v) and v.shape == dagg.shape for v in (lse, agg, dagg))
+    assert self_t is None or (self_t.dtype == torch.int64 and self_t.is_contiguous() and self_t.shape[0] == n_src)
+    assert (x.shape[0] if src_ids is None else src_ids.shape[0]) >= n_src
+    gx = _out_rows(gx, n_src, C, dev)
+    assert _kernel_rows_ok(gx)
+    blocks = int(L.lib().wgamd_gen_bwd_blocks(n_src, 0 if max_blocks is None else int(max_blocks)))
+    dt_part = torch.empty(blocks, dtype=torch.float32, device=dev)
+    if n_src > 0:
+        L.check(L.lib().wgamd_gen_bwd_src_f32(row_ptr_t.data_ptr(), _nonempty(col_t, torch.int32).data_ptr(), n_src, x.data_ptr(),
+                                              x.stride(0), C, *_ids_args(x, src_ids), t.data_ptr(), float(msg_eps),
+                                              _nonempty(lse, torch.float32).data_ptr(), lse.stride(0),
+                                              _nonempty(agg, torch.float32).data_ptr(), agg.stride(0),
+                                              _nonempty(dagg, torch.float32).data_ptr(), dagg.stride(0), _ptr(self_t), gx.data_ptr(),
+                                              gx.stride(0), dt_part.data_ptr(), blocks, get_stream()), "wgamd_gen_bwd_src_f32")
+    return gx, dt_part
+
+
+def _gen_aggregate_torch(x, xd, t, msg_eps: float, lg: LayerGraph):
+    """The torch-ops formulation of ``agg + xd`` over the hops of ``lg`` (any dtype and device): the [E, C] messages, their
+    exponentials against a scattered per-channel maximum, two ``index_add`` sums.  ``xd``: the destinations' rows back to back, or
+    None."""
+    C, aggs = x.shape[1], []
+    for h, rows, _ in _hops(lg):
+        n, E = h.n_rows, int(h.col.shape[0])
+        agg = torch.zeros((n, C), dtype=x.dtype, device=x.device)
+        if E > 0:
+            dst = _edge_dst(h.row_ptr, E)
+            m = torch.relu(x[h.col.long()]) + msg_eps
+            z = m * t.to(x.dtype)
+            top = torch.full((n, C), -math.inf, dtype=x.dtype, device=x.device).scatter_reduce(
+                0, dst.unsqueeze(1).expand(E, C), z.detach(), "amax")
+            w = torch.exp(z - top[dst])
+            den = agg.index_add(0, dst, w)
+            agg = agg.index_add(0, dst, w * m) / (den + (den == 0))
+        aggs.append(agg if xd is None else agg + xd[rows])
+    if not aggs:
+        return torch.zeros((0, C), dtype=x.dtype, device=x.device)
+    return aggs[0] if len(aggs) == 1 else torch.cat(aggs)
+
+
+class _GenLayer(torch.autograd.Function):
+    """The one-kernel GEN layer over a ``LayerGraph``: one ``wgamd_gen_layer_f32`` launch per hop; under autograd the ``_train`` form
+    keeps ``A = agg + x_dst``, the hidden activation, ``agg`` and the per-channel log-sum-exp — four rows per destination, nothing
+    per edge.  ``w1 = w2 = None``: ``A`` alone.  Backward, no atomics: the dense half as ``_GinLayer`` (``_dz``,
+    ``_dense_wgrad``, library GEMMs down to ``dA = dZ1 W1``), then per hop ``wgamd_gen_bwd_src_f32`` over the hop's transpose for
+    the input rows and the per-workgroup partials of ``dt`` (added in hop and block order); ``d x_dst = dA``.  A backward under
+    ``create_graph=True`` runs out of torch ops."""
+
+    @staticmethod
+    def forward(ctx, src, x_dst, t, w1, b1, w2, b2, graph, ids, relu_out, n_src, no_root, msg_eps):
+        C, n, dev = src.shape[1], graph.n_rows, t.device
+        keep = any(ctx.needs_input_grad[:7])
+        new = lambda width: torch.empty((n, width), dtype=torch.float32, device=dev)      # noqa: E731
+        out = new(C if w2 is None else w2.shape[0])
+        kept = None
+        if keep:
+            kept = (new(C), new(w1.shape[0]), new(C), new(C)) if w1 is not None else (None, None, new(C), new(C))
+        for h, rows, _ in _hops(graph):
+            if h.n_rows > 0:
+                self_rows, xd = _gin_hop_self(h, rows, _detached(x_dst), no_root)
+                gen_layer_forward(h.row_ptr, h.col, src, self_rows, *_detached((t, w1, b1, w2, b2)), msg_eps=msg_eps, relu_out=relu_out,
+                                  src_ids=ids, x_dst=xd, out=out[rows],
+                                  kept=None if kept is None else tuple(None if b is None else b[rows] for b in kept))
+        if keep:
+            ctx.save_for_backward(src if ids is None else None, x_dst, t, w1, b1, w2, b2, out)
+            ctx.kept, ctx.src = kept, src
+            ctx.graph, ctx.ids, ctx.relu_out, ctx.n_src, ctx.no_root, ctx.msg_eps = graph, ids, relu_out, n_src, no_root, msg_eps
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            return _gen_double_backward(ctx, g)
+        _released(ctx.kept, "GENConv", "activations and softmax rows")
+        _, x_dst, t, w1, _, w2, _, out = ctx.saved_tensors
+        a, hidden, agg, lse = ctx.kept
+        need_x, need_xd, need_t, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:7]
+        graph, dev, C, n_src = ctx.graph, g.device, agg.shape[1], ctx.n_src
+        gw1 = gb1 = gw2 = gb2 = gx = gxd = gt = None
+        if w1 is None:
+            d_a = g.contiguous().float()
+        else:
+            g, _ = _dz(g, out, ctx.relu_out)
+            if need_w2 or need_b2:
+                gw2, gb2 = _dense_wgrad(graph, hidden, g, w2, need_b2, None)
+                gw2 = gw2 if need_w2 else None
+            g1, _ = _dz(g @ w2, hidden, True)                                   # dHidden: one library GEMM
+            if need_w1 or need_b1:
+                gw1, gb1 = _dense_wgrad(graph, a, g1, w1, need_b1, None)
+                gw1 = gw1 if need_w1 else None
+            d_a = g1 @ w1 if graph.n_rows > 0 else torch.zeros((0, C), dtype=torch.float32, device=dev)
+        if need_x or need_t:
+            has_self = not ctx.no_root and x_dst is None
+            parts = []
+
+            def per_hop(h, rows, _, k):
+                row_ptr_t, col_t, _ = h.transposed(n_src, need_self=False)
+                gx_h, part = gen_bwd_src(row_ptr_t, col_t, ctx.src, t, lse[rows], agg[rows], d_a[rows],
+                                         h.input_dst(n_src) if has_self else None, ctx.msg_eps, src_ids=ctx.ids)
+                parts.append(part.sum())
+                return gx_h
+            gx = _sum_over_hops(graph, (n_src, C), dev, per_hop)
+            gx = gx if need_x else None
+            if need_t:
+                gt = (torch.stack(parts).sum() if parts else torch.zeros((), dtype=torch.float32, device=dev)).reshape(t.shape)
+        if need_xd:
+            gxd = torch.zeros_like(x_dst, dtype=torch.float32)
+            gxd[:d_a.shape[0]] = d_a
+        ctx.kept = ctx.src = None
+        return (gx, gxd, gt, gw1, gb1, gw2, gb2) + (None,) * 6
+
+
+def _gen_double_backward(ctx, g):
+    """The gradients as differentiable torch expressions of the saved inputs and ``g``."""
+    src, x_dst, t, w1, b1, w2, b2, _ = ctx.saved_tensors
+    if src is None:
+        raise _lazy_table_grad_error()
+
+    def make_y():
+        xd = None
+        if not ctx.no_root:
+            xd = x_dst if x_dst is not None else src[torch.cat([h.self_rows for h in ctx.graph.hops])]
+        y = _gen_aggregate_torch(src, xd, t, ctx.msg_eps, ctx.graph)
+        if w1 is not None:
+            y = torch.nn.functional.linear(torch.relu(torch.nn.functional.linear(y, w1, b1)), w2, b2)
+            y = torch.relu(y) if ctx.relu_out else y
+        return y
+    ins = [(i, v) for i, v in enumerate((src, x_dst, t, w1, b1, w2, b2)) if ctx.needs_input_grad[i]]
+    return tuple(_grads_from_torch(make_y, ins, g, [None] * 13))
+
+
+class _SoftmaxAggregation(torch.nn.Module):
+    """The holder of the softmax aggregator's temperature, ``aggr_module`` of ``GENConv``: ``t`` is a one-element Parameter with
+    ``learn`` (``aggr_module.t`` in the state dict) and a buffer outside the state dict otherwise — always ONE float the kernels
+    read on the device."""
+
+    def __init__(self, t: float = 1.0, learn: bool = False):
+        super().__init__()
+        self.initial_t, self.learn = float(t), bool(learn)
+        if learn:
+            self.t = torch.nn.Parameter(torch.empty(1))
+        else:
+            self.register_buffer("t", torch.empty(1), persistent=False)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        self.t.data.fill_(self.initial_t)
+
+
+class GENConv(torch.nn.Module):
+    """PyG ``GENConv`` (DeeperGCN, ``flow="source_to_target"``) with the per-channel softmax aggregator:
+
+        xs = lin_src(x_src), xd = lin_dst(x_dst)          (each only where its input width differs from ``out_channels``)
+        m_j = relu(xs_j) + eps
+        agg_i[c] = sum_{j in N(i)} softmax_j(t m_jc) m_jc                      (0 for a row without edges; t = 0: the mean)
+        out_i = mlp(agg_i + xd_i)
+
+    ``mlp`` is PyG's GEN ``MLP``: ``num_layers`` Linears (``bias=bias``), hidden width ``round(out_channels * expansion)``, and between two of
+    them ``[norm] -> ReLU -> Dropout(0)`` with ``norm`` None, ``"batch"`` (``BatchNorm1d``) or ``"layer"`` (``LayerNorm``).  ``t`` is a
+    float, or with ``learn_t`` a one-element Parameter.  Every edge counts, loops and duplicates too.  ``in_channels``: an int or
+    ``(src, dst)``.
+
+    State-dict names — chosen after PyG's as far as they are known here (not checked against an installed PyG):
+    ``lin_src.weight`` / ``lin_src.bias`` and ``lin_dst.*`` (only where the widths differ; biases only with ``bias=True``),
+    ``mlp.{i}.weight`` / ``mlp.{i}.bias`` at the ``Sequential`` positions of Linear, [norm], ReLU, Dropout, Linear — ``mlp.0`` and
+    ``mlp.3`` for the default two layers without a norm, ``mlp.0``, ``mlp.1`` (the norm) and ``mlp.4`` with one — and
+    ``aggr_module.t`` with ``learn_t`` (no entry otherwise).
+
+    ``forward(x, graph, act=None)``: ``graph`` = a COO ``edge_index`` (output rows = x's rows; ``x`` may be a sampler-layout pair
+    ``(x_src, x_dst)``, ``x_dst = None`` = no root term), a ``[csr_row_ptr, csr_col_ind]`` pair (destinations = the first rows of
+    x), or a call group's ``LayerGraph`` with ``x`` a tensor or ``LazyRows``, one launch per hop.  ``act="relu"`` is the ReLU that
+    follows the layer.  ``lin_src`` / ``lin_dst`` run BEFORE the kernel through ``linear_rows`` (a float32 ``LazyRows`` table is
+    read in place there; outside its domain it is ``torch.nn.functional.linear``) — a ReLU sits between them and the sum, so
+    there is no aggregate-first form.  ``route`` names what the last forward ran (before the first: what the parameters select):
+    * ``"mlp"`` — ``num_layers == 2``, ``norm=None`` and ``gen_layer_supported(C, H, C)`` (C % 4 == 0, H % 4 == 0, both <= 256):
+      the whole layer in ONE kernel per hop (``wgamd_gen_layer_f32``: the online softmax per (row, channel) in registers, both
+      products on the fp32 matrix pipe, no [E, C] array written); ``act`` rides in the kernel;
+    * ``"aggregate"`` — a norm or more layers: ``agg + xd`` in one launch per hop, then ``mlp`` as torch modules;
+    * ``"torch"`` — the same formula out of torch ops under ordinary autograd: CPU tensors, non-float32 inputs or parameters,
+      C outside the domain, a double backward, a float16 / bfloat16 ``LazyRows`` (after its one converting gather), and every
+      forward of a layer whose ``torch_ops`` attribute is set.
+    The backward of the kernel routes is one launch per hop over the hop's transpose (``wgamd_gen_bwd_src_f32``), without
+    atomics: the same gradient bits from run to run, ``t``'s included.
+    Refused (NotImplementedError): ``msg_norm=True``, ``edge_dim`` / ``edge_attr``, ``aggr="powermean"``, a ``HeteroLayerGraph``, an
+    ``(x_src, x_dst)`` pair over a ``LayerGraph``, a gradient into a lazily read table; any other ``aggr`` or ``norm`` is a
+    ValueError; HIP-graph capture in training mode is a RuntimeError (the hops' transposes are cached against the graph object)."""
+
+    def __init__(self, in_channels, out_channels: int, aggr: str = "softmax", t: float = 1.0, learn_t: bool = False,
+                 num_layers: int = 2, expansion: float = 2, norm: Optional[str] = None, eps: float = 1e-7, bias: bool = False,
+                 msg_norm: bool = False, edge_dim: Optional[int] = None):
+        super().__init__()
+        if aggr == "powermean":
+            raise NotImplementedError("GENConv: aggr='powermean' is not supported (the softmax aggregator only)")
+        if aggr != "softmax":
+            raise ValueError("GENConv: aggr must be 'softmax', got %r" % (aggr,))
+        if msg_norm:
+            raise NotImplementedError("GENConv: msg_norm=True is not supported")
+        if edge_dim is not None:
+            raise NotImplementedError("GENConv: edge_dim (edge features) is not supported")
+        if norm not in (None, "batch", "layer"):
+            raise ValueError("GENConv: norm must be None, 'batch' or 'layer', got %r" % (norm,))
+        if num_layers < 1 or expansion < 1:
+            raise ValueError("GENConv: num_layers and expansion must be positive")
+        pair = (in_channels, in_channels) if isinstance(in_channels, int) else tuple(in_channels)
+        self.in_channels, self.out_channels = (int(pair[0]), int(pair[1])), int(out_channels)
+        self.aggr, self.eps, self.norm, self.num_layers, self.expansion = aggr, float(eps), norm, int(num_layers), expansion
+        C = self.out_channels
+        self.hidden_channels = int(round(C * expansion))
+        self.aggr_module = _SoftmaxAggregation(t, learn_t)
+        self.lin_src = torch.nn.Linear(self.in_channels[0], C, bias=bias) if self.in_channels[0] != C else None
+        self.lin_dst = torch.nn.Linear(self.in_channels[1], C, bias=bias) if self.in_channels[1] != C else None
+        widths = [C] + [self.hidden_channels] * (self.num_layers - 1) + [C]
+        mods = []
+        for i in range(1, len(widths)):
+            mods.append(torch.nn.Linear(widths[i - 1], widths[i], bias=bias))
+            if i < len(widths) - 1:
+                if norm is not None:
+                    mods.append(torch.nn.BatchNorm1d(widths[i]) if norm == "batch" else torch.nn.LayerNorm(widths[i]))
+                mods += [torch.nn.ReLU(), torch.nn.Dropout(0.0)]
+        self.mlp = torch.nn.Sequential(*mods)
+        self._ran = None
+        self.torch_ops = False      # True: every forward takes the "torch" route (the examples' --torch-ops)
+
+    def reset_parameters(self):
+        for m in self.modules():
+            if m is not self and hasattr(m, "reset_parameters"):
+                m.reset_parameters()
+
+    @property
+    def t(self):
+        return self.aggr_module.t
+
+    def _plan(self) -> str:
+        C, H = self.out_channels, self.hidden_channels
+        tensors = list(self.parameters()) + [self.aggr_module.t]
+        if not all(p.is_cuda and p.dtype == torch.float32 for p in tensors):
+            return "torch"
+        if self.num_layers == 2 and self.norm is None and gen_layer_supported(C, H, C):
+            return "mlp"
+        return "aggregate" if gen_layer_supported(C, 1, 0) else "torch"
+
+    @property
+    def route(self) -> str:
+        """``"mlp"``, ``"aggregate"`` or ``"torch"``: what the last forward ran; before the first one, what the parameters select."""
+        return self._ran or self._plan()
+
+    def _forward_layer(self, x, lg: LayerGraph, act=None, x_dst=None, no_root=False):
+        assert act in (None, "relu"), "act: None or 'relu'"
+        relu, C = act == "relu", self.out_channels
+        x16 = isinstance(x, LazyRows) and x.table.dtype in _X16
+        x = _x16_as_rows(x)
+        lazy = isinstance(x, LazyRows)
+        if x.shape[1] != self.in_channels[0]:
+            raise ValueError("GENConv: x has %d features, the layer takes %d" % (x.shape[1], self.in_channels[0]))
+        if not no_root and (x_dst.shape[1] if x_dst is not None else x.shape[1]) != self.in_channels[1]:
+            raise ValueError("GENConv: the destination rows have %d features, the layer takes %d"
+                             % (x_dst.shape[1] if x_dst is not None else x.shape[1], self.in_channels[1]))
+        if lazy:
+            _refuse_lazy_table_grad(x.table)
+        t = self.aggr_module.t
+        plan = self._plan()
+        lin1, lin2 = (self.mlp[0], self.mlp[-1]) if plan == "mlp" else (None, None)
+        ok = (plan != "torch" and not x16 and not self.torch_ops
+              and all(v.is_cuda and v.dtype == torch.float32 for v in (x.table if lazy else x, x_dst) if torch.is_tensor(v))
+              and (not lazy or torch.is_tensor(x.table))
+              and all(_kernel_rows_ok(m.weight) and (m.bias is None or m.bias.is_contiguous()) for m in (lin1, lin2) if m is not None))
+        self_all = None
+        if not no_root and x_dst is None:
+            self_all = torch.cat([h.self_rows for h in lg.hops]) if lg.hops else torch.zeros(0, dtype=torch.int64, device=x.device)
+        if not ok:
+            self._ran = "torch"
+            xs = x.materialize() if lazy else x
+            xd = None if no_root else (x_dst[:lg.n_rows] if x_dst is not None else xs[self_all])
+            if self.lin_src is not None:
+                xs = self.lin_src(xs)
+            if self.lin_dst is not None and xd is not None:
+                xd = self.lin_dst(xd)
+            out = self.mlp(_gen_aggregate_torch(xs, xd, t, self.eps, lg))
+            return torch.relu(out) if relu else out
+        self._ran = plan
+        xd = None if x_dst is None else x_dst[:lg.n_rows]
+        if self.lin_dst is not None and not no_root:             # the destinations' rows, transformed: the kernel's x_dst
+            xd = linear_rows(x if xd is None else xd, self.lin_dst.weight, self.lin_dst.bias, rows=self_all if xd is None else None)
+        if self.lin_src is not None:
+            src, ids = linear_rows(x, self.lin_src.weight, self.lin_src.bias), None
+            n_src = src.shape[0]
+        else:
+            src, ids, n_src, _ = _layer_input(self, x, lg, C)
+            if lazy and not _kernel_rows_ok(src):
+                src, ids = x.materialize(), None
+            if ids is None and not _kernel_rows_ok(src):
+                src = src.contiguous()
+        if xd is not None and not _kernel_rows_ok(xd):
+            xd = xd.contiguous()
+        fuse_act = relu and plan == "mlp"
+        out = _GenLayer.apply(src, xd, t, lin1 and lin1.weight, lin1 and lin1.bias, lin2 and lin2.weight, lin2 and lin2.bias, lg, ids,
+                              fuse_act, n_src, no_root or (xd is None and self_all is None), self.eps)
+        if plan != "mlp":
+            out = self.mlp(out)
+        return torch.relu(out) if relu and not fuse_act else out
+
+    def forward(self, x, graph, act=None, edge_attr=None):
+        if edge_attr is not None or torch.is_tensor(act):
+            raise NotImplementedError("GENConv: edge_attr (edge features) is not supported")
+        if self.training:
+            _refuse_capture(self, "per-graph caches in training mode")      # (the hops' transposes, cached against the graph object)
+        x_dst, pair = None, False
+        if isinstance(x, (tuple, list)):
+            (x, x_dst), pair = x, True
+        _refuse_featureless(self, x)
+        if x_dst is not None:
+            _refuse_featureless(self, x_dst)
+        if isinstance(graph, HeteroLayerGraph):
+            raise NotImplementedError("GENConv over a heterogeneous call group's layer graph is not supported")
+        if isinstance(graph, LayerGraph):
+            if pair:
+                raise NotImplementedError("GENConv: an (x_src, x_dst) pair over a LayerGraph is not supported")
+            return self._forward_layer(x, graph, act)
+        if isinstance(x, LazyRows):
+            x = x.materialize()
+        if isinstance(x_dst, LazyRows):
+            x_dst = x_dst.materialize()
+        if isinstance(graph, (tuple, list)):
+            n_dst = int(graph[0].shape[0]) - 1
+        elif not pair:
+            n_dst = x.shape[0]
+        elif x_dst is not None:
+            n_dst = x_dst.shape[0]
+        else:                                                   # (x_src, None): as many rows as the edges reach (one read-back)
+            n_dst = int(graph[1].max()) + 1 if graph.shape[1] > 0 else 0
+        have = x.shape[0] if not pair else (x_dst.shape[0] if x_dst is not None else n_dst)
+        if have < n_dst:
+            raise ValueError("GENConv: %d destination rows for %d destinations" % (have, n_dst))
+        lg = _single_hop(graph, n_dst)[0]
+        return self._forward_layer(x, lg, act, x_dst=None if x_dst is None else x_dst[:n_dst], no_root=pair and x_dst is None)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1379,6 +1379,42 @@ wholememory_error_code_t wgamd_gine_bwd_src_f32(const int* row_ptr_t, const int*
                                                 const uint32_t* mask, const float* dagg, int64_t ld_dagg, int F,
                                                 const int64_t* self_t, const float* eps, float* gx, int64_t ldgx, void* stream);
 
+/* ---- GEN layer (csrc/wg_gen.hip): torch_geometric.nn.GENConv (DeeperGCN) with the per-channel softmax aggregator over a sampled hop --
+ *   m_j       = max(X[j], 0) + msg_eps
+ *   agg[i, c] = sum_{e = (j -> i)} p_ec m_jc,   p_ec = exp(t m_jc) / sum_{e' = (k -> i)} exp(t m_kc)       (0 for a row without edges)
+ *   A[i]      = agg[i] + XS[i]                                          (X, XS, src_ids, self_rows, x_dst as wgamd_gin_layer_f32)
+ *   out[i]    = act2(max(A[i] @ W1^T + b1, 0) @ W2^T + b2)              act2: WGAMD_GIN_RELU_OUT in flags
+ * t: ONE float on the device (any sign; 0 = the mean).  The softmax is an online one per (row, channel), in registers: no [E, C]
+ * array is written.  w1 and w2 come together; with both null (H = N = 0) the launch ends after A: out = A [n_rows, F].  _train also
+ * writes (each nullable) a_out = A, hidden_out, agg_out = agg and lse_out = L [n_rows, F] with p_ec = exp2(t log2(e) m_jc - L[i, c]).
+ * wgamd_gen_bwd_src_f32, over the hop's transpose (wgamd_csr_transpose_i32: col_t = destination row), x = the forward's rows:
+ *   gx[j, c] = [X[j, c] > 0] sum over the entries i of row j of p dagg[i, c] (1 + t (m_jc - agg[i, c]))  +  dagg[self_t[j], c]
+ *   dt       = sum over every entry and channel of dagg[i, c] p m_jc (m_jc - agg[i, c])
+ * (the last term of gx where self_t, nullable, is >= 0); every row of gx [n_src, F] is written; rows of more than 64 entries are
+ * summed in 64-entry pieces by all lane groups of a workgroup, the groups' sums added in a fixed order; dt_part[b] = the sum of
+ * workgroup b over its tiles of 16 input rows (a fixed stride), n_blocks = wgamd_gen_bwd_blocks(n_src, max_blocks) = min(tiles,
+ * max_blocks > 0 ? max_blocks : 4 x the device's compute units); dt is the sum of the partials in block order.  No atomics.
+ * Domain: wgamd_gen_layer_supported(F, H, N) = wgamd_gin_layer_supported(F, H, N). */
+int wgamd_gen_layer_supported(int F, int H, int N);
+int64_t wgamd_gen_bwd_blocks(int64_t n_src, int max_blocks);
+wholememory_error_code_t wgamd_gen_layer_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx, int F,
+                                             const void* src_ids, wholememory_dtype_t src_ids_dtype, const int64_t* self_rows,
+                                             const float* x_dst, int64_t ldx_dst, const float* t, float msg_eps, const float* w1,
+                                             int64_t ldw1, int H, const float* b1, const float* w2, int64_t ldw2, int N,
+                                             const float* b2, int flags, float* out, int64_t ldo, void* stream);
+wholememory_error_code_t wgamd_gen_layer_f32_train(const int* row_ptr, const int* col, int64_t n_rows, const float* x, int64_t ldx,
+                                                   int F, const void* src_ids, wholememory_dtype_t src_ids_dtype,
+                                                   const int64_t* self_rows, const float* x_dst, int64_t ldx_dst, const float* t,
+                                                   float msg_eps, const float* w1, int64_t ldw1, int H, const float* b1,
+                                                   const float* w2, int64_t ldw2, int N, const float* b2, int flags, float* out,
+                                                   int64_t ldo, float* a_out, int64_t ld_a, float* hidden_out, int64_t ld_hidden,
+                                                   float* agg_out, int64_t ld_agg, float* lse_out, int64_t ld_lse, void* stream);
+wholememory_error_code_t wgamd_gen_bwd_src_f32(const int* row_ptr_t, const int* col_t, int64_t n_src, const float* x, int64_t ldx,
+                                               int F, const void* src_ids, wholememory_dtype_t src_ids_dtype, const float* t,
+                                               float msg_eps, const float* lse, int64_t ld_lse, const float* agg, int64_t ld_agg,
+                                               const float* dagg, int64_t ld_dagg, const int64_t* self_t, float* gx, int64_t ldgx,
+                                               float* dt_part, int64_t n_blocks, void* stream);
+
 /* ---- NormDropoutAct (csrc/wg_norm_act.hip): the row-wise block between two message-passing layers -------------------------------
  * What the reference's models put after a conv (mag_lp_mnmg.py: norm -> dropout -> relu, with the `+ lin1(x)` residual in the
  * encoder; gnn_model.py / rgcn / gin: relu -> dropout), over [n_rows, C] float32, for up to WGAMD_NORM_ACT_MAX_SEGMENTS node types
