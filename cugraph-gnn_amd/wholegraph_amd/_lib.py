@@ -477,6 +477,20 @@ SYMBOLS = {
     "wgamd_gen_bwd_src_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_float,
                                       c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                       c_void_p, c_int64, c_void_p]),
+    # PNA layer, multi-aggregator reduction with degree scalers (wg_pna.hip)
+    "wgamd_pna_layer_supported": (c_int, [c_int, c_int]),
+    "wgamd_pna_row_tiles": (c_int, [c_int, c_int, c_int]),
+    "wgamd_pna_bwd_blocks": (c_int64, [c_int64, c_int]),
+    "wgamd_pna_layer_f32": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64,
+                                    c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_float, c_float, c_void_p, c_int64, c_int,
+                                    c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p]),
+    "wgamd_pna_layer_f32_train": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64,
+                                          c_void_p, c_int64, c_void_p, c_int, c_void_p, c_int, c_float, c_float, c_void_p, c_int64,
+                                          c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int64, c_void_p,
+                                          c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "wgamd_pna_bwd_src_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p,
+                                      c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                      c_void_p, c_int64, c_int64, c_void_p]),
     # NormDropoutAct (wg_norm_act.hip)
     "wgamd_norm_act_supported": (c_int, [c_int]),
     "wgamd_norm_act_segment_seed": (c_ulonglong, [c_ulonglong, c_int]),

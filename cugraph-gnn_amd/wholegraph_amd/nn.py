@@ -5203,6 +5203,42 @@ def _gen_double_backward(ctx, g):
     return tuple(_grads_from_torch(make_y, ins, g, [None] * 13))
 
 
+def _forward_graph_forms(layer, x, graph, act):
+    """``layer._forward_layer`` over the forms of ``graph`` that ``GENConv.forward`` and ``PNAConv.forward`` document: a
+    ``LayerGraph`` as it is; a COO ``edge_index`` or a ``[row_ptr, col]`` pair as a one-hop layer graph whose destinations are the
+    first rows of x, or the rows of ``x_dst`` of an ``(x_src, x_dst)`` pair."""
+    name = type(layer).__name__
+    x_dst, pair = None, False
+    if isinstance(x, (tuple, list)):
+        (x, x_dst), pair = x, True
+    _refuse_featureless(layer, x)
+    if x_dst is not None:
+        _refuse_featureless(layer, x_dst)
+    if isinstance(graph, HeteroLayerGraph):
+        raise NotImplementedError("%s over a heterogeneous call group's layer graph is not supported" % name)
+    if isinstance(graph, LayerGraph):
+        if pair:
+            raise NotImplementedError("%s: an (x_src, x_dst) pair over a LayerGraph is not supported" % name)
+        return layer._forward_layer(x, graph, act)
+    if isinstance(x, LazyRows):
+        x = x.materialize()
+    if isinstance(x_dst, LazyRows):
+        x_dst = x_dst.materialize()
+    if isinstance(graph, (tuple, list)):
+        n_dst = int(graph[0].shape[0]) - 1
+    elif not pair:
+        n_dst = x.shape[0]
+    elif x_dst is not None:
+        n_dst = x_dst.shape[0]
+    else:                                                   # (x_src, None): as many rows as the edges reach (one read-back)
+        n_dst = int(graph[1].max()) + 1 if graph.shape[1] > 0 else 0
+    have = x.shape[0] if not pair else (x_dst.shape[0] if x_dst is not None else n_dst)
+    if have < n_dst:
+        raise ValueError("%s: %d destination rows for %d destinations" % (name, have, n_dst))
+    lg = _single_hop(graph, n_dst)[0]
+    return layer._forward_layer(x, lg, act, x_dst=None if x_dst is None else x_dst[:n_dst], no_root=pair and x_dst is None)
+
+
 class _SoftmaxAggregation(torch.nn.Module):
     """The holder of the softmax aggregator's temperature, ``aggr_module`` of ``GENConv``: ``t`` is a one-element Parameter with
     ``learn`` (``aggr_module.t`` in the state dict) and a buffer outside the state dict otherwise — always ONE float the kernels
@@ -5378,35 +5414,456 @@ class GENConv(torch.nn.Module):
             raise NotImplementedError("GENConv: edge_attr (edge features) is not supported")
         if self.training:
             _refuse_capture(self, "per-graph caches in training mode")      # (the hops' transposes, cached against the graph object)
-        x_dst, pair = None, False
-        if isinstance(x, (tuple, list)):
-            (x, x_dst), pair = x, True
-        _refuse_featureless(self, x)
+        return _forward_graph_forms(self, x, graph, act)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# PNA layer: several statistics of a neighbourhood times degree scalers (torch_geometric.nn.PNAConv) — csrc/wg_pna.hip
+# ---------------------------------------------------------------------------------------------------------------------
+_PNA_AGGREGATORS = {"sum": 0, "mean": 1, "min": 2, "max": 3, "var": 4, "std": 5}                              # WGAMD_PNA_SUM ..
+_PNA_SCALERS = {"identity": 0, "amplification": 1, "attenuation": 2, "linear": 3, "inverse_linear": 4}      # WGAMD_PNA_IDENTITY ..
+_PNA_STD_EPS = 1e-5
+
+
+def pna_layer_supported(F_: int, N: int = 0) -> bool:
+    """Shapes of the one-kernel PNA layer (``wgamd_pna_layer_supported``): F % 4 == 0, 4 <= F <= 256, N <= 256 (``N = 0``: the launch
+    that ends after the statistics)."""
+    return bool(L.lib().wgamd_pna_layer_supported(int(F_), int(N)))
+
+
+def pna_row_tiles(F_: int, n_aggr: int, N: int) -> int:
+    """M: a workgroup of the layer kernel owns 16 M destination rows (``wgamd_pna_row_tiles``: 4, 2 or 1, what fits the LDS)."""
+    return int(L.lib().wgamd_pna_row_tiles(int(F_), int(n_aggr), int(N)))
+
+
+def pna_layer_forward(row_ptr, col, y, a, aggregators, x_dst=None, scalers=None, avg_deg=None, w_post=None, b_post=None, w_lin=None,
+                      b_lin=None, relu_out=False, src_ids=None, out=None, keep=False, kept=None):
+    """A whole PNA layer over one hop in ONE kernel (``wgamd_pna_layer_f32``, include/wgamd_ext.h):
+    ``act([x_dst | s_1 stat | .. | s_S stat] @ w_post^T + b_post) @ w_lin^T + b_lin)`` with ``stat`` the ``aggregators`` (names, in
+    order) of the messages ``a[i] + y[col]`` over a row's edges and ``s_k`` the ``scalers`` (names) of the row's degree against
+    ``avg_deg = (lin, log)``.  ``y`` is read by row or through ``src_ids``; ``a`` [n_rows, F] may be None (0).  ``w_post = w_lin =
+    None``: the launch ends after the statistics (output [n_rows, A F]).  ``keep`` (or ``kept``, the five buffers, None entries
+    allowed): the ``_train`` launch, returning ``(out, stats, mean_y, argmin, argmax, z)`` — ``stats`` is ``out`` itself without
+    the weights; ``argmin`` / ``argmax`` int32: the CSR edge slot of each channel's extreme, the lowest of a tie, -1 without edges."""
+    hop = _hop_args(row_ptr, col, y, src_ids)
+    n_rows, F_, dev = row_ptr.shape[0] - 1, y.shape[1], row_ptr.device
+    A, layer = len(aggregators), w_post is not None
+    assert (w_lin is not None) == layer and (a is None or (_kernel_rows_ok(a) and a.shape == (n_rows, F_)))
+    aggr = (ctypes.c_int * A)(*[_PNA_AGGREGATORS[k] for k in aggregators])
+    S = len(scalers) if layer else 0
+    scal = (ctypes.c_int * max(S, 1))(*[_PNA_SCALERS[k] for k in (scalers if layer else ())])
+    N, NO = (w_post.shape[0], w_lin.shape[0]) if layer else (0, 0)
+    if layer:
+        assert _kernel_rows_ok(x_dst) and x_dst.shape == (n_rows, F_) and w_post.shape[1] == (1 + S * A) * F_ and w_lin.shape[1] == N
+        assert all(w.dtype == torch.float32 and w.stride(1) == 1 for w in (w_post, w_lin))
+    out = _out_rows(out, n_rows, NO if layer else A * F_, dev)
+    lin, log = (float(avg_deg[0]), float(avg_deg[1])) if layer else (1.0, 1.0)
+    common = hop + (_ptr(a), 0 if a is None else a.stride(0), _ptr(x_dst) if layer else None, x_dst.stride(0) if layer else 0,
+                    ctypes.cast(aggr, ctypes.c_void_p), A, ctypes.cast(scal, ctypes.c_void_p), S, lin, log,
+                    _ptr(w_post), w_post.stride(0) if layer else 0, N, _ptr(b_post), _ptr(w_lin), w_lin.stride(0) if layer else 0, NO,
+                    _ptr(b_lin), GIN_RELU_OUT if relu_out else 0, out.data_ptr(), out.stride(0))
+    if not keep and kept is None:
+        L.check(L.lib().wgamd_pna_layer_f32(*common, get_stream()), "wgamd_pna_layer_f32")
+        return out
+    if kept is None:
+        new = lambda width, dt=torch.float32: torch.empty((n_rows, width), dtype=dt, device=dev)      # noqa: E731
+        kept = (new(A * F_) if layer else None, new(F_), new(F_, torch.int32), new(F_, torch.int32), new(N) if layer else None)
+    stats, mean_y, amin, amax, z = kept
+    for buf, width, dt in zip(kept, (A * F_, F_, F_, F_, N), (torch.float32, torch.float32, torch.int32, torch.int32, torch.float32)):
+        assert buf is None or (buf.shape == (n_rows, width) and buf.stride(1) == 1 and buf.dtype == dt)
+    ld_arg = amin.stride(0) if amin is not None else (amax.stride(0) if amax is not None else 0)
+    assert amin is None or amax is None or amin.stride(0) == amax.stride(0)
+    L.check(L.lib().wgamd_pna_layer_f32_train(*common, _ptr(stats), 0 if stats is None else stats.stride(0), _ptr(mean_y),
+                                              0 if mean_y is None else mean_y.stride(0), _ptr(amin), _ptr(amax), ld_arg, _ptr(z),
+                                              0 if z is None else z.stride(0), get_stream()), "wgamd_pna_layer_f32_train")
+    return out, (stats if layer else out), mean_y, amin, amax, z
+
+
+def pna_bwd_src(row_ptr_t, col_t, perm, y, c0=None, c1=None, mean_y=None, dmax=None, amax=None, dmin=None, amin=None, src_ids=None,
+                gy=None, max_blocks=None):
+    """The backward launch of one hop over its transpose (``wgamd_pna_bwd_src_f32``): ``gy`` [n_src, F], every row written — entry
+    (j -> i, CSR slot ``perm``) adds ``c0[i] + (y[j] - mean_y[i]) c1[i] + [amax[i] = slot] dmax[i] + [amin[i] = slot] dmin[i]``, each
+    term optional; ``c0`` and ``c1`` share their row stride, ``dmax`` and ``dmin`` too.  The grid is bounded
+    (``wgamd_pna_bwd_blocks``: at most 4 workgroups per compute unit, tiles of 16 input rows at a fixed stride); ``max_blocks``
+    forces a smaller one."""
+    n_src, F_ = row_ptr_t.shape[0] - 1, int(y.shape[1])
+    assert row_ptr_t.dtype == col_t.dtype == torch.int32 and row_ptr_t.is_contiguous() and col_t.is_contiguous()
+    assert pna_layer_supported(F_, 0) and y.dtype == torch.float32 and y.stride(1) == 1
+    assert all(v is None or (_kernel_rows_ok(v) and v.shape[1] == F_) for v in (c0, c1, mean_y, dmax, dmin))
+    assert all(v is None or (v.dtype == torch.int32 and v.stride(1) == 1 and v.shape[1] == F_) for v in (amax, amin))
+    assert (y.shape[0] if src_ids is None else src_ids.shape[0]) >= n_src
+    ld = lambda *vs: next((v.stride(0) for v in vs if v is not None), 0)      # noqa: E731
+    assert all(v is None or v.stride(0) == ld(c0, c1) for v in (c0, c1)) and all(v is None or v.stride(0) == ld(dmax, dmin) for v in (dmax, dmin))
+    assert all(v is None or v.stride(0) == ld(amax, amin) for v in (amax, amin))
+    gy = _out_rows(gy, n_src, F_, y.device)
+    assert _kernel_rows_ok(gy)
+    blocks = int(L.lib().wgamd_pna_bwd_blocks(n_src, 0 if max_blocks is None else int(max_blocks)))
+    if n_src > 0:
+        L.check(L.lib().wgamd_pna_bwd_src_f32(row_ptr_t.data_ptr(), _nonempty(col_t, torch.int32).data_ptr(), _ptr(perm), n_src,
+                                              y.data_ptr(), y.stride(0), F_, *_ids_args(y, src_ids), _ptr(c0), _ptr(c1), ld(c0, c1),
+                                              _ptr(mean_y), ld(mean_y), _ptr(dmax), _ptr(dmin), ld(dmax, dmin), _ptr(amax), _ptr(amin),
+                                              ld(amax, amin), gy.data_ptr(), gy.stride(0), blocks, get_stream()), "wgamd_pna_bwd_src_f32")
+    return gy, blocks
+
+
+def _pna_degrees(lg: LayerGraph):
+    """int64 [n_rows]: the in-degree of every destination row of ``lg``."""
+    degs = [(h.row_ptr[1:] - h.row_ptr[:-1]).long() for h in lg.hops]
+    return torch.cat(degs) if degs else torch.zeros(0, dtype=torch.int64)
+
+
+def _pna_scaler_values(deg, scalers, avg_lin, avg_log, dtype):
+    """[n, S]: PyG's degree scalers of ``deg`` clamped to >= 1, a column per name of ``scalers``."""
+    d = deg.clamp(min=1).to(dtype)
+    lg = torch.log(d + 1)
+    cols = {"identity": lambda: torch.ones_like(d), "amplification": lambda: lg / avg_log, "attenuation": lambda: avg_log / lg,
+            "linear": lambda: d / avg_lin, "inverse_linear": lambda: avg_lin / d}
+    return torch.stack([cols[k]() for k in scalers], 1)
+
+
+def _pna_stats_torch(m, dst, n: int, aggregators):
+    """[n, A W]: the ``aggregators`` of the per-edge messages ``m`` [E, W] over their destinations ``dst`` (sorted: an edge's index is
+    its slot) out of torch ops, any dtype and device — ``mean(m^2) - mean(m)^2`` for var, ``sqrt(relu(var) + 1e-5)`` for std, min and
+    max taken (value and gradient) at the lowest slot that holds the extreme, every statistic 0 for a row without edges."""
+    E, W = m.shape
+    zeros = torch.zeros((n, W), dtype=m.dtype, device=m.device)
+    if E == 0:
+        return zeros.repeat(1, len(aggregators))
+    deg = torch.bincount(dst, minlength=n)
+    has, d = (deg > 0).unsqueeze(1), deg.clamp(min=1).to(m.dtype).unsqueeze(1)
+    idx, made = dst.unsqueeze(1).expand(E, W), {}
+
+    def stat(name):
+        if name in made:
+            return made[name]
+        if name == "sum":
+            v = zeros.index_add(0, dst, m)
+        elif name == "mean":
+            v = stat("sum") / d
+        elif name in ("min", "max"):
+            ext = zeros.scatter_reduce(0, idx, m.detach(), "a" + name, include_self=False)
+            slot = torch.arange(E, device=m.device).unsqueeze(1).expand(E, W)
+            first = torch.full((n, W), E, dtype=torch.int64, device=m.device).scatter_reduce(
+                0, idx, torch.where(m.detach() == ext[dst], slot, E), "amin")
+            v = torch.where(has, m.gather(0, first.clamp(max=E - 1)), zeros)
+        elif name == "var":
+            v = zeros.index_add(0, dst, m * m) / d - stat("mean") ** 2
+        else:
+            v = torch.where(has, torch.sqrt(torch.relu(stat("var")) + _PNA_STD_EPS), zeros)
+        made[name] = v
+        return v
+    return torch.cat([stat(k) for k in aggregators], 1)
+
+
+def _pna_edges(lg: LayerGraph):
+    """``(dst, col)`` int64: destination row (in the layer's output) and input row of every edge of ``lg``, hop after hop."""
+    dev = lg.hops[0].row_ptr.device if lg.hops else None
+    dst = [_edge_dst(h.row_ptr, int(h.col.shape[0]), rows.start) for h, rows, _ in _hops(lg)]
+    col = [h.col.long() for h in lg.hops]
+    return (torch.cat(dst), torch.cat(col)) if dst else (torch.zeros(0, dtype=torch.int64, device=dev),) * 2
+
+
+class _PnaLayer(torch.autograd.Function):
+    """The one-kernel PNA layer over a ``LayerGraph``: one ``wgamd_pna_layer_f32`` launch per hop; under autograd the ``_train`` form
+    keeps per destination the unscaled statistics [n, A F], the phase-2 result Z, the mean of y (with var / std) and the edge
+    slots of min / max — nothing per edge.  ``wp = wl = None``: the statistics alone.  Backward, no atomics: ``d lin`` through
+    ``_dense_wgrad``; ``d post`` per scaler ``(s_k dZ)^T stats`` and ``d stats = sum_k (s_k dZ) W_k`` as library GEMMs into one
+    [n, A F] buffer (no [n, (1 + S A) F] array); then per hop ``wgamd_pna_bwd_src_f32`` over the hop's transpose for ``dy``;
+    ``da = deg dsum + dmean + dmin + dmax`` on rows with edges.  A backward under ``create_graph=True`` runs out of torch ops."""
+
+    @staticmethod
+    def forward(ctx, y, a, xd, wp, bp, wl, bl, graph, cfg, relu_out, n_src):
+        aggregators, scalers, avg = cfg
+        F_, n, dev, A = y.shape[1], graph.n_rows, y.device, len(aggregators)
+        keep = any(ctx.needs_input_grad[:7])
+        new = lambda width, dt=torch.float32: torch.empty((n, width), dtype=dt, device=dev)      # noqa: E731
+        out = new(A * F_ if wp is None else wl.shape[0])
+        kept = None
+        if keep:
+            kept = (new(A * F_) if wp is not None else None, new(F_) if {"var", "std"} & set(aggregators) else None,
+                    new(F_, torch.int32) if "min" in aggregators else None, new(F_, torch.int32) if "max" in aggregators else None,
+                    new(wp.shape[0]) if wp is not None else None)
+        for h, rows, _ in _hops(graph):
+            if h.n_rows > 0:
+                pna_layer_forward(h.row_ptr, h.col, y, a[rows], aggregators, None if xd is None else xd[rows], scalers, avg,
+                                  *_detached((wp, bp, wl, bl)), relu_out=relu_out, out=out[rows],
+                                  kept=None if kept is None else tuple(None if b is None else b[rows] for b in kept))
+        if keep:
+            ctx.save_for_backward(y, a, xd, wp, bp, wl, bl, out)
+            ctx.kept, ctx.graph, ctx.cfg, ctx.relu_out, ctx.n_src = kept, graph, cfg, relu_out, n_src
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            return _pna_double_backward(ctx, g)
+        _released(ctx.kept, "PNAConv", "statistics and edge slots")
+        y, a, xd, wp, _, wl, _, out = ctx.saved_tensors
+        stats, mean_y, amin, amax, z = ctx.kept
+        aggregators, scalers, avg = ctx.cfg
+        graph, F_, A = ctx.graph, y.shape[1], len(aggregators)
+        need_y, need_a, need_xd, need_wp, need_bp, need_wl, need_bl = ctx.needs_input_grad[:7]
+        deg = _pna_degrees(graph).to(y.device)
+        gy = ga = gxd = gwp = gbp = gwl = gbl = None
+        if wp is None:
+            stats, dstats = out, g.contiguous().float()
+        else:
+            g, _ = _dz(g, out, ctx.relu_out)
+            if need_wl or need_bl:
+                gwl, gbl = _dense_wgrad(graph, z, g, wl, need_bl, None)
+                gwl = gwl if need_wl else None
+            dz = g @ wl                                                                          # one library GEMM
+            scal = _pna_scaler_values(deg, scalers, avg[0], avg[1], torch.float32)
+            gwp = torch.empty_like(wp, memory_format=torch.contiguous_format) if need_wp else None
+            dstats = torch.zeros((dz.shape[0], A * F_), dtype=torch.float32, device=dz.device)
+            if need_wp:
+                gwp[:, :F_] = dz.t() @ xd
+            for k in range(len(scalers)):                                                        # the scaled concatenation: never
+                sz, blk = dz * scal[:, k:k + 1], slice(F_ + k * A * F_, F_ + (k + 1) * A * F_)
+                if need_wp:
+                    gwp[:, blk] = sz.t() @ stats
+                dstats.addmm_(sz, wp[:, blk])
+            gbp = dz.sum(0) if need_bp else None
+            gxd = dz @ wp[:, :F_] if need_xd else None
+        if need_y or need_a:
+            ds = {k: dstats[:, i * F_:(i + 1) * F_] for i, k in enumerate(aggregators)}
+            has, d = (deg > 0).unsqueeze(1), deg.clamp(min=1).float().unsqueeze(1)
+            c0 = c1 = None
+            if "sum" in ds or "mean" in ds:
+                c0 = _sum_of([ds[k] if k == "sum" else ds[k] / d for k in ("sum", "mean") if k in ds]).contiguous()
+            if "var" in ds or "std" in ds:
+                terms = [2 * ds["var"]] if "var" in ds else []
+                if "std" in ds:                                        # relu(var) = 0: no gradient (std is sqrt(1e-5) or, no edges, 0)
+                    std = stats[:, aggregators.index("std") * F_:][:, :F_]
+                    terms.append(torch.where(std > math.sqrt(_PNA_STD_EPS), ds["std"] / std, torch.zeros_like(std)))
+                c1 = (_sum_of(terms) / d).contiguous()
+            if need_y:
+                slots = "min" in ds or "max" in ds
+
+                def per_hop(h, rows, _, k):
+                    tr = h.transposed(ctx.n_src, need_self=False, need_perm=slots)
+                    pick = lambda v: None if v is None else v[rows]      # noqa: E731
+                    return pna_bwd_src(tr[0], tr[1], tr[3] if slots else None, y, pick(c0), pick(c1), pick(mean_y) if c1 is not None else None,
+                                       pick(ds.get("max")), pick(amax), pick(ds.get("min")), pick(amin))[0]
+                gy = _sum_over_hops(graph, (ctx.n_src, F_), y.device, per_hop)
+            if need_a:
+                ga = _sum_of([ds[k] * d if k == "sum" else ds[k] for k in ("sum", "mean", "min", "max") if k in ds])
+                ga = torch.zeros_like(a) if ga is None else ga * has
+        ctx.kept = None
+        return (gy, ga, gxd, gwp, gbp, gwl, gbl, None, None, None, None)
+
+
+def _pna_fold_torch(y, a, xd, wp, bp, wl, bl, graph: LayerGraph, cfg, relu_out: bool):
+    """What ``_PnaLayer`` computes, out of torch ops."""
+    aggregators, scalers, avg = cfg
+    dst, col = _pna_edges(graph)
+    stats = _pna_stats_torch(a[dst] + y[col], dst, graph.n_rows, aggregators)
+    if wp is None:
+        return stats
+    scal = _pna_scaler_values(_pna_degrees(graph).to(y.device), scalers, avg[0], avg[1], y.dtype)
+    cat = torch.cat([xd] + [stats * scal[:, k:k + 1] for k in range(len(scalers))], 1)
+    out = torch.nn.functional.linear(torch.nn.functional.linear(cat, wp, bp), wl, bl)
+    return torch.relu(out) if relu_out else out
+
+
+def _pna_double_backward(ctx, g):
+    """The gradients as differentiable torch expressions of the saved inputs and ``g``."""
+    saved = ctx.saved_tensors[:7]
+    make_y = lambda: _pna_fold_torch(*saved, ctx.graph, ctx.cfg, ctx.relu_out)      # noqa: E731
+    ins = [(i, v) for i, v in enumerate(saved) if ctx.needs_input_grad[i]]
+    return tuple(_grads_from_torch(make_y, ins, g, [None] * 11))
+
+
+class _DegreeScalers(torch.nn.Module):
+    """The holder of the degree averages, ``aggr_module`` of ``PNAConv``: ``avg_deg_lin``, ``avg_deg_log`` and ``avg_deg_exp`` of the
+    ``deg`` histogram as PyG's ``DegreeScalerAggregation`` keeps them — buffers, or Parameters with ``train_norm``."""
+
+    def __init__(self, deg, train_norm: bool):
+        super().__init__()
+        deg = torch.as_tensor(deg).to(torch.float64)
+        bins, total = torch.arange(deg.numel(), dtype=torch.float64), float(deg.sum())
+        for name, v in (("lin", bins), ("log", torch.log(bins + 1)), ("exp", torch.exp(bins))):
+            t = torch.tensor(float((v * deg).sum()) / total, dtype=torch.float32)
+            if train_norm:
+                setattr(self, "avg_deg_" + name, torch.nn.Parameter(t))
+            else:
+                self.register_buffer("avg_deg_" + name, t)
+        self._floats = None
+
+    def floats(self):
+        """``(lin, log)`` as Python floats for the kernel: read back once per value of the two buffers."""
+        key = tuple((t.data_ptr(), t._version) for t in (self.avg_deg_lin, self.avg_deg_log))
+        if self._floats is None or self._floats[0] != key:
+            self._floats = (key, (float(self.avg_deg_lin), float(self.avg_deg_log)))
+        return self._floats[1]
+
+
+class PNAConv(torch.nn.Module):
+    """PyG ``PNAConv`` (Principal Neighbourhood Aggregation, ``flow="source_to_target"``):
+
+        m_ji  = pre_nns[t]([x_i | x_j])                                                     per tower t
+        stat  = the ``aggregators`` of {m_ji : j -> i} per channel, in order: any of sum, mean, min, max, var, std
+                (var = mean(m^2) - mean(m)^2, std = sqrt(relu(var) + 1e-5); every statistic is 0 for a row without edges)
+        out_i = lin(cat_t post_nns[t]([x_i | s_1 stat | .. | s_S stat]))                     scaler-major
+
+    with the ``scalers`` (any of identity, amplification, attenuation, linear, inverse_linear) of the row's in-degree clamped
+    to >= 1 against the averages of the ``deg`` histogram (``deg[d]`` = number of training nodes of in-degree d).  ``towers``
+    splits the layer into independent towers (``divide_input``: each sees its slice of x); ``pre_layers`` / ``post_layers`` Linears
+    per tower with ``act`` between them.  Every edge counts, loops and duplicates too; a tie of min / max goes to the row's
+    first edge that holds the extreme, value and gradient.
+
+    State-dict names — chosen after PyG's as far as they are known here (not checked against an installed PyG):
+    ``pre_nns.{t}.{k}.weight`` / ``.bias`` and ``post_nns.{t}.{k}.*`` at the ``Sequential`` positions k = 0, 2, 4, .. of the Linears,
+    ``lin.weight`` / ``lin.bias``, and ``aggr_module.avg_deg_lin`` / ``avg_deg_log`` / ``avg_deg_exp``.
+
+    ``forward(x, graph, act=None)``: the call forms of ``GENConv.forward`` — a COO ``edge_index``, a ``[csr_row_ptr, csr_col_ind]``
+    pair or a call group's ``LayerGraph``; ``x`` a tensor, an ``(x_src, x_dst)`` pair or ``LazyRows``; ``act="relu"`` is the ReLU that
+    follows the layer (not the constructor's ``act``).  With ``pre_layers == 1`` the message is linear,
+    ``m_ji = W_i x_i + W_j x_j + b = a_i + y_j``: ``y`` over the input rows and ``a`` over the destinations run BEFORE the kernel through
+    ``linear_rows`` (a float32 ``LazyRows`` table is read in place there), the kernel reduces ``y_j`` alone and no [E, .] array is
+    written.  ``route`` names what the last forward ran (before the first: what the parameters select):
+    * ``"layer"`` — ``towers == 1``, ``pre_layers == post_layers == 1``, ``train_norm=False``, ``pna_layer_supported(F, N)`` (F % 4 == 0,
+      F and N <= 256) and N % 4 == 0: the whole layer in ONE kernel per hop (``wgamd_pna_layer_f32``: all statistics out of one walk
+      over the row, the scaled concatenation formed in registers in front of the fp32 matrix pipe, ``lin`` as a second product);
+    * ``"aggregate"`` — towers or deeper post_nns (``pre_layers == 1``, y at most 256 wide over all towers): the statistics in one
+      launch per hop, then scalers, ``post_nns`` and ``lin`` as torch modules;
+    * ``"torch"`` — the per-edge formula out of torch ops under ordinary autograd: ``pre_layers > 1``, ``train_norm=True``, CPU or
+      non-float32 tensors, widths outside the domain, a float16 / bfloat16 ``LazyRows`` (after its one converting gather), a
+      double backward, and every forward of a layer whose ``torch_ops`` attribute is set.
+    The backward of the kernel routes is one launch per hop over the hop's transpose (``wgamd_pna_bwd_src_f32``) between library
+    GEMMs, without atomics: the same gradient bits from run to run.
+    Refused (NotImplementedError): ``edge_dim`` / ``edge_attr``, a ``HeteroLayerGraph``, an ``(x_src, x_dst)`` pair over a
+    ``LayerGraph``, a gradient into a lazily read table; an unknown aggregator or scaler is a ValueError, and so is ``(x_src, None)``
+    (the message needs the destination's row); HIP-graph capture in training mode is a RuntimeError."""
+
+    def __init__(self, in_channels: int, out_channels: int, aggregators, scalers, deg, edge_dim: Optional[int] = None, towers: int = 1,
+                 pre_layers: int = 1, post_layers: int = 1, divide_input: bool = False, act: str = "relu", train_norm: bool = False):
+        super().__init__()
+        if edge_dim is not None:
+            raise NotImplementedError("PNAConv: edge_dim (edge features) is not supported")
+        aggregators, scalers = list(aggregators), list(scalers)
+        for names, known, what in ((aggregators, _PNA_AGGREGATORS, "aggregator"), (scalers, _PNA_SCALERS, "scaler")):
+            bad = [k for k in names if k not in known]
+            if bad or not names or len(set(names)) != len(names):
+                raise ValueError("PNAConv: unknown, repeated or missing %s in %r (known: %s)" % (what, names, ", ".join(known)))
+        if act != "relu":
+            raise ValueError("PNAConv: act must be 'relu', got %r" % (act,))
+        if towers < 1 or pre_layers < 1 or post_layers < 1 or out_channels % towers or (divide_input and in_channels % towers):
+            raise ValueError("PNAConv: towers must divide out_channels (and in_channels with divide_input); layers must be positive")
+        self.in_channels, self.out_channels, self.aggregators, self.scalers = int(in_channels), int(out_channels), aggregators, scalers
+        self.towers, self.pre_layers, self.post_layers, self.divide_input = int(towers), int(pre_layers), int(post_layers), bool(divide_input)
+        self.train_norm = bool(train_norm)
+        Fi = self.F_in = self.in_channels // towers if divide_input else self.in_channels
+        Fo = self.F_out = self.out_channels // towers
+        self.aggr_module = _DegreeScalers(deg, train_norm)
+
+        def mlp(first, width, layers):
+            mods = [torch.nn.Linear(first, width)]
+            for _ in range(layers - 1):
+                mods += [torch.nn.ReLU(), torch.nn.Linear(width, width)]
+            return torch.nn.Sequential(*mods)
+        self.pre_nns = torch.nn.ModuleList(mlp(2 * Fi, Fi, pre_layers) for _ in range(towers))
+        self.post_nns = torch.nn.ModuleList(mlp((len(aggregators) * len(scalers) + 1) * Fi, Fo, post_layers) for _ in range(towers))
+        self.lin = torch.nn.Linear(self.out_channels, self.out_channels)
+        self._ran = None
+        self.torch_ops = False      # True: every forward takes the "torch" route (the examples' --torch-ops)
+
+    def reset_parameters(self):
+        for m in self.modules():
+            if isinstance(m, torch.nn.Linear):
+                m.reset_parameters()
+
+    def _plan(self) -> str:
+        tensors = list(self.parameters()) + list(self.buffers())
+        return self._plan_shapes() if all(p.is_cuda and p.dtype == torch.float32 for p in tensors) else "torch"
+
+    def _plan_shapes(self) -> str:
+        """What the constructor's arguments select when the parameters are float32 on the device."""
+        if self.pre_layers > 1 or self.train_norm or not pna_layer_supported(self.towers * self.F_in, 0):
+            return "torch"
+        N = self.out_channels
+        if self.towers == 1 and self.post_layers == 1 and N % 4 == 0 and pna_layer_supported(self.F_in, N):
+            return "layer"
+        return "aggregate"
+
+    @property
+    def route(self) -> str:
+        """``"layer"``, ``"aggregate"`` or ``"torch"``: what the last forward ran; before the first one, what the parameters select."""
+        return self._ran or self._plan()
+
+    def _towers_of(self, v):
+        """[rows, T, F_in]: what every tower sees of the rows ``v``."""
+        T = self.towers
+        return v.view(v.shape[0], T, self.F_in) if self.divide_input else v.unsqueeze(1).expand(-1, T, -1)
+
+    def _post(self, xd, stats, lg: LayerGraph):
+        """scalers, ``post_nns`` and ``lin`` as torch modules over the statistics [n, A T F_in] (aggregator-major) of ``lg``'s rows."""
+        n, T, A = stats.shape[0], self.towers, len(self.aggregators)
+        am = self.aggr_module
+        scal = _pna_scaler_values(_pna_degrees(lg).to(stats.device), self.scalers, am.avg_deg_lin, am.avg_deg_log, stats.dtype)
+        st = stats.view(n, A, T, self.F_in).permute(0, 2, 1, 3).reshape(n, T, A * self.F_in)
+        cat = torch.cat([self._towers_of(xd)] + [st * scal[:, k].view(n, 1, 1) for k in range(len(self.scalers))], -1)
+        return self.lin(torch.cat([nn_t(cat[:, t]) for t, nn_t in enumerate(self.post_nns)], 1))
+
+    def _fold_weights(self):
+        """``(W_i, W_j, b)`` of ``m_ji = W_i x_i + W_j x_j + b`` over all towers ([T F_in, in_channels]; one tower: views of its weight)."""
+        Fi = self.F_in
+        ws, bs = [nn_t[0].weight for nn_t in self.pre_nns], [nn_t[0].bias for nn_t in self.pre_nns]
+        if self.towers == 1:
+            return ws[0][:, :Fi], ws[0][:, Fi:], bs[0]
+        stack = torch.block_diag if self.divide_input else (lambda *w: torch.cat(w))
+        return stack(*[w[:, :Fi] for w in ws]), stack(*[w[:, Fi:] for w in ws]), torch.cat(bs)
+
+    def _forward_layer(self, x, lg: LayerGraph, act=None, x_dst=None, no_root=False):
+        assert act in (None, "relu"), "act: None or 'relu'"
+        if no_root:
+            raise ValueError("PNAConv: (x_src, None) is not supported, the message needs the destinations' rows")
+        relu = act == "relu"
+        x16 = isinstance(x, LazyRows) and x.table.dtype in _X16
+        x = _x16_as_rows(x)
+        lazy = isinstance(x, LazyRows)
+        _, _, n_src, _ = _layer_input(self, x, lg, self.in_channels)
+        if x_dst is not None and x_dst.shape[1] != self.in_channels:
+            raise ValueError("PNAConv: the destination rows have %d features, the layer takes %d" % (x_dst.shape[1], self.in_channels))
+        plan = self._plan()
+        ok = (plan != "torch" and not x16 and not self.torch_ops
+              and all(v.is_cuda and v.dtype == torch.float32 for v in (x.table if lazy else x, x_dst) if torch.is_tensor(v))
+              and (not lazy or torch.is_tensor(x.table))
+              and all(_kernel_rows_ok(m.weight) for m in (self.post_nns[0][0], self.lin)))
+        self_all = None
+        if x_dst is None:
+            self_all = torch.cat([h.self_rows for h in lg.hops]) if lg.hops else torch.zeros(0, dtype=torch.int64, device=x.device)
+        if not ok:
+            self._ran = "torch"
+            xs = x.materialize() if lazy else x
+            xd = x_dst[:lg.n_rows] if x_dst is not None else xs[self_all]
+            dst, col = _pna_edges(lg)
+            h = torch.cat([self._towers_of(xd)[dst], self._towers_of(xs)[col]], -1)                   # [E, T, 2 F_in]
+            m = torch.stack([nn_t(h[:, t]) for t, nn_t in enumerate(self.pre_nns)], 1).reshape(h.shape[0], -1)
+            out = self._post(xd, _pna_stats_torch(m, dst, lg.n_rows, self.aggregators), lg)
+            return torch.relu(out) if relu else out
+        self._ran = plan
+        w_i, w_j, b = self._fold_weights()
+        y = linear_rows(x, w_j)
         if x_dst is not None:
-            _refuse_featureless(self, x_dst)
-        if isinstance(graph, HeteroLayerGraph):
-            raise NotImplementedError("GENConv over a heterogeneous call group's layer graph is not supported")
-        if isinstance(graph, LayerGraph):
-            if pair:
-                raise NotImplementedError("GENConv: an (x_src, x_dst) pair over a LayerGraph is not supported")
-            return self._forward_layer(x, graph, act)
-        if isinstance(x, LazyRows):
-            x = x.materialize()
-        if isinstance(x_dst, LazyRows):
-            x_dst = x_dst.materialize()
-        if isinstance(graph, (tuple, list)):
-            n_dst = int(graph[0].shape[0]) - 1
-        elif not pair:
-            n_dst = x.shape[0]
-        elif x_dst is not None:
-            n_dst = x_dst.shape[0]
-        else:                                                   # (x_src, None): as many rows as the edges reach (one read-back)
-            n_dst = int(graph[1].max()) + 1 if graph.shape[1] > 0 else 0
-        have = x.shape[0] if not pair else (x_dst.shape[0] if x_dst is not None else n_dst)
-        if have < n_dst:
-            raise ValueError("GENConv: %d destination rows for %d destinations" % (have, n_dst))
-        lg = _single_hop(graph, n_dst)[0]
-        return self._forward_layer(x, lg, act, x_dst=None if x_dst is None else x_dst[:n_dst], no_root=pair and x_dst is None)
+            xd = x_dst[:lg.n_rows]
+            a = linear_rows(xd, w_i, b)
+        else:
+            xd = x.table[x.ids[self_all].long()] if lazy else x[self_all]
+            a = linear_rows(x, w_i, b, rows=self_all)
+        cfg = (self.aggregators, self.scalers, self.aggr_module.floats())
+        if plan == "layer":
+            post, xd = self.post_nns[0][0], (xd if _kernel_rows_ok(xd) else xd.contiguous())
+            return _PnaLayer.apply(y, a, xd, post.weight, post.bias, self.lin.weight, self.lin.bias, lg, cfg, relu, n_src)
+        out = self._post(xd, _PnaLayer.apply(y, a, None, None, None, None, None, lg, cfg, False, n_src), lg)
+        return torch.relu(out) if relu else out
+
+    def forward(self, x, graph, act=None, edge_attr=None):
+        if edge_attr is not None or torch.is_tensor(act):
+            raise NotImplementedError("PNAConv: edge_attr (edge features) is not supported")
+        if self.training:
+            _refuse_capture(self, "per-graph caches in training mode")      # (the hops' transposes, cached against the graph object)
+        return _forward_graph_forms(self, x, graph, act)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -1415,6 +1415,64 @@ wholememory_error_code_t wgamd_gen_bwd_src_f32(const int* row_ptr_t, const int* 
                                                const float* dagg, int64_t ld_dagg, const int64_t* self_t, float* gx, int64_t ldgx,
                                                float* dt_part, int64_t n_blocks, void* stream);
 
+/* ---- PNA layer (csrc/wg_pna.hip): torch_geometric.nn.PNAConv (towers = 1, one pre and one post Linear) over a sampled hop ---------
+ * The message of edge j -> i is a[i] + Y[j] (Y = X W_j^T [n_src, F] read by row or through src_ids, a = X_dst W_i^T + b [n_rows, F],
+ * nullable = 0; both made by the caller), so only Y is reduced along a row's edges:
+ *   stat[i] = the n_aggr chosen of sum, mean, min, max, var, std of {a[i] + Y[j]} per channel, in the caller's order
+ *             var = mean of squares - square of mean (from deviations from the row's first message), std = sqrt(max(var, 0) + 1e-5);
+ *             every statistic of a row without edges is 0
+ *   Z[i]    = [x_dst[i] | s_1(deg_i) stat[i] | .. | s_S(deg_i) stat[i]] @ w_post^T + b_post      w_post [N, (1 + S n_aggr) F]
+ *   out[i]  = act(Z[i] @ w_lin^T + b_lin)          w_lin [N_out, N]; act = ReLU with WGAMD_GIN_RELU_OUT in flags
+ * scalers of d = max(deg_i, 1): identity 1, amplification log(d + 1) / avg_log, attenuation avg_log / log(d + 1), linear d / avg_lin,
+ * inverse_linear avg_lin / d.  aggregators / scalers: HOST arrays of the codes below.  One launch; a workgroup owns
+ * 16 x wgamd_pna_row_tiles(F, n_aggr, N) destination rows (4, 2 or 1 tiles: what fits 160 KB of LDS) and uses every weight fragment
+ * for all of them; neither the [E, F] messages nor the scaled concatenation are written.  w_post and w_lin come together; with
+ * both null (N = N_out = 0; scalers not read) the launch ends after the statistics: out = stat [n_rows, n_aggr F].
+ * _train also writes (each nullable) stats_out [n_rows, n_aggr F], mean_out = the mean of Y over the row [n_rows, F], argmin_out /
+ * argmax_out int32 [n_rows, ld_arg] = the CSR edge slot of the row's extreme per channel (strict compares: the lowest slot of a
+ * tie; -1 without edges) and z_out = Z [n_rows, N] (N % 4 == 0).
+ * wgamd_pna_bwd_src_f32, over the hop's transpose (wgamd_csr_transpose_i32: col_t = destination row, perm = CSR edge slot):
+ *   gy[j] = sum over the entries (i, slot e) of row j of  c0[i] + (Y[j] - meany[i]) c1[i] + [amax[i] = e] dmax[i] + [amin[i] = e] dmin[i]
+ * per channel, every term nullable (c1 with meany, dmax with amax, dmin with amin; perm is read only with dmax / dmin); every row of
+ * gy [n_src, F] is written; rows of more than 64 entries are summed in 64-entry pieces by all lane groups of a workgroup, the
+ * groups' sums added in a fixed order; n_blocks = wgamd_pna_bwd_blocks(n_src, max_blocks) = min(tiles of 16 input rows,
+ * max_blocks > 0 ? max_blocks : 4 x the device's compute units), tiles at a fixed stride.  No atomics.
+ * Domain: wgamd_pna_layer_supported(F, N): F % 4 == 0, 4 <= F <= 256, N <= 256 (N = 0: the statistics alone). */
+#define WGAMD_PNA_SUM 0
+#define WGAMD_PNA_MEAN 1
+#define WGAMD_PNA_MIN 2
+#define WGAMD_PNA_MAX 3
+#define WGAMD_PNA_VAR 4
+#define WGAMD_PNA_STD 5
+#define WGAMD_PNA_IDENTITY 0
+#define WGAMD_PNA_AMPLIFICATION 1
+#define WGAMD_PNA_ATTENUATION 2
+#define WGAMD_PNA_LINEAR 3
+#define WGAMD_PNA_INVERSE_LINEAR 4
+int wgamd_pna_layer_supported(int F, int N);
+int wgamd_pna_row_tiles(int F, int n_aggr, int N);
+int64_t wgamd_pna_bwd_blocks(int64_t n_src, int max_blocks);
+wholememory_error_code_t wgamd_pna_layer_f32(const int* row_ptr, const int* col, int64_t n_rows, const float* y, int64_t ldy, int F,
+                                             const void* src_ids, wholememory_dtype_t src_ids_dtype, const float* a, int64_t lda,
+                                             const float* x_dst, int64_t ldx_dst, const int* aggregators, int n_aggr,
+                                             const int* scalers, int n_scalers, float avg_lin, float avg_log, const float* w_post,
+                                             int64_t ldw_post, int N, const float* b_post, const float* w_lin, int64_t ldw_lin,
+                                             int N_out, const float* b_lin, int flags, float* out, int64_t ldo, void* stream);
+wholememory_error_code_t wgamd_pna_layer_f32_train(const int* row_ptr, const int* col, int64_t n_rows, const float* y, int64_t ldy,
+                                                   int F, const void* src_ids, wholememory_dtype_t src_ids_dtype, const float* a,
+                                                   int64_t lda, const float* x_dst, int64_t ldx_dst, const int* aggregators,
+                                                   int n_aggr, const int* scalers, int n_scalers, float avg_lin, float avg_log,
+                                                   const float* w_post, int64_t ldw_post, int N, const float* b_post,
+                                                   const float* w_lin, int64_t ldw_lin, int N_out, const float* b_lin, int flags,
+                                                   float* out, int64_t ldo, float* stats_out, int64_t ld_stats, float* mean_out,
+                                                   int64_t ld_mean, int* argmin_out, int* argmax_out, int64_t ld_arg, float* z_out,
+                                                   int64_t ld_z, void* stream);
+wholememory_error_code_t wgamd_pna_bwd_src_f32(const int* row_ptr_t, const int* col_t, const int* perm, int64_t n_src, const float* y,
+                                               int64_t ldy, int F, const void* src_ids, wholememory_dtype_t src_ids_dtype,
+                                               const float* c0, const float* c1, int64_t ld_c, const float* meany, int64_t ld_mean,
+                                               const float* dmax, const float* dmin, int64_t ld_d, const int* amax, const int* amin,
+                                               int64_t ld_arg, float* gy, int64_t ldgy, int64_t n_blocks, void* stream);
+
 /* ---- NormDropoutAct (csrc/wg_norm_act.hip): the row-wise block between two message-passing layers -------------------------------
  * What the reference's models put after a conv (mag_lp_mnmg.py: norm -> dropout -> relu, with the `+ lin1(x)` residual in the
  * encoder; gnn_model.py / rgcn / gin: relu -> dropout), over [n_rows, C] float32, for up to WGAMD_NORM_ACT_MAX_SEGMENTS node types
