@@ -51,6 +51,12 @@ class HeteroTransformerRelation(Structure):
                 ("F", c_int), ("ids_kind", c_int), ("D", c_int), ("H", c_int), ("col0", c_int)]
 
 
+class HgtRelation(Structure):
+    """wgamd_hgt_relation_t (include/wgamd_ext.h)."""
+    _fields_ = [("row_ptr", c_void_p), ("col", c_void_p), ("kv", c_void_p), ("ldkv", c_int64)]
+
+
+HGT_RELU = 1   # WGAMD_HGT_RELU (include/wgamd_ext.h)
 NORM_ACT_MAX_SEGMENTS, NORM_ACT_NORM, NORM_ACT_RELU, NORM_ACT_SAVE_STATS = 8, 1, 2, 4   # WGAMD_NORM_ACT_* (include/wgamd_ext.h)
 ROW_LINEAR_NORM_NONE, ROW_LINEAR_NORM_LAYER, ROW_LINEAR_NORM_L2 = 0, 1, 2                # WGAMD_ROW_LINEAR_NORM_* (include/wgamd_ext.h)
 
@@ -491,6 +497,15 @@ SYMBOLS = {
     "wgamd_pna_bwd_src_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p,
                                       c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
                                       c_void_p, c_int64, c_int64, c_void_p]),
+    # HGT layer, one softmax across the relations ending in a type (wg_hgt.hip)
+    "wgamd_hgt_layer_supported": (c_int, [c_int, c_int, c_int]),
+    "wgamd_hgt_layer_f32": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                    c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p,
+                                    c_int64, c_void_p, c_int64, c_void_p]),
+    "wgamd_hgt_bwd_dst_f32": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                      c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "wgamd_hgt_bwd_src_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                      c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     # NormDropoutAct (wg_norm_act.hip)
     "wgamd_norm_act_supported": (c_int, [c_int]),
     "wgamd_norm_act_segment_seed": (c_ulonglong, [c_ulonglong, c_int]),

@@ -7080,6 +7080,410 @@ class HeteroConv(torch.nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# HGT layer: ONE softmax over the edges of all relations into a row (torch_geometric.nn.HGTConv) — csrc/wg_hgt.hip
+# ---------------------------------------------------------------------------------------------------------------------
+hgt_launches = 0          # wgamd_hgt_layer_f32 launches so far (tests: the kernel route ran)
+
+
+def hgt_layer_supported(H: int, C: int, n_relations: int = 1) -> bool:
+    """Shapes of the one-kernel HGT layer (``wgamd_hgt_layer_supported``, answered on the host): H <= 8, C <= 256, D = C / H a
+    multiple of 4, at most ``WGAMD_HETERO_SAGE_MAX_RELATIONS`` (8) relations ending in one node type per hop — a joint softmax
+    cannot be cut across launches."""
+    return bool(L.lib().wgamd_hgt_layer_supported(int(H), int(C), int(n_relations)))
+
+
+def _hgt_relations(rels):
+    """The ``wgamd_hgt_relation_t`` array of ``rels = [(row_ptr, col, kv), ...]`` and what must outlive the launch."""
+    arr, keep = (L.HgtRelation * max(len(rels), 1))(), []
+    for d, (row_ptr, col, kv) in zip(arr, rels):
+        _check_csr(row_ptr, col)
+        assert _kernel_rows_ok(kv)
+        col = _nonempty(col, torch.int32)
+        keep.append(col)
+        d.row_ptr, d.col, d.kv, d.ldkv = row_ptr.data_ptr(), col.data_ptr(), kv.data_ptr(), kv.stride(0)
+    return arr, keep
+
+
+def hgt_layer_forward(rels, q, H: int, w_out, b_out=None, skip=None, root=None, relu=False, out_rows=None, out=None, keep=False):
+    """One ``wgamd_hgt_layer_f32`` launch (include/wgamd_ext.h) over the ``n`` rows of ``q`` [n, C]: ``rels = [(row_ptr, col, kv),
+    ...]`` with ``kv`` [*, 2C] the relation's folded keys and values side by side; ``skip`` (one float32 element on the device)
+    and ``root = (x_dst, dst_rows, dst_ids)`` come together: the gate.  ``keep``: returns ``(out, agg, lse)`` — the pre-GELU
+    aggregate [n, C] and the per-head log-sum-exp [n, H] the backward recomputes every weight from."""
+    global hgt_launches
+    n, C, dev = int(q.shape[0]), int(q.shape[1]), q.device
+    assert _kernel_rows_ok(q) and _kernel_rows_ok(w_out) and tuple(w_out.shape) == (C, C) and (skip is None) == (root is None)
+    x_dst, dst_rows, dst_ids = root if root is not None else (None, None, None)
+    assert x_dst is None or (_kernel_rows_ok(x_dst) and x_dst.shape[1] == C and skip.dtype == torch.float32 and skip.numel() == 1)
+    assert all(t is None or (t.dtype == torch.int64 and t.is_contiguous()) for t in (dst_rows, out_rows))
+    if out is None:
+        out = torch.empty((n, C), dtype=torch.float32, device=dev)
+    assert _kernel_rows_ok(out) and out.shape[1] == C
+    agg = torch.empty((n, C), dtype=torch.float32, device=dev) if keep else None
+    lse = torch.empty((n, H), dtype=torch.float32, device=dev) if keep else None
+    arr, alive = _hgt_relations(rels)
+    L.check(L.lib().wgamd_hgt_layer_f32(arr, len(rels), n, int(H), C, q.data_ptr(), q.stride(0), w_out.data_ptr(), w_out.stride(0),
+                                        _ptr(b_out), _ptr(skip), _ptr(x_dst), 0 if x_dst is None else x_dst.stride(0), _ptr(dst_rows),
+                                        _ptr(dst_ids), _sage_ids_kind(dst_ids), L.HGT_RELU if relu else 0, _ptr(out_rows),
+                                        out.data_ptr(), out.stride(0), _ptr(agg), C, _ptr(lse), int(H), get_stream()),
+            "wgamd_hgt_layer_f32")
+    del alive
+    if n > 0:
+        hgt_launches += 1
+    return (out, agg, lse) if keep else out
+
+
+def hgt_bwd_dst(rels, q, H: int, dagg, agg, lse):
+    """``wgamd_hgt_bwd_dst_f32``: ``(dq [n, C], delta [n, H])`` of one group from ``dagg = dL / d agg`` and the forward's ``agg`` and
+    ``lse`` — all relations walked again, every alpha recomputed."""
+    n, C = int(q.shape[0]), int(q.shape[1])
+    dq = torch.empty((n, C), dtype=torch.float32, device=q.device)
+    delta = torch.empty((n, H), dtype=torch.float32, device=q.device)
+    arr, alive = _hgt_relations(rels)
+    L.check(L.lib().wgamd_hgt_bwd_dst_f32(arr, len(rels), n, int(H), C, q.data_ptr(), q.stride(0), dagg.data_ptr(), dagg.stride(0),
+                                          agg.data_ptr(), agg.stride(0), lse.data_ptr(), lse.stride(0), dq.data_ptr(), dq.stride(0),
+                                          delta.data_ptr(), delta.stride(0), get_stream()), "wgamd_hgt_bwd_dst_f32")
+    del alive
+    return dq, delta
+
+
+def hgt_bwd_src(row_ptr_t, col_t, kv, q, H: int, dagg, lse, delta):
+    """``wgamd_hgt_bwd_src_f32`` over one relation hop's transpose: ``dkv`` [rows of kv, 2C], every row written."""
+    n_src, C = int(row_ptr_t.shape[0]) - 1, int(q.shape[1])
+    assert n_src == kv.shape[0] and _kernel_rows_ok(kv)
+    dkv = torch.empty((n_src, 2 * C), dtype=torch.float32, device=q.device)
+    L.check(L.lib().wgamd_hgt_bwd_src_f32(row_ptr_t.data_ptr(), _nonempty(col_t, torch.int32).data_ptr(), n_src, int(H), C, kv.data_ptr(),
+                                          kv.stride(0), q.data_ptr(), q.stride(0), dagg.data_ptr(), dagg.stride(0), lse.data_ptr(),
+                                          lse.stride(0), delta.data_ptr(), delta.stride(0), dkv.data_ptr(), dkv.stride(0), get_stream()),
+            "wgamd_hgt_bwd_src_f32")
+    return dkv
+
+
+def _hgt_group_torch(q, rels, H: int, w_out, b_out, skip, xd, relu: bool):
+    """One (hop, destination type) group of the HGT layer out of torch ops (any dtype and device, ordinary autograd): ``rels =
+    [(row_ptr, col, kv), ...]`` as ``hgt_layer_forward`` takes them, ``xd`` [n, C] the destination rows of the gate or None.  The
+    edges of all relations are concatenated, their [E, H] logits meet one scattered maximum and two ``index_add`` sums — what the
+    kernel never writes.  The ``"torch"`` route of ``HGTConv`` and the double backward of the kernel route."""
+    n, C = q.shape
+    D = C // H
+    logits, vals, dsts = [], [], []
+    for row_ptr, col, kv in rels:
+        E = int(col.shape[0])
+        if E == 0:
+            continue
+        dst = _edge_dst(row_ptr, E)
+        kvj = kv[col.long()]
+        logits.append((q[dst].view(E, H, D) * kvj[:, :C].reshape(E, H, D)).sum(-1))
+        vals.append(kvj[:, C:].reshape(E, H, D))
+        dsts.append(dst)
+    agg = torch.zeros((n, H, D), dtype=q.dtype, device=q.device)
+    if logits:
+        lg, v, dst = torch.cat(logits), torch.cat(vals), torch.cat(dsts)
+        top = torch.full((n, H), -math.inf, dtype=q.dtype, device=q.device).scatter_reduce(
+            0, dst.unsqueeze(1).expand(-1, H), lg.detach(), "amax")
+        w = torch.exp(lg - top[dst])
+        den = torch.zeros((n, H), dtype=q.dtype, device=q.device).index_add(0, dst, w)
+        agg = agg.index_add(0, dst, w.unsqueeze(-1) * v) / (den + (den == 0)).unsqueeze(-1)
+    o = torch.nn.functional.linear(torch.nn.functional.gelu(agg.reshape(n, C)), w_out, b_out)
+    if xd is not None:
+        g = torch.sigmoid(skip)
+        o = g * o + (1 - g) * xd
+    return torch.relu(o) if relu else o
+
+
+class _HgtGroup(torch.autograd.Function):
+    """One (hop, destination type) group of the HGT layer under autograd.  ``grp``: dict(rels = [(row_ptr, col, RelationHop | None),
+    ...], H, relu, dst_rows, dst_ids); differentiable inputs: the queries ``q``, ``out_lin``'s weight and bias, ``skip``, the
+    resident rows ``x_dst`` the gate reads (None: no gate, or a lazily read table) and every relation's ``kv``.  Forward: ONE
+    launch that keeps the pre-GELU ``agg`` and the per-head log-sum-exp.  Backward: the dense part out of library ops (``do``
+    from the gate and the ReLU mask, ``d out_lin``, ``dagg = (do @ W_out) gelu'(agg)``, ``d skip``, the gated part of ``dx_dst``),
+    then ``wgamd_hgt_bwd_dst_f32`` (dq, delta) and per relation ``wgamd_hgt_bwd_src_f32`` over the hop's transpose (dkv) — no
+    atomics: the same bits from run to run.  A backward under ``create_graph=True`` runs out of torch ops."""
+
+    @staticmethod
+    def forward(ctx, grp, q, w_out, b_out, skip, x_dst, x_gate, *kvs):
+        rels = [(rp, col, kv.detach()) for (rp, col, _), kv in zip(grp["rels"], kvs)]
+        root = None if skip is None else (x_gate, grp["dst_rows"], grp["dst_ids"])
+        out, agg, lse = hgt_layer_forward(rels, q.detach(), grp["H"], *_detached((w_out, b_out, skip)), root=root, relu=grp["relu"],
+                                          keep=True)
+        ctx.grp, ctx.kept, ctx.n_kv = grp, (agg, lse), len(kvs)
+        ctx.gate_rows = None if x_gate is x_dst else x_gate      # (rows that are no input of the graph: a table, or gathered rows)
+        ctx.save_for_backward(q, w_out, b_out, skip, x_dst, out, *kvs)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            return _hgt_double_backward(ctx, g)
+        _released(ctx.kept, "HGTConv", "aggregate and log-sum-exp rows")
+        q, w_out, b_out, skip, x_dst, out = _detached(ctx.saved_tensors[:6])
+        kvs = _detached(ctx.saved_tensors[6:])
+        grp, (agg, lse), H = ctx.grp, ctx.kept, ctx.grp["H"]
+        need = ctx.needs_input_grad
+        g, _ = _dz(g, out, grp["relu"])
+        ga = torch.nn.functional.gelu(agg)
+        gskip = gxd = None
+        do = g
+        if skip is not None:
+            sg = torch.sigmoid(skip)
+            do = g * sg
+            if need[4] or need[5]:
+                rows, x_gate = grp["dst_rows"], x_dst if ctx.gate_rows is None else ctx.gate_rows
+                xg = x_gate[rows] if grp["dst_ids"] is None else x_gate[grp["dst_ids"][rows].long()]
+                if need[4]:
+                    o = torch.nn.functional.linear(ga, w_out, b_out)
+                    gskip = ((g * (o - xg)).sum() * sg * (1 - sg)).reshape(skip.shape)
+                if need[5] and x_dst is not None:
+                    gxd = torch.zeros_like(x_dst, dtype=torch.float32).index_copy_(0, rows, g * (1 - sg))      # (rows of one group are distinct)
+        gw = do.t() @ ga if need[2] else None
+        gb = do.sum(0) if need[3] and b_out is not None else None
+        gq, gkvs = None, [None] * ctx.n_kv
+        if need[1] or any(need[7:]):
+            # gelu'(x) = Phi(x) + x phi(x)
+            dgelu = 0.5 * (1 + torch.erf(agg * (0.5 ** 0.5))) + agg * torch.exp(-0.5 * agg * agg) * (1 / math.sqrt(2 * math.pi))
+            dagg = ((do @ w_out) * dgelu).contiguous()
+            rels = [(rp, col, kv) for (rp, col, _), kv in zip(grp["rels"], kvs)]
+            gq, delta = hgt_bwd_dst(rels, q, H, dagg, agg, lse)
+            for k, ((_, _, hop), kv) in enumerate(zip(grp["rels"], kvs)):
+                if not need[7 + k]:
+                    continue
+                if hop is None or hop.n_edges == 0:
+                    gkvs[k] = torch.zeros_like(kv)
+                else:
+                    row_ptr_t, col_t, _ = _relation_transpose(hop, int(kv.shape[0]))
+                    gkvs[k] = hgt_bwd_src(row_ptr_t, col_t, kv, q, H, dagg, lse, delta)
+        ctx.kept = ctx.gate_rows = None
+        return (None, gq if need[1] else None, gw, gb, gskip, gxd, None) + tuple(gkvs)
+
+
+def _hgt_double_backward(ctx, g):
+    """The gradients as differentiable torch expressions of the saved inputs and ``g``."""
+    q, w_out, b_out, skip, x_dst, _ = ctx.saved_tensors[:6]
+    kvs, grp = ctx.saved_tensors[6:], ctx.grp
+
+    def make_y():
+        xd = None
+        if skip is not None:
+            if x_dst is None:
+                raise _lazy_table_grad_error()
+            xd = x_dst[grp["dst_rows"]]
+        rels = [(rp, col, kv) for (rp, col, _), kv in zip(grp["rels"], kvs)]
+        return _hgt_group_torch(q, rels, grp["H"], w_out, b_out, skip, xd, grp["relu"])
+    ins = [(1, q), (2, w_out), (3, b_out), (4, skip), (5, x_dst)] + [(7 + k, kv) for k, kv in enumerate(kvs)]
+    return tuple(_grads_from_torch(make_y, [(i, t) for i, t in ins if ctx.needs_input_grad[i]], g, [None] * (7 + len(kvs))))
+
+
+class _TypeLinears(torch.nn.Module):
+    """One ``torch.nn.Linear`` per node type under ``lins`` (state-dict names ``lins.{type}.weight`` / ``.bias``), glorot weights
+    and zero biases."""
+
+    def __init__(self, in_channels, out_channels: int):
+        super().__init__()
+        self.lins = torch.nn.ModuleDict({t: torch.nn.Linear(int(f), out_channels) for t, f in in_channels.items()})
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for lin in self.lins.values():
+            torch.nn.init.xavier_uniform_(lin.weight)
+            torch.nn.init.zeros_(lin.bias)
+
+    def __getitem__(self, t):
+        return self.lins[t]
+
+
+class _RelationMaps(torch.nn.Module):
+    """The head-wise ``D x D`` maps of every relation: ``weight`` [R H, D, D], map ``r H + h`` for head h of relation r."""
+
+    def __init__(self, n: int, D: int):
+        super().__init__()
+        self.weight = torch.nn.Parameter(torch.empty(n, D, D))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        torch.nn.init.xavier_uniform_(self.weight)
+
+
+class HGTConv(torch.nn.Module):
+    """PyG ``HGTConv`` (Heterogeneous Graph Transformer): for a destination row ``i`` of type ``d``, with ``D = out_channels // heads``,
+
+        k_s, q_d, v_s = split(kqv_lin[type](x))                                     [n, H, D] each
+        logit_ijh = q_i[h] . (k_j[h] @ k_rel[r, h]) * p_rel[r][h] / sqrt(D)         every relation r = (s, rel, d), edge j -> i
+        alpha     = softmax over ALL edges into i of ALL relations, per head
+        agg_i     = sum alpha_ijh (v_j[h] @ v_rel[r, h])                            (0 for a row without any edge)
+        o_i       = out_lin[d](gelu(agg_i))                                         exact (erf) GELU
+        out_i     = sigmoid(skip[d]) o_i + (1 - sigmoid(skip[d])) x_i   where x_d is ``out_channels`` wide, else o_i
+
+    — not ``HeteroConv`` over ``TransformerConv`` relations: that runs one softmax per relation and sums.  A node type no relation
+    of the graph ends in is absent from the result.  ``in_channels``: an int or ``{node type: int}``; ``metadata = (node_types,
+    edge_types)``.
+
+    State-dict names — chosen after PyG's current layout (not checked against an installed PyG): ``kqv_lin.lins.{type}.weight`` /
+    ``.bias`` ([3C, F_type], rows in the order k, q, v), ``out_lin.lins.{type}.weight`` / ``.bias``, ``k_rel.weight`` and
+    ``v_rel.weight`` ([R H, D, D], index ``r H + h`` with r the position in ``metadata[1]``), ``skip.{type}`` (one element) and
+    ``p_rel.{src__rel__dst}`` ([1, H]).  ``skip`` and ``p_rel`` start at 1, the rest glorot (biases 0).
+
+    ``forward(x_dict, graph, act=None)``: ``graph`` a call group's ``HeteroLayerGraph`` (``x_dict`` values tensors or ``LazyRows``;
+    hops, ``dst_rows`` and ``out_rows`` honoured; the result is ``{type: [n_out[type], C]}``), or a dict ``{edge_type: edge_index |
+    [row_ptr, col]}`` over a mini-batch ``HeteroData`` (each relation one hop; the same path).  ``act="relu"`` is fused.
+    ``route`` names what the last forward ran:
+    * ``"layer"`` — TRANSFORM-FIRST.  Per relation the key / value weights of the source type, the relation's maps and its prior are
+      folded (torch ops under autograd, cached by ``_derived``) into one ``[2C, F_s]`` weight — ``Wfold_r^T`` in the
+      ``torch.nn.Linear`` layout ``linear_rows`` reads — and ``kv_r = linear_rows(x_s, Wfold_r)`` puts a source row's key and value
+      side by side; ``q = linear_rows(x_d, W_q, rows=dst_rows)`` per (hop, destination type); then ONE ``wgamd_hgt_layer_f32``
+      launch per (hop, destination type) whatever the number of relations: one online softmax per (row, head) across the
+      relations' CSR rows, ``out_lin`` on the fp32 matrix pipe, the gate, ReLU and row placement in the kernel.  No ``[E, H]`` array
+      and no concatenated edge list is written; training keeps ``agg`` [n, C] and one log-sum-exp per (row, head), and the
+      backward is two kernels per group without atomics (``_HgtGroup``).  Domain: ``hgt_layer_supported`` and float32 device rows.
+    * ``"torch"`` — the same formula out of torch ops (``_hgt_group_torch``): shapes outside the domain (more than 8 relations
+      into one type: a joint softmax cannot be split into consecutive launches), CPU tensors, other dtypes, a double backward,
+      and every forward of a layer whose ``torch_ops`` attribute is set.
+    HIP-graph capture is a RuntimeError (derived-weight caches); a gradient into a lazily read table is NotImplementedError."""
+
+    def __init__(self, in_channels, out_channels: int, metadata, heads: int = 1):
+        super().__init__()
+        if out_channels % heads != 0:
+            raise ValueError("HGTConv: out_channels (%d) must be divisible by heads (%d)" % (out_channels, heads))
+        node_types, edge_types = list(metadata[0]), [tuple(et) for et in metadata[1]]
+        if not isinstance(in_channels, dict):
+            in_channels = {t: in_channels for t in node_types}
+        self.in_channels = {t: int(in_channels[t]) for t in node_types}
+        self.out_channels, self.heads = int(out_channels), int(heads)
+        self.node_types, self.edge_types = node_types, edge_types
+        C, H, D = self.out_channels, self.heads, self.out_channels // self.heads
+        self.kqv_lin = _TypeLinears(self.in_channels, 3 * C)
+        self.out_lin = _TypeLinears({t: C for t in node_types}, C)
+        self.k_rel = _RelationMaps(len(edge_types) * H, D)
+        self.v_rel = _RelationMaps(len(edge_types) * H, D)
+        self.skip = torch.nn.ParameterDict({t: torch.nn.Parameter(torch.ones(1)) for t in node_types})
+        self.p_rel = torch.nn.ParameterDict({"__".join(et): torch.nn.Parameter(torch.ones(1, H)) for et in edge_types})
+        self._wgamd_derived = {}
+        self.route = None
+        self.torch_ops = False      # True: every forward takes the "torch" route (the examples' --torch-ops)
+
+    def reset_parameters(self):
+        for m in (self.kqv_lin, self.out_lin, self.k_rel, self.v_rel):
+            m.reset_parameters()
+        for p in list(self.skip.values()) + list(self.p_rel.values()):
+            torch.nn.init.ones_(p)
+
+    def _fold(self, et, grad: bool):
+        """``(Wfold^T [2C, F_s], bias [2C])`` of relation ``et``: rows ``[:C]`` give ``(k[h] @ k_rel[r, h]) p_rel[r][h] / sqrt(D)``, rows
+        ``[C:]`` give ``v[h] @ v_rel[r, h]`` — ``torch.nn.Linear`` layout.  ``grad``: under autograd, so the gradient of ``kv`` reaches
+        ``kqv_lin``, ``k_rel``, ``v_rel`` and ``p_rel``; otherwise detached and kept."""
+        C, H = self.out_channels, self.heads
+        D, r = C // H, self.edge_types.index(et)
+        lin, p = self.kqv_lin[et[0]], self.p_rel["__".join(et)]
+
+        def build():
+            F_ = lin.weight.shape[1]
+            ka = self.k_rel.weight[r * H:(r + 1) * H] * (p.view(H, 1, 1) / math.sqrt(D))
+            va = self.v_rel.weight[r * H:(r + 1) * H]
+            wk, wv = lin.weight[:C].view(H, D, F_), lin.weight[2 * C:].view(H, D, F_)
+            bk, bv = lin.bias[:C].view(H, D), lin.bias[2 * C:].view(H, D)
+            w = torch.cat([torch.einsum("hde,hdf->hef", ka, wk).reshape(C, F_), torch.einsum("hde,hdf->hef", va, wv).reshape(C, F_)])
+            b = torch.cat([torch.einsum("hde,hd->he", ka, bk).reshape(C), torch.einsum("hde,hd->he", va, bv).reshape(C)])
+            return w.contiguous(), b.contiguous()
+        return _derived(self, ("fold", et), (lin.weight, lin.bias, self.k_rel.weight, self.v_rel.weight, p), build, grad=grad)
+
+    def _dict_graph(self, x_dict, graph):
+        """The dict form as a one-hop ``HeteroLayerGraph``: destinations of a type = all its rows, in order."""
+        rels, n_out = [], {}
+        for et in self.edge_types:
+            e = graph.get(et)
+            if e is None or x_dict.get(et[0]) is None or x_dict.get(et[2]) is None:
+                continue
+            n = int(x_dict[et[2]].shape[0])
+            row_ptr, col = (e[0], e[1]) if isinstance(e, (tuple, list)) else _to_csr(e, n)
+            if row_ptr.shape[0] != n + 1:
+                raise ValueError("HGTConv: the CSR of %r has %d rows, x_dict[%r] has %d" % (et, row_ptr.shape[0] - 1, et[2], n))
+            rels.append(RelationHop(et, 0, row_ptr, col, _arange(n, row_ptr.device), None, int(col.shape[0]), 0))
+            n_out[et[2]] = n
+        return HeteroLayerGraph(rels, n_out, self.node_types)
+
+    def forward(self, x_dict, graph, act=None):
+        if act not in (None, "relu"):
+            raise ValueError("HGTConv: act is None or 'relu', not %r" % (act,))
+        _refuse_capture(self, "derived-weight caches")
+        if not isinstance(graph, HeteroLayerGraph):
+            graph = self._dict_graph(x_dict, graph)
+        return self._forward_layer(x_dict, graph, act == "relu")
+
+    def _forward_layer(self, xs, graph: HeteroLayerGraph, relu: bool):
+        C, H = self.out_channels, self.heads
+        xs = {t: v for t, v in xs.items() if v is not None}
+        for t, v in xs.items():
+            _refuse_featureless(self, v)
+            if v.shape[1] != self.in_channels[t]:
+                raise ValueError("HGTConv: x_dict[%r] has %d features, the layer takes %d" % (t, v.shape[1], self.in_channels[t]))
+            if isinstance(v, LazyRows):
+                _refuse_lazy_table_grad(v.table)
+        groups = [(key, mine) for key, mine in _relation_groups(graph) if mine[0].n_rows > 0]
+        for (_, dt), mine in groups:
+            for r in mine:
+                if dt not in xs or (r.edge_type[0] not in xs and r.n_edges > 0):
+                    raise ValueError("HGTConv: x_dict has no rows for %r, which relation %r needs" % (
+                        dt if dt not in xs else r.edge_type[0], r.edge_type))
+        params = list(self.parameters())
+        dev = params[0].device
+        kernel = (not self.torch_ops and all(p.is_cuda and p.dtype == torch.float32 for p in params)
+                  and all(hgt_layer_supported(H, C, len(mine)) for _, mine in groups)
+                  and all(torch.is_tensor(v.table if isinstance(v, LazyRows) else v) and v.device == dev
+                          and (v.dtype == torch.float32 or (isinstance(v, LazyRows) and v.dtype in _X16)) for v in xs.values()))
+        self.route = "layer" if kernel else "torch"
+        if not kernel:
+            xs = {t: (v.materialize() if isinstance(v, LazyRows) else v) for t, v in xs.items()}
+        needs_grad = _needs_grad(params, *xs.values())
+        out = {}
+        if kernel:
+            out = _group_outputs(graph, groups, lambda t: C, dev, make=torch.zeros if needs_grad else torch.empty)
+        kvs = {}
+
+        def kv_of(et):      # [rows of x_s, 2C]: once per edge type, whatever the number of hops
+            if et not in kvs:
+                w, b = self._fold(et, needs_grad)
+                kvs[et] = linear_rows(xs[et[0]], w, b) if kernel else torch.nn.functional.linear(xs[et[0]], w, b)
+            return kvs[et]
+        for (hop, dt), mine in groups:
+            head = mine[0]
+            n_f, dst_rows, place = head.n_rows, head.dst_rows, head.out_rows
+            lin, lout, x_d = self.kqv_lin[dt], self.out_lin[dt], xs[dt]
+            gate = self.in_channels[dt] == C
+            live = [r for r in mine if r.n_edges > 0 and r.edge_type[0] in xs]      # (a relation without edges adds no term)
+            if not kernel:
+                q = torch.nn.functional.linear(x_d[dst_rows], lin.weight[C:2 * C], lin.bias[C:2 * C])
+                rels = [(r.row_ptr, r.col[:r.n_edges], kv_of(r.edge_type)) for r in live]
+                y = _hgt_group_torch(q, rels, H, lout.weight, lout.bias, self.skip[dt], x_d[dst_rows] if gate else None, relu)
+                if place is not None and dt not in out:
+                    out[dt] = torch.zeros((graph.n_out[dt], C), dtype=y.dtype, device=y.device)
+                _place_rows(out, dt, y, place)
+                continue
+            q = linear_rows(x_d, lin.weight[C:2 * C], lin.bias[C:2 * C], rows=dst_rows)
+            rel_kvs = [kv_of(r.edge_type) for r in live]
+            skip = x_res = x_gate = ids = None
+            rows = dst_rows
+            if gate:         # the gate's other side, read in the kernel: resident rows, a table through its node list, or gathered
+                skip = self.skip[dt]
+                lazy = _table_through_ids(x_d)
+                if lazy is not None:
+                    x_gate, ids = lazy
+                elif isinstance(x_d, LazyRows):
+                    x_gate, rows = x_d.table[x_d.ids[dst_rows].long()].float(), _arange(n_f, dev)
+                else:
+                    x_res = x_gate = x_d if _kernel_rows_ok(x_d) else x_d.contiguous()
+            if needs_grad:
+                grp = dict(rels=[(r.row_ptr, r.col[:r.n_edges], r) for r in live], H=H, relu=relu, dst_rows=rows, dst_ids=ids)
+                y = _HgtGroup.apply(grp, q, lout.weight, lout.bias, skip, x_res, x_gate, *rel_kvs)
+                _place_rows(out, dt, y, place)
+            else:
+                rels = [(r.row_ptr, r.col[:r.n_edges], kv.detach()) for r, kv in zip(live, rel_kvs)]
+                y = hgt_layer_forward(rels, q.detach(), H, *_detached((lout.weight, lout.bias, skip)),
+                                      root=None if skip is None else (x_gate, rows, ids), relu=relu, out_rows=place,
+                                      out=out[dt] if place is not None else None)
+                if place is None:
+                    out[dt] = y
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # NormDropoutAct: the row-wise block between two layers (LayerNorm, dropout, ReLU, residual) — csrc/wg_norm_act.hip
 # ---------------------------------------------------------------------------------------------------------------------
 _M64 = (1 << 64) - 1

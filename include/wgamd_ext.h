@@ -1473,6 +1473,51 @@ wholememory_error_code_t wgamd_pna_bwd_src_f32(const int* row_ptr_t, const int* 
                                                const float* dmax, const float* dmin, int64_t ld_d, const int* amax, const int* amin,
                                                int64_t ld_arg, float* gy, int64_t ldgy, int64_t n_blocks, void* stream);
 
+/* ---- HGT layer (csrc/wg_hgt.hip): torch_geometric.nn.HGTConv over one (hop, destination type) of a call group --------------------
+ * The caller folds the node-type key / value weights, the relation's head-wise D x D maps and its prior into one operand per
+ * relation: row j of kv ([*, ldkv], 2C floats used) = [ k'_j | v'_j ], k'_j[h] = (k_j[h] @ k_rel[r, h]) p_rel[r][h] / sqrt(D),
+ * v'_j[h] = v_j[h] @ v_rel[r, h].  Over n_rows destination rows with the queries q [n_rows, ldq] and every relation's CSR
+ * (row_ptr int32 [n_rows + 1], col int32 = row of kv):
+ *   alpha_ijh = softmax over ALL edges j -> i of ALL n_rel relations, per head, of  q_i[h] . k'_j[h]
+ *   agg_i     = sum alpha_ijh v'_j[h]                                  (0 for a row without an edge in any relation)
+ *   o_i       = gelu(agg_i) @ w_out^T + b_out                          exact (erf) GELU; w_out [C, ldw], b_out nullable
+ *   out[p]    = act(g o_i + (1 - g) XD[i])                             g = sigmoid(*skip), skip ONE float on the device; skip and
+ *                                                                      x_dst both null: out[p] = act(o_i)
+ * XD[i] = x_dst[dst_ids_kind ? dst_ids[s] : s], s = dst_rows ? dst_rows[i] : i (kinds as wgamd_hetero_sage_layer_f32: 0 by row,
+ * 1 int32, 2 int64); p = out_rows ? out_rows[i] : i; act = ReLU with WGAMD_HGT_RELU in flags.  ONE launch whatever n_rel: one
+ * online softmax state per (row, head) runs across the relations in array order.  agg_out [n_rows, ld_agg] (the pre-GELU agg) and
+ * lse_out [n_rows, ld_lse] (H used: the log-sum-exp of the row's logits per head; 0 without edges), each nullable, are what the
+ * backward recomputes every alpha from — nothing per edge is written.
+ * wgamd_hgt_bwd_dst_f32 (same relations): from dagg = dL / d agg, delta[i, h] = dagg_ih . agg_ih and
+ *   dq_i = sum_j ds_ijh k'_j[h],  ds_ijh = alpha_ijh (dagg_ih . v'_j[h] - delta_ih),  alpha = exp(q . k' - lse).
+ * wgamd_hgt_bwd_src_f32, per relation over the hop's transpose (wgamd_csr_transpose_i32: rows = rows of kv, col_t = destination
+ * row): dkv[j] = [ sum_i ds_ijh q_i[h] | sum_i alpha_ijh dagg_ih ], every one of the n_src rows written.  No atomics; sums in CSR
+ * (transposed CSR) order: the same bits on every run.
+ * Domain: wgamd_hgt_layer_supported(H, C, n_rel): 1 <= H <= 8, C <= 256, C % H == 0, (C / H) % 4 == 0, n_rel <=
+ * WGAMD_HETERO_SAGE_MAX_RELATIONS; kv / q / w_out / x_dst / out / agg / dagg / dq / dkv rows 16-B aligned.  The out_lin product
+ * runs on the exact fp32 matrix pipe (v_mfma_f32_16x16x4_f32). */
+#define WGAMD_HGT_RELU 1
+typedef struct {
+  const int* row_ptr;
+  const int* col;
+  const float* kv;
+  int64_t ldkv;
+} wgamd_hgt_relation_t;
+int wgamd_hgt_layer_supported(int H, int C, int n_rel);
+wholememory_error_code_t wgamd_hgt_layer_f32(const wgamd_hgt_relation_t* rels, int n_rel, int64_t n_rows, int H, int C, const float* q,
+                                             int64_t ldq, const float* w_out, int64_t ldw, const float* b_out, const float* skip,
+                                             const float* x_dst, int64_t ldx_dst, const int64_t* dst_rows, const void* dst_ids,
+                                             int dst_ids_kind, int flags, const int64_t* out_rows, float* out, int64_t ldo,
+                                             float* agg_out, int64_t ld_agg, float* lse_out, int64_t ld_lse, void* stream);
+wholememory_error_code_t wgamd_hgt_bwd_dst_f32(const wgamd_hgt_relation_t* rels, int n_rel, int64_t n_rows, int H, int C,
+                                               const float* q, int64_t ldq, const float* dagg, int64_t ld_dagg, const float* agg,
+                                               int64_t ld_agg, const float* lse, int64_t ld_lse, float* dq, int64_t ld_dq,
+                                               float* delta, int64_t ld_delta, void* stream);
+wholememory_error_code_t wgamd_hgt_bwd_src_f32(const int* row_ptr_t, const int* col_t, int64_t n_src, int H, int C, const float* kv,
+                                               int64_t ldkv, const float* q, int64_t ldq, const float* dagg, int64_t ld_dagg,
+                                               const float* lse, int64_t ld_lse, const float* delta, int64_t ld_delta, float* dkv,
+                                               int64_t ld_dkv, void* stream);
+
 /* ---- NormDropoutAct (csrc/wg_norm_act.hip): the row-wise block between two message-passing layers -------------------------------
  * What the reference's models put after a conv (mag_lp_mnmg.py: norm -> dropout -> relu, with the `+ lin1(x)` residual in the
  * encoder; gnn_model.py / rgcn / gin: relu -> dropout), over [n_rows, C] float32, for up to WGAMD_NORM_ACT_MAX_SEGMENTS node types
