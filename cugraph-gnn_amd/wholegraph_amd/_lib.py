@@ -506,6 +506,16 @@ SYMBOLS = {
                                       c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "wgamd_hgt_bwd_src_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                       c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    # attention inside the segments of a row table, GPSConv's global branch (wg_segment_attention.hip)
+    "wgamd_segment_attention_supported": (c_int, [c_int, c_int]),
+    "wgamd_segment_attention_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int,
+                                            c_int, c_float, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "wgamd_segment_attention_bwd_q_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                                  c_int, c_int, c_float, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                                  c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "wgamd_segment_attention_bwd_kv_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int64,
+                                                   c_int, c_int, c_float, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                                   c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     # NormDropoutAct (wg_norm_act.hip)
     "wgamd_norm_act_supported": (c_int, [c_int]),
     "wgamd_norm_act_segment_seed": (c_ulonglong, [c_ulonglong, c_int]),

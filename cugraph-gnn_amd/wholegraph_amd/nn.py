@@ -13,7 +13,7 @@ epilogue, one launch.
 
 Order of the file: ctypes helpers and the plumbing the one-kernel layers share; the SAGE-era kernel wrappers, derived-weight
 caches and GAT kernel wrappers; graph forms (``_single_hop``, ``LazyRows``, ``HopGraph``, ``LayerGraph``) and the helpers that
-walk a layer graph; then a section per layer — SAGE and GAT, GCN, RGCN, transformer, GIN, GATv2, GINE, GEN, heterogeneous, NormDropoutAct, RowLinear —
+walk a layer graph; then a section per layer — SAGE and GAT, GCN, RGCN, transformer, GIN, GATv2, GINE, GEN, heterogeneous, NormDropoutAct, RowLinear, segment attention and GPS —
 each with its kernel wrappers, its autograd Function(s) and its module.
 
 Shared by the one-kernel layers, so that they cannot drift apart: ``_hop_args`` (the eight leading arguments of a launch over a
@@ -8095,3 +8095,306 @@ class RowLinear(torch.nn.Module):
 
     def extra_repr(self):
         return "relu=%s, norm=%r, eps=%g" % (self.relu, self.norm_kind, self.eps)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Attention inside each graph of a batch and the GraphGPS block (torch_geometric.nn.GPSConv) — csrc/wg_segment_attention.hip
+# ---------------------------------------------------------------------------------------------------------------------
+segment_attention_launches = 0      # launches of the three wgamd_segment_attention* kernels so far (tests: the kernel route ran)
+
+
+def segment_attention_supported(H: int, D: int) -> bool:
+    """Shapes of the segment attention kernels (``wgamd_segment_attention_supported``, answered on the host): 1 <= H <= 8 heads
+    of D channels, D % 4 == 0, 4 <= D <= 64, H D <= 256."""
+    return bool(L.lib().wgamd_segment_attention_supported(int(H), int(D)))
+
+
+def _segment_attention_args(q, k, v, ptr, H: int, scale: float):
+    """The twelve leading arguments of the three launches, with their checks."""
+    n, C = int(q.shape[0]), int(q.shape[1])
+    assert all(_kernel_rows_ok(t) and tuple(t.shape) == (n, C) for t in (q, k, v)) and C % H == 0
+    assert ptr.dtype == torch.int64 and ptr.is_cuda and ptr.is_contiguous() and ptr.dim() == 1 and ptr.shape[0] >= 1
+    return (q.data_ptr(), q.stride(0), k.data_ptr(), k.stride(0), v.data_ptr(), v.stride(0), ptr.data_ptr(), int(ptr.shape[0]) - 1, n,
+            int(H), C // int(H), float(scale))
+
+
+def _segment_attention_launch(name: str, args, n: int):
+    global segment_attention_launches
+    L.check(getattr(L.lib(), name)(*args, get_stream()), name)
+    if n > 0:
+        segment_attention_launches += 1
+
+
+def segment_attention_forward(q, k, v, ptr, H: int, scale: float, keep: bool = False):
+    """One ``wgamd_segment_attention_f32`` launch (include/wgamd_ext.h): ``out`` [n, C] of the float32 ``[n, C]`` views ``q``,
+    ``k``, ``v`` (unit column stride, 16-B aligned rows any distance apart) over the segments of ``ptr`` (int64 [G + 1] on the
+    device).  ``keep``: returns ``(out, lse)`` with the per-head log-sum-exp [n, H] the backward recomputes every weight from."""
+    n, C = int(q.shape[0]), int(q.shape[1])
+    out = torch.empty((n, C), dtype=torch.float32, device=q.device)
+    lse = torch.empty((n, H), dtype=torch.float32, device=q.device) if keep else None
+    _segment_attention_launch("wgamd_segment_attention_f32", _segment_attention_args(q, k, v, ptr, H, scale)
+                              + (out.data_ptr(), out.stride(0), _ptr(lse), int(H)), n)
+    return (out, lse) if keep else out
+
+
+def segment_attention_backward(q, k, v, ptr, H: int, scale: float, dout, out, lse, need_kv: bool = True):
+    """``(dq, dk, dv)`` from ``dout`` [n, C] and the forward's ``out`` and ``lse``: ``wgamd_segment_attention_bwd_q_f32`` (dq and
+    delta [n, H]), then ``wgamd_segment_attention_bwd_kv_f32`` (``need_kv``) — column views of ONE packed [n, 3C] buffer, the
+    layout of an in-projection's gradient.  No atomics: the same bits from run to run."""
+    n, C = int(q.shape[0]), int(q.shape[1])
+    assert _kernel_rows_ok(dout) and _kernel_rows_ok(out) and lse.is_contiguous()
+    args = _segment_attention_args(q, k, v, ptr, H, scale)
+    packed = torch.empty((n, 3 * C), dtype=torch.float32, device=q.device)
+    dq, dk, dv = packed[:, :C], packed[:, C:2 * C], packed[:, 2 * C:]
+    delta = torch.empty((n, H), dtype=torch.float32, device=q.device)
+    _segment_attention_launch("wgamd_segment_attention_bwd_q_f32", args + (
+        dout.data_ptr(), dout.stride(0), out.data_ptr(), out.stride(0), lse.data_ptr(), int(H), dq.data_ptr(), dq.stride(0),
+        delta.data_ptr(), int(H)), n)
+    if not need_kv:
+        return dq, None, None
+    _segment_attention_launch("wgamd_segment_attention_bwd_kv_f32", args + (
+        dout.data_ptr(), dout.stride(0), lse.data_ptr(), int(H), delta.data_ptr(), int(H), dk.data_ptr(), dk.stride(0),
+        dv.data_ptr(), dv.stride(0)), n)
+    return dq, dk, dv
+
+
+def _segment_attention_torch(q, k, v, batch, G: int, H: int, scale: float, p: float = 0.0, training: bool = False):
+    """The same formula out of torch ops, in the inputs' dtype on any device, under ordinary autograd: every graph padded to the
+    longest (``batch`` [n] int64 in any order, ``G`` graphs), a masked softmax over [G, H, Nmax, Nmax] logits — what the kernels
+    never allocate.  ``p``: dropout on the attention weights, as ``torch.nn.MultiheadAttention`` applies it."""
+    n, C = q.shape
+    D = C // H
+    if n == 0 or G == 0:
+        return torch.zeros_like(q)
+    batch = batch.long()
+    sizes = torch.bincount(batch, minlength=G)
+    first = torch.cumsum(sizes, 0) - sizes
+    order = torch.argsort(batch, stable=True)
+    pos = torch.empty_like(batch)
+    pos[order] = torch.arange(n, device=batch.device) - first[batch[order]]
+    Nmax = int(sizes.max())
+
+    def dense(t):
+        return t.new_zeros((G, Nmax, H, D)).index_put((batch, pos), t.reshape(n, H, D))
+    s = torch.einsum("gihd,gjhd->ghij", dense(q), dense(k)) * scale
+    # (an empty graph keeps its first, all-zero key: no row of the padded batch is a softmax over nothing)
+    gone = torch.arange(Nmax, device=batch.device)[None, :] >= sizes.clamp(min=1)[:, None]
+    w = torch.softmax(s.masked_fill(gone[:, None, None, :], -math.inf), -1)
+    w = torch.nn.functional.dropout(w, p=p, training=training)
+    return torch.einsum("ghij,gjhd->gihd", w, dense(v))[batch, pos].reshape(n, C)
+
+
+def _batch_of_ptr(ptr, n: int):
+    G = int(ptr.shape[0]) - 1
+    return torch.repeat_interleave(torch.arange(G, device=ptr.device), ptr[1:] - ptr[:-1], output_size=n)
+
+
+class _SegmentAttention(torch.autograd.Function):
+    """``segment_attention`` on the kernel route under autograd.  Forward: ONE launch that keeps ``out`` and the per-head
+    log-sum-exp [n, H] — nothing per (row, row) pair.  Backward: two launches, ``bwd_q`` (delta, dq) and ``bwd_kv`` (dk, dv), every
+    probability recomputed; no atomics.  A backward under ``create_graph=True`` runs out of torch ops."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, ptr, H, scale):
+        out, lse = segment_attention_forward(q.detach(), k.detach(), v.detach(), ptr, H, scale, keep=True)
+        ctx.H, ctx.scale = H, scale
+        ctx.save_for_backward(q, k, v, ptr, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        q, k, v, ptr, out, lse = ctx.saved_tensors
+        if torch.is_grad_enabled():
+            n, G = int(q.shape[0]), int(ptr.shape[0]) - 1
+
+            def make_y():
+                return _segment_attention_torch(q, k, v, _batch_of_ptr(ptr, n), G, ctx.H, ctx.scale)
+            ins = [(i, t) for i, t in enumerate((q, k, v)) if ctx.needs_input_grad[i]]
+            return tuple(_grads_from_torch(make_y, ins, g, [None] * 6))
+        need = ctx.needs_input_grad
+        g, _ = _dz(g, None, False)
+        dq, dk, dv = segment_attention_backward(*_detached((q, k, v)), ptr, ctx.H, ctx.scale, g, out.detach(), lse,
+                                                need_kv=need[1] or need[2])
+        return (dq if need[0] else None, dk if need[1] else None, dv if need[2] else None, None, None, None)
+
+
+def _segment_attention(q, k, v, ptr, batch, G: int, H: int, scale, p: float = 0.0, training: bool = False):
+    """``(out, route)``: the kernels over ``ptr`` when they can run, the torch formulation over ``batch`` (None: made from
+    ``ptr``) otherwise."""
+    n, C = int(q.shape[0]), int(q.shape[1])
+    if q.dim() != 2 or k.shape != q.shape or v.shape != q.shape or H < 1 or C % H != 0:
+        raise ValueError("segment_attention: q, k, v must be [n, C] alike with C a multiple of heads=%d, got %s %s %s"
+                         % (H, tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    scale = 1.0 / math.sqrt(C // H) if scale is None else float(scale)
+    kernel = (ptr is not None and ptr.is_cuda and ptr.dtype == torch.int64 and all(_kernel_rows_ok(t) for t in (q, k, v))
+              and segment_attention_supported(H, C // H) and not (p > 0.0 and training))
+    if not kernel:
+        if batch is None:
+            batch = _batch_of_ptr(ptr.to(q.device).long(), n)
+        return _segment_attention_torch(q, k, v, batch, G, H, scale, p, training), "torch"
+    ptr = ptr.contiguous()
+    if _needs_grad((), q, k, v):
+        return _SegmentAttention.apply(q, k, v, ptr, H, scale), "kernel"
+    return segment_attention_forward(q.detach(), k.detach(), v.detach(), ptr, H, scale), "kernel"
+
+
+def segment_attention(q, k, v, ptr, heads: int, scale: Optional[float] = None):
+    """Multi-head self-attention inside each graph of a batch: ``q``, ``k``, ``v`` [n, C] with C = heads x D, ``ptr`` [G + 1]
+    (PyG's ``Batch.ptr``: ptr[0] = 0, non-decreasing, ptr[G] = n); per head h, with i and j rows of one graph,
+
+        out_i[h] = sum_j softmax_j((q_i[h] . k_j[h]) scale) v_j[h]           scale = 1 / sqrt(D) by default
+
+    ``segment_attention.route`` is what the last call took.  ``"kernel"``: float32 tensors on the device with unit column stride
+    and 16-B aligned rows — the three column blocks of a packed [n, 3C] in-projection as they are, no copies —, an int64
+    ``ptr`` on the device (trusted, never read back) and ``segment_attention_supported(heads, D)``: one launch forward
+    (``wgamd_segment_attention_f32``: 64 rows and one head per workgroup, both products on the fp32 matrix pipe), two backward;
+    only ``out`` and one log-sum-exp per (row, head) are kept, nothing of size n x n or G x longest graph exists, and no atomics
+    run: the same bits from call to call.  ``"torch"``: everything else — CPU tensors, float64, widths outside the domain,
+    misaligned rows — pads every graph to the longest and runs a masked softmax out of torch ops in the inputs' dtype; so does a
+    double backward of the kernel route."""
+    ptr = torch.as_tensor(ptr)
+    out, segment_attention.route = _segment_attention(q, k, v, ptr, None, int(ptr.shape[0]) - 1, int(heads), scale)
+    return out
+
+
+segment_attention.route = None
+
+
+class SegmentMultiheadAttention(torch.nn.Module):
+    """``torch.nn.MultiheadAttention(embed_dim, num_heads, batch_first=True)`` as self-attention over the graphs of a PyG batch,
+    without the padded batch: parameters, initialisation and state-dict keys are ``MultiheadAttention``'s (``in_proj_weight``
+    [3C, C], ``in_proj_bias``, ``out_proj.weight``, ``out_proj.bias``), so its state dict loads with ``strict=True``.
+
+    ``forward(x, batch=None, ptr=None, size=None, add=None)`` = ``out_proj(attention(in_proj(x))) + add`` [n, C]: ``ptr`` (PyG's
+    ``Batch.ptr``) vouches for a sorted batch; without it the offsets come from a sorted ``batch`` (one check, and one read-back
+    without ``size``, as ``global_add_pool``); an unsorted ``batch`` takes the torch route; neither: one graph.  The in-projection
+    is one library GEMM whose packed [n, 3C] result ``segment_attention`` reads in place; the out-projection is ``linear_rows``,
+    which carries ``add`` (GPSConv's residual) in its epilogue.  ``dropout`` acts on the attention weights in training mode and
+    then takes the torch route; in eval mode it is nothing and the kernels run.  ``route``: ``"kernel"`` or ``"torch"``, what the
+    attention of the last forward took."""
+
+    def __init__(self, embed_dim: int, num_heads: int, bias: bool = True, dropout: float = 0.0):
+        super().__init__()
+        if not isinstance(embed_dim, int) or not isinstance(num_heads, int) or embed_dim < 1 or num_heads < 1 \
+                or embed_dim % num_heads != 0:
+            raise ValueError("SegmentMultiheadAttention: embed_dim=%r must be a positive multiple of num_heads=%r"
+                             % (embed_dim, num_heads))
+        if not isinstance(dropout, (int, float)) or isinstance(dropout, bool) or not 0.0 <= dropout < 1.0:
+            raise ValueError("SegmentMultiheadAttention: dropout must be a number in [0, 1), got %r" % (dropout,))
+        self.embed_dim, self.num_heads, self.dropout, self.route = embed_dim, num_heads, float(dropout), None
+        self.in_proj_weight = torch.nn.Parameter(torch.empty((3 * embed_dim, embed_dim)))
+        if bias:
+            self.in_proj_bias = torch.nn.Parameter(torch.empty(3 * embed_dim))
+        else:
+            self.register_parameter("in_proj_bias", None)
+        self.out_proj = torch.nn.Linear(embed_dim, embed_dim, bias=bool(bias))
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        self.out_proj.reset_parameters()
+        torch.nn.init.xavier_uniform_(self.in_proj_weight)
+        if self.in_proj_bias is not None:
+            torch.nn.init.constant_(self.in_proj_bias, 0.0)
+            torch.nn.init.constant_(self.out_proj.bias, 0.0)
+
+    def forward(self, x, batch=None, ptr=None, size=None, add=None):
+        C = self.embed_dim
+        if x.dim() != 2 or x.shape[1] != C:
+            raise ValueError("SegmentMultiheadAttention: x must be [n, %d], got %s" % (C, tuple(x.shape)))
+        n = int(x.shape[0])
+        if batch is not None and (batch.dim() != 1 or batch.shape[0] != n):
+            raise ValueError("SegmentMultiheadAttention: batch must hold one graph index per row of x")
+        if ptr is not None:
+            G = int(ptr.shape[0]) - 1
+            ptr, batch = ptr.to(x.device).long(), None
+        elif batch is None:
+            G, ptr = 1, torch.tensor([0, n], dtype=torch.int64, device=x.device)
+        else:
+            batch = batch.to(x.device).long()
+            G = int(size) if size is not None else (int(batch.max()) + 1 if n > 0 else 0)
+            if n < 2 or bool((batch[1:] >= batch[:-1]).all()):
+                ptr = torch.searchsorted(batch.contiguous(), torch.arange(G + 1, device=x.device))
+        qkv = torch.nn.functional.linear(x, self.in_proj_weight, self.in_proj_bias)
+        o, self.route = _segment_attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], ptr, batch, G, self.num_heads, None,
+                                           self.dropout, self.training)
+        return _linear_rows(o, self.out_proj.weight, self.out_proj.bias, None, False, None, None, None, None, add, None)[0]
+
+    def extra_repr(self):
+        return "%d, heads=%d, dropout=%g" % (self.embed_dim, self.num_heads, self.dropout)
+
+
+class GPSConv(torch.nn.Module):
+    """PyG ``GPSConv`` (GraphGPS), by name, order and state dict: a local message-passing layer next to global attention inside
+    each graph, then a two-layer MLP, each with its residual and norm:
+
+        h1  = norm1(dropout(conv(x, graph, **kwargs)) + x)                        (skipped when ``conv`` is None)
+        h2  = norm2(dropout(attn(x over its graph)) + x)
+        out = h1 + h2;  out = norm3(out + mlp(out))
+        mlp = Sequential(Linear(C, 2C), ReLU(), Dropout(dropout), Linear(2C, C), Dropout(dropout))
+
+    ``conv``: any layer of this module called as ``conv(x, graph, **kwargs)`` over a whole-graph batch (``GINConv``,
+    ``GINEConv`` with ``edge_attr=``, ``PNAConv``, ...), or None.  ``attn`` is a ``SegmentMultiheadAttention(channels, heads,
+    **attn_kwargs)`` (``attn_kwargs``: ``bias``, ``dropout``) — the attention runs on the segment attention kernels, its residual
+    ``+ x`` in the out-projection's epilogue when no dropout separates them.  State-dict names: ``conv.*``, ``attn.in_proj_weight``,
+    ``attn.in_proj_bias``, ``attn.out_proj.*``, ``mlp.0.*``, ``mlp.3.*`` and, for ``norm="batch_norm"`` (``norm_kwargs``: ``eps``,
+    ``momentum``), ``norm{1,2,3}.module.*``; ``norm=None``: no norms.  Other norms, other activations and
+    ``attn_type="performer"`` are a ValueError.
+
+    ``forward(x, graph, batch=None, ptr=None, **kwargs)``: ``graph`` = a COO ``edge_index`` or a ``[csr_row_ptr, csr_col_ind]``
+    pair over all rows of ``x``; ``batch`` / ``ptr`` as ``SegmentMultiheadAttention.forward`` takes them.  ``route``: ``"kernel"``
+    or ``"torch"``, what the attention branch of the last forward took."""
+
+    def __init__(self, channels: int, conv, heads: int = 1, dropout: float = 0.0, act="relu", norm="batch_norm", norm_kwargs=None,
+                 attn_type: str = "multihead", attn_kwargs=None):
+        super().__init__()
+        if not isinstance(channels, int) or channels < 1:
+            raise ValueError("GPSConv: channels must be a positive int, got %r" % (channels,))
+        if conv is not None and not isinstance(conv, torch.nn.Module):
+            raise ValueError("GPSConv: conv must be a torch.nn.Module or None, got %s" % type(conv).__name__)
+        if attn_type != "multihead":
+            raise ValueError("GPSConv: attn_type=%r is not supported ('multihead')" % (attn_type,))
+        if norm not in ("batch_norm", None):
+            raise ValueError("GPSConv: norm=%r is not supported ('batch_norm' or None)" % (norm,))
+        if act != "relu":
+            raise ValueError("GPSConv: act=%r is not supported ('relu')" % (act,))
+        norm_kwargs, attn_kwargs = dict(norm_kwargs or {}), dict(attn_kwargs or {})
+        for name, given, known in (("norm_kwargs", norm_kwargs, {"eps", "momentum"}), ("attn_kwargs", attn_kwargs, {"bias", "dropout"})):
+            if set(given) - known:
+                raise ValueError("GPSConv: %s %s not supported (%s)" % (name, sorted(set(given) - known), sorted(known)))
+        if not isinstance(dropout, (int, float)) or isinstance(dropout, bool) or not 0.0 <= dropout <= 1.0:
+            raise ValueError("GPSConv: dropout must be a number in [0, 1], got %r" % (dropout,))
+        self.channels, self.conv, self.heads, self.dropout = channels, conv, int(heads), float(dropout)
+        self.attn = SegmentMultiheadAttention(channels, heads, **attn_kwargs)
+        self.mlp = torch.nn.Sequential(torch.nn.Linear(channels, 2 * channels), torch.nn.ReLU(), torch.nn.Dropout(dropout),
+                                       torch.nn.Linear(2 * channels, channels), torch.nn.Dropout(dropout))
+        for name in ("norm1", "norm2", "norm3"):
+            setattr(self, name, _MLPBatchNorm(channels, **norm_kwargs) if norm == "batch_norm" else None)
+
+    @property
+    def route(self):
+        return self.attn.route
+
+    def reset_parameters(self):
+        for m in [self.conv, self.attn] + list(self.mlp) + [self.norm1, self.norm2, self.norm3]:
+            if m is not None and hasattr(m, "reset_parameters"):
+                m.reset_parameters()
+
+    def forward(self, x, graph, batch=None, ptr=None, **kwargs):
+        if isinstance(graph, (LayerGraph, HeteroLayerGraph, dict)):
+            raise NotImplementedError("GPSConv runs over a batch of whole graphs (a COO edge_index or a [row_ptr, col] pair over "
+                                      "all rows of x), not over %s" % type(graph).__name__)
+        if not torch.is_tensor(x) or x.dim() != 2 or x.shape[1] != self.channels:
+            raise ValueError("GPSConv: x must be a [n, %d] tensor" % self.channels)
+        drop = self.dropout > 0.0 and self.training
+        hs = []
+        if self.conv is not None:
+            h = self.conv(x, graph, **kwargs)
+            h = torch.nn.functional.dropout(h, p=self.dropout, training=self.training) + x
+            hs.append(h if self.norm1 is None else self.norm1(h))
+        h = self.attn(x, batch=batch, ptr=ptr, add=None if drop else x)
+        if drop:
+            h = torch.nn.functional.dropout(h, p=self.dropout, training=True) + x
+        hs.append(h if self.norm2 is None else self.norm2(h))
+        out = hs[0] if len(hs) == 1 else hs[0] + hs[1]
+        out = out + self.mlp(out)
+        return out if self.norm3 is None else self.norm3(out)

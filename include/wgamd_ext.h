@@ -1518,6 +1518,36 @@ wholememory_error_code_t wgamd_hgt_bwd_src_f32(const int* row_ptr_t, const int* 
                                                const float* lse, int64_t ld_lse, const float* delta, int64_t ld_delta, float* dkv,
                                                int64_t ld_dkv, void* stream);
 
+/* ---- Segment attention (csrc/wg_segment_attention.hip): multi-head self-attention inside each graph of a batch ----------------------
+ * The global branch of torch_geometric.nn.GPSConv.  The n rows of q / k / v ([n, H D] float32, each with its own row stride: the
+ * three column blocks of a packed [n, 3 H D] in-projection are read in place) are cut into n_seg consecutive segments by ptr
+ * (int64 [n_seg + 1] on the device, non-decreasing, ptr[0] = 0, ptr[n_seg] = n: PyG's Batch.ptr); per head h
+ *   S_ij = (q_i[h] . k_j[h]) scale,  P = softmax over the rows j of i's segment,  out_i[h] = sum_j P_ij v_j[h].
+ * Grid ceil(n / 64) x H, one head and 64 rows per workgroup; both products on the exact fp32 matrix pipe
+ * (v_mfma_f32_16x16x4_f32) over 64-row tiles of the other side kept in LDS; a workgroup finds its segments by binary search in ptr
+ * (no tile table, nothing read back, nothing of size n x n or n_seg x longest segment).  lse_out [n, ld_lse] (H used, nullable):
+ * the natural log-sum-exp of row i's scaled logits, what the backward recomputes P from.  A row outside every segment gets zeros.
+ * wgamd_segment_attention_bwd_q_f32: from dout = dL / d out and the forward's out and lse, delta[i, h] = dout_ih . out_ih
+ * (written, [n, ld_delta]) and dq_i = scale sum_j dS_ij k_j, dS = P o (dout_i . v_j - delta_i).
+ * wgamd_segment_attention_bwd_kv_f32 (after bwd_q: reads delta): dk_j = scale sum_i dS_ij q_i, dv_j = sum_i P_ij dout_i.
+ * Every row of out / lse / delta / dq / dk / dv is written exactly once; no atomics: the same bits on every run.
+ * Domain: wgamd_segment_attention_supported(H, D): 1 <= H <= 8, D % 4 == 0, 4 <= D <= 64, H D <= 256; every [n, H D] operand
+ * with 16-B aligned rows; n < 2^31 - 128. */
+int wgamd_segment_attention_supported(int H, int D);
+wholememory_error_code_t wgamd_segment_attention_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
+                                                     int64_t ldv, const int64_t* ptr, int64_t n_seg, int64_t n, int H, int D, float scale,
+                                                     float* out, int64_t ldo, float* lse_out, int64_t ld_lse, void* stream);
+wholememory_error_code_t wgamd_segment_attention_bwd_q_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
+                                                           int64_t ldv, const int64_t* ptr, int64_t n_seg, int64_t n, int H, int D,
+                                                           float scale, const float* dout, int64_t ld_do, const float* out, int64_t ldo,
+                                                           const float* lse, int64_t ld_lse, float* dq, int64_t ld_dq, float* delta,
+                                                           int64_t ld_delta, void* stream);
+wholememory_error_code_t wgamd_segment_attention_bwd_kv_f32(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
+                                                            int64_t ldv, const int64_t* ptr, int64_t n_seg, int64_t n, int H, int D,
+                                                            float scale, const float* dout, int64_t ld_do, const float* lse,
+                                                            int64_t ld_lse, const float* delta, int64_t ld_delta, float* dk,
+                                                            int64_t ld_dk, float* dv, int64_t ld_dv, void* stream);
+
 /* ---- NormDropoutAct (csrc/wg_norm_act.hip): the row-wise block between two message-passing layers -------------------------------
  * What the reference's models put after a conv (mag_lp_mnmg.py: norm -> dropout -> relu, with the `+ lin1(x)` residual in the
  * encoder; gnn_model.py / rgcn / gin: relu -> dropout), over [n_rows, C] float32, for up to WGAMD_NORM_ACT_MAX_SEGMENTS node types
