@@ -69,6 +69,17 @@ class NormActSegment(Structure):
                 ("dweight", c_void_p), ("dbias", c_void_p)]
 
 
+GROUPED_LINEAR_MAX_SEGMENTS = 16   # WGAMD_GROUPED_LINEAR_MAX_SEGMENTS (include/wgamd_ext.h)
+
+
+class GroupedLinearSegment(Structure):
+    """wgamd_grouped_linear_segment (include/wgamd_ext.h)."""
+    _fields_ = [("x", c_void_p), ("ldx", c_int64), ("ids", c_void_p), ("n_rows", c_int64), ("K", c_int), ("N", c_int),
+                ("w", c_void_p), ("ld_n", c_int64), ("ld_k", c_int64), ("bias", c_void_p), ("add", c_void_p), ("ld_add", c_int64),
+                ("out", c_void_p), ("ldo", c_int64), ("out_rows", c_void_p), ("act_out", c_void_p), ("ld_act", c_int64),
+                ("grad_out", c_void_p), ("ldg", c_int64), ("dw", c_void_p), ("db", c_void_p)]
+
+
 class WholeGraphLibraryError(RuntimeError):
     pass
 
@@ -532,6 +543,12 @@ SYMBOLS = {
     "wgamd_row_linear_bwd_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_float,
                                          c_void_p, c_int64, c_void_p, c_void_p]),
     "wgamd_row_linear_affine_grad_f32": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    # Grouped Linear (wg_grouped_linear.hip)
+    "wgamd_grouped_linear_supported": (c_int, [c_int, c_int]),
+    "wgamd_grouped_linear_wgrad_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "wgamd_grouped_linear_f32": (c_int, [c_void_p, c_int, c_int, c_void_p]),
+    "wgamd_grouped_linear_wgrad_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
+    "wgamd_grouped_linear_wgrad_reduce_f32": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "wgamd_bias_act_rows_f32": (c_int, [c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "wgamd_gat_transform_heads_supported": (c_int, [c_int, c_int, c_int]),
     "wgamd_gat_transform_weight_bytes": (c_size_t, [c_int, c_int, c_int]),

@@ -9,11 +9,12 @@ the transformed rows (its logit is not linear in the neighbour row: no aggregate
 ``HeteroNormDropoutAct`` are what the reference's models put BETWEEN two layers (residual add, LayerNorm, dropout, ReLU): one
 launch forward and two backward for all node types of a layer.  ``RowLinear`` is the dense product AROUND the layers (input
 projection over the stored features, skip term, normalised tail, plain heads): gathered rows times a weight with a row-wise
-epilogue, one launch.
+epilogue, one launch.  ``HeteroDictLinear`` / ``HeteroLinear`` (``grouped_linear``) are those products for ALL node types of a
+heterogeneous model at once: up to 16 types per launch of a grouped GEMM kernel, forward and backward.
 
 Order of the file: ctypes helpers and the plumbing the one-kernel layers share; the SAGE-era kernel wrappers, derived-weight
 caches and GAT kernel wrappers; graph forms (``_single_hop``, ``LazyRows``, ``HopGraph``, ``LayerGraph``) and the helpers that
-walk a layer graph; then a section per layer — SAGE and GAT, GCN, RGCN, transformer, GIN, GATv2, GINE, GEN, heterogeneous, NormDropoutAct, RowLinear, segment attention and GPS —
+walk a layer graph; then a section per layer — SAGE and GAT, GCN, RGCN, transformer, GIN, GATv2, GINE, GEN, heterogeneous, NormDropoutAct, RowLinear, grouped Linear, segment attention and GPS —
 each with its kernel wrappers, its autograd Function(s) and its module.
 
 Shared by the one-kernel layers, so that they cannot drift apart: ``_hop_args`` (the eight leading arguments of a launch over a
@@ -8095,6 +8096,471 @@ class RowLinear(torch.nn.Module):
 
     def extra_repr(self):
         return "relu=%s, norm=%r, eps=%g" % (self.relu, self.norm_kind, self.eps)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Grouped Linear: one Linear per node type in one launch (PyG's HeteroLinear / HeteroDictLinear) — csrc/wg_grouped_linear.hip
+# ---------------------------------------------------------------------------------------------------------------------
+grouped_linear_launches = 0            # forward kernel launches of wgamd_grouped_linear_f32 so far (tests: ONE per 16 segments)
+grouped_linear_backward_launches = 0   # kernel launches of the backward so far: dX (the forward kernel), wgrad and reduce per 16 segments
+_GL_LAYOUTS = ("nk", "kn")             # weight [N, K] (torch.nn.Linear's) or [K, N] (PyG HeteroLinear's)
+
+
+def grouped_linear_supported(K: int, N: int) -> bool:
+    """Widths of the grouped Linear kernels (``wgamd_grouped_linear_supported``, answered on the host): K % 4 == 0, N % 4 == 0,
+    4 <= K, N <= 1024."""
+    return bool(L.lib().wgamd_grouped_linear_supported(int(K), int(N)))
+
+
+def _gl_row(t, first: int = 0):
+    """The address of row ``first`` of ``t`` (None: a null pointer)."""
+    return None if t is None else t.data_ptr() + int(first) * t.stride(0) * t.element_size()
+
+
+def _gl_desc(**fields):
+    """One ``wgamd_grouped_linear_segment`` as a dict of its fields (addresses as ints; what is not given is null / 0)."""
+    d = dict.fromkeys((name for name, _ in L.GroupedLinearSegment._fields_))
+    d.update(fields)
+    return d
+
+
+def _gl_weight(w, layout: str):
+    """``(K, N, ld_n, ld_k)`` of a 2-d weight in ``layout``."""
+    if layout == "nk":
+        return int(w.shape[1]), int(w.shape[0]), int(w.stride(0)), 1
+    return int(w.shape[0]), int(w.shape[1]), 1, int(w.stride(0))
+
+
+def _gl_chunks(descs):
+    """``descs`` 16 at a time, each chunk with its ``wgamd_grouped_linear_segment`` array (built once per chunk)."""
+    for a in range(0, len(descs), L.GROUPED_LINEAR_MAX_SEGMENTS):
+        chunk = descs[a:a + L.GROUPED_LINEAR_MAX_SEGMENTS]
+        arr = (L.GroupedLinearSegment * len(chunk))()
+        for c, d in zip(arr, chunk):
+            for field, ctype in L.GroupedLinearSegment._fields_:
+                setattr(c, field, d[field] if ctype is ctypes.c_void_p else int(d[field] or 0))
+        yield chunk, arr
+
+
+def _gl_products(descs, relu: bool) -> int:
+    """``wgamd_grouped_linear_f32`` over ``descs``, one call per 16; returns the number of kernel launches (a chunk whose
+    segments are all empty launches nothing)."""
+    launches = 0
+    for chunk, arr in _gl_chunks(descs):
+        L.check(L.lib().wgamd_grouped_linear_f32(arr, len(chunk), int(bool(relu)), get_stream()), "wgamd_grouped_linear_f32")
+        launches += any(d["n_rows"] for d in chunk)
+    return launches
+
+
+def grouped_linear_forward(descs, relu: bool = False):
+    """``wgamd_grouped_linear_f32`` (include/wgamd_ext.h) over segment descriptors (``_gl_desc``): ONE launch per 16."""
+    global grouped_linear_launches
+    grouped_linear_launches += _gl_products(descs, relu)
+
+
+def grouped_linear_backward(dx_descs, w_descs, device):
+    """The backward over descriptors of the dX products (run on the forward kernel with the weight's strides swapped) and of the
+    weight gradients: per 16 segments one dX launch, one ``wgamd_grouped_linear_wgrad_f32`` and one
+    ``wgamd_grouped_linear_wgrad_reduce_f32`` over a workspace of per-row-range partial blocks.  (The wgrad kernel has nothing to
+    do for a chunk of empty segments; the reduce still runs, and writes their zeros.)"""
+    global grouped_linear_backward_launches
+    grouped_linear_backward_launches += _gl_products(dx_descs, False)
+    lib = L.lib()
+    for chunk, arr in _gl_chunks(w_descs):
+        ws = torch.empty(max(int(lib.wgamd_grouped_linear_wgrad_workspace_bytes(arr, len(chunk))) // 4, 4), dtype=torch.float32,
+                         device=device)
+        L.check(lib.wgamd_grouped_linear_wgrad_f32(arr, len(chunk), ws.data_ptr(), get_stream()), "wgamd_grouped_linear_wgrad_f32")
+        L.check(lib.wgamd_grouped_linear_wgrad_reduce_f32(arr, len(chunk), ws.data_ptr(), get_stream()),
+                "wgamd_grouped_linear_wgrad_reduce_f32")
+        grouped_linear_backward_launches += any(d["n_rows"] for d in chunk) + 1
+
+
+def _gl_backward_descs(f, g, g_row0, act, dx, dx_row0, dx_rows, dw, dw_strides, db):
+    """From the forward descriptor ``f``, the upstream gradient ``g`` (rows placed as the output's, the segment's slice
+    beginning at row ``g_row0``) and the output ``act`` (None without ReLU): the descriptor of the dX product into ``dx`` (None:
+    not wanted) — x = dY read as the output was placed, written as the input was read — and of the weight gradient into
+    ``dw`` / ``db`` (``dw`` None: not wanted)."""
+    mask = dict(act_out=_gl_row(act, g_row0), ld_act=0 if act is None else act.stride(0))
+    dxd = wd = None
+    if dx is not None:
+        dxd = _gl_desc(x=_gl_row(g, g_row0), ldx=g.stride(0), ids=f["out_rows"], n_rows=f["n_rows"], K=f["N"], N=f["K"], w=f["w"],
+                       ld_n=f["ld_k"], ld_k=f["ld_n"], out=_gl_row(dx, dx_row0), ldo=dx.stride(0), out_rows=dx_rows, **mask)
+    if dw is not None:
+        wd = _gl_desc(x=f["x"], ldx=f["ldx"], ids=f["ids"], n_rows=f["n_rows"], K=f["K"], N=f["N"], ld_n=dw_strides[0],
+                      ld_k=dw_strides[1], out_rows=f["out_rows"], grad_out=_gl_row(g, g_row0), ldg=g.stride(0), dw=dw.data_ptr(),
+                      db=_ptr(db), **mask)
+    return dxd, wd
+
+
+def _gl_list_descs(xs, ids, ws, bs, adds, outs, layout):
+    """The forward descriptors of ``grouped_linear``'s segments."""
+    descs = []
+    for x, i, w, b, add, out in zip(xs, ids, ws, bs, adds, outs):
+        K, N, ld_n, ld_k = _gl_weight(w, layout)
+        descs.append(_gl_desc(x=x.data_ptr(), ldx=x.stride(0), ids=_ptr(i), n_rows=out.shape[0], K=K, N=N, w=w.data_ptr(), ld_n=ld_n,
+                              ld_k=ld_k, bias=_ptr(b), add=_ptr(add), ld_add=0 if add is None else add.stride(0), out=out.data_ptr(),
+                              ldo=out.stride(0)))
+    return descs
+
+
+def _grouped_linear_torch(xr, w, b, add, relu: bool, layout: str):
+    """One segment's formula out of torch ops under ordinary autograd, over the gathered rows ``xr``."""
+    y = xr @ (w.t() if layout == "nk" else w)
+    if b is not None:
+        y = y + b
+    if add is not None:
+        y = y + add
+    return y.relu() if relu else y
+
+
+class _GroupedLinear(torch.autograd.Function):
+    """``grouped_linear`` on the kernel route over n segments: ``tensors`` = the n inputs (a tensor, or the detached table of a
+    ``LazyRows``), then the n weights, biases and adds (None where absent); ``ids[k]``: what segment k's input is read through.
+    Keeps the inputs, the weights and — with ReLU only — the outputs.  The backward is ``grouped_linear_backward``: per 16
+    segments one dX launch, one wgrad launch and one reduce launch; a backward under ``create_graph=True`` runs the formula out
+    of torch ops instead."""
+
+    @staticmethod
+    def forward(ctx, conf, n, *tensors):
+        relu, layout, ids, x_grad = conf
+        xs, ws, bs, adds = (_detached(tensors[j * n:(j + 1) * n]) for j in range(4))
+        outs = [torch.empty(((x.shape[0] if i is None else i.shape[0]), w.shape[0 if layout == "nk" else 1]), dtype=torch.float32,
+                            device=x.device) for x, i, w in zip(xs, ids, ws)]
+        grouped_linear_forward(_gl_list_descs(xs, ids, ws, bs, adds, outs, layout), relu)
+        ctx.conf, ctx.n = conf, n
+        ctx.save_for_backward(*tensors, *(outs if relu else ()))
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        relu, layout, ids, x_grad = ctx.conf
+        n, saved = ctx.n, ctx.saved_tensors
+        tensors, outs = saved[:4 * n], (saved[4 * n:] if relu else (None,) * n)
+        if torch.is_grad_enabled():
+            return (None, None) + _grouped_linear_double_backward(ctx, tensors, grads)
+        xs, ws, bs, adds = (_detached(tensors[j * n:(j + 1) * n]) for j in range(4))
+        need, res = ctx.needs_input_grad[2:], [None] * (4 * n)
+        dx_descs, w_descs, scatter = [], [], []
+        for k in range(n):
+            if grads[k] is None:
+                continue
+            g = _grad_rows(grads[k])
+            f = _gl_list_descs(xs[k:k + 1], ids[k:k + 1], ws[k:k + 1], (None,), (None,), (g,), layout)[0]
+            dx = torch.empty((g.shape[0], f["K"]), dtype=torch.float32, device=g.device) if need[k] and x_grad[k] else None
+            dw = db = None
+            if need[n + k] or need[2 * n + k]:
+                dw = torch.empty(ws[k].shape, dtype=torch.float32, device=g.device)
+                db = torch.empty(f["N"], dtype=torch.float32, device=g.device) if need[2 * n + k] else None
+                res[n + k], res[2 * n + k] = (dw if need[n + k] else None), db
+            dxd, wd = _gl_backward_descs(f, g, 0, outs[k], dx, 0, None, dw, None if dw is None else _gl_weight(dw, layout)[2:], db)
+            dx_descs += [dxd] if dxd is not None else []
+            w_descs += [wd] if wd is not None else []
+            if dx is not None:
+                scatter.append((k, dx))
+            if need[3 * n + k]:
+                res[3 * n + k] = g * (outs[k] > 0) if relu else g
+        if dx_descs or w_descs:
+            grouped_linear_backward(dx_descs, w_descs, grads[0].device if grads[0] is not None else xs[0].device)
+        for k, dx in scatter:      # (a listed input: the compact dX scattered as linear_rows scatters it)
+            res[k] = dx if ids[k] is None else torch.zeros(xs[k].shape, dtype=torch.float32, device=dx.device).index_add_(0, ids[k], dx)
+        return (None, None) + tuple(res)
+
+
+def _grouped_linear_double_backward(ctx, tensors, grads):
+    """The gradients as differentiable torch expressions of the saved inputs and ``grads``."""
+    relu, layout, ids, x_grad = ctx.conf
+    n = ctx.n
+    res = [None] * (4 * n)
+    for k in range(n):
+        x, w, b, add = tensors[k::n]
+
+        def make_y():
+            return _grouped_linear_torch(x if ids[k] is None else x[ids[k]], w, b, add, relu, layout)
+        _grads_from_torch(make_y, ((k, x if x_grad[k] else None), (n + k, w), (2 * n + k, b), (3 * n + k, add)), grads[k], res)
+    return tuple(res)
+
+
+def grouped_linear(xs, weights, biases=None, *, rows=None, adds=None, relu=False, weight_layout="nk"):
+    """One Linear per segment — per node type — in one pass (PyG's ``HeteroDictLinear`` / ``pyg_lib.ops.grouped_matmul``):
+        out[k] = act( xs[k][rows[k]] @ W_k + biases[k] + adds[k] )        W_k = weights[k]^T ("nk": [N, K]) or weights[k] ("kn": [K, N])
+    ``xs``, ``weights`` and the optional ``biases``, ``rows``, ``adds``: lists of the same length, or dicts (``weights`` has at
+    least the keys of ``xs``; a missing key elsewhere = None); the result is a list or a dict likewise.  ``xs[k]``: a ``[m, K_k]``
+    tensor or ``LazyRows``; ``rows[k]``: an id tensor (repeats allowed), composed with a ``LazyRows``' id list by one index op.
+    Segments may differ in K and N and may be empty.
+
+    ``grouped_linear.route`` (what the last call took): the kernels (``wgamd_grouped_linear_f32``, include/wgamd_ext.h) run when
+    every segment is float32 on the device with unit column stride and 16-B aligned rows, ``grouped_linear_supported(K, N)``, and
+    a ``LazyRows`` table is a float32 ``torch.Tensor``: ONE launch per 16 segments forward, and per 16 segments backward one launch
+    for dX (the same kernel over the transposed weight, the ReLU mask applied while it stages dY), one for the weight-gradient
+    partials and one that adds them in a fixed order — no atomics, the same bits on every run.  The gradient of an input read
+    through ``rows`` is the compact dX scattered with ``index_add_`` (exact for distinct rows); a ``LazyRows`` table never gets
+    one (NotImplementedError when it asks).  Everything else — CPU tensors, other dtypes (a 16-bit ``LazyRows`` materialises),
+    widths outside the domain, misaligned rows, a ``MappedTable``-backed ``LazyRows`` — runs the same formula out of torch ops
+    under ordinary autograd, and so does a double backward.  The kernel route builds nothing on the host that a HIP-graph replay
+    would miss, so it may be captured."""
+    out, grouped_linear.route = _grouped_linear(xs, weights, biases, rows, adds, relu, weight_layout)
+    return out
+
+
+grouped_linear.route = None
+
+
+def _grouped_linear(xs, weights, biases, rows, adds, relu, layout, torch_ops=False):
+    """``(result, route)`` of ``grouped_linear``."""
+    if layout not in _GL_LAYOUTS:
+        raise ValueError("grouped_linear: weight_layout must be 'nk' or 'kn', got %r" % (layout,))
+    is_dict = isinstance(xs, dict)
+    keys = list(xs) if is_dict else list(range(len(xs)))
+    pick = (lambda d, t: None if d is None else d.get(t)) if is_dict else (lambda d, t: None if d is None else d[t])      # noqa: E731
+    if not is_dict and any(d is not None and len(d) != len(xs) for d in (weights, biases, rows, adds)):
+        raise ValueError("grouped_linear: xs, weights, biases, rows and adds must have the same length")
+    segs = []
+    for t in keys:
+        x, w, b, r, add = xs[t], weights[t], pick(biases, t), pick(rows, t), pick(adds, t)
+        lazy = isinstance(x, LazyRows)
+        if not lazy and not torch.is_tensor(x):
+            raise ValueError("grouped_linear: an input must be a tensor or LazyRows, got %s" % type(x).__name__)
+        K = w.shape[1 if layout == "nk" else 0] if w.dim() == 2 else -1
+        if x.dim() != 2 or w.dim() != 2 or x.shape[1] != K:
+            raise ValueError("grouped_linear: input %s of segment %r does not match weight %s (layout %r)"
+                             % (tuple(x.shape), t, tuple(w.shape), layout))
+        if r is not None and (r.dim() != 1 or r.dtype not in (torch.int32, torch.int64)):
+            raise ValueError("grouped_linear: rows must be 1-d int64 (or int32) tensors")
+        n, N = int(x.shape[0] if r is None else r.shape[0]), int(w.shape[0 if layout == "nk" else 1])
+        if b is not None and tuple(b.shape) != (N,):
+            raise ValueError("grouped_linear: bias of segment %r has shape %s, the weight has %d output columns" % (t, tuple(b.shape), N))
+        if add is not None and tuple(add.shape) != (n, N):
+            raise ValueError("grouped_linear: add of segment %r has shape %s, the result has (%d, %d)" % (t, tuple(add.shape), n, N))
+        if lazy:
+            _refuse_lazy_table_grad(x.table)
+        segs.append((x, w, b, r, add, lazy, int(K), N))
+
+    def wrap(outs):
+        return dict(zip(keys, outs)) if is_dict else list(outs)
+
+    def kernel_ok(x, w, b, r, add, lazy, K, N):
+        src = x.table if lazy else x
+        return (torch.is_tensor(src) and _kernel_rows_ok(src) and _kernel_rows_ok(w) and grouped_linear_supported(K, N)
+                and _norm_act_vec_ok(b, N) and (r is None or r.is_cuda) and (not lazy or x.ids.is_cuda)
+                and (add is None or _norm_act_rows_ok(add)))
+    if torch_ops or not segs or not all(kernel_ok(*s) for s in segs):
+        outs = []
+        for x, w, b, r, add, lazy, K, N in segs:
+            xr = x.materialize() if lazy else x
+            if r is not None:
+                if r.numel() and (int(r.min()) < 0 or int(r.max()) >= x.shape[0]):
+                    raise ValueError("grouped_linear: rows out of range for an input of %d rows" % x.shape[0])
+                xr = xr[r.long()]
+            outs.append(_grouped_linear_torch(xr, w, b, add, relu, layout))
+        return wrap(outs), "torch"
+    srcs, ids = [], []
+    for x, w, b, r, add, lazy, K, N in segs:
+        i = (x.ids if r is None else x.ids[r.long()]) if lazy else r
+        srcs.append(x.table.detach() if lazy else x)
+        ids.append(None if i is None else i.long().contiguous())
+    flat = srcs + [s[1] for s in segs] + [s[2] for s in segs] + [s[4] for s in segs]
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in flat):
+        outs = _GroupedLinear.apply((bool(relu), layout, ids, [not s[5] for s in segs]), len(segs), *flat)
+    else:
+        n = len(segs)
+        xs_d, ws_d, bs_d, adds_d = (_detached(flat[j * n:(j + 1) * n]) for j in range(4))
+        outs = [torch.empty(((x.shape[0] if i is None else i.shape[0]), s[7]), dtype=torch.float32, device=x.device)
+                for x, i, s in zip(xs_d, ids, segs)]
+        grouped_linear_forward(_gl_list_descs(xs_d, ids, ws_d, bs_d, adds_d, outs, layout), relu)
+    return wrap(outs), "kernel"
+
+
+class HeteroDictLinear(torch.nn.Module):
+    """PyG's ``HeteroDictLinear``: one Linear per node type, applied to a dict of inputs in ONE launch (``grouped_linear``).
+    ``in_channels``: an int with ``types`` (the node types), or ``{type: int}``.  The parameters are ``lins.{type}.weight``
+    ``[out_channels, in_channels[type]]`` and ``lins.{type}.bias`` — ``torch.nn.Linear``'s, under the keys of ``HGTConv``'s
+    ``kqv_lin`` / ``out_lin``, whose state dicts load.  ``forward(x_dict, *, rows_dict=None, add_dict=None, relu=False)`` returns
+    ``{type: [n, out_channels]}`` over the types of ``x_dict`` (a type the module does not know is a KeyError).  ``route``:
+    ``"kernel"`` or ``"torch"``, what the last forward took (see ``grouped_linear``); ``torch_ops = True`` forces ``"torch"``."""
+
+    def __init__(self, in_channels, out_channels: int, types=None, bias: bool = True):
+        super().__init__()
+        if isinstance(in_channels, dict) == (types is not None):
+            raise ValueError("HeteroDictLinear: in_channels is an int with `types`, or a dict {type: int} without")
+        if types is not None:
+            in_channels = {t: in_channels for t in types}
+        self.in_channels, self.out_channels = {t: int(k) for t, k in in_channels.items()}, int(out_channels)
+        self.lins = torch.nn.ModuleDict({t: torch.nn.Linear(k, self.out_channels, bias=bool(bias)) for t, k in self.in_channels.items()})
+        self.route, self.torch_ops = None, False
+
+    def reset_parameters(self):
+        for lin in self.lins.values():
+            lin.reset_parameters()
+
+    def forward(self, x_dict, *, rows_dict=None, add_dict=None, relu=False):
+        lins = {t: self.lins[t] for t in x_dict}
+        out, self.route = _grouped_linear(x_dict, {t: m.weight for t, m in lins.items()}, {t: m.bias for t, m in lins.items()},
+                                          rows_dict, add_dict, relu, "nk", self.torch_ops)
+        return out
+
+    def extra_repr(self):
+        return "%r, %d" % (self.in_channels, self.out_channels)
+
+
+class _HeteroLinear(torch.autograd.Function):
+    """``HeteroLinear`` on the kernel route: segment t is rows ``ptr[t] .. ptr[t + 1]`` of the type-sorted order — slices of
+    ``x`` and ``out`` themselves when ``perm`` is None (a sorted ``type_vec``), else read and written through ``perm``'s slices —
+    times ``weight[t]`` ([K, N]: layout "kn").  Keeps x, weight, bias and, with ReLU, the output; the backward places dX the way
+    the forward read x."""
+
+    @staticmethod
+    def descs(x, weight, bias, out, ptr, perm):
+        K, N = int(weight.shape[1]), int(weight.shape[2])
+        res = []
+        for t in range(weight.shape[0]):
+            a, n = ptr[t], ptr[t + 1] - ptr[t]
+            d = _gl_desc(n_rows=n, K=K, N=N, w=_gl_row(weight, t), ld_n=1, ld_k=weight.stride(1), bias=_gl_row(bias, t), ldx=x.stride(0),
+                         ldo=out.stride(0))
+            if perm is None:
+                d.update(x=_gl_row(x, a), out=_gl_row(out, a))
+            else:
+                d.update(x=x.data_ptr(), out=out.data_ptr(), ids=_gl_row(perm, a), out_rows=_gl_row(perm, a))
+            res.append(d)
+        return res
+
+    @staticmethod
+    def run(x, weight, bias, ptr, perm, relu):
+        out = torch.empty((x.shape[0], weight.shape[2]), dtype=torch.float32, device=x.device)
+        grouped_linear_forward(_HeteroLinear.descs(x, weight, bias, out, ptr, perm), relu)
+        return out
+
+    @staticmethod
+    def forward(ctx, conf, x, weight, bias):
+        relu, ptr, perm = conf
+        out = _HeteroLinear.run(x.detach(), weight.detach(), _detached(bias), ptr, perm, relu)
+        ctx.conf = conf
+        ctx.save_for_backward(x, weight, bias, *((out,) if relu else ()))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        relu, ptr, perm = ctx.conf
+        x, weight, bias = ctx.saved_tensors[:3]
+        act = ctx.saved_tensors[3] if relu else None
+        if torch.is_grad_enabled():
+            type_vec = torch.repeat_interleave(torch.arange(len(ptr) - 1, device=x.device),
+                                               torch.tensor([b - a for a, b in zip(ptr, ptr[1:])], device=x.device))
+            if perm is not None:
+                type_vec = torch.empty_like(type_vec).index_copy_(0, perm, type_vec)
+            res = _grads_from_torch(lambda: _hetero_linear_torch(x, type_vec, weight, bias, relu), ((1, x), (2, weight), (3, bias)), g,
+                                    [None] * 4)
+            return tuple(res)
+        need = ctx.needs_input_grad
+        g = _grad_rows(g)
+        xd, wd_ = x.detach(), weight.detach()
+        gx = torch.empty(x.shape, dtype=torch.float32, device=g.device) if need[1] else None
+        want_w = need[2] or (bias is not None and need[3])
+        gw = torch.empty(weight.shape, dtype=torch.float32, device=g.device) if want_w else None
+        gb = torch.empty(bias.shape, dtype=torch.float32, device=g.device) if bias is not None and need[3] else None
+        dx_descs, w_descs = [], []
+        for t, f in enumerate(_HeteroLinear.descs(xd, wd_, None, g, ptr, perm)):
+            row0 = ptr[t] if perm is None else 0
+            dxd, wd = _gl_backward_descs(f, g, row0, act, gx, row0, f["ids"], None, None, None)
+            if want_w:
+                wd = _gl_backward_descs(f, g, row0, act, None, 0, None, gw, (1, gw.stride(1)), None)[1]
+                wd.update(dw=_gl_row(gw, t), db=_gl_row(gb, t))
+                w_descs.append(wd)
+            dx_descs += [dxd] if dxd is not None else []
+        grouped_linear_backward(dx_descs, w_descs, g.device)
+        return None, gx, (gw if need[2] else None), gb
+
+
+def _hetero_linear_torch(x, type_vec, weight, bias, relu: bool):
+    """``HeteroLinear``'s formula out of torch ops under ordinary autograd: sort by type, one product per type, unsort."""
+    perm = torch.argsort(type_vec, stable=True)
+    counts = torch.bincount(type_vec, minlength=weight.shape[0]).tolist()
+    xs, at, parts = x[perm], 0, []
+    for t, c in enumerate(counts):
+        y = xs[at:at + c] @ weight[t]
+        parts.append(y if bias is None else y + bias[t])
+        at += c
+    y = torch.cat(parts, dim=0)
+    y = torch.zeros_like(y).index_copy(0, perm, y)
+    return y.relu() if relu else y
+
+
+class HeteroLinear(torch.nn.Module):
+    """PyG's ``HeteroLinear``: ``out[i] = x[i] @ weight[type_vec[i]] + bias[type_vec[i]]`` with ``weight`` ``[num_types,
+    in_channels, out_channels]`` and ``bias`` ``[num_types, out_channels]`` (PyG's parameters and state-dict keys), as ONE launch
+    per 16 types (``wgamd_grouped_linear_f32``): the segments are slices of ``x``, ``weight[t]`` and ``out`` — no copies.
+
+    ``forward(x, type_vec, *, ptr=None, relu=False)``: ``ptr`` (``[num_types + 1]`` row offsets, a list or a host tensor) vouches
+    that ``type_vec`` is sorted and saves the read-back of the type counts; without it ``is_sorted=True`` takes the offsets from
+    ``searchsorted``, and an unsorted ``type_vec`` costs one stable ``argsort``: the kernel then reads ``x`` and writes ``out``
+    through the permutation's slices (no permuted copy of either exists), and the backward places dX the same way — exact and
+    deterministic, since a permutation names every row once.  ``route``: ``"kernel"`` or ``"torch"``, what the last forward took —
+    the kernels for float32 device tensors with 16-B aligned rows and ``grouped_linear_supported(in_channels, out_channels)``,
+    torch ops otherwise, in a double backward and with ``torch_ops = True``.  Under HIP-graph capture the kernel route needs
+    ``ptr`` on the host (the type counts of a replay would otherwise be those of the capture): RuntimeError without."""
+
+    def __init__(self, in_channels: int, out_channels: int, num_types: int, is_sorted: bool = False, bias: bool = True):
+        super().__init__()
+        self.in_channels, self.out_channels, self.num_types = int(in_channels), int(out_channels), int(num_types)
+        self.is_sorted = bool(is_sorted)
+        self.weight = torch.nn.Parameter(torch.empty(self.num_types, self.in_channels, self.out_channels))
+        self.bias = torch.nn.Parameter(torch.empty(self.num_types, self.out_channels)) if bias else None
+        self.route, self.torch_ops = None, False
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        bound = 1.0 / math.sqrt(self.in_channels)      # (torch.nn.Linear's: kaiming_uniform(a = sqrt 5) per type)
+        torch.nn.init.uniform_(self.weight, -bound, bound)
+        if self.bias is not None:
+            torch.nn.init.uniform_(self.bias, -bound, bound)
+
+    def forward(self, x, type_vec, *, ptr=None, relu=False):
+        T, n = self.num_types, int(x.shape[0])
+        if x.dim() != 2 or x.shape[1] != self.in_channels:
+            raise ValueError("HeteroLinear: x %s does not match in_channels = %d" % (tuple(x.shape), self.in_channels))
+        if type_vec.dim() != 1 or type_vec.shape[0] != n:
+            raise ValueError("HeteroLinear: type_vec %s does not match the %d rows of x" % (tuple(type_vec.shape), n))
+        host_ptr = ptr is not None and not (torch.is_tensor(ptr) and ptr.is_cuda)
+        if ptr is not None:
+            if len(ptr) != T + 1:
+                raise ValueError("HeteroLinear: ptr has %d entries, num_types + 1 = %d are needed" % (len(ptr), T + 1))
+            if not host_ptr:
+                _refuse_capture(self, "type offsets read back from a device `ptr`")
+            ptr = [int(p) for p in (ptr.tolist() if torch.is_tensor(ptr) else ptr)]
+            if ptr[0] != 0 or ptr[-1] != n or any(b < a for a, b in zip(ptr, ptr[1:])):
+                raise ValueError("HeteroLinear: ptr must rise from 0 to the %d rows of x" % n)
+        w, b = self.weight, self.bias      # (every type's slice is read in place: [K, N] rows, a [N] vector)
+        kernel = (not self.torch_ops and _kernel_rows_ok(x) and type_vec.is_cuda and w.is_cuda
+                  and grouped_linear_supported(self.in_channels, self.out_channels)
+                  and (T == 0 or (_kernel_rows_ok(w[0]) and w.stride(0) % 4 == 0))
+                  and (T == 0 or b is None or (_norm_act_vec_ok(b[0], self.out_channels) and b.stride(0) % 4 == 0)))
+        if not kernel:
+            if n and (int(type_vec.min()) < 0 or int(type_vec.max()) >= T):
+                raise ValueError("HeteroLinear: type_vec holds a type outside 0 .. %d" % (T - 1))
+            self.route = "torch"
+            return _hetero_linear_torch(x, type_vec.long(), self.weight, self.bias, relu)
+        perm = None
+        if ptr is None:
+            _refuse_capture(self, "type counts read back from `type_vec` (pass `ptr`)")
+            tv = type_vec.long()
+            if self.is_sorted:
+                ptr = torch.searchsorted(tv, torch.arange(T + 1, device=tv.device)).tolist()
+            else:
+                perm = torch.argsort(tv, stable=True)
+                counts = torch.bincount(tv.clamp(min=-1) + 1, minlength=T + 2).tolist()      # (slot 0: negative types)
+                ptr = [0] + counts[1:T + 1]
+                for t in range(T):                # (a type outside 0 .. T - 1 is missing from the sum: ptr[T] < n)
+                    ptr[t + 1] += ptr[t]
+            if ptr[0] != 0 or ptr[-1] != n:
+                raise ValueError("HeteroLinear: type_vec holds a type outside 0 .. %d" % (T - 1))
+        self.route = "kernel"
+        conf = (bool(relu), ptr, perm)
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, self.weight, self.bias)):
+            return _HeteroLinear.apply(conf, x, self.weight, self.bias)
+        return _HeteroLinear.run(x.detach(), self.weight.detach(), _detached(self.bias), ptr, perm, relu)
+
+    def extra_repr(self):
+        return "%d, %d, num_types=%d, is_sorted=%s" % (self.in_channels, self.out_channels, self.num_types, self.is_sorted)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

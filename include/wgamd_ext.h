@@ -1646,6 +1646,60 @@ wholememory_error_code_t wgamd_row_linear_bwd_f32(const float* kept_y, int64_t l
 wholememory_error_code_t wgamd_row_linear_affine_grad_f32(const float* partials, int64_t n_rows, int N, float* dgamma,
                                                           float* dbeta, void* stream);
 
+/* ---- Grouped Linear (csrc/wg_grouped_linear.hip): one Linear per node type, up to 16 of them in ONE launch -----------------------
+ * What to_hetero makes of the dense products around the reference's layers (mag_lp_mnmg.py: lin1, paper_lin, lin2 per node type)
+ * and what HGTConv's per-type projections are: PyG's HeteroLinear / HeteroDictLinear (pyg_lib.segment_matmul / grouped_matmul).
+ * Segment s of wgamd_grouped_linear_f32 computes, for i < n_rows:
+ *   out[place(i), n] = act( sum_k X[list(i), k] W(n, k) + bias[n] + add[i, n] )
+ *   list(i) = ids ? ids[i] : i,  place(i) = out_rows ? out_rows[i] : i,  W(n, k) = w[n ld_n + k ld_k],  act = ReLU when relu != 0
+ * One of (ld_n, ld_k) is 1 and the other at least the width it steps over: (K.., 1) is torch.nn.Linear's [N, K] weight, (1, N..)
+ * HeteroLinear's [K, N]; swapping the two (and K with N) multiplies by the transposed weight: the dX product of the backward.
+ * bias, add, ids, out_rows, act_out are nullable.  With act_out ([*, ld_act], indexed as x is: row list(i)) the value of X at
+ * (row, column) counts as 0 where act_out there is not > 0: the backward passes x = dY and act_out = the forward's output.
+ * Segments may differ in K and N; n_rows = 0 is allowed.  ids and out_rows are not range-checked.
+ * wgamd_grouped_linear_wgrad_f32 (same segments, fields of the second group): per (segment, 64 x 64 weight block, row range)
+ * the partial sum over the range's rows of X[list(i), k] dY[place(i), n] -> workspace, dY = grad_out masked by act_out (here
+ * indexed as grad_out is: row place(i)); wgamd_grouped_linear_wgrad_reduce_f32 adds the partials in range order and writes
+ * dw[n ld_n + k ld_k] and db[n] = the column sums of the masked dY (zeros for an empty segment).  A segment with dw == NULL is
+ * skipped by both (db needs dw).  The ranges are a function of (n_rows, K, N) only and nothing is atomic: the same bits on every
+ * run.  workspace: wgamd_grouped_linear_wgrad_workspace_bytes(segs, n_segs) bytes, 16-B aligned, the same for both launches.
+ * Domain: wgamd_grouped_linear_supported(K, N) (K % 4 == 0, N % 4 == 0, 4 <= K, N <= 1024); 1 <= n_segs <= 16; float32 rows
+ * 16-B aligned with leading dimensions multiples of 4 and at least the width, weights 16-B aligned with the non-unit stride a
+ * multiple of 4 (WHOLEMEMORY_LOGIC_ERROR otherwise; null pointers, counts, strides: WHOLEMEMORY_INVALID_INPUT).  All checks come
+ * before any device call; a launch without rows is success without a launch. */
+#define WGAMD_GROUPED_LINEAR_MAX_SEGMENTS 16
+typedef struct {
+  const float* x;
+  int64_t ldx;
+  const int64_t* ids;
+  int64_t n_rows;
+  int K;
+  int N;
+  const float* w;
+  int64_t ld_n;
+  int64_t ld_k;
+  const float* bias;
+  const float* add;
+  int64_t ld_add;
+  float* out;
+  int64_t ldo;
+  const int64_t* out_rows;
+  const float* act_out;
+  int64_t ld_act;
+  /* the weight-gradient launches' (null / 0 in the forward) */
+  const float* grad_out;
+  int64_t ldg;
+  float* dw;
+  float* db;
+} wgamd_grouped_linear_segment;
+int wgamd_grouped_linear_supported(int K, int N);
+size_t wgamd_grouped_linear_wgrad_workspace_bytes(const wgamd_grouped_linear_segment* segs, int n_segs);
+wholememory_error_code_t wgamd_grouped_linear_f32(const wgamd_grouped_linear_segment* segs, int n_segs, int relu, void* stream);
+wholememory_error_code_t wgamd_grouped_linear_wgrad_f32(const wgamd_grouped_linear_segment* segs, int n_segs, float* workspace,
+                                                        void* stream);
+wholememory_error_code_t wgamd_grouped_linear_wgrad_reduce_f32(const wgamd_grouped_linear_segment* segs, int n_segs,
+                                                               const float* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
